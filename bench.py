@@ -12,9 +12,15 @@ Thetas change every step (bank of K+W parameter sets resident in HBM), so nothin
 served from a cache.  Default workload = BASELINE.json's headline: 16 qubits, 40 blocks
 (cx, spin layout, T = 208), state-vector path.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload NAME]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload NAME] [--full] [--dump-outputs DIR]
 For N > 1 launch with torch.distributed.run (one rank per GPU); ranks process their own
 lanes (weak scaling) and only the final result records are gathered (RCCL).
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds
+everything the headline figure does not need: the check of the last timed step against the
+C oracle, per-kernel profile and roofline, sustained rate, batch-1 latency, objective-object
+rates, the CPU baseline and (default workload) short runs of every other configuration.
+--dump-outputs DIR writes what the timed path delivered in its last step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -31,6 +37,7 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_PEAK_TFLOPS = 78.6  # fp64 vector peak = fp64 matrix (MFMA) peak on gfx950
 PARITY_TOL = 1e-10       # north-star tolerance (complex fp64, absolute)
+DUMP_LIMIT = 64 << 20    # bytes of --dump-outputs in all
 
 WORKLOADS = {
     # name: (n, layout, L, kind)
@@ -238,6 +245,26 @@ def reference_numpy_record(workload):
                         "tools/ref_baseline.py; NOT on this GPU box"}
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one ``path/<name>.npy`` per array, float64; a complex array becomes (..., 2) real / imaginary pairs.
+    Above DUMP_LIMIT bytes in all, a fixed seeded sample of the leading axis (the lanes) of every array that has it is
+    written, and the sampled indices go to ``lanes.npy``."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: (np.stack([v.real, v.imag], axis=-1) if np.iscomplexobj(v) else v).astype(np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        rows = max(v.shape[0] for v in arrays.values() if v.ndim)
+        per_lane = sum(v.nbytes // rows for v in arrays.values() if v.ndim and v.shape[0] == rows) + 8   # (+ its index)
+        rest = sum(v.nbytes for v in arrays.values() if not (v.ndim and v.shape[0] == rows))
+        keep = max(1, (DUMP_LIMIT - rest) // per_lane)
+        lanes = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {k: v[lanes] if v.ndim and v.shape[0] == rows else v for k, v in arrays.items()}
+        arrays["lanes"] = lanes.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
+
+
 # ---- config 4: the ASP job mix ---------------------------------------------------------------------------------------
 # What a horizon's jobs share stays resident between them (time_evol_best_init.py:337-382 builds everything per job): the
 # ansatz context and its plans (HipContext cache), ONE batched objective per (horizon, lanes) whose lanes are the seeds of a
@@ -312,8 +339,9 @@ def _mix_release():
         _MIX[kind].clear()
 
 
-def run_job_mix(args, w, comm, rank, local_rank, n_gpus, comm_note, steps=None):
-    """--workload cfg4_jobs: the whole mix through run_jobs (rank-sharded, fixed-size record gather)."""
+def run_job_mix(args, w, comm, rank, local_rank, n_gpus, comm_note, steps=None, outputs=None):
+    """--workload cfg4_jobs: the whole mix through run_jobs (rank-sharded, fixed-size record gather); the records' cost,
+    fidelity and thetas go to ``outputs`` if given."""
     from aqc_research_amd.job_executor import run_jobs
 
     # one entry = (horizon, a chunk of the 64 seeds); entry index = horizon * chunks + chunk and run_jobs puts entry j on
@@ -338,6 +366,9 @@ def run_job_mix(args, w, comm, rank, local_rank, n_gpus, comm_note, steps=None):
     if comm.size > 1:
         wall = float(comm.allreduce(np.array([wall]), "max")[0])
     _mix_release()
+    if outputs is not None:
+        outputs.update(cost=[r.get("cost", np.nan) for r in results], fidelity=[r.get("fidelity", np.nan) for r in results],
+                       thetas=np.concatenate([np.asarray(r.get("thetas", ()), np.float64) for r in results]))
     ok = [r for r in results if r["status"].startswith("ok")]
     njobs = w["seeds"] * w["horizons"]
     evals = njobs * w["evals"]
@@ -357,7 +388,7 @@ def run_job_mix(args, w, comm, rank, local_rank, n_gpus, comm_note, steps=None):
 
 def run_driver(args, w, env, full):
     """--workload cfg4_driver: the horizon driver itself (model_sp_lhs/time_evol.run_simulation), horizons sharded by run_jobs.
-    Short form (configs of the default line): 2 horizons.  After the run one restart is replayed against the C oracle: the
+    Short form (configs of the --full line): 2 horizons.  With --full one restart is replayed against the C oracle: the
     objective's amplitude and gradient at the optimised thetas of horizon 1, recomputed on the device AND by the oracle."""
     from aqc_research_amd.engine import BUF_X, BUF_Y, HipContext, Workspace
     from aqc_research_amd.model_sp_lhs import time_evol
@@ -380,9 +411,11 @@ def run_driver(args, w, env, full):
     if comm.size > 1:
         wall = float(comm.allreduce(np.array([wall]), "max")[0])
     evals = int(sum(r["num_fun_ev"] for r in recs))
-    # parity replay of one restart (rank 0): horizon 1, the best restart's thetas
-    parity = None
-    if rank == 0:
+    by_h = sorted(recs, key=lambda r: r["horizon"])
+    env.outputs = {"fidelity": [float(r["fidelity"]) for r in by_h], "thetas": np.concatenate([np.asarray(r["thetas"], np.float64) for r in by_h])}
+    # parity replay of one restart (rank 0, --full): horizon 1, the best restart's thetas
+    parity, fid_gap = None, None
+    if rank == 0 and args.full:
         r1 = min(recs, key=lambda r: r["horizon"])
         circ = trotter_ansatz(w["n"], int(r1["num_layers"]), True)
         tgt = time_evol.generate_target(opts, int(r1["horizon"]) - 1).t1_gt
@@ -403,7 +436,7 @@ def run_driver(args, w, env, full):
     return {
         "metric": "objective+gradient evals/sec", "value": evals / wall, "unit": "evals/s", "n_gpus": n_gpus, "steps": 1, "warmup": 1,
         "ms_per_step": wall * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "parity_maxerr": parity, "parity_lanes_checked": 1, "record_fidelity_vs_oracle": fid_gap if rank == 0 else None,
+        "parity_maxerr": parity, "parity_lanes_checked": 0 if parity is None else 1, "record_fidelity_vs_oracle": fid_gap,
         "parity_note": "horizon 1, best restart: amplitude <ini|V^H|t1_gt>, complex gradient and the record's fidelity at the optimised "
                        "thetas, device vs C oracle (target = the driver's own ground-truth state)",
         "config": {"workload": w["desc"], "n_qubits": w["n"], "horizons": H, "restarts_per_horizon": w["seeds"], "lbfgs": mode if w["seeds"] > 1 else "scipy L-BFGS-B under AqcOptimizer (one objective object per horizon)",
@@ -447,15 +480,17 @@ def run_cd(args, w, env, full):
     def sweep(th):
         L.check(lib.aqc_ws_cd_sweeps(ws.handle, L.dptr(th), L.dptr(fobj), 1, -1))
 
-    # the work is checked, not assumed: the first sweep of 8 lanes against the C restatement of the reference algorithm
+    # the work is checked, not assumed (--full): the first sweep of 8 lanes against the C restatement of the reference algorithm
     # (whole sweeps: ~T sequential Newton steps amplify rounding, hence 1e-8; single steps are pinned at 1e-10 in tests/)
     th = th0.copy()
     sweep(th)
-    lanes = sorted(set(int(round(v)) for v in np.linspace(0, B - 1, min(B, 8))))
-    t_ref, f_ref = cref.coord_descent_sweeps(circ, th0[lanes], targets[lanes], 1, threads=host_cores())
-    parity = max(float(np.abs(th[lanes] - t_ref).max()), float(np.abs(fobj[lanes, 0] - f_ref[:, 0]).max()))
-    if not parity < 1e-8:
-        raise SystemExit(f"bench.py: cd sweep deviates from the oracle by {parity:g} (> 1e-8)")
+    lanes, parity = [], None
+    if args.full:
+        lanes = sorted(set(int(round(v)) for v in np.linspace(0, B - 1, min(B, 8))))
+        t_ref, f_ref = cref.coord_descent_sweeps(circ, th0[lanes], targets[lanes], 1, threads=host_cores())
+        parity = max(float(np.abs(th[lanes] - t_ref).max()), float(np.abs(fobj[lanes, 0] - f_ref[:, 0]).max()))
+        if not parity < 1e-8:
+            raise SystemExit(f"bench.py: cd sweep deviates from the oracle by {parity:g} (> 1e-8)")
     f_first = float(fobj[:, 0].mean())
     for _ in range(W):
         sweep(th)
@@ -470,17 +505,20 @@ def run_cd(args, w, env, full):
     if env.comm.size > 1:
         wall = float(env.comm.allreduce(np.array([wall]), "max")[0])
     f_last = float(fobj[:, 0].mean())
-    ws.profile(True)
-    for _ in range(3):
-        sweep(th)
-    from aqc_research_amd.engine import K_MISC
+    env.outputs = {"thetas": th.copy(), "objective": fobj[:, 0].copy()}
+    launches, kern_ms = 0, 0.0
+    if args.full:
+        ws.profile(True)
+        for _ in range(3):
+            sweep(th)
+        from aqc_research_amd.engine import K_MISC
 
-    launches, kern_ms = ws.profile_get(K_MISC)
-    ws.profile(False)
+        launches, kern_ms = ws.profile_get(K_MISC)
+        ws.profile(False)
     ws.close()
-    # one lane: the persistent launch and the launch chain it replaced (2 launches per parameter + 1 per block)
+    # one lane (--full): the persistent launch and the launch chain it replaced (2 launches per parameter + 1 per block)
     one, chain = None, None
-    if env.rank == 0:
+    if env.rank == 0 and args.full:
         th1 = th0[0].copy()
         coord_descent_single_sweep(circ, th1, targets[0], None)
         t1 = time.perf_counter()
@@ -498,13 +536,13 @@ def run_cd(args, w, env, full):
     if env.rank != 0:
         return None
     value = K * B * env.n_gpus / wall
-    avg_launch_ms = kern_ms / max(launches, 1)
+    avg_launch_ms = kern_ms / max(launches, 1) if launches else None
     # bytes the reference's algorithm moves per sweep and lane: per parameter one pass over w, z for the two inner products and
     # one read-modify-write pass for the two rotations, per block the entangler on both, plus the T gate passes of V^H on z
     N = d * d
     alg_bytes = 16.0 * N * (6 * T + 4 * circ.num_blocks + 2 * T)
     lds_peak = 256 * 128 * 2.4e9 / 1e9      # GB/s: 128 B per clock and CU
-    achieved = alg_bytes * B / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
+    achieved = alg_bytes * B / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms else 0.0
     out = {
         "metric": "coordinate-descent sweeps/sec", "value": value, "unit": "sweeps/s", "n_gpus": env.n_gpus, "steps": K, "warmup": W,
         "ms_per_step": wall / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -519,14 +557,14 @@ def run_cd(args, w, env, full):
                              "served from LDS: one workgroup per lane holds both operands for the whole walk; HBM sees the target once per sweep. "
                              "The walk is a chain of T dependent steps (two barriers and one fixed-order reduction each): latency-bound, not "
                              "bandwidth-bound",
-                     "hbm_equivalent_frac_of_8TBps": achieved / HBM_PEAK_GBS},
+                     "hbm_equivalent_frac_of_8TBps": achieved / HBM_PEAK_GBS} if launches else None,
         "parity_maxerr": parity, "parity_lanes_checked": len(lanes), "parity_tolerance": 1e-8,
         "single_lane": {"ms_per_sweep_one_launch": None if one is None else one * 1e3, "ms_per_sweep_launch_chain": None if chain is None else chain * 1e3,
                         "speedup_one_lane": None if not one else chain / one,
                         "speedup_all_lanes_vs_chain": None if not chain else value / env.n_gpus * chain},
         "device_ms_per_step_events": ev_ms / K,
     }
-    if full and not args.no_cpu_baseline:
+    if full and args.full and not args.no_cpu_baseline:
         cores = host_cores()
         nb = max(cores, 16)
         t1 = time.perf_counter()
@@ -599,6 +637,7 @@ def run_mps_engine(args, w, env, full):
         h, g = me.evaluate_lanes(circ, thetas(10 + i), targets, basis, trunc_thr=thr, method="lockstep")
     env.comm.barrier()
     wall = time.perf_counter() - t0
+    env.outputs = {"amplitudes": h, "gradients": g}
     if env.comm.size > 1:
         wall = float(env.comm.allreduce(np.array([wall]), "max")[0])
     # roofline of the dominant kernel (lanes_gate2_kernel: a truncated 2-qubit gate = one-sided Jacobi SVD per lane in LDS): fp64 flops of
@@ -736,6 +775,7 @@ def run_mps_opt(args, w, env, full):
         evals += obj.num_evals - before
         fid = obj.fidelity.copy()
     env.comm.barrier()
+    env.outputs = {"thetas": res["x"], "fidelity": fid}
     wall = time.perf_counter() - t0
     if env.comm.size > 1:
         wall = float(env.comm.allreduce(np.array([wall]), "max")[0])
@@ -1027,6 +1067,10 @@ def main():
     ap.add_argument("--no-objective-object", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="default workload only: skip the short runs of the other BASELINE configurations")
     ap.add_argument("--config-steps", type=int, default=10, help="timed steps of each short configuration run")
+    ap.add_argument("--full", action="store_true", help="also check the last timed step against the C oracle and run what the headline "
+                    "figure does not need: kernel profile and roofline, sustained rate, latency, objective objects, CPU baseline, "
+                    "and (default workload) the short runs of the other BASELINE configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path delivered in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1094,12 +1138,14 @@ def main():
     import types
 
     env = types.SimpleNamespace(comm=comm, comm_note=comm_note, rank=rank, world=world, local_rank=local_rank, n_gpus=n_gpus,
-                                ranks_seen=ranks_seen)
+                                ranks_seen=ranks_seen, outputs=None)
     t_start = time.perf_counter()
     out = measure(args.workload, args, env, full=True)
-    # ---- every other BASELINE configuration in the SAME driver-run line: a few timed steps each, parity-checked against the
+    if args.dump_outputs and rank == 0:   # (rank 0's lanes)
+        dump_outputs(args.dump_outputs, env.outputs)
+    # ---- with --full, every other BASELINE configuration in the SAME line: a few timed steps each, parity-checked against the
     # C oracle like the headline (single GPU, default workload only; --no-configs skips them) ---------------------------------
-    if args.workload == "sv16_l40" and world == 1 and not args.no_configs:
+    if args.full and args.workload == "sv16_l40" and world == 1 and not args.no_configs:
         configs = {}
         for name in CONFIG_RUNS:
             t_cfg = time.perf_counter()
@@ -1124,14 +1170,14 @@ def main():
     comm.close()
 
 
-# the short configuration runs of the default invocation, in BASELINE.json's order (cfg 1, 2 first / last horizon, 3 through the
+# the short configuration runs of the --full line, in BASELINE.json's order (cfg 1, 2 first / last horizon, 3 through the
 # MPS front door at the no-truncation and at the reference's default threshold, 4 sizes + job mix, 5)
 CONFIG_RUNS = ["mat5_cyc180", "cd5_cyc180", "mat10_l40_k16", "sv12_trotter2", "sv12_trotter12", "mps16_l40_chi64", "mps16_l40_chi64_thr1e-6", "sv20_l40",
                "cfg2_driver", "sv20_trotter2", "cfg4_jobs", "cfg4_driver", "mat10_l40", "mps32_trotter2_engine", "mps32_trotter2_opt"]
 
 
 def brief(o):
-    """What a configs entry of the default line carries (the full record of a workload: --workload NAME)."""
+    """What a configs entry of the --full line carries (the whole record of a workload: --workload NAME --full)."""
     if o is None:
         return {"error": "no result"}
     r = o.get("roofline") or {}
@@ -1151,9 +1197,10 @@ def brief(o):
 
 
 def measure(workload, args, env, full):
-    """One workload: set-up, warm-up, K timed steps between barriers, parity check of the last timed step, kernel profile.
-    ``full`` adds the sustained loop, single-evaluation latency, objective objects and the CPU baseline (the headline run);
-    the short configuration runs of the default line leave them out and use --config-steps steps."""
+    """One workload: set-up, warm-up, K timed steps between barriers; --full adds the parity check of the last timed step and
+    the kernel profile.  ``full`` (the headline run) with --full adds the sustained loop, single-evaluation latency, objective
+    objects and the CPU baseline; the short configuration runs of the --full line leave them out and use --config-steps steps.
+    What the last timed step delivered is left in ``env.outputs`` (--dump-outputs)."""
     comm, comm_note, rank, world, local_rank, n_gpus, ranks_seen = (env.comm, env.comm_note, env.rank, env.world, env.local_rank,
                                                                      env.n_gpus, env.ranks_seen)
     from aqc_research_amd._lib import K_APPLY_LIST, K_APPLY_VIRTUAL, K_PROJECT, K_SWEEP_LIST, K_SWEEP_VIRTUAL
@@ -1170,7 +1217,8 @@ def measure(workload, args, env, full):
     if w["kind"] == "driver":
         return run_driver(args, w, env, full)
     if w["kind"] == "jobs":
-        out = run_job_mix(args, w, comm, rank, local_rank, n_gpus, comm_note, steps=(args.steps if full else 1))
+        env.outputs = {}
+        out = run_job_mix(args, w, comm, rank, local_rank, n_gpus, comm_note, steps=(args.steps if full else 1), outputs=env.outputs)
         out["config"]["ranks_seen"] = ranks_seen
         return out
     circ = build_circuit(w)
@@ -1276,10 +1324,11 @@ def measure(workload, args, env, full):
     # result record of the last step (checked + gathered: the only inter-GPU traffic)
     hs, grads = ws.results_fetch()   # the host copies the last timed step delivered
     hs = hs.reshape(B, -1)
+    env.outputs = {("amplitudes" if ncols == 1 else "overlaps"): hs, "gradients": grads}
 
     # sustained rate: the same step for >= --sustain-seconds of wall clock after the driver-sized loop (power / clock settling)
     sustained = None
-    if full and args.sustain_seconds > 0:
+    if full and args.full and args.sustain_seconds > 0:
         barrier()
         t1 = time.perf_counter()
         done_steps = 0
@@ -1312,32 +1361,78 @@ def measure(workload, args, env, full):
 
     # ---- the timed work is checked, not assumed: the last step's (hs, gradient) of a few lanes against the C
     # restatement of the reference algorithm (oracle/aqc_ref.c) on the same (theta, target) --------------------
-    last_th = bank[(W + K - 1) % nsets]
-    # headline-sized problems: 32 lanes spread over the batch (the GPU suite checks all 1024 lanes of this exact workload,
-    # tests/test_hip_round3.py::test_headline_all_lanes); 2^20-amplitude lanes: 2 (0.7 s of C oracle each)
-    n_check = (32 if full else 8) if N <= (1 << 17) else 2
-    check_lanes = sorted(set(int(round(v)) for v in np.linspace(0, B - 1, min(B, n_check))))
-    parity = 0.0
-    from oracle import aqc_ref as cref
+    parity, check_lanes = None, []
+    if args.full:
+        last_th = bank[(W + K - 1) % nsets]
+        # headline-sized problems: 32 lanes spread over the batch (the GPU suite checks all 1024 lanes of this exact workload,
+        # tests/test_hip_round3.py::test_headline_all_lanes); 2^20-amplitude lanes: 2 (0.7 s of C oracle each)
+        n_check = (32 if full else 8) if N <= (1 << 17) else 2
+        check_lanes = sorted(set(int(round(v)) for v in np.linspace(0, B - 1, min(B, n_check))))
+        parity = 0.0
+        from oracle import aqc_ref as cref
 
-    if ncols == 1:
-        for b in check_lanes:   # EVERY delivered output of the lane: all gathered flip-state amplitudes <state_i|V^H|target> and the full gradient
-            h_ref, g_ref = cref.eval_batch(circ, last_th[b][None, :], targets[b], 0, 1)
-            vh_ref = cref.v_dagger_mul_vec(circ, last_th[b], targets[b])
-            parity = max(parity, abs(hs[b, 0] - h_ref[0]), float(np.abs(hs[b] - vh_ref[np.asarray(flip_idx)]).max()),
-                         float(np.abs(grads[b] - g_ref[0]).max()))
-    else:
-        eye = np.eye(1 << n, ncols, dtype=complex)
-        for b in check_lanes[:1]:
-            vhy = cref.v_dagger_mul_mat(circ, last_th[b], targets[b])
-            g_ref = cref.grad_of_matrix_dot_product(circ, last_th[b], eye, vhy)
-            parity = max(parity, abs(hs[b, 0] - np.vdot(eye, vhy)) / ncols, float(np.abs(grads[b] - g_ref).max()) / ncols)
-    if not parity < PARITY_TOL:
-        print(f"bench.py: rank {rank}: timed result deviates from the oracle by {parity:g} (> {PARITY_TOL:g})", file=sys.stderr)
-        os._exit(3)
+        if ncols == 1:
+            for b in check_lanes:   # EVERY delivered output of the lane: all gathered flip-state amplitudes <state_i|V^H|target> and the full gradient
+                h_ref, g_ref = cref.eval_batch(circ, last_th[b][None, :], targets[b], 0, 1)
+                vh_ref = cref.v_dagger_mul_vec(circ, last_th[b], targets[b])
+                parity = max(parity, abs(hs[b, 0] - h_ref[0]), float(np.abs(hs[b] - vh_ref[np.asarray(flip_idx)]).max()),
+                             float(np.abs(grads[b] - g_ref[0]).max()))
+        else:
+            eye = np.eye(1 << n, ncols, dtype=complex)
+            for b in check_lanes[:1]:
+                vhy = cref.v_dagger_mul_mat(circ, last_th[b], targets[b])
+                g_ref = cref.grad_of_matrix_dot_product(circ, last_th[b], eye, vhy)
+                parity = max(parity, abs(hs[b, 0] - np.vdot(eye, vhy)) / ncols, float(np.abs(grads[b] - g_ref).max()) / ncols)
+        if not parity < PARITY_TOL:
+            print(f"bench.py: rank {rank}: timed result deviates from the oracle by {parity:g} (> {PARITY_TOL:g})", file=sys.stderr)
+            os._exit(3)
 
     out = None
     if rank == 0:
+        stages_inv, k_inv, tiles_inv = ws.plan_info(0)
+        stages_sw, k_sw, tiles_sw = ws.plan_info(1)
+        evals = K * B * n_gpus
+        value = evals / wall
+        out = {
+            "metric": "objective+gradient evals/sec",
+            "value": value,
+            "unit": "evals/s",
+            "n_gpus": n_gpus,
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": wall / K * 1e3,
+            "ms_per_eval": wall / (K * B) * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": w["desc"],
+                "n_qubits": n,
+                "num_thetas": T,
+                "gate_groups": G,
+                "batch_per_gpu": B,
+                "path": ("MPS front door (mps_dot_objective), dense route" if chi else "state-vector (core_operations)") if ncols == 1 else "matrix (core_op_matrix)",
+                "mps_bond_dimension": chi or None,
+                "mps_trunc_thr": thr if chi else None,
+                "columns": ncols,
+                "transport": comm.transport if comm_note is None else comm_note,
+                "records_gathered": len(gathered),
+                "ranks_seen": ranks_seen,
+                "per_rank_evals_per_s": {"min": min(rank_rates), "max": max(rank_rates), "mean": float(np.mean(rank_rates)),
+                                         "all": rank_rates, "clock": "HIP events on each rank's own stream over its timed steps"},
+                "launcher": os.environ.get("AQC_BENCH_LAUNCHER", "external" if world > 1 else "none"),
+                "tile_bits": {"vdag": k_inv, "sweep": k_sw},
+                "launches_per_eval_step": {"vdag": stages_inv, "sweep": stages_sw},
+            },
+            "debug_skip": os.environ.get("AQC_DEBUG_SKIP", ""),
+            "results_to_host": "every timed step ends with asynchronous copies of its gradients (batch x T complex128) and amplitudes "
+                               "into pinned host memory (aqc_ws_results_async: a second stream, overlapped with the next step's kernels; the "
+                               "kernels that overwrite the results wait for the copies); the last step's copies are the checked (--full) and dumped ones",
+            "device_ms_per_step_events": ev_ms / K,
+        }
+    if rank == 0 and args.full:
         # ---- per-kernel durations on this stream (HIP events around every launch) ----------
         # (the card idled through the CPU check above: half a second of the same steps first, so that the profiled launches run
         # at the clocks of the timed loop -- measured straight after the idle phase they come out 5-7 % longer than in the
@@ -1381,8 +1476,6 @@ def measure(workload, args, env, full):
         if stage_launches:   # matrix-core path: every stage launch on its own (a sweep over a tile list is a different launch from a dense one)
             dominant = max(stage_launches["launches"], key=lambda r: r["avg_ms"])
             exec_tflops, exec_flops_per_launch, sweep_avg_ms = dominant["TFLOPs"], dominant["flops"], dominant["avg_ms"]
-        stages_inv, k_inv, tiles_inv = ws.plan_info(0)
-        stages_sw, k_sw, tiles_sw = ws.plan_info(1)
 
         # ---- single-evaluation latency (batch 1, host-visible result each call) ---------------
         latency = None
@@ -1446,41 +1539,7 @@ def measure(workload, args, env, full):
             front_door = {"calls": "mps_operations.v_dagger_mul_mps + mps_dot_objective.fast_dot_gradient, trunc_thr = %g" % thr,
                           "evals_per_s": 35 / dt1, "ms_per_eval": dt1 / 35 * 1e3, "route": "dense" if mdo.use_dense(n, thr) else "mps engine",
                           "parity_maxerr": float(np.abs(g1 - g_ref).max())}
-        evals = K * B * n_gpus
-        value = evals / wall
-        out = {
-            "metric": "objective+gradient evals/sec",
-            "value": value,
-            "unit": "evals/s",
-            "n_gpus": n_gpus,
-            "steps": K,
-            "warmup": W,
-            "ms_per_step": wall / K * 1e3,
-            "ms_per_eval": wall / (K * B) * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": w["desc"],
-                "n_qubits": n,
-                "num_thetas": T,
-                "gate_groups": G,
-                "batch_per_gpu": B,
-                "path": ("MPS front door (mps_dot_objective), dense route" if chi else "state-vector (core_operations)") if ncols == 1 else "matrix (core_op_matrix)",
-                "mps_bond_dimension": chi or None,
-                "mps_trunc_thr": thr if chi else None,
-                "columns": ncols,
-                "transport": comm.transport if comm_note is None else comm_note,
-                "records_gathered": len(gathered),
-                "ranks_seen": ranks_seen,
-                "per_rank_evals_per_s": {"min": min(rank_rates), "max": max(rank_rates), "mean": float(np.mean(rank_rates)),
-                                         "all": rank_rates, "clock": "HIP events on each rank's own stream over its timed steps"},
-                "launcher": os.environ.get("AQC_BENCH_LAUNCHER", "external" if world > 1 else "none"),
-                "tile_bits": {"vdag": k_inv, "sweep": k_sw},
-                "launches_per_eval_step": {"vdag": stages_inv, "sweep": stages_sw},
-            },
+        out.update({
             # The sweep launches fuse many gate groups per HBM round trip, so what bounds them is fp64 arithmetic on the matrix
             # cores, not HBM.  `achieved` = flops the matrix pipe EXECUTED in one sweep launch (288 real flops per amplitude
             # and sub-stage: 9 real 16x16x16 products per 256 amplitudes) / its average duration (HIP events on the
@@ -1522,7 +1581,6 @@ def measure(workload, args, env, full):
             },
             "parity_maxerr": parity,
             "parity_lanes_checked": len(check_lanes) if ncols == 1 else 1,
-            "debug_skip": os.environ.get("AQC_DEBUG_SKIP", ""),
             # The fused launches are bound by the fp64 vector ALU, not by HBM: SURVEY 8(d)'s unfused flop count
             # (V^H 28 / block + 14 / front qubit, sweep 48 + 36, inner products 32 + 24 per element) against
             # the 78.6 TFLOP/s fp64 peak of MI355X_MICROARCH.md, over the whole evaluation (wall clock).
@@ -1535,16 +1593,12 @@ def measure(workload, args, env, full):
             },
             "sustained_evals_per_s": None if sustained is None else sustained[0],
             "sustained": None if sustained is None else {"seconds": sustained[1], "steps": sustained[2]},
-            "results_to_host": "every timed step ends with asynchronous copies of its gradients (batch x T complex128) and amplitudes "
-                               "into pinned host memory (aqc_ws_results_async: a second stream, overlapped with the next step's kernels; the "
-                               "kernels that overwrite the results wait for the copies); the last step's copies are the checked ones",
             "objective_object": objective_object,
             "kernel_ms_per_step": {k: v[1] / prof_steps for k, v in prof.items()},
-            "device_ms_per_step_events": ev_ms / K,
             "latency_batch1_ms": latency,
             "latency_batch1_rounds_ms": latency_rounds,
             "algorithmic_GBps_whole_eval": (sweep_bytes_per_step + apply_bytes_per_step) * K / wall / 1e9,
-        }
+        })
         if front_door is not None:
             out["front_door_single_lane"] = front_door
         if full and not args.no_cpu_baseline:

@@ -418,6 +418,28 @@ def test_bench_launches_its_own_ranks():
     assert p.returncode != 0 and p.stdout.strip() == ""
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs writes float64 arrays (complex ones as real / imaginary pairs); above the size limit the same seeded
+    sample of lanes is taken from every per-lane array, and its indices are written alongside."""
+    import bench
+
+    rng = np.random.default_rng(3)
+    amps = rng.standard_normal((64, 5)) + 1j * rng.standard_normal((64, 5))
+    grads = rng.standard_normal((64, 7)) + 1j * rng.standard_normal((64, 7))
+    bench.dump_outputs(str(tmp_path / "all"), {"amplitudes": amps, "gradients": grads, "fidelity": [0.5, 0.25]})
+    a, f = np.load(tmp_path / "all" / "amplitudes.npy"), np.load(tmp_path / "all" / "fidelity.npy")
+    assert a.dtype == np.float64 and a.shape == (64, 5, 2) and np.array_equal(a[..., 0] + 1j * a[..., 1], amps)
+    assert f.dtype == np.float64 and f.tolist() == [0.5, 0.25] and not (tmp_path / "all" / "lanes.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"amplitudes": amps, "gradients": grads})
+    lanes = np.load(tmp_path / "s1" / "lanes.npy").astype(int)
+    g = np.load(tmp_path / "s1" / "gradients.npy")
+    assert 0 < len(lanes) < 64 and sum(np.load(tmp_path / "s1" / f).nbytes for f in ("amplitudes.npy", "gradients.npy", "lanes.npy")) <= 4096
+    assert np.array_equal(g[..., 0] + 1j * g[..., 1], grads[lanes])
+    assert np.array_equal(lanes, np.load(tmp_path / "s2" / "lanes.npy").astype(int))
+
+
 def test_run_jobs_fails_instead_of_hanging_when_a_rank_dies(tmp_path):
     """A rank that dies before the final gather must fail the job list on the survivors (here: the gloo double's collective
     raises after its time-out), not leave them waiting forever (job_executor.py:149-159 reports failures, it never hangs)."""

@@ -10,11 +10,11 @@ tests)
   python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1 || true
   tail -3 $O/gpu_tests.log ;;
 bench)
-  python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err     # the driver's command: headline + every config
-  python bench.py --batch 64 --no-configs --no-cpu-baseline --no-objective-object > $O/bench_b64.json 2> $O/bench_b64.err
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err     # the driver's command: headline + every config
+  python bench.py --full --batch 64 --no-configs --no-cpu-baseline --no-objective-object > $O/bench_b64.json 2> $O/bench_b64.err
   echo "bench done" ;;
 trace)
-  rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 bench.py --no-configs --no-cpu-baseline --no-latency --no-objective-object --sustain-seconds 0 > $O/bench_under_rocprof.json 2> $O/kt.err
+  rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 bench.py --full --no-configs --no-cpu-baseline --no-latency --no-objective-object --sustain-seconds 0 > $O/bench_under_rocprof.json 2> $O/kt.err
   echo "kernel trace done" ;;
 pmc)
   rocprofv3 --pmc FETCH_SIZE -d $O/pmc_f -o f --output-format csv -- python3 tools/prof_run3.py > $O/pmc_f.log 2>&1
@@ -27,12 +27,12 @@ sq)
   echo "sq done" ;;
 workloads)
   for w in cd5_cyc180 mps32_trotter2_engine mps32_trotter2_opt mat10_l40_k16; do
-    python bench.py --workload $w --steps 40 --warmup 10 --sustain-seconds 0 > $O/bench_$w.json 2> $O/bench_$w.err
+    python bench.py --full --workload $w --steps 40 --warmup 10 --sustain-seconds 0 > $O/bench_$w.json 2> $O/bench_$w.err
     echo "bench $w done"
   done ;;
 cfg4)
-  timeout -k 10 400 python bench.py --workload cfg4_jobs --steps 2 --warmup 1 > $O/bench_cfg4_jobs.json 2> $O/bench_cfg4_jobs.err || echo "cfg4_jobs failed"
-  rocprofv3 --kernel-trace --stats -d $O/kt_cfg4 -o kt --output-format csv -- python3 bench.py --workload cfg4_jobs --steps 1 --warmup 1 > $O/bench_cfg4_under_rocprof.json 2> $O/kt_cfg4.err || echo "cfg4 trace failed"
+  timeout -k 10 400 python bench.py --full --workload cfg4_jobs --steps 2 --warmup 1 > $O/bench_cfg4_jobs.json 2> $O/bench_cfg4_jobs.err || echo "cfg4_jobs failed"
+  rocprofv3 --kernel-trace --stats -d $O/kt_cfg4 -o kt --output-format csv -- python3 bench.py --full --workload cfg4_jobs --steps 1 --warmup 1 > $O/bench_cfg4_under_rocprof.json 2> $O/kt_cfg4.err || echo "cfg4 trace failed"
   echo "cfg4 done" ;;
 lockstep)
   rm -f $O/lockstep_lanes.log
