@@ -35,6 +35,14 @@ int check_buf(const aqc_ws* ws, int buf) {
     return 0;
 }
 
+// block_from < 0: all blocks (what grad_from_impl checks again; the one-call evaluations ask before they enqueue anything)
+int check_block_range(const aqc_ws* ws, int block_from, int block_to) {
+    const int nb = ws->ctx->prog.num_blocks;
+    if (block_from < 0 || nb == 0) return 0;
+    if (!(block_from < block_to && block_to <= nb)) return fail("invalid block_range [%d, %d)", block_from, block_to);
+    return 0;
+}
+
 int ensure_small(aqc_ws* ws, size_t n_cplx) {
     if (n_cplx <= ws->small_cap) return 0;
     if (ws->d_small) HIP_OK(hipFree(ws->d_small));
@@ -509,12 +517,12 @@ int aqc_ws_upload(aqc_ws* ws, int buf, const double* src) {
 
 int aqc_ws_upload_lane(aqc_ws* ws, int buf, int lane, const double* src) {
     if (check_buf(ws, buf)) return 1;
-    if (buf == AQC_BUF_Z && ensure_z_full(ws, false)) return 1;
-    ws->combo_valid[buf] = false;
-    touch_buf(ws, buf);
     if (!src) return fail("null source");
     if (lane < 0 || lane >= ws->batch) return fail("lane out of range");
     HIP_OK(hipSetDevice(ws->device));
+    if (buf == AQC_BUF_Z && ensure_z_lanes(ws)) return 1;
+    ws->combo_valid[buf] = false;
+    touch_buf(ws, buf);
     return copy_in(ws, ws->bufs[buf] + (size_t)lane * ws->lane_elems, src, (size_t)1 << ws->ctx->prog.n);
 }
 
@@ -539,7 +547,7 @@ int aqc_ws_copy_lane(aqc_ws* dst_ws, int dst_buf, int dst_lane, aqc_ws* src_ws, 
     if (dst_ws->lane_elems != src_ws->lane_elems) return fail("copy_lane: lane sizes differ");
     if (dst_lane < 0 || dst_lane >= dst_ws->batch || src_lane < 0 || src_lane >= src_ws->batch) return fail("lane out of range");
     if (src_buf == AQC_BUF_Z && ensure_z_full(src_ws, true)) return 1;
-    if (dst_buf == AQC_BUF_Z && ensure_z_full(dst_ws, false)) return 1;
+    if (dst_buf == AQC_BUF_Z && ensure_z_lanes(dst_ws)) return 1;
     HIP_OK(hipSetDevice(dst_ws->device));
     dst_ws->combo_valid[dst_buf] = false;
     touch_buf(dst_ws, dst_buf);

@@ -262,6 +262,7 @@ struct ProfScope {  // brackets one launch with events when profiling is on
 
 // aqc_api.cpp
 int check_buf(const aqc_ws* ws, int buf);
+int check_block_range(const aqc_ws* ws, int block_from, int block_to);
 int ensure_small(aqc_ws* ws, size_t n_cplx);
 int ensure_tmp(aqc_ws* ws, size_t n_index, size_t n_cplx);
 int ensure_index(aqc_ws* ws, size_t n);
@@ -271,7 +272,9 @@ int copy_out(aqc_ws* ws, double* dst, const double2* src, size_t rows);
 int results_guard(aqc_ws* ws);
 // aqc_ws_sweep.cpp
 void touch_buf(aqc_ws* ws, int buf);   // somebody other than the V^H / sweep pair is about to write the whole buffer
-int ensure_z_full(aqc_ws* ws, bool reader);   // before anybody reads Z (or writes a part of it): complete a partial V^H y
+int ensure_z_full(aqc_ws* ws, bool reader);   // before anybody reads Z (reader) or overwrites ZW: complete a partial V^H y
+int ensure_z_lanes(aqc_ws* ws);               // before a write of some lanes of Z: complete the others, or refuse
+void replay_state_after(aqc_ws* ws);          // host-side lists a graph replay has rebuilt on the device behind the host's back
 bool vdag_route_restricted(const aqc_ws* ws, int x_buf);
 int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set = false);
 void vdag_restricted_state_after(aqc_ws* ws, int x_buf);

@@ -168,6 +168,7 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     if (ws->ncols != 1) return fail("the surrogate objective works on state-vector workspaces");
     if (ws->gather_count < 1) return fail("aqc_ws_gather_setup has not been called (flip-state indices, state 0 first)");
     if (update_state < 0 || update_state > 2) return fail("update_state is 0 (none), 1 (hysteresis and weight) or 2 (hysteresis only)");
+    if (check_block_range(ws, block_from, block_to)) return 1;
     HIP_OK(hipSetDevice(ws->device));
     if (ws->copy_pending) {   // as in aqc_ws_eval: the pinned staging buffer is reused
         HIP_OK(hipStreamSynchronize(ws->copy_stream));
@@ -301,6 +302,7 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
         ++ws->supp_version[AQC_BUF_X2];
         ws->combo_last_elem[AQC_BUF_X2].clear();
         sweep_state_after(ws, sparse, true);
+        replay_state_after(ws);
         HIP_OK(hipGraphLaunch(it->second, st));
     } else if (enqueue()) {
         return 1;

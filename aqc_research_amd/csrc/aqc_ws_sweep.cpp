@@ -163,6 +163,7 @@ int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
     DevPlan& p = inverse ? ws->inv : ws->fwd;
     const Program& prog = ws->ctx->prog;
     if (src_buf == AQC_BUF_Z && ensure_z_full(ws, true)) return 1;
+    if (dst_buf == AQC_BUF_ZW && ensure_z_full(ws, false)) return 1;   // the stages overwrite the checkpoint: complete Z from it first
     if (p.v3) {
         if (ensure_umat(ws, p)) return 1;
         const bool keep = keeps_checkpoint(ws, inverse, src_buf, dst_buf);
@@ -276,13 +277,23 @@ int ensure_z_full(aqc_ws* ws, bool reader) {
         ws->z_full = true;
         return 0;
     }
-    if (!reader) { ws->z_full = true; return 0; }   // a writer of parts of Z takes the buffer over
+    if (!reader) return 0;   // ZW is overwritten without a checkpoint in it: Z stays partial (its readers refuse, or complete it from Y)
     if (ws->z_from_y && ws->inv.u_valid) {   // (objective by projection: no checkpoint -- the whole V^H once more, from Y)
         ws->z_full = true;
         return run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z);
     }
     return fail("BUF_Z holds V^H y only on the tiles the last one-call evaluation read, and the thetas (or ZW) have changed since: "
                 "run aqc_ws_apply(inverse) for the whole vector");
+}
+
+// A writer of some lanes of Z keeps the others: they must hold V^H y in full.  With one lane the write covers the whole buffer.
+int ensure_z_lanes(aqc_ws* ws) { return ws->batch > 1 ? ensure_z_full(ws, true) : 0; }
+
+// A captured graph rebuilds the last V^H stage's tile list (d_vd_items) and the projected route's virtual pattern (vm) from
+// whatever the device holds when it is replayed: neither may be taken as built for any lhs buffer afterwards.
+void replay_state_after(aqc_ws* ws) {
+    ws->vd_key[0] = ws->vd_key[1] = ws->vd_key[2] = ~0ull;
+    ws->proj.init_buf = -1;
 }
 
 void drop_graphs(aqc_ws* ws) {
@@ -541,6 +552,7 @@ extern "C" {
 int aqc_ws_objective_launch(aqc_ws* ws, int x_buf, int block_from, int block_to, int front_layer) {
     if (check_buf(ws, x_buf)) return 1;
     if (x_buf == AQC_BUF_W || x_buf == AQC_BUF_ZW || x_buf == AQC_BUF_Z || x_buf == AQC_BUF_Y) return fail("lhs buffer must be X or X2");
+    if (check_block_range(ws, block_from, block_to)) return 1;   // (a refused call enqueues nothing)
     if (ensure_coef(ws)) return 1;
     HIP_OK(hipSetDevice(ws->device));
     const bool sparse = sweep_route_sparse(ws, x_buf, true);
@@ -573,8 +585,9 @@ int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered,
         nsm = (size_t)ws->batch * ws->gather_count;
         if (2 * nsm > ws->pin_small) return fail("too many gathered amplitudes for the staging buffer");
     }
-    if (!thetas && (do_vdag || grads) && ensure_coef(ws)) return 1;
     if (check_buf(ws, x_buf)) return 1;
+    if (grads && check_block_range(ws, block_from, block_to)) return 1;
+    if (!thetas && (do_vdag || grads) && ensure_coef(ws)) return 1;
     // Small results skip the device-to-host copy nodes: the producing kernels write a second copy straight into the pinned
     // staging buffer (two nodes and their dependencies less on the single-evaluation critical path).
     const bool zero_copy = sizeof(double2) * (nth + nsm) <= 65536;
@@ -657,6 +670,7 @@ int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered,
             if (by_projection) { ws->ckpt_valid = false; ws->z_from_y = true; ws->z_gather_gen = ~0ull; }   // (what run_vdag_projected leaves)
         }
         if (grads) sweep_state_after(ws, sparse, true);
+        replay_state_after(ws);
         HIP_OK(hipGraphLaunch(it->second, ws->stream));
     } else if (enqueue()) {
         return 1;

@@ -286,8 +286,8 @@ class Workspace:
 
     def gather_setup(self, index) -> None:
         idx = np.ascontiguousarray(index, dtype=np.int64).ravel()
-        self._gather_count = idx.size
         check(self._L.aqc_ws_gather_setup(self.handle, idx.ctypes.data_as(ctypes.POINTER(c_int64)), idx.size))
+        self._gather_count = idx.size   # (after the call: a refused set-up keeps the old count, which sizes every fetch)
 
     def gather_launch(self, buf: int) -> None:
         check(self._L.aqc_ws_gather_launch(self.handle, buf))

@@ -41,7 +41,10 @@ enum { AQC_CX = 0, AQC_CZ = 1, AQC_CP = 2 };
  * its last stage, which is what the sweep's second stage takes as z when the lhs state is sparse (aqc_ws_set_basis /
  * aqc_ws_set_combo; grad_of_dot_product, core_operations.py:892-935, copies x into w: a one-hot x leaves w zero outside one tile
  * during the first stage).  One-call evaluations (aqc_ws_eval, aqc_ws_objective_launch, aqc_ws_surrogate_eval, aqc_ws_lbfgs) may
- * leave Z computed only on the tiles they read; any reader of AQC_BUF_Z through this interface completes it first. */
+ * leave Z computed only on the tiles they read; any reader of AQC_BUF_Z through this interface completes it first, or fails
+ * ("BUF_Z holds ...") once the thetas have changed since.  A writer of ZW completes such a Z before it overwrites the checkpoint.
+ * A writer of some lanes of Z (aqc_ws_upload_lane, aqc_ws_copy_lane, aqc_ws_mps_to_vec[_batch]) completes the other lanes the
+ * same way, or refuses with the readers' message; with batch 1 it writes the whole buffer and takes it over. */
 enum { AQC_BUF_Y = 0, AQC_BUF_Z = 1, AQC_BUF_X = 2, AQC_BUF_W = 3, AQC_BUF_ZW = 4, AQC_BUF_X2 = 5, AQC_NUM_BUFS = 6 };
 /* kernel families for aqc_ws_profile_get */
 enum { AQC_K_APPLY = 0, AQC_K_SWEEP = 1, AQC_K_COEF = 2, AQC_K_FINALIZE = 3, AQC_K_MISC = 4,
