@@ -500,16 +500,13 @@ int aqc_ws_set_thetas(aqc_ws* ws, const double* thetas) {
     HIP_OK(hipSetDevice(ws->device));
     const Program& prog = ws->ctx->prog;
     const int T = prog.num_thetas();
-    ws->d_thetas = ws->d_thetas_own;
-    HIP_OK(hipMemcpyAsync(ws->d_thetas, thetas, sizeof(double) * (size_t)ws->batch * T, hipMemcpyHostToDevice, ws->stream));
+    HIP_OK(hipMemcpyAsync(ws->d_thetas_own, thetas, sizeof(double) * (size_t)ws->batch * T, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));  // the host buffer may be reused right away
-    return run_coef(ws);
+    return run_coef(ws, ws->d_thetas_own);
 }
 
 int aqc_ws_upload(aqc_ws* ws, int buf, const double* src) {
-    if (check_buf(ws, buf)) return 1;
-    ws->combo_valid[buf] = false;
-    touch_buf(ws, buf);
+    if (check_buf(ws, buf) || before_write(ws, buf)) return 1;
     if (!src) return fail("null source");
     HIP_OK(hipSetDevice(ws->device));
     return copy_in(ws, ws->bufs[buf], src, (size_t)ws->batch << ws->ctx->prog.n);
@@ -520,16 +517,12 @@ int aqc_ws_upload_lane(aqc_ws* ws, int buf, int lane, const double* src) {
     if (!src) return fail("null source");
     if (lane < 0 || lane >= ws->batch) return fail("lane out of range");
     HIP_OK(hipSetDevice(ws->device));
-    if (buf == AQC_BUF_Z && ensure_z_lanes(ws)) return 1;
-    ws->combo_valid[buf] = false;
-    touch_buf(ws, buf);
+    if (before_write(ws, buf, true)) return 1;
     return copy_in(ws, ws->bufs[buf] + (size_t)lane * ws->lane_elems, src, (size_t)1 << ws->ctx->prog.n);
 }
 
 int aqc_ws_broadcast(aqc_ws* ws, int buf, const double* src) {
-    if (check_buf(ws, buf)) return 1;
-    ws->combo_valid[buf] = false;
-    touch_buf(ws, buf);
+    if (check_buf(ws, buf) || before_write(ws, buf)) return 1;
     if (!src) return fail("null source");
     HIP_OK(hipSetDevice(ws->device));
     if (copy_in(ws, ws->bufs[buf], src, (size_t)1 << ws->ctx->prog.n)) return 1;
@@ -546,11 +539,8 @@ int aqc_ws_copy_lane(aqc_ws* dst_ws, int dst_buf, int dst_lane, aqc_ws* src_ws, 
     if (dst_ws->device != src_ws->device) return fail("copy_lane: the two workspaces live on different devices");
     if (dst_ws->lane_elems != src_ws->lane_elems) return fail("copy_lane: lane sizes differ");
     if (dst_lane < 0 || dst_lane >= dst_ws->batch || src_lane < 0 || src_lane >= src_ws->batch) return fail("lane out of range");
-    if (src_buf == AQC_BUF_Z && ensure_z_full(src_ws, true)) return 1;
-    if (dst_buf == AQC_BUF_Z && ensure_z_lanes(dst_ws)) return 1;
+    if (before_read(src_ws, src_buf) || before_write(dst_ws, dst_buf, true)) return 1;
     HIP_OK(hipSetDevice(dst_ws->device));
-    dst_ws->combo_valid[dst_buf] = false;
-    touch_buf(dst_ws, dst_buf);
     if (src_ws->stream != dst_ws->stream) HIP_OK(hipStreamSynchronize(src_ws->stream));   // the source is complete
     HIP_OK(hipMemcpyAsync(dst_ws->bufs[dst_buf] + (size_t)dst_lane * dst_ws->lane_elems, src_ws->bufs[src_buf] + (size_t)src_lane * src_ws->lane_elems,
                           sizeof(double2) * dst_ws->lane_elems, hipMemcpyDeviceToDevice, dst_ws->stream));
@@ -561,7 +551,7 @@ int aqc_ws_download(aqc_ws* ws, int buf, double* dst) {
     if (check_buf(ws, buf)) return 1;
     if (!dst) return fail("null destination");
     HIP_OK(hipSetDevice(ws->device));
-    if (buf == AQC_BUF_Z && ensure_z_full(ws, true)) return 1;
+    if (before_read(ws, buf)) return 1;
     return copy_out(ws, dst, ws->bufs[buf], (size_t)ws->batch << ws->ctx->prog.n);
 }
 
@@ -570,14 +560,12 @@ int aqc_ws_download_lane(aqc_ws* ws, int buf, int lane, double* dst) {
     if (!dst) return fail("null destination");
     if (lane < 0 || lane >= ws->batch) return fail("lane out of range");
     HIP_OK(hipSetDevice(ws->device));
-    if (buf == AQC_BUF_Z && ensure_z_full(ws, true)) return 1;
+    if (before_read(ws, buf)) return 1;
     return copy_out(ws, dst, ws->bufs[buf] + (size_t)lane * ws->lane_elems, (size_t)1 << ws->ctx->prog.n);
 }
 
 int aqc_ws_set_basis(aqc_ws* ws, int buf, const int64_t* index) {
-    if (check_buf(ws, buf)) return 1;
-    ws->combo_valid[buf] = false;
-    touch_buf(ws, buf);
+    if (check_buf(ws, buf) || before_write(ws, buf)) return 1;
     if (!index) return fail("null index");
     HIP_OK(hipSetDevice(ws->device));
     const int64_t dim = (int64_t)1 << ws->ctx->prog.n;
@@ -601,18 +589,14 @@ int aqc_ws_set_basis(aqc_ws* ws, int buf, const int64_t* index) {
     if (!ws->d_combo_prev[buf]) HIP_OK(hipMalloc((void**)&ws->d_combo_prev[buf], sizeof(long long) * 2 * ws->batch));
     HIP_OK(hipMemcpyAsync(ws->d_combo_prev[buf], supp.data(), sizeof(long long) * supp.size(), hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
-    ws->combo_valid[buf] = true;
-    ws->combo_last_elem[buf] = supp;
-    ws->combo_last_coef[buf].assign(4 * (size_t)ws->batch, 0.0);
-    for (int b = 0; b < ws->batch; ++b) ws->combo_last_coef[buf][4 * (size_t)b] = 1.0;
-    ++ws->supp_version[buf];
+    std::vector<double> coef(4 * (size_t)ws->batch, 0.0);
+    for (int b = 0; b < ws->batch; ++b) coef[4 * (size_t)b] = 1.0;
+    lhs_support_changed(ws, buf, std::move(supp), std::move(coef));
     return 0;
 }
 
 int aqc_ws_set_identity(aqc_ws* ws, int buf) {
-    if (check_buf(ws, buf)) return 1;
-    ws->combo_valid[buf] = false;
-    touch_buf(ws, buf);
+    if (check_buf(ws, buf) || before_write(ws, buf)) return 1;
     const int dim = 1 << ws->ctx->prog.n;
     if (ws->ncols != dim) return fail("identity needs a square workspace (ncols == 2^n)");
     HIP_OK(hipSetDevice(ws->device));
@@ -647,7 +631,7 @@ int aqc_ws_set_combo(aqc_ws* ws, int buf, const int64_t* index, const double* co
     if (ws->combo_valid[buf] && ws->combo_last_elem[buf] == elem && ws->combo_last_coef[buf] == cf) return 0;
     if (!ws->d_combo_index) HIP_OK(hipMalloc((void**)&ws->d_combo_index, sizeof(long long) * 2 * B));
     if (!ws->d_combo_coef) HIP_OK(hipMalloc((void**)&ws->d_combo_coef, sizeof(double2) * 2 * B));
-    if (!ws->d_combo_prev[buf]) { HIP_OK(hipMalloc((void**)&ws->d_combo_prev[buf], sizeof(long long) * 2 * B)); ws->combo_valid[buf] = false; }
+    if (!ws->d_combo_prev[buf]) HIP_OK(hipMalloc((void**)&ws->d_combo_prev[buf], sizeof(long long) * 2 * B));   // (combo_valid is false without it)
     HIP_OK(hipMemcpyAsync(ws->d_combo_index, elem.data(), sizeof(long long) * 2 * B, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipMemcpyAsync(ws->d_combo_coef, coef, sizeof(double2) * 2 * B, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));   // `elem` and the caller's array may go away
@@ -657,11 +641,7 @@ int aqc_ws_set_combo(aqc_ws* ws, int buf, const int64_t* index, const double* co
     }
     ProfScope ps(ws, AQC_K_MISC);
     HIP_OK(launch_scatter_two(ws->bufs[buf], ws->lane_elems, B, ws->d_combo_index, ws->d_combo_coef, ws->d_combo_prev[buf], ws->stream));
-    ws->combo_valid[buf] = true;
-    ws->combo_last_elem[buf] = elem;
-    ws->combo_last_coef[buf].swap(cf);
-    ++ws->supp_version[buf];
-    touch_buf(ws, buf);
+    lhs_support_changed(ws, buf, std::move(elem), std::move(cf));
     return 0;
 }
 
@@ -678,7 +658,7 @@ int aqc_ws_gather(aqc_ws* ws, int buf, const int64_t* index, int count, double* 
     if (check_buf(ws, buf)) return 1;
     if (!index || !out || count < 1) return fail("invalid gather arguments");
     HIP_OK(hipSetDevice(ws->device));
-    if (buf == AQC_BUF_Z && ensure_z_full(ws, true)) return 1;
+    if (before_read(ws, buf)) return 1;
     const int64_t dim = (int64_t)1 << ws->ctx->prog.n;
     std::vector<long long> elem(count);
     for (int i = 0; i < count; ++i) {
@@ -702,7 +682,7 @@ int aqc_ws_vdot(aqc_ws* ws, int buf_a, int buf_b, double* out) {
     if (check_buf(ws, buf_a) || check_buf(ws, buf_b)) return 1;
     if (!out) return fail("null output");
     HIP_OK(hipSetDevice(ws->device));
-    if ((buf_a == AQC_BUF_Z || buf_b == AQC_BUF_Z) && ensure_z_full(ws, true)) return 1;
+    if (before_read(ws, buf_a) || before_read(ws, buf_b)) return 1;
     HIP_OK(hipStreamSynchronize(ws->stream));
     if (ensure_tmp(ws, 0, ws->batch)) return 1;
     {
@@ -735,9 +715,7 @@ int aqc_ws_use_theta_set(aqc_ws* ws, int set_index) {
     if (!ws) return fail("null workspace");
     if (set_index < 0 || set_index >= ws->bank_sets) return fail("theta set %d out of range (%d loaded)", set_index, ws->bank_sets);
     HIP_OK(hipSetDevice(ws->device));
-    const Program& prog = ws->ctx->prog;
-    ws->d_thetas = ws->d_theta_bank + (size_t)set_index * ws->batch * prog.num_thetas();
-    return run_coef(ws);
+    return run_coef(ws, ws->d_theta_bank + (size_t)set_index * ws->batch * ws->ctx->prog.num_thetas());
 }
 
 int aqc_ws_gather_setup(aqc_ws* ws, const int64_t* index, int count) {
@@ -773,8 +751,7 @@ int aqc_ws_gather_launch(aqc_ws* ws, int buf) {
     if (ws->gather_count < 1) return fail("aqc_ws_gather_setup has not been called");
     HIP_OK(hipSetDevice(ws->device));
     if (results_guard(ws)) return 1;
-    if (buf == AQC_BUF_Z && !ws->z_full && ws->z_gather_gen != ws->gather_gen && ensure_z_full(ws, true)) return 1;   // a partial Z covers the
-                                                                                                                    // set it was computed for
+    if (before_gather(ws, buf)) return 1;
     ProfScope ps(ws, AQC_K_MISC);
     HIP_OK(launch_gather(ws->bufs[buf], ws->lane_elems, ws->d_index, ws->gather_count, ws->batch, ws->d_small, ws->stream, ws->mirror_small));
     return 0;
@@ -791,7 +768,7 @@ int aqc_ws_gather_fetch(aqc_ws* ws, double* out) {
 int aqc_ws_vdot_launch(aqc_ws* ws, int buf_a, int buf_b) {
     if (check_buf(ws, buf_a) || check_buf(ws, buf_b)) return 1;
     HIP_OK(hipSetDevice(ws->device));
-    if ((buf_a == AQC_BUF_Z || buf_b == AQC_BUF_Z) && ensure_z_full(ws, true)) return 1;
+    if (before_read(ws, buf_a) || before_read(ws, buf_b)) return 1;
     if (!ws->d_vdot_out) HIP_OK(hipMalloc((void**)&ws->d_vdot_out, sizeof(double2) * ws->batch));
     if (results_guard(ws)) return 1;
     ProfScope ps(ws, AQC_K_MISC);

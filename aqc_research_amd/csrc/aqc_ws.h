@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -67,6 +68,15 @@ struct DevPlan {
     int family() const { return v3 ? 3 : (v2 ? 2 : 1); }
 };
 
+// What a derived list (a tile list, the virtual lhs pattern, a route verdict, the tiles of a partial Z) was built for: the support of
+// one lhs buffer at one version, and the gather set at one generation (0: none; aqc_ws_gather_setup numbers the sets from 1)
+struct ListKey {
+    static constexpr int kUnknown = -2, kGatherOnly = -1;   // buf: nothing recorded / the gather set alone names the tiles
+    int buf = kUnknown;
+    unsigned long long supp = 0, gather = 0;
+    bool operator==(const ListKey& o) const { return buf != kUnknown && buf == o.buf && supp == o.supp && gather == o.gather; }
+};
+
 // Projected route of the sparse-lhs sweep (aqc_ws_project.cpp): the dense stages run on a virtual register
 struct ProjRoute {
     bool ok = false;
@@ -89,8 +99,7 @@ struct ProjRoute {
     TileItem* d_items = nullptr;   // [2 batch ntiles_v]
     int* d_count = nullptr;
     int* d_lane_parts = nullptr;   // [batch]
-    int init_buf = -1;             // vm holds the pattern M_0 (and d_items the list) of this lhs buffer ...
-    unsigned long long init_version = 0;   // ... at this version of its support (single virtual stage: nothing overwrites vm)
+    ListKey init_key;              // vm holds the pattern M_0 (and d_items the list) of this first-stage list (single virtual stage: nothing overwrites vm)
 };
 
 // aqc_ws_plan.cpp
@@ -210,8 +219,7 @@ struct aqc_ws {
     int* d_sw_lane_parts = nullptr;         // items (= partial-R slots in use) per lane
     int* d_sw_prev_tiles = nullptr;         // [batch][2] tiles of W written by the list in use
     int sw_lists_built = 0;                 // bit 0: the sweep's list has been built at least once, bit 1: V^H's
-    int sw_items_buf = -1;                  // the list in d_sw_items belongs to this lhs buffer ...
-    unsigned long long sw_items_version = 0;   // ... at this version of its support
+    aqc::ListKey sw_items_key;              // the list in d_sw_items belongs to this lhs support
     double2* w2 = nullptr;                  // second scratch pair of the sparse route (plans of >= 3 stages)
     double2* zw2 = nullptr;
     // "objective" V^H: the last stage of the mirrored V^H runs only over the tiles its readers touch -- the registered gather
@@ -221,10 +229,8 @@ struct aqc_ws {
     aqc::TileItem* d_vd_items = nullptr;    // [batch][2 + gather_count]
     size_t vd_items_cap = 0;
     unsigned long long gather_gen = 0;      // bumped by aqc_ws_gather_setup
-    unsigned long long vd_key[3] = {~0ull, ~0ull, ~0ull};   // what d_vd_items was built from: lhs buffer (or -1: gather set alone), its support version, gather_gen
-    unsigned long long z_gather_gen = 0;    // what the tiles of a partial Z were chosen for: the gather set ...
-    int z_x_buf = -1;                       // ... and the support of this lhs buffer at this version
-    unsigned long long z_x_version = 0;
+    aqc::ListKey vd_key;                    // what d_vd_items was built from
+    aqc::ListKey z_key;                     // what the tiles of a partial Z were chosen for
     aqc::ProjRoute proj;                    // dense stages of the sparse route on a virtual register (AQC_PROJECTED=0: off)
     bool proj_vdag_enabled = true;          // AQC_PROJECTED_VDAG=0: V^H of a one-call evaluation always by its stages
     long long proj_vdag_min_elems = 1ll << 24;   // ... and from this many amplitudes per batch (fewer: its extra launches cost more than V^H's stages; AQC_PROJECTED_VDAG_MIN_ELEMS)
@@ -232,7 +238,7 @@ struct aqc_ws {
     bool proj_y0_ready = false;             // the virtual z (proj.vy) holds Y_0 for the sweep that follows in the same call (run_vdag_projected)
     bool z_from_y = false;                  // a partial Z without a checkpoint: completed by a full V^H from Y (thetas and Y unchanged since)
     std::vector<long long> h_gather;        // host copy of the registered gather indices (elements)
-    unsigned long long projb_key[3] = {~0ull, ~0ull, ~0ull};   // (lhs buffer, its support version, gather_gen) the verdict below was taken for
+    aqc::ListKey projb_key;                 // what the verdict below was taken for
     bool projb_ok = false;
     bool profile = false;
     int64_t prof_count[AQC_NUM_KINDS] = {};
@@ -270,23 +276,31 @@ int ensure_coef(aqc_ws* ws);
 int copy_in(aqc_ws* ws, double2* dst, const double* src, size_t rows);
 int copy_out(aqc_ws* ws, double* dst, const double2* src, size_t rows);
 int results_guard(aqc_ws* ws);
-// aqc_ws_sweep.cpp
-void touch_buf(aqc_ws* ws, int buf);   // somebody other than the V^H / sweep pair is about to write the whole buffer
-int ensure_z_full(aqc_ws* ws, bool reader);   // before anybody reads Z (reader) or overwrites ZW: complete a partial V^H y
-int ensure_z_lanes(aqc_ws* ws);               // before a write of some lanes of Z: complete the others, or refuse
-void replay_state_after(aqc_ws* ws);          // host-side lists a graph replay has rebuilt on the device behind the host's back
+// aqc_ws_sweep.cpp: the host-side record of what the buffers hold (Z, ZW, W, the lhs supports, the derived lists) changes only here
+int before_read(aqc_ws* ws, int buf);         // the host, or a kernel over all of it, reads the buffer: completes a partial Z
+int before_gather(aqc_ws* ws, int buf);       // the registered gather reads it: a partial Z chosen for that set covers it
+int before_write(aqc_ws* ws, int buf, bool some_lanes = false);   // a writer other than the V^H / sweep pair (the lanes not written are kept)
+// written whole: the pattern d_combo_prev names, known to the host (elem, coef) or chosen on the device (none)
+void lhs_support_changed(aqc_ws* ws, int buf, std::vector<long long> elem = {}, std::vector<double> coef = {});
+int run_coef(aqc_ws* ws, double* d_thetas);   // new thetas in use (and their coefficients where the kernels need them)
+void thetas_changed(aqc_ws* ws, double* d_thetas);
+ListKey key_of(const aqc_ws* ws, int lhs_buf, bool gather);   // lhs_buf: ListKey::kGatherOnly for the gather set alone
+bool built_for(const aqc_ws* ws, const ListKey& slot, const ListKey& key);   // the list `slot` names is built for `key`
+void record_key(const aqc_ws* ws, ListKey& slot, const ListKey& key);         // ... it is now
+void replay_state_after(aqc_ws* ws);          // forgets the lists a graph replay has rebuilt on the device behind the host's back
+int run_graph(aqc_ws* ws, const std::vector<long long>& key, const std::function<int()>& enqueue, const std::function<void()>& state_after);
 bool vdag_route_restricted(const aqc_ws* ws, int x_buf);
 int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set = false);
 void vdag_restricted_state_after(aqc_ws* ws, int x_buf);
+void vdag_projected_state_after(aqc_ws* ws, int x_buf);
 int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int front_layer, bool support_in_gather_set);
 bool sweep_route_sparse(const aqc_ws* ws, int x_buf, bool will_vdag);
 bool sweep_skips_zero_w(const aqc_ws* ws, int x_buf);
 int sweep_r_only_sub(const aqc_ws* ws);   // the lhs state is a combination of basis states the device knows: zero groups of w are skipped
 int sweep_sparse_prepare(aqc_ws* ws);
 void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf);
-void sweep_state_after(aqc_ws* ws, bool sparse, bool replayed);
+void sweep_state_after(aqc_ws* ws, bool sparse);
 int ensure_umat(aqc_ws* ws, DevPlan& p);
-int run_coef(aqc_ws* ws);
 int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf);
 void drop_graphs(aqc_ws* ws);
 // aqc_ws_project.cpp

@@ -184,6 +184,7 @@ int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io, double* fobj) {
     if (aqc_ws_set_thetas(ws, thetas_io)) return 1;                  // theta_in = d_thetas_own
     if (aqc_ws_apply(ws, 1, AQC_BUF_Y, AQC_BUF_Z)) return 1;          // z = V^H U      (core_op_matrix.py:806-810)
     if (aqc_ws_set_identity(ws, AQC_BUF_X)) return 1;                 // w = I
+    if (before_write(ws, AQC_BUF_X) || before_write(ws, AQC_BUF_Z)) return 1;   // the chain below rewrites both in place
     double* d_theta_out = nullptr;
     HIP_OK(hipMalloc((void**)&d_theta_out, sizeof(double) * T));
     HIP_OK(hipMemcpyAsync(d_theta_out, ws->d_thetas_own, sizeof(double) * T, hipMemcpyDeviceToDevice, ws->stream));
@@ -316,9 +317,7 @@ int aqc_ws_mps_to_vec(aqc_ws* ws, int slot, int buf, int lane) {
         return aqc_ws_mps_to_vec_batch(ws, 1, &s1, buf, &l1);
     }
     // n == 1: the state is the site tensor itself, [b][1][1]
-    ws->combo_valid[buf] = false;
-    if (buf == AQC_BUF_Z && ensure_z_lanes(ws)) return 1;
-    touch_buf(ws, buf);
+    if (before_write(ws, buf, true)) return 1;
     ProfScope ps(ws, AQC_K_MISC);
     HIP_OK(hipMemcpyAsync(ws->bufs[buf] + (size_t)lane * ws->lane_elems, ws->mps[slot].d_t, sizeof(double2) * 2, hipMemcpyDeviceToDevice, ws->stream));
     return 0;
@@ -371,9 +370,7 @@ static int mps_to_vec_batch_uniform(aqc_ws* ws, int count, const int32_t* slots,
     HIP_OK(hipSetDevice(ws->device));
     const std::vector<int>& dims = ws->mps[slots[0]].dims;
     const std::vector<size_t>& off = ws->mps[slots[0]].offset;
-    ws->combo_valid[buf] = false;
-    if (buf == AQC_BUF_Z && ensure_z_lanes(ws)) return 1;   // (lanes of Z are rewritten, not all of it)
-    touch_buf(ws, buf);
+    if (before_write(ws, buf, true)) return 1;   // (lanes of Z are rewritten, not all of it)
     std::vector<const void*> tabs;
     auto table = [&](auto fn) { const size_t at = tabs.size(); for (int i = 0; i < count; ++i) tabs.push_back(fn(i)); return at; };
     auto out_lane = [&](int i) { return (const void*)(ws->bufs[buf] + (size_t)lanes[i] * ws->lane_elems); };

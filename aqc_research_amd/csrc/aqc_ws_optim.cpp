@@ -80,9 +80,7 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
         LB_OK(hipMemsetAsync(d_prev, 0xff, sizeof(long long) * 2 * B, st_));   // -1: nothing written yet
         LB_OK(hipMemcpyAsync(L.x, x0, sizeof(double) * BT, hipMemcpyHostToDevice, st_));
         LB_OK(hipMemsetAsync(ws->bufs[AQC_BUF_X2], 0, sizeof(double2) * (size_t)B * ws->lane_elems, st_));
-        ws->combo_valid[AQC_BUF_X2] = true;   // the buffer holds exactly the pattern its record names (nothing, so far)
-        ws->combo_last_elem[AQC_BUF_X2].clear();
-        ++ws->supp_version[AQC_BUF_X2];
+        lhs_support_changed(ws, AQC_BUF_X2);   // (nothing, so far)
         LB_OK(hipStreamSynchronize(st_));
     }
     int64_t nfev = 0;
@@ -94,16 +92,14 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
     // f, g at the point in the workspace's theta buffer; raw results to (raw_hs, raw_g).  V^H, the amplitudes, the lane's
     // combined lhs state (lb_prepare) and ONE sweep from it -- no host round trip inside an evaluation.
     auto evaluate = [&](int update, double* f_o, double* g_o, double2* raw_hs, double2* raw_g) -> int {
-        ws->d_thetas = ws->d_thetas_own;
-        if (run_coef(ws)) return 1;
+        if (run_coef(ws, ws->d_thetas_own)) return 1;
         const bool sparse = sweep_route_sparse(ws, AQC_BUF_X2, true);
         if (sparse && sweep_sparse_prepare(ws)) return 1;
         if (sparse && vdag_route_restricted(ws, AQC_BUF_X2)) { if (run_vdag_restricted(ws, AQC_BUF_X2, true)) return 1; }   // V^H where the gather and
         else if (run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)) return 1;                                                   // the sweep read it
         if (aqc_ws_gather_launch(ws, AQC_BUF_Z)) return 1;
         HIP_OK(lb_prepare(L, ws->d_small, update, f_o, raw_hs, ws->bufs[AQC_BUF_X2], ws->lane_elems, ws->d_index, d_prev, st_));
-        ++ws->supp_version[AQC_BUF_X2];   // (the leading flip state is chosen on the device: the support may have moved)
-        ws->combo_last_elem[AQC_BUF_X2].clear();
+        lhs_support_changed(ws, AQC_BUF_X2);   // (the leading flip state is chosen on the device: the support may have moved)
         if (grad_from_impl(ws, AQC_BUF_X2, block_from, block_to, front_layer, true)) return 1;
         HIP_OK(lb_take(L, ws->d_grads, g_o, raw_g, st_));
         ++nfev;
@@ -216,15 +212,11 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     double* pin_th = ws->h_pin;
     double* pin_gr = ws->h_pin + ws->pin_thetas;
     memcpy(pin_th, thetas, sizeof(double) * nth);
-    if (!ws->d_combo_prev[AQC_BUF_X2]) {
-        HIP_OK(hipMalloc((void**)&ws->d_combo_prev[AQC_BUF_X2], sizeof(long long) * 2 * B));
-        ws->combo_valid[AQC_BUF_X2] = false;
-    }
+    if (!ws->d_combo_prev[AQC_BUF_X2]) HIP_OK(hipMalloc((void**)&ws->d_combo_prev[AQC_BUF_X2], sizeof(long long) * 2 * B));   // (combo_valid is false without it)
     if (!ws->combo_valid[AQC_BUF_X2]) {   // (outside the replayed part: a whole-buffer clear is a one-off)
         HIP_OK(hipMemsetAsync(ws->bufs[AQC_BUF_X2], 0, sizeof(double2) * (size_t)B * ws->lane_elems, st));
         HIP_OK(hipMemsetAsync(ws->d_combo_prev[AQC_BUF_X2], 0xff, sizeof(long long) * 2 * B, st));   // -1: nothing to clear
-        ws->combo_valid[AQC_BUF_X2] = true;   // the buffer holds exactly the pattern its record names
-        ws->combo_last_elem[AQC_BUF_X2].clear();
+        lhs_support_changed(ws, AQC_BUF_X2);
     }
     const bool sparse = sweep_route_sparse(ws, AQC_BUF_X2, true);   // (decided here: part of the captured graph's key)
     if (sparse && sweep_sparse_prepare(ws)) return 1;
@@ -241,9 +233,8 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
             HIP_OK(hipMemcpyAsync(L.weight, hd + 2 * (size_t)B, sizeof(double) * B, hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(L.max_no, h_max, sizeof(int) * B, hipMemcpyHostToDevice, st));
         }
-        ws->d_thetas = ws->d_thetas_own;
-        if (!direct_thetas) HIP_OK(hipMemcpyAsync(ws->d_thetas, pin_th, sizeof(double) * nth, hipMemcpyHostToDevice, st));
-        if (run_coef(ws)) return 1;
+        if (!direct_thetas) HIP_OK(hipMemcpyAsync(ws->d_thetas_own, pin_th, sizeof(double) * nth, hipMemcpyHostToDevice, st));
+        if (run_coef(ws, ws->d_thetas_own)) return 1;
         ws->theta_host = direct_thetas ? pin_th : nullptr;   // the U builder reads the pinned thetas and stores them to HBM
         if (lazy ? run_vdag_restricted(ws, AQC_BUF_X2, true) : run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)) return 1;
         if (aqc_ws_gather_launch(ws, AQC_BUF_Z)) return 1;
@@ -251,8 +242,7 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
             ProfScope ps(ws, AQC_K_MISC);
             HIP_OK(lb_prepare(L, ws->d_small, update_state, d_f, d_hs, ws->bufs[AQC_BUF_X2], ws->lane_elems, ws->d_index,
                               ws->d_combo_prev[AQC_BUF_X2], st));
-            ++ws->supp_version[AQC_BUF_X2];
-            ws->combo_last_elem[AQC_BUF_X2].clear();
+            lhs_support_changed(ws, AQC_BUF_X2);
         }
         // (update_state == 0 leaves weight / max_no / fidelity as they came in; fidelity is only written by an update)
         if (grad_from_impl(ws, AQC_BUF_X2, block_from, block_to, front_layer, true)) return 1;
@@ -275,39 +265,16 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
                                             (long long)(size_t)ws->d_sur, (long long)(size_t)ws->h_sur, (long long)(size_t)ws->h_pin,
                                             (long long)(size_t)ws->d_small, (long long)(size_t)ws->d_combo_prev[AQC_BUF_X2], (sparse ? 1 : 0) + (lazy ? 2 : 0) + (sweep_skips_zero_w(ws, AQC_BUF_X2) ? 4 : 0),
                                             (long long)(size_t)ws->d_vd_items};
-        auto it = ws->graphs.find(key);
-        if (it == ws->graphs.end()) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            HIP_OK(hipStreamSynchronize(st));
-            HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            ws->capturing = true;
-            const int rc = enqueue();
-            ws->capturing = false;
-            const hipError_t e = hipStreamEndCapture(st, &graph);
-            if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return 1; }
-            if (e != hipSuccess || !graph) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
-            const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (ei != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(ei));
-            if (ws->graphs.size() >= 16) drop_graphs(ws);
-            it = ws->graphs.emplace(key, exec).first;
-        }
-        ws->d_thetas = ws->d_thetas_own;   // host-side state that enqueue() would have set
-        ws->coef_valid = true;
-        ws->fwd.u_valid = false;
-        ws->inv.u_valid = ws->sweep.u_valid = ws->inv.v3 && ws->sweep.v3;
-        ws->ckpt_valid = false;
-        if (lazy) vdag_restricted_state_after(ws, AQC_BUF_X2); else apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
-        ++ws->supp_version[AQC_BUF_X2];
-        ws->combo_last_elem[AQC_BUF_X2].clear();
-        sweep_state_after(ws, sparse, true);
-        replay_state_after(ws);
-        HIP_OK(hipGraphLaunch(it->second, st));
+        auto state_after = [&]() {
+            thetas_changed(ws, ws->d_thetas_own);
+            if (lazy) vdag_restricted_state_after(ws, AQC_BUF_X2); else apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
+            lhs_support_changed(ws, AQC_BUF_X2);
+            sweep_state_after(ws, sparse);
+        };
+        if (run_graph(ws, key, enqueue, state_after)) return 1;
     } else if (enqueue()) {
         return 1;
     }
-    ws->combo_valid[AQC_BUF_X2] = true;   // (grad_from does not write its lhs buffer)
     HIP_OK(hipStreamSynchronize(st));
     if (real_only) {
         memcpy(grad_real_out, pin_gr, sizeof(double) * nth);

@@ -171,13 +171,10 @@ static ProjArgs proj_args(aqc_ws* ws);
 // captured graph, whose replays follow a support the host does not see; always with several virtual stages, which work in place on vm)
 static int ensure_pattern(aqc_ws* ws, const ProjArgs& a) {
     ProjRoute& pr = ws->proj;
-    const bool keep = !ws->capturing && pr.vsw.h_stages.size() == 1 && pr.init_buf == ws->sw_items_buf && pr.init_buf >= 0 &&
-                      pr.init_version == ws->sw_items_version;
-    if (keep) return 0;
+    if (pr.vsw.h_stages.size() == 1 && built_for(ws, pr.init_key, ws->sw_items_key)) return 0;
     ProfScope ps(ws, AQC_K_MISC);
     HIP_OK(launch_project_init(a, ws->stream));
-    pr.init_buf = ws->capturing ? -1 : ws->sw_items_buf;
-    pr.init_version = ws->sw_items_version;
+    record_key(ws, pr.init_key, ws->sw_items_key);
     return 0;
 }
 
@@ -211,9 +208,7 @@ static ProjArgs proj_args(aqc_ws* ws) {
 int run_projected_stages(aqc_ws* ws) {
     ProjRoute& pr = ws->proj;
     DevPlan& v = pr.vsw;
-    if (ws->proj_y0_ready) {   // run_vdag_projected of this call has left M_0 and Y_0 (from the target) on the virtual register
-        ws->proj_y0_ready = false;
-    } else {
+    if (!ws->proj_y0_ready) {   // (else run_vdag_projected of this call has left M_0 and Y_0, from the target, on the virtual register)
         ProjArgs a = proj_args(ws);
         if (ensure_pattern(ws, a)) return 1;
         // Y_0[i_T, c] = sum_u conj(psi[u, c]) z[u, i_T]:  Y = the checkpoint, k = u, keep = i_T, S = psi in W, out = the virtual z
@@ -282,9 +277,9 @@ RgradSecond projected_rgrad_plan(aqc_ws* ws) {
 bool vdag_route_projected(aqc_ws* ws, int x_buf) {
     ProjRoute& pr = ws->proj;
     if (!pr.ok || !ws->proj_vdag_enabled || ws->capturing || (long long)ws->lane_elems * ws->batch < ws->proj_vdag_min_elems) return false;
-    const unsigned long long key[3] = {(unsigned long long)x_buf, ws->supp_version[x_buf], ws->gather_gen};
-    if (key[0] == ws->projb_key[0] && key[1] == ws->projb_key[1] && key[2] == ws->projb_key[2]) return ws->projb_ok;
-    for (int i = 0; i < 3; ++i) ws->projb_key[i] = key[i];
+    const ListKey key = key_of(ws, x_buf, true);
+    if (ws->projb_key == key) return ws->projb_ok;
+    ws->projb_key = key;
     ws->projb_ok = false;
     const std::vector<long long>& el = ws->combo_last_elem[x_buf];
     const std::vector<double>& cf = ws->combo_last_coef[x_buf];
@@ -402,11 +397,7 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // the caller has asked vdag_r
         ProfScope ps(ws, AQC_K_APPLY_LIST);
         HIP_OK(launch_apply3(iv.ntiles, ws->batch, iv.k, ws->stream, s3));
     }
-    vdag_restricted_state_after(ws, x_buf);
-    ws->ckpt_valid = false;         // ZW holds the lhs tiles of the checkpoint only
-    ws->z_gather_gen = ~0ull;       // Z covers the lhs tiles, not the gather set: a later gather completes it first
-    ws->z_from_y = true;
-    ws->proj_y0_ready = true;
+    vdag_projected_state_after(ws, x_buf);
     return 0;
 }
 

@@ -21,6 +21,71 @@ using namespace aqc;
 
 namespace aqc {
 
+// ---- bookkeeping: what the buffers hold ------------------------------------------------------------------------------
+// Every field of the record (ckpt_valid, z_full, z_key, z_from_y, w_clean, proj_y0_ready, the lhs supports, the list keys, the
+// theta state) is assigned in this section alone; the rest of the library calls these transitions.
+
+void thetas_changed(aqc_ws* ws, double* d_thetas) {
+    ws->d_thetas = d_thetas;
+    ws->coef_valid = true;
+    ws->fwd.u_valid = ws->inv.u_valid = ws->sweep.u_valid = false;
+    ws->ckpt_valid = false;   // ZW (and Z) belong to the previous thetas
+    ws->z_from_y = false;
+    ws->proj_y0_ready = false;
+}
+
+// family 3: ensure_umat has built the unitaries of `p` (the V^H and sweep plans share one launch)
+static void umat_state_after(aqc_ws* ws, const DevPlan& p) {
+    if (!p.v3) return;
+    if (&p == &ws->fwd) ws->fwd.u_valid = true;
+    else ws->inv.u_valid = ws->sweep.u_valid = true;
+}
+
+static int ensure_z_full(aqc_ws* ws, bool reader);
+
+// somebody other than the V^H / sweep pair below has written ALL of buffer `buf`
+static void touch_buf(aqc_ws* ws, int buf) {
+    ws->combo_valid[buf] = false;
+    if (buf == AQC_BUF_Z || buf == AQC_BUF_ZW) ws->ckpt_valid = false;
+    if (buf == AQC_BUF_Y || buf == AQC_BUF_Z) ws->z_from_y = false;
+    ws->proj_y0_ready = false;
+    if (buf == AQC_BUF_Z) ws->z_full = true;
+    if (buf == AQC_BUF_W) ws->w_clean = false;
+}
+
+int before_read(aqc_ws* ws, int buf) { return buf == AQC_BUF_Z ? ensure_z_full(ws, true) : 0; }
+
+int before_gather(aqc_ws* ws, int buf) {   // a partial Z covers the set it was computed for
+    return buf == AQC_BUF_Z && !ws->z_full && ws->z_key.gather != ws->gather_gen ? ensure_z_full(ws, true) : 0;
+}
+
+// A writer of some lanes of Z keeps the others: they must hold V^H y in full.  With one lane the write covers the whole buffer.
+int before_write(aqc_ws* ws, int buf, bool some_lanes) {
+    if (buf == AQC_BUF_ZW && ensure_z_full(ws, false)) return 1;   // the checkpoint goes away: complete Z while it is there
+    if (buf == AQC_BUF_Z && some_lanes && ws->batch > 1 && ensure_z_full(ws, true)) return 1;
+    touch_buf(ws, buf);
+    return 0;
+}
+
+void lhs_support_changed(aqc_ws* ws, int buf, std::vector<long long> elem, std::vector<double> coef) {
+    touch_buf(ws, buf);
+    ws->combo_valid[buf] = true;   // the buffer holds exactly the pattern d_combo_prev[buf] names
+    ++ws->supp_version[buf];
+    ws->combo_last_elem[buf].swap(elem);
+    ws->combo_last_coef[buf].swap(coef);
+}
+
+ListKey key_of(const aqc_ws* ws, int lhs_buf, bool gather) {
+    return ListKey{lhs_buf, lhs_buf >= 0 ? ws->supp_version[lhs_buf] : 0, gather ? ws->gather_gen : 0};
+}
+// While a graph is captured no list counts as built, and none is recorded: the replays rebuild it from whatever the device holds then.
+bool built_for(const aqc_ws* ws, const ListKey& slot, const ListKey& key) { return !ws->capturing && slot == key; }
+void record_key(const aqc_ws* ws, ListKey& slot, const ListKey& key) { slot = ws->capturing ? ListKey{} : key; }
+
+// A captured graph rebuilds the tile lists (d_sw_items, d_vd_items) and the projected route's virtual pattern (vm) from whatever the
+// device holds when it is replayed: none may be taken as built for any lhs buffer afterwards.
+void replay_state_after(aqc_ws* ws) { ws->sw_items_key = ws->vd_key = ws->proj.init_key = ListKey{}; }
+
 // family 3: the 16 x 16 unitaries of the plan's sub-stages for the coefficients in use
 // Jobs are laid out [V^H | sweep | V]: the objective+gradient path (V^H then the sweep) is built by one launch.
 int ensure_umat(aqc_ws* ws, DevPlan& p) {
@@ -34,38 +99,23 @@ int ensure_umat(aqc_ws* ws, DevPlan& p) {
     ProfScope ps(ws, AQC_K_COEF);
     if (&p == &ws->fwd) {
         HIP_OK(launch_ubuild(ws->d_ujobs + ninv + nsw, nfwd, ws->d_thetas, T, ws->batch, ws->stream));
-        p.u_valid = true;
     } else {
         // aqc_ws_eval (small batches): the thetas are read from its pinned staging buffer and land in HBM through this kernel
         HIP_OK(launch_ubuild(ws->d_ujobs, ninv + nsw, ws->theta_host ? ws->theta_host : ws->d_thetas, T, ws->batch, ws->stream,
                              ws->theta_host ? ws->d_thetas : nullptr));
         ws->theta_host = nullptr;
-        ws->inv.u_valid = ws->sweep.u_valid = true;
     }
+    umat_state_after(ws, p);
     return 0;
 }
 
-int run_coef(aqc_ws* ws) {
+int run_coef(aqc_ws* ws, double* d_thetas) {
     const Program& prog = ws->ctx->prog;
-    ws->fwd.u_valid = ws->inv.u_valid = ws->sweep.u_valid = false;
-    ws->coef_valid = true;
-    ws->ckpt_valid = false;   // ZW (and Z) belong to the previous thetas
-    ws->z_from_y = false;
-    ws->proj_y0_ready = false;
+    thetas_changed(ws, d_thetas);
     if (ws->fwd.v3 && ws->inv.v3 && ws->sweep.v3 && !ws->need_coef) return 0;   // the matrix-core path reads the thetas directly
     ProfScope ps(ws, AQC_K_COEF);
     HIP_OK(launch_coef(ws->d_thetas, ws->d_coef, prog.n, prog.num_blocks, prog.tpb, prog.tail_blocks, ws->batch, ws->stream));
     return 0;
-}
-
-// somebody other than the V^H / sweep pair below is about to write ALL of buffer `buf`
-void touch_buf(aqc_ws* ws, int buf) {
-    if (buf == AQC_BUF_ZW && !ws->z_full) (void)ensure_z_full(ws, false);   // the checkpoint goes away: complete Z while it is there
-    if (buf == AQC_BUF_Z || buf == AQC_BUF_ZW) ws->ckpt_valid = false;
-    if (buf == AQC_BUF_Y || buf == AQC_BUF_Z) ws->z_from_y = false;
-    ws->proj_y0_ready = false;
-    if (buf == AQC_BUF_Z) ws->z_full = true;
-    if (buf == AQC_BUF_W) ws->w_clean = false;
 }
 
 namespace {
@@ -155,6 +205,7 @@ static bool keeps_checkpoint(const aqc_ws* ws, bool inverse, int src_buf, int ds
     return inverse && ws->inv_mirrored && ws->inv.v3 && dst_buf == AQC_BUF_Z && src_buf != AQC_BUF_ZW && ws->inv.h_stages.size() >= 2;
 }
 void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {   // host-side state a V / V^H leaves (also after a graph replay)
+    umat_state_after(ws, inverse ? ws->inv : ws->fwd);
     touch_buf(ws, dst_buf);
     if (keeps_checkpoint(ws, inverse, src_buf, dst_buf)) { touch_buf(ws, AQC_BUF_ZW); ws->ckpt_valid = true; }
 }
@@ -162,8 +213,7 @@ void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {   /
 int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
     DevPlan& p = inverse ? ws->inv : ws->fwd;
     const Program& prog = ws->ctx->prog;
-    if (src_buf == AQC_BUF_Z && ensure_z_full(ws, true)) return 1;
-    if (dst_buf == AQC_BUF_ZW && ensure_z_full(ws, false)) return 1;   // the stages overwrite the checkpoint: complete Z from it first
+    if (before_read(ws, src_buf) || before_write(ws, dst_buf)) return 1;
     if (p.v3) {
         if (ensure_umat(ws, p)) return 1;
         const bool keep = keeps_checkpoint(ws, inverse, src_buf, dst_buf);
@@ -241,12 +291,12 @@ int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set) {   /
         HIP_OK(launch_apply3(p.ntiles, ws->batch, p.k, ws->stream, a));
     }
     const bool gather_only = support_in_gather_set && ws->gather_count > 0;
-    const unsigned long long key[3] = {gather_only ? ~0ull - 1 : (unsigned long long)x_buf, gather_only ? 0ull : ws->supp_version[x_buf], ws->gather_gen};
-    if (ws->capturing || key[0] != ws->vd_key[0] || key[1] != ws->vd_key[1] || key[2] != ws->vd_key[2]) {   // (a static list is built once)
+    const ListKey key = key_of(ws, gather_only ? ListKey::kGatherOnly : x_buf, true);
+    if (!built_for(ws, ws->vd_key, key)) {   // (a static list is built once)
         ProfScope ps(ws, AQC_K_MISC);
         HIP_OK(launch_tile_items(p.h_stages[m - 1], gather_only ? nullptr : ws->d_combo_prev[x_buf], 2, ws->gather_count > 0 ? ws->d_index : nullptr,
                                  ws->gather_count, ws->batch, ws->d_vd_items, ws->d_sw_counts + 2, nullptr, nullptr, nullptr, nullptr, ws->stream));
-        for (int i = 0; i < 3; ++i) ws->vd_key[i] = ws->capturing ? ~0ull : key[i];   // (a captured graph rebuilds it on every replay)
+        record_key(ws, ws->vd_key, key);
     }
     Stage3Args a = last_vdag_stage(ws);
     a.items = ws->d_vd_items;
@@ -263,11 +313,17 @@ int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set) {   /
 void vdag_restricted_state_after(aqc_ws* ws, int x_buf) {
     apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
     ws->z_full = false;
-    ws->z_gather_gen = ws->gather_gen;
-    ws->z_x_buf = x_buf;
-    ws->z_x_version = ws->supp_version[x_buf];
+    ws->z_key = key_of(ws, x_buf, true);   // (not a list a replay rebuilds: a replay states it again)
 }
-int ensure_z_full(aqc_ws* ws, bool reader) {
+// the objective's V^H by projection (run_vdag_projected, aqc_ws_project.cpp)
+void vdag_projected_state_after(aqc_ws* ws, int x_buf) {
+    vdag_restricted_state_after(ws, x_buf);
+    ws->z_key.gather = 0;       // Z covers the lhs tiles, not the gather set: a later gather completes it first
+    ws->ckpt_valid = false;     // ZW holds the lhs tiles of the checkpoint only
+    ws->z_from_y = true;
+    ws->proj_y0_ready = true;   // the virtual z holds Y_0 for the sweep of the same call
+}
+static int ensure_z_full(aqc_ws* ws, bool reader) {
     if (ws->z_full) return 0;
     if (ws->capturing) return fail("BUF_Z is partial inside a captured graph");
     if (ws->ckpt_valid && ws->inv.u_valid) {   // the last stage once more, over every tile (its inputs are all in ZW)
@@ -286,19 +342,36 @@ int ensure_z_full(aqc_ws* ws, bool reader) {
                 "run aqc_ws_apply(inverse) for the whole vector");
 }
 
-// A writer of some lanes of Z keeps the others: they must hold V^H y in full.  With one lane the write covers the whole buffer.
-int ensure_z_lanes(aqc_ws* ws) { return ws->batch > 1 ? ensure_z_full(ws, true) : 0; }
-
-// A captured graph rebuilds the last V^H stage's tile list (d_vd_items) and the projected route's virtual pattern (vm) from
-// whatever the device holds when it is replayed: neither may be taken as built for any lhs buffer afterwards.
-void replay_state_after(aqc_ws* ws) {
-    ws->vd_key[0] = ws->vd_key[1] = ws->vd_key[2] = ~0ull;
-    ws->proj.init_buf = -1;
-}
-
 void drop_graphs(aqc_ws* ws) {
     for (auto& kv : ws->graphs) (void)hipGraphExecDestroy(kv.second);
     ws->graphs.clear();
+}
+
+// A one-call evaluation as a HIP graph: enqueue() captured once per key (16 graphs, then all are dropped) and replayed.  A replay
+// enqueues nothing on the host: state_after() restates, by the same transitions, the record the enqueued calls would have left.
+int run_graph(aqc_ws* ws, const std::vector<long long>& key, const std::function<int()>& enqueue, const std::function<void()>& state_after) {
+    auto it = ws->graphs.find(key);
+    if (it == ws->graphs.end()) {
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        HIP_OK(hipStreamSynchronize(ws->stream));
+        HIP_OK(hipStreamBeginCapture(ws->stream, hipStreamCaptureModeThreadLocal));
+        ws->capturing = true;
+        const int rc = enqueue();
+        ws->capturing = false;
+        const hipError_t e = hipStreamEndCapture(ws->stream, &graph);
+        if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return 1; }
+        if (e != hipSuccess || !graph) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
+        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ei != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(ei));
+        if (ws->graphs.size() >= 16) drop_graphs(ws);
+        it = ws->graphs.emplace(key, exec).first;
+    }
+    state_after();
+    replay_state_after(ws);
+    HIP_OK(hipGraphLaunch(it->second, ws->stream));
+    return 0;
 }
 
 // ---- the sparse route --------------------------------------------------------------------------------------------
@@ -350,20 +423,20 @@ int sweep_sparse_prepare(aqc_ws* ws) {
         ws->d_vd_items = nullptr; ws->vd_items_cap = 0;
         HIP_OK(hipMalloc((void**)&ws->d_vd_items, sizeof(TileItem) * vd_need));
         ws->vd_items_cap = vd_need;
-        ws->vd_key[0] = ws->vd_key[1] = ws->vd_key[2] = ~0ull;
+        ws->vd_key = ListKey{};
     }
     if (!ws->w_clean) {
         HIP_OK(hipMemsetAsync(ws->bufs[AQC_BUF_W], 0, sizeof(double2) * (size_t)B * ws->lane_elems, ws->stream));
         HIP_OK(hipMemsetAsync(ws->d_sw_prev_tiles, 0xff, sizeof(int) * 2 * B, ws->stream));   // -1: W holds no tile of an earlier list
         ws->w_clean = true;
-        ws->sw_items_buf = -1;
+        ws->sw_items_key = ListKey{};
     }
     return 0;
 }
-void sweep_state_after(aqc_ws* ws, bool sparse, bool replayed) {   // host-side state a sweep leaves (also after a graph replay)
-    if (sparse) {
-        if (replayed) ws->sw_items_buf = -1;   // the replay rebuilt the list from whatever the support was: rebuild when asked next
-    } else {
+void sweep_state_after(aqc_ws* ws, bool sparse) {   // host-side state a sweep leaves (also after a graph replay)
+    umat_state_after(ws, ws->sweep);
+    ws->proj_y0_ready = false;                 // (consumed by the projected stages)
+    if (!sparse) {
         ws->w_clean = false;
         ws->ckpt_valid = false;                // the dense route works in place on (W, ZW)
     }
@@ -375,7 +448,6 @@ extern "C" {
 
 int aqc_ws_apply(aqc_ws* ws, int inverse, int src_buf, int dst_buf) {
     if (check_buf(ws, src_buf) || check_buf(ws, dst_buf)) return 1;
-    ws->combo_valid[dst_buf] = false;
     if (ensure_coef(ws)) return 1;
     HIP_OK(hipSetDevice(ws->device));
     return run_apply(ws, inverse != 0, src_buf, dst_buf);
@@ -399,13 +471,13 @@ namespace aqc {
 // rebuilt when the support changed; tiles of the previous list that the new one drops are zeroed in W
 int ensure_sweep_items(aqc_ws* ws, int x_buf) {
     const DevPlan& p = ws->sweep;
-    if (ws->capturing || ws->sw_items_buf != x_buf || ws->sw_items_version != ws->supp_version[x_buf]) {
+    const ListKey key = key_of(ws, x_buf, false);
+    if (!built_for(ws, ws->sw_items_key, key)) {
         ProfScope ps(ws, AQC_K_MISC);
         HIP_OK(launch_tile_items(p.h_stages[0], ws->d_combo_prev[x_buf], 2, nullptr, 0, ws->batch, ws->d_sw_items, ws->d_sw_counts,
                                  ws->d_sw_lane_parts, ws->d_sw_prev_tiles, ws->d_sw_clear, ws->d_sw_counts + 1, ws->stream));
         HIP_OK(launch_clear_tiles(p.h_stages[0], ws->bufs[AQC_BUF_W], ws->lane_elems, ws->d_sw_clear, ws->d_sw_counts + 1, 2 * ws->batch, ws->stream));
-        ws->sw_items_buf = x_buf;
-        ws->sw_items_version = ws->supp_version[x_buf];
+        record_key(ws, ws->sw_items_key, key);
         ws->sw_lists_built |= 1;
     }
     return 0;
@@ -437,8 +509,8 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
         if (first_stage_r_only) r_only_sub = p.h_stages[0].sub_begin + p.h_stages[0].nsubs - 1;
         // a partial Z covers the sparse route's reads when its tiles were chosen for this lhs state (or for a gather set the
         // state was picked from); anything else reads all of Z
-        if (!ws->z_full && !(sparse && ((support_in_gather_set && ws->z_gather_gen == ws->gather_gen) ||
-                                        (ws->z_x_buf == x_buf && ws->z_x_version == ws->supp_version[x_buf]))) && ensure_z_full(ws, true))
+        if (!ws->z_full && !(sparse && ((support_in_gather_set && ws->z_key.gather == ws->gather_gen) ||
+                                        (ws->z_key.buf == x_buf && ws->z_key.supp == ws->supp_version[x_buf]))) && ensure_z_full(ws, true))
             return 1;
         if (sparse) {
             if (!ws->capturing && sweep_sparse_prepare(ws)) return 1;
@@ -485,7 +557,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
 #endif
         }
         if (projected && run_projected_stages(ws)) return 1;
-        sweep_state_after(ws, sparse, false);
+        sweep_state_after(ws, sparse);
         ProfScope ps(ws, AQC_K_FINALIZE);
         RgradSecond vwalk;   // projected route: the virtual plan's walk in the same launch (two launches: 54 + 54 us at the headline, one: ~70)
         if (projected) vwalk = projected_rgrad_plan(ws);
@@ -505,9 +577,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
                                    1, prog.n, prog.tpb, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream, ws->mirror_grads));
         return 0;
     }
-    if (ensure_z_full(ws, true)) return 1;
-    touch_buf(ws, AQC_BUF_W);
-    touch_buf(ws, AQC_BUF_ZW);
+    if (before_read(ws, AQC_BUF_Z)) return 1;
     for (size_t s = 0; s < p.h_stages.size(); ++s) {
         StageArgs a;
         memset(&a, 0, sizeof a);
@@ -535,6 +605,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
         if (p.v2) HIP_OK(launch_sweep2(prog.entangler, p.ntiles, ws->batch, p.k, p.reg_bits, ws->stream, a));
         else HIP_OK(launch_sweep(prog.entangler, p.ntiles, ws->batch, ws->threads, p.k, ws->stream, a));
     }
+    sweep_state_after(ws, false);
     ProfScope ps(ws, AQC_K_FINALIZE);
     HIP_OK(launch_finalize(ws->d_partial, ws->d_theta_slots, ws->d_slot_ntiles, ws->d_grads, prog.num_thetas(), ws->nslots,
                            p.ntiles, prog.n, prog.tpb, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream, ws->mirror_grads));
@@ -604,17 +675,16 @@ int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered,
     const bool lazy = sparse && do_vdag && vdag_route_restricted(ws, x_buf);   // V^H only where this call (gather, sweep) reads it
     // ... and by two passes over y instead of its stages where the lhs state and the gather set allow (never with a riding gather)
     const bool by_projection = lazy && grads && !(gathered && zero_copy && ws->sweep.v3) && vdag_route_projected(ws, x_buf);
-    if (!do_vdag && (gathered || grads) && ensure_z_full(ws, true)) return 1;  // a partial Z left by an earlier call is completed here,
+    if (!do_vdag && (gathered || grads) && before_read(ws, AQC_BUF_Z)) return 1;  // a partial Z left by an earlier call is completed here,
                                                                               // outside whatever graph is captured below
     auto enqueue = [&]() -> int {   // everything between the host copy of the thetas and the final synchronisation
         if (thetas) {
-            ws->d_thetas = ws->d_thetas_own;
             // matrix-core path, small batch: no copy node -- the U builder (first kernel of V^H or of the sweep) reads the pinned
             // thetas over the bus and stores them to HBM for the gradient walk
             const bool direct_thetas = zero_copy && (do_vdag || grads) && ws->fwd.v3 && ws->inv.v3 && ws->sweep.v3 && !ws->need_coef &&
                                        (do_vdag ? ws->inv.v3 : true);
-            if (!direct_thetas) HIP_OK(hipMemcpyAsync(ws->d_thetas, pin_th, sizeof(double) * nth, hipMemcpyHostToDevice, ws->stream));
-            if (run_coef(ws)) return 1;
+            if (!direct_thetas) HIP_OK(hipMemcpyAsync(ws->d_thetas_own, pin_th, sizeof(double) * nth, hipMemcpyHostToDevice, ws->stream));
+            if (run_coef(ws, ws->d_thetas_own)) return 1;
             ws->theta_host = direct_thetas ? pin_th : nullptr;
         }
         if (do_vdag && (by_projection ? run_vdag_projected(ws, x_buf) : (lazy ? run_vdag_restricted(ws, x_buf) : run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)))) return 1;
@@ -642,36 +712,16 @@ int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered,
                                             (sparse ? 1 : 0) + (lazy ? 2 : 0) + (grads && sweep_skips_zero_w(ws, x_buf) ? 4 : 0) + (by_projection ? 8 : 0),
                                             (long long)(size_t)ws->d_combo_prev[x_buf],
                                             (long long)(size_t)ws->d_vd_items};
-        auto it = ws->graphs.find(key);
-        if (it == ws->graphs.end()) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            HIP_OK(hipStreamSynchronize(ws->stream));
-            HIP_OK(hipStreamBeginCapture(ws->stream, hipStreamCaptureModeThreadLocal));
-            ws->capturing = true;
-            const int rc = enqueue();
-            ws->capturing = false;
-            const hipError_t e = hipStreamEndCapture(ws->stream, &graph);
-            if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return 1; }
-            if (e != hipSuccess || !graph) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
-            const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (ei != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(ei));
-            if (ws->graphs.size() >= 16) drop_graphs(ws);
-            it = ws->graphs.emplace(key, exec).first;
-        }
-        ws->d_thetas = ws->d_thetas_own;   // host-side state that enqueue() would have set
-        ws->coef_valid = true;
-        ws->fwd.u_valid = false;
-        ws->inv.u_valid = ws->sweep.u_valid = (do_vdag || grads) && ws->inv.v3 && ws->sweep.v3;
-        ws->ckpt_valid = false;
-        if (do_vdag) {
-            if (lazy) vdag_restricted_state_after(ws, x_buf); else apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
-            if (by_projection) { ws->ckpt_valid = false; ws->z_from_y = true; ws->z_gather_gen = ~0ull; }   // (what run_vdag_projected leaves)
-        }
-        if (grads) sweep_state_after(ws, sparse, true);
-        replay_state_after(ws);
-        HIP_OK(hipGraphLaunch(it->second, ws->stream));
+        auto state_after = [&]() {
+            thetas_changed(ws, ws->d_thetas_own);
+            if (do_vdag) {
+                if (by_projection) vdag_projected_state_after(ws, x_buf);
+                else if (lazy) vdag_restricted_state_after(ws, x_buf);
+                else apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
+            }
+            if (grads) sweep_state_after(ws, sparse);
+        };
+        if (run_graph(ws, key, enqueue, state_after)) return 1;
     } else if (enqueue()) {
         return 1;
     }

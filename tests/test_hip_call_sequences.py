@@ -211,6 +211,37 @@ def test_refused_gather_setup_keeps_the_registered_set(monkeypatch):
     _run(monkeypatch, "cx12_t10", FORCED, ops)
 
 
+def test_coordinate_descent_chain_leaves_no_stale_checkpoint(monkeypatch):
+    """aqc_ws_extra.cpp aqc_ws_cd_sweep: beyond 6 qubits the sweep is a chain of gate launches that rewrites X and Z in place,
+    after its aqc_ws_apply has left V^H's checkpoint of the old Z in ZW.  A gradient from a basis state afterwards must read Z
+    as the chain left it: the sparse route (z of the second stage from the checkpoint) agrees with the dense one."""
+    from aqc_research_amd import _lib
+    from aqc_research_amd._lib import check, dptr
+    from aqc_research_amd.engine import HipContext, Workspace
+
+    n = 7
+    circ = _pc(n, "cx", 6)
+    ctx = HipContext(circ)
+    dim = 1 << n
+    rng = np.random.default_rng(706)
+    target, _ = np.linalg.qr(rng.standard_normal((dim, dim)) + 1j * rng.standard_normal((dim, dim)))
+    th0 = orc.rand_thetas(circ.num_thetas, rng)
+    out = {}
+    for cfg in ("forced", "dense_sweep"):
+        _configure(monkeypatch, CONFIGS[cfg])
+        ws = Workspace(ctx, batch=1, ncols=dim, tile_bits_apply=8, tile_bits_sweep=8)   # (two stages: V^H keeps a checkpoint)
+        assert not _lib.lib().aqc_ws_cd_fits_one_launch(ws.handle)
+        ws.upload(BUF_Y, target[None])
+        th, fobj = th0.copy(), np.zeros(1)
+        check(_lib.lib().aqc_ws_cd_sweep(ws.handle, dptr(th), dptr(fobj)))
+        ws.set_basis(BUF_X, [5])
+        ws.grad()
+        out[cfg] = (th, fobj, ws.get_grads()[0])
+        ws.close()
+    for a, b in zip(out["forced"], out["dense_sweep"]):
+        assert wm.maxdiff(a, b) < 1e-12
+
+
 # ---- random sequences ------------------------------------------------------------------------------------------------------
 
 CASES = [(s, seed) for s in ("cx12_t10", "cz13_t8", "trotter13_t10", "cp14_t9") for seed in (1, 2, 3)] + [("cx16_t9", 4), ("cx16_t9", 5)]
