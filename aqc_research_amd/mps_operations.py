@@ -146,9 +146,11 @@ def _svd(a: np.ndarray):
 
 def vector_to_canonical_mps(vec: np.ndarray, trunc_thr: float = _NO_TRUNCATION_THR) -> QiskitMPS:
     """Canonical Vidal form (Gamma, lambda) of a dense state by successive SVDs -- the form Aer hands the reference
-    (mps_operations.py:216-243): Schmidt values descending, at every bond the smallest ones dropped while the sum of their
-    squares stays below ``trunc_thr`` (none at the reference's no-truncation threshold 1e-16) and those below 1e-14 of the
-    largest, kept values renormalised."""
+    (mps_operations.py:216-243) -- truncated by the native engine's stated rule (aqc_mps_engine.cpp, gate_adjacent), so that a
+    ``DenseBackedMPS`` and the engine's own result describe the same state: at every bond, Schmidt values descending, those not
+    above 1e-14 of the largest go; then, for ``trunc_thr`` > 0, the smallest ones go while the sum of their squares stays
+    strictly below ``trunc_thr`` (an absolute weight, at least one value stays); the kept values are scaled by
+    sqrt(total / kept), so the tensors keep the norm of ``vec`` (normalised or not)."""
     vec = np.asarray(vec, dtype=np.complex128).ravel()
     n = int(round(np.log2(vec.size)))
     if vec.size != 1 << n or n < 2:
@@ -158,14 +160,18 @@ def vector_to_canonical_mps(vec: np.ndarray, trunc_thr: float = _NO_TRUNCATION_T
     for _ in range(n - 1):
         chi_l = rest.shape[0]
         u, sv, vh = _svd(rest.reshape(chi_l * 2, -1))
-        keep = int((sv > 1e-14 * sv[0]).sum())
-        total, dropped = float(np.sum(sv ** 2)), 0.0
-        # the rule of the native engine (mps_engine.py); the reference's "no truncation" threshold (1e-16) really means none:
-        # only numerically zero Schmidt values go, so that the tensors reproduce the state to ~1e-14
-        while trunc_thr > _NO_TRUNCATION_THR and keep > 1 and dropped + sv[keep - 1] ** 2 <= trunc_thr * total:
-            dropped += sv[keep - 1] ** 2
-            keep -= 1
-        u, sv, vh = u[:, :keep], sv[:keep] / np.linalg.norm(sv[:keep]), vh[:keep]
+        keep, total, dropped, kept = 0, 0.0, 0.0, 0.0
+        for j, s in enumerate(sv):
+            total += s * s
+            if s > 1e-14 * sv[0]:
+                keep = j + 1
+        if trunc_thr > 0.0:
+            while keep > 1 and dropped + sv[keep - 1] ** 2 < trunc_thr:
+                dropped += sv[keep - 1] ** 2
+                keep -= 1
+        for s in sv[:keep]:
+            kept += s * s
+        u, sv, vh = u[:, :keep], sv[:keep] * np.sqrt(total / kept), vh[:keep]
         a = u.reshape(chi_l, 2, keep)
         gam.append((np.ascontiguousarray(a[:, 0, :] / prev[:, None]), np.ascontiguousarray(a[:, 1, :] / prev[:, None])))
         lam.append(sv.copy())
@@ -194,8 +200,8 @@ class DenseBackedMPS(tuple):
         return self
 
     def _materialise(self) -> tuple:
-        if self._mps is None:
-            self._mps = vector_to_canonical_mps(self._vec, self._thr)
+        if self._mps is None:   # (exact: no truncation was asked for, the tensors stand for the dense state itself)
+            self._mps = vector_to_canonical_mps(self._vec, 0.0 if self.exact else self._thr)
         return self._mps
 
     @property
