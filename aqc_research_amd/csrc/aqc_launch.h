@@ -302,6 +302,10 @@ struct LaneSteps { LaneGate1 g[3]; double gh[3][8]; int count, pad; };
 hipError_t launch_lanes_grad_step(const LaneMps& w, const LaneMps& z, int q, const LaneSteps& steps, const double* thetas, int T, const void* env_l,
                                   size_t l_stride, const void* env_r, size_t r_stride, void* scratch, void* vals, int nvals, int slot, int lanes, hipStream_t s);
 hipError_t launch_lanes_basis(const LaneMps& m, const unsigned char* bits /* [lanes][n] */, int lanes, hipStream_t s);   // product basis states
+// vals[lane][slot0 + k] = <bank_k|vh_lane> for k < count and the first `lanes` lanes, one workgroup per (k, lane), the environments in LDS sized
+// for bonds <= bond_hint (a lane beyond raises kLaneLdsShort in status[lane])
+hipError_t launch_lanes_bank_dot(const LaneMps& bank, int count, const LaneMps& vh, int lanes, void* vals, int nvals, int slot0, int* status,
+                                 int bond_hint, hipStream_t s);
 hipError_t launch_lanes_env_init(void* env_l, size_t l_stride, void* env_r_last, size_t r_stride, int lanes, hipStream_t s);
 // environment steps of <(ops) w|z> for small bonds, one launch per site (aqc_svd.hip); gh8: 2x2 (row-major, 4 c128) applied to z's site or null
 bool mps_env_fits_small(int xa, int ua, int yb, int vb);

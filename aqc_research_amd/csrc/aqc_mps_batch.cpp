@@ -67,8 +67,9 @@ struct aqc_mpsb {
     int device = 0, n = 0, L = 0;
     hipStream_t st = nullptr;
     Lanes target, lhs, vh, w, z;
+    Lanes bank;                  // K lhs states shared by all lanes (aqc_mpsb_set_bank): amplitudes <bank_k|vh_l> of aqc_mpsb_vh_bank
     std::map<std::string, Schedule> schedules;
-    bool have_target = false, have_lhs = false;
+    bool have_target = false, have_lhs = false, have_bank = false;
     double* thetas = nullptr;    // [L][T] on the device
     double* h_thetas = nullptr;  // pinned staging of the same
     int T_cap = 0;
@@ -108,7 +109,7 @@ void destroy(aqc_mpsb* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    for (Lanes* s : {&b->target, &b->lhs, &b->vh, &b->w, &b->z}) s->release();
+    for (Lanes* s : {&b->target, &b->lhs, &b->vh, &b->w, &b->z, &b->bank}) s->release();
     for (auto& kv : b->schedules) { if (kv.second.ops1) (void)hipFree(kv.second.ops1); if (kv.second.ops2) (void)hipFree(kv.second.ops2); }
     for (void* p : {(void*)b->thetas, (void*)b->status, (void*)b->env_l, (void*)b->env_r, (void*)b->e0, (void*)b->e1, (void*)b->vals, (void*)b->bits,
                     (void*)b->jstats})
@@ -435,9 +436,9 @@ int gradient_all(aqc_mpsb* b, const aqc_circuit* c, int T, double trunc_thr, int
     return 0;
 }
 
-int load_lanes(aqc_mpsb* b, Lanes& dst, aqc_mps* const* src, int shared) {
+int load_lanes(aqc_mpsb* b, Lanes& dst, aqc_mps* const* src, int shared) {   // dst.L states (the lanes', or the bank's K)
     if (!src) return failf("null MPS list");
-    const int n = b->n, L = b->L, distinct = shared ? 1 : L;
+    const int n = b->n, L = dst.L, distinct = shared ? 1 : L;
     std::vector<int> dims_all((size_t)L * (n + 1));
     std::vector<double> disc(L);
     dst.max_dim_in = 1;
@@ -556,6 +557,22 @@ int enqueue_vh(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half, int num_a
     const M2 eye = {{1.0, 0.0, 0.0, 1.0}};
     const M2* g = &eye;
     return dot_all(b, 0, 1, &q, &g);
+}
+
+// The same for a bank of lhs states (aqc_mpsb_vh_bank): vh as above, then amps[l][k] = <bank_k|vh_l> in slots k of vals, one launch for all
+// (k, active lane) pairs.  (w, z) and the environments are left alone: the gradient phase starts them itself.
+int enqueue_vh_bank(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half) {
+    const int L = b->L;
+    HIP_OK(hipMemsetAsync(b->status, 0, sizeof(int) * 2 * (size_t)L, b->st));
+    if (clone(b, b->target, b->vh)) return 1;
+    b->active = half ? L / 2 : L;
+    const int rc = apply_circuit_all(b, b->vh, circ, T, true, b->cur_trunc, b->cur_max_bond);
+    b->active = L;
+    if (rc) return 1;
+    if (half && replicate_half(b, b->vh)) return 1;
+    const int h = std::max(b->hint, hint_for(b->bank.max_dim_in, 0));
+    HIP_OK(launch_lanes_bank_dot(b->bank.dev, b->bank.L, b->vh.dev, half ? L / 2 : L, b->vals, b->nvals, 0, b->status, h, b->st));
+    return 0;
 }
 
 // results of the enqueued work -> pinned host memory; 0 ok, 2 = a lane outgrew the launch size (the caller repeats at full size), 1 error
@@ -788,6 +805,52 @@ int aqc_mpsb_vh(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, doub
     cd* out = reinterpret_cast<cd*>(amps);
     for (int l = 0; l < L; ++l) {
         for (int k = 0; k < num_amps; ++k) out[(size_t)l * num_amps + k] = r.vals[(size_t)l * b->nvals + k];
+        if (discarded_out) discarded_out[l] = r.disc[l];
+        if (max_bond_out) max_bond_out[l] = r.max_dim(l, b->n);
+    }
+    b->vh_ready = true;
+    return 0;
+}
+
+/* K lhs states shared by all lanes (the states S|0>, S X_i|0> of a general state preparation, objective_base.py:345-435), bonds <= 32 */
+int aqc_mpsb_set_bank(aqc_mpsb* b, aqc_mps* const* states, int count) {
+    if (!b || !states) return failf("null argument");
+    if (count < 1 || count > 32767) return failf("bank: count out of range");
+    HIP_OK(hipSetDevice(b->device));
+    b->have_bank = false;
+    if (b->bank.L != count) {
+        HIP_OK(hipStreamSynchronize(b->st));
+        b->bank.release();
+        if (b->bank.alloc(b->n, count)) { b->bank.L = 0; return 1; }
+    }
+    if (load_lanes(b, b->bank, states, 0)) return 1;
+    b->have_bank = true;
+    return 0;
+}
+
+/* Phase 1 with the bank as the lhs side: vh of every lane as aqc_mpsb_vh, and amps[lane][k] = <bank_k|vh_l> (num_amps = the bank's K),
+ * all read back with the status words in one transfer.  half != 0: the overlaps of lanes [L/2, L) are those of lanes [0, L/2). */
+int aqc_mpsb_vh_bank(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double trunc_thr, int max_bond, int half, int num_amps,
+                     double* amps, double* discarded_out, int32_t* max_bond_out) {
+    if (!b || !circ || !thetas || !amps) return failf("null argument");
+    if (!b->have_target || !b->have_bank) return failf("set the targets and the bank of the lanes first (aqc_mpsb_set_bank)");
+    if (num_amps != b->bank.L) return failf("num_amps: the bank holds %d states", b->bank.L);
+    if (half && (b->L & 1)) return failf("half: the batch needs an even number of lanes");
+    int T = 0;
+    if (begin(b, circ, thetas, trunc_thr, max_bond, num_amps, &T)) return 1;
+    const int L = b->L;
+    for (int attempt = 0;; ++attempt) {
+        if (enqueue_vh_bank(b, circ, T, half != 0)) return 1;
+        const int rc = finish(b, attempt == 0, &b->peak_vh);
+        if (rc == 2) continue;
+        if (rc) return 1;
+        break;
+    }
+    const Readback r = readback(b);
+    cd* out = reinterpret_cast<cd*>(amps);
+    for (int l = 0; l < L; ++l) {
+        const int src = half && l >= L / 2 ? l - L / 2 : l;
+        for (int k = 0; k < num_amps; ++k) out[(size_t)l * num_amps + k] = r.vals[(size_t)src * b->nvals + k];
         if (discarded_out) discarded_out[l] = r.disc[l];
         if (max_bond_out) max_bond_out[l] = r.max_dim(l, b->n);
     }

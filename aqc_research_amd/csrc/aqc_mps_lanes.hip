@@ -291,6 +291,37 @@ __global__ __launch_bounds__(256) void lanes_grad_step_kernel(LaneMps w, LaneMps
         __syncthreads();   // (sr / si and the scratch are reused by the next parameter)
     }
 }
+// Overlaps of a bank of K lhs states with the vh of every lane: vals[lane][slot0 + k] = <bank_k|vh_lane>, one workgroup per (k, lane)
+// (blockIdx.x = k, blockIdx.y = lane).  The workgroup walks the sites 0..n-1 with the left environment in LDS, ping-ponging between two
+// buffers of env_elems complex after the step's own [xa][vb] intermediate (mps_env_left_body keeps that at the base of the dynamic LDS);
+// the last step leaves the 1 x 1 overlap.  Every sum runs in a fixed order: the result does not depend on the launch.  A lane whose
+// bonds do not fit the launch's sizing (env_elems = hint^2) raises kLaneLdsShort and the host repeats at full size (32 x 32).
+// The states S X_i|0> of a general preparation S share no environments, so each needs its whole walk: this is n + 1 of
+// aqc_mps_dot's transfer-matrix chains (~4n dependent launches each) in one launch -- the hs[i] = mps_dot(state_i, V^H|target>) of the
+// reference's MpsStateHandler.state_dot_vector (objective_base.py:406-409) for every state at once.
+__global__ __launch_bounds__(256) void lanes_bank_dot_kernel(LaneMps bank, LaneMps vh, cplx* __restrict__ vals, int nvals, int slot0,
+                                                             int* __restrict__ status, unsigned env_elems) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int k = blockIdx.x, l = blockIdx.y, n = vh.n, tid = threadIdx.x;
+    const int* da = bank.dims + (size_t)k * (n + 1);
+    const int* db = vh.dims + (size_t)l * (n + 1);
+    int too_big = 0;   // the step at site q holds [da[q]][db[q]] (in), [da[q]][db[q + 1]] (intermediate), [da[q + 1]][db[q + 1]] (out)
+    for (int q = tid; q <= n; q += 256)
+        too_big |= (unsigned)(da[q] * db[q]) > env_elems || (q < n && (unsigned)(da[q] * db[q + 1]) > env_elems);
+    if (__syncthreads_or(too_big)) {
+        if (tid == 0) atomicOr(&status[l], kLaneLdsShort);
+        return;
+    }
+    cplx* env[2] = {reinterpret_cast<cplx*>(smem) + env_elems, reinterpret_cast<cplx*>(smem) + 2 * (size_t)env_elems};
+    if (tid == 0) env[0][0] = make_double2(1.0, 0.0);
+    __syncthreads();
+    const Gate4c none{};
+    for (int p = 0; p < n; ++p)   // (the body ends with a barrier: its output is visible to the whole workgroup)
+        mps_env_left_body(env[p & 1], static_cast<const cplx*>(bank.T) + ((size_t)k * n + p) * kLaneSite,
+                          static_cast<const cplx*>(vh.T) + ((size_t)l * n + p) * kLaneSite, da[p], da[p + 1], db[p], db[p + 1], 0, none,
+                          env[(p + 1) & 1]);
+    if (tid == 0) vals[(size_t)l * nvals + slot0 + k] = env[n & 1][0];
+}
 // every lane <- the computational-basis state bits[lane][site]: site tensors [2][1][1], Schmidt values 1, bond dimensions 1
 __global__ void lanes_basis_kernel(LaneMps m, const unsigned char* __restrict__ bits, int lanes) {
     const int l = blockIdx.x, n = m.n, nb = n > 1 ? n - 1 : 1;
@@ -366,6 +397,14 @@ hipError_t launch_lanes_grad_step(const LaneMps& w, const LaneMps& z, int q, con
     lanes_grad_step_kernel<<<lanes, 256, sizeof(cplx) * kLaneEnv, s>>>(w, z, q, steps, thetas, T, static_cast<const cplx*>(env_l), l_stride,
                                                                         static_cast<const cplx*>(env_r), r_stride, static_cast<cplx*>(scratch),
                                                                         static_cast<cplx*>(vals), nvals, slot);
+    return hipGetLastError();
+}
+hipError_t launch_lanes_bank_dot(const LaneMps& bank, int count, const LaneMps& vh, int lanes, void* vals, int nvals, int slot0, int* status,
+                                 int bond_hint, hipStream_t s) {
+    const int h = std::min(kLaneCap, std::max(1, bond_hint));
+    const unsigned env_elems = (unsigned)(h * h);
+    lanes_bank_dot_kernel<<<dim3(count, lanes), 256, 3 * env_elems * sizeof(cplx), s>>>(bank, vh, static_cast<cplx*>(vals), nvals, slot0, status,
+                                                                                          env_elems);
     return hipGetLastError();
 }
 hipError_t launch_lanes_basis(const LaneMps& m, const unsigned char* bits, int lanes, hipStream_t s) {

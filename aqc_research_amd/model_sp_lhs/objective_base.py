@@ -155,6 +155,37 @@ def _circuit_gate_matrix(name: str, params) -> np.ndarray:
     return two
 
 
+def circuit_gate_list(qc, num_qubits: int):
+    """(gates, global phase) of a general state-preparation circuit: ``gates`` is the list of ``(matrix, qubits)`` in program order, a
+    2 x 2 matrix with one qubit or a 4 x 4 one (``_circuit_gate_matrix``'s index convention) with two; identities and barriers are
+    skipped.  The one parser behind ``GenericStateHandler`` (dense columns) and ``MpsStateHandler`` (device MPS); the circuit is duck-typed
+    as described there.  Unknown gates raise ``NotImplementedError``, unresolvable qubits and wrong arities ``ValueError``."""
+    n = int(num_qubits)
+    if getattr(qc, "num_qubits", n) != n:
+        raise ValueError("state_prep_func returned a circuit on a different number of qubits")
+    out = []
+    for ins in qc.data:
+        op, qubits = getattr(ins, "operation", None), getattr(ins, "qubits", None)
+        if op is None:
+            op, qubits = ins[0], ins[1]
+        name = str(getattr(op, "name", "")).lower()
+        if name in ("id", "i", "barrier", "delay"):
+            continue
+        idx = []
+        for q in qubits:
+            if not isinstance(q, (int, np.integer)):
+                find = getattr(qc, "find_bit", None)
+                q = find(q).index if find is not None else getattr(q, "index", getattr(q, "_index", None))
+            if q is None or not 0 <= int(q) < n:
+                raise ValueError("state_prep_func: cannot resolve a qubit index of the circuit")
+            idx.append(int(q))
+        g = _circuit_gate_matrix(name, getattr(op, "params", ()))
+        if not ((g.shape == (2, 2) and len(idx) == 1) or (g.shape == (4, 4) and len(idx) == 2)):
+            raise ValueError(f"gate '{name}' on {len(idx)} qubit(s)")
+        out.append((g, tuple(idx)))
+    return out, float(getattr(qc, "global_phase", 0.0) or 0.0)
+
+
 class GenericStateHandler(DenseStateHandler):
     """The reference's ``GenericStateHandler`` (objective_base.py:258-342): the states ``S|0>`` and ``S X_i|0>`` of a GENERAL
     state-preparation circuit S, built explicitly.  Qiskit is absent here, so S is any duck-typed circuit -- ``num_qubits``
@@ -175,34 +206,108 @@ class GenericStateHandler(DenseStateHandler):
             cols[1 << (i - 1), i] = 1.0
         qc = state_prep_func(n) if callable(state_prep_func) else state_prep_func
         if qc is not None:
-            if getattr(qc, "num_qubits", n) != n:
-                raise ValueError("state_prep_func returned a circuit on a different number of qubits")
-            for ins in qc.data:
-                op, qubits = getattr(ins, "operation", None), getattr(ins, "qubits", None)
-                if op is None:
-                    op, qubits = ins[0], ins[1]
-                name = str(getattr(op, "name", "")).lower()
-                if name in ("id", "i", "barrier", "delay"):
-                    continue
-                idx = []
-                for q in qubits:
-                    if not isinstance(q, (int, np.integer)):
-                        find = getattr(qc, "find_bit", None)
-                        q = find(q).index if find is not None else getattr(q, "index", getattr(q, "_index", None))
-                    if q is None or not 0 <= int(q) < n:
-                        raise ValueError("state_prep_func: cannot resolve a qubit index of the circuit")
-                    idx.append(int(q))
-                g = _circuit_gate_matrix(name, getattr(op, "params", ()))
-                if g.shape == (2, 2) and len(idx) == 1:
+            glist, phase = circuit_gate_list(qc, n)
+            for g, idx in glist:
+                if len(idx) == 1:
                     gates.apply_1q(g, idx[0], cols, cols)
-                elif g.shape == (4, 4) and len(idx) == 2:
-                    gates.apply_2q(g, idx[0], idx[1], cols, cols)
                 else:
-                    raise ValueError(f"gate '{name}' on {len(idx)} qubit(s)")
-            phase = float(getattr(qc, "global_phase", 0.0) or 0.0)
+                    gates.apply_2q(g, idx[0], idx[1], cols, cols)
             if phase:
                 cols *= np.exp(1j * phase)
         super().__init__(np.ascontiguousarray(cols.T))
+
+
+class MpsStateHandler:
+    """The reference's ``MpsStateHandler`` (objective_base.py:345-435): the n + 1 states ``S|0>`` and ``S X_i|0>`` of a general
+    state-preparation circuit S as matrix-product states, for registers beyond dense reach.  Each state is built on the device
+    (``DeviceMPS``) from the basis state X_i|0> -- the flip BEFORE S, as the reference composes it (:383-389) -- by S's gates one by one
+    (``gate1`` / ``gate2`` on any pair, swaps for non-neighbours) at the reference's no-truncation threshold; S's global phase goes onto
+    site 0.  Gate set, qubit resolution and errors are those of ``GenericStateHandler`` (``circuit_gate_list``).  ``device_state(i)``
+    is what the native MPS objective walks; ``init_state`` exports the Qiskit-format tuple on first request."""
+
+    _NO_TRUNCATION_THR = 1e-16   # mps_operations.py of the reference: the states are assumed low-entangled
+
+    def __init__(self, num_qubits: int, max_flips: int, state_prep_func=None, verbose: bool = False, device: Optional[int] = None):
+        from ..mps_engine import DeviceMPS
+
+        if not (isinstance(num_qubits, (int, np.integer)) and num_qubits >= 2):
+            raise ValueError("num_qubits must be an integer >= 2")
+        if max_flips > 1:
+            raise ValueError("expects 'max_flips <= 1' to save memory & time")    # objective_base.py:379-380
+        n = int(num_qubits)
+        qc = state_prep_func(n) if callable(state_prep_func) else state_prep_func
+        glist, phase = circuit_gate_list(qc, n) if qc is not None else ([], 0.0)
+        self._n = n
+        self._states = []
+        self._exported = {}
+        for i in range(n + 1):
+            m = DeviceMPS.basis_state(n, 0 if i == 0 else 1 << (i - 1), device=device)
+            for g, idx in glist:
+                if len(idx) == 1:
+                    m.gate1(g, idx[0])
+                else:
+                    m.gate2(g, idx[0], idx[1], self._NO_TRUNCATION_THR)
+            if phase:
+                m.gate1(np.exp(1j * phase) * np.eye(2, dtype=np.complex128), 0)
+            self._states.append(m)
+
+    @property
+    def num_states(self) -> int:
+        return len(self._states)
+
+    @property
+    def device_states(self) -> list:
+        """The states on the device, S|0> first (read-only: the objective hands them to the engine as they are)."""
+        return list(self._states)
+
+    def device_state(self, state_no: int):
+        return self._states[state_no]
+
+    @property
+    def max_bond(self) -> int:
+        """Largest bond dimension over all states."""
+        return max(int(m.bond_dims.max()) for m in self._states)
+
+    def init_state(self, state_no: int):
+        """The state as a Qiskit-format MPS tuple (exported once; must not be modified)."""
+        if not 0 <= state_no < self.num_states:
+            raise IndexError("state number out of range")
+        if state_no not in self._exported:
+            self._exported[state_no] = self._states[state_no].to_qiskit()
+        return self._exported[state_no]
+
+    @property
+    def state0(self):
+        return self.init_state(0)
+
+    def state_dot_vector(self, state_no: int, vec) -> np.complex128:
+        """<state|vec> for a Qiskit-format MPS or a ``DeviceMPS`` (objective_base.py:406-409)."""
+        from .. import _lib
+        from ..mps_engine import DeviceMPS
+
+        if isinstance(vec, DeviceMPS):
+            return self._states[state_no].dot(vec)
+        other = DeviceMPS.from_qiskit(vec, device=int(_lib.lib().aqc_mps_device(self._states[state_no].handle)))
+        try:
+            return self._states[state_no].dot(other)
+        finally:
+            other.close()
+
+    def init_composite_state_no_zero(self, _):
+        raise NotImplementedError()
+
+    def init_composite_state(self, _):
+        raise NotImplementedError()
+
+    def composite_state_dot_vector_no_zero(self, _, __):
+        raise NotImplementedError()
+
+    def composite_state_dot_vector(self, _, __):
+        raise NotImplementedError()
+
+    def close(self) -> None:
+        for m in self._states:
+            m.close()
 
 
 class SpService:
@@ -281,7 +386,8 @@ class SpLHSObjectiveBase:
     ``state_prep_func(num_qubits)`` may return an ``int`` (bit mask of a computational-basis
     preparation, e.g. the Neel state), a circuit that only flips qubits (the reference's ``neel_init_state`` & co.,
     duck-typed: ``basis_mask_of_circuit``), a dense (num_states, 2^n) array of prepared states, or a general (duck-typed)
-    circuit over the gate set of ``GenericStateHandler``, whose states are then built explicitly on the device."""
+    circuit over the gate set of ``GenericStateHandler``, whose states are then built explicitly on the device: as dense
+    columns within dense reach, as device MPS (``MpsStateHandler``) on the native MPS route."""
 
     def __init__(self, user_parameters: dict, circuit: ParametricCircuit, use_mps: bool = False, verbose: bool = False):
         if not isinstance(user_parameters, dict):
@@ -306,14 +412,17 @@ class SpLHSObjectiveBase:
             try:            # X gates only: the flip states stay one-hot (ThinStateHandler, objective_base.py:42-255)
                 self._state_handler = ThinStateHandler(n, max_flips, verbose, base_index=basis_mask_of_circuit(prepared, n))
             except NotImplementedError:   # a general preparation: explicit states (GenericStateHandler, :258-342)
-                if self._use_mps:
-                    from ..mps_dot_objective import use_dense
+                from ..mps_dot_objective import use_dense
 
-                    if not use_dense(n, float(user_parameters.get("trunc_thr", 1e-16))):
+                if self._use_mps and not use_dense(n, float(user_parameters.get("trunc_thr", 1e-16))):
+                    if user_parameters.get("workspace", None) is not None:
                         raise NotImplementedError(
-                            "a general state-preparation circuit on the native MPS route (registers beyond dense reach: the reference's "
-                            "MpsStateHandler, objective_base.py:345-435) is not built; circuits of X gates (basis preparations) are")
-                self._state_handler = GenericStateHandler(n, max_flips, prepared, verbose)
+                            "a general state-preparation circuit on the native MPS route takes a private objective, not a lane "
+                            "of a lockstep batch (user_parameters['workspace'])")
+                    # registers beyond dense reach: the states as device MPS (the reference's MpsStateHandler, :345-435, :681-683)
+                    self._state_handler = MpsStateHandler(n, max_flips, prepared, verbose, device=user_parameters.get("device"))
+                else:
+                    self._state_handler = GenericStateHandler(n, max_flips, prepared, verbose)
         else:
             raise NotImplementedError(
                 "state_prep_func must return a basis-state bit mask (int) or a dense array of states; "

@@ -498,7 +498,7 @@ class LockstepLanes:
         h = c_void_p()
         check(_lib.lib().aqc_mpsb_create(_default_device() if device is None else int(device), int(num_qubits), int(lanes), byref(h)))
         self.handle, self.num_qubits, self.lanes = h, int(num_qubits), int(lanes)
-        self._targets = self._lhs = None
+        self._targets = self._lhs = self._bank = None
 
     def gate2_stats(self, enable: Optional[bool] = None, reset: bool = False) -> dict:
         """Work and time of the truncated 2-qubit gates (``aqc_mpsb_gate2_stats``): fp64 flops of the Jacobi rotations that ran, SVDs,
@@ -582,6 +582,40 @@ class LockstepLanes:
         del keep
         return (amps, disc, bonds) if details else amps
 
+    def set_bank(self, states) -> "LockstepLanes":
+        """A bank of K lhs states shared by all lanes (``aqc_mpsb_set_bank``; bonds <= 32): the states S|0>, S X_i|0> of a general
+        state preparation, whose amplitudes ``apply_vh_bank`` returns.  Unchanged states since the last call (``DeviceMPS.version``)
+        are not copied again."""
+        lst = list(states)
+        if not lst:
+            raise ValueError("the bank needs at least one state")
+        stamp = [(m.serial, m.version) for m in lst]
+        if self._bank != stamp:
+            self._bank = None
+            arr = (c_void_p * len(lst))(*[m.handle for m in lst])
+            check(_lib.lib().aqc_mpsb_set_bank(self.handle, arr, len(lst)))
+            self._bank = stamp
+        return self
+
+    def apply_vh_bank(self, circ, thetas, *, trunc_thr: float = 0.0, max_bond: int = 0, half: bool = False, details: bool = False):
+        """``apply_vh`` with the bank as the lhs side: vh_l = V(thetas[l])^H|target_l> stays in the lanes; returns amps[lanes][K] with
+        amps[l][k] = <bank_k|vh_l> (all K x lanes overlaps in one launch, read back with V^H's results).  ``gradient`` continues from
+        here with whatever lhs states are set then."""
+        if not self._bank:
+            raise RuntimeError("aqc_hip: set the bank of the lanes first (set_bank)")
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        if th.shape != (self.lanes, circ.num_thetas) or circ.num_qubits != self.num_qubits:
+            raise ValueError("thetas: expects shape (lanes, circ.num_thetas) on a circuit of the lanes' size")
+        desc, keep = _describe(circ)
+        na = len(self._bank)
+        amps = np.zeros((self.lanes, na), dtype=np.complex128)
+        disc = np.zeros(self.lanes, dtype=np.float64)
+        bonds = np.zeros(self.lanes, dtype=np.int32)
+        check(_lib.lib().aqc_mpsb_vh_bank(self.handle, byref(desc), dptr(th), float(trunc_thr), int(max_bond), int(bool(half)), na, dptr(amps),
+                                          dptr(disc), bonds.ctypes.data_as(POINTER(c_int32))))
+        del keep
+        return (amps, disc, bonds) if details else amps
+
     def apply_circuit(self, circ, thetas, *, inverse: bool = False, trunc_thr: float = 0.0, max_bond: int = 0, details: bool = False):
         """The lanes' working state <- V(thetas[l])|target_l> (or V^H with ``inverse``): ``v_mul_mps`` / ``v_dagger_mul_mps`` for every lane,
         the gates of a circuit layer in one launch.  ``export(lane)`` hands a result out; no lhs states needed."""
@@ -617,7 +651,7 @@ class LockstepLanes:
         if getattr(self, "handle", None):
             _lib.lib().aqc_mpsb_destroy(self.handle)
             self.handle = None
-            self._targets = self._lhs = None
+            self._targets = self._lhs = self._bank = None
 
     def __del__(self):
         try:

@@ -279,6 +279,14 @@ int aqc_mpsb_export(aqc_mpsb* b, int lane, aqc_mps** out);
 int aqc_mpsb_vh(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double trunc_thr, int max_bond, int half, int num_amps,
                 double* amps /* [lanes][num_amps] c128 */, double* discarded /* [lanes] or NULL */, int32_t* max_bond_out /* or NULL */);
 int aqc_mpsb_grad(aqc_mpsb* b, const aqc_circuit* circ, int block_from, int block_to, int front_layer, double* grad /* [lanes][T] c128 */);
+/* Phase 1 against a bank of K general lhs states shared by all lanes -- the states S|0>, S X_i|0> of a general state-preparation circuit
+ * S (the reference's MpsStateHandler, objective_base.py:345-435, whose state_dot_vector it replaces): aqc_mpsb_set_bank copies the K
+ * states (bonds <= 32, count = K) into the batch; aqc_mpsb_vh_bank takes the arguments of aqc_mpsb_vh with num_amps = K and returns
+ * amps[lane][k] = <bank_k|vh_l>, one launch for all (k, lane) pairs, read back with V^H's results in one transfer.  Phase 2
+ * (aqc_mpsb_grad) follows from whatever lhs states are set then. */
+int aqc_mpsb_set_bank(aqc_mpsb* b, aqc_mps* const* states, int count);
+int aqc_mpsb_vh_bank(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double trunc_thr, int max_bond, int half, int num_amps,
+                     double* amps /* [lanes][num_amps] c128 */, double* discarded /* [lanes] or NULL */, int32_t* max_bond_out /* or NULL */);
 /* fast_dot_gradient with vh_phi formed by the caller, as the reference's function takes it (mps_dot_objective.py:41): the states given to
  * aqc_mpsb_set_targets ARE vh_phi_l = V^H|phi_l>, those given to aqc_mpsb_set_lhs the lvec_l */
 int aqc_mpsb_gradient_of(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double trunc_thr, int max_bond, int block_from,
