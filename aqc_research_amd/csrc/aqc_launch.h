@@ -7,6 +7,7 @@
 #include <cstddef>
 
 #include "aqc_device.h"
+#include "aqc_mps_walk.h"
 
 namespace aqc {
 
@@ -274,11 +275,7 @@ constexpr int kLaneSite = 2 * kLaneCap * kLaneCap;  // complex elements reserved
 constexpr int kLaneEnv = kLaneCap * kLaneCap;       // ... per environment
 constexpr int kLaneNoConv = 1, kLaneOverflow = 2, kLaneZero = 4, kLaneLdsShort = 8;   // status bits of a lane
 struct LaneMps { void* T; double* lam; int* dims; double* discarded; int n, pad; };   // T[L][n][kLaneSite], lam[L][max(n-1,1)][kLaneCap], dims[L][n+1]
-struct LaneRot { int kind /* 0 none, 1 rz, 2 ry, 3 rx */, idx; double scale; };        // angle = scale * thetas[lane][idx], or = scale when idx < 0
-struct LaneGate1 { LaneRot r[3]; };                                                    // the product r[0] r[1] r[2]
-struct LaneGate2 { int kind /* 0 swap, 1 cx, 2 cz, 3 cp */, idx, flip, pad; double scale; };   // cp angle = scale * thetas[lane][idx]; flip: control on site q + 1
-struct LaneOp1 { int q, pad; LaneGate1 g; };   // a 1-qubit gate on site q
-struct LaneOp2 { int q, pad; LaneGate2 g; };   // a 2-qubit gate on the sites (q, q + 1)
+// (gate notation LaneRot / LaneGate1 / LaneGate2 / LaneOp1 / LaneOp2: aqc_mps_walk.h)
 // One gate (`one`), or -- ops != null -- `nops` gates on pairwise disjoint sites from a table in device memory, all in one launch (gates of
 // one layer of the circuit touch disjoint tensors and bond dimensions: any order, and so also "at once", gives the same bits).
 // b / m2 (may be null): a second state that takes the same gates.

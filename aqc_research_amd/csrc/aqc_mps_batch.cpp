@@ -126,10 +126,6 @@ int clone(aqc_mpsb* b, const Lanes& src, Lanes& dst) {
     return 0;
 }
 
-LaneRot rot(int kind, int idx, double scale) { return LaneRot{kind, idx, scale}; }
-LaneGate1 g1(LaneRot a, LaneRot b = LaneRot{0, -1, 0.0}, LaneRot c = LaneRot{0, -1, 0.0}) { return LaneGate1{{a, b, c}}; }
-constexpr int RZ = 1, RY = 2, RX = 3;
-
 int gate1_all(aqc_mpsb* b, Lanes& s, int q, const LaneGate1& g, int T, Lanes* s2 = nullptr) {
     HIP_OK(launch_lanes_gate1(s.dev, s2 ? &s2->dev : nullptr, nullptr, 1, LaneOp1{q, 0, g}, b->thetas, T, b->active, b->hint, b->st));
     return 0;
@@ -167,90 +163,33 @@ int gate_adjacent_all(aqc_mpsb* b, Lanes& s, Lanes* s2, int q, const LaneGate2& 
     return 0;
 }
 
-// entangler of a block (control c, target t) on any pair of qubits of `s` (and of `s2`, when given: the two operands of the gradient walk
-// take every gate in one launch): swaps bring the upper one next to the lower one and back
-int gate2_pair_all(aqc_mpsb* b, Lanes& s, Lanes* s2, int ctrl, int targ, int kind, int idx, double scale, int T, double trunc_thr, int max_bond) {
-    const LaneGate2 swap{0, -1, 0, 0, 0.0};
-    const int lo = std::min(ctrl, targ), hi = std::max(ctrl, targ);
-    for (int p = hi - 1; p > lo; --p)
-        if (gate_adjacent_all(b, s, s2, p, swap, T, trunc_thr, max_bond)) return 1;
-    const LaneGate2 g{kind, idx, ctrl > targ ? 1 : 0, 0, scale};
-    if (gate_adjacent_all(b, s, s2, lo, g, T, trunc_thr, max_bond)) return 1;
-    for (int p = lo + 1; p < hi; ++p)
-        if (gate_adjacent_all(b, s, s2, p, swap, T, trunc_thr, max_bond)) return 1;
+// entangler of a block on any pair of qubits of `s` (and of `s2`, when given: the two operands of the gradient walk take every gate in one
+// launch), routed by route_pair (aqc_mps_walk.h)
+int gate2_pair_all(aqc_mpsb* b, Lanes& s, Lanes* s2, int ctrl, int targ, const LaneGate2& g, int T, double trunc_thr, int max_bond) {
+    for (const RouteStep& r : route_pair(ctrl, targ))
+        if (gate_adjacent_all(b, s, s2, r.q, routed_gate(r, g), T, trunc_thr, max_bond)) return 1;
     return 0;
 }
 
-int entangler_kind(const aqc_circuit* c) { return c->entangler == AQC_CX ? 1 : (c->entangler == AQC_CZ ? 2 : 3); }
-
-// V(theta_l) or V(theta_l)^H on every lane (apply_circuit of aqc_mps_engine.cpp; core_operations.py:671-708, :787-818), layer by layer:
+// V(theta_l) or V(theta_l)^H on every lane (circuit_ops of aqc_mps_walk.h), layer by layer:
 // the gates in program order (long-range entanglers already routed by swaps) are levelled as soon as possible -- a gate goes one level
 // above the last gate on any of its sites.  The gates of a level act on pairwise disjoint site tensors, Schmidt vectors and bond
 // dimensions, so they run in ONE launch per kind (1-qubit, 2-qubit) and leave exactly the bits the one-after-the-other order leaves:
 // a brickwork layer of n / 2 entanglers is one launch of n / 2 x lanes workgroups instead of n / 2 dependent launches.
-void emit_circuit(const aqc_circuit* c, int n, bool inverse, std::vector<std::pair<int, LaneOp1>>& o1, std::vector<std::pair<int, LaneOp2>>& o2) {
-    // (first = position in program order, shared by both lists)
-    const int tpb = c->entangler == AQC_CP ? 5 : 4;
-    const bool cx = c->entangler == AQC_CX, cp = c->entangler == AQC_CP;
-    const std::vector<BlockRef> blocks = blocks_of(c);
-    const double half_pi = 1.5707963267948966;
-    const int ek = entangler_kind(c), rt = cx ? RX : RZ;
-    const LaneGate1 pre = g1(rot(RZ, -1, -half_pi)), post = g1(rot(RZ, -1, half_pi));
-    int pos = 0;
-    auto one = [&](int q, const LaneGate1& g) { o1.emplace_back(pos++, LaneOp1{q, 0, g}); };
-    auto two = [&](int ctrl, int targ, int idx, double scale) {   // swaps bring the upper qubit next to the lower one and back
-        const LaneGate2 swap{0, -1, 0, 0, 0.0};
-        const int lo = std::min(ctrl, targ), hi = std::max(ctrl, targ);
-        for (int p = hi - 1; p > lo; --p) o2.emplace_back(pos++, LaneOp2{p, 0, swap});
-        o2.emplace_back(pos++, LaneOp2{lo, 0, LaneGate2{ek, idx, ctrl > targ ? 1 : 0, 0, scale}});
-        for (int p = lo + 1; p < hi; ++p) o2.emplace_back(pos++, LaneOp2{p, 0, swap});
-    };
-    if (!inverse) {
-        for (int q = 0; q < n; ++q) one(q, g1(rot(RZ, 3 * q, 1.0), rot(RY, 3 * q + 1, 1.0), rot(RZ, 3 * q + 2, 1.0)));
-        for (const BlockRef& blk : blocks) {
-            const int p = 3 * n + tpb * blk.j;
-            if (c->trotter && blk.i % 3 == 0) one(blk.c, pre);
-            two(blk.c, blk.t, cp ? p + 4 : -1, 1.0);
-            one(blk.c, g1(rot(RZ, p + 1, 1.0), rot(RY, p, 1.0)));
-            one(blk.t, g1(rot(rt, p + 3, 1.0), rot(RY, p + 2, 1.0)));
-            if (c->trotter && blk.i % 3 == 2) one(blk.t, post);
-        }
-    } else {
-        for (auto it = blocks.rbegin(); it != blocks.rend(); ++it) {
-            const BlockRef& blk = *it;
-            const int p = 3 * n + tpb * blk.j;
-            if (c->trotter && blk.i % 3 == 2) one(blk.t, pre);
-            one(blk.t, g1(rot(RY, p + 2, -1.0), rot(rt, p + 3, -1.0)));
-            one(blk.c, g1(rot(RY, p, -1.0), rot(RZ, p + 1, -1.0)));
-            two(blk.c, blk.t, cp ? p + 4 : -1, -1.0);
-            if (c->trotter && blk.i % 3 == 0) one(blk.c, post);
-        }
-        for (int q = 0; q < n; ++q) one(q, g1(rot(RZ, 3 * q + 2, -1.0), rot(RY, 3 * q + 1, -1.0), rot(RZ, 3 * q, -1.0)));
-    }
-}
-
 int build_schedule(aqc_mpsb* b, const aqc_circuit* c, bool inverse, Schedule& out) {
     const int n = b->n;
-    std::vector<std::pair<int, LaneOp1>> o1;
-    std::vector<std::pair<int, LaneOp2>> o2;
-    emit_circuit(c, n, inverse, o1, o2);
+    const std::vector<CircuitOp> ops = circuit_ops(c, n, inverse);
     // as-soon-as-possible levels in program order
-    std::vector<int> site_level(n, -1), lev1(o1.size()), lev2(o2.size());
-    size_t i1 = 0, i2 = 0;
+    std::vector<int> site_level(n, -1), lev(ops.size());
     int depth = 0;
-    while (i1 < o1.size() || i2 < o2.size()) {
-        if (i2 >= o2.size() || (i1 < o1.size() && o1[i1].first < o2[i2].first)) {
-            const int q = o1[i1].second.q;
-            lev1[i1] = ++site_level[q];
-            depth = std::max(depth, lev1[i1] + 1);
-            ++i1;
+    for (size_t i = 0; i < ops.size(); ++i) {
+        if (!ops[i].two) {
+            lev[i] = ++site_level[ops[i].op1.q];
         } else {
-            const int q = o2[i2].second.q;
-            const int lv = std::max(site_level[q], site_level[q + 1]) + 1;
-            site_level[q] = site_level[q + 1] = lev2[i2] = lv;
-            depth = std::max(depth, lv + 1);
-            ++i2;
+            const int q = ops[i].op2.q;
+            site_level[q] = site_level[q + 1] = lev[i] = std::max(site_level[q], site_level[q + 1]) + 1;
         }
+        depth = std::max(depth, lev[i] + 1);
     }
     std::vector<LaneOp1> t1;
     std::vector<LaneOp2> t2;
@@ -258,8 +197,8 @@ int build_schedule(aqc_mpsb* b, const aqc_circuit* c, bool inverse, Schedule& ou
     for (int lv = 0; lv < depth; ++lv) {
         Level& L = out.levels[lv];
         L.off1 = (int)t1.size(); L.off2 = (int)t2.size();
-        for (size_t i = 0; i < o1.size(); ++i) if (lev1[i] == lv) t1.push_back(o1[i].second);
-        for (size_t i = 0; i < o2.size(); ++i) if (lev2[i] == lv) t2.push_back(o2[i].second);
+        for (size_t i = 0; i < ops.size(); ++i)
+            if (lev[i] == lv) { if (ops[i].two) t2.push_back(ops[i].op2); else t1.push_back(ops[i].op1); }
         L.n1 = (int)t1.size() - L.off1; L.n2 = (int)t2.size() - L.off2;
     }
     if (!t1.empty()) {
@@ -306,7 +245,7 @@ int apply_circuit_all(aqc_mpsb* b, Lanes& s, const aqc_circuit* c, int T, bool i
     return 0;
 }
 
-// ---- environments of the pair (w, z), all lanes per launch (struct Environments of aqc_mps_engine.cpp) -------------------------
+// ---- environments of the pair (w, z), all lanes per launch (same scheme as struct Environments of aqc_mps_engine.cpp) -------------------------
 constexpr size_t kEnvL(int n) { return (size_t)(n + 1) * kLaneEnv; }
 constexpr size_t kEnvR(int n) { return (size_t)n * kLaneEnv; }
 
@@ -321,7 +260,7 @@ void env_touched(aqc_mpsb* b, int lo, int hi) { b->valid_l = std::min(b->valid_l
 // out[u][v] = sum_bit sum_xy conj(A_p[bit][x][u]) in[x][y] B_p[bit][y][v]; `op` (may be null) sits on w's side of site p
 int step_left_all(aqc_mpsb* b, int p, const double2* in, size_t in_stride, const M2* op, double2* out, size_t out_stride) {
     double g8[8];
-    if (op) { const M2 gh = {{std::conj(op->m[0]), std::conj(op->m[2]), std::conj(op->m[1]), std::conj(op->m[3])}}; pack(gh, g8); }
+    if (op) pack(adjoint(*op), g8);
     HIP_OK(launch_lanes_env_left(b->w.dev, b->z.dev, p, in, in_stride, out, out_stride, op ? g8 : nullptr, b->L, b->st));
     return 0;
 }
@@ -358,80 +297,43 @@ int dot_all(aqc_mpsb* b, int slot, int nops, const int* q, const M2* const* g) {
     return 0;
 }
 
-// the gate-by-gate gradient walk of mps_dot_objective.py:41-242 on every lane: w = lhs, z = vh (both consumed); the inner products go
+// the gate-by-gate gradient walk (gradient_steps of aqc_mps_walk.h) on every lane: w = lhs, z = vh (both consumed); the inner products go
 // to slots slot0, slot0 + 1, ... of vals; rec = (theta index, factor) per slot
 int gradient_all(aqc_mpsb* b, const aqc_circuit* c, int T, double trunc_thr, int max_bond, int lo_blk, int hi_blk, bool front_layer, int slot0,
                  std::vector<std::pair<int, cd>>& rec) {
-    const int n = b->n, tpb = c->entangler == AQC_CP ? 5 : 4;
-    const bool cx = c->entangler == AQC_CX, cp = c->entangler == AQC_CP;
-    const std::vector<BlockRef> blocks = blocks_of(c);
-    const double half_pi = 1.5707963267948966;
-    const int ek = entangler_kind(c);
+    const int n = b->n;
     rec.clear();
-    auto both = [&](int q, const LaneGate1& g) -> int {
-        if (gate1_all(b, b->w, q, g, T, &b->z)) return 1;
-        env_touched(b, q, q);
-        return 0;
-    };
-    auto record = [&](int tindex, cd factor, int nops, const int* q, const M2* const* g) -> int {
-        if (dot_all(b, slot0 + (int)rec.size(), nops, q, g)) return 1;
-        rec.emplace_back(tindex, factor);
-        return 0;
-    };
-    // consecutive parameters on one site q: per parameter the rotation on both operands + its inner product 0.5j <P w|z>, up to three of them
-    // in one launch (the environments do not involve site q: they are advanced once, in front)
-    auto rotate_and_record = [&](int q, int count, const int* tindex, const LaneGate1* g, const M2* const* op) -> int {
-        const int slot = slot0 + (int)rec.size();
-        if (slot + count > b->nvals) return failf("inner-product slot out of range");
-        if (env_advance(b, q, q)) return 1;
-        LaneSteps st{};
-        st.count = count;
-        for (int k = 0; k < count; ++k) {
-            st.g[k] = g[k];
-            const M2 gh = {{std::conj(op[k]->m[0]), std::conj(op[k]->m[2]), std::conj(op[k]->m[1]), std::conj(op[k]->m[3])}};
-            pack(gh, st.gh[k]);
-        }
-        HIP_OK(launch_lanes_grad_step(b->w.dev, b->z.dev, q, st, b->thetas, T, b->env_l + (size_t)q * kLaneEnv, kEnvL(n), b->env_r + (size_t)q * kLaneEnv, kEnvR(n),
-                                      b->e0, b->vals, b->nvals, slot, b->L, b->st));
-        env_touched(b, q, q);
-        for (int k = 0; k < count; ++k) rec.emplace_back(tindex[k], cd(0, 0.5));
-        return 0;
-    };
-    for (int q = 0; q < n; ++q) {   // front layer: Rz(t2), Ry(t1), Rz(t0), rightmost first (core_operations.py:921-935)
-        const int tix[3] = {3 * q + 2, 3 * q + 1, 3 * q};
-        const LaneGate1 gs[3] = {g1(rot(RZ, tix[0], 1.0)), g1(rot(RY, tix[1], 1.0)), g1(rot(RZ, tix[2], 1.0))};
-        const M2* ops[3] = {&kPauliZ, &kPauliY, &kPauliZ};
-        if (front_layer) {
-            if (rotate_and_record(q, 3, tix, gs, ops)) return 1;
-        } else {
-            for (int k = 0; k < 3; ++k)
-                if (both(q, gs[k])) return 1;
-        }
-    }
-    const LaneGate1 pre = g1(rot(RZ, -1, -half_pi)), post = g1(rot(RZ, -1, half_pi));
-    for (const BlockRef& blk : blocks) {
-        const int base = 3 * n + tpb * blk.j;
-        const bool live = lo_blk <= blk.j && blk.j < hi_blk;
-        if (c->trotter && blk.i % 3 == 0 && both(blk.c, pre)) return 1;
-        if (live && cp) {
-            const int qq[2] = {std::min(blk.c, blk.t), std::max(blk.c, blk.t)};
+    for (const GradStep& s : gradient_steps(c, n, lo_blk, hi_blk, front_layer)) {
+        if (s.kind == GradStep::RecordP11) {
+            const int qq[2] = {s.q, s.q2};
             const M2* gg[2] = {&kProj1, &kProj1};
-            if (record(base + 4, cd(0, -1.0), 2, qq, gg)) return 1;
-        }
-        if (gate2_pair_all(b, b->z, &b->w, blk.c, blk.t, ek, cp ? base + 4 : -1, 1.0, T, trunc_thr, max_bond)) return 1;
-        env_touched(b, std::min(blk.c, blk.t), std::max(blk.c, blk.t));
-        const int qs[4] = {blk.c, blk.c, blk.t, blk.t};
-        const int kinds[4] = {RY, RZ, RY, cx ? RX : RZ};
-        const M2* ps[4] = {&kPauliY, &kPauliZ, &kPauliY, cx ? &kPauliX : &kPauliZ};
-        const int tix[4] = {base, base + 1, base + 2, base + 3};
-        const LaneGate1 gs[4] = {g1(rot(kinds[0], base, 1.0)), g1(rot(kinds[1], base + 1, 1.0)), g1(rot(kinds[2], base + 2, 1.0)), g1(rot(kinds[3], base + 3, 1.0))};
-        if (live) {   // the two rotations of the control, then the two of the target: one launch per qubit
-            if (rotate_and_record(blk.c, 2, tix, gs, ps) || rotate_and_record(blk.t, 2, tix + 2, gs + 2, ps + 2)) return 1;
+            if (dot_all(b, slot0 + (int)rec.size(), 2, qq, gg)) return 1;
+            rec.emplace_back(s.tindex, s.factor);
+        } else if (s.kind == GradStep::Entangle) {
+            if (gate2_pair_all(b, b->z, &b->w, s.q, s.q2, s.ent, T, trunc_thr, max_bond)) return 1;
+            env_touched(b, std::min(s.q, s.q2), std::max(s.q, s.q2));
+        } else if (!s.recorded) {
+            for (int k = 0; k < s.count; ++k) {
+                if (gate1_all(b, b->w, s.q, s.r[k].g, T, &b->z)) return 1;
+                env_touched(b, s.q, s.q);
+            }
         } else {
-            for (int k = 0; k < 4; ++k)
-                if (both(qs[k], gs[k])) return 1;
+            // consecutive parameters on one site: per parameter the rotation on both operands + its inner product <P w|z>, up to three of
+            // them in one launch (the environments do not involve the site: they are advanced once, in front)
+            const int slot = slot0 + (int)rec.size();
+            if (slot + s.count > b->nvals) return failf("inner-product slot out of range");
+            if (env_advance(b, s.q, s.q)) return 1;
+            LaneSteps st{};
+            st.count = s.count;
+            for (int k = 0; k < s.count; ++k) {
+                st.g[k] = s.r[k].g;
+                pack(adjoint(pauli_of(s.r[k].pauli)), st.gh[k]);
+            }
+            HIP_OK(launch_lanes_grad_step(b->w.dev, b->z.dev, s.q, st, b->thetas, T, b->env_l + (size_t)s.q * kLaneEnv, kEnvL(n), b->env_r + (size_t)s.q * kLaneEnv,
+                                          kEnvR(n), b->e0, b->vals, b->nvals, slot, b->L, b->st));
+            env_touched(b, s.q, s.q);
+            for (int k = 0; k < s.count; ++k) rec.emplace_back(s.r[k].tindex, s.factor);
         }
-        if (c->trotter && blk.i % 3 == 2 && both(blk.t, post)) return 1;
     }
     return 0;
 }
@@ -496,7 +398,7 @@ int begin(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double tru
     if (!(trunc_thr >= 0.0)) return failf("trunc_thr must be non-negative");
     if (max_bond > kLaneCap) return failf("the lockstep lanes keep bonds up to %d", kLaneCap);
     HIP_OK(hipSetDevice(b->device));
-    const int n = b->n, L = b->L, tpb = circ->entangler == AQC_CP ? 5 : 4, T = 3 * n + tpb * circ->num_blocks;
+    const int n = b->n, L = b->L, tpb = thetas_per_block(circ), T = 3 * n + tpb * circ->num_blocks;
     const int need = num_amps + 3 * n + tpb * (int)blocks_of(circ).size();
     const auto out_size = [&](int nv) { return sizeof(double2) * (size_t)L * nv + sizeof(int) * 2 * (size_t)L + sizeof(double) * (size_t)L + sizeof(int) * (size_t)L * (n + 1); };
     if (need > b->nvals || T > b->T_cap) {
@@ -866,7 +768,7 @@ int aqc_mpsb_grad(aqc_mpsb* b, const aqc_circuit* circ, int block_from, int bloc
     if (!b->have_lhs) return failf("set the lhs states of the lanes first");
     if (check_circuit(circ, b->n)) return 1;
     HIP_OK(hipSetDevice(b->device));
-    const int n = b->n, L = b->L, tpb = circ->entangler == AQC_CP ? 5 : 4, T = 3 * n + tpb * circ->num_blocks;
+    const int n = b->n, L = b->L, tpb = thetas_per_block(circ), T = 3 * n + tpb * circ->num_blocks;
     if (T != b->cur_T || 3 * n + tpb * (int)blocks_of(circ).size() > b->nvals) return failf("aqc_mpsb_grad: not the circuit of the last aqc_mpsb_vh");
     if (block_from < 0) { block_from = 0; block_to = circ->num_blocks; }
     if (block_from > block_to || block_to > circ->num_blocks) return failf("invalid block range");

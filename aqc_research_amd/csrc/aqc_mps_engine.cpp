@@ -326,57 +326,30 @@ int gate1_site(aqc_mps* m, int q, const double* g8) {
     return 0;
 }
 
-// 4x4 gate (index 2 * bit_ctrl + bit_targ) on any pair of qubits
+// one routed 2-qubit op on the sites (q, q + 1)
+int gate2_site(aqc_mps* m, int q, const LaneGate2& g, const double* th, double trunc_thr, int max_bond) {
+    double g32[32];
+    gate2_matrix(g, th, g32);
+    return gate_adjacent(m, q, g32, trunc_thr, max_bond);
+}
+
+// 4x4 gate (index 2 * bit_ctrl + bit_targ) on any pair of qubits, routed by route_pair (aqc_mps_walk.h)
 int gate2_pair(aqc_mps* m, int ctrl, int targ, const double* gate, double trunc_thr, int max_bond) {
     static const double swap_gate[32] = {1, 0, 0, 0, 0, 0, 0, 0,  0, 0, 0, 0, 1, 0, 0, 0,  0, 0, 1, 0, 0, 0, 0, 0,  0, 0, 0, 0, 0, 0, 1, 0};
-    const int lo = std::min(ctrl, targ), hi = std::max(ctrl, targ);
-    // bring qubit `hi` down to position lo + 1 by swaps, apply, swap back (the route Aer takes as well)
-    for (int p = hi - 1; p > lo; --p)
-        if (gate_adjacent(m, p, swap_gate, trunc_thr, max_bond)) return 1;
-    double g[32];
-    permute_gate(gate, ctrl > targ, g);      // site lo carries the lower qubit: flip when ctrl is the upper one
-    if (gate_adjacent(m, lo, g, trunc_thr, max_bond)) return 1;
-    for (int p = lo + 1; p < hi; ++p)
-        if (gate_adjacent(m, p, swap_gate, trunc_thr, max_bond)) return 1;
+    for (const RouteStep& r : route_pair(ctrl, targ)) {
+        double g[32];
+        if (!r.swap) permute_gate(gate, r.flip != 0, g);
+        if (gate_adjacent(m, r.q, r.swap ? swap_gate : g, trunc_thr, max_bond)) return 1;
+    }
     return 0;
 }
 
-// ---- the ansatz, gate by gate (host side of aqc_mps_apply_circuit / aqc_mps_fast_dot_gradient) ----------
+// ---- the ansatz, gate by gate (host side of aqc_mps_apply_circuit / aqc_mps_fast_dot_gradient): executors of the lists of aqc_mps_walk.h
 int gate1(aqc_mps* m, int q, const M2& g) { double g8[8]; pack(g, g8); return gate1_site(m, q, g8); }
 
 int apply_circuit(aqc_mps* m, const aqc_circuit* c, const double* th, bool inverse, double trunc_thr, int max_bond) {
-    const int n = m->n, tpb = c->entangler == AQC_CP ? 5 : 4;
-    const double* t2 = th + 3 * n;
-    const bool cx = c->entangler == AQC_CX;
-    const std::vector<BlockRef> blocks = blocks_of(c);
-    const double half_pi = 1.5707963267948966;
-    double ent[32];
-    if (!inverse) {   // core_operations.py:671-708
-        for (int q = 0; q < n; ++q)
-            if (gate1(m, q, rz_m(th[3 * q]) * ry_m(th[3 * q + 1]) * rz_m(th[3 * q + 2]))) return 1;
-        for (const BlockRef& b : blocks) {
-            const double* p = t2 + (size_t)tpb * b.j;
-            if (c->trotter && b.i % 3 == 0 && gate1(m, b.c, rz_m(-half_pi))) return 1;
-            entangler_matrix(c->entangler, tpb == 5 ? p[4] : 0.0, ent);
-            if (gate2_pair(m, b.c, b.t, ent, trunc_thr, max_bond)) return 1;
-            if (gate1(m, b.c, rz_m(p[1]) * ry_m(p[0]))) return 1;
-            if (gate1(m, b.t, (cx ? rx_m(p[3]) : rz_m(p[3])) * ry_m(p[2]))) return 1;
-            if (c->trotter && b.i % 3 == 2 && gate1(m, b.t, rz_m(half_pi))) return 1;
-        }
-    } else {          // core_operations.py:787-818
-        for (auto it = blocks.rbegin(); it != blocks.rend(); ++it) {
-            const BlockRef& b = *it;
-            const double* p = t2 + (size_t)tpb * b.j;
-            if (c->trotter && b.i % 3 == 2 && gate1(m, b.t, rz_m(-half_pi))) return 1;
-            if (gate1(m, b.t, ry_m(-p[2]) * (cx ? rx_m(-p[3]) : rz_m(-p[3])))) return 1;
-            if (gate1(m, b.c, ry_m(-p[0]) * rz_m(-p[1]))) return 1;
-            entangler_matrix(c->entangler, tpb == 5 ? -p[4] : 0.0, ent);
-            if (gate2_pair(m, b.c, b.t, ent, trunc_thr, max_bond)) return 1;
-            if (c->trotter && b.i % 3 == 0 && gate1(m, b.c, rz_m(half_pi))) return 1;
-        }
-        for (int q = 0; q < n; ++q)
-            if (gate1(m, q, rz_m(-th[3 * q + 2]) * ry_m(-th[3 * q + 1]) * rz_m(-th[3 * q]))) return 1;
-    }
+    for (const CircuitOp& op : circuit_ops(c, m->n, inverse))
+        if (op.two ? gate2_site(m, op.op2.q, op.op2.g, th, trunc_thr, max_bond) : gate1(m, op.op1.q, gate1_matrix(op.op1.g, th))) return 1;
     return 0;
 }
 
@@ -408,8 +381,7 @@ struct Environments {
         if (!op) return 0;
         const size_t ne = (size_t)z->dims[p] * z->dims[p + 1];
         if (bsite.reserve(sizeof(double2) * 2 * ne)) return 1;
-        const M2 gh = {{std::conj(op->m[0]), std::conj(op->m[2]), std::conj(op->m[1]), std::conj(op->m[3])}};
-        double g8[8]; pack(gh, g8);
+        double g8[8]; pack(adjoint(*op), g8);
         HIP_OK(launch_gate1q(z->t[p], bsite.p, 1, ne, 0, g8, st));
         *out = static_cast<const double2*>(bsite.p);
         return 0;
@@ -420,7 +392,7 @@ struct Environments {
         if (mps_env_fits_small(xa, ua, yb, vb)) {   // small bonds: one launch, the operator folded in
             if (out.reserve(sizeof(double2) * (size_t)ua * vb)) return 1;
             double g8[8];
-            if (op) { const M2 gh = {{std::conj(op->m[0]), std::conj(op->m[2]), std::conj(op->m[1]), std::conj(op->m[3])}}; pack(gh, g8); }
+            if (op) pack(adjoint(*op), g8);
             HIP_OK(launch_mps_env_left(in, w->t[p], z->t[p], xa, ua, yb, vb, op ? g8 : nullptr, out.p, st));
             return 0;
         }
@@ -470,63 +442,45 @@ struct Environments {
 
 int fast_dot_gradient(const aqc_circuit* c, aqc_mps* w, aqc_mps* z, const double* th, double trunc_thr, int max_bond, int lo_blk, int hi_blk,
                       bool front_layer, double* grad) {
-    const int n = w->n, tpb = c->entangler == AQC_CP ? 5 : 4, L = c->num_blocks, T = 3 * n + tpb * L;
-    const bool cx = c->entangler == AQC_CX;
-    const std::vector<BlockRef> blocks = blocks_of(c);
-    const double half_pi = 1.5707963267948966;
+    const int n = w->n, T = 3 * n + thetas_per_block(c) * c->num_blocks;
+    const std::vector<GradStep> steps = gradient_steps(c, n, lo_blk, hi_blk, front_layer);
     // every recorded inner product: (theta index, factor); several may add into one theta (Trotter tail)
     std::vector<std::pair<int, cd>> rec;
-    rec.reserve((size_t)3 * n + (size_t)tpb * blocks.size());
+    const int nrec = 3 * n + thetas_per_block(c) * (int)blocks_of(c).size();   // at most
+    rec.reserve(nrec);
     Environments env;
-    if (env.init(w, z, 3 * n + tpb * (int)blocks.size())) { env.release(); return 1; }
-    auto both = [&](int q, const M2& g) -> int {
-        if (gate1(w, q, g) || gate1(z, q, g)) return 1;
-        env.touched(q, q);
-        return 0;
-    };
+    if (env.init(w, z, nrec)) { env.release(); return 1; }
     auto record = [&](int tindex, cd factor, int nops, const int* q, const M2* const* g) -> int {
         if (env.dot((int)rec.size(), nops, q, g)) return 1;
         rec.emplace_back(tindex, factor);
         return 0;
     };
+    auto run = [&](const GradStep& s) -> int {
+        if (s.kind == GradStep::RecordP11) {
+            const int qq[2] = {s.q, s.q2};
+            const M2* gg[2] = {&kProj1, &kProj1};
+            return record(s.tindex, s.factor, 2, qq, gg);
+        }
+        if (s.kind == GradStep::Entangle) {
+            double ent[32];
+            entangler_matrix(c->entangler, s.ent.idx >= 0 ? s.ent.scale * th[s.ent.idx] : 0.0, ent);
+            if (gate2_pair(z, s.q, s.q2, ent, trunc_thr, max_bond) || gate2_pair(w, s.q, s.q2, ent, trunc_thr, max_bond)) return 1;
+            env.touched(std::min(s.q, s.q2), std::max(s.q, s.q2));
+            return 0;
+        }
+        for (int k = 0; k < s.count; ++k) {
+            const M2 g = gate1_matrix(s.r[k].g, th);
+            if (gate1(w, s.q, g) || gate1(z, s.q, g)) return 1;
+            env.touched(s.q, s.q);
+            const M2* op = &pauli_of(s.r[k].pauli);
+            if (s.recorded && record(s.r[k].tindex, s.factor, 1, &s.q, &op)) return 1;
+        }
+        return 0;
+    };
     int rc = 1;
     do {
         bool bad = false;
-        // front layer: Rz(t2), Ry(t1), Rz(t0), rightmost first (core_operations.py:921-935)
-        for (int q = 0; q < n && !bad; ++q) {
-            const int slots[3] = {2, 1, 0};
-            for (int k = 0; k < 3 && !bad; ++k) {
-                const int slot = slots[k];
-                const bool is_y = slot == 1;
-                if (both(q, is_y ? ry_m(th[3 * q + slot]) : rz_m(th[3 * q + slot]))) { bad = true; break; }
-                const M2* op = is_y ? &kPauliY : &kPauliZ;
-                if (front_layer && record(3 * q + slot, cd(0, 0.5), 1, &q, &op)) bad = true;
-            }
-        }
-        double ent[32];
-        for (size_t bi = 0; bi < blocks.size() && !bad; ++bi) {
-            const BlockRef& b = blocks[bi];
-            const double* p = th + 3 * n + (size_t)tpb * b.j;
-            const int base = 3 * n + tpb * b.j;
-            const bool live = lo_blk <= b.j && b.j < hi_blk;
-            if (c->trotter && b.i % 3 == 0 && both(b.c, rz_m(-half_pi))) { bad = true; break; }
-            if (live && tpb == 5) {   // -1j <P11 w|z> before the gate (core_op_matrix.py:430-477)
-                const int qq[2] = {std::min(b.c, b.t), std::max(b.c, b.t)};
-                const M2* gg[2] = {&kProj1, &kProj1};
-                if (record(base + 4, cd(0, -1.0), 2, qq, gg)) { bad = true; break; }
-            }
-            entangler_matrix(c->entangler, tpb == 5 ? p[4] : 0.0, ent);
-            if (gate2_pair(z, b.c, b.t, ent, trunc_thr, max_bond) || gate2_pair(w, b.c, b.t, ent, trunc_thr, max_bond)) { bad = true; break; }
-            env.touched(std::min(b.c, b.t), std::max(b.c, b.t));
-            const int qs[4] = {b.c, b.c, b.t, b.t};
-            const M2 gs[4] = {ry_m(p[0]), rz_m(p[1]), ry_m(p[2]), cx ? rx_m(p[3]) : rz_m(p[3])};
-            const M2* ps[4] = {&kPauliY, &kPauliZ, &kPauliY, cx ? &kPauliX : &kPauliZ};
-            for (int k = 0; k < 4 && !bad; ++k) {
-                if (both(qs[k], gs[k])) { bad = true; break; }
-                if (live && record(base + k, cd(0, 0.5), 1, &qs[k], &ps[k])) bad = true;
-            }
-            if (!bad && c->trotter && b.i % 3 == 2 && both(b.t, rz_m(half_pi))) bad = true;
-        }
+        for (size_t i = 0; i < steps.size() && !bad; ++i) bad = run(steps[i]) != 0;
         if (bad) break;
         std::vector<cd> vals(rec.size());
         if (!rec.empty() && hipMemcpyAsync(vals.data(), env.vals.p, sizeof(cd) * rec.size(), hipMemcpyDeviceToHost, env.st) != hipSuccess) { failf("gradient download failed"); break; }

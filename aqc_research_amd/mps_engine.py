@@ -484,7 +484,7 @@ def _pool(workers: int):
     return _POOL
 
 
-LOCKSTEP_MAX_BOND = 32   # kCap of csrc/aqc_mps_batch.cpp
+LOCKSTEP_MAX_BOND = 32   # kLaneCap of csrc/aqc_launch.h
 
 
 class LockstepLanes:

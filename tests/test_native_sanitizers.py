@@ -1,11 +1,14 @@
 """CPU builds of the native host code under AddressSanitizer + UBSan (GPU sanitizers are not available on the
-pool; the reference has no sanitizer runs at all): the C restatement of the oracle and the HIP-free
-stage planner, each with a self-test driver from tests/native/."""
+pool; the reference has no sanitizer runs at all): the C restatement of the oracle, the HIP-free
+stage planner and the HIP-free gate walk of the MPS engines, each with a self-test driver from tests/native/."""
 import os
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
+
+from tests.helpers import TOL, load, maxdiff
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
@@ -33,3 +36,30 @@ def test_planner_under_asan_ubsan(tmp_path):
           os.path.join(ROOT, "aqc_research_amd", "csrc", "aqc_plan.cpp"), "-o", exe])
     out = _run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert " 0 failures" in out
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_mps_walk_under_asan_ubsan(tmp_path):
+    """The one statement of the MPS engines' gate walk (csrc/aqc_mps_walk.h: circuit_ops, gradient_steps, route_pair) evaluated on a
+    dense state vector against the reference's own outputs, on every golden state-vector case."""
+    exe = str(tmp_path / "walk_selftest")
+    _run(["g++", "-std=c++17", *SAN, os.path.join(ROOT, "tests", "native", "walk_selftest.cpp"), "-o", exe])
+    sv = load("state_vector.npz")
+    names = [str(k) for k in sv["names"]]
+    assert len(names) == 32
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1")
+    for key in names:
+        n, blocks, th = int(sv[f"{key}/n"]), sv[f"{key}/blocks"], sv[f"{key}/thetas"]
+        ent = {"cx": 0, "cz": 1, "cp": 2}[str(sv[f"{key}/ent"])]
+        words = [n, ent, blocks.shape[1], int(sv[f"{key}/trotter"]), int(sv[f"{key}/second_order"]), *blocks.ravel().tolist(), th.size]
+        words += [repr(float(t)) for t in th]
+        for vec in (sv[f"{key}/x"], sv[f"{key}/y"]):
+            words += [repr(float(v)) for v in vec.view(np.float64)]
+        words += [int(v) for v in sv[f"{key}/block_range"]]
+        out = np.array(_run([exe], env=env, input=" ".join(str(w) for w in words)).split(), dtype=np.float64).view(np.complex128)
+        dim = 1 << n
+        assert out.size == 2 * dim + 2 * th.size, key
+        got = {"v_x": out[:dim], "vh_y": out[dim:2 * dim], "grad_full": out[2 * dim:2 * dim + th.size], "grad_part": out[2 * dim + th.size:]}
+        for name, arr in got.items():
+            err = maxdiff(arr, sv[f"{key}/{name}"])
+            assert err < TOL, f"{key}/{name}: {err:g}"
