@@ -160,9 +160,18 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+LANES_REFUSED = 3   # AQC_LANES_REFUSED of include/aqc_hip.h
+
+
+class LanesRefused(RuntimeError):
+    """The lockstep lanes of the MPS engine cannot do this call (a bond beyond their limit, a lane gone bad, no memory for them) and
+    returned nothing; the single-lane engine may.  What callers that have such a route catch in order to take it."""
+
+
 def check(status: int) -> None:
     if status != 0:
-        raise RuntimeError("aqc_hip: " + lib().aqc_last_error().decode("utf-8", "replace"))
+        kind = LanesRefused if status == LANES_REFUSED else RuntimeError
+        raise kind("aqc_hip: " + lib().aqc_last_error().decode("utf-8", "replace"))
 
 
 def dptr(arr: np.ndarray):

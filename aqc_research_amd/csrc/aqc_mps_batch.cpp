@@ -14,7 +14,7 @@
 //     bond statistics in one transfer at the end.
 // Workgroups are sized for the bonds seen so far (`hint`: LDS and threads for bonds <= 4 / 6 / 8 / ... / 32); a lane that outgrows
 // the launch raises a status bit and the evaluation is repeated at full size -- never a wrong result.  Bonds above 32 (a work
-// matrix larger than 64 x 64 does not fit one workgroup's LDS) are refused: the caller goes to the single-lane engine.
+// matrix larger than 64 x 64 does not fit one workgroup's LDS) are refused (AQC_LANES_REFUSED): the caller goes to the single-lane engine.
 // Arithmetic and truncation rule are the single-lane engine's (same device bodies, aqc_mps_dev.h), lane by lane.
 #include <hip/hip_runtime_api.h>
 
@@ -59,6 +59,7 @@ struct Schedule {
     std::vector<Level> levels;
     LaneOp1* ops1 = nullptr;   // device tables, level after level
     LaneOp2* ops2 = nullptr;
+    void release() { if (ops1) (void)hipFree(ops1); if (ops2) (void)hipFree(ops2); ops1 = nullptr; ops2 = nullptr; }
 };
 
 }  // namespace
@@ -105,12 +106,27 @@ struct aqc_mpsb {
 
 namespace {
 
+// A failure that sends the caller to the single-lane engine: failf's message with the status AQC_LANES_REFUSED (include/aqc_hip.h).
+// Its callers are exactly the failures whose text named "the lockstep lanes" while callers decided the fallback by those words: the
+// bond checks, but also a lane's SVD or state gone bad, the full-size workgroup and the allocation.  The decision moved from the
+// wording to this code and was not taken again; narrowing the set changes behaviour and is a decision of its own.
+int refuse(const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    set_error(buf);
+    return AQC_LANES_REFUSED;
+}
+constexpr int kRepeatAtFullSize = -1;   // finish() to run_phase() only: never a status of the ABI
+
 void destroy(aqc_mpsb* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
     for (Lanes* s : {&b->target, &b->lhs, &b->vh, &b->w, &b->z, &b->bank}) s->release();
-    for (auto& kv : b->schedules) { if (kv.second.ops1) (void)hipFree(kv.second.ops1); if (kv.second.ops2) (void)hipFree(kv.second.ops2); }
+    for (auto& kv : b->schedules) kv.second.release();
     for (void* p : {(void*)b->thetas, (void*)b->status, (void*)b->env_l, (void*)b->env_r, (void*)b->e0, (void*)b->e1, (void*)b->vals, (void*)b->bits,
                     (void*)b->jstats})
         if (p) (void)hipFree(p);
@@ -225,7 +241,7 @@ int apply_circuit_all(aqc_mpsb* b, Lanes& s, const aqc_circuit* c, int T, bool i
     if (it == b->schedules.end()) {
         if (b->schedules.size() >= 16) {   // (a driver walks a few horizons; nothing keeps more than a handful of circuits alive)
             HIP_OK(hipStreamSynchronize(b->st));
-            for (auto& kv : b->schedules) { if (kv.second.ops1) (void)hipFree(kv.second.ops1); if (kv.second.ops2) (void)hipFree(kv.second.ops2); }
+            for (auto& kv : b->schedules) kv.second.release();
             b->schedules.clear();
         }
         Schedule sch;
@@ -352,7 +368,7 @@ int load_lanes(aqc_mpsb* b, Lanes& dst, aqc_mps* const* src, int shared) {   // 
         if (aqc_mps_dims(m, dims.data())) return 1;
         for (int q = 0; q <= n; ++q) {
             if (dims[q] > kLaneCap)
-                return failf("lane %d: bond dimension %d exceeds the %d of the lockstep lanes (use the single-lane engine)", l, dims[q], kLaneCap);
+                return refuse("lane %d: bond dimension %d exceeds the %d of the lockstep lanes (use the single-lane engine)", l, dims[q], kLaneCap);
             dims_all[(size_t)l * (n + 1) + q] = dims[q];
             dst.max_dim_in = std::max(dst.max_dim_in, (int)dims[q]);
         }
@@ -390,13 +406,17 @@ int hint_for(int loaded, int produced) {
     for (int h : {4, 6, 8, 12, 16, 20, 24}) if (want <= h) return h;
     return kLaneCap;
 }
-
+// the size of the next phase's launches: full size until a phase has reported what its gates produce
+int next_hint(const aqc_mpsb* b) {
+    const int produced = std::max(b->peak_vh, b->peak_grad);
+    return produced == 0 ? kLaneCap : hint_for(std::max(b->target.max_dim_in, b->lhs.max_dim_in), produced);
+}
 
 // validates, sizes the per-evaluation buffers for `circ` (inner-product slots: amplitudes, then one per parameter) and uploads thetas
 int begin(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double trunc_thr, int max_bond, int num_amps, int* T_out) {
     if (check_circuit(circ, b->n)) return 1;
     if (!(trunc_thr >= 0.0)) return failf("trunc_thr must be non-negative");
-    if (max_bond > kLaneCap) return failf("the lockstep lanes keep bonds up to %d", kLaneCap);
+    if (max_bond > kLaneCap) return refuse("the lockstep lanes keep bonds up to %d", kLaneCap);
     HIP_OK(hipSetDevice(b->device));
     const int n = b->n, L = b->L, tpb = thetas_per_block(circ), T = 3 * n + tpb * circ->num_blocks;
     const int need = num_amps + 3 * n + tpb * (int)blocks_of(circ).size();
@@ -421,8 +441,7 @@ int begin(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double tru
     HIP_OK(hipMemcpyAsync(b->thetas, b->h_thetas, sizeof(double) * (size_t)L * T, hipMemcpyHostToDevice, b->st));
     b->cur_T = T; b->cur_trunc = trunc_thr; b->cur_max_bond = max_bond;
     b->vh_ready = false;
-    b->hint = b->peak_vh + b->peak_grad == 0 ? kLaneCap   // first evaluation: full size
-                                             : hint_for(std::max(b->target.max_dim_in, b->lhs.max_dim_in), std::max(b->peak_vh, b->peak_grad));
+    b->hint = next_hint(b);
     *T_out = T;
     return 0;
 }
@@ -437,25 +456,31 @@ int replicate_half(aqc_mpsb* b, Lanes& s) {
     return 0;
 }
 
-// vh = V^H target on every lane (the first half when the second repeats it), (w, z) = (lhs, vh) with fresh environments, and the
-// amplitudes <lhs|vh> (slot 0), <X_q lhs|vh> (slots 1 + q)
-int enqueue_vh(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half, int num_amps) {
-    const int n = b->n, L = b->L;
-    HIP_OK(hipMemsetAsync(b->status, 0, sizeof(int) * 2 * (size_t)L, b->st));
+// vh = V^H target on every lane (inverse = false: V target, aqc_mpsb_apply_circuit); half: on the first half of the lanes, copied to the second
+int form_vh(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half, bool inverse = true) {
     if (clone(b, b->target, b->vh)) return 1;
-    b->active = half ? L / 2 : L;
-    const int rc = apply_circuit_all(b, b->vh, circ, T, true, b->cur_trunc, b->cur_max_bond);
-    b->active = L;
+    b->active = half ? b->L / 2 : b->L;
+    const int rc = apply_circuit_all(b, b->vh, circ, T, inverse, b->cur_trunc, b->cur_max_bond);
+    b->active = b->L;
     if (rc) return 1;
-    if (half && replicate_half(b, b->vh)) return 1;
-    if (clone(b, b->lhs, b->w) || clone(b, b->vh, b->z)) return 1;
-    if (env_init(b)) return 1;
+    return half ? replicate_half(b, b->vh) : 0;
+}
+
+// (w, z) = (lhs, zsrc) with fresh environments: where a gradient walk and the amplitudes start
+int start_pair(aqc_mpsb* b, const Lanes& zsrc) {
+    if (clone(b, b->lhs, b->w) || clone(b, zsrc, b->z)) return 1;
+    return env_init(b);
+}
+
+// vh as above, (w, z) = (lhs, vh), and the amplitudes <lhs|vh> (slot 0), <X_q lhs|vh> (slots 1 + q)
+int enqueue_vh(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half, int num_amps) {
+    if (form_vh(b, circ, T, half) || start_pair(b, b->vh)) return 1;
     for (int k = 1; k < num_amps; ++k) {   // flips first: site 0 upwards, the right environments are built once on the way down to site 0
         const int q = k - 1;
         const M2* g = &kPauliX;
         if (dot_all(b, k, 1, &q, &g)) return 1;
     }
-    const int q = n - 1;
+    const int q = b->n - 1;
     const M2 eye = {{1.0, 0.0, 0.0, 1.0}};
     const M2* g = &eye;
     return dot_all(b, 0, 1, &q, &g);
@@ -464,20 +489,13 @@ int enqueue_vh(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half, int num_a
 // The same for a bank of lhs states (aqc_mpsb_vh_bank): vh as above, then amps[l][k] = <bank_k|vh_l> in slots k of vals, one launch for all
 // (k, active lane) pairs.  (w, z) and the environments are left alone: the gradient phase starts them itself.
 int enqueue_vh_bank(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half) {
-    const int L = b->L;
-    HIP_OK(hipMemsetAsync(b->status, 0, sizeof(int) * 2 * (size_t)L, b->st));
-    if (clone(b, b->target, b->vh)) return 1;
-    b->active = half ? L / 2 : L;
-    const int rc = apply_circuit_all(b, b->vh, circ, T, true, b->cur_trunc, b->cur_max_bond);
-    b->active = L;
-    if (rc) return 1;
-    if (half && replicate_half(b, b->vh)) return 1;
+    if (form_vh(b, circ, T, half)) return 1;
     const int h = std::max(b->hint, hint_for(b->bank.max_dim_in, 0));
-    HIP_OK(launch_lanes_bank_dot(b->bank.dev, b->bank.L, b->vh.dev, half ? L / 2 : L, b->vals, b->nvals, 0, b->status, h, b->st));
+    HIP_OK(launch_lanes_bank_dot(b->bank.dev, b->bank.L, b->vh.dev, half ? b->L / 2 : b->L, b->vals, b->nvals, 0, b->status, h, b->st));
     return 0;
 }
 
-// results of the enqueued work -> pinned host memory; 0 ok, 2 = a lane outgrew the launch size (the caller repeats at full size), 1 error
+// results of the enqueued work -> pinned host memory; 0 ok, kRepeatAtFullSize = a lane outgrew the launch size, else the failure's status
 int finish(aqc_mpsb* b, bool may_retry, int* peak_out) {
     const int n = b->n, L = b->L;
     char* h_vals = b->h_out;
@@ -494,15 +512,15 @@ int finish(aqc_mpsb* b, bool may_retry, int* peak_out) {
     for (int l = 0; l < L; ++l) { flags |= st[l]; peak = std::max(peak, st[L + l]); }
     if ((flags & kLaneLdsShort) && may_retry && b->hint < kLaneCap) {
         b->hint = kLaneCap;
-        return 2;
+        return kRepeatAtFullSize;
     }
     *peak_out = peak;
     for (int l = 0; l < L; ++l) {
         if (st[l] & kLaneOverflow)
-            return failf("lane %d: a bond grows beyond the %d of the lockstep lanes (set max_bond <= %d or use the single-lane engine)", l, kLaneCap, kLaneCap);
-        if (st[l] & kLaneNoConv) return failf("Jacobi SVD: no convergence within 60 sweeps (lane %d of the lockstep lanes)", l);
-        if (st[l] & kLaneZero) return failf("2-qubit gate produced a zero or non-finite state (lane %d of the lockstep lanes)", l);
-        if (st[l] & kLaneLdsShort) return failf("internal: workgroup of the lockstep lanes too small at full size (lane %d)", l);
+            return refuse("lane %d: a bond grows beyond the %d of the lockstep lanes (set max_bond <= %d or use the single-lane engine)", l, kLaneCap, kLaneCap);
+        if (st[l] & kLaneNoConv) return refuse("Jacobi SVD: no convergence within 60 sweeps (lane %d of the lockstep lanes)", l);
+        if (st[l] & kLaneZero) return refuse("2-qubit gate produced a zero or non-finite state (lane %d of the lockstep lanes)", l);
+        if (st[l] & kLaneLdsShort) return refuse("internal: workgroup of the lockstep lanes too small at full size (lane %d)", l);
     }
     return 0;
 }
@@ -530,6 +548,29 @@ void assemble(const aqc_mpsb* b, const Readback& r, const std::vector<std::pair<
     }
 }
 
+// One phase of work on all lanes, the skeleton of every evaluating entry point: the status words cleared, `enqueue` (the entry point's
+// launches; it waits for nothing), the results brought to the host -- and all of it once more at full size when a lane outgrew the
+// launches.  Then the bookkeeping: *peak = the largest bond a gate produced (also when a lane made finish fail), vh_ready = whether vh
+// now holds V^H target for the thetas of begin, and per lane the discarded weight and largest bond of vh (either output may be null).
+// The entry point copies its own values out of readback().
+template <class Enqueue>
+int run_phase(aqc_mpsb* b, int* peak, bool vh_ready, double* discarded_out, int32_t* max_bond_out, Enqueue enqueue) {
+    int rc = kRepeatAtFullSize;
+    for (int attempt = 0; rc == kRepeatAtFullSize; ++attempt) {
+        HIP_OK(hipMemsetAsync(b->status, 0, sizeof(int) * 2 * (size_t)b->L, b->st));
+        if (enqueue()) return 1;
+        rc = finish(b, attempt == 0, peak);
+    }
+    if (rc) return rc;
+    b->vh_ready = vh_ready;
+    const Readback r = readback(b);
+    for (int l = 0; l < b->L; ++l) {
+        if (discarded_out) discarded_out[l] = r.disc[l];
+        if (max_bond_out) max_bond_out[l] = r.max_dim(l, b->n);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -544,17 +585,16 @@ int aqc_mpsb_create(int device, int num_qubits, int lanes, aqc_mpsb** out) {
     HIP_OK(hipSetDevice(device));
     aqc_mpsb* b = new aqc_mpsb();
     b->device = device; b->n = num_qubits; b->L = lanes; b->active = lanes;
-    auto bad = [&]() { destroy(b); return 1; };
-    if (hipStreamCreate(&b->st) != hipSuccess) { failf("hipStreamCreate failed"); return bad(); }
+    auto bad = [&](int rc) { destroy(b); return rc; };
+    if (hipStreamCreate(&b->st) != hipSuccess) return bad(failf("hipStreamCreate failed"));
     for (Lanes* s : {&b->target, &b->lhs, &b->vh, &b->w, &b->z})
-        if (s->alloc(num_qubits, lanes)) return bad();
+        if (s->alloc(num_qubits, lanes)) return bad(1);
     const size_t L = lanes;
     if (hipMalloc((void**)&b->status, sizeof(int) * 2 * L) != hipSuccess ||
         hipMalloc((void**)&b->env_l, sizeof(double2) * L * kEnvL(num_qubits)) != hipSuccess ||
         hipMalloc((void**)&b->env_r, sizeof(double2) * L * kEnvR(num_qubits)) != hipSuccess ||
         hipMalloc((void**)&b->e0, sizeof(double2) * L * kLaneEnv) != hipSuccess || hipMalloc((void**)&b->e1, sizeof(double2) * L * kLaneEnv) != hipSuccess) {
-        failf("allocation of the lockstep lanes failed (%d lanes, %d qubits)", lanes, num_qubits);
-        return bad();
+        return bad(refuse("allocation of the lockstep lanes failed (%d lanes, %d qubits)", lanes, num_qubits));
     }
     *out = b;
     return 0;
@@ -601,7 +641,7 @@ int aqc_mpsb_gate2_stats(aqc_mpsb* b, int enable, double* out, int reset) {
 int aqc_mpsb_set_targets(aqc_mpsb* b, aqc_mps* const* targets, int shared) {
     if (!b) return failf("null batch");
     HIP_OK(hipSetDevice(b->device));
-    if (load_lanes(b, b->target, targets, shared)) return 1;
+    if (const int rc = load_lanes(b, b->target, targets, shared)) return rc;
     b->have_target = true;
     return 0;
 }
@@ -609,7 +649,7 @@ int aqc_mpsb_set_targets(aqc_mpsb* b, aqc_mps* const* targets, int shared) {
 int aqc_mpsb_set_lhs(aqc_mpsb* b, aqc_mps* const* lhs, int shared) {
     if (!b) return failf("null batch");
     HIP_OK(hipSetDevice(b->device));
-    if (load_lanes(b, b->lhs, lhs, shared)) return 1;
+    if (const int rc = load_lanes(b, b->lhs, lhs, shared)) return rc;
     b->have_lhs = true;
     return 0;
 }
@@ -644,23 +684,8 @@ int aqc_mpsb_apply_circuit(aqc_mpsb* b, const aqc_circuit* circ, const double* t
     if (!b || !circ || !thetas) return failf("null argument");
     if (!b->have_target) return failf("set the states of the lanes first (aqc_mpsb_set_targets)");
     int T = 0;
-    if (begin(b, circ, thetas, trunc_thr, max_bond, 1, &T)) return 1;
-    for (int attempt = 0;; ++attempt) {
-        HIP_OK(hipMemsetAsync(b->status, 0, sizeof(int) * 2 * (size_t)b->L, b->st));
-        if (clone(b, b->target, b->vh)) return 1;
-        if (apply_circuit_all(b, b->vh, circ, T, inverse != 0, trunc_thr, max_bond)) return 1;
-        const int rc = finish(b, attempt == 0, &b->peak_vh);
-        if (rc == 2) continue;
-        if (rc) return 1;
-        break;
-    }
-    const Readback r = readback(b);
-    for (int l = 0; l < b->L; ++l) {
-        if (discarded_out) discarded_out[l] = r.disc[l];
-        if (max_bond_out) max_bond_out[l] = r.max_dim(l, b->n);
-    }
-    b->vh_ready = inverse != 0;
-    return 0;
+    if (const int rc = begin(b, circ, thetas, trunc_thr, max_bond, 1, &T)) return rc;
+    return run_phase(b, &b->peak_vh, inverse != 0, discarded_out, max_bond_out, [&] { return form_vh(b, circ, T, false, inverse != 0); });
 }
 
 /* lane `lane` of the working state (the result of aqc_mpsb_apply_circuit / aqc_mpsb_vh) as a single-lane MPS of its own */
@@ -694,23 +719,12 @@ int aqc_mpsb_vh(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, doub
     if (num_amps != 1 && num_amps != 1 + b->n) return failf("num_amps: 1 (<lhs|vh>) or 1 + n (and the single-flip amplitudes)");
     if (half && (b->L & 1)) return failf("half: the batch needs an even number of lanes");
     int T = 0;
-    if (begin(b, circ, thetas, trunc_thr, max_bond, num_amps, &T)) return 1;
-    const int L = b->L;
-    for (int attempt = 0;; ++attempt) {
-        if (enqueue_vh(b, circ, T, half != 0, num_amps)) return 1;
-        const int rc = finish(b, attempt == 0, &b->peak_vh);
-        if (rc == 2) continue;
-        if (rc) return 1;
-        break;
-    }
+    if (const int rc = begin(b, circ, thetas, trunc_thr, max_bond, num_amps, &T)) return rc;
+    if (const int rc = run_phase(b, &b->peak_vh, true, discarded_out, max_bond_out, [&] { return enqueue_vh(b, circ, T, half != 0, num_amps); })) return rc;
     const Readback r = readback(b);
     cd* out = reinterpret_cast<cd*>(amps);
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < b->L; ++l)
         for (int k = 0; k < num_amps; ++k) out[(size_t)l * num_amps + k] = r.vals[(size_t)l * b->nvals + k];
-        if (discarded_out) discarded_out[l] = r.disc[l];
-        if (max_bond_out) max_bond_out[l] = r.max_dim(l, b->n);
-    }
-    b->vh_ready = true;
     return 0;
 }
 
@@ -725,7 +739,7 @@ int aqc_mpsb_set_bank(aqc_mpsb* b, aqc_mps* const* states, int count) {
         b->bank.release();
         if (b->bank.alloc(b->n, count)) { b->bank.L = 0; return 1; }
     }
-    if (load_lanes(b, b->bank, states, 0)) return 1;
+    if (const int rc = load_lanes(b, b->bank, states, 0)) return rc;
     b->have_bank = true;
     return 0;
 }
@@ -739,24 +753,15 @@ int aqc_mpsb_vh_bank(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas,
     if (num_amps != b->bank.L) return failf("num_amps: the bank holds %d states", b->bank.L);
     if (half && (b->L & 1)) return failf("half: the batch needs an even number of lanes");
     int T = 0;
-    if (begin(b, circ, thetas, trunc_thr, max_bond, num_amps, &T)) return 1;
-    const int L = b->L;
-    for (int attempt = 0;; ++attempt) {
-        if (enqueue_vh_bank(b, circ, T, half != 0)) return 1;
-        const int rc = finish(b, attempt == 0, &b->peak_vh);
-        if (rc == 2) continue;
-        if (rc) return 1;
-        break;
-    }
+    if (const int rc = begin(b, circ, thetas, trunc_thr, max_bond, num_amps, &T)) return rc;
+    if (const int rc = run_phase(b, &b->peak_vh, true, discarded_out, max_bond_out, [&] { return enqueue_vh_bank(b, circ, T, half != 0); })) return rc;
     const Readback r = readback(b);
     cd* out = reinterpret_cast<cd*>(amps);
+    const int L = b->L;
     for (int l = 0; l < L; ++l) {
-        const int src = half && l >= L / 2 ? l - L / 2 : l;
+        const int src = half && l >= L / 2 ? l - L / 2 : l;   // (the overlaps were taken for the first half only)
         for (int k = 0; k < num_amps; ++k) out[(size_t)l * num_amps + k] = r.vals[(size_t)src * b->nvals + k];
-        if (discarded_out) discarded_out[l] = r.disc[l];
-        if (max_bond_out) max_bond_out[l] = r.max_dim(l, b->n);
     }
-    b->vh_ready = true;
     return 0;
 }
 
@@ -768,24 +773,16 @@ int aqc_mpsb_grad(aqc_mpsb* b, const aqc_circuit* circ, int block_from, int bloc
     if (!b->have_lhs) return failf("set the lhs states of the lanes first");
     if (check_circuit(circ, b->n)) return 1;
     HIP_OK(hipSetDevice(b->device));
-    const int n = b->n, L = b->L, tpb = thetas_per_block(circ), T = 3 * n + tpb * circ->num_blocks;
+    const int n = b->n, tpb = thetas_per_block(circ), T = 3 * n + tpb * circ->num_blocks;
     if (T != b->cur_T || 3 * n + tpb * (int)blocks_of(circ).size() > b->nvals) return failf("aqc_mpsb_grad: not the circuit of the last aqc_mpsb_vh");
-    if (block_from < 0) { block_from = 0; block_to = circ->num_blocks; }
-    if (block_from > block_to || block_to > circ->num_blocks) return failf("invalid block range");
+    if (check_block_range(circ, block_from, block_to)) return 1;
     std::vector<std::pair<int, cd>> rec;
-    b->hint = b->peak_vh + b->peak_grad == 0 ? kLaneCap : hint_for(std::max(b->target.max_dim_in, b->lhs.max_dim_in), std::max(b->peak_vh, b->peak_grad));
-    for (int attempt = 0;; ++attempt) {
-        HIP_OK(hipMemsetAsync(b->status, 0, sizeof(int) * 2 * (size_t)L, b->st));
-        if (clone(b, b->lhs, b->w) || clone(b, b->vh, b->z)) return 1;
-        if (env_init(b)) return 1;
-        if (gradient_all(b, circ, T, b->cur_trunc, b->cur_max_bond, block_from, block_to, front_layer != 0, 0, rec)) return 1;
-        const int rc = finish(b, attempt == 0, &b->peak_grad);
-        if (rc == 2) continue;
-        if (rc) return 1;
-        break;
-    }
-    const Readback r = readback(b);
-    assemble(b, r, rec, 0, T, reinterpret_cast<cd*>(grad_out));
+    b->hint = next_hint(b);
+    if (const int rc = run_phase(b, &b->peak_grad, true, nullptr, nullptr, [&] {
+            return start_pair(b, b->vh) || gradient_all(b, circ, T, b->cur_trunc, b->cur_max_bond, block_from, block_to, front_layer != 0, 0, rec);
+        }))
+        return rc;
+    assemble(b, readback(b), rec, 0, T, reinterpret_cast<cd*>(grad_out));
     return 0;
 }
 
@@ -796,20 +793,13 @@ int aqc_mpsb_gradient_of(aqc_mpsb* b, const aqc_circuit* circ, const double* the
     if (!b || !circ || !thetas || !grad_out) return failf("null argument");
     if (!b->have_target || !b->have_lhs) return failf("set the vh_phi states (aqc_mpsb_set_targets) and the lhs states of the lanes first");
     int T = 0;
-    if (begin(b, circ, thetas, trunc_thr, max_bond, 0, &T)) return 1;
-    if (block_from < 0) { block_from = 0; block_to = circ->num_blocks; }
-    if (block_from > block_to || block_to > circ->num_blocks) return failf("invalid block range");
+    if (const int rc = begin(b, circ, thetas, trunc_thr, max_bond, 0, &T)) return rc;
+    if (check_block_range(circ, block_from, block_to)) return 1;
     std::vector<std::pair<int, cd>> rec;
-    for (int attempt = 0;; ++attempt) {
-        HIP_OK(hipMemsetAsync(b->status, 0, sizeof(int) * 2 * (size_t)b->L, b->st));
-        if (clone(b, b->lhs, b->w) || clone(b, b->target, b->z)) return 1;
-        if (env_init(b)) return 1;
-        if (gradient_all(b, circ, T, trunc_thr, max_bond, block_from, block_to, front_layer != 0, 0, rec)) return 1;
-        const int rc = finish(b, attempt == 0, &b->peak_grad);
-        if (rc == 2) continue;
-        if (rc) return 1;
-        break;
-    }
+    if (const int rc = run_phase(b, &b->peak_grad, false, nullptr, nullptr, [&] {   // (vh is not involved: z starts from the states given as targets)
+            return start_pair(b, b->target) || gradient_all(b, circ, T, trunc_thr, max_bond, block_from, block_to, front_layer != 0, 0, rec);
+        }))
+        return rc;
     assemble(b, readback(b), rec, 0, T, reinterpret_cast<cd*>(grad_out));
     return 0;
 }
@@ -820,28 +810,17 @@ int aqc_mpsb_eval(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, do
     if (!b || !circ || !thetas || !h_out || !grad_out) return failf("null argument");
     if (!b->have_target || !b->have_lhs) return failf("set the targets and the lhs states of the lanes first");
     int T = 0;
-    if (begin(b, circ, thetas, trunc_thr, max_bond, 1, &T)) return 1;
-    const int L = b->L;
-    if (block_from < 0) { block_from = 0; block_to = circ->num_blocks; }
-    if (block_from > block_to || block_to > circ->num_blocks) return failf("invalid block range");
+    if (const int rc = begin(b, circ, thetas, trunc_thr, max_bond, 1, &T)) return rc;
+    if (check_block_range(circ, block_from, block_to)) return 1;
     std::vector<std::pair<int, cd>> rec;
-    for (int attempt = 0;; ++attempt) {
-        if (enqueue_vh(b, circ, T, false, 1)) return 1;   // leaves (w, z) = (lhs, vh) with their environments started
-        if (gradient_all(b, circ, T, trunc_thr, max_bond, block_from, block_to, front_layer != 0, 1, rec)) return 1;
-        const int rc = finish(b, attempt == 0, &b->peak_vh);
-        if (rc == 2) continue;
-        if (rc) return 1;
-        break;
-    }
+    if (const int rc = run_phase(b, &b->peak_vh, true, discarded_out, max_bond_out, [&] {   // enqueue_vh leaves (w, z) = (lhs, vh), environments started
+            return enqueue_vh(b, circ, T, false, 1) || gradient_all(b, circ, T, trunc_thr, max_bond, block_from, block_to, front_layer != 0, 1, rec);
+        }))
+        return rc;
     b->peak_grad = 0;   // (peak_vh covers the whole evaluation here)
-    b->vh_ready = true;
     const Readback r = readback(b);
     cd* hh = reinterpret_cast<cd*>(h_out);
-    for (int l = 0; l < L; ++l) {
-        hh[l] = r.vals[(size_t)l * b->nvals];
-        if (discarded_out) discarded_out[l] = r.disc[l];
-        if (max_bond_out) max_bond_out[l] = r.max_dim(l, b->n);
-    }
+    for (int l = 0; l < b->L; ++l) hh[l] = r.vals[(size_t)l * b->nvals];
     assemble(b, r, rec, 1, T, reinterpret_cast<cd*>(grad_out));
     return 0;
 }

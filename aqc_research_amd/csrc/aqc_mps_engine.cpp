@@ -649,8 +649,7 @@ int aqc_mps_fast_dot_gradient(const aqc_circuit* circ, const aqc_mps* lvec, cons
     if (lvec->n != vh_phi->n || lvec->device != vh_phi->device) return failf("MPS operands differ in size or device");
     if (check_circuit(circ, lvec->n)) return 1;
     if (!(trunc_thr >= 0.0)) return failf("trunc_thr must be non-negative");
-    if (block_from < 0) { block_from = 0; block_to = circ->num_blocks; }
-    if (block_from > block_to || block_to > circ->num_blocks) return failf("invalid block range");
+    if (check_block_range(circ, block_from, block_to)) return 1;
     HIP_OK(hipSetDevice(lvec->device));
     aqc_mps *w = nullptr, *z = nullptr;
     if (aqc_mps_clone(lvec, &w)) return 1;

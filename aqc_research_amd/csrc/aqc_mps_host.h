@@ -1,5 +1,5 @@
 // Host-side helpers shared by the single-lane MPS engine (aqc_mps_engine.cpp) and the lockstep lanes (aqc_mps_batch.cpp): error
-// reporting, the check of a circuit description.  The gates themselves -- 2 x 2 algebra, entangler matrices, the block list and the walk of
+// reporting, the checks of a circuit description and of a block range.  The gates themselves -- 2 x 2 algebra, entangler matrices, the block list and the walk of
 // an ansatz -- are stated in aqc_mps_walk.h (included through aqc_launch.h).  Private to csrc/ (everything has internal linkage).
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -46,6 +46,13 @@ namespace {
         const int ct = c->blocks[b], tg = c->blocks[c->num_blocks + b];
         if (ct < 0 || ct >= n || tg < 0 || tg >= n || ct == tg) return failf("block %d couples invalid qubits", b);
     }
+    return 0;
+}
+
+// block range of a gradient walk: block_from < 0 stands for all blocks of the circuit
+[[maybe_unused]] int check_block_range(const aqc_circuit* c, int& block_from, int& block_to) {
+    if (block_from < 0) { block_from = 0; block_to = c->num_blocks; }
+    if (block_from > block_to || block_to > c->num_blocks) return failf("invalid block range");
     return 0;
 }
 

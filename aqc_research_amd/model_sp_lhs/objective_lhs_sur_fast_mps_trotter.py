@@ -7,6 +7,7 @@ semantics the reference's tests pin for trunc_thr -> 0.
 """
 from typing import Optional, Tuple
 
+from .._lib import LanesRefused
 from ..engine import BUF_Y
 from ..mps_operations import DenseBackedMPS, check_mps, mps_num_qubits
 from ..parametric_circuit import TrotterAnsatz, first_layer_included, layer_to_block_range
@@ -129,9 +130,7 @@ class SpSurrogateObjectiveFastMpsTrotter(SpSurrogateObjectiveMax):
                     self._hs[:] = lk.apply_vh(self._circuit, np.stack([th, th]), trunc_thr=self._trunc_thr, flips=True, half=True)[0]
                 self._lk_live = True
                 return
-            except RuntimeError as err:
-                if "lockstep lanes" not in str(err):
-                    raise
+            except LanesRefused:
                 self._leave_lanes()   # a bond outgrew the lanes: this objective stays on the single-lane engine
         self._single_lane_vh(thetas)
         for i in range(self._num_states):
@@ -158,12 +157,10 @@ class SpSurrogateObjectiveFastMpsTrotter(SpSurrogateObjectiveMax):
         try:
             self._lk.set_lhs([prep.device_state(state_a), prep.device_state(state_b)])
             return self._lk.gradient(self._circuit, block_range=self._block_range, front_layer=front)
-        except RuntimeError as err:
-            if "lockstep lanes" not in str(err):
-                raise
-        self._leave_lanes()
-        self._single_lane_vh(self._last_thetas)
-        return None
+        except LanesRefused:
+            self._leave_lanes()
+            self._single_lane_vh(self._last_thetas)
+            return None
 
     def _sweep(self, state_no: int, front: bool):
         if not self._native_mps:

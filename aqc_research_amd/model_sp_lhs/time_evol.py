@@ -20,6 +20,7 @@ from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
+from .._lib import LanesRefused
 from ..job_executor import run_jobs
 from ..mps_operations import DenseBackedMPS, check_mps, mps_dot, mps_to_vector, no_truncation_threshold
 from ..optimizer import AqcOptimizer, EarlyStopper, GradientAmplifier, TimeoutChecker
@@ -313,9 +314,7 @@ def _seeded_horizon_job(job_index: int, cfg: Dict) -> Dict:
             try:
                 bo = BatchedMpsSurrogateObjective(circ, target_dev, lanes=opts.num_seeds, base_index=ini, trunc_thr=float(opts.trunc_thr), device=opts.device)
                 res = batched_lbfgs(bo.value_and_grad, starts, maxiter=opts.maxiter, stop=lambda f, x: bo.fidelity >= fid_thr)
-            except RuntimeError as err:
-                if "lockstep lanes" not in str(err):
-                    raise
+            except LanesRefused:
                 if bo is not None:
                     bo.close()
                 bo = None            # a bond beyond the lanes' 32 (long horizons: the untruncated target alone can exceed it)

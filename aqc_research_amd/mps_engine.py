@@ -10,12 +10,13 @@ against the dense oracle); Aer's truncation arithmetic itself is third party and
 """
 import ctypes
 from ctypes import POINTER, byref, c_int, c_int32, c_void_p
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import numpy as np
 
 from . import _lib, gates
-from ._lib import check, dptr
+from ._lib import LanesRefused, check, dptr
 
 _X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
 _Y = np.array([[0, -1j], [1j, 0]], dtype=np.complex128)
@@ -269,6 +270,16 @@ def _thetas(circ, thetas) -> np.ndarray:
     return th
 
 
+def _block_range(circ, block_range) -> Tuple[int, int]:
+    """(block_from, block_to) as the ABI takes them; (-1, -1): all blocks."""
+    if block_range is None:
+        return -1, -1
+    lo, hi = int(block_range[0]), int(block_range[1])
+    if not 0 <= lo <= hi <= circ.num_blocks:
+        raise ValueError("invalid block range")
+    return lo, hi
+
+
 def _apply_circuit(circ, thetas, mps: DeviceMPS, inverse: bool, trunc_thr: float, max_bond: int) -> DeviceMPS:
     """The whole ansatz in ONE ABI call (``aqc_mps_apply_circuit``)."""
     desc, keep = _describe(circ)
@@ -315,25 +326,34 @@ def _apply_circuit_gatewise(circ, thetas, mps: DeviceMPS, inverse: bool, trunc_t
     return mps
 
 
+def _fits_a_lane(num_qubits: int, max_bond: int, operands) -> bool:
+    """Whether a call can start on the lockstep lanes: a register of two qubits or more, a bond cap and operands (all of the
+    register's size) within ``LOCKSTEP_MAX_BOND``.  A bond that outgrows the lanes on the way is theirs to refuse (``LanesRefused``)."""
+    return (num_qubits >= 2 and max_bond <= LOCKSTEP_MAX_BOND
+            and all(m.num_qubits == num_qubits and int(m.bond_dims.max()) <= LOCKSTEP_MAX_BOND for m in operands))
+
+
+def _one_lane(kind: str, like: DeviceMPS) -> "LockstepLanes":
+    """The calling thread's single lockstep lane for ``kind`` of work, on the device and of the size of ``like`` (a lane of its own per
+    host thread: the thread lanes of ``evaluate_lanes`` call in parallel)."""
+    import threading
+
+    n, dev = like.num_qubits, int(_lib.lib().aqc_mps_device(like.handle))
+    return _lockstep_cached((dev, n, 1, kind, threading.get_ident()), 6, lambda: LockstepLanes(n, 1, dev))
+
+
 def _apply_on_a_lane(circ, thetas, mps: DeviceMPS, inverse: bool, trunc_thr: float, max_bond: int) -> Optional[DeviceMPS]:
     """The circuit on a copy of ``mps`` through ONE lockstep lane (``LockstepLanes.apply_circuit``: the gates of a circuit layer in one
     launch, ranks decided on the device -- a 32-qubit Trotter circuit in a few milliseconds where the single-lane engine's launch chain
     takes tens); None when the state, the bond cap or a bond met on the way does not fit the lanes (bonds <= 32)."""
-    n = circ.num_qubits
-    if n < 2 or max_bond > LOCKSTEP_MAX_BOND or mps.num_qubits != n or int(mps.bond_dims.max()) > LOCKSTEP_MAX_BOND:
+    if not _fits_a_lane(circ.num_qubits, max_bond, [mps]):
         return None
-    import threading
-
-    dev = int(_lib.lib().aqc_mps_device(mps.handle))
-    key = (dev, n, 1, "apply", threading.get_ident())   # (a lane of its own per host thread: the thread lanes of evaluate_lanes call in parallel)
-    ls = _lockstep_cached(key, 6, lambda: LockstepLanes(n, 1, dev))
+    ls = _one_lane("apply", mps)
     try:
         ls.set_targets(mps)
         ls.apply_circuit(circ, np.asarray(thetas, dtype=np.float64)[None, :], inverse=inverse, trunc_thr=trunc_thr, max_bond=max_bond)
         return ls.export(0)
-    except RuntimeError as err:
-        if "lockstep lanes" not in str(err):
-            raise
+    except LanesRefused:
         return None
 
 
@@ -346,30 +366,27 @@ def _apply_method(method: Optional[str]) -> str:
     return method
 
 
-def v_mul_mps(circ, thetas, mps: DeviceMPS, trunc_thr: float = 0.0, max_bond: int = 0, method: Optional[str] = None) -> DeviceMPS:
-    """V(thetas)|mps> on a copy (mps_operations.py:326-346).  ``method``: "single" -- the single-lane engine (one whole-circuit ABI
-    call, any bond); "lockstep" / "auto" -- through one lockstep lane while bonds stay <= 32 ("auto" falls back to "single"); None:
-    the environment's AQC_MPS_APPLY, else "auto"."""
+def _apply(circ, thetas, mps: DeviceMPS, inverse: bool, trunc_thr: float, max_bond: int, method: Optional[str]) -> DeviceMPS:
     method = _apply_method(method)
     if method != "single":
-        out = _apply_on_a_lane(circ, thetas, mps, False, trunc_thr, max_bond)
+        out = _apply_on_a_lane(circ, thetas, mps, inverse, trunc_thr, max_bond)
         if out is not None:
             return out
         if method == "lockstep":
-            raise RuntimeError("aqc_hip: the state or a bond on the way exceeds the lockstep lanes (bonds <= 32)")
-    return _apply_circuit(circ, thetas, mps.clone(), False, trunc_thr, max_bond)
+            raise LanesRefused("aqc_hip: the state or a bond on the way exceeds the lockstep lanes (bonds <= 32)")
+    return _apply_circuit(circ, thetas, mps.clone(), inverse, trunc_thr, max_bond)
+
+
+def v_mul_mps(circ, thetas, mps: DeviceMPS, trunc_thr: float = 0.0, max_bond: int = 0, method: Optional[str] = None) -> DeviceMPS:
+    """V(thetas)|mps> on a copy (mps_operations.py:326-346).  ``method``: "single" -- the single-lane engine (one whole-circuit ABI
+    call, any bond); "lockstep" / "auto" -- through one lockstep lane while bonds stay <= 32 ("auto" falls back to "single",
+    "lockstep" raises ``LanesRefused``); None: the environment's AQC_MPS_APPLY, else "auto"."""
+    return _apply(circ, thetas, mps, False, trunc_thr, max_bond, method)
 
 
 def v_dagger_mul_mps(circ, thetas, mps: DeviceMPS, trunc_thr: float = 0.0, max_bond: int = 0, method: Optional[str] = None) -> DeviceMPS:
     """V(thetas)^H|mps> on a copy (mps_operations.py:349-371); ``method`` as in ``v_mul_mps``."""
-    method = _apply_method(method)
-    if method != "single":
-        out = _apply_on_a_lane(circ, thetas, mps, True, trunc_thr, max_bond)
-        if out is not None:
-            return out
-        if method == "lockstep":
-            raise RuntimeError("aqc_hip: the state or a bond on the way exceeds the lockstep lanes (bonds <= 32)")
-    return _apply_circuit(circ, thetas, mps.clone(), True, trunc_thr, max_bond)
+    return _apply(circ, thetas, mps, True, trunc_thr, max_bond, method)
 
 
 def fast_dot_gradient_mps(circ, thetas, lvec: DeviceMPS, vh_phi: DeviceMPS, *, trunc_thr: float = 0.0, max_bond: int = 0,
@@ -382,30 +399,22 @@ def fast_dot_gradient_mps(circ, thetas, lvec: DeviceMPS, vh_phi: DeviceMPS, *, t
     (``aqc_mps_fast_dot_gradient``) otherwise; ``method`` as in ``v_mul_mps``."""
     desc, keep = _describe(circ)
     th = _thetas(circ, thetas)
-    lo, hi = (-1, -1) if block_range is None else (int(block_range[0]), int(block_range[1]))
-    if block_range is not None and not 0 <= lo <= hi <= circ.num_blocks:
-        raise ValueError("invalid block range")
+    lo, hi = _block_range(circ, block_range)
     grad = np.zeros(circ.num_thetas, dtype=np.complex128)
     method = _apply_method(method)
-    n = circ.num_qubits
-    if (method != "single" and n >= 2 and max_bond <= LOCKSTEP_MAX_BOND and lvec.num_qubits == n == vh_phi.num_qubits
-            and max(int(lvec.bond_dims.max()), int(vh_phi.bond_dims.max())) <= LOCKSTEP_MAX_BOND):
-        import threading
-
-        dev = int(_lib.lib().aqc_mps_device(vh_phi.handle))   # one lockstep lane: the walk is a chain of fused steps instead of ~10 launches per gate
-        key = (dev, n, 1, "gradient", threading.get_ident())
-        ls = _lockstep_cached(key, 6, lambda: LockstepLanes(n, 1, dev))
+    if method != "single" and _fits_a_lane(circ.num_qubits, max_bond, [lvec, vh_phi]):
+        ls = _one_lane("gradient", vh_phi)   # one lockstep lane: the walk is a chain of fused steps instead of ~10 launches per gate
         try:
             ls.set_targets(vh_phi).set_lhs(lvec)
             check(_lib.lib().aqc_mpsb_gradient_of(ls.handle, byref(desc), dptr(th), float(trunc_thr), int(max_bond), lo, hi, int(bool(front_layer)),
                                                   dptr(grad)))
             del keep
             return grad
-        except RuntimeError as err:
-            if method == "lockstep" or "lockstep lanes" not in str(err):
+        except LanesRefused:
+            if method == "lockstep":
                 raise
     elif method == "lockstep":
-        raise RuntimeError("aqc_hip: the operands exceed the lockstep lanes (bonds <= 32)")
+        raise LanesRefused("aqc_hip: the operands exceed the lockstep lanes (bonds <= 32)")
     check(_lib.lib().aqc_mps_fast_dot_gradient(byref(desc), lvec.handle, vh_phi.handle, dptr(th), float(trunc_thr), int(max_bond),
                                                lo, hi, int(bool(front_layer)), dptr(grad)))
     del keep
@@ -515,46 +524,60 @@ class LockstepLanes:
         arr = (c_void_p * len(lst))(*[m.handle for m in lst])
         return lst, arr, int(len(lst) == 1)
 
-    def set_targets(self, targets) -> "LockstepLanes":
-        """Copies |phi_l> of every lane into the lanes (one state per lane, or one for all).  A call with the very states of the
-        previous one, unchanged since (``DeviceMPS.version``), is free: the batches of an optimisation come back every iteration."""
-        lst, arr, shared = self._handles(targets)
-        stamp = [(m.serial, m.version) for m in lst]   # (no reference to the states: a closed one is not kept alive by its copy)
-        if self._targets != stamp:
-            check(_lib.lib().aqc_mpsb_set_targets(self.handle, arr, shared))
-            self._targets = stamp
+    def _load(self, slot: str, states, load) -> "LockstepLanes":
+        """``load()`` copies ``states`` into the lanes -- unless they hold exactly these states, unchanged since (``DeviceMPS.version``):
+        the batches of an optimisation come back every iteration.  The stamp remembered in ``slot`` holds no reference to the states (a
+        closed one is not kept alive by its copy), and is dropped before the copy so that a failed one is never taken for the old."""
+        stamp = [(m.serial, m.version) for m in states]
+        if getattr(self, slot) != stamp:
+            setattr(self, slot, None)
+            load()
+            setattr(self, slot, stamp)
         return self
 
+    def set_targets(self, targets) -> "LockstepLanes":
+        """Copies |phi_l> of every lane into the lanes (one state per lane, or one for all).  A call with the very states of the
+        previous one, unchanged since, is free.  (``_load`` forgets the remembered states before it copies: after a failed copy the
+        lanes hold neither the old nor the new ones, and the next call copies again.)"""
+        lst, arr, shared = self._handles(targets)
+        return self._load("_targets", lst, lambda: check(_lib.lib().aqc_mpsb_set_targets(self.handle, arr, shared)))
+
     def set_lhs(self, lhs) -> "LockstepLanes":
-        """The same for the left-hand states <lhs_l|."""
+        """The same for the left-hand states <lhs_l| (a failed copy is forgotten in the same way)."""
         lst, arr, shared = self._handles(lhs)
-        stamp = [(m.serial, m.version) for m in lst]
-        if self._lhs != stamp:
-            check(_lib.lib().aqc_mpsb_set_lhs(self.handle, arr, shared))
-            self._lhs = stamp
-        return self
+        return self._load("_lhs", lst, lambda: check(_lib.lib().aqc_mpsb_set_lhs(self.handle, arr, shared)))
+
+    def _call(self, circ, thetas=None, block_range=None) -> SimpleNamespace:
+        """What the calls below hand to the ABI.  Always: ``circ`` (pointer to the descriptor ``desc``, whose block array ``keep``
+        lives as long as the returned object) and the block range ``lo``, ``hi``.  With ``thetas`` (every call but ``gradient``):
+        ``th``, checked against (lanes, num_thetas) and the lanes' size, and the per-lane outputs such a call fills -- ``disc``
+        (discarded weight), ``bonds`` (largest bond of the working state), ``details`` (their two pointers)."""
+        c = SimpleNamespace()
+        if thetas is not None:
+            th = np.ascontiguousarray(thetas, dtype=np.float64)
+            if th.shape != (self.lanes, circ.num_thetas):
+                raise ValueError("thetas: expects shape (lanes, circ.num_thetas)")
+            if circ.num_qubits != self.num_qubits:
+                raise ValueError("circuit and lanes differ in the number of qubits")
+            c.th = th
+            c.disc = np.zeros(self.lanes, dtype=np.float64)
+            c.bonds = np.zeros(self.lanes, dtype=np.int32)
+            c.details = (dptr(c.disc), c.bonds.ctypes.data_as(POINTER(c_int32)))
+        c.desc, c.keep = _describe(circ)
+        c.circ = byref(c.desc)
+        c.lo, c.hi = _block_range(circ, block_range)
+        return c
 
     def evaluate(self, circ, thetas, *, trunc_thr: float = 0.0, max_bond: int = 0, block_range: Optional[Tuple[int, int]] = None,
                  front_layer: bool = True, details: bool = False):
         """(h[lanes], grads[lanes][T]) -- per lane the values of ``v_dagger_mul_mps`` + ``dot`` + ``fast_dot_gradient_mps``;
         with ``details`` also (discarded weight, largest bond) of every lane's V^H|target>."""
-        th = np.ascontiguousarray(thetas, dtype=np.float64)
-        if th.shape != (self.lanes, circ.num_thetas):
-            raise ValueError("thetas: expects shape (lanes, circ.num_thetas)")
-        if circ.num_qubits != self.num_qubits:
-            raise ValueError("circuit and lanes differ in the number of qubits")
-        desc, keep = _describe(circ)
-        lo, hi = (-1, -1) if block_range is None else (int(block_range[0]), int(block_range[1]))
-        if block_range is not None and not 0 <= lo <= hi <= circ.num_blocks:
-            raise ValueError("invalid block range")
+        c = self._call(circ, thetas, block_range)
         h = np.zeros(self.lanes, dtype=np.complex128)
         grads = np.zeros((self.lanes, circ.num_thetas), dtype=np.complex128)
-        disc = np.zeros(self.lanes, dtype=np.float64)
-        bonds = np.zeros(self.lanes, dtype=np.int32)
-        check(_lib.lib().aqc_mpsb_eval(self.handle, byref(desc), dptr(th), float(trunc_thr), int(max_bond), lo, hi, int(bool(front_layer)),
-                                       dptr(h), dptr(grads), dptr(disc), bonds.ctypes.data_as(POINTER(c_int32))))
-        del keep
-        return (h, grads, disc, bonds) if details else (h, grads)
+        check(_lib.lib().aqc_mpsb_eval(self.handle, c.circ, dptr(c.th), float(trunc_thr), int(max_bond), c.lo, c.hi, int(bool(front_layer)),
+                                       dptr(h), dptr(grads), *c.details))
+        return (h, grads, c.disc, c.bonds) if details else (h, grads)
 
     def set_lhs_basis(self, bits) -> "LockstepLanes":
         """lhs state of every lane = the computational-basis state ``bits[lane][qubit]`` (0 / 1), built on the device."""
@@ -569,33 +592,19 @@ class LockstepLanes:
         """Phase 1 of ``evaluate``: vh_l = V(thetas[l])^H|target_l> stays in the lanes; returns amps[lanes][1 (+ n)] with
         amps[l][0] = <lhs_l|vh_l> and, with ``flips``, amps[l][1 + q] = <X_q lhs_l|vh_l>.  ``half``: lanes [lanes/2, lanes) repeat targets
         and thetas of the first half -- V^H runs once for both.  ``gradient`` continues from here."""
-        th = np.ascontiguousarray(thetas, dtype=np.float64)
-        if th.shape != (self.lanes, circ.num_thetas) or circ.num_qubits != self.num_qubits:
-            raise ValueError("thetas: expects shape (lanes, circ.num_thetas) on a circuit of the lanes' size")
-        desc, keep = _describe(circ)
+        c = self._call(circ, thetas)
         na = 1 + self.num_qubits if flips else 1
         amps = np.zeros((self.lanes, na), dtype=np.complex128)
-        disc = np.zeros(self.lanes, dtype=np.float64)
-        bonds = np.zeros(self.lanes, dtype=np.int32)
-        check(_lib.lib().aqc_mpsb_vh(self.handle, byref(desc), dptr(th), float(trunc_thr), int(max_bond), int(bool(half)), na, dptr(amps), dptr(disc),
-                                     bonds.ctypes.data_as(POINTER(c_int32))))
-        del keep
-        return (amps, disc, bonds) if details else amps
+        check(_lib.lib().aqc_mpsb_vh(self.handle, c.circ, dptr(c.th), float(trunc_thr), int(max_bond), int(bool(half)), na, dptr(amps), *c.details))
+        return (amps, c.disc, c.bonds) if details else amps
 
     def set_bank(self, states) -> "LockstepLanes":
         """A bank of K lhs states shared by all lanes (``aqc_mpsb_set_bank``; bonds <= 32): the states S|0>, S X_i|0> of a general
-        state preparation, whose amplitudes ``apply_vh_bank`` returns.  Unchanged states since the last call (``DeviceMPS.version``)
-        are not copied again."""
+        state preparation, whose amplitudes ``apply_vh_bank`` returns.  Unchanged states since the last call are not copied again."""
         lst = list(states)
         if not lst:
             raise ValueError("the bank needs at least one state")
-        stamp = [(m.serial, m.version) for m in lst]
-        if self._bank != stamp:
-            self._bank = None
-            arr = (c_void_p * len(lst))(*[m.handle for m in lst])
-            check(_lib.lib().aqc_mpsb_set_bank(self.handle, arr, len(lst)))
-            self._bank = stamp
-        return self
+        return self._load("_bank", lst, lambda: check(_lib.lib().aqc_mpsb_set_bank(self.handle, (c_void_p * len(lst))(*[m.handle for m in lst]), len(lst))))
 
     def apply_vh_bank(self, circ, thetas, *, trunc_thr: float = 0.0, max_bond: int = 0, half: bool = False, details: bool = False):
         """``apply_vh`` with the bank as the lhs side: vh_l = V(thetas[l])^H|target_l> stays in the lanes; returns amps[lanes][K] with
@@ -603,32 +612,18 @@ class LockstepLanes:
         here with whatever lhs states are set then."""
         if not self._bank:
             raise RuntimeError("aqc_hip: set the bank of the lanes first (set_bank)")
-        th = np.ascontiguousarray(thetas, dtype=np.float64)
-        if th.shape != (self.lanes, circ.num_thetas) or circ.num_qubits != self.num_qubits:
-            raise ValueError("thetas: expects shape (lanes, circ.num_thetas) on a circuit of the lanes' size")
-        desc, keep = _describe(circ)
+        c = self._call(circ, thetas)
         na = len(self._bank)
         amps = np.zeros((self.lanes, na), dtype=np.complex128)
-        disc = np.zeros(self.lanes, dtype=np.float64)
-        bonds = np.zeros(self.lanes, dtype=np.int32)
-        check(_lib.lib().aqc_mpsb_vh_bank(self.handle, byref(desc), dptr(th), float(trunc_thr), int(max_bond), int(bool(half)), na, dptr(amps),
-                                          dptr(disc), bonds.ctypes.data_as(POINTER(c_int32))))
-        del keep
-        return (amps, disc, bonds) if details else amps
+        check(_lib.lib().aqc_mpsb_vh_bank(self.handle, c.circ, dptr(c.th), float(trunc_thr), int(max_bond), int(bool(half)), na, dptr(amps), *c.details))
+        return (amps, c.disc, c.bonds) if details else amps
 
     def apply_circuit(self, circ, thetas, *, inverse: bool = False, trunc_thr: float = 0.0, max_bond: int = 0, details: bool = False):
         """The lanes' working state <- V(thetas[l])|target_l> (or V^H with ``inverse``): ``v_mul_mps`` / ``v_dagger_mul_mps`` for every lane,
         the gates of a circuit layer in one launch.  ``export(lane)`` hands a result out; no lhs states needed."""
-        th = np.ascontiguousarray(thetas, dtype=np.float64)
-        if th.shape != (self.lanes, circ.num_thetas) or circ.num_qubits != self.num_qubits:
-            raise ValueError("thetas: expects shape (lanes, circ.num_thetas) on a circuit of the lanes' size")
-        desc, keep = _describe(circ)
-        disc = np.zeros(self.lanes, dtype=np.float64)
-        bonds = np.zeros(self.lanes, dtype=np.int32)
-        check(_lib.lib().aqc_mpsb_apply_circuit(self.handle, byref(desc), dptr(th), int(bool(inverse)), float(trunc_thr), int(max_bond), dptr(disc),
-                                                bonds.ctypes.data_as(POINTER(c_int32))))
-        del keep
-        return (disc, bonds) if details else None
+        c = self._call(circ, thetas)
+        check(_lib.lib().aqc_mpsb_apply_circuit(self.handle, c.circ, dptr(c.th), int(bool(inverse)), float(trunc_thr), int(max_bond), *c.details))
+        return (c.disc, c.bonds) if details else None
 
     def export(self, lane: int) -> DeviceMPS:
         """Lane ``lane`` of the working state (after ``apply_circuit`` / ``apply_vh``) as a ``DeviceMPS`` of its own."""
@@ -638,13 +633,9 @@ class LockstepLanes:
 
     def gradient(self, circ, *, block_range: Optional[Tuple[int, int]] = None, front_layer: bool = True) -> np.ndarray:
         """Phase 2: grads[lanes][T] (complex) of <V lhs_l|target_l> from the CURRENT lhs states and the vh of ``apply_vh``."""
-        desc, keep = _describe(circ)
-        lo, hi = (-1, -1) if block_range is None else (int(block_range[0]), int(block_range[1]))
-        if block_range is not None and not 0 <= lo <= hi <= circ.num_blocks:
-            raise ValueError("invalid block range")
+        c = self._call(circ, None, block_range)
         grads = np.zeros((self.lanes, circ.num_thetas), dtype=np.complex128)
-        check(_lib.lib().aqc_mpsb_grad(self.handle, byref(desc), lo, hi, int(bool(front_layer)), dptr(grads)))
-        del keep
+        check(_lib.lib().aqc_mpsb_grad(self.handle, c.circ, c.lo, c.hi, int(bool(front_layer)), dptr(grads)))
         return grads
 
     def close(self) -> None:
@@ -707,8 +698,7 @@ def evaluate_lanes(circ, thetas: np.ndarray, targets, lhs, *, trunc_thr: float =
 
     if method != "threads":   # (a single lane as well: its walk is 5x shorter on the lockstep kernels than on the single-lane engine's launch chain)
         distinct = list({id(m): m for m in tg + lh}.values())
-        fits = circ.num_qubits >= 2 and max_bond <= LOCKSTEP_MAX_BOND and all(int(m.bond_dims.max()) <= LOCKSTEP_MAX_BOND for m in distinct)
-        if fits or method == "lockstep":
+        if _fits_a_lane(circ.num_qubits, max_bond, distinct) or method == "lockstep":
             try:
                 shared_t = targets if not isinstance(targets, (list, tuple)) else tg
                 shared_l = lhs if not isinstance(lhs, (list, tuple)) else lh
@@ -717,8 +707,8 @@ def evaluate_lanes(circ, thetas: np.ndarray, targets, lhs, *, trunc_thr: float =
                     raise ValueError(f"the operands of evaluate_lanes live on different devices: {sorted(devs)}")
                 ls = _lockstep_for(circ.num_qubits, lanes, devs.pop(), shared_t, shared_l)
                 return ls.evaluate(circ, th, trunc_thr=trunc_thr, max_bond=max_bond, block_range=block_range, front_layer=front_layer)
-            except RuntimeError as err:
-                if method == "lockstep" or "lockstep lanes" not in str(err):
+            except LanesRefused:
+                if method == "lockstep":
                     raise
 
     def one(b: int):

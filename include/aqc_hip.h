@@ -16,7 +16,8 @@
  *     (parametric_circuit.py:24-70);
  *   - every function returns 0 on success; on failure a non-zero code is
  *     returned and aqc_last_error() gives the message (the ABI never throws
- *     and never calls back into the host language);
+ *     and never calls back into the host language).  One code has a name:
+ *     AQC_LANES_REFUSED, from the aqc_mpsb_* functions only (see below);
  *   - a context is immutable after creation and may be shared; a workspace
  *     owns one HIP device + one stream and is NOT thread-safe (one workspace
  *     per thread / process, exactly like the reference's one-objective-per-
@@ -36,6 +37,10 @@ typedef struct aqc_ctx aqc_ctx; /* ansatz description + gate program (host only)
 typedef struct aqc_ws aqc_ws;   /* device-resident batch workspace            */
 
 enum { AQC_CX = 0, AQC_CZ = 1, AQC_CP = 2 };
+/* Status of an aqc_mpsb_* call that the lockstep lanes cannot do (a bond beyond their 32, in what was loaded or on the way; a lane's
+ * SVD or state gone bad; no memory for the lanes): nothing was returned, and the single-lane engine (aqc_mps_*) may still do the
+ * work -- the code a caller falls back on.  Every other failure is some other non-zero code and is final. */
+enum { AQC_LANES_REFUSED = 3 };
 /* device buffers of a workspace, each [batch][2^n][ncols] complex128: Y target, Z = V^H Y, X / X2 lhs states of the sweep,
  * W / ZW scratch of the sweep.  ZW doubles as the checkpoint of V^H: aqc_ws_apply(inverse, Y -> Z) leaves there the state before
  * its last stage, which is what the sweep's second stage takes as z when the lhs state is sparse (aqc_ws_set_basis /
@@ -241,8 +246,8 @@ int aqc_mps_fast_dot_gradient(const aqc_circuit* circ, const aqc_mps* lvec, cons
  * every step of the gate walk is one launch for all lanes (grid dimension = lane); a truncated 2-qubit gate is one workgroup per
  * lane (two-site tensor, Jacobi SVD, rank / truncation decision, new tensors -- the lane's bond dimensions never leave the device);
  * gate matrices are formed by the kernels from thetas[lane][index].  The host enqueues the whole evaluation without waiting and
- * reads all results in one transfer.  Bonds up to 32 per lane; a lane whose bond would grow beyond that makes the call fail (never
- * a silent truncation) and the caller falls back to aqc_mps_fast_dot_gradient lane by lane.  Truncation rule and outputs per lane
+ * reads all results in one transfer.  Bonds up to 32 per lane; a lane whose bond would grow beyond that makes the call fail with
+ * AQC_LANES_REFUSED (never a silent truncation) and the caller falls back to aqc_mps_fast_dot_gradient lane by lane.  Truncation rule and outputs per lane
  * are those of aqc_mps_apply_circuit + aqc_mps_dot + aqc_mps_fast_dot_gradient (sums of the rule are taken in a different order:
  * last-bit differences). */
 typedef struct aqc_mpsb aqc_mpsb;

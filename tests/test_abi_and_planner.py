@@ -152,6 +152,50 @@ def test_mps_lanes_fail_loudly_without_gpu():
     assert out.count("RAISED") == 2 and out.count("no CPU fallback") == 2 and "CREATED" not in out, out
 
 
+def test_lanes_refusal_is_a_status_and_an_exception_class():
+    """The fallback from the lockstep lanes to the single-lane engine hangs on a status code (AQC_LANES_REFUSED) and its exception
+    class, not on the wording of a message: ``check`` maps that status -- and only that one -- to ``LanesRefused``, a RuntimeError;
+    nothing under the package decides by the message's words any more; a batch that cannot be created for want of a device is an
+    ordinary failure, not a refusal (there is no single-lane route to take either)."""
+    from aqc_research_amd import _lib
+    from aqc_research_amd.mps_engine import LanesRefused
+
+    assert LanesRefused is _lib.LanesRefused and issubclass(LanesRefused, RuntimeError)
+    header = open(os.path.join(ROOT, "include", "aqc_hip.h")).read()
+    assert int(re.search(r"AQC_LANES_REFUSED\s*=\s*(\d+)", header).group(1)) == _lib.LANES_REFUSED != 0
+    _lib.check(0)
+    with pytest.raises(LanesRefused, match="aqc_hip: "):
+        _lib.check(_lib.LANES_REFUSED)
+    for status in (1, 2, -1, _lib.LANES_REFUSED + 1):
+        with pytest.raises(RuntimeError, match="aqc_hip: ") as exc:
+            _lib.check(status)
+        assert not isinstance(exc.value, LanesRefused)
+    pkg = os.path.join(ROOT, "aqc_research_amd")
+    for folder, _, names in os.walk(pkg):
+        for name in names:
+            if name.endswith(".py"):
+                text = open(os.path.join(folder, name)).read()
+                assert not re.search(r"""["']lockstep lanes["']\s+(not\s+)?in\b""", text), os.path.join(folder, name)
+
+    import subprocess
+    import sys
+
+    code = (
+        "import sys; sys.path.insert(0, %r)\n"
+        "from aqc_research_amd import mps_engine as me\n"
+        "try:\n"
+        "    me.LockstepLanes(6, 4)\n"
+        "    print('CREATED')\n"
+        "except me.LanesRefused as e:\n"
+        "    print('REFUSED', e)\n"
+        "except RuntimeError as e:\n"
+        "    print('PLAIN', e)\n" % ROOT
+    )
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300).stdout
+    assert out.startswith("PLAIN") and "no HIP device" in out, out
+
+
 def test_projected_route_is_planned_on_the_host():
     """The projected route of the sparse-lhs sweep (csrc/aqc_ws_project.cpp) is decided and planned without a GPU: the qubits the
     stages after the first touch, those they share with the first stage, the virtual register and its (checked) plan.  Headline

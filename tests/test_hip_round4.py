@@ -632,7 +632,7 @@ def test_lockstep_lanes_against_the_single_lane_engine_on_random_problems():
         try:
             h, g = me.evaluate_lanes(circ, ths, targets, lhs, method="lockstep", **kw)
         except RuntimeError as err:
-            assert "lockstep lanes" in str(err)
+            assert isinstance(err, me.LanesRefused) and "lockstep lanes" in str(err)
             continue
         hs, gs = me.evaluate_lanes(circ, ths, targets, lhs, method="threads", **kw)
         assert maxdiff(h, hs) < 1e-11 and maxdiff(g, gs) < 1e-11, (n, ent, nb, lanes, thr, cap, kw)
