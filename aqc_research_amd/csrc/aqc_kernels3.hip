@@ -247,11 +247,20 @@ __device__ __forceinline__ ItemAt item_at(const Stage3Args& a, int wi) {
     const int bl = wi / a.ntiles;
     return ItemAt{bl, wi - bl * a.ntiles, 0};
 }
-template <int K, bool LIST = false>
-__global__ __launch_bounds__(TileShape<K>::kWaves * 64, 2) void apply_mfma_kernel(const Stage3Args a) {
+// The kernel's body as a device function of (arguments, workgroup index wg, workgroup count nwg): the single launches pass
+// blockIdx.x / gridDim.x, the pair kernels (below) call it once per member with the same workgroup.
+// PAIR (persistent list launches only): when the workgroup's share of a0's list ends it goes on with its share of b0's, and
+// everything that runs AHEAD of an item -- the operand fetch, the address terms, the tile prefetch into accumulation registers -- crosses
+// that boundary with b0's tables: the change of list exposes no load and no store.  The per-plan state (stage tables, sub-stages,
+// operands, buffers, lane offsets) is read through `ca`, a wave-uniform pointer to the running member's argument block.
+template <int K, bool LIST, bool PAIR = false>
+__device__ __forceinline__ void apply_mfma_body(const Stage3Args& a0, const Stage3Args& b0, const int wg, const int nwg) {
     using TS = TileShape<K>;
+    static_assert(!PAIR || (LIST && K >= 12), "the pair form walks two lists with persistent workgroups");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const DevStage& st = a.stage;
+    const Stage3Args* ca = &a0;   // the running member (never reassigned without PAIR)
+#define a (*ca)
+#define st (ca->stage)
     cplx* tw = reinterpret_cast<cplx*>(smem);
     const unsigned lds_base = lds_address(smem);
     if (lds_base & ((16u << K) - 1)) __builtin_trap();   // XOR addressing needs the tile aligned to its own size
@@ -259,13 +268,16 @@ __global__ __launch_bounds__(TileShape<K>::kWaves * 64, 2) void apply_mfma_kerne
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     constexpr int NL = TS::kLoads, NW = TS::kWaves;
     constexpr bool kPersist = K >= 12;      // grid < items only there (launch_apply3)
-    const int nwork = LIST ? uniform_load(a.nitems) : a.ntiles * a.batch;   // items = (tile, lane of the batch), item wi on workgroup wi mod gridDim.x
-    const unsigned lo = st.dlo[lane];
-    const unsigned lo16 = lo << 4;
+    int nwork = LIST ? uniform_load(a.nitems) : a.ntiles * a.batch;   // items = (tile, lane of the batch), item wi on workgroup wi mod gridDim.x
+    bool second = false;   // PAIR: the running member is b0
+    if (PAIR && wg >= nwork) { ca = &b0; second = true; nwork = uniform_load(b0.nitems); }   // (nothing of a0's list falls to this workgroup)
+    unsigned lo = st.dlo[lane];
+    unsigned lo16 = lo << 4;
+    (void)lo16;
     SubRegs cur, nxt;
     SubAddr<TS::kGpw> ad;   // clustered software pipeline, see sweep_mfma_kernel
     dbl2_t pw[NL];          // the prefetched tile: accumulation registers, inline-assembly loads (see sweep_mfma_kernel)
-    int wi = blockIdx.x + ((kPersist || LIST) ? 0 : (int)blockIdx.y * a.ntiles);
+    int wi = wg + ((kPersist || LIST) ? 0 : (int)blockIdx.y * a.ntiles);
     if (LIST && wi >= nwork) return;   // (a whole workgroup, before any barrier)
     ItemAt it = item_at<LIST>(a, wi);
     {
@@ -285,24 +297,33 @@ __global__ __launch_bounds__(TileShape<K>::kWaves * 64, 2) void apply_mfma_kerne
     const int bl = it.bl;
     const size_t lane_off = (size_t)bl * a.lane_stride + tile_base3(st, it.tile);
     const double* umat = a.umat + (size_t)bl * a.nsubs_total * 12 * 64;
-    const int nwi = wi + (int)gridDim.x;
-    const bool more = kPersist && st.nsubs > 0 && nwi < nwork;
-    const ItemAt nit = more ? item_at<LIST>(a, nwi) : ItemAt{0, 0, 0};
+    int nwi = wi + nwg;
+    bool more = kPersist && st.nsubs > 0 && nwi < nwork;
+    const Stage3Args* na = ca;   // the member of the NEXT item
+    int nnwork = nwork;
+    if (PAIR && !more && !second) {   // a0's share ends with this item: the next one is the first of b0's share
+        na = &b0; nwi = wg; nnwork = uniform_load(b0.nitems);
+        more = nwi < nnwork;
+    }
+    const bool change = PAIR && na != ca;
+    const ItemAt nit = more ? item_at<LIST>(*na, nwi) : ItemAt{0, 0, 0};
     const int nbl = nit.bl;
-    const size_t next_off = more ? (size_t)nbl * a.lane_stride + tile_base3(st, nit.tile) : 0;
+    const size_t next_off = more ? (size_t)nbl * na->lane_stride + tile_base3(na->stage, nit.tile) : 0;
+    const unsigned nlo = change ? na->stage.dlo[lane] : lo;
+    const unsigned nlo16 = nlo << 4;
     for (int si = 0; si < st.nsubs; ++si) {
         AQC_STAMP(4 + si);
         if (!(kApplySkip & 512)) __syncthreads();
         if (si + 1 < st.nsubs) fetch_sub<TS::kGpw>(nxt, a.subs, umat, st.sub_begin + si + 1, lane, wave, NW);
-        else if (more) fetch_sub<TS::kGpw>(nxt, a.subs, a.umat + (size_t)nbl * a.nsubs_total * 12 * 64, st.sub_begin, lane, wave, NW);
+        else if (more) fetch_sub<TS::kGpw>(nxt, na->subs, na->umat + (size_t)nbl * na->nsubs_total * 12 * 64, na->stage.sub_begin, lane, wave, NW);
         if (kPersist && more && !(kApplySkip & 64)) {   // a quarter of the next item's tile, issued BEHIND the operand fetch (loads retire in order)
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 if (si == (c < st.nsubs ? c : st.nsubs - 1)) {
 #pragma unroll
                     for (int i = c * (NL / 4); i < (c + 1) * (NL / 4); ++i) {
-                        const size_t ub = next_off + st.dhi[wave + i * NW];
-                        asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=a"(pw[i]) : "v"(lo16), "s"(uniform_ptr(a.in0 + ub)) : "memory");
+                        const size_t ub = next_off + na->stage.dhi[wave + i * NW];
+                        asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=a"(pw[i]) : "v"(nlo16), "s"(uniform_ptr(na->in0 + ub)) : "memory");
                     }
                 }
             }
@@ -366,7 +387,8 @@ __global__ __launch_bounds__(TileShape<K>::kWaves * 64, 2) void apply_mfma_kerne
         }
         if (si + 1 < st.nsubs || more) {
             cur = nxt;
-            fetch_k<TS::kGpw>(ad, a.subs, si + 1 < st.nsubs ? st.sub_begin + si + 1 : st.sub_begin, wave, NW);
+            if (si + 1 < st.nsubs) fetch_k<TS::kGpw>(ad, a.subs, st.sub_begin + si + 1, wave, NW);
+            else fetch_k<TS::kGpw>(ad, na->subs, na->stage.sub_begin, wave, NW);
         }
     }
     AQC_STAMP(4 + st.nsubs);
@@ -385,6 +407,43 @@ __global__ __launch_bounds__(TileShape<K>::kWaves * 64, 2) void apply_mfma_kerne
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the LDS writes above are not tracked by the compiler
     wi = nwi;
     it = nit;
+    if (PAIR) { ca = na; second = second || change; nwork = nnwork; lo = nlo; lo16 = nlo16; }
+    }
+#undef a
+#undef st
+}
+template <int K, bool LIST = false>
+__global__ __launch_bounds__(TileShape<K>::kWaves * 64, 2) void apply_mfma_kernel(const Stage3Args a) {
+    apply_mfma_body<K, LIST>(a, a, (int)blockIdx.x, (int)gridDim.x);
+}
+// Two independent list launches of the same tile size in ONE grid (objective by projection: psi with M_end, Y_0 with V^H's last stage --
+// disjoint buffers, no order between them).  Every workgroup walks its share wg, wg + nwg, ... of list A and then its share of list B,
+// by exactly the code of the single launches: each item is computed as before, bit for bit, and the load stays balanced whatever the
+// two sub-stage counts are (a static split of the workgroups between the lists does not: 7 : 4 sub-stages, integer items).  What the
+// pair saves is one launch ramp, tail and inter-launch gap, and the grid-wide exposed last store of A, which now drains under B's
+// first load.  Below 2^12 amplitudes there is no persistent walk: the grid is the two lists behind each other (launch_apply3_pair).
+#ifndef AQC_PAIR_PLAIN_BOUNDARY   // (variant builds: the change of list as a's last store, a barrier, b's first load)
+#define AQC_PAIR_PLAIN_BOUNDARY 0
+#endif
+template <int K>
+__global__ __launch_bounds__(TileShape<K>::kWaves * 64, 2) void apply_pair_kernel(const Stage3Args a, const Stage3Args b, const int grid_a) {
+    if constexpr (K >= 12 && !AQC_PAIR_PLAIN_BOUNDARY) {
+        // The body selects between the two blocks at run time.  Through the addresses of the by-value parameters that select would
+        // make the compiler copy both blocks to scratch memory; through the kernel-argument segment itself (a at offset 0, b right
+        // behind it) the tables stay scalar loads from the constant address space.
+        static_assert(sizeof(Stage3Args) % 8 == 0 && alignof(Stage3Args) == 8, "b follows a in the kernel-argument segment without padding");
+        const __attribute__((address_space(4))) char* kp = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+        const Stage3Args* pa = (const Stage3Args*)(const void*)kp;
+        const Stage3Args* pb = (const Stage3Args*)(const void*)(kp + sizeof(Stage3Args));
+        apply_mfma_body<K, true, true>(*pa, *pb, (int)blockIdx.x, (int)gridDim.x);
+    } else if (K >= 12) {
+        apply_mfma_body<K, true>(a, a, (int)blockIdx.x, (int)gridDim.x);
+        __syncthreads();   // a's last store has read the LDS tile that b's first load writes
+        apply_mfma_body<K, true>(b, b, (int)blockIdx.x, (int)gridDim.x);
+    } else if ((int)blockIdx.x < grid_a) {
+        apply_mfma_body<K, true>(a, a, (int)blockIdx.x, grid_a);
+    } else {
+        apply_mfma_body<K, true>(b, b, (int)blockIdx.x - grid_a, (int)gridDim.x - grid_a);
     }
 }
 
@@ -442,8 +501,8 @@ __device__ __forceinline__ void skip_masks(const DevStage& st, unsigned info, lo
 }
 // RLAST: the launch of the LAST stage when its last sub-stage is taken from its inputs alone (Stage3Args::r_only_last); a variant of
 // its own because the explicit copies it needs cost the plain loop 3 % (see `substage` below).
-template <int K, bool LIST = false, bool SKIPW = false, bool RLAST = false>
-__global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void sweep_mfma_kernel(const Stage3Args a) {
+template <int K, bool LIST, bool SKIPW, bool RLAST>
+__device__ __forceinline__ void sweep_mfma_body(const Stage3Args& a, const int wg, const int nwg) {   // (wg, nwg: see apply_mfma_body)
     using TS = TileShape<K, true>;
     constexpr int kSlots = TS::kWaves > 4 ? 4 : TS::kWaves;   // scratch slots; 8 waves reduce in pairs first
     constexpr unsigned tsize = 1u << K;
@@ -484,8 +543,8 @@ __global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void s
     // line was written by this workgroup one item earlier) and added where the sum over the waves is formed.
     // LIST (items from a device table, see apply_mfma_kernel): every item writes the partial slot the table names and nothing
     // is accumulated over a segment; the chunk follows from the length of the list.
-    const int chunk = kPersist ? (LIST ? (nwork + (int)gridDim.x - 1) / (int)gridDim.x : a.chunk) : 0;
-    const int wi_first = kPersist ? (int)blockIdx.x * chunk : (int)blockIdx.x;
+    const int chunk = kPersist ? (LIST ? (nwork + nwg - 1) / nwg : a.chunk) : 0;
+    const int wi_first = kPersist ? wg * chunk : wg;
     const int wi_end = kPersist ? (wi_first + chunk < nwork ? wi_first + chunk : nwork) : wi_first + 1;
     int wi = wi_first;
     if (wi >= nwork) return;   // (a whole workgroup: no barrier has been reached yet)
@@ -542,7 +601,7 @@ __global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void s
     const double* umat = a.umat + (size_t)bl * a.nsubs_total * 12 * 64;
     // slot of this item's partial: its tile (one partial per tile), or its segment = number of workgroups that hold earlier
     // tiles of the lane
-    const int part = LIST ? it.slot : (kPersist ? (int)blockIdx.x - (bl * a.ntiles) / chunk : tile);
+    const int part = LIST ? it.slot : (kPersist ? wg - (bl * a.ntiles) / chunk : tile);
     const bool seg_first = LIST || !kPersist || wi == wi_first || tile == 0;   // nothing accumulated yet in this segment
     cplx* rpart = a.rpart + (((size_t)bl * a.nsubs_total + st.sub_begin) * a.nparts + part) * 256;
     const int nwi = wi + 1;
@@ -631,6 +690,27 @@ __global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void s
     item_off = next_off;
     }
     AQC_STAMP(kStampSlots - 4);
+}
+template <int K, bool LIST = false, bool SKIPW = false, bool RLAST = false>
+__global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void sweep_mfma_kernel(const Stage3Args a) {
+    sweep_mfma_body<K, LIST, SKIPW, RLAST>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+// The sweep's pair (see apply_pair_kernel): the real plan's first stage on the lhs tiles with the virtual plan's stage on the virtual
+// register.  Each member keeps its own item list, partial-R slots and R-only form (RLAST_A / RLAST_B); a workgroup walks its contiguous
+// share of A and then of B.  The change of list is the plain one -- A's last stores, a barrier, B's first operands; carrying B's
+// prefetch through A's last item (as apply_mfma_body<K, true, true> does) has not been built here: this kernel runs one wave per SIMD
+// with every architectural register taken, and the prefetch registers are the first sub-stage's operands in a per-stage layout.
+template <int K, bool RLAST_A, bool RLAST_B>
+__global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void sweep_pair_kernel(const Stage3Args a, const Stage3Args b, const int grid_a) {
+    if (K >= 12) {
+        sweep_mfma_body<K, true, false, RLAST_A>(a, (int)blockIdx.x, (int)gridDim.x);
+        __syncthreads();   // A's last sub-stage and stores have read the LDS tiles and scratch that B's first sub-stage writes
+        sweep_mfma_body<K, true, false, RLAST_B>(b, (int)blockIdx.x, (int)gridDim.x);
+    } else if ((int)blockIdx.x < grid_a) {
+        sweep_mfma_body<K, true, false, RLAST_A>(a, (int)blockIdx.x, grid_a);
+    } else {
+        sweep_mfma_body<K, true, false, RLAST_B>(b, (int)blockIdx.x - grid_a, (int)gridDim.x - grid_a);
+    }
 }
 
 // ---- small kernels: U of every sub-stage, gradient entries from R -----------------------------------------
@@ -1101,6 +1181,14 @@ hipError_t init_kernels3() {
     AQC_TRY(big_lds((sweep_mfma_kernel<8, true, false, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<9, true, false, true>)));
     AQC_TRY(big_lds((sweep_mfma_kernel<10, true, false, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<11, true, false, true>)));
     AQC_TRY(big_lds((sweep_mfma_kernel<12, true, false, true>)));
+    AQC_TRY(big_lds(apply_pair_kernel<8>)); AQC_TRY(big_lds(apply_pair_kernel<9>)); AQC_TRY(big_lds(apply_pair_kernel<10>));
+    AQC_TRY(big_lds(apply_pair_kernel<11>)); AQC_TRY(big_lds(apply_pair_kernel<12>));
+    AQC_TRY(big_lds((sweep_pair_kernel<8, false, false>))); AQC_TRY(big_lds((sweep_pair_kernel<9, false, false>)));
+    AQC_TRY(big_lds((sweep_pair_kernel<10, false, false>))); AQC_TRY(big_lds((sweep_pair_kernel<11, false, false>)));
+    AQC_TRY(big_lds((sweep_pair_kernel<12, false, false>)));
+    AQC_TRY(big_lds((sweep_pair_kernel<8, true, false>))); AQC_TRY(big_lds((sweep_pair_kernel<9, true, false>)));
+    AQC_TRY(big_lds((sweep_pair_kernel<10, true, false>))); AQC_TRY(big_lds((sweep_pair_kernel<11, true, false>)));
+    AQC_TRY(big_lds((sweep_pair_kernel<12, true, false>)));
 #undef AQC_TRY
     return hipSuccess;
 }
@@ -1127,6 +1215,10 @@ static long persistent_sweep_grid() {
     if (const char* e = getenv("AQC_SWEEP_GRID")) { const long v = atol(e); if (v > 0) return v; }   // experiments
     return cus[dev];
 }
+static long apply_persist() {   // persistent V / V^H on 2^12 tiles: workgroups per CU, 0 = off
+    static const long persist = []() { const char* e = getenv("AQC_APPLY_PERSIST"); return e ? atol(e) : 2L; }();
+    return persist;
+}
 hipError_t launch_apply3(int ntiles, int batch, int k, hipStream_t s, const Stage3Args& a) {
     if (a.ntiles != ntiles || a.batch != batch) return hipErrorInvalidValue;
     for (int l = 0; l < 64; ++l)   // 32-bit byte offset per lane in the prefetch (see launch_sweep3)
@@ -1135,13 +1227,37 @@ hipError_t launch_apply3(int ntiles, int batch, int k, hipStream_t s, const Stag
     if (list && (!a.nitems || a.max_items < 1)) return hipErrorInvalidValue;
     // 2^12 tiles: persistent workgroups, two per CU, walking over (tile, lane) items; smaller tiles: one item per workgroup
     const long nwork = list ? (long)a.max_items : (long)ntiles * batch;
-    static const long persist = []() { const char* e = getenv("AQC_APPLY_PERSIST"); return e ? atol(e) : 2L; }();   // workgroups per CU, 0 = off
+    const long persist = apply_persist();
     const dim3 grid = (k >= 12 && persist > 0 && a.stage.nsubs > 0) ? dim3((unsigned)std::min<long>(nwork, persist * persistent_sweep_grid()))
                                                                      : ((k >= 12 || list) ? dim3((unsigned)nwork) : dim3(ntiles, batch));
     if (list && k >= 12 && !(persist > 0 && a.stage.nsubs > 0)) return hipErrorInvalidValue;   // (a list launch of 2^12 tiles is persistent)
     const int t = mfma_threads(k, false);
     const size_t l = apply3_lds_bytes(k);
 #define AQC_LAUNCH(KK) case KK: if (list) apply_mfma_kernel<KK, true><<<grid, t, l, s>>>(a); else apply_mfma_kernel<KK, false><<<grid, t, l, s>>>(a); break
+    switch (k) {
+        AQC_LAUNCH(8); AQC_LAUNCH(9); AQC_LAUNCH(10); AQC_LAUNCH(11); AQC_LAUNCH(12);
+        default: return hipErrorInvalidValue;
+    }
+#undef AQC_LAUNCH
+    return hipGetLastError();
+}
+// Two list launches of the same tile size as one (apply_pair_kernel).  2^12 tiles: the persistent grid of the single launches, sized for
+// the longer list; smaller tiles: a's workgroups, then b's.
+static_assert(2 * sizeof(Stage3Args) + 16 <= 3840, "two argument blocks must fit the kernel-argument segment");
+hipError_t launch_apply3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b) {
+    if (!a.items || !b.items || !a.nitems || !b.nitems || a.max_items < 1 || b.max_items < 1) return hipErrorInvalidValue;
+    const long persist = apply_persist();
+    if (k >= 12 && !(persist > 0 && a.stage.nsubs > 0 && b.stage.nsubs > 0)) {   // no persistent walk to share: the two launches
+        const hipError_t e = launch_apply3(a.ntiles, a.batch, k, s, a);
+        return e != hipSuccess ? e : launch_apply3(b.ntiles, b.batch, k, s, b);
+    }
+    for (int l = 0; l < 64; ++l)   // 32-bit byte offset per lane in the prefetch (see launch_sweep3)
+        if (k >= 12 && (a.stage.dlo[l] >= (1u << 28) || b.stage.dlo[l] >= (1u << 28))) return hipErrorInvalidValue;
+    const long longer = std::max(a.max_items, b.max_items);
+    const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persist * persistent_sweep_grid()) : (long)a.max_items + b.max_items));
+    const int t = mfma_threads(k, false);
+    const size_t l = apply3_lds_bytes(k);
+#define AQC_LAUNCH(KK) case KK: apply_pair_kernel<KK><<<grid, t, l, s>>>(a, b, a.max_items); break
     switch (k) {
         AQC_LAUNCH(8); AQC_LAUNCH(9); AQC_LAUNCH(10); AQC_LAUNCH(11); AQC_LAUNCH(12);
         default: return hipErrorInvalidValue;
@@ -1179,6 +1295,27 @@ hipError_t launch_sweep3(int ntiles, int batch, int k, hipStream_t s, const Stag
                                 else if (skipw) sweep_mfma_kernel<KK, false, true><<<grid, t, l, s>>>(a); \
                                 else if (rlast) sweep_mfma_kernel<KK, false, false, true><<<grid, t, l, s>>>(a); \
                                 else sweep_mfma_kernel<KK, false, false><<<grid, t, l, s>>>(a); break
+    switch (k) {
+        AQC_LAUNCH(8); AQC_LAUNCH(9); AQC_LAUNCH(10); AQC_LAUNCH(11); AQC_LAUNCH(12);
+        default: return hipErrorInvalidValue;
+    }
+#undef AQC_LAUNCH
+    return hipGetLastError();
+}
+
+// Two list launches of the sweep as one (sweep_pair_kernel): a may be the R-only form of its stage, b is not.
+hipError_t launch_sweep3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b) {
+    if (!a.items || !b.items || !a.nitems || !b.nitems || a.max_items < 1 || b.max_items < 1) return hipErrorInvalidValue;
+    if (a.nparts < 1 || b.nparts < 1 || a.supp || b.supp || b.r_only_last) return hipErrorInvalidValue;
+    if (k >= 12 && (a.stage.nsubs <= 0 || b.stage.nsubs <= 0)) return hipErrorInvalidValue;   // (see launch_sweep3)
+    for (int l = 0; l < 64; ++l)
+        if (k >= 12 && (a.stage.dlo[l] >= (1u << 28) || b.stage.dlo[l] >= (1u << 28))) return hipErrorInvalidValue;
+    const long longer = std::max(a.max_items, b.max_items);
+    const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persistent_sweep_grid()) : (long)a.max_items + b.max_items));
+    const int t = mfma_threads(k, true);
+    const size_t l = sweep3_lds_bytes(k);
+#define AQC_LAUNCH(KK) case KK: if (a.r_only_last) sweep_pair_kernel<KK, true, false><<<grid, t, l, s>>>(a, b, a.max_items); \
+                                else sweep_pair_kernel<KK, false, false><<<grid, t, l, s>>>(a, b, a.max_items); break
     switch (k) {
         AQC_LAUNCH(8); AQC_LAUNCH(9); AQC_LAUNCH(10); AQC_LAUNCH(11); AQC_LAUNCH(12);
         default: return hipErrorInvalidValue;

@@ -91,6 +91,11 @@ int mfma_threads(int k, bool sweep);
 int mfma_occupancy(int k, bool sweep);
 hipError_t launch_apply3(int ntiles, int batch, int k, hipStream_t s, const Stage3Args& a);
 hipError_t launch_sweep3(int ntiles, int batch, int k, hipStream_t s, const Stage3Args& a);
+// Two independent item-list launches of the same tile size k in one grid: every workgroup walks its share of a's list, then of b's, each
+// item exactly as the single launch computes it (apply_pair_kernel / sweep_pair_kernel).  The lists, partial-R slots and lane_parts are
+// the single launches' own.
+hipError_t launch_apply3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b);
+hipError_t launch_sweep3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b);
 void rgrad_print_stamps(int nsubs);   // tuning builds only
 int sweep3_chunk(int ntiles, int batch, int k);
 int sweep3_nparts(int ntiles, int batch, int k);

@@ -235,6 +235,7 @@ struct aqc_ws {
     bool proj_vdag_enabled = true;          // AQC_PROJECTED_VDAG=0: V^H of a one-call evaluation always by its stages
     long long proj_vdag_min_elems = 1ll << 24;   // ... and from this many amplitudes per batch (fewer: its extra launches cost more than V^H's stages; AQC_PROJECTED_VDAG_MIN_ELEMS)
     bool proj_fused_enabled = true;         // AQC_PROJECTED_FUSED=0: its two products as two launches (two fetches of the target)
+    bool proj_pairs_enabled = true;         // AQC_PROJECTED_PAIRS=0: its independent tile launches one by one instead of in pairs (projected_pairs)
     bool proj_y0_ready = false;             // the virtual z (proj.vy) holds Y_0 for the sweep that follows in the same call (run_vdag_projected)
     bool z_from_y = false;                  // a partial Z without a checkpoint: completed by a full V^H from Y (thetas and Y unchanged since)
     std::vector<long long> h_gather;        // host copy of the registered gather indices (elements)
@@ -308,6 +309,8 @@ void proj_plan(aqc_ws* ws, int low_bits);   // decides the route and lowers the 
 int proj_alloc(aqc_ws* ws);                 // its device side (plan tables, buffers, offset tables)
 void proj_free(aqc_ws* ws);
 bool sweep_route_projected(const aqc_ws* ws, bool sparse);
+bool projected_pairs(const aqc_ws* ws);      // the route's independent tile launches run in pairs
+Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s);   // arguments of stage s of the virtual sweep plan
 int run_projected_stages(aqc_ws* ws);       // projection + the virtual stage launches (after the sweep's first stage)
 aqc::RgradSecond projected_rgrad_plan(aqc_ws* ws);   // the virtual plan's gradient walk, to ride in the real plan's launch
 bool vdag_route_projected(aqc_ws* ws, int x_buf);   // the objective's V^H by two passes over y instead of its stages (host-known single basis state)

@@ -229,28 +229,46 @@ int run_projected_stages(aqc_ws* ws) {
         HIP_OK(launch_project(a, ws->stream));
     }
     const size_t m = v.h_stages.size();
-    const int ntiles = 2 * pr.ntiles_v;
     for (size_t s = 0; s < m; ++s) {
-        Stage3Args a;
-        memset(&a, 0, sizeof a);
-        a.stage = v.h_stages[s];
-        a.subs = v.d_subs3;
-        a.umat = v.d_umat;
-        a.nsubs_total = (int)v.h_subs3.size();
-        a.lane_stride = 2ull << pr.nvp;
-        a.ntiles = ntiles;
-        a.batch = ws->batch;
-        a.in0 = pr.vm; a.in1 = pr.vy; a.out0 = pr.vm; a.out1 = pr.vy;
-        a.store_out = s + 1 < m ? 3 : 0;
-        a.items = pr.d_items; a.nitems = pr.d_count; a.max_items = 2 * ws->batch * pr.ntiles_v;
-        a.rpart = v.d_rpart;
-        a.nparts = ntiles;
-        a.chunk = 0;
-        if (a.stage.nsubs > 0) stage3_first_offsets(a, v.h_subs3[a.stage.sub_begin]);
+        const Stage3Args a = projected_sweep_stage(ws, s);
         ProfScope ps(ws, AQC_K_SWEEP_VIRTUAL);
-        HIP_OK(launch_sweep3(ntiles, ws->batch, pr.kv, ws->stream, a));
+        HIP_OK(launch_sweep3(a.ntiles, ws->batch, pr.kv, ws->stream, a));
     }
     return 0;
+}
+
+// stage s of the virtual sweep plan on (vm, vy)
+Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s) {
+    ProjRoute& pr = ws->proj;
+    DevPlan& v = pr.vsw;
+    const size_t m = v.h_stages.size();
+    const int ntiles = 2 * pr.ntiles_v;
+    Stage3Args a;
+    memset(&a, 0, sizeof a);
+    a.stage = v.h_stages[s];
+    a.subs = v.d_subs3;
+    a.umat = v.d_umat;
+    a.nsubs_total = (int)v.h_subs3.size();
+    a.lane_stride = 2ull << pr.nvp;
+    a.ntiles = ntiles;
+    a.batch = ws->batch;
+    a.in0 = pr.vm; a.in1 = pr.vy; a.out0 = pr.vm; a.out1 = pr.vy;
+    a.store_out = s + 1 < m ? 3 : 0;
+    a.items = pr.d_items; a.nitems = pr.d_count; a.max_items = 2 * ws->batch * pr.ntiles_v;
+    a.rpart = v.d_rpart;
+    a.nparts = ntiles;
+    a.chunk = 0;
+    if (a.stage.nsubs > 0) stage3_first_offsets(a, v.h_subs3[a.stage.sub_begin]);
+    return a;
+}
+
+// Objective by projection: its six tile launches are three pairs of independent launches over disjoint buffers (psi with M_end, V^H's
+// last stage with Y_0, the sweep's first stage with the virtual stage), and each pair runs as ONE launch (launch_apply3_pair /
+// launch_sweep3_pair) when the virtual plan has a single stage of the real plans' tile size.  AQC_PROJECTED_PAIRS=0: single launches.
+bool projected_pairs(const aqc_ws* ws) {
+    const ProjRoute& pr = ws->proj;
+    return pr.ok && ws->proj_pairs_enabled && !ws->capturing && pr.vsw.h_stages.size() == 1 && pr.vinv.h_stages.size() == 1 &&
+           ws->sweep.k == pr.kv && ws->inv.k == pr.kv;
 }
 
 // the gradient entries of the virtual plan's gate groups: its walk rides in the launch of the real plan's (which stops after its first stage)
@@ -299,25 +317,27 @@ bool vdag_route_projected(aqc_ws* ws, int x_buf) {
     return true;
 }
 
-static int virtual_apply(aqc_ws* ws, DevPlan& v, const double2* src, double2* dst) {
+static Stage3Args virtual_apply_stage(aqc_ws* ws, DevPlan& v, size_t s, const double2* src, double2* dst) {
     ProjRoute& pr = ws->proj;
-    const size_t m = v.h_stages.size();
-    const int ntiles = 2 * pr.ntiles_v;
-    for (size_t s = 0; s < m; ++s) {
-        Stage3Args a;
-        memset(&a, 0, sizeof a);
-        a.stage = v.h_stages[s];
-        a.subs = v.d_subs3;
-        a.umat = v.d_umat;
-        a.nsubs_total = (int)v.h_subs3.size();
-        a.lane_stride = 2ull << pr.nvp;
-        a.ntiles = ntiles;
-        a.batch = ws->batch;
-        a.in0 = s == 0 ? src : dst;
-        a.out0 = dst;
-        a.items = pr.d_items; a.nitems = pr.d_count; a.max_items = 2 * ws->batch * pr.ntiles_v;
+    Stage3Args a;
+    memset(&a, 0, sizeof a);
+    a.stage = v.h_stages[s];
+    a.subs = v.d_subs3;
+    a.umat = v.d_umat;
+    a.nsubs_total = (int)v.h_subs3.size();
+    a.lane_stride = 2ull << pr.nvp;
+    a.ntiles = 2 * pr.ntiles_v;
+    a.batch = ws->batch;
+    a.in0 = s == 0 ? src : dst;
+    a.out0 = dst;
+    a.items = pr.d_items; a.nitems = pr.d_count; a.max_items = 2 * ws->batch * pr.ntiles_v;
+    return a;
+}
+static int virtual_apply(aqc_ws* ws, DevPlan& v, const double2* src, double2* dst) {
+    for (size_t s = 0; s < v.h_stages.size(); ++s) {
+        const Stage3Args a = virtual_apply_stage(ws, v, s, src, dst);
         ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
-        HIP_OK(launch_apply3(ntiles, ws->batch, pr.kv, ws->stream, a));
+        HIP_OK(launch_apply3(a.ntiles, ws->batch, ws->proj.kv, ws->stream, a));
     }
     return 0;
 }
@@ -328,6 +348,8 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // the caller has asked vdag_r
     if (ensure_umat(ws, ws->inv)) return 1;
     if (!ws->d_sw_items || !ws->w_clean) return fail("objective by projection without the sparse route's preparation");
     if (ensure_sweep_items(ws, x_buf)) return 1;
+    const bool pairs = projected_pairs(ws);
+    Stage3Args psi;
     {   // psi: the first stage's gates on the basis index, on the listed tiles (x -> W)
         Stage3Args a;
         memset(&a, 0, sizeof a);
@@ -341,12 +363,20 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // the caller has asked vdag_r
         a.in0 = ws->bufs[x_buf];
         a.out0 = ws->bufs[AQC_BUF_W];
         a.items = ws->d_sw_items; a.nitems = ws->d_sw_counts; a.max_items = 2 * ws->batch;
-        ProfScope ps(ws, AQC_K_APPLY_LIST);
-        HIP_OK(launch_apply3(p.ntiles, ws->batch, p.k, ws->stream, a));
+        if (pairs) {
+            psi = a;
+        } else {
+            ProfScope ps(ws, AQC_K_APPLY_LIST);
+            HIP_OK(launch_apply3(p.ntiles, ws->batch, p.k, ws->stream, a));
+        }
     }
     ProjArgs a = proj_args(ws);
     if (ensure_pattern(ws, a)) return 1;
-    if (virtual_apply(ws, pr.vsw, pr.vm, pr.vme)) return 1;   // M_end
+    if (pairs) {   // psi with M_end
+        const Stage3Args mend = virtual_apply_stage(ws, pr.vsw, 0, pr.vm, pr.vme);
+        ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
+        HIP_OK(launch_apply3_pair(pr.kv, ws->stream, psi, mend));
+    } else if (virtual_apply(ws, pr.vsw, pr.vm, pr.vme)) return 1;   // M_end
     const unsigned* off_us = pr.d_tab + (1u << pr.t);
     if (ws->proj_fused_enabled && pr.us <= 10 && pr.cb <= 4 && (pr.us <= 8 || pr.vy_copies == 1 << (pr.us - 8))) {   // both products from one fetch of the target
         ProjArgs q = a;
@@ -379,7 +409,7 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // the caller has asked vdag_r
         HIP_OK(launch_project(q, ws->stream));
     }
     }
-    if (virtual_apply(ws, pr.vinv, pr.vy, pr.vy)) return 1;   // Y_0
+    if (!pairs && virtual_apply(ws, pr.vinv, pr.vy, pr.vy)) return 1;   // Y_0
     {   // V^H's last stage on the lhs tiles: ZW -> Z
         DevPlan& iv = ws->inv;
         Stage3Args s3;
@@ -394,8 +424,14 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // the caller has asked vdag_r
         s3.in0 = ws->bufs[AQC_BUF_ZW];
         s3.out0 = ws->bufs[AQC_BUF_Z];
         s3.items = ws->d_sw_items; s3.nitems = ws->d_sw_counts; s3.max_items = 2 * ws->batch;
-        ProfScope ps(ws, AQC_K_APPLY_LIST);
-        HIP_OK(launch_apply3(iv.ntiles, ws->batch, iv.k, ws->stream, s3));
+        if (pairs) {   // ... with Y_0
+            const Stage3Args y0 = virtual_apply_stage(ws, pr.vinv, 0, pr.vy, pr.vy);
+            ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
+            HIP_OK(launch_apply3_pair(pr.kv, ws->stream, s3, y0));
+        } else {
+            ProfScope ps(ws, AQC_K_APPLY_LIST);
+            HIP_OK(launch_apply3(iv.ntiles, ws->batch, iv.k, ws->stream, s3));
+        }
     }
     vdag_projected_state_after(ws, x_buf);
     return 0;

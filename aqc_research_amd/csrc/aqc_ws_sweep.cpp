@@ -507,6 +507,10 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
         const bool first_stage_r_only = projected && ws->proj_y0_ready && ws->r_only_enabled && p.h_stages[0].nsubs >= 2 &&
                                         p.h_stages[0].nsubs <= ws->r_only_max_subs;
         if (first_stage_r_only) r_only_sub = p.h_stages[0].sub_begin + p.h_stages[0].nsubs - 1;
+        bool pair_virtual = projected && ws->proj_y0_ready && projected_pairs(ws);   // the first stage and the virtual stage as one launch
+#ifdef AQC_TUNING
+        if (env_int("AQC_STAMPS", 0) != 0) pair_virtual = false;
+#endif
         // a partial Z covers the sparse route's reads when its tiles were chosen for this lhs state (or for a gather set the
         // state was picked from); anything else reads all of Z
         if (!ws->z_full && !(sparse && ((support_in_gather_set && ws->z_key.gather == ws->gather_gen) ||
@@ -548,7 +552,11 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
             a.debug = env_int("AQC_DEBUG_SKIP", 0);
             if (stamps_begin(ws, a, nwg)) return 1;
 #endif
-            {
+            if (pair_virtual) {   // ... with the virtual stage (Y_0 is there already: nothing of it waits for this stage)
+                const Stage3Args b = projected_sweep_stage(ws, 0);
+                ProfScope ps(ws, AQC_K_SWEEP_LIST);
+                HIP_OK(launch_sweep3_pair(p.k, ws->stream, a, b));
+            } else {
                 ProfScope ps(ws, a.items ? AQC_K_SWEEP_LIST : AQC_K_SWEEP);
                 HIP_OK(launch_sweep3(p.ntiles, ws->batch, p.k, ws->stream, a));
             }
@@ -556,7 +564,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
             if (stamps_sweep(ws, a, s, nwg)) return 1;
 #endif
         }
-        if (projected && run_projected_stages(ws)) return 1;
+        if (projected && !pair_virtual && run_projected_stages(ws)) return 1;
         sweep_state_after(ws, sparse);
         ProfScope ps(ws, AQC_K_FINALIZE);
         RgradSecond vwalk;   // projected route: the virtual plan's walk in the same launch (two launches: 54 + 54 us at the headline, one: ~70)
