@@ -456,16 +456,7 @@ int aqc_ws_destroy(aqc_ws* ws) {
     if (ws->stream) (void)hipStreamSynchronize(ws->stream);
     drop_graphs(ws);
     proj_free(ws);
-    for (DevPlan* p : {&ws->fwd, &ws->inv, &ws->sweep}) {
-        if (p->d_stages) (void)hipFree(p->d_stages);
-        if (p->d_ops) (void)hipFree(p->d_ops);
-        if (p->d_subs) (void)hipFree(p->d_subs);
-        if (p->d_mops) (void)hipFree(p->d_mops);
-        if (p->d_subs3) (void)hipFree(p->d_subs3);
-        if (p->d_grps) (void)hipFree(p->d_grps);
-        if (p->d_umat) (void)hipFree(p->d_umat);
-        if (p->d_rpart) (void)hipFree(p->d_rpart);
-    }
+    for (DevPlan* p : {&ws->fwd, &ws->inv, &ws->sweep}) free_plan(*p);
     void* ptrs[] = {ws->d_thetas_own, ws->d_theta_bank, ws->d_coef, ws->d_partial, ws->d_grads, ws->d_small, ws->d_vdot_part, ws->d_index, ws->d_tmp_index, ws->d_tmp_small,
                     ws->d_theta_slots, ws->d_slot_theta, ws->d_slot_ntiles, ws->d_basis_index, ws->d_vdot_out, ws->d_ujobs};
     for (void* p : ptrs) if (p) (void)hipFree(p);

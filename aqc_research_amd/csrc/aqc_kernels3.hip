@@ -1157,50 +1157,60 @@ size_t sweep3_lds_bytes(int k) {   // two tiles + R scratch of up to 4 slots, do
     return ((size_t)32 << k) + (size_t)(sweep_scratch_double(k) ? 2 : 1) * std::min(4, mfma_threads(k, true) / 64) * 256 * sizeof(cplx);
 }
 
+// The tile size k = 8..12 as a compile-time constant: f(std::integral_constant<int, K>), hipErrorInvalidValue for any other k
+template <typename F>
+static hipError_t with_tile_size(int k, F&& f) {
+    switch (k) {
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 9: return f(std::integral_constant<int, 9>{});
+        case 10: return f(std::integral_constant<int, 10>{});
+        case 11: return f(std::integral_constant<int, 11>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+// The kernel variant of every family as a function of the run-time flags.  The launchers take their kernels from these selectors and
+// init_kernels3 walks the same selectors over every flag combination: what can be launched has been initialised.
+using Stage3Kernel = void (*)(Stage3Args);
+using Pair3Kernel = void (*)(Stage3Args, Stage3Args, int);
+template <int K> static Stage3Kernel apply_variant(bool list) { return list ? apply_mfma_kernel<K, true> : apply_mfma_kernel<K, false>; }
+template <int K> static Stage3Kernel sweep_variant(bool list, bool skipw, bool rlast) {   // (a list launch has no zero-w form, the zero-w form no R-only one)
+    if (list) return rlast ? sweep_mfma_kernel<K, true, false, true> : sweep_mfma_kernel<K, true, false, false>;
+    if (skipw) return sweep_mfma_kernel<K, false, true, false>;
+    return rlast ? sweep_mfma_kernel<K, false, false, true> : sweep_mfma_kernel<K, false, false, false>;
+}
+template <int K> static Pair3Kernel apply_pair_variant() { return apply_pair_kernel<K>; }
+template <int K> static Pair3Kernel sweep_pair_variant(bool rlast_a) { return rlast_a ? sweep_pair_kernel<K, true, false> : sweep_pair_kernel<K, false, false>; }
+
 template <typename F>
 static hipError_t big_lds(F kernel) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
-hipError_t init_kernels3() {
-    hipError_t e;
-#define AQC_TRY(x) if ((e = (x)) != hipSuccess) return e
-    AQC_TRY(big_lds(apply_mfma_kernel<8>)); AQC_TRY(big_lds(apply_mfma_kernel<9>)); AQC_TRY(big_lds(apply_mfma_kernel<10>));
-    AQC_TRY(big_lds(apply_mfma_kernel<11>)); AQC_TRY(big_lds(apply_mfma_kernel<12>));
-    AQC_TRY(big_lds(sweep_mfma_kernel<8>)); AQC_TRY(big_lds(sweep_mfma_kernel<9>)); AQC_TRY(big_lds(sweep_mfma_kernel<10>));
-    AQC_TRY(big_lds(sweep_mfma_kernel<11>)); AQC_TRY(big_lds(sweep_mfma_kernel<12>));
-    AQC_TRY(big_lds((apply_mfma_kernel<8, true>))); AQC_TRY(big_lds((apply_mfma_kernel<9, true>))); AQC_TRY(big_lds((apply_mfma_kernel<10, true>)));
-    AQC_TRY(big_lds((apply_mfma_kernel<11, true>))); AQC_TRY(big_lds((apply_mfma_kernel<12, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<8, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<9, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<10, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<11, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<12, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<8, false, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<9, false, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<10, false, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<11, false, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<12, false, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<8, false, false, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<9, false, false, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<10, false, false, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<11, false, false, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<12, false, false, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<8, true, false, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<9, true, false, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<10, true, false, true>))); AQC_TRY(big_lds((sweep_mfma_kernel<11, true, false, true>)));
-    AQC_TRY(big_lds((sweep_mfma_kernel<12, true, false, true>)));
-    AQC_TRY(big_lds(apply_pair_kernel<8>)); AQC_TRY(big_lds(apply_pair_kernel<9>)); AQC_TRY(big_lds(apply_pair_kernel<10>));
-    AQC_TRY(big_lds(apply_pair_kernel<11>)); AQC_TRY(big_lds(apply_pair_kernel<12>));
-    AQC_TRY(big_lds((sweep_pair_kernel<8, false, false>))); AQC_TRY(big_lds((sweep_pair_kernel<9, false, false>)));
-    AQC_TRY(big_lds((sweep_pair_kernel<10, false, false>))); AQC_TRY(big_lds((sweep_pair_kernel<11, false, false>)));
-    AQC_TRY(big_lds((sweep_pair_kernel<12, false, false>)));
-    AQC_TRY(big_lds((sweep_pair_kernel<8, true, false>))); AQC_TRY(big_lds((sweep_pair_kernel<9, true, false>)));
-    AQC_TRY(big_lds((sweep_pair_kernel<10, true, false>))); AQC_TRY(big_lds((sweep_pair_kernel<11, true, false>)));
-    AQC_TRY(big_lds((sweep_pair_kernel<12, true, false>)));
-#undef AQC_TRY
-    return hipSuccess;
+hipError_t init_kernels3() {   // eager: a launch may sit inside a graph capture
+    hipError_t e = hipSuccess;
+    for (int k = 8; k <= 12 && e == hipSuccess; ++k)
+        e = with_tile_size(k, [](auto kk) {
+            constexpr int K = decltype(kk)::value;
+            hipError_t e = big_lds(apply_pair_variant<K>());
+            for (int f = 0; f < 2 && e == hipSuccess; ++f) e = big_lds(apply_variant<K>(f));
+            for (int f = 0; f < 2 && e == hipSuccess; ++f) e = big_lds(sweep_pair_variant<K>(f));
+            for (int f = 0; f < 8 && e == hipSuccess; ++f) e = big_lds(sweep_variant<K>(f & 1, f & 2, f & 4));   // (flag combinations that share a kernel: set twice)
+            return e;
+        });
+    return e;
+}
+template <typename... Args>   // one launch of a stage kernel with its family's workgroup size and LDS
+static hipError_t launch3(void (*kernel)(Args...), dim3 grid, int k, bool sweep, hipStream_t s, const Args&... args) {
+    kernel<<<grid, mfma_threads(k, sweep), sweep ? sweep3_lds_bytes(k) : apply3_lds_bytes(k), s>>>(args...);
+    return hipGetLastError();
 }
 int mfma_occupancy(int k, bool sweep) {   // resident workgroups per CU for the tile size (diagnostics)
     int n = 0;
-    hipError_t e = hipErrorInvalidValue;
-    const int t = mfma_threads(k, sweep);
-    const size_t l = sweep ? sweep3_lds_bytes(k) : apply3_lds_bytes(k);
-#define AQC_OCC(KK) case KK: e = sweep ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sweep_mfma_kernel<KK>, t, l) \
-                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, apply_mfma_kernel<KK>, t, l); break
-    switch (k) { AQC_OCC(8); AQC_OCC(9); AQC_OCC(10); AQC_OCC(11); AQC_OCC(12); default: break; }
-#undef AQC_OCC
+    const hipError_t e = with_tile_size(k, [&](auto kk) {
+        constexpr int K = decltype(kk)::value;
+        return sweep ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sweep_variant<K>(false, false, false), mfma_threads(k, true), sweep3_lds_bytes(k))
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, apply_variant<K>(false), mfma_threads(k, false), apply3_lds_bytes(k));
+    });
     return e == hipSuccess ? n : -1;
 }
 // workgroups of the persistent 2^12 sweep: one per CU of the current device (the occupancy its 144 KiB of LDS allows)
@@ -1219,51 +1229,35 @@ static long apply_persist() {   // persistent V / V^H on 2^12 tiles: workgroups 
     static const long persist = []() { const char* e = getenv("AQC_APPLY_PERSIST"); return e ? atol(e) : 2L; }();
     return persist;
 }
-hipError_t launch_apply3(int ntiles, int batch, int k, hipStream_t s, const Stage3Args& a) {
-    if (a.ntiles != ntiles || a.batch != batch) return hipErrorInvalidValue;
-    for (int l = 0; l < 64; ++l)   // 32-bit byte offset per lane in the prefetch (see launch_sweep3)
-        if (k >= 12 && a.stage.dlo[l] >= (1u << 28)) return hipErrorInvalidValue;
+// What the four launchers ask of a member: a complete item list (need_list: an item list at all), and on 2^12 tiles lane offsets
+// that fit the prefetch (a 32-bit byte offset per lane) and -- need_subs: the launch takes the persistent form there -- a sub-stage
+static bool stage3_launchable(int k, const Stage3Args& a, bool need_list, bool need_subs) {
+    if (a.items ? (!a.nitems || a.max_items < 1) : need_list) return false;
+    if (k < 12) return true;
+    if (need_subs && a.stage.nsubs <= 0) return false;
+    for (int l = 0; l < 64; ++l)
+        if (a.stage.dlo[l] >= (1u << 28)) return false;
+    return true;
+}
+hipError_t launch_apply3(int k, hipStream_t s, const Stage3Args& a) {
     const bool list = a.items != nullptr;
-    if (list && (!a.nitems || a.max_items < 1)) return hipErrorInvalidValue;
-    // 2^12 tiles: persistent workgroups, two per CU, walking over (tile, lane) items; smaller tiles: one item per workgroup
-    const long nwork = list ? (long)a.max_items : (long)ntiles * batch;
     const long persist = apply_persist();
+    if (!stage3_launchable(k, a, false, list) || (list && k >= 12 && persist <= 0)) return hipErrorInvalidValue;   // (a list launch of 2^12 tiles is persistent)
+    // 2^12 tiles: persistent workgroups, two per CU, walking over (tile, lane) items; smaller tiles: one item per workgroup
+    const long nwork = list ? (long)a.max_items : (long)a.ntiles * a.batch;
     const dim3 grid = (k >= 12 && persist > 0 && a.stage.nsubs > 0) ? dim3((unsigned)std::min<long>(nwork, persist * persistent_sweep_grid()))
-                                                                     : ((k >= 12 || list) ? dim3((unsigned)nwork) : dim3(ntiles, batch));
-    if (list && k >= 12 && !(persist > 0 && a.stage.nsubs > 0)) return hipErrorInvalidValue;   // (a list launch of 2^12 tiles is persistent)
-    const int t = mfma_threads(k, false);
-    const size_t l = apply3_lds_bytes(k);
-#define AQC_LAUNCH(KK) case KK: if (list) apply_mfma_kernel<KK, true><<<grid, t, l, s>>>(a); else apply_mfma_kernel<KK, false><<<grid, t, l, s>>>(a); break
-    switch (k) {
-        AQC_LAUNCH(8); AQC_LAUNCH(9); AQC_LAUNCH(10); AQC_LAUNCH(11); AQC_LAUNCH(12);
-        default: return hipErrorInvalidValue;
-    }
-#undef AQC_LAUNCH
-    return hipGetLastError();
+                                                                     : ((k >= 12 || list) ? dim3((unsigned)nwork) : dim3(a.ntiles, a.batch));
+    return with_tile_size(k, [&](auto kk) { return launch3(apply_variant<decltype(kk)::value>(list), grid, k, false, s, a); });
 }
 // Two list launches of the same tile size as one (apply_pair_kernel).  2^12 tiles: the persistent grid of the single launches, sized for
 // the longer list; smaller tiles: a's workgroups, then b's.
 static_assert(2 * sizeof(Stage3Args) + 16 <= 3840, "two argument blocks must fit the kernel-argument segment");
 hipError_t launch_apply3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b) {
-    if (!a.items || !b.items || !a.nitems || !b.nitems || a.max_items < 1 || b.max_items < 1) return hipErrorInvalidValue;
     const long persist = apply_persist();
-    if (k >= 12 && !(persist > 0 && a.stage.nsubs > 0 && b.stage.nsubs > 0)) {   // no persistent walk to share: the two launches
-        const hipError_t e = launch_apply3(a.ntiles, a.batch, k, s, a);
-        return e != hipSuccess ? e : launch_apply3(b.ntiles, b.batch, k, s, b);
-    }
-    for (int l = 0; l < 64; ++l)   // 32-bit byte offset per lane in the prefetch (see launch_sweep3)
-        if (k >= 12 && (a.stage.dlo[l] >= (1u << 28) || b.stage.dlo[l] >= (1u << 28))) return hipErrorInvalidValue;
+    if (!stage3_launchable(k, a, true, true) || !stage3_launchable(k, b, true, true) || (k >= 12 && persist <= 0)) return hipErrorInvalidValue;
     const long longer = std::max(a.max_items, b.max_items);
     const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persist * persistent_sweep_grid()) : (long)a.max_items + b.max_items));
-    const int t = mfma_threads(k, false);
-    const size_t l = apply3_lds_bytes(k);
-#define AQC_LAUNCH(KK) case KK: apply_pair_kernel<KK><<<grid, t, l, s>>>(a, b, a.max_items); break
-    switch (k) {
-        AQC_LAUNCH(8); AQC_LAUNCH(9); AQC_LAUNCH(10); AQC_LAUNCH(11); AQC_LAUNCH(12);
-        default: return hipErrorInvalidValue;
-    }
-#undef AQC_LAUNCH
-    return hipGetLastError();
+    return with_tile_size(k, [&](auto kk) { return launch3(apply_pair_variant<decltype(kk)::value>(), grid, k, false, s, a, b, a.max_items); });
 }
 // persistent sweep: items per workgroup (contiguous, lane-major) and partial slots per (lane, sub-stage); 0 / ntiles otherwise
 int sweep3_chunk(int ntiles, int batch, int k) {
@@ -1275,53 +1269,25 @@ int sweep3_nparts(int ntiles, int batch, int k) {
     const int chunk = sweep3_chunk(ntiles, batch, k);
     return chunk > 0 ? std::min(ntiles, (ntiles + chunk - 1) / chunk + 1) : ntiles;
 }
-hipError_t launch_sweep3(int ntiles, int batch, int k, hipStream_t s, const Stage3Args& a) {
-    if (a.ntiles != ntiles || a.batch != batch) return hipErrorInvalidValue;
+hipError_t launch_sweep3(int k, hipStream_t s, const Stage3Args& a) {
     const bool list = a.items != nullptr;
-    if (list && (!a.nitems || a.max_items < 1)) return hipErrorInvalidValue;
-    if (a.nparts < 1 || (!list && (a.nparts != sweep3_nparts(ntiles, batch, k) || a.chunk != sweep3_chunk(ntiles, batch, k)))) return hipErrorInvalidValue;   // (a list names its slots)
-    if (k >= 12 && a.stage.nsubs <= 0) return hipErrorInvalidValue;   // the persistent form feeds the first sub-stage from registers
-    for (int l = 0; l < 64; ++l)   // the persistent sweep addresses its prefetch with a 32-bit byte offset per lane
-        if (k >= 12 && a.stage.dlo[l] >= (1u << 28)) return hipErrorInvalidValue;
+    if (!stage3_launchable(k, a, false, true)) return hipErrorInvalidValue;   // (the persistent form feeds the first sub-stage from registers)
+    if (a.nparts < 1 || (!list && (a.nparts != sweep3_nparts(a.ntiles, a.batch, k) || a.chunk != sweep3_chunk(a.ntiles, a.batch, k)))) return hipErrorInvalidValue;   // (a list names its slots)
     // 2^12 tiles: one persistent workgroup per CU walking over its items (see the kernel); smaller tiles: one item each
-    const long nwork = list ? (long)a.max_items : (long)ntiles * batch;
+    const long nwork = list ? (long)a.max_items : (long)a.ntiles * a.batch;
     const dim3 grid((unsigned)(k >= 12 ? (list ? std::min<long>(nwork, persistent_sweep_grid()) : (nwork + a.chunk - 1) / a.chunk) : nwork));
-    const int t = mfma_threads(k, true);
-    const size_t l = sweep3_lds_bytes(k);
     const bool skipw = !list && a.supp != nullptr;
     const bool rlast = !skipw && a.r_only_last != 0;
-#define AQC_LAUNCH(KK) case KK: if (list && rlast) sweep_mfma_kernel<KK, true, false, true><<<grid, t, l, s>>>(a); \
-                                else if (list) sweep_mfma_kernel<KK, true, false><<<grid, t, l, s>>>(a); \
-                                else if (skipw) sweep_mfma_kernel<KK, false, true><<<grid, t, l, s>>>(a); \
-                                else if (rlast) sweep_mfma_kernel<KK, false, false, true><<<grid, t, l, s>>>(a); \
-                                else sweep_mfma_kernel<KK, false, false><<<grid, t, l, s>>>(a); break
-    switch (k) {
-        AQC_LAUNCH(8); AQC_LAUNCH(9); AQC_LAUNCH(10); AQC_LAUNCH(11); AQC_LAUNCH(12);
-        default: return hipErrorInvalidValue;
-    }
-#undef AQC_LAUNCH
-    return hipGetLastError();
+    return with_tile_size(k, [&](auto kk) { return launch3(sweep_variant<decltype(kk)::value>(list, skipw, rlast), grid, k, true, s, a); });
 }
 
 // Two list launches of the sweep as one (sweep_pair_kernel): a may be the R-only form of its stage, b is not.
 hipError_t launch_sweep3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b) {
-    if (!a.items || !b.items || !a.nitems || !b.nitems || a.max_items < 1 || b.max_items < 1) return hipErrorInvalidValue;
+    if (!stage3_launchable(k, a, true, true) || !stage3_launchable(k, b, true, true)) return hipErrorInvalidValue;
     if (a.nparts < 1 || b.nparts < 1 || a.supp || b.supp || b.r_only_last) return hipErrorInvalidValue;
-    if (k >= 12 && (a.stage.nsubs <= 0 || b.stage.nsubs <= 0)) return hipErrorInvalidValue;   // (see launch_sweep3)
-    for (int l = 0; l < 64; ++l)
-        if (k >= 12 && (a.stage.dlo[l] >= (1u << 28) || b.stage.dlo[l] >= (1u << 28))) return hipErrorInvalidValue;
     const long longer = std::max(a.max_items, b.max_items);
     const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persistent_sweep_grid()) : (long)a.max_items + b.max_items));
-    const int t = mfma_threads(k, true);
-    const size_t l = sweep3_lds_bytes(k);
-#define AQC_LAUNCH(KK) case KK: if (a.r_only_last) sweep_pair_kernel<KK, true, false><<<grid, t, l, s>>>(a, b, a.max_items); \
-                                else sweep_pair_kernel<KK, false, false><<<grid, t, l, s>>>(a, b, a.max_items); break
-    switch (k) {
-        AQC_LAUNCH(8); AQC_LAUNCH(9); AQC_LAUNCH(10); AQC_LAUNCH(11); AQC_LAUNCH(12);
-        default: return hipErrorInvalidValue;
-    }
-#undef AQC_LAUNCH
-    return hipGetLastError();
+    return with_tile_size(k, [&](auto kk) { return launch3(sweep_pair_variant<decltype(kk)::value>(a.r_only_last != 0), grid, k, true, s, a, b, a.max_items); });
 }
 
 // ---- tile lists ------------------------------------------------------------------------------------------------

@@ -89,8 +89,8 @@ void stage3_first_offsets(Stage3Args& a, const DevSub3& first_sub);   // host: f
 hipError_t init_kernels3();
 int mfma_threads(int k, bool sweep);
 int mfma_occupancy(int k, bool sweep);
-hipError_t launch_apply3(int ntiles, int batch, int k, hipStream_t s, const Stage3Args& a);
-hipError_t launch_sweep3(int ntiles, int batch, int k, hipStream_t s, const Stage3Args& a);
+hipError_t launch_apply3(int k, hipStream_t s, const Stage3Args& a);   // k: tile size, 8..12
+hipError_t launch_sweep3(int k, hipStream_t s, const Stage3Args& a);
 // Two independent item-list launches of the same tile size k in one grid: every workgroup walks its share of a's list, then of b's, each
 // item exactly as the single launch computes it (apply_pair_kernel / sweep_pair_kernel).  The lists, partial-R slots and lane_parts are
 // the single launches' own.

@@ -105,6 +105,7 @@ struct ProjRoute {
 // aqc_ws_plan.cpp
 void lower_plan(const Program& prog, const Plan& plan, DevPlan& out, int reg_bits, bool with_dots, bool mfma = false, bool presplit = false, int beam_width = 64);
 int upload_plan(DevPlan& p);
+void free_plan(DevPlan& p);   // the device side of a plan
 Plan mirror_plan(const Plan& plan);   // the same stages and sub-stages walked backwards: the plan of V^H whose intermediate states are the sweep's
 
 }  // namespace aqc
@@ -303,6 +304,11 @@ void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf);
 void sweep_state_after(aqc_ws* ws, bool sparse);
 int ensure_umat(aqc_ws* ws, DevPlan& p);
 int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf);
+// descriptions of a matrix-core stage launch; the buffers and what is particular to the launch are the caller's
+Stage3Args stage3_args(aqc_ws* ws, const DevPlan& p, size_t s);   // stage s of a plan on the full-size register, over all (tile, lane) pairs
+void stage3_first_list(const aqc_ws* ws, Stage3Args& a);          // ... over the first-stage item list of the sparse sweep instead
+void stage3_sweep_fields(Stage3Args& a, const DevPlan& p, int nparts, int chunk);   // the sweep-only fields: p's partial-R buffer with its slots per (lane,
+                                                                                    // sub-stage), the persistent chunk, the first sub-stage's operand offsets
 void drop_graphs(aqc_ws* ws);
 // aqc_ws_project.cpp
 void proj_plan(aqc_ws* ws, int low_bits);   // decides the route and lowers the virtual plan (host only)
@@ -310,6 +316,7 @@ int proj_alloc(aqc_ws* ws);                 // its device side (plan tables, buf
 void proj_free(aqc_ws* ws);
 bool sweep_route_projected(const aqc_ws* ws, bool sparse);
 bool projected_pairs(const aqc_ws* ws);      // the route's independent tile launches run in pairs
+Stage3Args virtual_stage3_args(aqc_ws* ws, const DevPlan& v, size_t s);   // stage s of a virtual plan (vsw, vinv) on the virtual register, over its item list
 Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s);   // arguments of stage s of the virtual sweep plan
 int run_projected_stages(aqc_ws* ws);       // projection + the virtual stage launches (after the sweep's first stage)
 aqc::RgradSecond projected_rgrad_plan(aqc_ws* ws);   // the virtual plan's gradient walk, to ride in the real plan's launch

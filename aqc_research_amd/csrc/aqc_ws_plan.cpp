@@ -237,6 +237,12 @@ int upload_plan(DevPlan& p) {
     }
     return 0;
 }
+void free_plan(DevPlan& p) {   // what upload_plan allocated, and the plan's operand and partial-R buffers
+    for (void* q : {(void*)p.d_stages, (void*)p.d_ops, (void*)p.d_subs, (void*)p.d_mops, (void*)p.d_subs3, (void*)p.d_grps, (void*)p.d_umat, (void*)p.d_rpart})
+        if (q) (void)hipFree(q);
+    p.d_stages = nullptr; p.d_ops = nullptr; p.d_subs = nullptr; p.d_mops = nullptr; p.d_subs3 = nullptr; p.d_grps = nullptr;
+    p.d_umat = nullptr; p.d_rpart = nullptr;
+}
 
 // The plan of V^H that walks a forward plan backwards: stages in reverse order with the same local bits, sub-stages in reverse
 // order with the same register bits, the groups of every sub-stage in reverse order.  Per-qubit program order of the inverse

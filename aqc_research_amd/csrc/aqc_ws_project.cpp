@@ -151,13 +151,8 @@ int proj_alloc(aqc_ws* ws) {
 
 void proj_free(aqc_ws* ws) {
     ProjRoute& pr = ws->proj;
-    for (DevPlan* vp : {&pr.vsw, &pr.vinv}) {
-        DevPlan& v = *vp;
-        for (void* q : {(void*)v.d_stages, (void*)v.d_ops, (void*)v.d_subs, (void*)v.d_mops, (void*)v.d_subs3, (void*)v.d_grps, (void*)v.d_umat, (void*)v.d_rpart})
-            if (q) (void)hipFree(q);
-        v.d_stages = nullptr; v.d_ops = nullptr; v.d_subs = nullptr; v.d_mops = nullptr; v.d_subs3 = nullptr; v.d_grps = nullptr;
-        v.d_umat = nullptr; v.d_rpart = nullptr;
-    }
+    free_plan(pr.vsw);
+    free_plan(pr.vinv);
     for (void* q : {(void*)pr.vm, (void*)pr.vy, (void*)pr.vme, (void*)pr.cpart, (void*)pr.d_tab, (void*)pr.d_items, (void*)pr.d_count, (void*)pr.d_lane_parts})
         if (q) (void)hipFree(q);
     pr.vm = pr.vy = pr.vme = nullptr; pr.cpart = nullptr; pr.d_tab = nullptr; pr.d_items = nullptr; pr.d_count = nullptr; pr.d_lane_parts = nullptr;
@@ -204,61 +199,59 @@ static ProjArgs proj_args(aqc_ws* ws) {
     return a;
 }
 
+// The product of the route,  Y[i_T, c] = sum_u conj(psi[u, c]) y[u, i_T]  per first-stage item, into the virtual z:  Y = the full-size
+// operand y, k = u, keep = i_T, S = psi in W
+static ProjArgs y_product(aqc_ws* ws, ProjArgs a, const double2* y) {
+    const ProjRoute& pr = ws->proj;
+    a.y = y;
+    a.s = ws->bufs[AQC_BUF_W];
+    a.out = pr.vy;
+    a.s_virtual = 0; a.out_virtual = 1;
+    a.staged = 1;   // (proj_plan: address bits 0..3 are among the summed ones)
+    a.keep_bits = pr.t; a.k_bits = pr.us;
+    a.y_keep = ProjMap{a.off_t, 0};
+    a.y_k = ProjMap{a.off_us, 0};
+    a.s_k = ProjMap{a.off_us, 0};
+    a.s_c = ProjMap{a.off_cb, 0};
+    a.o_keep = ProjMap{nullptr, 0};
+    a.o_c = ProjMap{nullptr, pr.t};
+    return a;
+}
+
 // after the sweep's first stage (W holds psi on the listed tiles, ZW the checkpoint): the projection, then the virtual stages
 int run_projected_stages(aqc_ws* ws) {
     ProjRoute& pr = ws->proj;
-    DevPlan& v = pr.vsw;
     if (!ws->proj_y0_ready) {   // (else run_vdag_projected of this call has left M_0 and Y_0, from the target, on the virtual register)
-        ProjArgs a = proj_args(ws);
+        const ProjArgs a = proj_args(ws);
         if (ensure_pattern(ws, a)) return 1;
-        // Y_0[i_T, c] = sum_u conj(psi[u, c]) z[u, i_T]:  Y = the checkpoint, k = u, keep = i_T, S = psi in W, out = the virtual z
-        a.y = ws->bufs[AQC_BUF_ZW];
-        a.s = ws->bufs[AQC_BUF_W];
-        a.out = pr.vy;
-        a.s_virtual = 0; a.out_virtual = 1;
-        a.staged = 1;   // (proj_plan: address bits 0..3 are among the summed ones)
-        a.keep_bits = pr.t; a.k_bits = pr.us;
-        const unsigned* off_us = pr.d_tab + (1u << pr.t);
-        a.y_keep = ProjMap{pr.d_tab, 0};
-        a.y_k = ProjMap{off_us, 0};
-        a.s_k = ProjMap{off_us, 0};
-        a.s_c = ProjMap{a.off_cb, 0};
-        a.o_keep = ProjMap{nullptr, 0};
-        a.o_c = ProjMap{nullptr, pr.t};
         ProfScope ps(ws, AQC_K_PROJECT);
-        HIP_OK(launch_project(a, ws->stream));
+        HIP_OK(launch_project(y_product(ws, a, ws->bufs[AQC_BUF_ZW]), ws->stream));   // Y_0, from the checkpoint
     }
-    const size_t m = v.h_stages.size();
-    for (size_t s = 0; s < m; ++s) {
+    for (size_t s = 0; s < pr.vsw.h_stages.size(); ++s) {
         const Stage3Args a = projected_sweep_stage(ws, s);
         ProfScope ps(ws, AQC_K_SWEEP_VIRTUAL);
-        HIP_OK(launch_sweep3(a.ntiles, ws->batch, pr.kv, ws->stream, a));
+        HIP_OK(launch_sweep3(pr.kv, ws->stream, a));
     }
     return 0;
 }
 
-// stage s of the virtual sweep plan on (vm, vy)
-Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s) {
-    ProjRoute& pr = ws->proj;
-    DevPlan& v = pr.vsw;
-    const size_t m = v.h_stages.size();
-    const int ntiles = 2 * pr.ntiles_v;
-    Stage3Args a;
-    memset(&a, 0, sizeof a);
-    a.stage = v.h_stages[s];
-    a.subs = v.d_subs3;
-    a.umat = v.d_umat;
-    a.nsubs_total = (int)v.h_subs3.size();
+// Stage s of a virtual plan (vsw, vinv) on the virtual register.  Its geometry: two items per lane (the tiles of the first stage that
+// the lhs state occupies), each a register of nvp qubits in ntiles_v tiles, walked by the item list that project_init_kernel writes.
+Stage3Args virtual_stage3_args(aqc_ws* ws, const DevPlan& v, size_t s) {
+    const ProjRoute& pr = ws->proj;
+    Stage3Args a = stage3_args(ws, v, s);
     a.lane_stride = 2ull << pr.nvp;
-    a.ntiles = ntiles;
-    a.batch = ws->batch;
-    a.in0 = pr.vm; a.in1 = pr.vy; a.out0 = pr.vm; a.out1 = pr.vy;
-    a.store_out = s + 1 < m ? 3 : 0;
+    a.ntiles = 2 * pr.ntiles_v;
     a.items = pr.d_items; a.nitems = pr.d_count; a.max_items = 2 * ws->batch * pr.ntiles_v;
-    a.rpart = v.d_rpart;
-    a.nparts = ntiles;
-    a.chunk = 0;
-    if (a.stage.nsubs > 0) stage3_first_offsets(a, v.h_subs3[a.stage.sub_begin]);
+    return a;
+}
+// stage s of the virtual sweep plan on (vm, vy); every item writes the partial-R slot its list entry names
+Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s) {
+    const ProjRoute& pr = ws->proj;
+    Stage3Args a = virtual_stage3_args(ws, pr.vsw, s);
+    a.in0 = pr.vm; a.in1 = pr.vy; a.out0 = pr.vm; a.out1 = pr.vy;
+    a.store_out = s + 1 < pr.vsw.h_stages.size() ? 3 : 0;
+    stage3_sweep_fields(a, pr.vsw, a.ntiles, 0);
     return a;
 }
 
@@ -317,67 +310,55 @@ bool vdag_route_projected(aqc_ws* ws, int x_buf) {
     return true;
 }
 
-static Stage3Args virtual_apply_stage(aqc_ws* ws, DevPlan& v, size_t s, const double2* src, double2* dst) {
-    ProjRoute& pr = ws->proj;
-    Stage3Args a;
-    memset(&a, 0, sizeof a);
-    a.stage = v.h_stages[s];
-    a.subs = v.d_subs3;
-    a.umat = v.d_umat;
-    a.nsubs_total = (int)v.h_subs3.size();
-    a.lane_stride = 2ull << pr.nvp;
-    a.ntiles = 2 * pr.ntiles_v;
-    a.batch = ws->batch;
-    a.in0 = s == 0 ? src : dst;
-    a.out0 = dst;
-    a.items = pr.d_items; a.nitems = pr.d_count; a.max_items = 2 * ws->batch * pr.ntiles_v;
+// One member of a couple of independent launches: a list stage on the full-size register (real), or the stages of a virtual plan
+// from src into dst (in place after the first).  enqueue_couple runs the members it is given -- both: as ONE launch
+// (projected_pairs: the virtual plan has a single stage then, of the real stage's tile size k).
+struct VirtualRun { const DevPlan& plan; const double2* src; double2* dst; };
+static Stage3Args virtual_apply_stage(aqc_ws* ws, const VirtualRun& v, size_t s) {
+    Stage3Args a = virtual_stage3_args(ws, v.plan, s);
+    a.in0 = s == 0 ? v.src : v.dst;
+    a.out0 = v.dst;
     return a;
 }
-static int virtual_apply(aqc_ws* ws, DevPlan& v, const double2* src, double2* dst) {
-    for (size_t s = 0; s < v.h_stages.size(); ++s) {
-        const Stage3Args a = virtual_apply_stage(ws, v, s, src, dst);
+static int enqueue_couple(aqc_ws* ws, int k, const Stage3Args* real, const VirtualRun* v) {
+    if (real && v) {
         ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
-        HIP_OK(launch_apply3(a.ntiles, ws->batch, ws->proj.kv, ws->stream, a));
+        HIP_OK(launch_apply3_pair(k, ws->stream, *real, virtual_apply_stage(ws, *v, 0)));
+    } else if (real) {
+        ProfScope ps(ws, AQC_K_APPLY_LIST);
+        HIP_OK(launch_apply3(k, ws->stream, *real));
+    } else {
+        for (size_t s = 0; s < v->plan.h_stages.size(); ++s) {
+            ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
+            HIP_OK(launch_apply3(ws->proj.kv, ws->stream, virtual_apply_stage(ws, *v, s)));
+        }
     }
     return 0;
 }
 
 int run_vdag_projected(aqc_ws* ws, int x_buf) {   // the caller has asked vdag_route_projected, sweep_sparse_prepare
     ProjRoute& pr = ws->proj;
-    DevPlan& p = ws->sweep;
+    const DevPlan& p = ws->sweep;
+    const DevPlan& iv = ws->inv;
     if (ensure_umat(ws, ws->inv)) return 1;
     if (!ws->d_sw_items || !ws->w_clean) return fail("objective by projection without the sparse route's preparation");
     if (ensure_sweep_items(ws, x_buf)) return 1;
+    Stage3Args psi = stage3_args(ws, p, 0);   // the first stage's gates on the basis index, on the listed tiles: x -> W
+    psi.in0 = ws->bufs[x_buf];
+    psi.out0 = ws->bufs[AQC_BUF_W];
+    stage3_first_list(ws, psi);
+    Stage3Args last = stage3_args(ws, iv, iv.h_stages.size() - 1);   // V^H's last stage on the lhs tiles: ZW -> Z
+    last.in0 = ws->bufs[AQC_BUF_ZW];
+    last.out0 = ws->bufs[AQC_BUF_Z];
+    stage3_first_list(ws, last);
+    const VirtualRun mend{pr.vsw, pr.vm, pr.vme};   // M_end = (later stages' gates) M_0
+    const VirtualRun y0{pr.vinv, pr.vy, pr.vy};     // Y_0 = (later stages)^H Y_end
+    const ProjArgs a = proj_args(ws);
     const bool pairs = projected_pairs(ws);
-    Stage3Args psi;
-    {   // psi: the first stage's gates on the basis index, on the listed tiles (x -> W)
-        Stage3Args a;
-        memset(&a, 0, sizeof a);
-        a.stage = p.h_stages[0];
-        a.subs = p.d_subs3;
-        a.umat = p.d_umat;
-        a.nsubs_total = (int)p.h_subs3.size();
-        a.lane_stride = ws->lane_elems;
-        a.ntiles = p.ntiles;
-        a.batch = ws->batch;
-        a.in0 = ws->bufs[x_buf];
-        a.out0 = ws->bufs[AQC_BUF_W];
-        a.items = ws->d_sw_items; a.nitems = ws->d_sw_counts; a.max_items = 2 * ws->batch;
-        if (pairs) {
-            psi = a;
-        } else {
-            ProfScope ps(ws, AQC_K_APPLY_LIST);
-            HIP_OK(launch_apply3(p.ntiles, ws->batch, p.k, ws->stream, a));
-        }
-    }
-    ProjArgs a = proj_args(ws);
-    if (ensure_pattern(ws, a)) return 1;
-    if (pairs) {   // psi with M_end
-        const Stage3Args mend = virtual_apply_stage(ws, pr.vsw, 0, pr.vm, pr.vme);
-        ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
-        HIP_OK(launch_apply3_pair(pr.kv, ws->stream, psi, mend));
-    } else if (virtual_apply(ws, pr.vsw, pr.vm, pr.vme)) return 1;   // M_end
-    const unsigned* off_us = pr.d_tab + (1u << pr.t);
+
+    if (!pairs && enqueue_couple(ws, p.k, &psi, nullptr)) return 1;          // psi
+    if (ensure_pattern(ws, a)) return 1;                                      // M_0
+    if (enqueue_couple(ws, p.k, pairs ? &psi : nullptr, &mend)) return 1;     // M_end (pairs: with psi)
     if (ws->proj_fused_enabled && pr.us <= 10 && pr.cb <= 4 && (pr.us <= 8 || pr.vy_copies == 1 << (pr.us - 8))) {   // both products from one fetch of the target
         ProjArgs q = a;
         q.part_stride = (size_t)ws->batch * (2ull << pr.nvp);
@@ -386,53 +367,22 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // the caller has asked vdag_r
         ProfScope ps(ws, AQC_K_PROJECT);
         HIP_OK(launch_project_fused(q, pr.vme, ws->bufs[AQC_BUF_ZW], pr.vy, ws->stream));
     } else {
-    {   // Y_end = proj(y)
-        ProjArgs q = a;
-        q.y = ws->bufs[AQC_BUF_Y]; q.s = ws->bufs[AQC_BUF_W]; q.out = pr.vy;
-        q.s_virtual = 0; q.out_virtual = 1; q.staged = 1;
-        q.keep_bits = pr.t; q.k_bits = pr.us;
-        q.y_keep = ProjMap{pr.d_tab, 0}; q.y_k = ProjMap{off_us, 0};
-        q.s_k = ProjMap{off_us, 0}; q.s_c = ProjMap{a.off_cb, 0};
-        q.o_keep = ProjMap{nullptr, 0}; q.o_c = ProjMap{nullptr, pr.t};
-        ProfScope ps(ws, AQC_K_PROJECT);
-        HIP_OK(launch_project(q, ws->stream));
-    }
-    {   // the lhs tile of (later stages)^H y, into ZW
-        ProjArgs q = a;
+        {   // Y_end = proj(y)
+            ProfScope ps(ws, AQC_K_PROJECT);
+            HIP_OK(launch_project(y_product(ws, a, ws->bufs[AQC_BUF_Y]), ws->stream));
+        }
+        ProjArgs q = a;   // the lhs tile of (later stages)^H y, into ZW
         q.y = ws->bufs[AQC_BUF_Y]; q.s = pr.vme; q.out = ws->bufs[AQC_BUF_ZW];
         q.s_virtual = 1; q.out_virtual = 0; q.staged = 0;
         q.keep_bits = pr.us; q.k_bits = pr.t;
-        q.y_keep = ProjMap{off_us, 0}; q.y_k = ProjMap{pr.d_tab, 0};
+        q.y_keep = ProjMap{a.off_us, 0}; q.y_k = ProjMap{a.off_t, 0};
         q.s_k = ProjMap{nullptr, 0}; q.s_c = ProjMap{nullptr, pr.t};
-        q.o_keep = ProjMap{off_us, 0}; q.o_c = ProjMap{a.off_cb, 0};
+        q.o_keep = ProjMap{a.off_us, 0}; q.o_c = ProjMap{a.off_cb, 0};
         ProfScope ps(ws, AQC_K_PROJECT);
         HIP_OK(launch_project(q, ws->stream));
     }
-    }
-    if (!pairs && virtual_apply(ws, pr.vinv, pr.vy, pr.vy)) return 1;   // Y_0
-    {   // V^H's last stage on the lhs tiles: ZW -> Z
-        DevPlan& iv = ws->inv;
-        Stage3Args s3;
-        memset(&s3, 0, sizeof s3);
-        s3.stage = iv.h_stages.back();
-        s3.subs = iv.d_subs3;
-        s3.umat = iv.d_umat;
-        s3.nsubs_total = (int)iv.h_subs3.size();
-        s3.lane_stride = ws->lane_elems;
-        s3.ntiles = iv.ntiles;
-        s3.batch = ws->batch;
-        s3.in0 = ws->bufs[AQC_BUF_ZW];
-        s3.out0 = ws->bufs[AQC_BUF_Z];
-        s3.items = ws->d_sw_items; s3.nitems = ws->d_sw_counts; s3.max_items = 2 * ws->batch;
-        if (pairs) {   // ... with Y_0
-            const Stage3Args y0 = virtual_apply_stage(ws, pr.vinv, 0, pr.vy, pr.vy);
-            ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
-            HIP_OK(launch_apply3_pair(pr.kv, ws->stream, s3, y0));
-        } else {
-            ProfScope ps(ws, AQC_K_APPLY_LIST);
-            HIP_OK(launch_apply3(iv.ntiles, ws->batch, iv.k, ws->stream, s3));
-        }
-    }
+    if (!pairs && enqueue_couple(ws, iv.k, nullptr, &y0)) return 1;           // Y_0
+    if (enqueue_couple(ws, iv.k, &last, pairs ? &y0 : nullptr)) return 1;     // V^H's last stage (pairs: with Y_0)
     vdag_projected_state_after(ws, x_buf);
     return 0;
 }

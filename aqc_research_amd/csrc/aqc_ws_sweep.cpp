@@ -118,9 +118,8 @@ int run_coef(aqc_ws* ws, double* d_thetas) {
     return 0;
 }
 
-namespace {
-
 #ifdef AQC_TUNING   // AQC_STAMPS=1: mean cycles per phase of the workgroups of one launch, on stderr (tuning builds only)
+namespace {
 unsigned long long* g_stamps = nullptr;
 int stamps_begin(aqc_ws* ws, Stage3Args& a, size_t nwg) {
     if (env_int("AQC_STAMPS", 0) == 0 || nwg > 65536) return 0;
@@ -183,6 +182,7 @@ int stamps_sweep(aqc_ws* ws, const Stage3Args& a, size_t s, size_t nwg) {
             "first start -> last end %llu\n", s, wg_min, wg_max, last_start - first_start, last_end - first_end, last_end - first_start);
     return 0;
 }
+}  // namespace
 #endif
 
 Stage3Args stage3_args(aqc_ws* ws, const DevPlan& p, size_t s) {
@@ -197,8 +197,15 @@ Stage3Args stage3_args(aqc_ws* ws, const DevPlan& p, size_t s) {
     a.batch = ws->batch;
     return a;
 }
-
-}  // namespace
+void stage3_first_list(const aqc_ws* ws, Stage3Args& a) {   // (ensure_sweep_items: at most two tiles per lane)
+    a.items = ws->d_sw_items; a.nitems = ws->d_sw_counts; a.max_items = 2 * ws->batch;
+}
+void stage3_sweep_fields(Stage3Args& a, const DevPlan& p, int nparts, int chunk) {
+    a.rpart = p.d_rpart;
+    a.nparts = nparts;
+    a.chunk = chunk;
+    if (a.stage.nsubs > 0) stage3_first_offsets(a, p.h_subs3[a.stage.sub_begin]);
+}
 
 // V^H into Z by the mirrored plan keeps the state before its last stage in ZW (see the head of this file)
 static bool keeps_checkpoint(const aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
@@ -229,7 +236,7 @@ int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
 #endif
             {
                 ProfScope ps(ws, AQC_K_APPLY);
-                HIP_OK(launch_apply3(p.ntiles, ws->batch, p.k, ws->stream, a));
+                HIP_OK(launch_apply3(p.k, ws->stream, a));
             }
 #ifdef AQC_TUNING
             if (stamps_apply(ws, a, s, nwg)) return 1;
@@ -288,7 +295,7 @@ int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set) {   /
         a.in0 = s == 0 ? ws->bufs[AQC_BUF_Y] : ws->bufs[AQC_BUF_ZW];
         a.out0 = ws->bufs[AQC_BUF_ZW];
         ProfScope ps(ws, AQC_K_APPLY);
-        HIP_OK(launch_apply3(p.ntiles, ws->batch, p.k, ws->stream, a));
+        HIP_OK(launch_apply3(p.k, ws->stream, a));
     }
     const bool gather_only = support_in_gather_set && ws->gather_count > 0;
     const ListKey key = key_of(ws, gather_only ? ListKey::kGatherOnly : x_buf, true);
@@ -305,7 +312,7 @@ int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set) {   /
     ws->sw_lists_built |= 2;
     {
         ProfScope ps(ws, AQC_K_APPLY_LIST);
-        HIP_OK(launch_apply3(p.ntiles, ws->batch, p.k, ws->stream, a));
+        HIP_OK(launch_apply3(p.k, ws->stream, a));
     }
     vdag_restricted_state_after(ws, x_buf);
     return 0;
@@ -329,7 +336,7 @@ static int ensure_z_full(aqc_ws* ws, bool reader) {
     if (ws->ckpt_valid && ws->inv.u_valid) {   // the last stage once more, over every tile (its inputs are all in ZW)
         Stage3Args a = last_vdag_stage(ws);
         ProfScope ps(ws, AQC_K_APPLY);
-        HIP_OK(launch_apply3(ws->inv.ntiles, ws->batch, ws->inv.k, ws->stream, a));
+        HIP_OK(launch_apply3(ws->inv.k, ws->stream, a));
         ws->z_full = true;
         return 0;
     }
@@ -499,6 +506,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
         if (ensure_umat(ws, p)) return 1;
         const int nsubs = (int)p.h_subs3.size();
         const size_t m = p.h_stages.size();
+        const int nparts = sweep3_nparts(p.ntiles, ws->batch, p.k), chunk = sweep3_chunk(p.ntiles, ws->batch, p.k);
         const bool sparse = sweep_route_sparse(ws, x_buf, false);
         const bool skipw = sweep_skips_zero_w(ws, x_buf);
         const bool projected = sweep_route_projected(ws, sparse);   // the stages after the first on the virtual register (aqc_ws_project.cpp)
@@ -532,7 +540,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
                 a.out0 = s == 0 ? ws->bufs[AQC_BUF_W] : w2;
                 a.out1 = s == 0 ? nullptr : z2;
                 a.store_out = s + 1 < m ? (s == 0 ? 1 : 3) : 0;
-                if (s == 0) { a.items = ws->d_sw_items; a.nitems = ws->d_sw_counts; a.max_items = 2 * ws->batch; }
+                if (s == 0) stage3_first_list(ws, a);
                 if (s == 0 && first_stage_r_only) { a.r_only_last = 1; a.store_out = 0; }
             } else {
                 a.in0 = s == 0 ? ws->bufs[x_buf] : ws->bufs[AQC_BUF_W];
@@ -543,10 +551,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
             }
             if (skipw && !a.items) a.supp = ws->d_combo_prev[x_buf];
             if (s + 1 == m && r_only_sub >= 0) a.r_only_last = 1;
-            a.rpart = p.d_rpart;
-            a.chunk = sweep3_chunk(p.ntiles, ws->batch, p.k);
-            a.nparts = sweep3_nparts(p.ntiles, ws->batch, p.k);
-            if (a.stage.nsubs > 0) stage3_first_offsets(a, p.h_subs3[a.stage.sub_begin]);
+            stage3_sweep_fields(a, p, nparts, chunk);
 #ifdef AQC_TUNING
             const size_t nwg = (size_t)p.ntiles * ws->batch;
             a.debug = env_int("AQC_DEBUG_SKIP", 0);
@@ -558,7 +563,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
                 HIP_OK(launch_sweep3_pair(p.k, ws->stream, a, b));
             } else {
                 ProfScope ps(ws, a.items ? AQC_K_SWEEP_LIST : AQC_K_SWEEP);
-                HIP_OK(launch_sweep3(p.ntiles, ws->batch, p.k, ws->stream, a));
+                HIP_OK(launch_sweep3(p.k, ws->stream, a));
             }
 #ifdef AQC_TUNING
             if (stamps_sweep(ws, a, s, nwg)) return 1;
@@ -574,7 +579,7 @@ int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int fron
                             ws->grads_direct ? ws->d_slot_theta : nullptr, ws->d_grads, ws->mirror_grads,
                             ws->gather_rides ? GatherJob{ws->bufs[AQC_BUF_Z], ws->lane_elems, ws->d_index, ws->gather_count, ws->d_small, ws->mirror_small}
                                              : GatherJob{nullptr, 0, nullptr, 0, nullptr, nullptr},
-                            sweep3_nparts(p.ntiles, ws->batch, p.k), sweep3_chunk(p.ntiles, ws->batch, p.k),
+                            nparts, chunk,
                             sparse ? p.h_stages[0].nsubs : 0, sparse ? ws->d_sw_lane_parts : nullptr, r_only_sub, p.d_umat,
                             projected ? p.h_stages[0].nsubs : -1, projected ? &vwalk : nullptr));
 #ifdef AQC_TUNING

@@ -124,11 +124,11 @@ def test_pairs_equal_the_single_launches(case, grid, monkeypatch):
 
 
 @pytest.mark.parametrize("kind,n,arg,tile,paired", [("spin", 14, 24, 8, False), ("trotter", 14, 2, 12, False), ("spin", 13, 18, 8, True),
-                                                    ("spin", 15, 30, 10, True)])
+                                                    ("spin", 15, 30, 10, True), ("spin", 14, 24, 11, True)])
 def test_shapes_off_the_headline_form(kind, n, arg, tile, paired, monkeypatch):
     """Two virtual stages (14 qubits, 24 blocks, 2^8 tiles) and a Trotter circuit whose virtual tiles are smaller than the real ones: the
-    route keeps its single launches.  One virtual stage of 2^8 and 2^10 tiles: no persistent walk, the pair is the two lists behind
-    each other in one grid.  The same bits either way."""
+    route keeps its single launches.  One virtual stage of 2^8, 2^10 and 2^11 tiles: no persistent walk, the pair is the two lists
+    behind each other in one grid.  The same bits either way."""
     circ, tg, ths, basis, gather, ref = _case(kind, n, arg, tile, "zero")
     on, kinds_on, info = _run(circ, tg, ths, basis, gather, monkeypatch, tile, True)
     off, kinds_off, _ = _run(circ, tg, ths, basis, gather, monkeypatch, tile, False)
