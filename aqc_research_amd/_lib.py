@@ -125,6 +125,12 @@ SIGNATURES = {
     "aqc_ws_lbfgs": (c_int, [_P, _D, c_int, c_int, c_double, c_double, c_double, c_int, c_int, c_int, c_int, _D, _D, _D, POINTER(c_int64),
                      POINTER(c_int64), _D, POINTER(c_int64)]),
     "aqc_ws_surrogate_eval": (c_int, [_P, _D, c_int, _D, POINTER(c_int64), c_int, c_int, c_int, _D, _D, _D, _D, _D]),
+    "aqc_qr": (c_int, [c_int, c_int, c_int, _D, _D, POINTER(c_int32)]),
+    "aqc_ws_sketch_target": (c_int, [_P, _D, c_int]),
+    "aqc_ws_sketch_generate": (c_int, [_P, c_int, ctypes.c_uint64, c_int64, POINTER(c_int32), _D, POINTER(c_int32)]),
+    "aqc_ws_sketch_draw": (c_int, [_P, c_int, ctypes.c_uint64, c_int64, c_int]),
+    "aqc_ws_sketch_adam": (c_int, [_P, c_int, _D, c_int, _D, c_double, c_double, c_double, c_double, ctypes.c_uint64, c_int64, POINTER(c_int32),
+                           POINTER(c_int32), _D, _D, _D, _D, POINTER(c_int64), POINTER(c_int32)]),
     "aqc_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "aqc_comm_create": (c_int, [ctypes.c_char_p, c_int, c_int, c_int, POINTER(_P)]),
     "aqc_comm_destroy": (c_int, [_P]),
@@ -161,6 +167,8 @@ def lib() -> ctypes.CDLL:
 
 
 LANES_REFUSED = 3   # AQC_LANES_REFUSED of include/aqc_hip.h
+SKETCH_KINDS = {"rand": 0, "alt": 1, "eigen": 2}   # AQC_SKETCH_*
+QR_RANK_DEFICIENT = 1   # AQC_QR_RANK_DEFICIENT
 
 
 class LanesRefused(RuntimeError):

@@ -478,6 +478,9 @@ int aqc_ws_destroy(aqc_ws* ws) {
     if (ws->d_cd_thetas) (void)hipFree(ws->d_cd_thetas);
     if (ws->d_cd_fobj) (void)hipFree(ws->d_cd_fobj);
     if (ws->d_mps_lam) (void)hipFree(ws->d_mps_lam);
+    for (void* q : {(void*)ws->sk.target, (void*)ws->sk.qr_part, (void*)ws->sk.qr_rinv, (void*)ws->sk.tmp, (void*)ws->sk.status, (void*)ws->sk.idx,
+                    (void*)ws->sk.adam, (void*)ws->sk.adam_i, (void*)ws->sk.profile})
+        if (q) (void)hipFree(q);
     for (hipEvent_t ev : {ws->ev0, ws->ev1, ws->pev0, ws->pev1, ws->ev_ready, ws->ev_copied}) if (ev) (void)hipEventDestroy(ev);
     if (ws->copy_stream) { (void)hipStreamSynchronize(ws->copy_stream); (void)hipStreamDestroy(ws->copy_stream); }
     if (ws->mps_stream) { (void)hipStreamSynchronize(ws->mps_stream); (void)hipStreamDestroy(ws->mps_stream); }

@@ -319,4 +319,35 @@ hipError_t launch_mps_split(const void* W, const void* V, const int* ord, const 
                             int k, int mode, double rescale, void* tq, void* tq1, const double* lam_new, double* lam_dst, hipStream_t s);   // lam_new (device, may be null) -> lam_dst[0..k)
 hipError_t launch_mps_colscale(void* t, const double* lam, size_t rows, int cols, int mul, hipStream_t s);
 
+// aqc_sketch.hip (sketched AQC on the device: generators, tall-skinny QR, ADAM)
+// CholeskyQR2 of `batch` (d x k) c128 matrices (row-major, leading dimension lda, lane_stride elements apart), in place; k a power of
+// two <= 64, k <= d.  partial: [batch][sk_qr_slabs(d)][k][k] c128, rinv: [batch][k][k] c128, status: [batch] ints (lanes with a non-zero
+// word are skipped; a pivot <= abs_floor, or negligible against its column, sets AQC_QR_RANK_DEFICIENT and leaves the lane untouched)
+int sk_qr_slabs(int d);
+hipError_t launch_sk_qr(void* a, size_t lane_stride, int lda, int d, int k, int batch, double abs_floor, void* partial, void* rinv, int* status,
+                        hipStream_t s);
+// x <- one-hot columns idx[lane][k], y <- u[:, idx]; u: [batch or 1][d][d] (u_stride 0: one target for all lanes)
+hipError_t launch_sk_alt(void* x, void* y, size_t lane_stride, int pitch, int d, int k, const void* u, size_t u_stride, const int* idx, int batch,
+                         hipStream_t s);
+// the (d x k) draw of every lane by the rule of aqc_philox.h: uniform + i uniform, or (normal != 0) Box-Muller normals
+hipError_t launch_sk_omega(void* out, size_t lane_stride, int pitch, int d, int k, unsigned long long seed, unsigned long long stream,
+                           unsigned long long iteration, int normal, int batch, hipStream_t s);
+hipError_t launch_sk_sub(void* a, const void* b, size_t lane_stride, int pitch, int d, int k, int batch, hipStream_t s);
+// One evaluation's bookkeeping and (do_update) one ADAM step per lane.  fobj = 1 - Re trace / k goes to profile[lane][col]; a lane that
+// has not finished (flag < 2) records the best value and its thetas; flag 0 -> the m / v / theta update of optimizer.py:178-189 with
+// g = -Re grads / k, t and nit advance, and a step norm below tol turns the flag to 1 (converged: thetas stay); flag 1 -> 2 (the
+// evaluation at the final point has been taken).
+struct SkAdam {
+    int B, T, k, profile_stride;
+    double* thetas;            // [B][T], updated in place
+    const double2* trace;      // [B]
+    const double2* grads;      // [B][T]
+    double *m, *v, *best_x;    // [B][T]
+    double *best_f, *profile;  // [B], [B][profile_stride]
+    const double* lr;          // [B]
+    int *t, *nit, *flag;       // [B]
+    double beta1, beta2, eps, tol;
+};
+hipError_t launch_sk_adam(const SkAdam& st, int col, int do_update, hipStream_t s);
+
 }  // namespace aqc

@@ -4,6 +4,7 @@
 //   aqc_ws_sweep.cpp   V / V^H launches, the w/z sweep (dense and sparse-lhs routes), aqc_ws_eval
 //   aqc_ws_optim.cpp   device-resident L-BFGS and the one-call surrogate evaluation
 //   aqc_ws_extra.cpp   zgemm, gate-level building blocks, coordinate descent, MPS helpers
+//   aqc_ws_sketch.cpp  sketched AQC: resident targets, sketching-vector generators, device-resident ADAM, aqc_qr
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -242,6 +243,22 @@ struct aqc_ws {
     std::vector<long long> h_gather;        // host copy of the registered gather indices (elements)
     aqc::ListKey projb_key;                 // what the verdict below was taken for
     bool projb_ok = false;
+    // sketched AQC (aqc_ws_sketch.cpp): the d x d target(s) and everything a device-resident ADAM run keeps between its launches
+    struct Sketch {
+        double2* target = nullptr;      // [batch or 1][d][d]
+        bool shared = false;
+        double2* qr_part = nullptr;     // gram partials [batch][slabs][k][k]
+        double2* qr_rinv = nullptr;     // [batch][k][k]
+        double2* tmp = nullptr;         // [batch] lanes of scratch (U^H Omega)
+        int* status = nullptr;          // [batch] QR status words
+        int* idx = nullptr;             // alt column indices [sets][batch][k]
+        size_t idx_cap = 0;
+        double* adam = nullptr;         // m | v | best_x [batch][T] each, then best_f | lr [batch]
+        int* adam_i = nullptr;          // t | nit | flag [batch]
+        double* profile = nullptr;      // [batch][profile_cap]
+        size_t profile_cap = 0;
+        bool adam_started = false;
+    } sk;
     bool profile = false;
     int64_t prof_count[AQC_NUM_KINDS] = {};
     double prof_ms[AQC_NUM_KINDS] = {};

@@ -325,6 +325,69 @@ class Workspace:
     def sync(self) -> None:
         check(self._L.aqc_ws_sync(self.handle))
 
+    # -- sketched AQC on the device (aqc_ws_sketch_*) ---------------------------
+    def sketch_target(self, target, shared: Optional[bool] = None) -> None:
+        """The target unitary of every lane, (batch, d, d), or one (d, d) for all lanes, resident in HBM."""
+        u = _lib.as_c128(target)
+        if shared is None:
+            shared = u.ndim == 2
+        if u.size != (1 if shared else self.batch) * self.dim * self.dim:
+            raise ValueError(f"target of shape {u.shape} does not fit {'one' if shared else self.batch} ({self.dim}, {self.dim}) matrices")
+        check(self._L.aqc_ws_sketch_target(self.handle, dptr(u), int(bool(shared))))
+
+    def _alt_idx(self, alt_idx, sets: int):
+        if alt_idx is None:
+            return None, None
+        idx = np.ascontiguousarray(alt_idx, dtype=np.int32)
+        if idx.size != sets * self.batch * self.ncols:
+            raise ValueError(f"alt_idx needs {sets} x {self.batch} x {self.ncols} column indices, got shape {idx.shape}")
+        return idx, idx.ctypes.data_as(ctypes.POINTER(c_int32))
+
+    def sketch_generate(self, kind: str, seed: int = 0, iteration: int = 0, alt_idx=None, omega=None, status: bool = True):
+        """X, Y = U X of every lane into BUF_X / BUF_Y on the device, with the thetas in use (``eigen``).  ``omega``: a host
+        draw (batch, d, k) instead of the device's Philox draw; ``alt_idx``: (batch, k) columns for ``alt``.  Returns the QR's
+        status word per lane (int32[batch]; 0 = fine), or None with ``status=False`` (nothing is waited for then)."""
+        self._touch(BUF_X, BUF_Y)
+        keep, idx = self._alt_idx(alt_idx, 1)
+        om = None
+        if omega is not None:
+            om = _lib.as_c128(omega)
+            if om.size != self.batch * self.dim * self.ncols:
+                raise ValueError(f"omega must have shape {self._shape()}")
+        st = np.zeros(self.batch, dtype=np.int32) if status else None
+        check(self._L.aqc_ws_sketch_generate(self.handle, _lib.SKETCH_KINDS[kind], int(seed), int(iteration), idx, None if om is None else dptr(om),
+                                             None if st is None else st.ctypes.data_as(ctypes.POINTER(c_int32))))
+        del keep
+        return st
+
+    def sketch_draw(self, kind: str, seed: int = 0, iteration: int = 0, buf: int = BUF_X) -> None:
+        """``buf`` <- the device's draw Omega of every lane for (kind, seed, iteration), nothing else (``rand`` / ``eigen``)."""
+        self._touch(buf)
+        check(self._L.aqc_ws_sketch_draw(self.handle, _lib.SKETCH_KINDS[kind], int(seed), int(iteration), buf))
+
+    def sketch_adam(self, kind: str, x0, niter: int, lr, *, beta1: float = 0.9, beta2: float = 0.99, eps: float = 1e-8, tol: float = 1e-6,
+                    seed: int = 0, iter0: int = 0, reset=None, alt_idx=None) -> dict:
+        """``niter`` ADAM iterations of the sketched objective on every lane without leaving the device (aqc_ws_sketch_adam), one
+        fetch at the end.  ``lr``: a number or one per lane; ``reset``: None, a number or one per lane (0 continue, 1 restart from
+        x0, 2 parked); ``alt_idx``: (niter + 1, batch, k).  Returns x (batch, T), profile (batch, niter + 1), nit (batch,), cost
+        (profile[lane][nit[lane]]: the objective at the final point under the next sketch), best_f, best_x, status."""
+        self._touch(BUF_X, BUF_Y, BUF_Z, BUF_W, BUF_ZW)
+        niter = int(niter)
+        keep, idx = self._alt_idx(alt_idx, niter + 1)
+        x0a = None if x0 is None else _lib.as_f64(x0, self.batch * self.T, "x0")
+        lra = np.ascontiguousarray(np.broadcast_to(np.asarray(lr, dtype=np.float64), (self.batch,)))
+        rs = None if reset is None else np.ascontiguousarray(np.broadcast_to(np.asarray(reset, dtype=np.int32), (self.batch,)))
+        x = np.empty((self.batch, self.T))
+        prof = np.empty((self.batch, niter + 1))
+        best_f, best_x = np.empty(self.batch), np.empty((self.batch, self.T))
+        nit, st = np.zeros(self.batch, dtype=np.int64), np.zeros(self.batch, dtype=np.int32)
+        i32 = ctypes.POINTER(c_int32)
+        check(self._L.aqc_ws_sketch_adam(self.handle, _lib.SKETCH_KINDS[kind], None if x0a is None else dptr(x0a), niter, dptr(lra), beta1, beta2,
+                                         eps, tol, int(seed), int(iter0), None if rs is None else rs.ctypes.data_as(i32), idx, dptr(x), dptr(prof),
+                                         dptr(best_f), dptr(best_x), nit.ctypes.data_as(ctypes.POINTER(c_int64)), st.ctypes.data_as(i32)))
+        del keep
+        return {"x": x, "profile": prof, "nit": nit, "cost": prof[np.arange(self.batch), nit], "best_f": best_f, "best_x": best_x, "status": st}
+
     # -- measurement ---------------------------------------------------------
     def timer_start(self) -> None:
         check(self._L.aqc_ws_timer_start(self.handle))
@@ -612,6 +675,29 @@ Workspace.mps_dot = _ws_mps_dot
 Workspace.mps_slot_for = _ws_mps_slot_for
 Workspace.mps_forget = _ws_mps_forget
 Workspace.mps_to_vec_batch = _ws_mps_to_vec_batch
+
+
+class RankDeficientSketch(RuntimeError):
+    """The device QR of a lane's sketching matrix met a vanishing pivot (for instance ``eigen`` with V = U: nothing left to sketch).
+    ``lanes`` names the lanes."""
+
+    def __init__(self, lanes):
+        self.lanes = [int(b) for b in lanes]
+        super().__init__(f"aqc_hip: the sketching matrix of lane(s) {self.lanes} is rank deficient")
+
+
+def qr(a: np.ndarray, device: Optional[int] = None) -> np.ndarray:
+    """Orthonormal basis of the columns of ``a`` (m x k, k a power of two <= 64) by the device's CholeskyQR2 (aqc_qr): what
+    ``np.linalg.qr(a)[0]`` spans.  Raises RankDeficientSketch when a pivot vanishes."""
+    a = _lib.as_c128(a)
+    if a.ndim != 2:
+        raise ValueError("qr expects a matrix")
+    q = np.empty_like(a)
+    st = c_int32(0)
+    check(_lib.lib().aqc_qr(default_device() if device is None else int(device), a.shape[0], a.shape[1], dptr(a), dptr(q), byref(st)))
+    if st.value:
+        raise RankDeficientSketch([0])
+    return q
 
 
 def zgemm(a: np.ndarray, b: np.ndarray, conj_trans_a: bool = False, device: Optional[int] = None) -> np.ndarray:

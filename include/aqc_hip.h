@@ -382,6 +382,42 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
                  int max_backtracks, int block_from, int block_to, int front_layer, double* x_out, double* f_out,
                  double* fidelity_out, int64_t* nit_out, int64_t* nfev_out, double* weight_out, int64_t* max_no_out);
 
+/* ---- sketched AQC on the device: the stochastic optimisation of aqc_sketching.py:53-104 (ADAM on SketchingObjectiveEx with a fresh
+ * set of `rand` / `alt` / `eigen` sketching vectors on every objective call, sk_core.py:329-464) with every iteration resident in HBM.
+ * Matrix workspaces with ncols = k sketching vectors, k a power of two, 1 < k <= 64, k < 2^n; no Trotter ansatz.  Draws come from
+ * Philox4x64-10 by the rule at the head of csrc/aqc_philox.h (NumPy's Philox reproduces them bit for bit); the host path
+ * (model_sketching/sk_core.py with np.random) is untouched. */
+enum { AQC_SKETCH_RAND = 0, AQC_SKETCH_ALT = 1, AQC_SKETCH_EIGEN = 2 };
+enum { AQC_QR_OK = 0, AQC_QR_RANK_DEFICIENT = 1 };   /* per-matrix status word of the device QR */
+/* np.linalg.qr(a)[0] of sk_core.py:353,459 up to the choice of basis: q_out (m x k, row-major) has orthonormal columns spanning the
+ * columns of a (m x k, k a power of two <= 64, m >= k), by CholeskyQR2 on the matrix cores; host pointers, one matrix, like the SVD entry.
+ * A rank-deficient a sets *status = AQC_QR_RANK_DEFICIENT and q_out = a (status NULL: the call fails instead). */
+int aqc_qr(int device, int m, int k, const double* a, double* q_out, int32_t* status);
+/* the target unitary of every lane (shared != 0: one for all), [batch or 1][2^n][2^n] c128, kept resident: what
+ * SketchingVectorsBase holds as target_matrix (sk_core.py:34-91).  The buffer is allocated on first use. */
+int aqc_ws_sketch_target(aqc_ws* ws, const double* U, int shared);
+/* SketchingVectorsBase.generate (sk_core.py:350-357 rand, :385-399 alt, :447-463 eigen) for every lane, on the device: AQC_BUF_X <- X,
+ * AQC_BUF_Y <- U X, with the thetas in use (eigen).  `iteration` numbers the sketch (part of the Philox counter); omega, when not
+ * NULL, is a host draw [batch][2^n][k] c128 used instead of the device's; alt_idx [batch][k] are the columns of `alt` (required
+ * there).  status (optional, [batch]; synchronises): the QR's word per lane -- a rank-deficient lane keeps its un-orthonormalised
+ * matrix in X, finite, and the other lanes are complete. */
+int aqc_ws_sketch_generate(aqc_ws* ws, int kind, uint64_t seed, int64_t iteration, const int32_t* alt_idx, const double* omega,
+                           int32_t* status);
+/* the draw alone: buf <- Omega of every lane for (kind = rand or eigen, seed, iteration), as the generate entry would draw it
+ * (np.random.rand / randn of sk_core.py:352,449-451; asynchronous) */
+int aqc_ws_sketch_draw(aqc_ws* ws, int kind, uint64_t seed, int64_t iteration, int buf);
+/* optimizer.py:178-189 (ADAM) driving sk_core.py:175-212 on every lane: niter iterations are enqueued without a host synchronisation
+ * in between (generate, V^H Y, trace, sweep, ADAM step per iteration), then one fetch.  Iteration t = 1..niter evaluates at x_{t-1}
+ * under sketch number iter0 + t; one more evaluation under sketch iter0 + niter + 1 follows without a step.  A lane whose step norm
+ * falls below tol stops moving; its nit counts the steps it took in this call, and fobj_profile[lane][nit] is the cost at its final
+ * point, as ADAM's result reports fun(x).  fobj_profile: [batch][niter + 1].  best_f / best_x: the smallest value seen since the
+ * lane's last restart and its thetas (sk_core.py:198-200).  lr: [batch].  reset (NULL: restart all on the first call, continue
+ * after): per lane 0 = continue with the m / v / t state and thetas left on the device (x0 ignored), 1 = restart from x0[lane],
+ * 2 = parked (no further steps).  alt_idx: [niter + 1][batch][k].  status: [batch] QR words, OR over the call. */
+int aqc_ws_sketch_adam(aqc_ws* ws, int kind, const double* x0, int niter, const double* lr, double beta1, double beta2, double eps,
+                       double tol, uint64_t seed, int64_t iter0, const int32_t* reset, const int32_t* alt_idx, double* x_out,
+                       double* fobj_profile, double* best_f, double* best_x, int64_t* nit, int32_t* status);
+
 /* ---- multi-GPU: the one collective layer of the path, bound straight to librccl (RCCL over xGMI; loaded lazily).
  * One process per GPU; jobs are sharded over the ranks (job_executor.py:136-143: joblib processes in the reference) and
  * only fixed-size result records cross GPUs.  All buffers are HOST pointers (the records are a few KB).

@@ -1,0 +1,288 @@
+"""Sketched AQC on the device (csrc/aqc_sketch.hip, aqc_ws_sketch_*): the tall-skinny QR, the three sketching-vector generators,
+the device-resident ADAM run against optimizer._adam on the oracle, and the driver's restart policy."""
+import numpy as np
+import pytest
+
+from oracle import aqc_oracle as orc
+from tests import sketch_ref as sk
+from tests.helpers import TOL, maxdiff
+
+pytestmark = pytest.mark.gpu
+
+QR_SHAPES = [(4, 1), (4, 2), (16, 4), (32, 8), (64, 16), (256, 64), (1024, 16)]
+
+
+def _rand_c(rng, *shape):
+    return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+
+
+def _unitary(rng, d):
+    return np.ascontiguousarray(np.linalg.qr(_rand_c(rng, d, d))[0])
+
+
+def _problem(n, ent, depth, k, lanes, seed):
+    from aqc_research_amd import ParametricCircuit
+    from aqc_research_amd.engine import HipContext, Workspace
+
+    rng = np.random.default_rng(seed)
+    circ = ParametricCircuit(n, ent, orc.spin_blocks(n, depth))
+    targets = np.stack([_unitary(rng, 1 << n) for _ in range(lanes)])
+    thetas = np.stack([orc.rand_thetas(circ.num_thetas, rng) for _ in range(lanes)])
+    ws = Workspace(HipContext.of(circ), batch=lanes, ncols=k)
+    ws.sketch_target(targets)
+    return circ, targets, thetas, ws, rng
+
+
+# ---- QR -------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("d,k", QR_SHAPES)
+def test_qr_orthonormal_basis_of_the_range(d, k):
+    from aqc_research_amd.engine import qr
+
+    a = _rand_c(np.random.default_rng(100 * d + k), d, k)
+    q, qh = qr(a), np.linalg.qr(a)[0]
+    e_orth, e_proj = maxdiff(np.conj(q.T) @ q, np.eye(k)), maxdiff(q @ np.conj(q.T), qh @ np.conj(qh.T))
+    print(f"qr {d}x{k}: |Q^H Q - I| = {e_orth:.2e}, |Q Q^H - Qh Qh^H| = {e_proj:.2e}")
+    assert e_orth < 1e-12
+    assert e_proj < TOL
+    assert np.array_equal(q, qr(a))   # bit-reproducible
+
+
+def test_qr_lanes_equal_single_calls_and_rank_deficiency_is_per_lane():
+    from aqc_research_amd.engine import BUF_X, BUF_Y, RankDeficientSketch, qr
+
+    n, k, lanes = 5, 8, 3
+    circ, targets, thetas, ws, rng = _problem(n, "cz", 12, k, lanes, 5)
+    d = 1 << n
+    mats = _rand_c(rng, lanes, d, k)
+    st = ws.sketch_generate("rand", omega=mats)
+    x = ws.download(BUF_X)
+    assert not st.any()
+    for b in range(lanes):
+        assert np.array_equal(x[b], qr(mats[b])), b   # the batched kernels do each lane as the single call does
+    twin = mats.copy()
+    twin[1][:, 5] = twin[1][:, 2]                      # two equal columns
+    for bad in (twin, np.concatenate([mats[:2], np.zeros((1, d, k))])):
+        lane = 1 if bad is twin else 2
+        st = ws.sketch_generate("rand", omega=bad)
+        x, y = ws.download(BUF_X), ws.download(BUF_Y)
+        assert [int(s) for s in st] == [sk.QR_RANK_DEFICIENT if b == lane else 0 for b in range(lanes)]
+        assert np.array_equal(x[lane], bad[lane]) and np.all(np.isfinite(y))
+        for b in set(range(lanes)) - {lane}:
+            assert np.array_equal(x[b], qr(mats[b]))
+            assert maxdiff(y[b], targets[b] @ x[b]) < TOL
+    with pytest.raises(RankDeficientSketch):
+        qr(twin[1])
+    ws.close()
+
+
+def test_sketch_entries_refuse_what_they_cannot_do():
+    from aqc_research_amd import ParametricCircuit, TrotterAnsatz
+    from aqc_research_amd.engine import HipContext, Workspace, qr
+    from aqc_research_amd.model_sp_lhs.trotter.trotter import make_trotter_like_circuit
+
+    circ = ParametricCircuit(3, "cz", orc.spin_blocks(3, 6))
+    u = _unitary(np.random.default_rng(0), 8)
+    for ncols, word in ((1, "state-vector"), (8, "square")):
+        ws = Workspace(HipContext.of(circ), batch=1, ncols=ncols)
+        with pytest.raises(RuntimeError, match=word):
+            ws.sketch_target(u)
+        ws.close()
+    ws = Workspace(HipContext.of(circ), batch=1, ncols=2)
+    with pytest.raises(RuntimeError, match="aqc_ws_sketch_target"):
+        ws.sketch_generate("alt", alt_idx=[[0, 1]])
+    ws.sketch_target(u)
+    with pytest.raises(RuntimeError, match="out of range"):
+        ws.sketch_generate("alt", alt_idx=[[0, 8]])
+    with pytest.raises(RuntimeError, match="column indices"):
+        ws.sketch_generate("alt")
+    ws.close()
+    circ7 = ParametricCircuit(8, "cz", orc.spin_blocks(8, 8))
+    ws = Workspace(HipContext.of(circ7), batch=1, ncols=128)
+    with pytest.raises(RuntimeError, match="at most 64"):
+        ws.sketch_target(np.eye(256, dtype=complex))
+    ws.close()
+    trot = TrotterAnsatz(4, make_trotter_like_circuit(4, 1), False)
+    ws = Workspace(HipContext.of(trot), batch=1, ncols=2)
+    with pytest.raises(RuntimeError, match="Trotter"):
+        ws.sketch_target(np.eye(16, dtype=complex))
+    ws.close()
+    with pytest.raises(RuntimeError, match="power of two"):
+        qr(np.ones((8, 3), dtype=complex))
+
+
+# ---- generators -----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n,k", [(3, 2), (5, 8), (6, 16)])
+@pytest.mark.parametrize("kind,source", [("alt", "host"), ("rand", "device"), ("rand", "host"), ("eigen", "device"), ("eigen", "host")])
+def test_generate_matches_the_numpy_statement(n, k, kind, source):
+    from aqc_research_amd.engine import BUF_X, BUF_Y, BUF_Z
+
+    lanes, seed, it = 2, 77, 3
+    circ, targets, thetas, ws, rng = _problem(n, "cz", 2 * n + 2, k, lanes, 10 * n + k)
+    d = 1 << n
+    code = {"rand": sk.SKETCH_RAND, "alt": sk.SKETCH_ALT, "eigen": sk.SKETCH_EIGEN}[kind]
+    ws.set_thetas(thetas)
+    idx = om = None
+    if kind == "alt":
+        idx = np.stack([rng.permutation(d)[:k] for _ in range(lanes)])
+    elif source == "host":
+        om = _rand_c(rng, lanes, d, k) if kind == "eigen" else rng.random((lanes, d, k)) + 1j * rng.random((lanes, d, k))
+    st = ws.sketch_generate(kind, seed=seed, iteration=it, alt_idx=idx, omega=om)
+    assert not st.any()
+    x, y = ws.download(BUF_X), ws.download(BUF_Y)
+    ws.apply(True, BUF_Y, BUF_Z)
+    trace = ws.vdot(BUF_X, BUF_Z)
+    ws.grad(None, True)
+    cg = ws.get_grads()
+    for b in range(lanes):
+        assert maxdiff(np.conj(x[b].T) @ x[b], np.eye(k)) < 1e-12
+        assert maxdiff(y[b], targets[b] @ x[b]) < TOL
+        om_b = None if kind == "alt" else (om[b] if om is not None else sk.omega(code, seed, it, b, d, k))
+        x_ref, y_ref = sk.generate(code, targets[b], k, om=om_b, idx=None if idx is None else idx[b],
+                                   vh_mul=lambda m, b=b: orc.v_dagger_mul_mat(circ, thetas[b], m))
+        f_ref, g_ref = orc.sketching_objective_and_gradient(circ, thetas[b], x_ref, y_ref)
+        f, g = 1 - trace[b].real / k, -cg[b].real / k
+        print(f"{kind}/{source} n={n} k={k} lane {b}: |f - f_ref| = {abs(f - f_ref):.2e}, |g - g_ref| = {maxdiff(g, g_ref):.2e}")
+        assert abs(f - f_ref) < 1e-9 and maxdiff(g, g_ref) < 1e-9
+    ws.close()
+
+
+def test_device_draws_equal_the_numpy_philox_call():
+    from aqc_research_amd.engine import BUF_X
+
+    n, k, lanes, seed, it = 5, 8, 2, 2024, 11
+    circ, targets, thetas, ws, rng = _problem(n, "cz", 12, k, lanes, 3)
+    d = 1 << n
+    ws.sketch_draw("rand", seed=seed, iteration=it, buf=BUF_X)
+    got = ws.download(BUF_X)
+    for b in range(lanes):
+        assert np.array_equal(got[b], sk.omega(sk.SKETCH_RAND, seed, it, b, d, k))        # bit for bit
+    ws.sketch_draw("eigen", seed=seed, iteration=it, buf=BUF_X)
+    got = ws.download(BUF_X)
+    worst = 0.0
+    for b in range(lanes):
+        ref = sk.omega(sk.SKETCH_EIGEN, seed, it, b, d, k)
+        for part in (np.real, np.imag):
+            worst = max(worst, float(np.max(np.abs(part(got[b]) - part(ref)) / np.abs(part(ref)))))
+            np.testing.assert_allclose(part(got[b]), part(ref), rtol=1e-12, atol=0)      # libm against the device's log / cos
+    print(f"Box-Muller normals: largest relative difference from NumPy {worst:.2e}")
+    ws.close()
+
+
+# ---- the ADAM run ---------------------------------------------------------------------------------------------------------
+
+ADAM_CASES = {"n3": (3, "cz", 6, 2), "n5": (5, "cx", 12, 8)}
+NITER, LR = 6, 0.1
+
+
+@pytest.fixture(scope="module", params=sorted(ADAM_CASES))
+def adam_case(request):
+    """The problem, the alt index sequence, the device run of 6 iterations in one call, and the CPU walk of optimizer._adam on the
+    oracle's objective under the same sketches -- computed once, read by the tests below."""
+    n, ent, depth, k = ADAM_CASES[request.param]
+    lanes = 2
+    circ, targets, thetas, ws, rng = _problem(n, ent, depth, k, lanes, 40 + n)
+    d = 1 << n
+    idx = np.stack([np.stack([rng.permutation(d)[:k] for _ in range(lanes)]) for _ in range(NITER + 1)]).astype(np.int32)
+    dev = ws.sketch_adam("alt", thetas, NITER, LR, alt_idx=idx)
+    ws.close()
+    ref = []
+    for b in range(lanes):
+        def fun_grad(x, s, b=b):
+            xm, ym = sk.generate(sk.SKETCH_ALT, targets[b], k, idx=idx[s - 1, b])
+            return orc.sketching_objective_and_gradient(circ, x, xm, ym)
+        ref.append(sk.adam_walk(fun_grad, thetas[b], NITER, LR))
+    return {"circ": circ, "targets": targets, "thetas": thetas, "k": k, "idx": idx, "dev": dev, "ref": ref, "lanes": lanes}
+
+
+def test_adam_run_equals_the_cpu_walk(adam_case):
+    dev = adam_case["dev"]
+    assert not dev["status"].any()
+    for b, (x_ref, prof_ref, nit_ref, pts) in enumerate(adam_case["ref"]):
+        assert nit_ref == NITER and int(dev["nit"][b]) == NITER
+        per_iter = np.abs(dev["profile"][b] - prof_ref)
+        print(f"lane {b}: |profile - ref| per evaluation {np.array2string(per_iter, precision=2)}, |x - x_ref| = {maxdiff(dev['x'][b], x_ref):.2e}")
+        assert per_iter.max() < 1e-9 and maxdiff(dev["x"][b], x_ref) < 1e-9
+        assert dev["cost"][b] == dev["profile"][b, NITER]
+        best = int(np.argmin(dev["profile"][b]))
+        assert dev["best_f"][b] == dev["profile"][b, best]
+        assert maxdiff(dev["best_x"][b], pts[best]) < 1e-9
+
+
+def test_adam_chunks_continue_bit_for_bit(adam_case):
+    from aqc_research_amd.engine import HipContext, Workspace
+
+    c = adam_case
+    ws = Workspace(HipContext.of(c["circ"]), batch=c["lanes"], ncols=c["k"])
+    ws.sketch_target(c["targets"])
+    first = ws.sketch_adam("alt", c["thetas"], 3, LR, alt_idx=c["idx"][:4])
+    second = ws.sketch_adam("alt", None, 3, LR, iter0=3, reset=0, alt_idx=c["idx"][3:])
+    ws.close()
+    whole = c["dev"]
+    assert np.array_equal(first["profile"], whole["profile"][:, :4]) and np.array_equal(second["profile"], whole["profile"][:, 3:])
+    for key in ("x", "best_f", "best_x"):
+        assert np.array_equal(second[key], whole[key]), key
+    assert [int(v) for v in second["nit"]] == [3] * c["lanes"]
+
+
+def test_adam_tolerance_flag_freezes_the_lane(adam_case):
+    from aqc_research_amd.engine import HipContext, Workspace
+
+    c = adam_case
+    ws = Workspace(HipContext.of(c["circ"]), batch=c["lanes"], ncols=c["k"])
+    ws.sketch_target(c["targets"])
+    tiny = 1e-12                                # first step: lr * sign(g) per parameter, norm lr sqrt(T) << tol = 1e-6
+    one = ws.sketch_adam("alt", c["thetas"], 1, tiny, alt_idx=c["idx"][:2])
+    four = ws.sketch_adam("alt", c["thetas"], 4, tiny, reset=1, alt_idx=c["idx"][:5])
+    ws.close()
+    assert [int(v) for v in four["nit"]] == [1] * c["lanes"]
+    assert np.array_equal(four["x"], one["x"]) and not np.array_equal(four["x"], c["thetas"])
+    assert np.array_equal(four["cost"], four["profile"][:, 1]) and np.array_equal(four["profile"][:, :2], one["profile"])
+
+
+# ---- the driver -----------------------------------------------------------------------------------------------------------
+
+def test_stochastic_aqc_restarts_and_accounts_like_its_policy():
+    from aqc_research_amd import ParametricCircuit
+    from aqc_research_amd.model_sketching.aqc_sketching import ChunkPolicy, stochastic_aqc
+    from aqc_research_amd.optimizer import NotImproveStopper
+
+    n, k, maxiter, lr0 = 3, 2, 60, 0.1
+    rng = np.random.default_rng(9)
+    circ = ParametricCircuit(n, "cz", orc.spin_blocks(n, 6))
+    target = _unitary(rng, 1 << n)
+    th0 = np.stack([orc.rand_thetas(circ.num_thetas, rng) for _ in range(2)])
+    np.random.seed(12)
+    res = stochastic_aqc(circ, target, "alt", k, th0, maxiter=maxiter, learn_rate=lr0, chunk=8, stop_stagnant=NotImproveStopper(num_iters=2))
+    assert len(res) == 2
+    for r in res:
+        assert r["exit_status"] in ("normal", "early", "timeout", "premature")
+        assert 1 <= r["corrections"] <= 5, "the stopper was set to fire"
+        assert r["learn_rate"] == lr0 * 0.5 ** min(r["corrections"], 4)
+        replay = ChunkPolicy(maxiter, lr0, NotImproveStopper(num_iters=2))
+        for chunk in r["stats"]["chunks"]:
+            assert not replay.finished
+            replay.feed(chunk)
+        assert (replay.evals_total, replay.corrections, replay.learn_rate) == (r["num_iters"], r["corrections"], r["learn_rate"])
+        assert replay.exit_status in (r["exit_status"], None)
+        assert set(r) >= {"cost", "num_fun_ev", "num_grad_ev", "num_iters", "thetas", "entangler", "blocks", "exit_status"}
+        assert np.isfinite(r["cost"]) and r["thetas"].shape == (circ.num_thetas,)
+    one = stochastic_aqc(circ, target, "rand", k, th0[0], maxiter=5, learn_rate=lr0, seed=3)
+    assert isinstance(one, dict) and one["exit_status"] == "normal" and one["num_iters"] == 5
+
+
+def test_stochastic_aqc_names_the_rank_deficient_lane():
+    from aqc_research_amd import ParametricCircuit
+    from aqc_research_amd.engine import RankDeficientSketch
+    from aqc_research_amd.model_sketching.aqc_sketching import stochastic_aqc
+
+    n, k = 3, 2
+    rng = np.random.default_rng(21)
+    circ = ParametricCircuit(n, "cz", orc.spin_blocks(n, 6))
+    th0 = np.stack([orc.rand_thetas(circ.num_thetas, rng) for _ in range(2)])
+    v0 = orc.v_mul_mat(circ, th0[0], np.eye(1 << n, dtype=np.complex128))      # lane 0: the target IS V(theta_0)
+    targets = np.stack([v0, _unitary(rng, 1 << n)])
+    with pytest.raises(RankDeficientSketch) as err:
+        stochastic_aqc(circ, targets, "eigen", k, th0, maxiter=4, learn_rate=0.1, seed=1)
+    assert err.value.lanes == [0] and "lane(s) [0]" in str(err.value)
