@@ -1,7 +1,7 @@
 // Internal declarations shared by the translation units behind the C ABI (include/aqc_hip.h):
 //   aqc_api.cpp        contexts, workspaces, buffers, thetas, small results, one-shot entry points
 //   aqc_ws_plan.cpp    lowering of stage plans to device tables (micro-ops, sub-stage slot tables), mirrored V^H plans
-//   aqc_ws_sweep.cpp   V / V^H launches, the w/z sweep (dense and sparse-lhs routes), aqc_ws_eval
+//   aqc_ws_sweep.cpp   V / V^H launches, the w/z sweep (dense and sparse-lhs routes), the route of an evaluation (eval_route), aqc_ws_eval
 //   aqc_ws_optim.cpp   device-resident L-BFGS and the one-call surrogate evaluation
 //   aqc_ws_extra.cpp   zgemm, gate-level building blocks, coordinate descent, MPS helpers
 //   aqc_ws_sketch.cpp  sketched AQC: resident targets, sketching-vector generators, device-resident ADAM, aqc_qr
@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -76,6 +77,31 @@ struct ListKey {
     int buf = kUnknown;
     unsigned long long supp = 0, gather = 0;
     bool operator==(const ListKey& o) const { return buf != kUnknown && buf == o.buf && supp == o.supp && gather == o.gather; }
+};
+
+// Route of one evaluation.  The caller states what the call does; eval_route (aqc_ws_sweep.cpp) alone decides how, before anything
+// is enqueued, and runs the sparse route's allocations and one-off clears (a captured graph must not hold them).  enqueue_vdag,
+// enqueue_gather, the sweep and route_state_after act on the value and ask nothing again.
+struct EvalRoute {
+    // what the call does (the caller's part)
+    int x_buf = AQC_BUF_X;         // the lhs buffer of the sweep
+    bool vdag = false;             // V^H from Y into Z
+    bool new_thetas = false;       // thetas arrive with the call
+    bool gather = false;           // the registered gather from Z ...
+    bool gather_rides = false;     // ... inside the gradient walk instead of a launch of its own (aqc_ws_eval)
+    bool grads = false;            // the sweep from x_buf
+    // Surrogate objective: between V^H and the sweep a kernel of the call picks the lhs state among the gather indices.  The gather
+    // set alone names V^H's tiles, and the support of x_buf counts as changed at that point (route_state_after restates it).
+    bool support_in_gather_set = false;
+    // how (eval_route's part)
+    bool sparse = false;           // the sweep's first stage over the tiles of the lhs state only (head of aqc_ws_sweep.cpp)
+    enum VdagKind { kStages, kRestricted, kProjected } vdag_kind = kStages;   // all stages / last stage where it is read / by projection
+    bool skip_zero_w = false;      // AQC_SKIP_ZERO_W
+    int key_bits() const {         // what a captured graph's key must tell apart
+        static_assert(AQC_NUM_BUFS <= 8, "x_buf takes the low three bits");
+        return x_buf | (vdag ? 8 : 0) | (gather ? 16 : 0) | (gather_rides ? 32 : 0) | (grads ? 64 : 0) | (sparse ? 128 : 0) |
+               (support_in_gather_set ? 256 : 0) | (skip_zero_w ? 512 : 0) | ((int)vdag_kind << 10);
+    }
 };
 
 // Projected route of the sparse-lhs sweep (aqc_ws_project.cpp): the dense stages run on a virtual register
@@ -204,7 +230,6 @@ struct aqc_ws {
     hipEvent_t ev_mps_fork = nullptr, ev_mps_join = nullptr;
     bool copy_pending = false;                // the producers of the next evaluation wait for ev_copied before they overwrite the results
     const double* theta_host = nullptr;      // aqc_ws_eval: pinned thetas the next U build reads directly (and copies to d_thetas)
-    bool gather_rides = false;               // aqc_ws_eval: the next gradient walk also performs the registered gather (see there)
     // mirrored V^H plan, its checkpoint, the sparse-lhs sweep (aqc_ws_sweep.cpp)
     bool inv_mirrored = false;     // inv = the sweep plan walked backwards: V^H into Z leaves the state before its last stage in ZW ...
     bool ckpt_valid = false;       // ... and ZW holds it for the thetas in use and the present contents of Z
@@ -285,6 +310,27 @@ struct ProfScope {  // brackets one launch with events when profiling is on
     }
 };
 
+// ---- what the two calls that replay graphs (aqc_ws_eval, aqc_ws_surrogate_eval) share before they enqueue ----
+// result copies of an earlier aqc_ws_results_async: the call reuses the pinned staging buffer and may replay a graph
+inline int wait_result_copies(aqc_ws* ws) {
+    if (!ws->copy_pending) return 0;
+    HIP_OK(hipStreamSynchronize(ws->copy_stream));
+    ws->copy_pending = false;
+    return 0;
+}
+// Small results skip the device-to-host copy nodes: the producing kernels write a second copy straight into pinned memory (null: no
+// second copy).  Cleared on every exit, the error paths of enqueue() too: no stale pinned thetas in the next call.
+struct MirrorScope {
+    aqc_ws* w;
+    MirrorScope(aqc_ws* w_, double* grads, double* small) : w(w_) { w->mirror_grads = grads; w->mirror_small = small; }
+    ~MirrorScope() { w->mirror_grads = nullptr; w->mirror_small = nullptr; w->theta_host = nullptr; }
+};
+// matrix-core path, small batch: no copy node for the thetas -- the U builder (first kernel of V^H or of the sweep) reads the pinned
+// thetas over the bus and stores them to HBM for the gradient walk
+inline bool direct_thetas(const aqc_ws* ws, bool zero_copy) {
+    return zero_copy && ws->fwd.v3 && ws->inv.v3 && ws->sweep.v3 && !ws->need_coef;
+}
+
 // aqc_api.cpp
 int check_buf(const aqc_ws* ws, int buf);
 int check_block_range(const aqc_ws* ws, int block_from, int block_to);
@@ -307,18 +353,15 @@ ListKey key_of(const aqc_ws* ws, int lhs_buf, bool gather);   // lhs_buf: ListKe
 bool built_for(const aqc_ws* ws, const ListKey& slot, const ListKey& key);   // the list `slot` names is built for `key`
 void record_key(const aqc_ws* ws, ListKey& slot, const ListKey& key);         // ... it is now
 void replay_state_after(aqc_ws* ws);          // forgets the lists a graph replay has rebuilt on the device behind the host's back
-int run_graph(aqc_ws* ws, const std::vector<long long>& key, const std::function<int()>& enqueue, const std::function<void()>& state_after);
-bool vdag_route_restricted(const aqc_ws* ws, int x_buf);
-int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set = false);
-void vdag_restricted_state_after(aqc_ws* ws, int x_buf);
+int eval_route(aqc_ws* ws, EvalRoute& route);             // completes the route (see EvalRoute)
+int enqueue_vdag(aqc_ws* ws, const EvalRoute& route);     // Y -> Z by the route's kind of V^H
+int enqueue_gather(aqc_ws* ws, const EvalRoute& route);   // the registered gather of that Z (a launch of its own)
+void route_state_after(aqc_ws* ws, const EvalRoute& route);   // the record those and the sweep leave, restated after a graph replay
+// enqueue() with new thetas, captured once per (call's own words, route, addresses the nodes hold) and replayed
+int run_graph(aqc_ws* ws, const EvalRoute& route, std::initializer_list<long long> call, const std::function<int()>& enqueue);
 void vdag_projected_state_after(aqc_ws* ws, int x_buf);
-int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int front_layer, bool support_in_gather_set);
-bool sweep_route_sparse(const aqc_ws* ws, int x_buf, bool will_vdag);
-bool sweep_skips_zero_w(const aqc_ws* ws, int x_buf);
-int sweep_r_only_sub(const aqc_ws* ws);   // the lhs state is a combination of basis states the device knows: zero groups of w are skipped
-int sweep_sparse_prepare(aqc_ws* ws);
-void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf);
-void sweep_state_after(aqc_ws* ws, bool sparse);
+int grad_from_impl(aqc_ws* ws, const EvalRoute& route, int block_from, int block_to, int front_layer);   // the sweep and the gradient walk
+int sweep_r_only_sub(const aqc_ws* ws);
 int ensure_umat(aqc_ws* ws, DevPlan& p);
 int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf);
 // descriptions of a matrix-core stage launch; the buffers and what is particular to the launch are the caller's

@@ -13,9 +13,8 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
                  int block_from, int block_to, int front_layer, double* x_out, double* f_out, double* fidelity_out, int64_t* nit_out,
                  int64_t* nfev_out, double* weight_out, int64_t* max_no_out) {
     if (!ws || !x0 || !x_out || !f_out) return fail("null argument");
+    if (check_block_range(ws, block_from, block_to)) return 1;
     if (block_from < 0) { block_from = 0; block_to = ws->ctx->prog.num_blocks; }
-    if (ws->ctx->prog.num_blocks > 0 && !(0 <= block_from && block_from < block_to && block_to <= ws->ctx->prog.num_blocks))
-        return fail("invalid block_range [%d, %d)", block_from, block_to);
     if (ws->ncols != 1) return fail("the L-BFGS driver works on state-vector workspaces");
     if (ws->gather_count < 1) return fail("aqc_ws_gather_setup has not been called (flip-state indices, state 0 first)");
     if (memory < 1 || memory > 32 || maxiter < 1 || max_backtracks < 1) return fail("invalid L-BFGS parameters");
@@ -93,14 +92,13 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
     // combined lhs state (lb_prepare) and ONE sweep from it -- no host round trip inside an evaluation.
     auto evaluate = [&](int update, double* f_o, double* g_o, double2* raw_hs, double2* raw_g) -> int {
         if (run_coef(ws, ws->d_thetas_own)) return 1;
-        const bool sparse = sweep_route_sparse(ws, AQC_BUF_X2, true);
-        if (sparse && sweep_sparse_prepare(ws)) return 1;
-        if (sparse && vdag_route_restricted(ws, AQC_BUF_X2)) { if (run_vdag_restricted(ws, AQC_BUF_X2, true)) return 1; }   // V^H where the gather and
-        else if (run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)) return 1;                                                   // the sweep read it
-        if (aqc_ws_gather_launch(ws, AQC_BUF_Z)) return 1;
+        EvalRoute route;   // V^H (where the gather and the sweep read it), the gather, the sweep; the lhs state is picked in between
+        route.x_buf = AQC_BUF_X2; route.vdag = route.new_thetas = route.gather = route.grads = route.support_in_gather_set = true;
+        if (eval_route(ws, route)) return 1;
+        if (enqueue_vdag(ws, route) || enqueue_gather(ws, route)) return 1;
         HIP_OK(lb_prepare(L, ws->d_small, update, f_o, raw_hs, ws->bufs[AQC_BUF_X2], ws->lane_elems, ws->d_index, d_prev, st_));
         lhs_support_changed(ws, AQC_BUF_X2);   // (the leading flip state is chosen on the device: the support may have moved)
-        if (grad_from_impl(ws, AQC_BUF_X2, block_from, block_to, front_layer, true)) return 1;
+        if (grad_from_impl(ws, route, block_from, block_to, front_layer)) return 1;
         HIP_OK(lb_take(L, ws->d_grads, g_o, raw_g, st_));
         ++nfev;
         return 0;
@@ -166,10 +164,7 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     if (update_state < 0 || update_state > 2) return fail("update_state is 0 (none), 1 (hysteresis and weight) or 2 (hysteresis only)");
     if (check_block_range(ws, block_from, block_to)) return 1;
     HIP_OK(hipSetDevice(ws->device));
-    if (ws->copy_pending) {   // as in aqc_ws_eval: the pinned staging buffer is reused
-        HIP_OK(hipStreamSynchronize(ws->copy_stream));
-        ws->copy_pending = false;
-    }
+    if (wait_result_copies(ws)) return 1;
     const Program& prog = ws->ctx->prog;
     const int B = ws->batch, T = prog.num_thetas(), S = ws->gather_count;
     const size_t nth = (size_t)B * T;
@@ -190,13 +185,9 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     // Small problems (single evaluations above all): no copy nodes -- the kernels read the thetas and the objective state from
     // pinned host memory and write the state block and a second copy of the gradient straight back into it (as aqc_ws_eval does)
     const bool zero_copy = sizeof(double2) * (nth + (size_t)B * S) <= 65536;
-    const bool direct_thetas = zero_copy && ws->fwd.v3 && ws->inv.v3 && ws->sweep.v3 && !ws->need_coef;
+    const bool direct = direct_thetas(ws, zero_copy);
     double* dd = zero_copy ? hd : static_cast<double*>(ws->d_sur);
-    struct Scope {
-        aqc_ws* w;
-        Scope(aqc_ws* w_, double* g) : w(w_) { w->mirror_grads = g; w->mirror_small = nullptr; }
-        ~Scope() { w->mirror_grads = nullptr; w->mirror_small = nullptr; w->theta_host = nullptr; w->gather_rides = false; }
-    } scope(ws, zero_copy ? ws->h_pin + ws->pin_thetas : nullptr);
+    MirrorScope mirror_scope(ws, zero_copy ? ws->h_pin + ws->pin_thetas : nullptr, nullptr);
     LbState L;
     memset(&L, 0, sizeof L);
     L.B = B; L.T = T; L.S = S;
@@ -218,9 +209,9 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
         HIP_OK(hipMemsetAsync(ws->d_combo_prev[AQC_BUF_X2], 0xff, sizeof(long long) * 2 * B, st));   // -1: nothing to clear
         lhs_support_changed(ws, AQC_BUF_X2);
     }
-    const bool sparse = sweep_route_sparse(ws, AQC_BUF_X2, true);   // (decided here: part of the captured graph's key)
-    if (sparse && sweep_sparse_prepare(ws)) return 1;
-    const bool lazy = sparse && vdag_route_restricted(ws, AQC_BUF_X2);
+    EvalRoute route;   // as the evaluate step of aqc_ws_lbfgs
+    route.x_buf = AQC_BUF_X2; route.vdag = route.new_thetas = route.gather = route.grads = route.support_in_gather_set = true;
+    if (eval_route(ws, route)) return 1;
     const bool real_only = !zero_copy && !grads_out;
     if (real_only && ws->sur_real_cap < nth) {
         HIP_OK(hipStreamSynchronize(st));
@@ -233,11 +224,10 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
             HIP_OK(hipMemcpyAsync(L.weight, hd + 2 * (size_t)B, sizeof(double) * B, hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(L.max_no, h_max, sizeof(int) * B, hipMemcpyHostToDevice, st));
         }
-        if (!direct_thetas) HIP_OK(hipMemcpyAsync(ws->d_thetas_own, pin_th, sizeof(double) * nth, hipMemcpyHostToDevice, st));
+        if (!direct) HIP_OK(hipMemcpyAsync(ws->d_thetas_own, pin_th, sizeof(double) * nth, hipMemcpyHostToDevice, st));
         if (run_coef(ws, ws->d_thetas_own)) return 1;
-        ws->theta_host = direct_thetas ? pin_th : nullptr;   // the U builder reads the pinned thetas and stores them to HBM
-        if (lazy ? run_vdag_restricted(ws, AQC_BUF_X2, true) : run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)) return 1;
-        if (aqc_ws_gather_launch(ws, AQC_BUF_Z)) return 1;
+        ws->theta_host = direct ? pin_th : nullptr;   // the U builder reads the pinned thetas and stores them to HBM
+        if (enqueue_vdag(ws, route) || enqueue_gather(ws, route)) return 1;
         {
             ProfScope ps(ws, AQC_K_MISC);
             HIP_OK(lb_prepare(L, ws->d_small, update_state, d_f, d_hs, ws->bufs[AQC_BUF_X2], ws->lane_elems, ws->d_index,
@@ -245,7 +235,7 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
             lhs_support_changed(ws, AQC_BUF_X2);
         }
         // (update_state == 0 leaves weight / max_no / fidelity as they came in; fidelity is only written by an update)
-        if (grad_from_impl(ws, AQC_BUF_X2, block_from, block_to, front_layer, true)) return 1;
+        if (grad_from_impl(ws, route, block_from, block_to, front_layer)) return 1;
         ws->theta_host = nullptr;
         if (!zero_copy) {
             if (real_only) {   // the surrogate's gradient is the real part: half the bytes over the bus, no pass over them on the host
@@ -260,18 +250,9 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     };
     static const bool graphs_on = env_int("AQC_GRAPH", 1) != 0;
     if (graphs_on && !ws->profile) {   // the launch sequence is replayed as a graph, as in aqc_ws_eval
-        const std::vector<long long> key = {1000 + update_state + (zero_copy ? 10 : 0) + (real_only ? 20 : 0), block_from, block_to, front_layer,
-                                            (long long)S, (long long)(size_t)ws->d_sur_real,
-                                            (long long)(size_t)ws->d_sur, (long long)(size_t)ws->h_sur, (long long)(size_t)ws->h_pin,
-                                            (long long)(size_t)ws->d_small, (long long)(size_t)ws->d_combo_prev[AQC_BUF_X2], (sparse ? 1 : 0) + (lazy ? 2 : 0) + (sweep_skips_zero_w(ws, AQC_BUF_X2) ? 4 : 0),
-                                            (long long)(size_t)ws->d_vd_items};
-        auto state_after = [&]() {
-            thetas_changed(ws, ws->d_thetas_own);
-            if (lazy) vdag_restricted_state_after(ws, AQC_BUF_X2); else apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
-            lhs_support_changed(ws, AQC_BUF_X2);
-            sweep_state_after(ws, sparse);
-        };
-        if (run_graph(ws, key, enqueue, state_after)) return 1;
+        const long long tag = 1000 + update_state + (zero_copy ? 10 : 0) + (real_only ? 20 : 0);   // (1000: no key of aqc_ws_eval)
+        if (run_graph(ws, route, {tag, block_from, block_to, front_layer, (long long)S, (long long)(size_t)ws->d_sur_real, (long long)(size_t)ws->d_sur,
+                                  (long long)(size_t)ws->h_sur}, enqueue)) return 1;
     } else if (enqueue()) {
         return 1;
     }

@@ -336,7 +336,7 @@ static int enqueue_couple(aqc_ws* ws, int k, const Stage3Args* real, const Virtu
     return 0;
 }
 
-int run_vdag_projected(aqc_ws* ws, int x_buf) {   // the caller has asked vdag_route_projected, sweep_sparse_prepare
+int run_vdag_projected(aqc_ws* ws, int x_buf) {   // for a route eval_route has decided (vdag_route_projected) and prepared
     ProjRoute& pr = ws->proj;
     const DevPlan& p = ws->sweep;
     const DevPlan& iv = ws->inv;

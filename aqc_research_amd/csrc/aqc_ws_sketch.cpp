@@ -241,7 +241,7 @@ int aqc_ws_sketch_adam(aqc_ws* ws, int kind, const double* x0, int niter, const 
         if (sk_generate(ws, kind, seed, (unsigned long long)iter0 + e + 1, kind == AQC_SKETCH_ALT ? ws->sk.idx + e * B * k : nullptr, nullptr)) return 1;
         if (run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)) return 1;                 // V^H Y       (sk_core.py:191)
         if (aqc_ws_vdot_launch(ws, AQC_BUF_X, AQC_BUF_Z)) return 1;              // <X|V^H Y>   (:192)
-        if (grad_from_impl(ws, AQC_BUF_X, -1, 0, 1, false)) return 1;            // the sweep   (:193)
+        if (aqc_ws_grad_from(ws, AQC_BUF_X, -1, 0, 1)) return 1;                 // the sweep   (:193)
         s.trace = ws->d_vdot_out;
         ProfScope ps(ws, AQC_K_MISC);
         HIP_OK(launch_sk_adam(s, (int)e, e + 1 < sets ? 1 : 0, st));

@@ -207,11 +207,22 @@ void stage3_sweep_fields(Stage3Args& a, const DevPlan& p, int nparts, int chunk)
     if (a.stage.nsubs > 0) stage3_first_offsets(a, p.h_subs3[a.stage.sub_begin]);
 }
 
+// families 1 and 2: stage s of a plan; the buffers and the sweep's own fields are the caller's
+static StageArgs stage_args(const aqc_ws* ws, const DevPlan& p, size_t s) {
+    const Program& prog = ws->ctx->prog;
+    StageArgs a;
+    memset(&a, 0, sizeof a);
+    a.stage = p.d_stages + s; a.ops = p.d_ops; a.subs = p.d_subs; a.mops = p.d_mops;
+    a.coef = ws->d_coef; a.ncoef = prog.n + prog.num_blocks + 1;
+    a.lane_stride = ws->lane_elems;
+    return a;
+}
+
 // V^H into Z by the mirrored plan keeps the state before its last stage in ZW (see the head of this file)
 static bool keeps_checkpoint(const aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
     return inverse && ws->inv_mirrored && ws->inv.v3 && dst_buf == AQC_BUF_Z && src_buf != AQC_BUF_ZW && ws->inv.h_stages.size() >= 2;
 }
-void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {   // host-side state a V / V^H leaves (also after a graph replay)
+static void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {   // host-side state a V / V^H leaves (also after a graph replay)
     umat_state_after(ws, inverse ? ws->inv : ws->fwd);
     touch_buf(ws, dst_buf);
     if (keeps_checkpoint(ws, inverse, src_buf, dst_buf)) { touch_buf(ws, AQC_BUF_ZW); ws->ckpt_valid = true; }
@@ -246,17 +257,9 @@ int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
         return 0;
     }
     for (size_t s = 0; s < p.h_stages.size(); ++s) {
-        StageArgs a;
-        memset(&a, 0, sizeof a);
-        a.stage = p.d_stages + s;
-        a.ops = p.d_ops;
-        a.subs = p.d_subs;
-        a.mops = p.d_mops;
-        a.coef = ws->d_coef;
-        a.ncoef = prog.n + prog.num_blocks + 1;
+        StageArgs a = stage_args(ws, p, s);
         a.in0 = s == 0 ? ws->bufs[src_buf] : ws->bufs[dst_buf];
         a.out0 = ws->bufs[dst_buf];
-        a.lane_stride = ws->lane_elems;
         a.final_stage = (s + 1 == p.h_stages.size()) ? 1 : 0;
         ProfScope ps(ws, AQC_K_APPLY);
         if (p.v2) HIP_OK(launch_apply2(prog.entangler, p.ntiles, ws->batch, p.k, ws->stream, a));
@@ -272,8 +275,8 @@ int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
 // last stage of the mirrored V^H therefore runs over those tiles only (at the headline 5 of 16 per lane: the tile of |0> and
 // of its four flips on qubits 12..15); everything before it is needed in full (it is the second sweep stage's z).  Z is
 // completed on demand -- the checkpoint in ZW is all it takes -- as long as the thetas have not changed.
-bool vdag_route_restricted(const aqc_ws* ws, int x_buf) {
-    return ws->lazy_z_enabled && sweep_route_sparse(ws, x_buf, true) && 2 + ws->gather_count <= kMaxTileCands;
+static bool vdag_route_restricted(const aqc_ws* ws) {   // asked of a sparse route whose V^H is part of the call (eval_route)
+    return ws->lazy_z_enabled && 2 + ws->gather_count <= kMaxTileCands;
 }
 static Stage3Args last_vdag_stage(aqc_ws* ws) {
     DevPlan& p = ws->inv;
@@ -282,9 +285,22 @@ static Stage3Args last_vdag_stage(aqc_ws* ws) {
     a.out0 = ws->bufs[AQC_BUF_Z];
     return a;
 }
+static void vdag_restricted_state_after(aqc_ws* ws, int x_buf) {
+    apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
+    ws->z_full = false;
+    ws->z_key = key_of(ws, x_buf, true);   // (not a list a replay rebuilds: a replay states it again)
+}
+// the objective's V^H by projection (run_vdag_projected, aqc_ws_project.cpp)
+void vdag_projected_state_after(aqc_ws* ws, int x_buf) {
+    vdag_restricted_state_after(ws, x_buf);
+    ws->z_key.gather = 0;       // Z covers the lhs tiles, not the gather set: a later gather completes it first
+    ws->ckpt_valid = false;     // ZW holds the lhs tiles of the checkpoint only
+    ws->z_from_y = true;
+    ws->proj_y0_ready = true;   // the virtual z holds Y_0 for the sweep of the same call
+}
 // support_in_gather_set: the lhs state is picked among the registered gather indices (surrogate objective: |state_0> and the
 // leading flip state) -- the gather set alone names the tiles, and the list only changes when that set does
-int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set) {   // Y -> Z; the caller has asked vdag_route_restricted and sweep_sparse_prepare
+static int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set) {   // Y -> Z, for a route eval_route has decided and prepared
     DevPlan& p = ws->inv;
     if (ensure_umat(ws, p)) return 1;
     const size_t m = p.h_stages.size();
@@ -317,19 +333,6 @@ int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set) {   /
     vdag_restricted_state_after(ws, x_buf);
     return 0;
 }
-void vdag_restricted_state_after(aqc_ws* ws, int x_buf) {
-    apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
-    ws->z_full = false;
-    ws->z_key = key_of(ws, x_buf, true);   // (not a list a replay rebuilds: a replay states it again)
-}
-// the objective's V^H by projection (run_vdag_projected, aqc_ws_project.cpp)
-void vdag_projected_state_after(aqc_ws* ws, int x_buf) {
-    vdag_restricted_state_after(ws, x_buf);
-    ws->z_key.gather = 0;       // Z covers the lhs tiles, not the gather set: a later gather completes it first
-    ws->ckpt_valid = false;     // ZW holds the lhs tiles of the checkpoint only
-    ws->z_from_y = true;
-    ws->proj_y0_ready = true;   // the virtual z holds Y_0 for the sweep of the same call
-}
 static int ensure_z_full(aqc_ws* ws, bool reader) {
     if (ws->z_full) return 0;
     if (ws->capturing) return fail("BUF_Z is partial inside a captured graph");
@@ -354,37 +357,9 @@ void drop_graphs(aqc_ws* ws) {
     ws->graphs.clear();
 }
 
-// A one-call evaluation as a HIP graph: enqueue() captured once per key (16 graphs, then all are dropped) and replayed.  A replay
-// enqueues nothing on the host: state_after() restates, by the same transitions, the record the enqueued calls would have left.
-int run_graph(aqc_ws* ws, const std::vector<long long>& key, const std::function<int()>& enqueue, const std::function<void()>& state_after) {
-    auto it = ws->graphs.find(key);
-    if (it == ws->graphs.end()) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        HIP_OK(hipStreamSynchronize(ws->stream));
-        HIP_OK(hipStreamBeginCapture(ws->stream, hipStreamCaptureModeThreadLocal));
-        ws->capturing = true;
-        const int rc = enqueue();
-        ws->capturing = false;
-        const hipError_t e = hipStreamEndCapture(ws->stream, &graph);
-        if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return 1; }
-        if (e != hipSuccess || !graph) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
-        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ei != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(ei));
-        if (ws->graphs.size() >= 16) drop_graphs(ws);
-        it = ws->graphs.emplace(key, exec).first;
-    }
-    state_after();
-    replay_state_after(ws);
-    HIP_OK(hipGraphLaunch(it->second, ws->stream));
-    return 0;
-}
-
 // ---- the sparse route --------------------------------------------------------------------------------------------
-// Route of the next sweep from x_buf.  will_vdag: a V^H from Y into Z precedes it inside the same call (one-call
-// evaluations decide before they enqueue anything: the decision is part of the key of their captured graph).
-bool sweep_route_sparse(const aqc_ws* ws, int x_buf, bool will_vdag) {
+// Route of the next sweep from x_buf.  will_vdag: a V^H from Y into Z precedes it inside the same call.
+static bool sweep_route_sparse(const aqc_ws* ws, int x_buf, bool will_vdag) {
     const DevPlan& p = ws->sweep;
     if (!ws->sparse_enabled || !p.v3 || !ws->inv_mirrored || p.h_stages.size() < 2) return false;
     if (!ws->combo_valid[x_buf] || !ws->d_combo_prev[x_buf]) return false;          // support of the lhs state known on the device
@@ -403,11 +378,11 @@ int sweep_r_only_sub(const aqc_ws* ws) {
     return last.sub_begin + last.nsubs - 1;
 }
 // Inside a stage the same knowledge goes further (any number of stages, either route): see sweep_mfma_kernel<K, false, true>.
-bool sweep_skips_zero_w(const aqc_ws* ws, int x_buf) {
+static bool sweep_skips_zero_w(const aqc_ws* ws, int x_buf) {
     return ws->skipw_enabled && ws->sweep.v3 && ws->combo_valid[x_buf] && ws->d_combo_prev[x_buf] != nullptr;
 }
 // Allocations and one-off clears of the sparse route: everything that must not sit inside a captured graph.
-int sweep_sparse_prepare(aqc_ws* ws) {
+static int sweep_sparse_prepare(aqc_ws* ws) {
     const DevPlan& p = ws->sweep;
     const int B = ws->batch;
     if (!ws->d_sw_items) {
@@ -419,8 +394,10 @@ int sweep_sparse_prepare(aqc_ws* ws) {
         HIP_OK(hipMalloc((void**)&ws->d_sw_prev_tiles, sizeof(int) * 2 * B));
         ws->w_clean = false;
     }
-    if (p.h_stages.size() >= 3 && !ws->w2 && !ws->proj.ok) {   // (the projected route runs the later stages on its own small register)   // stages from the second one on work on their own pair: W stays zero outside the listed
-        HIP_OK(hipMalloc((void**)&ws->w2, sizeof(double2) * (size_t)B * ws->lane_elems));   // tiles, ZW keeps the checkpoint
+    // The second scratch pair: the stages from the second one on work on it, so that W stays zero outside the listed tiles and ZW keeps
+    // the checkpoint.  Plans of two stages have no such stage, and the projected route runs them on its own small register.
+    if (p.h_stages.size() >= 3 && !ws->w2 && !ws->proj.ok) {
+        HIP_OK(hipMalloc((void**)&ws->w2, sizeof(double2) * (size_t)B * ws->lane_elems));
         HIP_OK(hipMalloc((void**)&ws->zw2, sizeof(double2) * (size_t)B * ws->lane_elems));
     }
     const size_t vd_need = (2 + (size_t)ws->gather_count) * B;
@@ -440,13 +417,232 @@ int sweep_sparse_prepare(aqc_ws* ws) {
     }
     return 0;
 }
-void sweep_state_after(aqc_ws* ws, bool sparse) {   // host-side state a sweep leaves (also after a graph replay)
+static void sweep_state_after(aqc_ws* ws, bool sparse) {   // host-side state a sweep leaves (also after a graph replay)
     umat_state_after(ws, ws->sweep);
     ws->proj_y0_ready = false;                 // (consumed by the projected stages)
     if (!sparse) {
         ws->w_clean = false;
         ws->ckpt_valid = false;                // the dense route works in place on (W, ZW)
     }
+}
+
+// ---- the route of an evaluation: one decision, one set of actions (EvalRoute, aqc_ws.h) ------------------------------------------
+int eval_route(aqc_ws* ws, EvalRoute& r) {
+    // new thetas invalidate the checkpoint, a V^H in this call renews it
+    r.sparse = r.grads && (r.vdag || !r.new_thetas) && sweep_route_sparse(ws, r.x_buf, r.vdag);
+    r.skip_zero_w = r.grads && sweep_skips_zero_w(ws, r.x_buf);
+    r.vdag_kind = EvalRoute::kStages;
+    if (r.sparse && sweep_sparse_prepare(ws)) return 1;
+    if (!(r.sparse && r.vdag && vdag_route_restricted(ws))) return 0;
+    // V^H only where this call (gather, sweep) reads it -- and by two passes over y instead of its stages where the lhs state (known to
+    // the host) and the gather set allow, never with a riding gather: the gradient walk gathers from Z, which holds the lhs tiles only
+    const bool projected = !r.gather_rides && !r.support_in_gather_set && vdag_route_projected(ws, r.x_buf);
+    r.vdag_kind = projected ? EvalRoute::kProjected : EvalRoute::kRestricted;
+    return 0;
+}
+int enqueue_vdag(aqc_ws* ws, const EvalRoute& r) {
+    if (r.vdag_kind == EvalRoute::kProjected) return run_vdag_projected(ws, r.x_buf);
+    if (r.vdag_kind == EvalRoute::kRestricted) return run_vdag_restricted(ws, r.x_buf, r.support_in_gather_set);
+    return run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z);
+}
+int enqueue_gather(aqc_ws* ws, const EvalRoute& r) {
+    return r.vdag_kind == EvalRoute::kProjected ? proj_fix_amplitudes(ws, r.x_buf) : aqc_ws_gather_launch(ws, AQC_BUF_Z);
+}
+void route_state_after(aqc_ws* ws, const EvalRoute& r) {
+    if (r.vdag && r.vdag_kind == EvalRoute::kProjected) vdag_projected_state_after(ws, r.x_buf);
+    else if (r.vdag && r.vdag_kind == EvalRoute::kRestricted) vdag_restricted_state_after(ws, r.x_buf);
+    else if (r.vdag) apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
+    if (r.support_in_gather_set) lhs_support_changed(ws, r.x_buf);   // (lb_prepare: the support may have moved)
+    if (r.grads) sweep_state_after(ws, r.sparse);
+}
+// the key of a captured evaluation: the call's own words, the route's, and the addresses its nodes hold (one allocation)
+static std::vector<long long> graph_key(const aqc_ws* ws, const EvalRoute& r, std::initializer_list<long long> call) {
+    std::vector<long long> key;
+    key.reserve(call.size() + 5);
+    key.insert(key.end(), call.begin(), call.end());
+    key.push_back(r.key_bits());
+    for (const void* addr : {(const void*)ws->d_small, (const void*)ws->h_pin, (const void*)ws->d_combo_prev[r.x_buf], (const void*)ws->d_vd_items})
+        key.push_back((long long)(size_t)addr);
+    return key;
+}
+
+// A one-call evaluation with new thetas as a HIP graph: enqueue() captured once per key (16 graphs, then all are dropped) and replayed.
+// A replay enqueues nothing on the host: the record the enqueued calls would have left is restated by the same transitions.
+int run_graph(aqc_ws* ws, const EvalRoute& route, std::initializer_list<long long> call, const std::function<int()>& enqueue) {
+    const std::vector<long long> key = graph_key(ws, route, call);
+    auto it = ws->graphs.find(key);
+    if (it == ws->graphs.end()) {
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        HIP_OK(hipStreamSynchronize(ws->stream));
+        HIP_OK(hipStreamBeginCapture(ws->stream, hipStreamCaptureModeThreadLocal));
+        ws->capturing = true;
+        const int rc = enqueue();
+        ws->capturing = false;
+        const hipError_t e = hipStreamEndCapture(ws->stream, &graph);
+        if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return 1; }
+        if (e != hipSuccess || !graph) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
+        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ei != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(ei));
+        if (ws->graphs.size() >= 16) drop_graphs(ws);
+        it = ws->graphs.emplace(key, exec).first;
+    }
+    thetas_changed(ws, ws->d_thetas_own);
+    route_state_after(ws, route);
+    replay_state_after(ws);
+    HIP_OK(hipGraphLaunch(it->second, ws->stream));
+    return 0;
+}
+
+// tiles of the first stage that hold the lhs state: a device-side list (the support may have been chosen on the device),
+// rebuilt when the support changed; tiles of the previous list that the new one drops are zeroed in W
+int ensure_sweep_items(aqc_ws* ws, int x_buf) {
+    const DevPlan& p = ws->sweep;
+    const ListKey key = key_of(ws, x_buf, false);
+    if (!built_for(ws, ws->sw_items_key, key)) {
+        ProfScope ps(ws, AQC_K_MISC);
+        HIP_OK(launch_tile_items(p.h_stages[0], ws->d_combo_prev[x_buf], 2, nullptr, 0, ws->batch, ws->d_sw_items, ws->d_sw_counts,
+                                 ws->d_sw_lane_parts, ws->d_sw_prev_tiles, ws->d_sw_clear, ws->d_sw_counts + 1, ws->stream));
+        HIP_OK(launch_clear_tiles(p.h_stages[0], ws->bufs[AQC_BUF_W], ws->lane_elems, ws->d_sw_clear, ws->d_sw_counts + 1, 2 * ws->batch, ws->stream));
+        record_key(ws, ws->sw_items_key, key);
+        ws->sw_lists_built |= 1;
+    }
+    return 0;
+}
+
+// The matrix-core sweep and its gradient walk.  The route says sparse or dense; what depends on the state the V^H of the same call
+// has just written (the projected stages, Y_0 ready, the R-only sub-stage, the paired launch) is asked here.
+static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int block_to, int front_layer) {
+    const Program& prog = ws->ctx->prog;
+    DevPlan& p = ws->sweep;
+    const int x_buf = route.x_buf;
+    if (ensure_umat(ws, p)) return 1;
+    const int nsubs = (int)p.h_subs3.size();
+    const size_t m = p.h_stages.size();
+    const int nparts = sweep3_nparts(p.ntiles, ws->batch, p.k), chunk = sweep3_chunk(p.ntiles, ws->batch, p.k);
+    const bool sparse = route.sparse, skipw = route.skip_zero_w;
+    const bool projected = sweep_route_projected(ws, sparse);   // the stages after the first on the virtual register (aqc_ws_project.cpp)
+    int r_only_sub = skipw || projected ? -1 : sweep_r_only_sub(ws);   // (the zero-w variant of the kernel has no R-only form)
+    // objective by projection: psi is in W already and nobody reads the first stage's z': ITS last sub-stage is the R-only one
+    const bool first_stage_r_only = projected && ws->proj_y0_ready && ws->r_only_enabled && p.h_stages[0].nsubs >= 2 &&
+                                    p.h_stages[0].nsubs <= ws->r_only_max_subs;
+    if (first_stage_r_only) r_only_sub = p.h_stages[0].sub_begin + p.h_stages[0].nsubs - 1;
+    bool pair_virtual = projected && ws->proj_y0_ready && projected_pairs(ws);   // the first stage and the virtual stage as one launch
+#ifdef AQC_TUNING
+    if (env_int("AQC_STAMPS", 0) != 0) pair_virtual = false;
+#endif
+    // a partial Z covers the sparse route's reads when its tiles were chosen for this lhs state (or for a gather set the
+    // state was picked from); anything else reads all of Z
+    if (!ws->z_full && !(sparse && ((route.support_in_gather_set && ws->z_key.gather == ws->gather_gen) ||
+                                    (ws->z_key.buf == x_buf && ws->z_key.supp == ws->supp_version[x_buf]))) && ensure_z_full(ws, true))
+        return 1;
+    if (sparse) {
+        if (!ws->d_sw_items || !ws->w_clean || (m >= 3 && !ws->w2 && !projected)) return fail("sparse sweep inside a captured graph without its preparation");
+        if (ensure_sweep_items(ws, x_buf)) return 1;
+    }
+    for (size_t s = 0; s < (projected ? 1 : m); ++s) {
+        Stage3Args a = stage3_args(ws, p, s);
+        if (sparse) {
+            // stage 0: (x, Z) on the listed tiles -> W there; stage 1: (W, checkpoint in ZW) -> the second pair; then in place
+            double2* w2 = m >= 3 ? ws->w2 : nullptr;
+            double2* z2 = m >= 3 ? ws->zw2 : nullptr;
+            a.in0 = s == 0 ? ws->bufs[x_buf] : (s == 1 ? ws->bufs[AQC_BUF_W] : w2);
+            a.in1 = s == 0 ? ws->bufs[AQC_BUF_Z] : (s == 1 ? ws->bufs[AQC_BUF_ZW] : z2);
+            a.out0 = s == 0 ? ws->bufs[AQC_BUF_W] : w2;
+            a.out1 = s == 0 ? nullptr : z2;
+            a.store_out = s + 1 < m ? (s == 0 ? 1 : 3) : 0;
+            if (s == 0) stage3_first_list(ws, a);
+            if (s == 0 && first_stage_r_only) { a.r_only_last = 1; a.store_out = 0; }
+        } else {
+            a.in0 = s == 0 ? ws->bufs[x_buf] : ws->bufs[AQC_BUF_W];
+            a.in1 = s == 0 ? ws->bufs[AQC_BUF_Z] : ws->bufs[AQC_BUF_ZW];
+            a.out0 = ws->bufs[AQC_BUF_W];
+            a.out1 = ws->bufs[AQC_BUF_ZW];
+            a.store_out = s + 1 < m ? 3 : 0;
+        }
+        if (skipw && !a.items) a.supp = ws->d_combo_prev[x_buf];
+        if (s + 1 == m && r_only_sub >= 0) a.r_only_last = 1;
+        stage3_sweep_fields(a, p, nparts, chunk);
+#ifdef AQC_TUNING
+        const size_t nwg = (size_t)p.ntiles * ws->batch;
+        a.debug = env_int("AQC_DEBUG_SKIP", 0);
+        if (stamps_begin(ws, a, nwg)) return 1;
+#endif
+        if (pair_virtual) {   // ... with the virtual stage (Y_0 is there already: nothing of it waits for this stage)
+            const Stage3Args b = projected_sweep_stage(ws, 0);
+            ProfScope ps(ws, AQC_K_SWEEP_LIST);
+            HIP_OK(launch_sweep3_pair(p.k, ws->stream, a, b));
+        } else {
+            ProfScope ps(ws, a.items ? AQC_K_SWEEP_LIST : AQC_K_SWEEP);
+            HIP_OK(launch_sweep3(p.k, ws->stream, a));
+        }
+#ifdef AQC_TUNING
+        if (stamps_sweep(ws, a, s, nwg)) return 1;
+#endif
+    }
+    if (projected && !pair_virtual && run_projected_stages(ws)) return 1;
+    sweep_state_after(ws, sparse);
+    ProfScope ps(ws, AQC_K_FINALIZE);
+    RgradSecond vwalk;   // projected route: the virtual plan's walk in the same launch (two launches: 54 + 54 us at the headline, one: ~70)
+    if (projected) vwalk = projected_rgrad_plan(ws);
+    HIP_OK(launch_rgrad(p.d_subs3, p.d_grps, prog.entangler, ws->d_thetas, prog.num_thetas(), p.d_rpart, p.ntiles, nsubs, ws->d_partial,
+                        ws->nslots, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream,
+                        ws->grads_direct ? ws->d_slot_theta : nullptr, ws->d_grads, ws->mirror_grads,
+                        route.gather_rides ? GatherJob{ws->bufs[AQC_BUF_Z], ws->lane_elems, ws->d_index, ws->gather_count, ws->d_small, ws->mirror_small}
+                                         : GatherJob{nullptr, 0, nullptr, 0, nullptr, nullptr},
+                        nparts, chunk,
+                        sparse ? p.h_stages[0].nsubs : 0, sparse ? ws->d_sw_lane_parts : nullptr, r_only_sub, p.d_umat,
+                        projected ? p.h_stages[0].nsubs : -1, projected ? &vwalk : nullptr));
+#ifdef AQC_TUNING
+    if (env_int("AQC_STAMPS", 0) != 0) { HIP_OK(hipStreamSynchronize(ws->stream)); rgrad_print_stamps(nsubs); }
+#endif
+    if (!ws->grads_direct)   // some theta collects two slots (2nd-order Trotter half-layers, core_operations.py:966-968)
+        HIP_OK(launch_finalize(ws->d_partial, ws->d_theta_slots, ws->d_slot_ntiles, ws->d_grads, prog.num_thetas(), ws->nslots,
+                               1, prog.n, prog.tpb, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream, ws->mirror_grads));
+    return 0;
+}
+
+// The VALU families (1 and 2): every stage over all tiles, in place on (W, ZW), the partial gradients summed by launch_finalize.
+static int sweep_valu(aqc_ws* ws, int x_buf, int block_from, int block_to, int front_layer) {
+    const Program& prog = ws->ctx->prog;
+    DevPlan& p = ws->sweep;
+    if (before_read(ws, AQC_BUF_Z)) return 1;
+    for (size_t s = 0; s < p.h_stages.size(); ++s) {
+        StageArgs a = stage_args(ws, p, s);
+        a.in0 = s == 0 ? ws->bufs[x_buf] : ws->bufs[AQC_BUF_W];
+        a.in1 = s == 0 ? ws->bufs[AQC_BUF_Z] : ws->bufs[AQC_BUF_ZW];
+        a.out0 = ws->bufs[AQC_BUF_W];
+        a.out1 = ws->bufs[AQC_BUF_ZW];
+        a.partial = ws->d_partial; a.nslots = ws->nslots; a.ntiles_max = p.ntiles;
+#ifdef AQC_TUNING   // timing experiments only (tools/tune.py); never part of the shipped library
+        a.debug = env_int("AQC_DEBUG_SKIP", 0);
+#endif
+        a.from = block_from; a.to = block_to; a.front = front_layer ? 1 : 0;
+        ProfScope ps(ws, AQC_K_SWEEP);
+        if (p.v2) HIP_OK(launch_sweep2(prog.entangler, p.ntiles, ws->batch, p.k, p.reg_bits, ws->stream, a));
+        else HIP_OK(launch_sweep(prog.entangler, p.ntiles, ws->batch, ws->threads, p.k, ws->stream, a));
+    }
+    sweep_state_after(ws, false);
+    ProfScope ps(ws, AQC_K_FINALIZE);
+    HIP_OK(launch_finalize(ws->d_partial, ws->d_theta_slots, ws->d_slot_ntiles, ws->d_grads, prog.num_thetas(), ws->nslots,
+                           p.ntiles, prog.n, prog.tpb, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream, ws->mirror_grads));
+    return 0;
+}
+
+// what every sweep asks of its arguments and of the workspace, before anything is decided or enqueued
+static int sweep_refused(aqc_ws* ws, int x_buf, int block_from, int block_to) {
+    if (check_buf(ws, x_buf)) return 1;
+    if (x_buf == AQC_BUF_W || x_buf == AQC_BUF_ZW || x_buf == AQC_BUF_Z) return fail("lhs buffer must not be Z, W or ZW");
+    return ensure_coef(ws) || check_block_range(ws, block_from, block_to);
+}
+
+int grad_from_impl(aqc_ws* ws, const EvalRoute& route, int block_from, int block_to, int front_layer) {
+    const int x_buf = route.x_buf;
+    if (sweep_refused(ws, x_buf, block_from, block_to) || results_guard(ws)) return 1;
+    if (block_from < 0) { block_from = 0; block_to = ws->ctx->prog.num_blocks; }
+    HIP_OK(hipSetDevice(ws->device));
+    return ws->sweep.v3 ? sweep_mfma(ws, route, block_from, block_to, front_layer) : sweep_valu(ws, x_buf, block_from, block_to, front_layer);
 }
 
 }  // namespace aqc
@@ -467,167 +663,13 @@ int aqc_ws_grad(aqc_ws* ws, int block_from, int block_to, int front_layer) {
 }
 
 int aqc_ws_grad_from(aqc_ws* ws, int x_buf, int block_from, int block_to, int front_layer) {
-    return grad_from_impl(ws, x_buf, block_from, block_to, front_layer, false);
-}
-
-}  // extern "C"
-
-namespace aqc {
-
-// tiles of the first stage that hold the lhs state: a device-side list (the support may have been chosen on the device),
-// rebuilt when the support changed; tiles of the previous list that the new one drops are zeroed in W
-int ensure_sweep_items(aqc_ws* ws, int x_buf) {
-    const DevPlan& p = ws->sweep;
-    const ListKey key = key_of(ws, x_buf, false);
-    if (!built_for(ws, ws->sw_items_key, key)) {
-        ProfScope ps(ws, AQC_K_MISC);
-        HIP_OK(launch_tile_items(p.h_stages[0], ws->d_combo_prev[x_buf], 2, nullptr, 0, ws->batch, ws->d_sw_items, ws->d_sw_counts,
-                                 ws->d_sw_lane_parts, ws->d_sw_prev_tiles, ws->d_sw_clear, ws->d_sw_counts + 1, ws->stream));
-        HIP_OK(launch_clear_tiles(p.h_stages[0], ws->bufs[AQC_BUF_W], ws->lane_elems, ws->d_sw_clear, ws->d_sw_counts + 1, 2 * ws->batch, ws->stream));
-        record_key(ws, ws->sw_items_key, key);
-        ws->sw_lists_built |= 1;
-    }
-    return 0;
-}
-
-// support_in_gather_set: the lhs state was chosen on the device among the registered gather indices (surrogate objective)
-int grad_from_impl(aqc_ws* ws, int x_buf, int block_from, int block_to, int front_layer, bool support_in_gather_set) {
-    if (check_buf(ws, x_buf)) return 1;
-    if (results_guard(ws)) return 1;
-    if (x_buf == AQC_BUF_W || x_buf == AQC_BUF_ZW || x_buf == AQC_BUF_Z) return fail("lhs buffer must not be Z, W or ZW");
-    if (ensure_coef(ws)) return 1;
-    const Program& prog = ws->ctx->prog;
-    if (block_from < 0) { block_from = 0; block_to = prog.num_blocks; }
-    if (prog.num_blocks > 0 && !(0 <= block_from && block_from < block_to && block_to <= prog.num_blocks))
-        return fail("invalid block_range [%d, %d)", block_from, block_to);
+    if (sweep_refused(ws, x_buf, block_from, block_to)) return 1;   // (a refused call prepares and enqueues nothing)
     HIP_OK(hipSetDevice(ws->device));
-    DevPlan& p = ws->sweep;
-    if (p.v3) {
-        if (ensure_umat(ws, p)) return 1;
-        const int nsubs = (int)p.h_subs3.size();
-        const size_t m = p.h_stages.size();
-        const int nparts = sweep3_nparts(p.ntiles, ws->batch, p.k), chunk = sweep3_chunk(p.ntiles, ws->batch, p.k);
-        const bool sparse = sweep_route_sparse(ws, x_buf, false);
-        const bool skipw = sweep_skips_zero_w(ws, x_buf);
-        const bool projected = sweep_route_projected(ws, sparse);   // the stages after the first on the virtual register (aqc_ws_project.cpp)
-        int r_only_sub = skipw || projected ? -1 : sweep_r_only_sub(ws);   // (the zero-w variant of the kernel has no R-only form)
-        // objective by projection: psi is in W already and nobody reads the first stage's z': ITS last sub-stage is the R-only one
-        const bool first_stage_r_only = projected && ws->proj_y0_ready && ws->r_only_enabled && p.h_stages[0].nsubs >= 2 &&
-                                        p.h_stages[0].nsubs <= ws->r_only_max_subs;
-        if (first_stage_r_only) r_only_sub = p.h_stages[0].sub_begin + p.h_stages[0].nsubs - 1;
-        bool pair_virtual = projected && ws->proj_y0_ready && projected_pairs(ws);   // the first stage and the virtual stage as one launch
-#ifdef AQC_TUNING
-        if (env_int("AQC_STAMPS", 0) != 0) pair_virtual = false;
-#endif
-        // a partial Z covers the sparse route's reads when its tiles were chosen for this lhs state (or for a gather set the
-        // state was picked from); anything else reads all of Z
-        if (!ws->z_full && !(sparse && ((support_in_gather_set && ws->z_key.gather == ws->gather_gen) ||
-                                        (ws->z_key.buf == x_buf && ws->z_key.supp == ws->supp_version[x_buf]))) && ensure_z_full(ws, true))
-            return 1;
-        if (sparse) {
-            if (!ws->capturing && sweep_sparse_prepare(ws)) return 1;
-            if (!ws->d_sw_items || !ws->w_clean || (m >= 3 && !ws->w2 && !projected)) return fail("sparse sweep inside a captured graph without its preparation");
-            if (ensure_sweep_items(ws, x_buf)) return 1;
-        }
-        for (size_t s = 0; s < (projected ? 1 : m); ++s) {
-            Stage3Args a = stage3_args(ws, p, s);
-            if (sparse) {
-                // stage 0: (x, Z) on the listed tiles -> W there; stage 1: (W, checkpoint in ZW) -> the second pair; then in place
-                double2* w2 = m >= 3 ? ws->w2 : nullptr;
-                double2* z2 = m >= 3 ? ws->zw2 : nullptr;
-                a.in0 = s == 0 ? ws->bufs[x_buf] : (s == 1 ? ws->bufs[AQC_BUF_W] : w2);
-                a.in1 = s == 0 ? ws->bufs[AQC_BUF_Z] : (s == 1 ? ws->bufs[AQC_BUF_ZW] : z2);
-                a.out0 = s == 0 ? ws->bufs[AQC_BUF_W] : w2;
-                a.out1 = s == 0 ? nullptr : z2;
-                a.store_out = s + 1 < m ? (s == 0 ? 1 : 3) : 0;
-                if (s == 0) stage3_first_list(ws, a);
-                if (s == 0 && first_stage_r_only) { a.r_only_last = 1; a.store_out = 0; }
-            } else {
-                a.in0 = s == 0 ? ws->bufs[x_buf] : ws->bufs[AQC_BUF_W];
-                a.in1 = s == 0 ? ws->bufs[AQC_BUF_Z] : ws->bufs[AQC_BUF_ZW];
-                a.out0 = ws->bufs[AQC_BUF_W];
-                a.out1 = ws->bufs[AQC_BUF_ZW];
-                a.store_out = s + 1 < m ? 3 : 0;
-            }
-            if (skipw && !a.items) a.supp = ws->d_combo_prev[x_buf];
-            if (s + 1 == m && r_only_sub >= 0) a.r_only_last = 1;
-            stage3_sweep_fields(a, p, nparts, chunk);
-#ifdef AQC_TUNING
-            const size_t nwg = (size_t)p.ntiles * ws->batch;
-            a.debug = env_int("AQC_DEBUG_SKIP", 0);
-            if (stamps_begin(ws, a, nwg)) return 1;
-#endif
-            if (pair_virtual) {   // ... with the virtual stage (Y_0 is there already: nothing of it waits for this stage)
-                const Stage3Args b = projected_sweep_stage(ws, 0);
-                ProfScope ps(ws, AQC_K_SWEEP_LIST);
-                HIP_OK(launch_sweep3_pair(p.k, ws->stream, a, b));
-            } else {
-                ProfScope ps(ws, a.items ? AQC_K_SWEEP_LIST : AQC_K_SWEEP);
-                HIP_OK(launch_sweep3(p.k, ws->stream, a));
-            }
-#ifdef AQC_TUNING
-            if (stamps_sweep(ws, a, s, nwg)) return 1;
-#endif
-        }
-        if (projected && !pair_virtual && run_projected_stages(ws)) return 1;
-        sweep_state_after(ws, sparse);
-        ProfScope ps(ws, AQC_K_FINALIZE);
-        RgradSecond vwalk;   // projected route: the virtual plan's walk in the same launch (two launches: 54 + 54 us at the headline, one: ~70)
-        if (projected) vwalk = projected_rgrad_plan(ws);
-        HIP_OK(launch_rgrad(p.d_subs3, p.d_grps, prog.entangler, ws->d_thetas, prog.num_thetas(), p.d_rpart, p.ntiles, nsubs, ws->d_partial,
-                            ws->nslots, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream,
-                            ws->grads_direct ? ws->d_slot_theta : nullptr, ws->d_grads, ws->mirror_grads,
-                            ws->gather_rides ? GatherJob{ws->bufs[AQC_BUF_Z], ws->lane_elems, ws->d_index, ws->gather_count, ws->d_small, ws->mirror_small}
-                                             : GatherJob{nullptr, 0, nullptr, 0, nullptr, nullptr},
-                            nparts, chunk,
-                            sparse ? p.h_stages[0].nsubs : 0, sparse ? ws->d_sw_lane_parts : nullptr, r_only_sub, p.d_umat,
-                            projected ? p.h_stages[0].nsubs : -1, projected ? &vwalk : nullptr));
-#ifdef AQC_TUNING
-        if (env_int("AQC_STAMPS", 0) != 0) { HIP_OK(hipStreamSynchronize(ws->stream)); rgrad_print_stamps(nsubs); }
-#endif
-        if (!ws->grads_direct)   // some theta collects two slots (2nd-order Trotter half-layers, core_operations.py:966-968)
-            HIP_OK(launch_finalize(ws->d_partial, ws->d_theta_slots, ws->d_slot_ntiles, ws->d_grads, prog.num_thetas(), ws->nslots,
-                                   1, prog.n, prog.tpb, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream, ws->mirror_grads));
-        return 0;
-    }
-    if (before_read(ws, AQC_BUF_Z)) return 1;
-    for (size_t s = 0; s < p.h_stages.size(); ++s) {
-        StageArgs a;
-        memset(&a, 0, sizeof a);
-        a.stage = p.d_stages + s;
-        a.ops = p.d_ops;
-        a.subs = p.d_subs;
-        a.mops = p.d_mops;
-        a.coef = ws->d_coef;
-        a.ncoef = prog.n + prog.num_blocks + 1;
-        a.in0 = s == 0 ? ws->bufs[x_buf] : ws->bufs[AQC_BUF_W];
-        a.in1 = s == 0 ? ws->bufs[AQC_BUF_Z] : ws->bufs[AQC_BUF_ZW];
-        a.out0 = ws->bufs[AQC_BUF_W];
-        a.out1 = ws->bufs[AQC_BUF_ZW];
-        a.lane_stride = ws->lane_elems;
-        a.partial = ws->d_partial;
-        a.nslots = ws->nslots;
-        a.ntiles_max = p.ntiles;
-#ifdef AQC_TUNING   // timing experiments only (tools/tune.py); never part of the shipped library
-        a.debug = env_int("AQC_DEBUG_SKIP", 0);
-#endif
-        a.from = block_from;
-        a.to = block_to;
-        a.front = front_layer ? 1 : 0;
-        ProfScope ps(ws, AQC_K_SWEEP);
-        if (p.v2) HIP_OK(launch_sweep2(prog.entangler, p.ntiles, ws->batch, p.k, p.reg_bits, ws->stream, a));
-        else HIP_OK(launch_sweep(prog.entangler, p.ntiles, ws->batch, ws->threads, p.k, ws->stream, a));
-    }
-    sweep_state_after(ws, false);
-    ProfScope ps(ws, AQC_K_FINALIZE);
-    HIP_OK(launch_finalize(ws->d_partial, ws->d_theta_slots, ws->d_slot_ntiles, ws->d_grads, prog.num_thetas(), ws->nslots,
-                           p.ntiles, prog.n, prog.tpb, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream, ws->mirror_grads));
-    return 0;
+    EvalRoute route;   // the sweep alone: no V^H in this call, the thetas are the ones in use
+    route.x_buf = x_buf; route.grads = true;
+    if (eval_route(ws, route)) return 1;
+    return grad_from_impl(ws, route, block_from, block_to, front_layer);
 }
-
-}  // namespace aqc
-
-extern "C" {
 
 // Z = V^H Y where the objective reads it, the registered gather (if any), the sweep from x_buf: enqueued, not waited for.
 // What a driver that keeps its thetas on the device (aqc_ws_use_theta_set) calls per evaluation, followed by
@@ -639,25 +681,19 @@ int aqc_ws_objective_launch(aqc_ws* ws, int x_buf, int block_from, int block_to,
     if (check_block_range(ws, block_from, block_to)) return 1;   // (a refused call enqueues nothing)
     if (ensure_coef(ws)) return 1;
     HIP_OK(hipSetDevice(ws->device));
-    const bool sparse = sweep_route_sparse(ws, x_buf, true);
-    if (sparse && sweep_sparse_prepare(ws)) return 1;
-    const bool lazy = sparse && vdag_route_restricted(ws, x_buf);
-    const bool by_projection = lazy && vdag_route_projected(ws, x_buf);
-    if (by_projection) { if (run_vdag_projected(ws, x_buf)) return 1; }
-    else if (lazy) { if (run_vdag_restricted(ws, x_buf)) return 1; }
-    else if (run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)) return 1;
-    if (ws->gather_count > 0 && (by_projection ? proj_fix_amplitudes(ws, x_buf) : aqc_ws_gather_launch(ws, AQC_BUF_Z))) return 1;
-    return grad_from_impl(ws, x_buf, block_from, block_to, front_layer, false);
+    EvalRoute route;   // V^H, the gather as a launch of its own, the sweep; the thetas are the ones in use
+    route.x_buf = x_buf; route.vdag = route.grads = true; route.gather = ws->gather_count > 0;
+    if (eval_route(ws, route)) return 1;
+    if (enqueue_vdag(ws, route)) return 1;
+    if (route.gather && enqueue_gather(ws, route)) return 1;
+    return grad_from_impl(ws, route, block_from, block_to, front_layer);
 }
 
 int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered, int x_buf, int block_from, int block_to,
                 int front_layer, double* grads) {
     if (!ws) return fail("null workspace");
     HIP_OK(hipSetDevice(ws->device));
-    if (ws->copy_pending) {   // result copies of an earlier aqc_ws_results_async: this call reuses the pinned buffer and may replay a graph
-        HIP_OK(hipStreamSynchronize(ws->copy_stream));
-        ws->copy_pending = false;
-    }
+    if (wait_result_copies(ws)) return 1;
     const Program& prog = ws->ctx->prog;
     const size_t nth = (size_t)ws->batch * prog.num_thetas();
     double* pin_th = ws->h_pin;
@@ -672,69 +708,42 @@ int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered,
     if (check_buf(ws, x_buf)) return 1;
     if (grads && check_block_range(ws, block_from, block_to)) return 1;
     if (!thetas && (do_vdag || grads) && ensure_coef(ws)) return 1;
-    // Small results skip the device-to-host copy nodes: the producing kernels write a second copy straight into the pinned
-    // staging buffer (two nodes and their dependencies less on the single-evaluation critical path).
+    // small results: no copy nodes (two nodes and their dependencies less on the single-evaluation critical path)
     const bool zero_copy = sizeof(double2) * (nth + nsm) <= 65536;
-    struct MirrorScope {
-        aqc_ws* w;
-        MirrorScope(aqc_ws* w_, double* g, double* s) : w(w_) { w->mirror_grads = g; w->mirror_small = s; }
-        ~MirrorScope() {   // also on the error paths of enqueue(): no stale pinned thetas / riding gather in the next call
-            w->mirror_grads = nullptr; w->mirror_small = nullptr; w->theta_host = nullptr; w->gather_rides = false;
-        }
-    } mirror_scope(ws, zero_copy ? pin_gr : nullptr, zero_copy ? pin_sm : nullptr);
-    // route of the sweep (decided before anything is enqueued: new thetas invalidate the checkpoint, a V^H in this call renews it)
-    const bool sparse = grads && (do_vdag ? sweep_route_sparse(ws, x_buf, true) : (!thetas && sweep_route_sparse(ws, x_buf, false)));
-    if (sparse && sweep_sparse_prepare(ws)) return 1;
-    const bool lazy = sparse && do_vdag && vdag_route_restricted(ws, x_buf);   // V^H only where this call (gather, sweep) reads it
-    // ... and by two passes over y instead of its stages where the lhs state and the gather set allow (never with a riding gather)
-    const bool by_projection = lazy && grads && !(gathered && zero_copy && ws->sweep.v3) && vdag_route_projected(ws, x_buf);
-    if (!do_vdag && (gathered || grads) && before_read(ws, AQC_BUF_Z)) return 1;  // a partial Z left by an earlier call is completed here,
-                                                                              // outside whatever graph is captured below
+    MirrorScope mirror_scope(ws, zero_copy ? pin_gr : nullptr, zero_copy ? pin_sm : nullptr);
+    // a partial Z left by an earlier call is completed here, outside whatever graph is captured below (and before the route is
+    // decided: completing it from Y renews the checkpoint the decision asks about)
+    if (!do_vdag && (gathered || grads) && before_read(ws, AQC_BUF_Z)) return 1;
+    // with a gradient in the same call the gather (it only reads Z, which the sweep leaves intact) rides along as one
+    // extra workgroup per lane of the gradient-walk kernel: one node less on the single-evaluation critical path
+    EvalRoute route;
+    route.x_buf = x_buf; route.vdag = do_vdag != 0; route.new_thetas = thetas != nullptr;
+    route.gather = gathered != nullptr; route.grads = grads != nullptr;
+    route.gather_rides = gathered && grads && zero_copy && ws->sweep.v3;
+    if (eval_route(ws, route)) return 1;
     auto enqueue = [&]() -> int {   // everything between the host copy of the thetas and the final synchronisation
         if (thetas) {
-            // matrix-core path, small batch: no copy node -- the U builder (first kernel of V^H or of the sweep) reads the pinned
-            // thetas over the bus and stores them to HBM for the gradient walk
-            const bool direct_thetas = zero_copy && (do_vdag || grads) && ws->fwd.v3 && ws->inv.v3 && ws->sweep.v3 && !ws->need_coef &&
-                                       (do_vdag ? ws->inv.v3 : true);
-            if (!direct_thetas) HIP_OK(hipMemcpyAsync(ws->d_thetas_own, pin_th, sizeof(double) * nth, hipMemcpyHostToDevice, ws->stream));
+            const bool direct = (do_vdag || grads) && direct_thetas(ws, zero_copy);   // (somebody builds unitaries from them)
+            if (!direct) HIP_OK(hipMemcpyAsync(ws->d_thetas_own, pin_th, sizeof(double) * nth, hipMemcpyHostToDevice, ws->stream));
             if (run_coef(ws, ws->d_thetas_own)) return 1;
-            ws->theta_host = direct_thetas ? pin_th : nullptr;
+            ws->theta_host = direct ? pin_th : nullptr;
         }
-        if (do_vdag && (by_projection ? run_vdag_projected(ws, x_buf) : (lazy ? run_vdag_restricted(ws, x_buf) : run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)))) return 1;
-        // with a gradient in the same call the gather (it only reads Z, which the sweep leaves intact) rides along as one
-        // extra workgroup per lane of the gradient-walk kernel: one node less on the single-evaluation critical path
-        const bool ride = gathered && grads && zero_copy && ws->sweep.v3;
-        if (gathered && !ride) {
-            if (by_projection ? proj_fix_amplitudes(ws, x_buf) : aqc_ws_gather_launch(ws, AQC_BUF_Z)) return 1;
+        if (route.vdag && enqueue_vdag(ws, route)) return 1;
+        if (route.gather && !route.gather_rides) {
+            if (enqueue_gather(ws, route)) return 1;
             if (!zero_copy) HIP_OK(hipMemcpyAsync(pin_sm, ws->d_small, sizeof(double2) * nsm, hipMemcpyDeviceToHost, ws->stream));
         }
-        ws->gather_rides = ride;
         if (grads) {
-            if (aqc_ws_grad_from(ws, x_buf, block_from, block_to, front_layer)) return 1;
+            if (grad_from_impl(ws, route, block_from, block_to, front_layer)) return 1;
             if (!zero_copy) HIP_OK(hipMemcpyAsync(pin_gr, ws->d_grads, sizeof(double2) * nth, hipMemcpyDeviceToHost, ws->stream));
         }
-        ws->gather_rides = false;
         ws->theta_host = nullptr;
         return 0;
     };
     if (thetas) memcpy(pin_th, thetas, sizeof(double) * nth);
     static const bool graphs_on = env_int("AQC_GRAPH", 1) != 0;
     if (thetas && graphs_on && !ws->profile) {
-        const std::vector<long long> key = {do_vdag, gathered ? 1 : 0, grads ? 1 : 0, x_buf, block_from, block_to, front_layer,
-                                            (long long)ws->gather_count, (long long)(size_t)ws->d_small, (long long)(size_t)ws->h_pin,
-                                            (sparse ? 1 : 0) + (lazy ? 2 : 0) + (grads && sweep_skips_zero_w(ws, x_buf) ? 4 : 0) + (by_projection ? 8 : 0),
-                                            (long long)(size_t)ws->d_combo_prev[x_buf],
-                                            (long long)(size_t)ws->d_vd_items};
-        auto state_after = [&]() {
-            thetas_changed(ws, ws->d_thetas_own);
-            if (do_vdag) {
-                if (by_projection) vdag_projected_state_after(ws, x_buf);
-                else if (lazy) vdag_restricted_state_after(ws, x_buf);
-                else apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
-            }
-            if (grads) sweep_state_after(ws, sparse);
-        };
-        if (run_graph(ws, key, enqueue, state_after)) return 1;
+        if (run_graph(ws, route, {0, block_from, block_to, front_layer, (long long)ws->gather_count}, enqueue)) return 1;
     } else if (enqueue()) {
         return 1;
     }

@@ -242,6 +242,59 @@ def test_coordinate_descent_chain_leaves_no_stale_checkpoint(monkeypatch):
         assert wm.maxdiff(a, b) < 1e-12
 
 
+def test_device_lbfgs_in_every_configuration(monkeypatch):
+    """aqc_ws_optim.cpp aqc_ws_lbfgs (maxiter=2): its evaluate step decides its route like the one-call evaluations do, and picks
+    the lhs state on the device between V^H and the sweep.  Under every configuration the point it reports has the reported
+    fidelity and surrogate value (oracle, 1e-10), an objective_launch from another lhs state afterwards reads nothing stale (Z,
+    amplitudes, gradient: oracle, 1e-10), and all of it agrees across the configurations (1e-12).  Lane 1's target sits on a flip
+    state in another first-stage tile: that lane leads with it, so the support of the combined lhs state moves."""
+    import ctypes
+
+    from aqc_research_amd import _lib
+
+    circ, ctx, tile, batch, oracle = _shape("cx12_t10")
+    n, T = circ.num_qubits, circ.num_thetas
+    rng = np.random.default_rng(707)
+    idx = np.array([5, 5 ^ (1 << tile), 5 ^ 2, 5 ^ (1 << (n - 1))], np.int64)
+    basis = np.eye(1 << n, dtype=complex)
+    x0 = 0.05 * np.stack([orc.rand_thetas(T, rng) for _ in range(batch)])
+    near = x0 + 0.01 * np.stack([orc.rand_thetas(T, rng) for _ in range(batch)])   # targets a short way from the start
+    tg = np.stack([orc.v_mul_vec(circ, near[0], basis[idx[0]]), orc.v_mul_vec(circ, near[1], basis[idx[1]]), orc.rand_state(n, rng)])
+    th = np.stack([orc.rand_thetas(T, rng) for _ in range(batch)])
+    x_late = [(3 << tile) | (7 + b) for b in range(batch)]
+    i64 = ctypes.POINTER(ctypes.c_int64)
+    results = {}
+    for cfg, env in CONFIGS.items():
+        _configure(monkeypatch, env)
+        ws = _maker(ctx, batch, tile)()
+        ws.upload(BUF_Y, tg)
+        ws.set_basis(BUF_X, int(idx[0]))
+        ws.gather_setup(idx)
+        x, f, fid, w = np.empty_like(x0), np.empty(batch), np.empty(batch), np.empty(batch)
+        nit, lead, nfev = np.zeros(batch, np.int64), np.zeros(batch, np.int64), ctypes.c_int64()
+        _lib.check(ws._L.aqc_ws_lbfgs(ws.handle, _lib.dptr(x0.copy()), 2, 5, 1e-7, 1e-12, 0.0, 12, -1, -1, 1, _lib.dptr(x), _lib.dptr(f),
+                                      _lib.dptr(fid), nit.ctypes.data_as(i64), ctypes.byref(nfev), _lib.dptr(w), lead.ctypes.data_as(i64)))
+        ws.set_basis(BUF_X, x_late)
+        ws.set_thetas(th)
+        ws.objective_launch(BUF_X)
+        hs, g, z = ws.gather_fetch(), ws.get_grads(), ws.download(BUF_Z)
+        ws.close()
+        assert lead[1] == 1 and nfev.value >= 3, (lead, nfev.value)   # the case this test is about really occurs
+        reads = [("x", x), ("f", f), ("fidelity", fid), ("weight", w), ("leading", lead.astype(float)), ("nit", nit.astype(float)),
+                 ("nfev", np.array([float(nfev.value)])), ("launch.hs", hs), ("launch.grads", g), ("launch.z", z)]
+        for b in range(batch):
+            h2 = np.abs(oracle.vdag(x[b], tg[b])[idx]) ** 2
+            f_ref = 1.0 - (1.0 - w[b]) * h2[0] - w[b] * h2[lead[b]]
+            vh = oracle.vdag(th[b], tg[b])
+            print(f"{cfg} lane {b}: f = {f[b]:.6f}, leading state {lead[b]}, nit {nit[b]}; |fidelity - oracle| = {abs(fid[b] - h2[0]):.3g}, "
+                  f"|f - oracle| = {abs(f[b] - f_ref):.3g}, |Z - oracle| = {wm.maxdiff(z[b], vh):.3g}")
+            assert abs(fid[b] - h2[0]) < wm.TOL and abs(f[b] - f_ref) < wm.TOL
+            assert wm.maxdiff(z[b], vh) < wm.TOL and wm.maxdiff(hs[b], vh[idx]) < wm.TOL
+            assert wm.maxdiff(g[b], oracle.grad(th[b], basis[x_late[b]], vh)) < wm.TOL
+        results[cfg] = [(0, label, np.array(got)) for label, got in reads]
+    _cross_check(results)
+
+
 # ---- random sequences ------------------------------------------------------------------------------------------------------
 
 CASES = [(s, seed) for s in ("cx12_t10", "cz13_t8", "trotter13_t10", "cp14_t9") for seed in (1, 2, 3)] + [("cx16_t9", 4), ("cx16_t9", 5)]
