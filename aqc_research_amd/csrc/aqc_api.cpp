@@ -405,7 +405,8 @@ int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_
     {
         // [V^H | sweep | virtual sweep | V]; with the mirrored V^H plan the sweep's jobs write V^H's operands as well (sub-stage s of the
         // sweep is sub-stage nsubs - 1 - s of V^H, conjugate-transposed) and V^H gets no jobs of its own
-        std::vector<UJob> jobs;
+        std::vector<UJob> jobs, route_jobs;
+        size_t n_vdag_sweep = 0;   // jobs of [V^H | sweep | virtual sweep]: what a reader of everything launches (V's jobs run on their own)
         DevPlan* vsw = ws->proj.ok ? &ws->proj.vsw : nullptr;
         const int nsw = ws->sweep.v3 ? (int)ws->sweep.h_subs3.size() : 0;
         ws->ujobs_mirror = ws->inv_mirrored && ws->inv.v3 && (int)ws->inv.h_subs3.size() == nsw && env_int("AQC_UBUILD_MIRROR", 1) != 0;
@@ -420,7 +421,16 @@ int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_
                         j.umat_mirror = ws->proj.vinv.d_umat; j.mirror_index = nvs - 1 - (int)i; j.mirror_nsubs = nvs;
                     }
                     jobs.push_back(j);
+                    if (p != &ws->fwd) ++n_vdag_sweep;
+                    // what the objective-by-projection route reads: V^H's last stage (= the sweep's first, mirrored), the sweep's first, the virtual plans
+                    if (vsw && ((p == &ws->inv && (int)i >= p->h_stages.back().sub_begin) || (p == &ws->sweep && (int)i < p->h_stages[0].nsubs) || p == vsw))
+                        route_jobs.push_back(j);
                 }
+        if (vsw && !route_jobs.empty() && route_jobs.size() < n_vdag_sweep && env_int("AQC_UBUILD_SUBSET", 1) != 0) {
+            WS_HIP(hipMalloc((void**)&ws->d_ujobs_route, sizeof(UJob) * route_jobs.size()));
+            WS_HIP(hipMemcpy(ws->d_ujobs_route, route_jobs.data(), sizeof(UJob) * route_jobs.size(), hipMemcpyHostToDevice));
+            ws->n_ujobs_route = (int)route_jobs.size();
+        }
         if (!jobs.empty()) {
             WS_HIP(hipMalloc((void**)&ws->d_ujobs, sizeof(UJob) * jobs.size()));
             WS_HIP(hipMemcpy(ws->d_ujobs, jobs.data(), sizeof(UJob) * jobs.size(), hipMemcpyHostToDevice));
@@ -458,7 +468,7 @@ int aqc_ws_destroy(aqc_ws* ws) {
     proj_free(ws);
     for (DevPlan* p : {&ws->fwd, &ws->inv, &ws->sweep}) free_plan(*p);
     void* ptrs[] = {ws->d_thetas_own, ws->d_theta_bank, ws->d_coef, ws->d_partial, ws->d_grads, ws->d_small, ws->d_vdot_part, ws->d_index, ws->d_tmp_index, ws->d_tmp_small,
-                    ws->d_theta_slots, ws->d_slot_theta, ws->d_slot_ntiles, ws->d_basis_index, ws->d_vdot_out, ws->d_ujobs};
+                    ws->d_theta_slots, ws->d_slot_theta, ws->d_slot_ntiles, ws->d_basis_index, ws->d_vdot_out, ws->d_ujobs, ws->d_ujobs_route};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (int b = 0; b < AQC_NUM_BUFS; ++b) if (ws->bufs[b]) (void)hipFree(ws->bufs[b]);
     for (int b = 0; b < AQC_NUM_BUFS; ++b) if (ws->d_combo_prev[b]) (void)hipFree(ws->d_combo_prev[b]);

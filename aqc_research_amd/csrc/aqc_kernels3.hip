@@ -107,6 +107,10 @@ constexpr int kApplySkip = AQC_EXP_APPLY_SKIP;
 #define AQC_EXP_SWEEP_SKIP 0
 #endif
 constexpr int kSweepSkip = AQC_EXP_SWEEP_SKIP;
+#ifndef AQC_EXP_UBUILD_SKIP   // the U builder: 1 = none of its plane-set stores, 2 = none of the mirror sets' (the chain of gate groups stays alive)
+#define AQC_EXP_UBUILD_SKIP 0
+#endif
+constexpr int kUbuildSkip = AQC_EXP_UBUILD_SKIP;
 
 constexpr int kSweepSpread = AQC_SWEEP_SPREAD, kApplySpread = AQC_APPLY_SPREAD;   // MFMAs between two LDS writes inside a matrix run (sweep / V, V^H)
 template <int K, bool SWEEP = false> struct TileShape {   // compile-time shape of a 2^K-amplitude tile
@@ -860,6 +864,12 @@ __global__ __launch_bounds__(64) void ubuild_kernel(const UJob* jobs, const doub
     }
     __syncthreads();
     double* out = job.umat + ((size_t)b * job.nsubs + job.index) * 12 * 64;
+    if (kUbuildSkip) {   // (experiment builds: the values stay live behind a store that never happens)
+        double acc = 0.0;
+        for (int m = 0; m < 4; ++m) acc += u[lane + 64 * m].x * u[lane + 64 * m].y;
+        if (acc == 1.0e300) out[lane] = acc;
+    }
+    if (kUbuildSkip & 1) return;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         const cplx v = u[(lane & 15) * 16 + 4 * s + (lane >> 4)];
@@ -867,7 +877,7 @@ __global__ __launch_bounds__(64) void ubuild_kernel(const UJob* jobs, const doub
         out[(1 * 4 + s) * 64 + lane] = v.y - v.x;   // u1 = Im U - Re U
         out[(2 * 4 + s) * 64 + lane] = v.x + v.y;   // u2 = Re U + Im U
     }
-    if (job.umat_mirror) {   // the mirrored V^H plan runs this sub-stage's U^H: the same matrix conjugate-transposed, no second chain
+    if (job.umat_mirror && !(kUbuildSkip & 2)) {   // the mirrored V^H plan runs this sub-stage's U^H: the same matrix conjugate-transposed, no second chain
         double* om = job.umat_mirror + ((size_t)b * job.mirror_nsubs + job.mirror_index) * 12 * 64;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {

@@ -46,6 +46,10 @@ inline int ceil_log2(int v) {
     return b;
 }
 
+// How much of a plan's operand buffer (d_umat) matches the coefficients in use.  The V^H and sweep plans are built by one launch and
+// share the level; kURoute: only the plane sets the objective-by-projection route reads (ensure_umat, aqc_ws_sweep.cpp).
+enum ULevel { kUNone = 0, kURoute = 1, kUAll = 2 };
+
 struct DevPlan {
     Plan plan;
     std::vector<DevStage> h_stages;
@@ -66,7 +70,7 @@ struct DevPlan {
     DevGrp* d_grps = nullptr;
     double* d_umat = nullptr;     // [batch][nsubs][12][64]
     double2* d_rpart = nullptr;   // sweep plan only: [batch][nsubs][ntiles][256]
-    bool u_valid = false;         // d_umat matches the coefficients in use
+    int u_level = kUNone;         // how much of d_umat matches the coefficients in use (ULevel)
     int family() const { return v3 ? 3 : (v2 ? 2 : 1); }
 };
 
@@ -200,8 +204,12 @@ struct aqc_ws {
     // D2H copies) captured once per call signature and replayed -- one launch instead of ~11 host calls per evaluation
     std::map<std::vector<long long>, hipGraphExec_t> graphs;
     bool capturing = false;
-    UJob* d_ujobs = nullptr;          // family 3: [V^H subs | sweep subs | V subs]; ujobs_mirror: no V^H jobs, the sweep's write both operand sets
+    UJob* d_ujobs = nullptr;          // family 3: [V^H subs | sweep subs | virtual sweep subs | V subs]; ujobs_mirror: no V^H jobs, the sweep's write both operand sets
     bool ujobs_mirror = false;
+    // The jobs the objective-by-projection route reads, as a compact list of their own: [V^H's last stage (its own jobs only) | the
+    // sweep's first stage | virtual sweep].  Null: the route builds everything (no projected route, or AQC_UBUILD_SUBSET=0).
+    UJob* d_ujobs_route = nullptr;
+    int n_ujobs_route = 0;
     struct MpsSlot {
         std::vector<int> dims;          // n + 1 bond dimensions
         std::vector<size_t> offset;     // element offset of site q inside d_t
@@ -362,7 +370,7 @@ int run_graph(aqc_ws* ws, const EvalRoute& route, std::initializer_list<long lon
 void vdag_projected_state_after(aqc_ws* ws, int x_buf);
 int grad_from_impl(aqc_ws* ws, const EvalRoute& route, int block_from, int block_to, int front_layer);   // the sweep and the gradient walk
 int sweep_r_only_sub(const aqc_ws* ws);
-int ensure_umat(aqc_ws* ws, DevPlan& p);
+int ensure_umat(aqc_ws* ws, DevPlan& p, int need = kUAll);   // need: kURoute when the caller reads the projected route's plane sets only
 int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf);
 // descriptions of a matrix-core stage launch; the buffers and what is particular to the launch are the caller's
 Stage3Args stage3_args(aqc_ws* ws, const DevPlan& p, size_t s);   // stage s of a plan on the full-size register, over all (tile, lane) pairs

@@ -340,7 +340,7 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // for a route eval_route has 
     ProjRoute& pr = ws->proj;
     const DevPlan& p = ws->sweep;
     const DevPlan& iv = ws->inv;
-    if (ensure_umat(ws, ws->inv)) return 1;
+    if (ensure_umat(ws, ws->inv, kURoute)) return 1;   // V^H's last stage, the sweep's first, the virtual plans: nothing else is read
     if (!ws->d_sw_items || !ws->w_clean) return fail("objective by projection without the sparse route's preparation");
     if (ensure_sweep_items(ws, x_buf)) return 1;
     Stage3Args psi = stage3_args(ws, p, 0);   // the first stage's gates on the basis index, on the listed tiles: x -> W

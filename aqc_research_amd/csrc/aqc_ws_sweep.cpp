@@ -28,18 +28,20 @@ namespace aqc {
 void thetas_changed(aqc_ws* ws, double* d_thetas) {
     ws->d_thetas = d_thetas;
     ws->coef_valid = true;
-    ws->fwd.u_valid = ws->inv.u_valid = ws->sweep.u_valid = false;
+    ws->fwd.u_level = ws->inv.u_level = ws->sweep.u_level = kUNone;
     ws->ckpt_valid = false;   // ZW (and Z) belong to the previous thetas
     ws->z_from_y = false;
     ws->proj_y0_ready = false;
 }
 
-// family 3: ensure_umat has built the unitaries of `p` (the V^H and sweep plans share one launch)
-static void umat_state_after(aqc_ws* ws, const DevPlan& p) {
+// family 3: ensure_umat has built the unitaries of `p` up to `level` (the V^H and sweep plans share one launch); a level never drops here
+static void umat_state_after(aqc_ws* ws, const DevPlan& p, int level = kUAll) {
     if (!p.v3) return;
-    if (&p == &ws->fwd) ws->fwd.u_valid = true;
-    else ws->inv.u_valid = ws->sweep.u_valid = true;
+    if (&p == &ws->fwd) ws->fwd.u_level = kUAll;
+    else ws->inv.u_level = ws->sweep.u_level = std::max(ws->sweep.u_level, level);
 }
+// the level a reader of the projected route's plane sets asks for, and leaves: the route's subset where a list of it exists
+static int route_level(const aqc_ws* ws) { return ws->d_ujobs_route ? kURoute : kUAll; }
 
 static int ensure_z_full(aqc_ws* ws, bool reader);
 
@@ -87,9 +89,13 @@ void record_key(const aqc_ws* ws, ListKey& slot, const ListKey& key) { slot = ws
 void replay_state_after(aqc_ws* ws) { ws->sw_items_key = ws->vd_key = ws->proj.init_key = ListKey{}; }
 
 // family 3: the 16 x 16 unitaries of the plan's sub-stages for the coefficients in use
-// Jobs are laid out [V^H | sweep | V]: the objective+gradient path (V^H then the sweep) is built by one launch.
-int ensure_umat(aqc_ws* ws, DevPlan& p) {
-    if (!p.v3 || p.u_valid) return 0;
+// Jobs are laid out [V^H | sweep | virtual sweep | V]: the objective+gradient path (V^H then the sweep) is built by one launch.
+// need = kURoute (the objective by projection and its sweep): only the jobs of d_ujobs_route run.  A caller that needs everything
+// while the level is kURoute launches the whole [V^H | sweep | virtual sweep] list again, from the same thetas in HBM.
+int ensure_umat(aqc_ws* ws, DevPlan& p, int need) {
+    if (!p.v3) return 0;
+    if (&p != &ws->fwd && need == kURoute) need = route_level(ws);
+    if (p.u_level >= need) return 0;
     const int T = ws->ctx->prog.num_thetas();
     const int ninv = ws->inv.v3 && !ws->ujobs_mirror ? (int)ws->inv.h_subs3.size() : 0;
     int nsw = ws->sweep.v3 ? (int)ws->sweep.h_subs3.size() : 0;
@@ -101,11 +107,12 @@ int ensure_umat(aqc_ws* ws, DevPlan& p) {
         HIP_OK(launch_ubuild(ws->d_ujobs + ninv + nsw, nfwd, ws->d_thetas, T, ws->batch, ws->stream));
     } else {
         // aqc_ws_eval (small batches): the thetas are read from its pinned staging buffer and land in HBM through this kernel
-        HIP_OK(launch_ubuild(ws->d_ujobs, ninv + nsw, ws->theta_host ? ws->theta_host : ws->d_thetas, T, ws->batch, ws->stream,
-                             ws->theta_host ? ws->d_thetas : nullptr));
+        const bool subset = need == kURoute;
+        HIP_OK(launch_ubuild(subset ? ws->d_ujobs_route : ws->d_ujobs, subset ? ws->n_ujobs_route : ninv + nsw,
+                             ws->theta_host ? ws->theta_host : ws->d_thetas, T, ws->batch, ws->stream, ws->theta_host ? ws->d_thetas : nullptr));
         ws->theta_host = nullptr;
     }
-    umat_state_after(ws, p);
+    umat_state_after(ws, p, need);
     return 0;
 }
 
@@ -222,8 +229,8 @@ static StageArgs stage_args(const aqc_ws* ws, const DevPlan& p, size_t s) {
 static bool keeps_checkpoint(const aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
     return inverse && ws->inv_mirrored && ws->inv.v3 && dst_buf == AQC_BUF_Z && src_buf != AQC_BUF_ZW && ws->inv.h_stages.size() >= 2;
 }
-static void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {   // host-side state a V / V^H leaves (also after a graph replay)
-    umat_state_after(ws, inverse ? ws->inv : ws->fwd);
+static void apply_state_after(aqc_ws* ws, bool inverse, int src_buf, int dst_buf, int level = kUAll) {   // host-side state a V / V^H leaves (also after a graph replay)
+    umat_state_after(ws, inverse ? ws->inv : ws->fwd, level);
     touch_buf(ws, dst_buf);
     if (keeps_checkpoint(ws, inverse, src_buf, dst_buf)) { touch_buf(ws, AQC_BUF_ZW); ws->ckpt_valid = true; }
 }
@@ -285,14 +292,14 @@ static Stage3Args last_vdag_stage(aqc_ws* ws) {
     a.out0 = ws->bufs[AQC_BUF_Z];
     return a;
 }
-static void vdag_restricted_state_after(aqc_ws* ws, int x_buf) {
-    apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z);
+static void vdag_restricted_state_after(aqc_ws* ws, int x_buf, int level = kUAll) {
+    apply_state_after(ws, true, AQC_BUF_Y, AQC_BUF_Z, level);
     ws->z_full = false;
     ws->z_key = key_of(ws, x_buf, true);   // (not a list a replay rebuilds: a replay states it again)
 }
 // the objective's V^H by projection (run_vdag_projected, aqc_ws_project.cpp)
 void vdag_projected_state_after(aqc_ws* ws, int x_buf) {
-    vdag_restricted_state_after(ws, x_buf);
+    vdag_restricted_state_after(ws, x_buf, route_level(ws));   // (run_vdag_projected asks ensure_umat for the route's plane sets only)
     ws->z_key.gather = 0;       // Z covers the lhs tiles, not the gather set: a later gather completes it first
     ws->ckpt_valid = false;     // ZW holds the lhs tiles of the checkpoint only
     ws->z_from_y = true;
@@ -336,7 +343,8 @@ static int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set
 static int ensure_z_full(aqc_ws* ws, bool reader) {
     if (ws->z_full) return 0;
     if (ws->capturing) return fail("BUF_Z is partial inside a captured graph");
-    if (ws->ckpt_valid && ws->inv.u_valid) {   // the last stage once more, over every tile (its inputs are all in ZW)
+    if (ws->ckpt_valid && ws->inv.u_level != kUNone) {   // the last stage once more, over every tile (its inputs are all in ZW)
+        if (ensure_umat(ws, ws->inv)) return 1;
         Stage3Args a = last_vdag_stage(ws);
         ProfScope ps(ws, AQC_K_APPLY);
         HIP_OK(launch_apply3(ws->inv.k, ws->stream, a));
@@ -344,7 +352,7 @@ static int ensure_z_full(aqc_ws* ws, bool reader) {
         return 0;
     }
     if (!reader) return 0;   // ZW is overwritten without a checkpoint in it: Z stays partial (its readers refuse, or complete it from Y)
-    if (ws->z_from_y && ws->inv.u_valid) {   // (objective by projection: no checkpoint -- the whole V^H once more, from Y)
+    if (ws->z_from_y && ws->inv.u_level != kUNone) {   // (objective by projection: no checkpoint -- the whole V^H once more, from Y; run_apply completes the plane sets)
         ws->z_full = true;
         return run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z);
     }
@@ -418,7 +426,7 @@ static int sweep_sparse_prepare(aqc_ws* ws) {
     return 0;
 }
 static void sweep_state_after(aqc_ws* ws, bool sparse) {   // host-side state a sweep leaves (also after a graph replay)
-    umat_state_after(ws, ws->sweep);
+    umat_state_after(ws, ws->sweep, sweep_route_projected(ws, sparse) ? route_level(ws) : kUAll);
     ws->proj_y0_ready = false;                 // (consumed by the projected stages)
     if (!sparse) {
         ws->w_clean = false;
@@ -517,12 +525,12 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
     const Program& prog = ws->ctx->prog;
     DevPlan& p = ws->sweep;
     const int x_buf = route.x_buf;
-    if (ensure_umat(ws, p)) return 1;
     const int nsubs = (int)p.h_subs3.size();
     const size_t m = p.h_stages.size();
     const int nparts = sweep3_nparts(p.ntiles, ws->batch, p.k), chunk = sweep3_chunk(p.ntiles, ws->batch, p.k);
     const bool sparse = route.sparse, skipw = route.skip_zero_w;
     const bool projected = sweep_route_projected(ws, sparse);   // the stages after the first on the virtual register (aqc_ws_project.cpp)
+    if (ensure_umat(ws, p, projected ? kURoute : kUAll)) return 1;   // (projected: its first stage and the virtual plan are all it reads)
     int r_only_sub = skipw || projected ? -1 : sweep_r_only_sub(ws);   // (the zero-w variant of the kernel has no R-only form)
     // objective by projection: psi is in W already and nobody reads the first stage's z': ITS last sub-stage is the R-only one
     const bool first_stage_r_only = projected && ws->proj_y0_ready && ws->r_only_enabled && p.h_stages[0].nsubs >= 2 &&
