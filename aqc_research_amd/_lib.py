@@ -25,6 +25,7 @@ SIGNATURES = {
     "aqc_version": (c_char_p, []),
     "aqc_last_error": (c_char_p, []),
     "aqc_device_count": (c_int, []),
+    "aqc_live_buffers": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
     "aqc_create": (c_int, [c_int, c_int, POINTER(c_int32), c_int, c_int, c_int, POINTER(_P)]),
     "aqc_destroy": (c_int, [_P]),
     "aqc_num_thetas": (c_int, [_P]),

@@ -43,40 +43,6 @@ int check_block_range(const aqc_ws* ws, int block_from, int block_to) {
     return 0;
 }
 
-int ensure_small(aqc_ws* ws, size_t n_cplx) {
-    if (n_cplx <= ws->small_cap) return 0;
-    if (ws->d_small) HIP_OK(hipFree(ws->d_small));
-    ws->d_small = nullptr;
-    HIP_OK(hipMalloc((void**)&ws->d_small, n_cplx * sizeof(double2)));
-    ws->small_cap = n_cplx;
-    return 0;
-}
-
-int ensure_tmp(aqc_ws* ws, size_t n_index, size_t n_cplx) {
-    if (n_index > ws->tmp_index_cap) {
-        if (ws->d_tmp_index) HIP_OK(hipFree(ws->d_tmp_index));
-        ws->d_tmp_index = nullptr;
-        HIP_OK(hipMalloc((void**)&ws->d_tmp_index, n_index * sizeof(long long)));
-        ws->tmp_index_cap = n_index;
-    }
-    if (n_cplx > ws->tmp_small_cap) {
-        if (ws->d_tmp_small) HIP_OK(hipFree(ws->d_tmp_small));
-        ws->d_tmp_small = nullptr;
-        HIP_OK(hipMalloc((void**)&ws->d_tmp_small, n_cplx * sizeof(double2)));
-        ws->tmp_small_cap = n_cplx;
-    }
-    return 0;
-}
-
-int ensure_index(aqc_ws* ws, size_t n) {
-    if (n <= ws->index_cap) return 0;
-    if (ws->d_index) HIP_OK(hipFree(ws->d_index));
-    ws->d_index = nullptr;
-    HIP_OK(hipMalloc((void**)&ws->d_index, n * sizeof(long long)));
-    ws->index_cap = n;
-    return 0;
-}
-
 int ensure_coef(aqc_ws* ws) {
     if (ws->coef_valid) return 0;
     return fail("thetas have not been uploaded (aqc_ws_set_thetas)");
@@ -124,6 +90,12 @@ extern "C" {
 
 const char* aqc_version(void) { return "aqc_hip 0.1.0 (gfx950)"; }
 const char* aqc_last_error(void) { return g_error.c_str(); }
+
+int aqc_live_buffers(int64_t* device, int64_t* pinned) {
+    if (device) *device = g_live_device.load();
+    if (pinned) *pinned = g_live_pinned.load();
+    return 0;
+}
 
 int aqc_device_count(void) {
     int ndev = 0;
@@ -228,34 +200,13 @@ int aqc_plan_substages(aqc_ctx* ctx, int ncols, int which, int tile_bits, int lo
     return 0;
 }
 
-int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_apply, int tile_bits_sweep, aqc_ws** out) {
-    if (!out) return fail("out pointer is null");
-    *out = nullptr;
-    if (!ctx) return fail("null context");
-    if (batch < 1 || batch > 65535) return fail("batch must be in [1, 65535] (lanes are the y dimension of the launch grid)");
-    if (ncols < 1) return fail("ncols must be >= 1");
-    const Program& prog = ctx->prog;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-        return fail("no HIP device available (%s): the aqc_hip path needs an AMD GPU and has no CPU fallback",
-                    e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
-    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
-    HIP_OK(hipSetDevice(device));
-    HIP_OK(init_kernels());
-    HIP_OK(init_kernels2());
-    HIP_OK(init_kernels3());
+// ---- aqc_ws_create in three parts: what the host decides, the slot tables, the device side ----------------------------
 
-    aqc_ws* ws = new aqc_ws();
-    ws->ctx = ctx;
-    ws->device = device;
-    ws->batch = batch;
-    ws->ncols = ncols;
-    ws->col_bits = ceil_log2(ncols);
-    ws->pitch = 1 << ws->col_bits;
-    ws->nbits = ws->col_bits + prog.n;
-    if (ws->nbits > kMaxBits) { delete ws; return fail("2^%d elements per lane is beyond this build's limit", ws->nbits); }
-    ws->lane_elems = (size_t)1 << ws->nbits;
+// Host only: kernel family, tile sizes, the three plans (lowered once per shape in the context's cache), the switches
+static int ws_decide(aqc_ws* ws, int tile_bits_apply, int tile_bits_sweep) {
+    aqc_ctx* ctx = ws->ctx;
+    const Program& prog = ctx->prog;
+    const int batch = ws->batch;
     // Kernel family and tile size.  Throughput regime (enough tiles x lanes to give every CU >= 1 workgroup of
     // the largest tile): register-blocked kernels on 2^12 / 2^13 tiles.  Latency regime (few lanes): the
     // per-gate-group kernels on small tiles, where all threads of a workgroup share every gate group and the
@@ -269,7 +220,7 @@ int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_
     // AQC_KERNEL_FAMILY = 1 (per-group) | 2 (register-blocked VALU) | 3 forces a family (tests run every family);
     // AQC_KERNEL_V2 = 0 / 1 is the older spelling of 1 / 2.
     const int family = env_int("AQC_KERNEL_FAMILY", env_int("AQC_KERNEL_V2", -1) >= 0 ? env_int("AQC_KERNEL_V2", -1) + 1 : 0);
-    if (family < 0 || family > 3) { delete ws; return fail("AQC_KERNEL_FAMILY must be 1 (per-group), 2 (register-blocked) or 3 (matrix cores)"); }
+    if (family < 0 || family > 3) return fail("AQC_KERNEL_FAMILY must be 1 (per-group), 2 (register-blocked) or 3 (matrix cores)");
     const bool want_v3 = (family == 3 || family == 0) && ws->nbits >= 8;
     const int force_v2 = family == 3 ? 0 : (family ? family - 1 : -1);
     // Measured on MI355X (tools/tune.py mid / b1k): the register-blocked kernels pay off once 2^12-amplitude tiles x
@@ -299,7 +250,7 @@ int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_
     ks = std::min(std::min(ks, 12), ws->nbits);
     ws->threads = env_int("AQC_THREADS", 0);
     if (ws->threads <= 0) ws->threads = std::min(256, std::max(64, 1 << (std::min(ka, ks) - 2)));
-    if (ws->threads < 64 || ws->threads > 512 || ws->threads % 64) { delete ws; return fail("AQC_THREADS must be a multiple of 64 in [64, 512]"); }
+    if (ws->threads < 64 || ws->threads > 512 || ws->threads % 64) return fail("AQC_THREADS must be a multiple of 64 in [64, 512]");
 
     // fewest launches wins; among equals prefer the longer contiguous HBM runs (more forced low bits)
     auto best_plan = [&](int k, bool inverse) {
@@ -311,35 +262,31 @@ int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_
         return best;
     };
     if (want_v3) { ka = std::min(std::max(ka, 8), 12); ks = std::max(ks, 8); }   // MFMA tiles: 2^8 .. 2^12 amplitudes
-    auto cached_plan = [&](int which, int k, bool inverse, int reg_bits, bool dots, DevPlan& out) {
-        const std::vector<int> key = {which, ws->col_bits, k, low_bits, reg_bits, (int)dots, (int)want_v3};
-        std::lock_guard<std::mutex> lock(ctx->mu);
+    // the workspace's plan: the host part of the cached one, lowered by `lower` on a miss
+    auto cached = [&](const std::vector<int>& key, DevPlan& out, const std::function<void(HostPlan&)>& lower) {
+        std::lock_guard<std::recursive_mutex> lock(ctx->mu);
         auto it = ctx->plan_cache.find(key);
         if (it == ctx->plan_cache.end()) {
-            DevPlan fresh;
-            lower_plan(prog, best_plan(k, inverse), fresh, reg_bits, dots, want_v3);
+            HostPlan fresh;
+            lower(fresh);
             it = ctx->plan_cache.emplace(key, std::move(fresh)).first;
         }
-        out = it->second;   // host vectors copied; device pointers are null in the cache
+        out = it->second;
+    };
+    auto cached_plan = [&](int which, int k, bool inverse, int reg_bits, bool dots, DevPlan& out) {
+        cached({which, ws->col_bits, k, low_bits, reg_bits, (int)dots, (int)want_v3}, out,
+               [&](HostPlan& fresh) { lower_plan(prog, best_plan(k, inverse), fresh, reg_bits, dots, want_v3); });
     };
     cached_plan(2, ka, false, (want_v2 || want_v3) ? 4 : 0, false, ws->fwd);
     cached_plan(1, ks, false, want_v3 ? 4 : (want_v2 ? (env_int("AQC_SWEEP_REG_BITS", 4) == 3 ? 3 : 4) : 0), true, ws->sweep);
     // V^H: on the matrix-core path with equal tile sizes, the SWEEP's plan walked backwards (same stages, same sub-stages, same
     // cost), so that the states between its stages are the states z takes between the sweep's stages -- see aqc_ws_sweep.cpp
     ws->inv_mirrored = want_v3 && ka == ks && ws->sweep.v3 && ws->sweep.plan.stages.size() >= 2 && env_int("AQC_MIRROR_PLAN", 1) != 0;
-    if (ws->inv_mirrored) {
-        const std::vector<int> key = {3, ws->col_bits, ks, low_bits, 4, 0, 1};
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        auto it = ctx->plan_cache.find(key);
-        if (it == ctx->plan_cache.end()) {
-            DevPlan fresh;
-            lower_plan(prog, mirror_plan(ws->sweep.plan), fresh, 4, false, true, true);
-            it = ctx->plan_cache.emplace(key, std::move(fresh)).first;
-        }
-        ws->inv = it->second;
-    } else {
+    if (ws->inv_mirrored)
+        cached({3, ws->col_bits, ks, low_bits, 4, 0, 1}, ws->inv,
+               [&](HostPlan& fresh) { lower_plan(prog, mirror_plan(ws->sweep.plan), fresh, 4, false, true, true); });
+    else
         cached_plan(0, ka, true, (want_v2 || want_v3) ? 4 : 0, false, ws->inv);
-    }
     ws->sparse_enabled = env_int("AQC_SPARSE_SWEEP", 1) != 0;
     ws->sparse_min_items = env_int("AQC_SPARSE_MIN_ITEMS", 512);
     ws->lazy_z_enabled = env_int("AQC_LAZY_Z", 1) != 0;
@@ -352,17 +299,32 @@ int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_
     ws->skipw_enabled = env_int("AQC_SKIP_ZERO_W", 0) != 0;   // (measured slower than multiplying the zeros: opt-in, see sweep_mfma_kernel)
     for (DevPlan* p : {&ws->fwd, &ws->inv, &ws->sweep}) {
         const std::string err = check_plan(prog, p->plan);
-        if (!err.empty()) { delete ws; return fail("planner produced an invalid plan: %s", err.c_str()); }
+        if (!err.empty()) return fail("planner produced an invalid plan: %s", err.c_str());
     }
     proj_plan(ws, low_bits);   // the sweep's later stages on a virtual register, where the plan allows (aqc_ws_project.cpp)
+    if (env_int("AQC_VERBOSE", 0) && want_v3)
+        fprintf(stderr, "aqc_hip: matrix-core kernels, tiles 2^%d (V / V^H, %d workgroups per CU) / 2^%d (sweep, %d per CU), sub-stages %zu / %zu / %zu\n",
+                ws->inv.k, mfma_occupancy(ws->inv.k, false), ws->sweep.k, mfma_occupancy(ws->sweep.k, true), ws->fwd.h_subs3.size(),
+                ws->inv.h_subs3.size(), ws->sweep.h_subs3.size());
+    return 0;
+}
 
+// Host only: the partial-sum slots of every theta (two at most), the theta of every slot where that is one to one, tiles per slot
+struct SlotTables {
+    std::vector<int> theta_slots, slot_theta, slot_ntiles;
+    int partial_tiles = 1;
+};
+static SlotTables ws_slot_tables(aqc_ws* ws) {
+    const Program& prog = ws->ctx->prog;
     const int T = prog.num_thetas();
     const int G = (int)prog.groups.size();
     ws->nslots = G * kSlotsPerGroup;
-    const int partial_tiles = ws->sweep.v3 ? 1 : ws->sweep.ntiles;   // family 3: rgrad_kernel writes one value per slot
-    std::vector<int> theta_slots(2 * (size_t)std::max(T, 1), -1), slot_ntiles((size_t)std::max(ws->nslots, 1), partial_tiles);
+    SlotTables t;
+    t.partial_tiles = ws->sweep.v3 ? 1 : ws->sweep.ntiles;   // family 3: rgrad_kernel writes one value per slot
+    t.theta_slots.assign(2 * (size_t)std::max(T, 1), -1);
+    t.slot_ntiles.assign((size_t)std::max(ws->nslots, 1), t.partial_tiles);
     auto feed = [&](int theta, int slot) {
-        if (theta_slots[2 * theta] < 0) theta_slots[2 * theta] = slot; else theta_slots[2 * theta + 1] = slot;
+        if (t.theta_slots[2 * theta] < 0) t.theta_slots[2 * theta] = slot; else t.theta_slots[2 * theta + 1] = slot;
     };
     for (int gi = 0; gi < G; ++gi) {
         const GateGroup& g = prog.groups[gi];
@@ -374,128 +336,127 @@ int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_
             for (int d = 0; d < prog.tpb; ++d) feed(g.theta0 + d, gi * kSlotsPerGroup + d);
         }
     }
-
-    std::vector<int> slot_theta((size_t)std::max(ws->nslots, 1), -1);
+    t.slot_theta.assign((size_t)std::max(ws->nslots, 1), -1);
     ws->grads_direct = ws->sweep.v3 && T > 0 && env_int("AQC_GRADS_DIRECT", 1) != 0;
-    for (int t = 0; t < T; ++t) {
-        if (theta_slots[2 * t] < 0 || theta_slots[2 * t + 1] >= 0) { ws->grads_direct = false; break; }
-        slot_theta[theta_slots[2 * t]] = t;
+    for (int th = 0; th < T; ++th) {
+        if (t.theta_slots[2 * th] < 0 || t.theta_slots[2 * th + 1] >= 0) { ws->grads_direct = false; break; }
+        t.slot_theta[t.theta_slots[2 * th]] = th;
     }
-    if (env_int("AQC_VERBOSE", 0) && want_v3)
-        fprintf(stderr, "aqc_hip: matrix-core kernels, tiles 2^%d (V / V^H, %d workgroups per CU) / 2^%d (sweep, %d per CU), sub-stages %zu / %zu / %zu\n",
-                ws->inv.k, mfma_occupancy(ws->inv.k, false), ws->sweep.k, mfma_occupancy(ws->sweep.k, true), ws->fwd.h_subs3.size(),
-                ws->inv.h_subs3.size(), ws->sweep.h_subs3.size());
-#define WS_TRY(x) do { if ((x) != 0) { aqc_ws_destroy(ws); return 1; } } while (0)
-#define WS_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fail("%s failed: %s", #x, hipGetErrorString(e_)); aqc_ws_destroy(ws); return 1; } } while (0)
-    WS_HIP(hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking));
-    WS_HIP(hipEventCreate(&ws->ev0)); WS_HIP(hipEventCreate(&ws->ev1));
-    WS_HIP(hipEventCreate(&ws->pev0)); WS_HIP(hipEventCreate(&ws->pev1));
-    WS_TRY(upload_plan(ws->fwd)); WS_TRY(upload_plan(ws->inv)); WS_TRY(upload_plan(ws->sweep));
-    WS_TRY(proj_alloc(ws));
-    WS_HIP(hipMalloc((void**)&ws->d_thetas_own, sizeof(double) * (size_t)batch * std::max(T, 1)));
-    ws->d_thetas = ws->d_thetas_own;
-    WS_HIP(hipMalloc((void**)&ws->d_coef, sizeof(double) * (size_t)batch * (prog.n + prog.num_blocks + 1) * kCoefStride));
-    for (int b = 0; b < AQC_NUM_BUFS; ++b) {
-        WS_HIP(hipMalloc((void**)&ws->bufs[b], sizeof(double2) * (size_t)batch * ws->lane_elems));
-        WS_HIP(hipMemsetAsync(ws->bufs[b], 0, sizeof(double2) * (size_t)batch * ws->lane_elems, ws->stream));
-    }
-    WS_HIP(hipMalloc((void**)&ws->d_partial, sizeof(double2) * (size_t)batch * std::max(ws->nslots, 1) * partial_tiles));
-    for (DevPlan* p : {&ws->fwd, &ws->inv, &ws->sweep})
-        if (p->v3) WS_HIP(hipMalloc((void**)&p->d_umat, sizeof(double) * (size_t)batch * std::max<size_t>(p->h_subs3.size(), 1) * 12 * 64));
-    {
-        // [V^H | sweep | virtual sweep | V]; with the mirrored V^H plan the sweep's jobs write V^H's operands as well (sub-stage s of the
-        // sweep is sub-stage nsubs - 1 - s of V^H, conjugate-transposed) and V^H gets no jobs of its own
-        std::vector<UJob> jobs, route_jobs;
-        size_t n_vdag_sweep = 0;   // jobs of [V^H | sweep | virtual sweep]: what a reader of everything launches (V's jobs run on their own)
-        DevPlan* vsw = ws->proj.ok ? &ws->proj.vsw : nullptr;
-        const int nsw = ws->sweep.v3 ? (int)ws->sweep.h_subs3.size() : 0;
-        ws->ujobs_mirror = ws->inv_mirrored && ws->inv.v3 && (int)ws->inv.h_subs3.size() == nsw && env_int("AQC_UBUILD_MIRROR", 1) != 0;
-        for (DevPlan* p : {&ws->inv, &ws->sweep, vsw, &ws->fwd})
-            if (p && p->v3)
-                for (size_t i = 0; i < p->h_subs3.size(); ++i) {
-                    if (p == &ws->inv && ws->ujobs_mirror) continue;
-                    UJob j{p->d_subs3 + i, p->d_grps, p->d_umat, (int)i, (int)p->h_subs3.size(), p->plan.inverse ? 1 : 0, prog.entangler, nullptr, 0, 0};
-                    if (p == &ws->sweep && ws->ujobs_mirror) { j.umat_mirror = ws->inv.d_umat; j.mirror_index = nsw - 1 - (int)i; j.mirror_nsubs = nsw; }
-                    if (p == vsw) {   // the virtual plan walked backwards takes its operands from the same jobs
-                        const int nvs = (int)vsw->h_subs3.size();
-                        j.umat_mirror = ws->proj.vinv.d_umat; j.mirror_index = nvs - 1 - (int)i; j.mirror_nsubs = nvs;
-                    }
-                    jobs.push_back(j);
-                    if (p != &ws->fwd) ++n_vdag_sweep;
-                    // what the objective-by-projection route reads: V^H's last stage (= the sweep's first, mirrored), the sweep's first, the virtual plans
-                    if (vsw && ((p == &ws->inv && (int)i >= p->h_stages.back().sub_begin) || (p == &ws->sweep && (int)i < p->h_stages[0].nsubs) || p == vsw))
-                        route_jobs.push_back(j);
+    return t;
+}
+
+// The U builder's job lists (family 3), once the plans' tables and operand buffers have their addresses
+static int ws_upload_ujobs(aqc_ws* ws) {
+    const Program& prog = ws->ctx->prog;
+    // [V^H | sweep | virtual sweep | V]; with the mirrored V^H plan the sweep's jobs write V^H's operands as well (sub-stage s of the
+    // sweep is sub-stage nsubs - 1 - s of V^H, conjugate-transposed) and V^H gets no jobs of its own
+    std::vector<UJob> jobs, route_jobs;
+    size_t n_vdag_sweep = 0;   // jobs of [V^H | sweep | virtual sweep]: what a reader of everything launches (V's jobs run on their own)
+    DevPlan* vsw = ws->proj.ok ? &ws->proj.vsw : nullptr;
+    const int nsw = ws->sweep.v3 ? (int)ws->sweep.h_subs3.size() : 0;
+    ws->ujobs_mirror = ws->inv_mirrored && ws->inv.v3 && (int)ws->inv.h_subs3.size() == nsw && env_int("AQC_UBUILD_MIRROR", 1) != 0;
+    for (DevPlan* p : {&ws->inv, &ws->sweep, vsw, &ws->fwd})
+        if (p && p->v3)
+            for (size_t i = 0; i < p->h_subs3.size(); ++i) {
+                if (p == &ws->inv && ws->ujobs_mirror) continue;
+                UJob j{p->d_subs3 + i, p->d_grps, p->d_umat, (int)i, (int)p->h_subs3.size(), p->plan.inverse ? 1 : 0, prog.entangler, nullptr, 0, 0};
+                if (p == &ws->sweep && ws->ujobs_mirror) { j.umat_mirror = ws->inv.d_umat; j.mirror_index = nsw - 1 - (int)i; j.mirror_nsubs = nsw; }
+                if (p == vsw) {   // the virtual plan walked backwards takes its operands from the same jobs
+                    const int nvs = (int)vsw->h_subs3.size();
+                    j.umat_mirror = ws->proj.vinv.d_umat; j.mirror_index = nvs - 1 - (int)i; j.mirror_nsubs = nvs;
                 }
-        if (vsw && !route_jobs.empty() && route_jobs.size() < n_vdag_sweep && env_int("AQC_UBUILD_SUBSET", 1) != 0) {
-            WS_HIP(hipMalloc((void**)&ws->d_ujobs_route, sizeof(UJob) * route_jobs.size()));
-            WS_HIP(hipMemcpy(ws->d_ujobs_route, route_jobs.data(), sizeof(UJob) * route_jobs.size(), hipMemcpyHostToDevice));
-            ws->n_ujobs_route = (int)route_jobs.size();
-        }
-        if (!jobs.empty()) {
-            WS_HIP(hipMalloc((void**)&ws->d_ujobs, sizeof(UJob) * jobs.size()));
-            WS_HIP(hipMemcpy(ws->d_ujobs, jobs.data(), sizeof(UJob) * jobs.size(), hipMemcpyHostToDevice));
-        }
+                jobs.push_back(j);
+                if (p != &ws->fwd) ++n_vdag_sweep;
+                // what the objective-by-projection route reads: V^H's last stage (= the sweep's first, mirrored), the sweep's first, the virtual plans
+                if (vsw && ((p == &ws->inv && (int)i >= p->h_stages.back().sub_begin) || (p == &ws->sweep && (int)i < p->h_stages[0].nsubs) || p == vsw))
+                    route_jobs.push_back(j);
+            }
+    if (vsw && !route_jobs.empty() && route_jobs.size() < n_vdag_sweep && env_int("AQC_UBUILD_SUBSET", 1) != 0) {
+        if (ws->d_ujobs_route.upload(route_jobs)) return 1;
+        ws->n_ujobs_route = (int)route_jobs.size();
     }
-    if (ws->sweep.v3)
-        WS_HIP(hipMalloc((void**)&ws->sweep.d_rpart, sizeof(double2) * (size_t)batch * std::max<size_t>(ws->sweep.h_subs3.size(), 1) *
-                                                        sweep3_nparts(ws->sweep.ntiles, batch, ws->sweep.k) * 256));
-    WS_HIP(hipMalloc((void**)&ws->d_grads, sizeof(double2) * (size_t)batch * std::max(T, 1)));
-    WS_HIP(hipMalloc((void**)&ws->d_theta_slots, sizeof(int) * theta_slots.size()));
-    WS_HIP(hipMalloc((void**)&ws->d_slot_ntiles, sizeof(int) * slot_ntiles.size()));
-    WS_HIP(hipMemcpy(ws->d_theta_slots, theta_slots.data(), sizeof(int) * theta_slots.size(), hipMemcpyHostToDevice));
-    WS_HIP(hipMalloc((void**)&ws->d_slot_theta, sizeof(int) * slot_theta.size()));
-    WS_HIP(hipMemcpy(ws->d_slot_theta, slot_theta.data(), sizeof(int) * slot_theta.size(), hipMemcpyHostToDevice));
-    WS_HIP(hipMemcpy(ws->d_slot_ntiles, slot_ntiles.data(), sizeof(int) * slot_ntiles.size(), hipMemcpyHostToDevice));
-    ws->pin_thetas = (size_t)batch * std::max(T, 1);
-    ws->pin_grads = 2 * (size_t)batch * std::max(T, 1);
-    ws->pin_small = 2 * (size_t)batch * 64;
-    WS_HIP(hipHostMalloc((void**)&ws->h_pin, sizeof(double) * (ws->pin_thetas + ws->pin_grads + ws->pin_small), hipHostMallocDefault));
-    ws->vdot_parts = (int)std::min<size_t>(1024, std::max<size_t>(1, ws->lane_elems / 1024));
-    WS_HIP(hipMalloc((void**)&ws->d_vdot_part, sizeof(double2) * (size_t)batch * ws->vdot_parts));
-    WS_HIP(hipStreamSynchronize(ws->stream));
-#undef WS_TRY
-#undef WS_HIP
-    *out = ws;
+    if (!jobs.empty() && ws->d_ujobs.upload(jobs)) return 1;
     return 0;
 }
 
+// The device side: streams, events and every buffer a workspace holds from its creation on (the rest is allocated at first use)
+static int ws_device_side(aqc_ws* ws, const SlotTables& t) {
+    const Program& prog = ws->ctx->prog;
+    const size_t B = (size_t)ws->batch, T1 = (size_t)std::max(prog.num_thetas(), 1), lanes = B * ws->lane_elems;
+    HIP_OK(hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking));
+    HIP_OK(hipEventCreate(&ws->ev0)); HIP_OK(hipEventCreate(&ws->ev1));
+    HIP_OK(hipEventCreate(&ws->pev0)); HIP_OK(hipEventCreate(&ws->pev1));
+    if (upload_plan(ws->fwd) || upload_plan(ws->inv) || upload_plan(ws->sweep) || proj_alloc(ws)) return 1;
+    if (ws->d_thetas_own.alloc(B * T1)) return 1;
+    ws->d_thetas = ws->d_thetas_own;
+    if (ws->d_coef.alloc(B * (prog.n + prog.num_blocks + 1) * kCoefStride)) return 1;
+    for (auto& buf : ws->bufs) {
+        if (buf.alloc(lanes)) return 1;
+        HIP_OK(hipMemsetAsync(buf, 0, sizeof(double2) * lanes, ws->stream));
+    }
+    if (ws->d_partial.alloc(B * std::max(ws->nslots, 1) * t.partial_tiles)) return 1;
+    for (DevPlan* p : {&ws->fwd, &ws->inv, &ws->sweep})
+        if (p->v3 && p->d_umat.alloc(B * std::max<size_t>(p->h_subs3.size(), 1) * 12 * 64)) return 1;
+    if (ws_upload_ujobs(ws)) return 1;
+    if (ws->sweep.v3 && ws->sweep.d_rpart.alloc(B * std::max<size_t>(ws->sweep.h_subs3.size(), 1) *
+                                                sweep3_nparts(ws->sweep.ntiles, ws->batch, ws->sweep.k) * 256)) return 1;
+    if (ws->d_grads.alloc(B * T1)) return 1;
+    if (ws->d_theta_slots.upload(t.theta_slots) || ws->d_slot_ntiles.upload(t.slot_ntiles) || ws->d_slot_theta.upload(t.slot_theta)) return 1;
+    ws->pin_thetas = B * T1;
+    ws->pin_grads = 2 * B * T1;
+    ws->pin_small = 2 * B * 64;
+    if (ws->h_pin.alloc(ws->pin_thetas + ws->pin_grads + ws->pin_small)) return 1;
+    ws->vdot_parts = (int)std::min<size_t>(1024, std::max<size_t>(1, ws->lane_elems / 1024));
+    if (ws->d_vdot_part.alloc(B * ws->vdot_parts)) return 1;
+    HIP_OK(hipStreamSynchronize(ws->stream));
+    return 0;
+}
 
+int aqc_ws_create(aqc_ctx* ctx, int device, int batch, int ncols, int tile_bits_apply, int tile_bits_sweep, aqc_ws** out) {
+    if (!out) return fail("out pointer is null");
+    *out = nullptr;
+    if (!ctx) return fail("null context");
+    if (batch < 1 || batch > 65535) return fail("batch must be in [1, 65535] (lanes are the y dimension of the launch grid)");
+    if (ncols < 1) return fail("ncols must be >= 1");
+    const Program& prog = ctx->prog;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return fail("no HIP device available (%s): the aqc_hip path needs an AMD GPU and has no CPU fallback",
+                    e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
+    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(init_kernels());
+    HIP_OK(init_kernels2());
+    HIP_OK(init_kernels3());
+
+    struct Destroy { void operator()(aqc_ws* w) const { aqc_ws_destroy(w); } };
+    std::unique_ptr<aqc_ws, Destroy> ws(new aqc_ws());   // every early return below tears down what exists so far
+    ws->ctx = ctx;
+    ws->device = device;
+    ws->batch = batch;
+    ws->ncols = ncols;
+    ws->col_bits = ceil_log2(ncols);
+    ws->pitch = 1 << ws->col_bits;
+    ws->nbits = ws->col_bits + prog.n;
+    if (ws->nbits > kMaxBits) return fail("2^%d elements per lane is beyond this build's limit", ws->nbits);
+    ws->lane_elems = (size_t)1 << ws->nbits;
+    if (ws_decide(ws.get(), tile_bits_apply, tile_bits_sweep)) return 1;
+    if (ws_device_side(ws.get(), ws_slot_tables(ws.get()))) return 1;
+    *out = ws.release();
+    return 0;
+}
+
+// Order: nothing in flight (the streams), nothing that holds addresses (the graphs), then events and streams; the buffers go last,
+// with the workspace (the destructors of its members)
 int aqc_ws_destroy(aqc_ws* ws) {
     if (!ws) return 0;
     (void)hipSetDevice(ws->device);
-    if (ws->stream) (void)hipStreamSynchronize(ws->stream);
+    for (hipStream_t s : {ws->stream, ws->copy_stream, ws->mps_stream}) if (s) (void)hipStreamSynchronize(s);
     drop_graphs(ws);
-    proj_free(ws);
-    for (DevPlan* p : {&ws->fwd, &ws->inv, &ws->sweep}) free_plan(*p);
-    void* ptrs[] = {ws->d_thetas_own, ws->d_theta_bank, ws->d_coef, ws->d_partial, ws->d_grads, ws->d_small, ws->d_vdot_part, ws->d_index, ws->d_tmp_index, ws->d_tmp_small,
-                    ws->d_theta_slots, ws->d_slot_theta, ws->d_slot_ntiles, ws->d_basis_index, ws->d_vdot_out, ws->d_ujobs, ws->d_ujobs_route};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (int b = 0; b < AQC_NUM_BUFS; ++b) if (ws->bufs[b]) (void)hipFree(ws->bufs[b]);
-    for (int b = 0; b < AQC_NUM_BUFS; ++b) if (ws->d_combo_prev[b]) (void)hipFree(ws->d_combo_prev[b]);
-    for (void* q : {(void*)ws->d_sw_items, (void*)ws->d_sw_clear, (void*)ws->d_sw_counts, (void*)ws->d_sw_lane_parts, (void*)ws->d_sw_prev_tiles,
-                    (void*)ws->w2, (void*)ws->zw2, (void*)ws->d_vd_items})
-        if (q) (void)hipFree(q);
-    if (ws->d_sur) (void)hipFree(ws->d_sur);
-    if (ws->d_sur_real) (void)hipFree(ws->d_sur_real);
-    if (ws->h_sur) (void)hipHostFree(ws->h_sur);
-    if (ws->d_combo_index) (void)hipFree(ws->d_combo_index);
-    if (ws->d_combo_coef) (void)hipFree(ws->d_combo_coef);
-    if (ws->h_pin) (void)hipHostFree(ws->h_pin);
-    for (auto& m : ws->mps) if (m.d_t) (void)hipFree(m.d_t);
-    if (ws->d_mps_scratch) (void)hipFree(ws->d_mps_scratch);
-    for (auto& t : ws->mps_tabs) if (t.dev) (void)hipFree(t.dev);
-    if (ws->d_cd_prog) (void)hipFree(ws->d_cd_prog);
-    if (ws->d_cd_thetas) (void)hipFree(ws->d_cd_thetas);
-    if (ws->d_cd_fobj) (void)hipFree(ws->d_cd_fobj);
-    if (ws->d_mps_lam) (void)hipFree(ws->d_mps_lam);
-    for (void* q : {(void*)ws->sk.target, (void*)ws->sk.qr_part, (void*)ws->sk.qr_rinv, (void*)ws->sk.tmp, (void*)ws->sk.status, (void*)ws->sk.idx,
-                    (void*)ws->sk.adam, (void*)ws->sk.adam_i, (void*)ws->sk.profile})
-        if (q) (void)hipFree(q);
-    for (hipEvent_t ev : {ws->ev0, ws->ev1, ws->pev0, ws->pev1, ws->ev_ready, ws->ev_copied}) if (ev) (void)hipEventDestroy(ev);
-    if (ws->copy_stream) { (void)hipStreamSynchronize(ws->copy_stream); (void)hipStreamDestroy(ws->copy_stream); }
-    if (ws->mps_stream) { (void)hipStreamSynchronize(ws->mps_stream); (void)hipStreamDestroy(ws->mps_stream); }
-    for (hipEvent_t ev : {ws->ev_mps_fork, ws->ev_mps_join}) if (ev) (void)hipEventDestroy(ev);
-    if (ws->stream) (void)hipStreamDestroy(ws->stream);
+    for (hipEvent_t ev : {ws->ev0, ws->ev1, ws->pev0, ws->pev1, ws->ev_ready, ws->ev_copied, ws->ev_mps_fork, ws->ev_mps_join})
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipStream_t s : {ws->copy_stream, ws->mps_stream, ws->stream}) if (s) (void)hipStreamDestroy(s);
     delete ws;
     return 0;
 }
@@ -579,7 +540,7 @@ int aqc_ws_set_basis(aqc_ws* ws, int buf, const int64_t* index) {
         if (index[b] < 0 || index[b] >= dim) return fail("basis index out of range");
         elem[b] = (long long)index[b] << ws->col_bits;
     }
-    if (!ws->d_basis_index) HIP_OK(hipMalloc((void**)&ws->d_basis_index, sizeof(long long) * ws->batch));
+    if (ws->d_basis_index.reserve(ws->batch)) return 1;
     HIP_OK(hipMemcpyAsync(ws->d_basis_index, elem.data(), sizeof(long long) * ws->batch, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
     HIP_OK(hipMemsetAsync(ws->bufs[buf], 0, sizeof(double2) * (size_t)ws->batch * ws->lane_elems, ws->stream));
@@ -591,7 +552,7 @@ int aqc_ws_set_basis(aqc_ws* ws, int buf, const int64_t* index) {
     // absent), so that a later set_combo clears one element per lane instead of the buffer and the sweep knows the support
     std::vector<long long> supp(2 * (size_t)ws->batch, -1);
     for (int b = 0; b < ws->batch; ++b) supp[2 * (size_t)b] = elem[b];
-    if (!ws->d_combo_prev[buf]) HIP_OK(hipMalloc((void**)&ws->d_combo_prev[buf], sizeof(long long) * 2 * ws->batch));
+    if (ws->d_combo_prev[buf].reserve(2 * (size_t)ws->batch)) return 1;
     HIP_OK(hipMemcpyAsync(ws->d_combo_prev[buf], supp.data(), sizeof(long long) * supp.size(), hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
     std::vector<double> coef(4 * (size_t)ws->batch, 0.0);
@@ -634,9 +595,8 @@ int aqc_ws_set_combo(aqc_ws* ws, int buf, const int64_t* index, const double* co
     // the same combination as the buffer already holds (an objective hands the same lhs state in on every call): nothing to do
     std::vector<double> cf(coef, coef + 4 * (size_t)B);
     if (ws->combo_valid[buf] && ws->combo_last_elem[buf] == elem && ws->combo_last_coef[buf] == cf) return 0;
-    if (!ws->d_combo_index) HIP_OK(hipMalloc((void**)&ws->d_combo_index, sizeof(long long) * 2 * B));
-    if (!ws->d_combo_coef) HIP_OK(hipMalloc((void**)&ws->d_combo_coef, sizeof(double2) * 2 * B));
-    if (!ws->d_combo_prev[buf]) HIP_OK(hipMalloc((void**)&ws->d_combo_prev[buf], sizeof(long long) * 2 * B));   // (combo_valid is false without it)
+    if (ws->d_combo_index.reserve(2 * (size_t)B) || ws->d_combo_coef.reserve(2 * (size_t)B)) return 1;
+    if (ws->d_combo_prev[buf].reserve(2 * (size_t)B)) return 1;   // (combo_valid is false without it)
     HIP_OK(hipMemcpyAsync(ws->d_combo_index, elem.data(), sizeof(long long) * 2 * B, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipMemcpyAsync(ws->d_combo_coef, coef, sizeof(double2) * 2 * B, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));   // `elem` and the caller's array may go away
@@ -671,7 +631,7 @@ int aqc_ws_gather(aqc_ws* ws, int buf, const int64_t* index, int count, double* 
         elem[i] = (long long)index[i] << ws->col_bits;
     }
     HIP_OK(hipStreamSynchronize(ws->stream));   // the temporaries may be re-allocated
-    if (ensure_tmp(ws, count, (size_t)ws->batch * count)) return 1;
+    if (ws->d_tmp_index.reserve(count) || ws->d_tmp_small.reserve((size_t)ws->batch * count)) return 1;
     HIP_OK(hipMemcpyAsync(ws->d_tmp_index, elem.data(), sizeof(long long) * count, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
     {
@@ -689,7 +649,7 @@ int aqc_ws_vdot(aqc_ws* ws, int buf_a, int buf_b, double* out) {
     HIP_OK(hipSetDevice(ws->device));
     if (before_read(ws, buf_a) || before_read(ws, buf_b)) return 1;
     HIP_OK(hipStreamSynchronize(ws->stream));
-    if (ensure_tmp(ws, 0, ws->batch)) return 1;
+    if (ws->d_tmp_small.reserve(ws->batch)) return 1;
     {
         ProfScope ps(ws, AQC_K_MISC);
         HIP_OK(launch_vdot(ws->bufs[buf_a], ws->bufs[buf_b], ws->lane_elems, ws->lane_elems, ws->batch, ws->d_vdot_part,
@@ -703,13 +663,12 @@ int aqc_ws_vdot(aqc_ws* ws, int buf_a, int buf_b, double* out) {
 int aqc_ws_theta_bank(aqc_ws* ws, const double* thetas, int nsets) {
     if (!ws || !thetas || nsets < 1) return fail("invalid theta bank arguments");
     HIP_OK(hipSetDevice(ws->device));
-    const size_t bytes = sizeof(double) * (size_t)nsets * ws->batch * std::max(ws->ctx->prog.num_thetas(), 1);
+    const size_t count = (size_t)nsets * ws->batch * std::max(ws->ctx->prog.num_thetas(), 1), bytes = sizeof(double) * count;
     HIP_OK(hipStreamSynchronize(ws->stream));
-    if (ws->d_theta_bank) HIP_OK(hipFree(ws->d_theta_bank));
-    ws->d_theta_bank = nullptr;
+    if (ws->d_theta_bank.release()) return 1;
     ws->bank_sets = 0;
     ws->d_thetas = ws->d_thetas_own;
-    HIP_OK(hipMalloc((void**)&ws->d_theta_bank, bytes));
+    if (ws->d_theta_bank.alloc(count)) return 1;
     HIP_OK(hipMemcpyAsync(ws->d_theta_bank, thetas, bytes, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
     ws->bank_sets = nsets;
@@ -734,13 +693,12 @@ int aqc_ws_gather_setup(aqc_ws* ws, const int64_t* index, int count) {
     }
     HIP_OK(hipStreamSynchronize(ws->stream));
     drop_graphs(ws);   // captured evaluations hold the old index / staging pointers
-    if (ensure_index(ws, count) || ensure_small(ws, (size_t)ws->batch * count)) return 1;
+    if (ws->d_index.reserve(count) || ws->d_small.reserve((size_t)ws->batch * count)) return 1;
     if (2 * (size_t)ws->batch * count > ws->pin_small) {   // aqc_ws_eval stages the gathered amplitudes in pinned memory
-        double* pin = nullptr;
         const size_t want = 2 * (size_t)ws->batch * count;
-        HIP_OK(hipHostMalloc((void**)&pin, sizeof(double) * (ws->pin_thetas + ws->pin_grads + want), hipHostMallocDefault));
-        if (ws->h_pin) HIP_OK(hipHostFree(ws->h_pin));
-        ws->h_pin = pin;
+        PinBuf<double> pin;   // (the old block stays until the new one exists)
+        if (pin.alloc(ws->pin_thetas + ws->pin_grads + want)) return 1;
+        ws->h_pin = std::move(pin);
         ws->pin_small = want;
     }
     HIP_OK(hipMemcpyAsync(ws->d_index, elem.data(), sizeof(long long) * count, hipMemcpyHostToDevice, ws->stream));
@@ -774,7 +732,7 @@ int aqc_ws_vdot_launch(aqc_ws* ws, int buf_a, int buf_b) {
     if (check_buf(ws, buf_a) || check_buf(ws, buf_b)) return 1;
     HIP_OK(hipSetDevice(ws->device));
     if (before_read(ws, buf_a) || before_read(ws, buf_b)) return 1;
-    if (!ws->d_vdot_out) HIP_OK(hipMalloc((void**)&ws->d_vdot_out, sizeof(double2) * ws->batch));
+    if (ws->d_vdot_out.reserve(ws->batch)) return 1;
     if (results_guard(ws)) return 1;
     ProfScope ps(ws, AQC_K_MISC);
     HIP_OK(launch_vdot(ws->bufs[buf_a], ws->bufs[buf_b], ws->lane_elems, ws->lane_elems, ws->batch, ws->d_vdot_part,
@@ -966,7 +924,7 @@ static int oneshot_ws(aqc_ctx* ctx, int ncols, aqc_ws** out) {
 
 static int oneshot_apply(aqc_ctx* ctx, const double* thetas, const double* src, double* dst, int ncols, int inverse) {
     if (!thetas || !src || !dst) return fail("null argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     aqc_ws* ws = nullptr;
     if (oneshot_ws(ctx, ncols, &ws)) return 1;
     if (aqc_ws_set_thetas(ws, thetas)) return 1;
@@ -997,7 +955,7 @@ int aqc_vdag_mul_mat(aqc_ctx* ctx, const double* thetas, double* mat, int ncols)
 static int oneshot_grad(aqc_ctx* ctx, const double* thetas, const double* x, const double* vh_y, int ncols, int from, int to,
                         int front, double* grad) {
     if (!thetas || !x || !vh_y || !grad) return fail("null argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     aqc_ws* ws = nullptr;
     if (oneshot_ws(ctx, ncols, &ws)) return 1;
     if (aqc_ws_set_thetas(ws, thetas)) return 1;

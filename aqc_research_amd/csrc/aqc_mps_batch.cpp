@@ -25,6 +25,7 @@
 
 #include "../../include/aqc_hip.h"
 #include "aqc_launch.h"
+#include "aqc_devbuf.h"
 #include "aqc_mps_host.h"
 
 using namespace aqc;
@@ -33,33 +34,29 @@ namespace {
 
 struct Lanes {   // L MPS of n sites, flat device storage with fixed strides; T_q = Gamma_q diag(lambda_q) like the single-lane engine
     int n = 0, L = 0, nb = 1;
-    char* base = nullptr;        // one allocation: T | lam | discarded | dims, so that a state is cloned by ONE copy
-    size_t bytes = 0;
+    DevBuf<char> base;           // one allocation: T | lam | discarded | dims, so that a state is cloned by ONE copy
     LaneMps dev{};
     int max_dim_in = 1;          // largest bond of what was loaded (host side)
     int alloc(int n_, int L_) {
         n = n_; L = L_; nb = std::max(n - 1, 1);
         const size_t t = sizeof(double2) * (size_t)L * n * kLaneSite, lam = sizeof(double) * (size_t)L * nb * kLaneCap;
         const size_t disc = sizeof(double) * (size_t)L, dims = sizeof(int) * (size_t)L * (n + 1);
-        bytes = t + lam + disc + dims;
-        HIP_OK(hipMalloc((void**)&base, bytes));
-        dev.T = base; dev.lam = reinterpret_cast<double*>(base + t); dev.discarded = reinterpret_cast<double*>(base + t + lam);
+        if (base.alloc(t + lam + disc + dims)) return 1;
+        dev.T = (char*)base; dev.lam = reinterpret_cast<double*>(base + t); dev.discarded = reinterpret_cast<double*>(base + t + lam);
         dev.dims = reinterpret_cast<int*>(base + t + lam + disc);
         dev.n = n; dev.pad = 0;
         return 0;
     }
     double2* site(int l, int q) const { return static_cast<double2*>(dev.T) + ((size_t)l * n + q) * kLaneSite; }
     double* lambda(int l, int b) const { return dev.lam + ((size_t)l * nb + b) * kLaneCap; }
-    void release() { if (base) (void)hipFree(base); base = nullptr; }
 };
 
 // the gates of V or V^H in levels of pairwise disjoint gates (apply_circuit_all below), cached per circuit
 struct Level { int off1, n1, off2, n2; };
 struct Schedule {
     std::vector<Level> levels;
-    LaneOp1* ops1 = nullptr;   // device tables, level after level
-    LaneOp2* ops2 = nullptr;
-    void release() { if (ops1) (void)hipFree(ops1); if (ops2) (void)hipFree(ops2); ops1 = nullptr; ops2 = nullptr; }
+    DevBuf<LaneOp1> ops1;      // device tables, level after level
+    DevBuf<LaneOp2> ops2;
 };
 
 }  // namespace
@@ -71,18 +68,17 @@ struct aqc_mpsb {
     Lanes bank;                  // K lhs states shared by all lanes (aqc_mpsb_set_bank): amplitudes <bank_k|vh_l> of aqc_mpsb_vh_bank
     std::map<std::string, Schedule> schedules;
     bool have_target = false, have_lhs = false, have_bank = false;
-    double* thetas = nullptr;    // [L][T] on the device
-    double* h_thetas = nullptr;  // pinned staging of the same
-    int T_cap = 0;
-    int* status = nullptr;       // [L] status bits | [L] largest bond a gate has produced
+    DevBuf<double> thetas;       // [L][T_cap] on the device
+    PinBuf<double> h_thetas;     // pinned staging of the same
+    int T_cap = 0;               // thetas per lane the two are laid out for (a shape, like nvals)
+    DevBuf<int> status;          // [L] status bits | [L] largest bond a gate has produced
     // environments of the pair (w, z), see aqc_mps_engine.cpp
-    double2* env_l = nullptr;    // [L][n + 1][kLaneEnv]
-    double2* env_r = nullptr;    // [L][n][kLaneEnv]
-    double2* e0 = nullptr;       // [L][kLaneEnv]
-    double2* e1 = nullptr;
-    double2* vals = nullptr;     // [L][nvals]
-    char* h_out = nullptr;       // pinned: vals | status+peak | discarded | dims of vh
-    size_t h_out_bytes = 0;
+    DevBuf<double2> env_l;       // [L][n + 1][kLaneEnv]
+    DevBuf<double2> env_r;       // [L][n][kLaneEnv]
+    DevBuf<double2> e0;          // [L][kLaneEnv]
+    DevBuf<double2> e1;
+    DevBuf<double2> vals;        // [L][nvals]
+    PinBuf<char> h_out;          // pinned: vals | status+peak | discarded | dims of vh
     int nvals = 0, valid_l = 0, valid_r = 0;
     int hint = kLaneCap;         // bonds the launches are sized for
     int peak_vh = 0, peak_grad = 0;   // largest bond the gates of the last V^H / gradient phase produced (0: none yet)
@@ -93,15 +89,14 @@ struct aqc_mpsb {
     // statistics of the truncated 2-qubit gates (aqc_mpsb_gate2_stats): work of the Jacobi sweeps on the device, and -- while
     // profiling is on -- the duration of every lanes_gate2 launch from a pool of event pairs (read back when the pool is full
     // and when the figures are asked for)
-    unsigned long long* jstats = nullptr;   // device [4]
+    DevBuf<unsigned long long> jstats;      // device [4]
     bool prof = false;
     std::vector<hipEvent_t> ev;             // pairs
     size_t ev_used = 0;
     double gate2_ms = 0.0;
     long long gate2_launches = 0;
-    uint8_t* bits = nullptr;     // basis-state patterns of aqc_mpsb_set_lhs_basis and their pinned staging
-    uint8_t* h_bits = nullptr;
-    size_t bits_cap = 0;
+    DevBuf<uint8_t> bits;        // basis-state patterns of aqc_mpsb_set_lhs_basis and their pinned staging (both grow-only)
+    PinBuf<uint8_t> h_bits;
 };
 
 namespace {
@@ -125,20 +120,13 @@ void destroy(aqc_mpsb* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    for (Lanes* s : {&b->target, &b->lhs, &b->vh, &b->w, &b->z, &b->bank}) s->release();
-    for (auto& kv : b->schedules) kv.second.release();
-    for (void* p : {(void*)b->thetas, (void*)b->status, (void*)b->env_l, (void*)b->env_r, (void*)b->e0, (void*)b->e1, (void*)b->vals, (void*)b->bits,
-                    (void*)b->jstats})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
-    for (void* p : {(void*)b->h_thetas, (void*)b->h_out, (void*)b->h_bits})
-        if (p) (void)hipHostFree(p);
     if (b->st) (void)hipStreamDestroy(b->st);
-    delete b;
+    delete b;   // the buffers, after the stream has drained
 }
 
 int clone(aqc_mpsb* b, const Lanes& src, Lanes& dst) {
-    HIP_OK(hipMemcpyAsync(dst.base, src.base, src.bytes, hipMemcpyDeviceToDevice, b->st));
+    HIP_OK(hipMemcpyAsync(dst.base, src.base, src.base.capacity(), hipMemcpyDeviceToDevice, b->st));
     return 0;
 }
 
@@ -217,14 +205,7 @@ int build_schedule(aqc_mpsb* b, const aqc_circuit* c, bool inverse, Schedule& ou
             if (lev[i] == lv) { if (ops[i].two) t2.push_back(ops[i].op2); else t1.push_back(ops[i].op1); }
         L.n1 = (int)t1.size() - L.off1; L.n2 = (int)t2.size() - L.off2;
     }
-    if (!t1.empty()) {
-        HIP_OK(hipMalloc((void**)&out.ops1, sizeof(LaneOp1) * t1.size()));
-        HIP_OK(hipMemcpy(out.ops1, t1.data(), sizeof(LaneOp1) * t1.size(), hipMemcpyHostToDevice));
-    }
-    if (!t2.empty()) {
-        HIP_OK(hipMalloc((void**)&out.ops2, sizeof(LaneOp2) * t2.size()));
-        HIP_OK(hipMemcpy(out.ops2, t2.data(), sizeof(LaneOp2) * t2.size(), hipMemcpyHostToDevice));
-    }
+    if ((!t1.empty() && out.ops1.upload(t1)) || (!t2.empty() && out.ops2.upload(t2))) return 1;
     return 0;
 }
 
@@ -241,7 +222,6 @@ int apply_circuit_all(aqc_mpsb* b, Lanes& s, const aqc_circuit* c, int T, bool i
     if (it == b->schedules.end()) {
         if (b->schedules.size() >= 16) {   // (a driver walks a few horizons; nothing keeps more than a handful of circuits alive)
             HIP_OK(hipStreamSynchronize(b->st));
-            for (auto& kv : b->schedules) kv.second.release();
             b->schedules.clear();
         }
         Schedule sch;
@@ -423,17 +403,10 @@ int begin(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double tru
     const auto out_size = [&](int nv) { return sizeof(double2) * (size_t)L * nv + sizeof(int) * 2 * (size_t)L + sizeof(double) * (size_t)L + sizeof(int) * (size_t)L * (n + 1); };
     if (need > b->nvals || T > b->T_cap) {
         HIP_OK(hipStreamSynchronize(b->st));
-        if (b->vals) HIP_OK(hipFree(b->vals));
-        if (b->thetas) HIP_OK(hipFree(b->thetas));
-        if (b->h_thetas) HIP_OK(hipHostFree(b->h_thetas));
-        if (b->h_out) HIP_OK(hipHostFree(b->h_out));
-        b->vals = nullptr; b->thetas = nullptr; b->h_thetas = nullptr; b->h_out = nullptr;
         const int nv = std::max(need, b->nvals), tc = std::max({T, b->T_cap, 1});
         b->nvals = 0; b->T_cap = 0;
-        HIP_OK(hipMalloc((void**)&b->vals, sizeof(double2) * (size_t)L * nv));
-        HIP_OK(hipMalloc((void**)&b->thetas, sizeof(double) * (size_t)L * tc));
-        HIP_OK(hipHostMalloc((void**)&b->h_thetas, sizeof(double) * (size_t)L * tc, hipHostMallocDefault));
-        HIP_OK(hipHostMalloc((void**)&b->h_out, out_size(nv), hipHostMallocDefault));
+        if (b->vals.reserve((size_t)L * nv) || b->thetas.reserve((size_t)L * tc) || b->h_thetas.reserve((size_t)L * tc) ||
+            b->h_out.reserve(out_size(nv))) return 1;
         b->nvals = nv; b->T_cap = tc;
     }
     HIP_OK(hipStreamSynchronize(b->st));   // (the staging buffer may still feed the previous upload)
@@ -590,10 +563,8 @@ int aqc_mpsb_create(int device, int num_qubits, int lanes, aqc_mpsb** out) {
     for (Lanes* s : {&b->target, &b->lhs, &b->vh, &b->w, &b->z})
         if (s->alloc(num_qubits, lanes)) return bad(1);
     const size_t L = lanes;
-    if (hipMalloc((void**)&b->status, sizeof(int) * 2 * L) != hipSuccess ||
-        hipMalloc((void**)&b->env_l, sizeof(double2) * L * kEnvL(num_qubits)) != hipSuccess ||
-        hipMalloc((void**)&b->env_r, sizeof(double2) * L * kEnvR(num_qubits)) != hipSuccess ||
-        hipMalloc((void**)&b->e0, sizeof(double2) * L * kLaneEnv) != hipSuccess || hipMalloc((void**)&b->e1, sizeof(double2) * L * kLaneEnv) != hipSuccess) {
+    if (b->status.alloc(2 * L) || b->env_l.alloc(L * kEnvL(num_qubits)) || b->env_r.alloc(L * kEnvR(num_qubits)) || b->e0.alloc(L * kLaneEnv) ||
+        b->e1.alloc(L * kLaneEnv)) {
         return bad(refuse("allocation of the lockstep lanes failed (%d lanes, %d qubits)", lanes, num_qubits));
     }
     *out = b;
@@ -613,7 +584,7 @@ int aqc_mpsb_gate2_stats(aqc_mpsb* b, int enable, double* out, int reset) {
     if (!b) return failf("null batch");
     HIP_OK(hipSetDevice(b->device));
     if (!b->jstats) {
-        HIP_OK(hipMalloc((void**)&b->jstats, 4 * sizeof(unsigned long long)));
+        if (b->jstats.alloc(4)) return 1;
         HIP_OK(hipMemset(b->jstats, 0, 4 * sizeof(unsigned long long)));
     }
     if (gate2_events_flush(b)) return 1;
@@ -659,14 +630,9 @@ int aqc_mpsb_set_lhs_basis(aqc_mpsb* b, const uint8_t* bits) {
     if (!b || !bits) return failf("null argument");
     HIP_OK(hipSetDevice(b->device));
     const size_t bytes = (size_t)b->L * b->n;
-    if (bytes > b->bits_cap) {
+    if (bytes > b->bits.capacity()) {
         HIP_OK(hipStreamSynchronize(b->st));
-        if (b->bits) HIP_OK(hipFree(b->bits));
-        if (b->h_bits) HIP_OK(hipHostFree(b->h_bits));
-        b->bits = nullptr; b->h_bits = nullptr; b->bits_cap = 0;
-        HIP_OK(hipMalloc((void**)&b->bits, bytes));
-        HIP_OK(hipHostMalloc((void**)&b->h_bits, bytes, hipHostMallocDefault));
-        b->bits_cap = bytes;
+        if (b->bits.reserve(bytes) || b->h_bits.reserve(bytes)) return 1;
     }
     HIP_OK(hipStreamSynchronize(b->st));   // (the staging buffer may still feed the previous upload)
     memcpy(b->h_bits, bits, bytes);
@@ -736,7 +702,7 @@ int aqc_mpsb_set_bank(aqc_mpsb* b, aqc_mps* const* states, int count) {
     b->have_bank = false;
     if (b->bank.L != count) {
         HIP_OK(hipStreamSynchronize(b->st));
-        b->bank.release();
+        if (b->bank.base.release()) return 1;
         if (b->bank.alloc(b->n, count)) { b->bank.L = 0; return 1; }
     }
     if (const int rc = load_lanes(b, b->bank, states, 0)) return rc;

@@ -26,26 +26,13 @@
 #include <vector>
 
 #include "../../include/aqc_hip.h"
+#include "aqc_devbuf.h"
 #include "aqc_launch.h"
 #include "aqc_mps_host.h"
 
 using namespace aqc;
 
 namespace {
-
-struct Scratch {   // grow-only device buffer
-    void* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) HIP_OK(hipFree(p));
-        p = nullptr; cap = 0;
-        HIP_OK(hipMalloc(&p, bytes));
-        cap = bytes;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 // Round-robin tournament: rounds x (n2/2) pairs over n2 = even(cols) players; index >= cols is a bye (-1).
 void tournament(int cols, std::vector<int>& pairs, int& rounds, int& per_round) {
@@ -68,10 +55,10 @@ void tournament(int cols, std::vector<int>& pairs, int& rounds, int& per_round) 
 }
 
 struct SvdWork {
-    Scratch pairs, flag, sigma;
+    DevBuf<int> pairs, flag;
+    DevBuf<double> sigma;
     std::vector<int> h_pairs;
     int cached_cols = -1, cached_blocked = -1, rounds = 0, per_round = 0;
-    void release() { pairs.release(); flag.release(); sigma.release(); }
 };
 
 // Tournament over column blocks: a block without a partner (odd number of blocks) still plays, alone (.y = -1).
@@ -104,26 +91,26 @@ int jacobi_svd(SvdWork& sw, void* W, int rows, void* V, int cols, hipStream_t st
     if (!small && (sw.cached_cols != cols || sw.cached_blocked != (int)blocked)) {   // (the one-workgroup kernel works its pairing out itself)
         if (blocked) block_tournament((cols + svd_block_size() - 1) / svd_block_size(), sw.h_pairs, sw.rounds, sw.per_round);
         else tournament(cols, sw.h_pairs, sw.rounds, sw.per_round);
-        if (sw.pairs.reserve(std::max<size_t>(sw.h_pairs.size(), 2) * sizeof(int))) return 1;
-        if (!sw.h_pairs.empty()) HIP_OK(hipMemcpyAsync(sw.pairs.p, sw.h_pairs.data(), sw.h_pairs.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        if (sw.pairs.reserve(std::max<size_t>(sw.h_pairs.size(), 2))) return 1;
+        if (!sw.h_pairs.empty()) HIP_OK(hipMemcpyAsync(sw.pairs, sw.h_pairs.data(), sw.h_pairs.size() * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_OK(hipStreamSynchronize(st));
         sw.cached_cols = cols;
         sw.cached_blocked = (int)blocked;
     }
     constexpr int kFlagInts = 64 + 4;   // [0..63] rotations per sweep | [64] barrier | [65] sweeps used | [66] barrier timeout
-    if (sw.flag.reserve(sizeof(int) * kFlagInts) || sw.sigma.reserve(sizeof(double) * (std::max(cols, 1) + 2))) return 1;   // sigma | fro2 | sweeps
-    double* fro2 = static_cast<double*>(sw.sigma.p) + std::max(cols, 1);   // scale of the negligible-column rule (aqc_mps_dev.h: kNegligible2)
-    int* flag = static_cast<int*>(sw.flag.p);
+    if (sw.flag.reserve(kFlagInts) || sw.sigma.reserve((size_t)std::max(cols, 1) + 2)) return 1;   // sigma | fro2 | sweeps
+    double* fro2 = sw.sigma + std::max(cols, 1);   // scale of the negligible-column rule (aqc_mps_dev.h: kNegligible2)
+    int* flag = sw.flag;
     const double tol = 1e-15;
     int sweeps = 0;
     int status[2] = {0, 0};
     if (small) {   // one launch: matrix and V live in the LDS of one workgroup
-        HIP_OK(launch_jacobi_small(W, rows, V, cols, tol, 60, flag, static_cast<double*>(sw.sigma.p), st));
+        HIP_OK(launch_jacobi_small(W, rows, V, cols, tol, 60, flag, sw.sigma, st));
     } else if (blocked) {   // one cooperative launch: persistent workgroups, 16 columns at a time in LDS
         HIP_OK(launch_svd_identity(V, cols, st));
         HIP_OK(launch_svd_fro2(W, (size_t)rows * cols, fro2, st));
         HIP_OK(hipMemsetAsync(flag, 0, sizeof(int) * kFlagInts, st));
-        HIP_OK(launch_jacobi_block(W, rows, V, cols, sw.pairs.p, sw.rounds, sw.per_round, tol, 60, fro2, flag, reinterpret_cast<unsigned*>(flag + 64), flag + 65, st));
+        HIP_OK(launch_jacobi_block(W, rows, V, cols, sw.pairs, sw.rounds, sw.per_round, tol, 60, fro2, flag, reinterpret_cast<unsigned*>(flag + 64), flag + 65, st));
         HIP_OK(hipMemcpyAsync(status, flag + 65, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     } else {
         HIP_OK(launch_svd_identity(V, cols, st));
@@ -132,15 +119,15 @@ int jacobi_svd(SvdWork& sw, void* W, int rows, void* V, int cols, hipStream_t st
     for (; !small && !blocked && sweeps < 60 && cols > 1; ++sweeps) {
         HIP_OK(hipMemsetAsync(flag, 0, sizeof(int), st));
         for (int r = 0; r < sw.rounds; ++r)
-            HIP_OK(launch_jacobi_round(W, rows, V, cols, static_cast<int*>(sw.pairs.p) + (size_t)r * sw.per_round * 2, sw.per_round, tol, fro2, flag, st));
+            HIP_OK(launch_jacobi_round(W, rows, V, cols, sw.pairs + (size_t)r * sw.per_round * 2, sw.per_round, tol, fro2, flag, st));
         int rotations = 0;
         HIP_OK(hipMemcpyAsync(&rotations, flag, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         if (rotations == 0) { ++sweeps; break; }
     }
     h_sigma.resize(cols + 2);
-    if (!small) HIP_OK(launch_svd_norms(W, rows, cols, static_cast<double*>(sw.sigma.p), st));   // (the one-launch kernel delivers them itself)
-    HIP_OK(hipMemcpyAsync(h_sigma.data(), sw.sigma.p, sizeof(double) * (small ? cols + 2 : cols), hipMemcpyDeviceToHost, st));
+    if (!small) HIP_OK(launch_svd_norms(W, rows, cols, sw.sigma, st));   // (the one-launch kernel delivers them itself)
+    HIP_OK(hipMemcpyAsync(h_sigma.data(), sw.sigma, sizeof(double) * (small ? cols + 2 : cols), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (small) sweeps = (int)h_sigma[cols + 1];   // the sweep count came with the singular values
     h_sigma.resize(cols);
@@ -161,16 +148,15 @@ struct aqc_mps {
     hipStream_t stream = nullptr;
     bool owns_stream = true;
     std::vector<int> dims;                    // n + 1 bond dimensions, dims[0] = dims[n] = 1
-    std::vector<double2*> t;                  // per site: [2][dims[q]][dims[q+1]]
-    std::vector<size_t> t_cap, lam_cap;       // allocated elements (buffers only grow)
+    std::vector<DevBuf<double2>> t;           // per site: [2][dims[q]][dims[q+1]] (the buffers only grow)
     std::vector<std::vector<double>> lam;     // n - 1 Schmidt vectors (host copy)
-    std::vector<double*> d_lam;               // the same on the device
-    Scratch theta, work, vmat, ord, tmp;
+    std::vector<DevBuf<double>> d_lam;        // the same on the device (grow-only)
+    DevBuf<double2> theta, work, vmat, tmp;
+    DevBuf<char> ord;                         // column order (ints) | new Schmidt values (doubles, 16-byte aligned)
     // Pinned staging of what the host decides per 2-qubit gate (column order, new Schmidt values): two buffers used in turn.
     // A gate's uploads are asynchronous; the NEXT gate synchronises the stream to read its singular values, so by the time a
     // buffer is written again (two gates later) the copy out of it has completed -- no synchronisation of its own.
-    void* stage[2] = {nullptr, nullptr};
-    size_t stage_cap[2] = {0, 0};
+    PinBuf<char> stage[2];
     unsigned stage_turn = 0;
     SvdWork svd;
     double discarded = 0.0;                   // accumulated discarded weight (sum of squared singular values)
@@ -182,14 +168,9 @@ namespace {
 size_t site_elems(const aqc_mps* m, int q) { return (size_t)2 * m->dims[q] * m->dims[q + 1]; }
 
 int reserve_lambda(aqc_mps* m, int bond, size_t count) {
-    if (count > m->lam_cap[bond]) {
-        HIP_OK(hipStreamSynchronize(m->stream));
-        if (m->d_lam[bond]) HIP_OK(hipFree(m->d_lam[bond]));
-        m->d_lam[bond] = nullptr;
-        HIP_OK(hipMalloc((void**)&m->d_lam[bond], sizeof(double) * count));
-        m->lam_cap[bond] = count;
-    }
-    return 0;
+    if (count <= m->d_lam[bond].capacity()) return 0;
+    HIP_OK(hipStreamSynchronize(m->stream));
+    return m->d_lam[bond].reserve(count);
 }
 
 int set_lambda(aqc_mps* m, int bond, const std::vector<double>& v) {
@@ -203,37 +184,26 @@ int set_lambda(aqc_mps* m, int bond, const std::vector<double>& v) {
 // pinned staging buffer of this gate (see aqc_mps::stage)
 int stage_buffer(aqc_mps* m, size_t bytes, void** out) {
     const unsigned i = m->stage_turn++ & 1u;
-    if (bytes > m->stage_cap[i]) {
+    if (bytes > m->stage[i].capacity()) {
         HIP_OK(hipStreamSynchronize(m->stream));
-        if (m->stage[i]) HIP_OK(hipHostFree(m->stage[i]));
-        m->stage[i] = nullptr; m->stage_cap[i] = 0;
-        const size_t cap = std::max<size_t>(bytes * 2, 4096);
-        HIP_OK(hipHostMalloc(&m->stage[i], cap, hipHostMallocDefault));
-        m->stage_cap[i] = cap;
+        if (m->stage[i].reserve(std::max<size_t>(bytes * 2, 4096))) return 1;
     }
-    *out = m->stage[i];
+    *out = (char*)m->stage[i];
     return 0;
 }
 
 int reserve_site(aqc_mps* m, int q, size_t elems) {   // contents are NOT preserved
-    if (elems <= m->t_cap[q]) return 0;
+    if (elems <= m->t[q].capacity()) return 0;
     HIP_OK(hipStreamSynchronize(m->stream));
-    if (m->t[q]) HIP_OK(hipFree(m->t[q]));
-    m->t[q] = nullptr;
-    HIP_OK(hipMalloc((void**)&m->t[q], sizeof(double2) * elems));
-    m->t_cap[q] = elems;
-    return 0;
+    return m->t[q].reserve(elems);
 }
 
 void destroy(aqc_mps* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    for (double2* p : m->t) if (p) (void)hipFree(p);
-    for (double* p : m->d_lam) if (p) (void)hipFree(p);
-    m->theta.release(); m->work.release(); m->vmat.release(); m->ord.release(); m->tmp.release(); m->svd.release();
-    for (void* p : m->stage) if (p) (void)hipHostFree(p);
-    if (m->stream && m->owns_stream) (void)hipStreamDestroy(m->stream);
-    delete m;
+    hipStream_t own = m->owns_stream ? m->stream : nullptr;
+    delete m;   // (the buffers go before the stream, as they always have)
+    if (own) (void)hipStreamDestroy(own);
 }
 
 int new_mps(int device, int n, aqc_mps** out) {
@@ -245,11 +215,9 @@ int new_mps(int device, int n, aqc_mps** out) {
     aqc_mps* m = new aqc_mps();
     m->device = device; m->n = n;
     m->dims.assign(n + 1, 1);
-    m->t.assign(n, nullptr);
-    m->t_cap.assign(n, 0);
-    m->lam_cap.assign(std::max(n - 1, 0), 0);
+    m->t.resize(n);
     m->lam.assign(std::max(n - 1, 0), {});
-    m->d_lam.assign(std::max(n - 1, 0), nullptr);
+    m->d_lam.resize(std::max(n - 1, 0));
     if (hipStreamCreate(&m->stream) != hipSuccess) { delete m; return failf("hipStreamCreate failed"); }
     *out = m;
     return 0;
@@ -263,20 +231,20 @@ int gate_adjacent(aqc_mps* m, int q, const double* g16, double trunc_thr, int ma
     // Jacobi runs on the side with fewer columns
     const int mode = cols <= rows ? 0 : 1;
     const int wrows = mode == 0 ? rows : cols, wcols = mode == 0 ? cols : rows;
-    if (m->work.reserve(sizeof(double2) * (size_t)wrows * wcols) || m->vmat.reserve(sizeof(double2) * (size_t)wcols * wcols)) return 1;
-    const double* lam_left = q > 0 ? m->d_lam[q - 1] : nullptr;
+    if (m->work.reserve((size_t)wrows * wcols) || m->vmat.reserve((size_t)wcols * wcols)) return 1;
+    const double* lam_left = q > 0 ? (double*)m->d_lam[q - 1] : nullptr;
     if (chim <= 64 && (size_t)chil * chir <= 4096) {   // small bonds: product, scaling and gate in one launch
-        HIP_OK(launch_mps_theta_fused(m->t[q], m->t[q + 1], lam_left, chil, chim, chir, g16, mode, m->work.p, st));
+        HIP_OK(launch_mps_theta_fused(m->t[q], m->t[q + 1], lam_left, chil, chim, chir, g16, mode, m->work, st));
     } else {
-        if (m->theta.reserve(sizeof(double2) * (size_t)rows * cols)) return 1;
+        if (m->theta.reserve((size_t)rows * cols)) return 1;
         // theta0[(a,l), (b,r)] = sum_m T_q[(a,l), m] T_{q+1}[b][m][r]
         for (int b = 0; b < 2; ++b)
             HIP_OK(launch_zgemm(false, false, rows, chir, chim, m->t[q], chim, m->t[q + 1] + (size_t)b * chim * chir, chir,
-                                static_cast<double2*>(m->theta.p) + (size_t)b * chir, cols, st));
-        HIP_OK(launch_mps_theta(m->theta.p, lam_left, chil, chir, g16, mode, m->work.p, st));
+                                m->theta + (size_t)b * chir, cols, st));
+        HIP_OK(launch_mps_theta(m->theta, lam_left, chil, chir, g16, mode, m->work, st));
     }
     std::vector<double> sigma;
-    if (jacobi_svd(m->svd, m->work.p, wrows, m->vmat.p, wcols, st, sigma, &m->last_sweeps)) return 1;
+    if (jacobi_svd(m->svd, m->work, wrows, m->vmat, wcols, st, sigma, &m->last_sweeps)) return 1;
     // order, rank and truncation (host: wcols numbers)
     std::vector<int> ord(wcols);
     std::iota(ord.begin(), ord.end(), 0);
@@ -313,9 +281,9 @@ int gate_adjacent(aqc_mps* m, int q, const double* g16, double trunc_thr, int ma
     lam.resize(k);
     for (int j = 0; j < k; ++j) h_lam[j] = lam[j] = sigma[ord[j]] * rescale;
     // ONE upload (column order | new Schmidt values); the split kernel copies the latter into the bond's vector
-    HIP_OK(hipMemcpyAsync(m->ord.p, stage, lam_off + sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
-    HIP_OK(launch_mps_split(m->work.p, m->vmat.p, static_cast<int*>(m->ord.p), static_cast<double*>(m->svd.sigma.p), lam_left, chil, chir, k,
-                            mode, rescale, m->t[q], m->t[q + 1], reinterpret_cast<const double*>(static_cast<const char*>(m->ord.p) + lam_off),
+    HIP_OK(hipMemcpyAsync(m->ord, stage, lam_off + sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
+    HIP_OK(launch_mps_split(m->work, m->vmat, reinterpret_cast<int*>((char*)m->ord), m->svd.sigma, lam_left, chil, chir, k,
+                            mode, rescale, m->t[q], m->t[q + 1], reinterpret_cast<const double*>(m->ord + lam_off),
                             m->d_lam[q], st));
     m->dims[q + 1] = k;
     return 0;
@@ -359,49 +327,48 @@ int apply_circuit(aqc_mps* m, const aqc_circuit* c, const double* th, bool inver
 struct Environments {
     aqc_mps* w; aqc_mps* z;
     int n, valid_l, valid_r;
-    std::vector<Scratch> L, R;
-    Scratch t, e0, e1, bsite, vals;
+    std::vector<DevBuf<double2>> L, R;
+    DevBuf<double2> t, e0, e1, bsite, vals;
     hipStream_t st;
     int init(aqc_mps* w_, aqc_mps* z_, int nvals) {
         w = w_; z = z_; n = w->n; st = w->stream;
         L.resize(n + 1); R.resize(n);
         valid_l = 0; valid_r = n - 1;
         const double one[2] = {1.0, 0.0};
-        if (L[0].reserve(sizeof(double2)) || R[n - 1].reserve(sizeof(double2)) || vals.reserve(sizeof(double2) * std::max(nvals, 1))) return 1;
-        HIP_OK(hipMemcpyAsync(L[0].p, one, sizeof one, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(R[n - 1].p, one, sizeof one, hipMemcpyHostToDevice, st));
+        if (L[0].reserve(1) || R[n - 1].reserve(1) || vals.reserve(std::max(nvals, 1))) return 1;
+        HIP_OK(hipMemcpyAsync(L[0], one, sizeof one, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(R[n - 1], one, sizeof one, hipMemcpyHostToDevice, st));
         HIP_OK(hipStreamSynchronize(st));
         return 0;
     }
-    void release() { for (Scratch& x : L) x.release(); for (Scratch& x : R) x.release(); t.release(); e0.release(); e1.release(); bsite.release(); vals.release(); }
     void touched(int lo, int hi) { valid_l = std::min(valid_l, lo); valid_r = std::max(valid_r, hi); }
     // site p of z, seen through G^H when an operator G sits on w's side there (<G w|z> = <w|G^H z>)
     int z_site(int p, const M2* op, const double2** out) {
         *out = z->t[p];
         if (!op) return 0;
         const size_t ne = (size_t)z->dims[p] * z->dims[p + 1];
-        if (bsite.reserve(sizeof(double2) * 2 * ne)) return 1;
+        if (bsite.reserve(2 * ne)) return 1;
         double g8[8]; pack(adjoint(*op), g8);
-        HIP_OK(launch_gate1q(z->t[p], bsite.p, 1, ne, 0, g8, st));
-        *out = static_cast<const double2*>(bsite.p);
+        HIP_OK(launch_gate1q(z->t[p], bsite, 1, ne, 0, g8, st));
+        *out = bsite;
         return 0;
     }
     // out[u][v] = sum_bit sum_xy conj(A_p[bit][x][u]) in[x][y] B_p[bit][y][v]
-    int step_left(int p, const void* in, const M2* op, Scratch& out) {
+    int step_left(int p, const void* in, const M2* op, DevBuf<double2>& out) {
         const int xa = w->dims[p], ua = w->dims[p + 1], yb = z->dims[p], vb = z->dims[p + 1];
         if (mps_env_fits_small(xa, ua, yb, vb)) {   // small bonds: one launch, the operator folded in
-            if (out.reserve(sizeof(double2) * (size_t)ua * vb)) return 1;
+            if (out.reserve((size_t)ua * vb)) return 1;
             double g8[8];
             if (op) pack(adjoint(*op), g8);
-            HIP_OK(launch_mps_env_left(in, w->t[p], z->t[p], xa, ua, yb, vb, op ? g8 : nullptr, out.p, st));
+            HIP_OK(launch_mps_env_left(in, w->t[p], z->t[p], xa, ua, yb, vb, op ? g8 : nullptr, out, st));
             return 0;
         }
         const double2* bq = nullptr;
         if (z_site(p, op, &bq)) return 1;
-        if (t.reserve(sizeof(double2) * (size_t)xa * vb) || out.reserve(sizeof(double2) * (size_t)ua * vb)) return 1;
+        if (t.reserve((size_t)xa * vb) || out.reserve((size_t)ua * vb)) return 1;
         for (int bit = 0; bit < 2; ++bit) {
-            HIP_OK(launch_zgemm(false, false, xa, vb, yb, in, yb, bq + (size_t)bit * yb * vb, vb, t.p, vb, st));
-            HIP_OK(launch_zgemm(true, bit == 1, ua, vb, xa, w->t[p] + (size_t)bit * xa * ua, ua, t.p, vb, out.p, vb, st));
+            HIP_OK(launch_zgemm(false, false, xa, vb, yb, in, yb, bq + (size_t)bit * yb * vb, vb, t, vb, st));
+            HIP_OK(launch_zgemm(true, bit == 1, ua, vb, xa, w->t[p] + (size_t)bit * xa * ua, ua, t, vb, out, vb, st));
         }
         return 0;
     }
@@ -409,14 +376,14 @@ struct Environments {
     int step_right(int p) {
         const int xa = w->dims[p], ua = w->dims[p + 1], yb = z->dims[p], vb = z->dims[p + 1];
         if (mps_env_fits_small(xa, ua, yb, vb)) {
-            if (R[p - 1].reserve(sizeof(double2) * (size_t)xa * yb)) return 1;
-            HIP_OK(launch_mps_env_right(R[p].p, w->t[p], z->t[p], xa, ua, yb, vb, R[p - 1].p, st));
+            if (R[p - 1].reserve((size_t)xa * yb)) return 1;
+            HIP_OK(launch_mps_env_right(R[p], w->t[p], z->t[p], xa, ua, yb, vb, R[p - 1], st));
             return 0;
         }
-        if (t.reserve(sizeof(double2) * (size_t)ua * yb) || R[p - 1].reserve(sizeof(double2) * (size_t)xa * yb)) return 1;
+        if (t.reserve((size_t)ua * yb) || R[p - 1].reserve((size_t)xa * yb)) return 1;
         for (int bit = 0; bit < 2; ++bit) {
-            HIP_OK(launch_zgemm_bh(false, false, ua, yb, vb, R[p].p, vb, z->t[p] + (size_t)bit * yb * vb, vb, t.p, yb, st));
-            HIP_OK(launch_zgemm(false, bit == 1, xa, yb, ua, w->t[p] + (size_t)bit * xa * ua, ua, t.p, yb, R[p - 1].p, yb, st));
+            HIP_OK(launch_zgemm_bh(false, false, ua, yb, vb, R[p], vb, z->t[p] + (size_t)bit * yb * vb, vb, t, yb, st));
+            HIP_OK(launch_zgemm(false, bit == 1, xa, yb, ua, w->t[p] + (size_t)bit * xa * ua, ua, t, yb, R[p - 1], yb, st));
         }
         return 0;
     }
@@ -424,18 +391,18 @@ struct Environments {
     int dot(int slot, int nops, const int* q, const M2* const* g) {
         const int lo = q[0], hi = q[nops - 1];
         for (; valid_l < lo; ++valid_l)
-            if (step_left(valid_l, L[valid_l].p, nullptr, L[valid_l + 1])) return 1;
+            if (step_left(valid_l, L[valid_l], nullptr, L[valid_l + 1])) return 1;
         for (; valid_r > hi; --valid_r)
             if (step_right(valid_r)) return 1;
-        const void* cur = L[lo].p;
-        Scratch* pp[2] = {&e0, &e1};
+        const void* cur = L[lo];
+        DevBuf<double2>* pp[2] = {&e0, &e1};
         for (int p = lo; p <= hi; ++p) {
             const M2* op = p == q[0] ? g[0] : (nops > 1 && p == q[1] ? g[1] : nullptr);
-            Scratch& out = *pp[(p - lo) & 1];
+            DevBuf<double2>& out = *pp[(p - lo) & 1];
             if (step_left(p, cur, op, out)) return 1;
-            cur = out.p;
+            cur = out;
         }
-        HIP_OK(launch_mps_env_dot(cur, R[hi].p, (size_t)w->dims[hi + 1] * z->dims[hi + 1], static_cast<double2*>(vals.p) + slot, st));
+        HIP_OK(launch_mps_env_dot(cur, R[hi], (size_t)w->dims[hi + 1] * z->dims[hi + 1], vals + slot, st));
         return 0;
     }
 };
@@ -449,7 +416,7 @@ int fast_dot_gradient(const aqc_circuit* c, aqc_mps* w, aqc_mps* z, const double
     const int nrec = 3 * n + thetas_per_block(c) * (int)blocks_of(c).size();   // at most
     rec.reserve(nrec);
     Environments env;
-    if (env.init(w, z, nrec)) { env.release(); return 1; }
+    if (env.init(w, z, nrec)) return 1;
     auto record = [&](int tindex, cd factor, int nops, const int* q, const M2* const* g) -> int {
         if (env.dot((int)rec.size(), nops, q, g)) return 1;
         rec.emplace_back(tindex, factor);
@@ -483,14 +450,13 @@ int fast_dot_gradient(const aqc_circuit* c, aqc_mps* w, aqc_mps* z, const double
         for (size_t i = 0; i < steps.size() && !bad; ++i) bad = run(steps[i]) != 0;
         if (bad) break;
         std::vector<cd> vals(rec.size());
-        if (!rec.empty() && hipMemcpyAsync(vals.data(), env.vals.p, sizeof(cd) * rec.size(), hipMemcpyDeviceToHost, env.st) != hipSuccess) { failf("gradient download failed"); break; }
+        if (!rec.empty() && hipMemcpyAsync(vals.data(), env.vals, sizeof(cd) * rec.size(), hipMemcpyDeviceToHost, env.st) != hipSuccess) { failf("gradient download failed"); break; }
         if (hipStreamSynchronize(env.st) != hipSuccess) { failf("stream synchronisation failed"); break; }
         std::vector<cd> g(T, cd(0.0, 0.0));
         for (size_t i = 0; i < rec.size(); ++i) g[rec[i].first] += rec[i].second * vals[i];
         std::memcpy(grad, g.data(), sizeof(cd) * T);
         rc = 0;
     } while (false);
-    env.release();
     return rc;
 }
 
@@ -500,7 +466,7 @@ int aqc::mps_peek(const aqc_mps* m, int q, const void** site, const double** lam
     if (!m || q < 0 || q >= m->n) return failf("mps_peek: invalid argument");
     HIP_OK(hipStreamSynchronize(m->stream));
     *site = m->t[q];
-    *lam = q < m->n - 1 ? m->d_lam[q] : nullptr;
+    *lam = q < m->n - 1 ? (double*)m->d_lam[q] : nullptr;
     return 0;
 }
 
@@ -601,14 +567,14 @@ int aqc_mps_export(aqc_mps* m, double* gammas, double* lambdas) {
     size_t off = 0, loff = 0;
     for (int q = 0; q < m->n; ++q) {
         const size_t ne = site_elems(m, q);
-        if (m->tmp.reserve(sizeof(double2) * ne)) return 1;
-        HIP_OK(hipMemcpyAsync(m->tmp.p, m->t[q], sizeof(double2) * ne, hipMemcpyDeviceToDevice, m->stream));
+        if (m->tmp.reserve(ne)) return 1;
+        HIP_OK(hipMemcpyAsync(m->tmp, m->t[q], sizeof(double2) * ne, hipMemcpyDeviceToDevice, m->stream));
         if (q < m->n - 1) {
-            HIP_OK(launch_mps_colscale(m->tmp.p, m->d_lam[q], (size_t)2 * m->dims[q], m->dims[q + 1], 0, m->stream));
+            HIP_OK(launch_mps_colscale(m->tmp, m->d_lam[q], (size_t)2 * m->dims[q], m->dims[q + 1], 0, m->stream));
             std::memcpy(lambdas + loff, m->lam[q].data(), sizeof(double) * m->lam[q].size());
             loff += m->lam[q].size();
         }
-        HIP_OK(hipMemcpyAsync(gammas + 2 * off, m->tmp.p, sizeof(double2) * ne, hipMemcpyDeviceToHost, m->stream));
+        HIP_OK(hipMemcpyAsync(gammas + 2 * off, m->tmp, sizeof(double2) * ne, hipMemcpyDeviceToHost, m->stream));
         HIP_OK(hipStreamSynchronize(m->stream));
         off += ne;
     }
@@ -684,8 +650,8 @@ int aqc_mps_dot_ops(aqc_mps* a, aqc_mps* b, int nops, const int32_t* qubits, con
         need = std::max(need, (size_t)a->dims[q] * b->dims[q + 1]);
         if (op_of[q] >= 0) site_max = std::max(site_max, site_elems(b, q));
     }
-    if (a->tmp.reserve(sizeof(double2) * (3 * need + site_max))) return 1;
-    double2* e = static_cast<double2*>(a->tmp.p);
+    if (a->tmp.reserve((3 * need + site_max))) return 1;
+    double2* e = a->tmp;
     double2* en = e + need;
     double2* t = en + need;
     double2* bsite = t + need;
@@ -729,31 +695,32 @@ int aqc_svd(int device, int m, int n, const double* a_in, double* u_out, double*
     const int mode = n <= m ? 0 : 1, k = std::min(m, n);
     const int wrows = mode == 0 ? m : n, wcols = k;
     const size_t na = (size_t)m * n;
-    Scratch da, dw, dv, du, dvh, dord, dss;
+    DevBuf<double2> da, dw, dv, du, dvh;
+    DevBuf<int> dord;
+    DevBuf<double> dss;
     SvdWork sw;
     std::vector<double> sigma;
     int rc = 1;
     hipStream_t st = nullptr;
     HIP_OK(hipStreamCreate(&st));   // the rounds are many short dependent launches: keep them off the legacy default stream
     do {
-        if (da.reserve(sizeof(double2) * na) || dw.reserve(sizeof(double2) * na) || dv.reserve(sizeof(double2) * (size_t)wcols * wcols) ||
-            du.reserve(sizeof(double2) * (size_t)m * k) || dvh.reserve(sizeof(double2) * (size_t)k * n) || dord.reserve(sizeof(int) * k) ||
-            dss.reserve(sizeof(double) * k)) break;
-        if (hipMemcpy(da.p, a_in, sizeof(double2) * na, hipMemcpyHostToDevice) != hipSuccess) { failf("SVD upload failed"); break; }
-        if (launch_svd_load(da.p, m, n, mode, dw.p, st) != hipSuccess) { failf("SVD load kernel failed"); break; }
-        if (jacobi_svd(sw, dw.p, wrows, dv.p, wcols, st, sigma, sweeps)) break;
+        if (da.reserve(na) || dw.reserve(na) || dv.reserve((size_t)wcols * wcols) ||
+            du.reserve((size_t)m * k) || dvh.reserve((size_t)k * n) || dord.reserve(k) ||
+            dss.reserve(k)) break;
+        if (hipMemcpy(da, a_in, sizeof(double2) * na, hipMemcpyHostToDevice) != hipSuccess) { failf("SVD upload failed"); break; }
+        if (launch_svd_load(da, m, n, mode, dw, st) != hipSuccess) { failf("SVD load kernel failed"); break; }
+        if (jacobi_svd(sw, dw, wrows, dv, wcols, st, sigma, sweeps)) break;
         std::vector<int> ord(wcols);
         std::iota(ord.begin(), ord.end(), 0);
         std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return sigma[x] > sigma[y]; });
-        if (hipMemcpy(dord.p, ord.data(), sizeof(int) * k, hipMemcpyHostToDevice) != hipSuccess) { failf("SVD upload failed"); break; }
-        if (launch_svd_assemble(dw.p, dv.p, static_cast<int*>(dord.p), static_cast<double*>(sw.sigma.p), m, n, k, mode, du.p, dvh.p,
-                                static_cast<double*>(dss.p), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { failf("SVD assemble kernel failed"); break; }
-        if (hipMemcpy(u_out, du.p, sizeof(double2) * (size_t)m * k, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(vh_out, dvh.p, sizeof(double2) * (size_t)k * n, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(s_out, dss.p, sizeof(double) * k, hipMemcpyDeviceToHost) != hipSuccess) { failf("SVD download failed"); break; }
+        if (hipMemcpy(dord, ord.data(), sizeof(int) * k, hipMemcpyHostToDevice) != hipSuccess) { failf("SVD upload failed"); break; }
+        if (launch_svd_assemble(dw, dv, dord, sw.sigma, m, n, k, mode, du, dvh,
+                                dss, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { failf("SVD assemble kernel failed"); break; }
+        if (hipMemcpy(u_out, du, sizeof(double2) * (size_t)m * k, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(vh_out, dvh, sizeof(double2) * (size_t)k * n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(s_out, dss, sizeof(double) * k, hipMemcpyDeviceToHost) != hipSuccess) { failf("SVD download failed"); break; }
         rc = 0;
     } while (false);
-    da.release(); dw.release(); dv.release(); du.release(); dvh.release(); dord.release(); dss.release(); sw.release();
     (void)hipStreamDestroy(st);
     return rc;
 }

@@ -16,11 +16,14 @@
 #include <functional>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/aqc_hip.h"
+#include "aqc_devbuf.h"
 #include "aqc_device.h"
 #include "aqc_launch.h"
 #include "aqc_plan.h"
@@ -50,28 +53,36 @@ inline int ceil_log2(int v) {
 // share the level; kURoute: only the plane sets the objective-by-projection route reads (ensure_umat, aqc_ws_sweep.cpp).
 enum ULevel { kUNone = 0, kURoute = 1, kUAll = 2 };
 
-struct DevPlan {
+// A lowered plan, host side only: what aqc_ctx::plan_cache keeps and the workspaces of one shape copy
+struct HostPlan {
     Plan plan;
     std::vector<DevStage> h_stages;
     std::vector<DevOp> h_ops;
     std::vector<DevSub> h_subs;   // register-blocked kernels
     std::vector<DevMop> h_mops;
-    DevStage* d_stages = nullptr;
-    DevOp* d_ops = nullptr;
-    DevSub* d_subs = nullptr;
-    DevMop* d_mops = nullptr;
     int k = 0, ntiles = 0, reg_bits = 0;
     bool v2 = false;              // run the register-blocked kernels
     // matrix-core kernels (family 3)
     bool v3 = false;
     std::vector<DevSub3> h_subs3;
     std::vector<DevGrp> h_grps;
-    DevSub3* d_subs3 = nullptr;
-    DevGrp* d_grps = nullptr;
-    double* d_umat = nullptr;     // [batch][nsubs][12][64]
-    double2* d_rpart = nullptr;   // sweep plan only: [batch][nsubs][ntiles][256]
-    int u_level = kUNone;         // how much of d_umat matches the coefficients in use (ULevel)
     int family() const { return v3 ? 3 : (v2 ? 2 : 1); }
+};
+static_assert(std::is_copy_constructible<HostPlan>::value && std::is_copy_assignable<HostPlan>::value,
+              "a cached plan is copied out of the cache: it owns no device memory (a buffer member would make it move-only)");
+
+// ... and with its device tables: one workspace's own
+struct DevPlan : HostPlan {
+    DevBuf<DevStage> d_stages;
+    DevBuf<DevOp> d_ops;
+    DevBuf<DevSub> d_subs;
+    DevBuf<DevMop> d_mops;
+    DevBuf<DevSub3> d_subs3;
+    DevBuf<DevGrp> d_grps;
+    DevBuf<double> d_umat;        // [batch][nsubs][12][64]
+    DevBuf<double2> d_rpart;      // sweep plan only: [batch][nsubs][ntiles][256]
+    int u_level = kUNone;         // how much of d_umat matches the coefficients in use (ULevel)
+    DevPlan& operator=(const HostPlan& host) { HostPlan::operator=(host); return *this; }   // the host part alone
 };
 
 // What a derived list (a tile list, the virtual lhs pattern, a route verdict, the tiles of a partial Z) was built for: the support of
@@ -117,40 +128,39 @@ struct ProjRoute {
     std::vector<int> rest;         // their indices, in execution order
     DevPlan vsw;                   // sweep plan of the virtual register
     DevPlan vinv;                  // ... walked backwards (the objective's V^H by projection: Y_0 = (later stages)^H proj(y))
-    double2* vm = nullptr;         // [batch][2][2^nvp]: the virtual lhs pattern M_0 ...
-    double2* vy = nullptr;         // ... the virtual z ...
-    double2* vme = nullptr;        // ... and M after the later stages' gates (objective by projection)
-    double2* cpart = nullptr;      // partial tile products of the fused pass when its walk is split (few lanes)
+    DevBuf<double2> vm;            // [batch][2][2^nvp]: the virtual lhs pattern M_0 ...
+    DevBuf<double2> vy;            // ... the virtual z ...
+    DevBuf<double2> vme;           // ... and M after the later stages' gates (objective by projection)
+    DevBuf<double2> cpart;         // partial tile products of the fused pass when its walk is split (few lanes)
     int cpart_shares = 0;
     int vy_copies = 1;             // vy holds this many copies of the virtual z (fused pass over more than 256 summed values: partial sums)
     unsigned l0_mask = 0;          // address bits local to the first stage
-    unsigned* d_tab = nullptr;     // off_t | off_usblk | off_cb
+    DevBuf<unsigned> d_tab;        // off_t | off_usblk | off_cb
     std::vector<unsigned> h_tab;
     unsigned ff_mask = 0, cb_mask = 0, tf_mask = 0;
-    TileItem* d_items = nullptr;   // [2 batch ntiles_v]
-    int* d_count = nullptr;
-    int* d_lane_parts = nullptr;   // [batch]
+    DevBuf<TileItem> d_items;      // [2 batch ntiles_v]
+    DevBuf<int> d_count;
+    DevBuf<int> d_lane_parts;      // [batch]
     ListKey init_key;              // vm holds the pattern M_0 (and d_items the list) of this first-stage list (single virtual stage: nothing overwrites vm)
 };
 
 // aqc_ws_plan.cpp
-void lower_plan(const Program& prog, const Plan& plan, DevPlan& out, int reg_bits, bool with_dots, bool mfma = false, bool presplit = false, int beam_width = 64);
-int upload_plan(DevPlan& p);
-void free_plan(DevPlan& p);   // the device side of a plan
+void lower_plan(const Program& prog, const Plan& plan, HostPlan& out, int reg_bits, bool with_dots, bool mfma = false, bool presplit = false, int beam_width = 64);
+int upload_plan(DevPlan& p);   // the device tables of a lowered plan
 Plan mirror_plan(const Plan& plan);   // the same stages and sub-stages walked backwards: the plan of V^H whose intermediate states are the sweep's
 
 }  // namespace aqc
 
 // the two handle types of the C ABI live in the global namespace (include/aqc_hip.h)
-using aqc::DevPlan; using aqc::Program; using aqc::UJob;
+using aqc::DevBuf; using aqc::DevPlan; using aqc::HostPlan; using aqc::PinBuf; using aqc::Program; using aqc::UJob;
 
 struct aqc_ctx {
     Program prog;
-    std::mutex mu;
+    std::recursive_mutex mu;   // (recursive: a one-shot entry point holds it while it creates its workspace, which looks a plan up under it)
     // lowered plans (host side: stages, sub-stages, micro-ops) by (which, col_bits, tile bits, low bits, family): workspaces
     // of the same shape -- one per batch of jobs in the drivers -- share the planning work (the sub-stage search of a
     // deep Trotter ansatz takes a few tenths of a second)
-    std::map<std::vector<int>, DevPlan> plan_cache;
+    std::map<std::vector<int>, HostPlan> plan_cache;
     std::map<int, aqc_ws*> oneshot;  // ncols -> batch-1 workspace used by the host-pointer entry points
 };
 
@@ -161,42 +171,39 @@ struct aqc_ws {
     hipStream_t stream = nullptr;
     DevPlan fwd, inv, sweep;
     double* d_thetas = nullptr;       // parameters in use (own buffer or a slice of the bank)
-    double* d_thetas_own = nullptr;
-    double* d_theta_bank = nullptr;
+    DevBuf<double> d_thetas_own;
+    DevBuf<double> d_theta_bank;
     int bank_sets = 0, gather_count = 0;
-    double* d_coef = nullptr;
-    double2* bufs[AQC_NUM_BUFS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double* h_pin = nullptr;           // pinned staging: thetas | grads | gathered
+    DevBuf<double> d_coef;
+    DevBuf<double2> bufs[AQC_NUM_BUFS];
+    PinBuf<double> h_pin;              // pinned staging: thetas | grads | gathered
     size_t pin_thetas = 0, pin_grads = 0, pin_small = 0;
-    double2* d_partial = nullptr;
-    double2* d_grads = nullptr;
+    DevBuf<double2> d_partial;
+    DevBuf<double2> d_grads;
     double* mirror_grads = nullptr;    // set by aqc_ws_eval around its launches: pinned host copies written by the kernels
     double* mirror_small = nullptr;
-    double2* d_small = nullptr;  // gather / vdot results
-    double2* d_vdot_part = nullptr;
-    double2* d_vdot_out = nullptr;
-    long long* d_index = nullptr;
-    long long* d_tmp_index = nullptr;   // one-shot gather / vdot: never disturb the persistent gather set-up
-    double2* d_tmp_small = nullptr;
-    size_t tmp_index_cap = 0, tmp_small_cap = 0;
-    long long* d_basis_index = nullptr;   // [batch], set_basis only (keeps the gather set-up intact)
-    long long* d_combo_prev[AQC_NUM_BUFS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // set_combo: positions written last time
+    DevBuf<double2> d_small;     // gather / vdot results (grow-only, like d_index and the two temporaries)
+    DevBuf<double2> d_vdot_part;
+    DevBuf<double2> d_vdot_out;
+    DevBuf<long long> d_index;
+    DevBuf<long long> d_tmp_index;      // one-shot gather / vdot: never disturb the persistent gather set-up
+    DevBuf<double2> d_tmp_small;
+    DevBuf<long long> d_basis_index;      // [batch], set_basis only (keeps the gather set-up intact)
+    DevBuf<long long> d_combo_prev[AQC_NUM_BUFS];   // set_combo: positions written last time
     bool combo_valid[AQC_NUM_BUFS] = {false, false, false, false, false, false};   // buffer holds exactly that sparse pattern
     std::vector<long long> combo_last_elem[AQC_NUM_BUFS];   // host copy of the pattern (positions, coefficients) the HOST wrote last; device-side
     std::vector<double> combo_last_coef[AQC_NUM_BUFS];      // writers (lb_prepare) clear it
     // aqc_ws_surrogate_eval: device block [f B | fidelity B | weight B | hs 2 B S | max_no B ints], its pinned mirror
-    void* d_sur = nullptr;
-    void* h_sur = nullptr;
+    DevBuf<char> d_sur;
+    PinBuf<char> h_sur;
     int sur_states = 0;
-    double* d_sur_real = nullptr;     // real parts of the gradient when only those are asked for
-    size_t sur_real_cap = 0;
-    long long* d_combo_index = nullptr;   // [batch][2] staging of set_combo
-    double2* d_combo_coef = nullptr;      // [batch][2]
-    size_t small_cap = 0, index_cap = 0;
-    int* d_theta_slots = nullptr;
-    int* d_slot_theta = nullptr;       // slot -> theta when every theta has exactly one slot (grads_direct), see rgrad_kernel
+    DevBuf<double> d_sur_real;        // real parts of the gradient when only those are asked for (grow-only)
+    DevBuf<long long> d_combo_index;      // [batch][2] staging of set_combo
+    DevBuf<double2> d_combo_coef;         // [batch][2]
+    DevBuf<int> d_theta_slots;
+    DevBuf<int> d_slot_theta;          // slot -> theta when every theta has exactly one slot (grads_direct), see rgrad_kernel
     bool grads_direct = false;
-    int* d_slot_ntiles = nullptr;
+    DevBuf<int> d_slot_ntiles;
     int nslots = 0, vdot_parts = 0;
     bool coef_valid = false;
     bool need_coef = false;           // something besides the stage kernels reads d_coef (coordinate descent)
@@ -204,31 +211,27 @@ struct aqc_ws {
     // D2H copies) captured once per call signature and replayed -- one launch instead of ~11 host calls per evaluation
     std::map<std::vector<long long>, hipGraphExec_t> graphs;
     bool capturing = false;
-    UJob* d_ujobs = nullptr;          // family 3: [V^H subs | sweep subs | virtual sweep subs | V subs]; ujobs_mirror: no V^H jobs, the sweep's write both operand sets
+    DevBuf<UJob> d_ujobs;             // family 3: [V^H subs | sweep subs | virtual sweep subs | V subs]; ujobs_mirror: no V^H jobs, the sweep's write both operand sets
     bool ujobs_mirror = false;
     // The jobs the objective-by-projection route reads, as a compact list of their own: [V^H's last stage (its own jobs only) | the
     // sweep's first stage | virtual sweep].  Null: the route builds everything (no projected route, or AQC_UBUILD_SUBSET=0).
-    UJob* d_ujobs_route = nullptr;
+    DevBuf<UJob> d_ujobs_route;
     int n_ujobs_route = 0;
     struct MpsSlot {
         std::vector<int> dims;          // n + 1 bond dimensions
         std::vector<size_t> offset;     // element offset of site q inside d_t
-        double2* d_t = nullptr;         // [q][2][dims[q]][dims[q+1]], lambda folded in
-        size_t cap = 0;                 // capacity of d_t (grow-only: re-uploads of the same shape allocate nothing)
+        DevBuf<double2> d_t;            // [q][2][dims[q]][dims[q+1]], lambda folded in (grow-only: re-uploads of the same shape allocate nothing)
     } mps[AQC_MPS_SLOTS];
-    double* d_mps_lam = nullptr;        // staging of the packed Schmidt vectors (grow-only)
-    size_t mps_lam_cap = 0;
-    double2* d_mps_scratch = nullptr;
-    size_t mps_scratch_cap = 0;
+    DevBuf<double> d_mps_lam;           // staging of the packed Schmidt vectors (grow-only)
+    DevBuf<double2> d_mps_scratch;      // (grow-only)
     // device pointer tables of the batched MPS -> dense contraction: a few resident sets, found again by their contents (an
     // optimisation converts the same operands into the same lanes evaluation after evaluation: no upload, no synchronisation)
-    struct MpsTabs { std::vector<const void*> host; const void** dev = nullptr; size_t cap = 0; unsigned long long tick = 0; };
+    struct MpsTabs { std::vector<const void*> host; DevBuf<const void*> dev; unsigned long long tick = 0; };
     // coordinate descent as one persistent launch: the walk's step list, thetas [batch][T] and objective values on the device
-    void* d_cd_prog = nullptr;
+    DevBuf<aqc::CdSegHost> d_cd_prog;
     int cd_nsteps = 0;
-    double* d_cd_thetas = nullptr;
-    double* d_cd_fobj = nullptr;
-    size_t cd_fobj_cap = 0;
+    DevBuf<double> d_cd_thetas;
+    DevBuf<double> d_cd_fobj;           // (grow-only)
     MpsTabs mps_tabs[32];   // resident pointer-table sets (one per distinct chain: operands x lanes x bond dimensions)
     unsigned long long mps_tabs_tick = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, pev0 = nullptr, pev1 = nullptr;
@@ -248,21 +251,20 @@ struct aqc_ws {
     bool skipw_enabled = false;    // AQC_SKIP_ZERO_W=1: skip zero groups / K-steps of w inside a stage (exact; measured slower, off by default)
     long sparse_min_items = 512;   // the sparse route pays from this many (tile, lane) items per stage launch (AQC_SPARSE_MIN_ITEMS)
     unsigned long long supp_version[AQC_NUM_BUFS] = {0, 0, 0, 0, 0, 0};   // bumped whenever d_combo_prev[buf] (the support of a sparse lhs) changes
-    aqc::TileItem* d_sw_items = nullptr;    // first-stage items of the sparse sweep [2 batch], and the tiles to clear in W
-    aqc::TileItem* d_sw_clear = nullptr;
-    int* d_sw_counts = nullptr;             // [0] items, [1] tiles to clear
-    int* d_sw_lane_parts = nullptr;         // items (= partial-R slots in use) per lane
-    int* d_sw_prev_tiles = nullptr;         // [batch][2] tiles of W written by the list in use
+    DevBuf<aqc::TileItem> d_sw_items;       // first-stage items of the sparse sweep [2 batch], and the tiles to clear in W
+    DevBuf<aqc::TileItem> d_sw_clear;
+    DevBuf<int> d_sw_counts;                // [0] items, [1] tiles to clear
+    DevBuf<int> d_sw_lane_parts;            // items (= partial-R slots in use) per lane
+    DevBuf<int> d_sw_prev_tiles;            // [batch][2] tiles of W written by the list in use
     int sw_lists_built = 0;                 // bit 0: the sweep's list has been built at least once, bit 1: V^H's
     aqc::ListKey sw_items_key;              // the list in d_sw_items belongs to this lhs support
-    double2* w2 = nullptr;                  // second scratch pair of the sparse route (plans of >= 3 stages)
-    double2* zw2 = nullptr;
+    DevBuf<double2> w2;                     // second scratch pair of the sparse route (plans of >= 3 stages)
+    DevBuf<double2> zw2;
     // "objective" V^H: the last stage of the mirrored V^H runs only over the tiles its readers touch -- the registered gather
     // indices and the support of the lhs state -- and Z is completed on demand (ensure_z_full) while the checkpoint is valid
     bool lazy_z_enabled = true;             // AQC_LAZY_Z=0: V^H always writes all of Z
     bool z_full = true;                     // Z holds V^H y everywhere (false: on the tiles of d_vd_items only)
-    aqc::TileItem* d_vd_items = nullptr;    // [batch][2 + gather_count]
-    size_t vd_items_cap = 0;
+    DevBuf<aqc::TileItem> d_vd_items;       // [batch][2 + gather_count] (grow-only)
     unsigned long long gather_gen = 0;      // bumped by aqc_ws_gather_setup
     aqc::ListKey vd_key;                    // what d_vd_items was built from
     aqc::ListKey z_key;                     // what the tiles of a partial Z were chosen for
@@ -278,18 +280,16 @@ struct aqc_ws {
     bool projb_ok = false;
     // sketched AQC (aqc_ws_sketch.cpp): the d x d target(s) and everything a device-resident ADAM run keeps between its launches
     struct Sketch {
-        double2* target = nullptr;      // [batch or 1][d][d]
+        DevBuf<double2> target;         // [batch or 1][d][d]
         bool shared = false;
-        double2* qr_part = nullptr;     // gram partials [batch][slabs][k][k]
-        double2* qr_rinv = nullptr;     // [batch][k][k]
-        double2* tmp = nullptr;         // [batch] lanes of scratch (U^H Omega)
-        int* status = nullptr;          // [batch] QR status words
-        int* idx = nullptr;             // alt column indices [sets][batch][k]
-        size_t idx_cap = 0;
-        double* adam = nullptr;         // m | v | best_x [batch][T] each, then best_f | lr [batch]
-        int* adam_i = nullptr;          // t | nit | flag [batch]
-        double* profile = nullptr;      // [batch][profile_cap]
-        size_t profile_cap = 0;
+        DevBuf<double2> qr_part;        // gram partials [batch][slabs][k][k]
+        DevBuf<double2> qr_rinv;        // [batch][k][k]
+        DevBuf<double2> tmp;            // [batch] lanes of scratch (U^H Omega)
+        DevBuf<int> status;             // [batch] QR status words
+        DevBuf<int> idx;                // alt column indices [sets][batch][k] (grow-only)
+        DevBuf<double> adam;            // m | v | best_x [batch][T] each, then best_f | lr [batch]
+        DevBuf<int> adam_i;             // t | nit | flag [batch]
+        DevBuf<double> profile;         // [batch][capacity / batch] (grow-only)
         bool adam_started = false;
     } sk;
     bool profile = false;
@@ -342,9 +342,6 @@ inline bool direct_thetas(const aqc_ws* ws, bool zero_copy) {
 // aqc_api.cpp
 int check_buf(const aqc_ws* ws, int buf);
 int check_block_range(const aqc_ws* ws, int block_from, int block_to);
-int ensure_small(aqc_ws* ws, size_t n_cplx);
-int ensure_tmp(aqc_ws* ws, size_t n_index, size_t n_cplx);
-int ensure_index(aqc_ws* ws, size_t n);
 int ensure_coef(aqc_ws* ws);
 int copy_in(aqc_ws* ws, double2* dst, const double* src, size_t rows);
 int copy_out(aqc_ws* ws, double* dst, const double2* src, size_t rows);
@@ -381,7 +378,6 @@ void drop_graphs(aqc_ws* ws);
 // aqc_ws_project.cpp
 void proj_plan(aqc_ws* ws, int low_bits);   // decides the route and lowers the virtual plan (host only)
 int proj_alloc(aqc_ws* ws);                 // its device side (plan tables, buffers, offset tables)
-void proj_free(aqc_ws* ws);
 bool sweep_route_projected(const aqc_ws* ws, bool sparse);
 bool projected_pairs(const aqc_ws* ws);      // the route's independent tile launches run in pairs
 Stage3Args virtual_stage3_args(aqc_ws* ws, const DevPlan& v, size_t s);   // stage s of a virtual plan (vsw, vinv) on the virtual register, over its item list

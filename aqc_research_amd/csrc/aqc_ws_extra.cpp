@@ -5,7 +5,12 @@ using namespace aqc;
 
 extern "C" {
 
-static int mps_scratch(aqc_ws* ws, size_t n_cplx);
+// the workspace's grow-only scratch (coordinate descent chain, MPS helpers)
+static int mps_scratch(aqc_ws* ws, size_t n_cplx) {
+    if (n_cplx <= ws->d_mps_scratch.capacity()) return 0;
+    HIP_OK(hipStreamSynchronize(ws->stream));   // launches in flight may still read the block that goes
+    return ws->d_mps_scratch.reserve(n_cplx);
+}
 
 // ---- dense zgemm with host pointers ---------------------------------------------------------------
 
@@ -18,34 +23,21 @@ int aqc_zgemm(int device, int conj_trans_a, int M, int N, int K, const double* A
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: the aqc_hip path has no CPU fallback");
     if (device < 0 || device >= ndev) return fail("device out of range");
     HIP_OK(hipSetDevice(device));
-    double2 *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    DevBuf<double2> dA, dB, dC;
     const size_t na = (size_t)a_rows * lda, nb = (size_t)K * ldb, nc = (size_t)M * ldc;
-    int rc = 0;
-    hipError_t e = hipMalloc((void**)&dA, na * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void**)&dB, nb * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void**)&dC, nc * sizeof(double2));
-    if (e == hipSuccess) e = hipMemcpy(dA, A, na * sizeof(double2), hipMemcpyHostToDevice);
+    if (dA.alloc(na) || dB.alloc(nb) || dC.alloc(nc)) return 1;
+    hipError_t e = hipMemcpy(dA, A, na * sizeof(double2), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dB, B, nb * sizeof(double2), hipMemcpyHostToDevice);
     if (e == hipSuccess && ldc != N) e = hipMemcpy(dC, C, nc * sizeof(double2), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = launch_zgemm(conj_trans_a != 0, false, M, N, K, dA, lda, dB, ldb, dC, ldc, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(C, dC, nc * sizeof(double2), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail("aqc_zgemm failed: %s", hipGetErrorString(e));
-    if (dA) (void)hipFree(dA);
-    if (dB) (void)hipFree(dB);
-    if (dC) (void)hipFree(dC);
-    return rc;
+    return e == hipSuccess ? 0 : fail("aqc_zgemm failed: %s", hipGetErrorString(e));
 }
 
 // ---- gate-level building blocks (one-shot, host pointers) ---------------------------------------
 
 namespace {
-
-struct DevBuf {   // RAII for the one-shot calls
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
 
 int gate_args_ok(int device, int n, int64_t ncols) {
     if (n < 1 || n > 30 || ncols < 1 || ((size_t)ncols << n) > ((size_t)1 << kMaxBits)) return fail("invalid array shape");
@@ -63,12 +55,12 @@ int aqc_gate_1q(int device, int n, int64_t ncols, int qubit, const double* gate,
     if (qubit < 0 || qubit >= n) return fail("qubit out of range");
     HIP_OK(hipSetDevice(device));
     const size_t bytes = sizeof(double2) * ((size_t)ncols << n);
-    DevBuf d;
-    HIP_OK(d.alloc(bytes));
-    HIP_OK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-    HIP_OK(launch_gate1q(d.p, d.p, n, (size_t)ncols, qubit, gate, nullptr));
+    DevBuf<double2> d;
+    if (d.alloc((size_t)ncols << n)) return 1;
+    HIP_OK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    HIP_OK(launch_gate1q(d, d, n, (size_t)ncols, qubit, gate, nullptr));
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -78,12 +70,12 @@ int aqc_gate_2q(int device, int n, int64_t ncols, int ctrl, int targ, const doub
     if (n < 2 || ctrl < 0 || ctrl >= n || targ < 0 || targ >= n || ctrl == targ) return fail("invalid qubit pair");
     HIP_OK(hipSetDevice(device));
     const size_t bytes = sizeof(double2) * ((size_t)ncols << n);
-    DevBuf d;
-    HIP_OK(d.alloc(bytes));
-    HIP_OK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-    HIP_OK(launch_gate2q(d.p, d.p, n, (size_t)ncols, ctrl, targ, gate, nullptr));
+    DevBuf<double2> d;
+    if (d.alloc((size_t)ncols << n)) return 1;
+    HIP_OK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    HIP_OK(launch_gate2q(d, d, n, (size_t)ncols, ctrl, targ, gate, nullptr));
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -94,14 +86,12 @@ int aqc_gate_dot(int device, int n, int64_t ncols, int kind, int q0, int q1, con
     if (kind == 3 && (n < 2 || q1 < 0 || q1 >= n || q1 == q0)) return fail("invalid qubit pair");
     HIP_OK(hipSetDevice(device));
     const size_t bytes = sizeof(double2) * ((size_t)ncols << n);
-    DevBuf dw, dz, dp;
-    HIP_OK(dw.alloc(bytes));
-    HIP_OK(dz.alloc(bytes));
-    HIP_OK(dp.alloc(sizeof(double2) * (size_t)(gate_dot_parts(n, (size_t)ncols, kind) + 1)));
-    HIP_OK(hipMemcpy(dw.p, w, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dz.p, z, bytes, hipMemcpyHostToDevice));
-    double2* parts = static_cast<double2*>(dp.p);
-    HIP_OK(launch_gate_dot(dw.p, dz.p, n, (size_t)ncols, kind, q0, q1, parts + 1, parts, nullptr));
+    DevBuf<double2> dw, dz, dp;
+    if (dw.alloc((size_t)ncols << n) || dz.alloc((size_t)ncols << n) || dp.alloc((size_t)(gate_dot_parts(n, (size_t)ncols, kind) + 1))) return 1;
+    HIP_OK(hipMemcpy(dw, w, bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dz, z, bytes, hipMemcpyHostToDevice));
+    double2* parts = dp;
+    HIP_OK(launch_gate_dot(dw, dz, n, (size_t)ncols, kind, q0, q1, parts + 1, parts, nullptr));
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(out, parts, sizeof(double2), hipMemcpyDeviceToHost));
     return 0;
@@ -147,18 +137,12 @@ int aqc_ws_cd_sweeps(aqc_ws* ws, double* thetas_io, double* fobj, int nsweeps, i
             }
             segs.push_back(sg);
         }
-        HIP_OK(hipMalloc(&ws->d_cd_prog, segs.size() * sizeof(aqc::CdSegHost)));
-        HIP_OK(hipMemcpy(ws->d_cd_prog, segs.data(), segs.size() * sizeof(aqc::CdSegHost), hipMemcpyHostToDevice));
+        if (ws->d_cd_prog.upload(segs, 0)) return 1;
         ws->cd_nsteps = (int)segs.size();
-        HIP_OK(hipMalloc((void**)&ws->d_cd_thetas, sizeof(double) * (size_t)ws->batch * T));
+        if (ws->d_cd_thetas.reserve((size_t)ws->batch * T)) return 1;
     }
     const size_t nf = (size_t)ws->batch * nsweeps;
-    if (nf > ws->cd_fobj_cap) {
-        if (ws->d_cd_fobj) HIP_OK(hipFree(ws->d_cd_fobj));
-        ws->d_cd_fobj = nullptr;
-        HIP_OK(hipMalloc((void**)&ws->d_cd_fobj, sizeof(double) * nf));
-        ws->cd_fobj_cap = nf;
-    }
+    if (ws->d_cd_fobj.reserve(nf)) return 1;
     HIP_OK(hipMemcpyAsync(ws->d_cd_thetas, thetas_io, sizeof(double) * (size_t)ws->batch * T, hipMemcpyHostToDevice, ws->stream));
     {
         ProfScope ps(ws, AQC_K_MISC);
@@ -185,14 +169,14 @@ int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io, double* fobj) {
     if (aqc_ws_apply(ws, 1, AQC_BUF_Y, AQC_BUF_Z)) return 1;          // z = V^H U      (core_op_matrix.py:806-810)
     if (aqc_ws_set_identity(ws, AQC_BUF_X)) return 1;                 // w = I
     if (before_write(ws, AQC_BUF_X) || before_write(ws, AQC_BUF_Z)) return 1;   // the chain below rewrites both in place
-    double* d_theta_out = nullptr;
-    HIP_OK(hipMalloc((void**)&d_theta_out, sizeof(double) * T));
+    DevBuf<double> d_theta_out;   // (every return releases it; the chain's own exit synchronises first)
+    if (d_theta_out.alloc(T)) return 1;
     HIP_OK(hipMemcpyAsync(d_theta_out, ws->d_thetas_own, sizeof(double) * T, hipMemcpyDeviceToDevice, ws->stream));
     double2* w = ws->bufs[AQC_BUF_X];
     double2* z = ws->bufs[AQC_BUF_Z];
     const size_t npairs = ws->lane_elems >> 1, ngroups = ws->lane_elems >> 2;
     const int nparts = cd_num_parts(npairs);
-    if (mps_scratch(ws, 2 * (size_t)nparts)) { (void)hipFree(d_theta_out); return 1; }
+    if (mps_scratch(ws, 2 * (size_t)nparts)) return 1;
     double2* part = ws->d_mps_scratch;
     int rc = 0;
     auto step = [&](int qubit, int kind, int tindex) -> int {
@@ -225,22 +209,11 @@ int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io, double* fobj) {
         }
     }
     (void)hipStreamSynchronize(ws->stream);
-    (void)hipFree(d_theta_out);
     return rc;
 }
 
 // ---- MPS helpers ------------------------------------------------------------------------------
 
-static int mps_scratch(aqc_ws* ws, size_t n_cplx) {
-    if (n_cplx <= ws->mps_scratch_cap) return 0;
-    HIP_OK(hipStreamSynchronize(ws->stream));
-    if (ws->d_mps_scratch) HIP_OK(hipFree(ws->d_mps_scratch));
-    ws->d_mps_scratch = nullptr;
-    ws->mps_scratch_cap = 0;
-    HIP_OK(hipMalloc((void**)&ws->d_mps_scratch, n_cplx * sizeof(double2)));
-    ws->mps_scratch_cap = n_cplx;
-    return 0;
-}
 
 static int check_mps_slot(const aqc_ws* ws, int slot, bool need_data) {
     if (!ws) return fail("null workspace");
@@ -276,20 +249,9 @@ int aqc_ws_mps_upload(aqc_ws* ws, int slot, const int32_t* dims, const double* g
     m.offset[n] = total;
     sites.offset[n] = total;
     sites.total = total;
-    if (total > m.cap || lam_total > ws->mps_lam_cap) {   // grow-only device buffers
+    if (total > m.d_t.capacity() || lam_total > ws->d_mps_lam.capacity()) {   // grow-only device buffers
         HIP_OK(hipStreamSynchronize(ws->stream));
-        if (total > m.cap) {
-            if (m.d_t) HIP_OK(hipFree(m.d_t));
-            m.d_t = nullptr; m.cap = 0;
-            HIP_OK(hipMalloc((void**)&m.d_t, total * sizeof(double2)));
-            m.cap = total;
-        }
-        if (lam_total > ws->mps_lam_cap) {
-            if (ws->d_mps_lam) HIP_OK(hipFree(ws->d_mps_lam));
-            ws->d_mps_lam = nullptr; ws->mps_lam_cap = 0;
-            HIP_OK(hipMalloc((void**)&ws->d_mps_lam, std::max<size_t>(lam_total, 1) * sizeof(double)));
-            ws->mps_lam_cap = std::max<size_t>(lam_total, 1);
-        }
+        if (m.d_t.reserve(total) || ws->d_mps_lam.reserve(lam_total)) return 1;
     }
     HIP_OK(hipMemcpyAsync(m.d_t, gammas, total * sizeof(double2), hipMemcpyHostToDevice, ws->stream));
     if (lam_total) {
@@ -384,12 +346,7 @@ static int mps_to_vec_batch_uniform(aqc_ws* ws, int count, const int32_t* slots,
         }
         if (!hit) {
             HIP_OK(hipStreamSynchronize(ws->stream));   // launches in flight may still read the set that is recycled
-            if (tabs.size() > lru->cap) {
-                if (lru->dev) HIP_OK(hipFree(lru->dev));
-                lru->dev = nullptr; lru->cap = 0; lru->host.clear();
-                HIP_OK(hipMalloc((void**)&lru->dev, tabs.size() * sizeof(void*)));
-                lru->cap = tabs.size();
-            }
+            if (lru->dev.reserve(tabs.size())) return 1;
             lru->host = tabs;   // (stays alive next to the device copy: nothing to wait for after the upload)
             HIP_OK(hipMemcpyAsync(lru->dev, lru->host.data(), tabs.size() * sizeof(void*), hipMemcpyHostToDevice, ws->stream));
             hit = lru;

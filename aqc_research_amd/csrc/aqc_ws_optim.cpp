@@ -26,28 +26,15 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
     HIP_OK(hipStreamSynchronize(st_));
     // one allocation for all double arrays, one for the complex ones, one for the integers
     const size_t nd = BT * (7 + 2 * (size_t)memory) + (size_t)B * (6 + memory + 2 + 2);
-    double* dd = nullptr;
-    double2* dc = nullptr;
-    int* di = nullptr;
-    long long* dl = nullptr;
-    int* h_flags = nullptr;
-    auto cleanup = [&]() {
-        if (dd) (void)hipFree(dd);
-        if (dc) (void)hipFree(dc);
-        if (di) (void)hipFree(di);
-        if (dl) (void)hipFree(dl);
-        if (h_flags) (void)hipHostFree(h_flags);
-    };
-#define LB_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail("%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
-#define LB_TRY(expr) do { if ((expr) != 0) { cleanup(); return 1; } } while (0)
-    LB_OK(hipMalloc((void**)&dd, nd * sizeof(double)));
-    LB_OK(hipMalloc((void**)&dc, (3 * BT + 3 * BS) * sizeof(double2)));
-    LB_OK(hipMalloc((void**)&di, (size_t)(3 * B + 8) * sizeof(int)));
-    LB_OK(hipMalloc((void**)&dl, (size_t)B * sizeof(long long)));
-    if (!ws->d_combo_prev[AQC_BUF_X2]) LB_OK(hipMalloc((void**)&ws->d_combo_prev[AQC_BUF_X2], sizeof(long long) * 2 * B));
-    LB_OK(hipHostMalloc((void**)&h_flags, 8 * sizeof(int), hipHostMallocDefault));
-    LB_OK(hipMemsetAsync(dd, 0, nd * sizeof(double), st_));
-    LB_OK(hipMemsetAsync(di, 0, (size_t)(3 * B + 8) * sizeof(int), st_));
+    DevBuf<double> dd;
+    DevBuf<double2> dc;
+    DevBuf<int> di;
+    DevBuf<long long> dl;
+    PinBuf<int> h_flags;
+    if (dd.alloc(nd) || dc.alloc(3 * BT + 3 * BS) || di.alloc((size_t)(3 * B + 8)) || dl.alloc(B)) return 1;
+    if (ws->d_combo_prev[AQC_BUF_X2].reserve(2 * (size_t)B) || h_flags.alloc(8)) return 1;
+    HIP_OK(hipMemsetAsync(dd, 0, nd * sizeof(double), st_));
+    HIP_OK(hipMemsetAsync(di, 0, (size_t)(3 * B + 8) * sizeof(int), st_));
     LbState L;
     double* p = dd;
     auto take = [&](size_t n) { double* r = p; p += n; return r; };
@@ -73,14 +60,14 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
     {   // weight = 1, max_no = 0, active = 1, X2 empty
         std::vector<double> ones(B, 1.0);
         std::vector<int> one_i(B, 1);
-        LB_OK(hipMemcpyAsync(L.weight, ones.data(), sizeof(double) * B, hipMemcpyHostToDevice, st_));
-        LB_OK(hipMemcpyAsync(L.active, one_i.data(), sizeof(int) * B, hipMemcpyHostToDevice, st_));
-        LB_OK(hipMemsetAsync(dl, 0, sizeof(long long) * B, st_));
-        LB_OK(hipMemsetAsync(d_prev, 0xff, sizeof(long long) * 2 * B, st_));   // -1: nothing written yet
-        LB_OK(hipMemcpyAsync(L.x, x0, sizeof(double) * BT, hipMemcpyHostToDevice, st_));
-        LB_OK(hipMemsetAsync(ws->bufs[AQC_BUF_X2], 0, sizeof(double2) * (size_t)B * ws->lane_elems, st_));
+        HIP_OK(hipMemcpyAsync(L.weight, ones.data(), sizeof(double) * B, hipMemcpyHostToDevice, st_));
+        HIP_OK(hipMemcpyAsync(L.active, one_i.data(), sizeof(int) * B, hipMemcpyHostToDevice, st_));
+        HIP_OK(hipMemsetAsync(dl, 0, sizeof(long long) * B, st_));
+        HIP_OK(hipMemsetAsync(d_prev, 0xff, sizeof(long long) * 2 * B, st_));   // -1: nothing written yet
+        HIP_OK(hipMemcpyAsync(L.x, x0, sizeof(double) * BT, hipMemcpyHostToDevice, st_));
+        HIP_OK(hipMemsetAsync(ws->bufs[AQC_BUF_X2], 0, sizeof(double2) * (size_t)B * ws->lane_elems, st_));
         lhs_support_changed(ws, AQC_BUF_X2);   // (nothing, so far)
-        LB_OK(hipStreamSynchronize(st_));
+        HIP_OK(hipStreamSynchronize(st_));
     }
     int64_t nfev = 0;
     auto read_flags = [&]() -> int {
@@ -103,51 +90,48 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
         ++nfev;
         return 0;
     };
-    LB_OK(hipMemcpyAsync(ws->d_thetas_own, L.x, sizeof(double) * BT, hipMemcpyDeviceToDevice, st_));
-    LB_TRY(evaluate(1, L.f, L.g, L.cur_hs, L.cur_g0));
+    HIP_OK(hipMemcpyAsync(ws->d_thetas_own, L.x, sizeof(double) * BT, hipMemcpyDeviceToDevice, st_));
+    if (evaluate(1, L.f, L.g, L.cur_hs, L.cur_g0)) return 1;
     int count = 0;
     for (int it = 0; it < maxiter; ++it) {
-        LB_OK(hipMemsetAsync(d_flags, 0, 4 * sizeof(int), st_));
-        LB_OK(lb_active(L, gtol, fid_thr, d_flags, st_));
-        LB_TRY(read_flags());
+        HIP_OK(hipMemsetAsync(d_flags, 0, 4 * sizeof(int), st_));
+        HIP_OK(lb_active(L, gtol, fid_thr, d_flags, st_));
+        if (read_flags()) return 1;
         if (!h_flags[2]) break;
-        LB_OK(lb_direction(L, count, st_));
-        LB_OK(lb_copy_raw(L, st_));
+        HIP_OK(lb_direction(L, count, st_));
+        HIP_OK(lb_copy_raw(L, st_));
         for (int bt = 0; bt < max_backtracks; ++bt) {
-            LB_OK(lb_trial(L, ws->d_thetas_own, st_));
-            LB_TRY(evaluate(0, ft, gt, raw_hs_t, raw_g0_t));
-            LB_OK(hipMemsetAsync(d_flags + 3, 0, sizeof(int), st_));
-            LB_OK(lb_armijo(L, 1e-4, ws->d_thetas_own, ft, raw_hs_t, raw_g0_t, d_flags, st_));
+            HIP_OK(lb_trial(L, ws->d_thetas_own, st_));
+            if (evaluate(0, ft, gt, raw_hs_t, raw_g0_t)) return 1;
+            HIP_OK(hipMemsetAsync(d_flags + 3, 0, sizeof(int), st_));
+            HIP_OK(lb_armijo(L, 1e-4, ws->d_thetas_own, ft, raw_hs_t, raw_g0_t, d_flags, st_));
             // the probe of the state update rides on the same read of the flags (it is only used once no lane backtracks any more)
-            LB_OK(hipMemsetAsync(d_flags + 1, 0, sizeof(int), st_));
-            LB_OK(lb_probe(L, L.acc_hs, d_flags, st_));
-            LB_TRY(read_flags());
+            HIP_OK(hipMemsetAsync(d_flags + 1, 0, sizeof(int), st_));
+            HIP_OK(lb_probe(L, L.acc_hs, d_flags, st_));
+            if (read_flags()) return 1;
             if (!h_flags[3]) break;
         }
         // state update at the accepted points: from their raw results when no lane would lead with a flip state,
         // else by a device evaluation at x_new (the second sweep depends on the state chosen now)
         if (h_flags[1]) {   // (the last round's probe: nothing has touched the accepted points since)
-            LB_OK(hipMemcpyAsync(ws->d_thetas_own, L.x_new, sizeof(double) * BT, hipMemcpyDeviceToDevice, st_));
-            LB_TRY(evaluate(1, f_acc, g_acc, L.acc_hs, L.acc_g0));
+            HIP_OK(hipMemcpyAsync(ws->d_thetas_own, L.x_new, sizeof(double) * BT, hipMemcpyDeviceToDevice, st_));
+            if (evaluate(1, f_acc, g_acc, L.acc_hs, L.acc_g0)) return 1;
         } else {
-            LB_OK(lb_commit0(L, L.acc_hs, L.acc_g0, f_acc, g_acc, st_));
+            HIP_OK(lb_commit0(L, L.acc_hs, L.acc_g0, f_acc, g_acc, st_));
         }
-        LB_OK(lb_history(L, count, ftol, f_acc, g_acc, st_));
+        HIP_OK(lb_history(L, count, ftol, f_acc, g_acc, st_));
         ++count;
     }
-    LB_OK(hipMemcpyAsync(x_out, L.x, sizeof(double) * BT, hipMemcpyDeviceToHost, st_));
-    LB_OK(hipMemcpyAsync(f_out, L.f, sizeof(double) * B, hipMemcpyDeviceToHost, st_));
-    if (fidelity_out) LB_OK(hipMemcpyAsync(fidelity_out, L.fidelity, sizeof(double) * B, hipMemcpyDeviceToHost, st_));
-    if (nit_out) LB_OK(hipMemcpyAsync(nit_out, L.nit, sizeof(long long) * B, hipMemcpyDeviceToHost, st_));
-    if (weight_out) LB_OK(hipMemcpyAsync(weight_out, L.weight, sizeof(double) * B, hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipMemcpyAsync(x_out, L.x, sizeof(double) * BT, hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipMemcpyAsync(f_out, L.f, sizeof(double) * B, hipMemcpyDeviceToHost, st_));
+    if (fidelity_out) HIP_OK(hipMemcpyAsync(fidelity_out, L.fidelity, sizeof(double) * B, hipMemcpyDeviceToHost, st_));
+    if (nit_out) HIP_OK(hipMemcpyAsync(nit_out, L.nit, sizeof(long long) * B, hipMemcpyDeviceToHost, st_));
+    if (weight_out) HIP_OK(hipMemcpyAsync(weight_out, L.weight, sizeof(double) * B, hipMemcpyDeviceToHost, st_));
     std::vector<int> h_max_no(B, 0);
-    if (max_no_out) LB_OK(hipMemcpyAsync(h_max_no.data(), L.max_no, sizeof(int) * B, hipMemcpyDeviceToHost, st_));
-    LB_OK(hipStreamSynchronize(st_));
+    if (max_no_out) HIP_OK(hipMemcpyAsync(h_max_no.data(), L.max_no, sizeof(int) * B, hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
     if (max_no_out) for (int b = 0; b < B; ++b) max_no_out[b] = h_max_no[b];
     if (nfev_out) *nfev_out = nfev;
-    cleanup();
-#undef LB_OK
-#undef LB_TRY
     return 0;
 }
 
@@ -174,19 +158,17 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     const size_t ndbl = (size_t)B * (3 + 2 * (size_t)S), bytes = ndbl * sizeof(double) + (size_t)B * sizeof(int);
     if (ws->sur_states != S) {
         HIP_OK(hipStreamSynchronize(st));
-        if (ws->d_sur) { HIP_OK(hipFree(ws->d_sur)); ws->d_sur = nullptr; }
-        if (ws->h_sur) { HIP_OK(hipHostFree(ws->h_sur)); ws->h_sur = nullptr; }
+        if (ws->d_sur.release() || ws->h_sur.release()) return 1;
         ws->sur_states = 0;
-        HIP_OK(hipMalloc(&ws->d_sur, bytes));
-        HIP_OK(hipHostMalloc(&ws->h_sur, bytes, hipHostMallocDefault));
+        if (ws->d_sur.alloc(bytes) || ws->h_sur.alloc(bytes)) return 1;
         ws->sur_states = S;
     }
-    double* hd = static_cast<double*>(ws->h_sur);
+    double* hd = reinterpret_cast<double*>((char*)ws->h_sur);
     // Small problems (single evaluations above all): no copy nodes -- the kernels read the thetas and the objective state from
     // pinned host memory and write the state block and a second copy of the gradient straight back into it (as aqc_ws_eval does)
     const bool zero_copy = sizeof(double2) * (nth + (size_t)B * S) <= 65536;
     const bool direct = direct_thetas(ws, zero_copy);
-    double* dd = zero_copy ? hd : static_cast<double*>(ws->d_sur);
+    double* dd = zero_copy ? hd : reinterpret_cast<double*>((char*)ws->d_sur);
     MirrorScope mirror_scope(ws, zero_copy ? ws->h_pin + ws->pin_thetas : nullptr, nullptr);
     LbState L;
     memset(&L, 0, sizeof L);
@@ -203,7 +185,7 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     double* pin_th = ws->h_pin;
     double* pin_gr = ws->h_pin + ws->pin_thetas;
     memcpy(pin_th, thetas, sizeof(double) * nth);
-    if (!ws->d_combo_prev[AQC_BUF_X2]) HIP_OK(hipMalloc((void**)&ws->d_combo_prev[AQC_BUF_X2], sizeof(long long) * 2 * B));   // (combo_valid is false without it)
+    if (ws->d_combo_prev[AQC_BUF_X2].reserve(2 * (size_t)B)) return 1;   // (combo_valid is false without it)
     if (!ws->combo_valid[AQC_BUF_X2]) {   // (outside the replayed part: a whole-buffer clear is a one-off)
         HIP_OK(hipMemsetAsync(ws->bufs[AQC_BUF_X2], 0, sizeof(double2) * (size_t)B * ws->lane_elems, st));
         HIP_OK(hipMemsetAsync(ws->d_combo_prev[AQC_BUF_X2], 0xff, sizeof(long long) * 2 * B, st));   // -1: nothing to clear
@@ -213,11 +195,9 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     route.x_buf = AQC_BUF_X2; route.vdag = route.new_thetas = route.gather = route.grads = route.support_in_gather_set = true;
     if (eval_route(ws, route)) return 1;
     const bool real_only = !zero_copy && !grads_out;
-    if (real_only && ws->sur_real_cap < nth) {
+    if (real_only && ws->d_sur_real.capacity() < nth) {
         HIP_OK(hipStreamSynchronize(st));
-        if (ws->d_sur_real) { HIP_OK(hipFree(ws->d_sur_real)); ws->d_sur_real = nullptr; ws->sur_real_cap = 0; }
-        HIP_OK(hipMalloc((void**)&ws->d_sur_real, sizeof(double) * nth));
-        ws->sur_real_cap = nth;
+        if (ws->d_sur_real.reserve(nth)) return 1;
     }
     auto enqueue = [&]() -> int {   // everything between the host copies of the inputs and the final synchronisation
         if (!zero_copy) {
@@ -251,8 +231,8 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
     static const bool graphs_on = env_int("AQC_GRAPH", 1) != 0;
     if (graphs_on && !ws->profile) {   // the launch sequence is replayed as a graph, as in aqc_ws_eval
         const long long tag = 1000 + update_state + (zero_copy ? 10 : 0) + (real_only ? 20 : 0);   // (1000: no key of aqc_ws_eval)
-        if (run_graph(ws, route, {tag, block_from, block_to, front_layer, (long long)S, (long long)(size_t)ws->d_sur_real, (long long)(size_t)ws->d_sur,
-                                  (long long)(size_t)ws->h_sur}, enqueue)) return 1;
+        if (run_graph(ws, route, {tag, block_from, block_to, front_layer, (long long)S, (long long)(size_t)(double*)ws->d_sur_real, (long long)(size_t)(char*)ws->d_sur,
+                                  (long long)(size_t)(char*)ws->h_sur}, enqueue)) return 1;
     } else if (enqueue()) {
         return 1;
     }

@@ -77,7 +77,7 @@ void emit_mops(const Program& prog, int gi, int pc, int pt, bool inverse, bool w
 
 }  // namespace
 
-void lower_plan(const Program& prog, const Plan& plan, DevPlan& out, int reg_bits, bool with_dots, bool mfma, bool presplit, int beam_width) {
+void lower_plan(const Program& prog, const Plan& plan, HostPlan& out, int reg_bits, bool with_dots, bool mfma, bool presplit, int beam_width) {
     out.plan = plan;
     out.h_stages.clear();
     out.h_ops.clear();
@@ -216,32 +216,15 @@ void lower_plan(const Program& prog, const Plan& plan, DevPlan& out, int reg_bit
 }
 
 int upload_plan(DevPlan& p) {
-    HIP_OK(hipMalloc((void**)&p.d_stages, p.h_stages.size() * sizeof(DevStage)));
-    HIP_OK(hipMemcpy(p.d_stages, p.h_stages.data(), p.h_stages.size() * sizeof(DevStage), hipMemcpyHostToDevice));
-    const size_t nops = std::max<size_t>(p.h_ops.size(), 1);
-    HIP_OK(hipMalloc((void**)&p.d_ops, nops * sizeof(DevOp)));
+    if (p.d_stages.upload(p.h_stages)) return 1;
+    const size_t nops = std::max<size_t>(p.h_ops.size(), 1);   // (not an upload: the table is zeroed first)
+    if (p.d_ops.alloc(nops)) return 1;
     HIP_OK(hipMemset(p.d_ops, 0, nops * sizeof(DevOp)));
     if (!p.h_ops.empty())
         HIP_OK(hipMemcpy(p.d_ops, p.h_ops.data(), p.h_ops.size() * sizeof(DevOp), hipMemcpyHostToDevice));
-    HIP_OK(hipMalloc((void**)&p.d_subs, std::max<size_t>(p.h_subs.size(), 1) * sizeof(DevSub)));
-    HIP_OK(hipMalloc((void**)&p.d_mops, std::max<size_t>(p.h_mops.size(), 1) * sizeof(DevMop)));
-    if (!p.h_subs.empty())
-        HIP_OK(hipMemcpy(p.d_subs, p.h_subs.data(), p.h_subs.size() * sizeof(DevSub), hipMemcpyHostToDevice));
-    if (!p.h_mops.empty())
-        HIP_OK(hipMemcpy(p.d_mops, p.h_mops.data(), p.h_mops.size() * sizeof(DevMop), hipMemcpyHostToDevice));
-    if (p.v3 && !p.h_subs3.empty()) {
-        HIP_OK(hipMalloc((void**)&p.d_subs3, p.h_subs3.size() * sizeof(DevSub3)));
-        HIP_OK(hipMemcpy(p.d_subs3, p.h_subs3.data(), p.h_subs3.size() * sizeof(DevSub3), hipMemcpyHostToDevice));
-        HIP_OK(hipMalloc((void**)&p.d_grps, std::max<size_t>(p.h_grps.size(), 1) * sizeof(DevGrp)));
-        if (!p.h_grps.empty()) HIP_OK(hipMemcpy(p.d_grps, p.h_grps.data(), p.h_grps.size() * sizeof(DevGrp), hipMemcpyHostToDevice));
-    }
+    if (p.d_subs.upload(p.h_subs) || p.d_mops.upload(p.h_mops)) return 1;
+    if (p.v3 && !p.h_subs3.empty() && (p.d_subs3.upload(p.h_subs3) || p.d_grps.upload(p.h_grps))) return 1;
     return 0;
-}
-void free_plan(DevPlan& p) {   // what upload_plan allocated, and the plan's operand and partial-R buffers
-    for (void* q : {(void*)p.d_stages, (void*)p.d_ops, (void*)p.d_subs, (void*)p.d_mops, (void*)p.d_subs3, (void*)p.d_grps, (void*)p.d_umat, (void*)p.d_rpart})
-        if (q) (void)hipFree(q);
-    p.d_stages = nullptr; p.d_ops = nullptr; p.d_subs = nullptr; p.d_mops = nullptr; p.d_subs3 = nullptr; p.d_grps = nullptr;
-    p.d_umat = nullptr; p.d_rpart = nullptr;
 }
 
 // The plan of V^H that walks a forward plan backwards: stages in reverse order with the same local bits, sub-stages in reverse

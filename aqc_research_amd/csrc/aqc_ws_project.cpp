@@ -117,13 +117,11 @@ int proj_alloc(aqc_ws* ws) {
     const size_t B = (size_t)ws->batch;
     if (upload_plan(pr.vsw) || upload_plan(pr.vinv)) return 1;
     const size_t nsubs = std::max<size_t>(pr.vsw.h_subs3.size(), 1);
-    HIP_OK(hipMalloc((void**)&pr.vsw.d_umat, sizeof(double) * B * nsubs * 12 * 64));
-    HIP_OK(hipMalloc((void**)&pr.vinv.d_umat, sizeof(double) * B * nsubs * 12 * 64));
-    HIP_OK(hipMalloc((void**)&pr.vsw.d_rpart, sizeof(double2) * B * nsubs * (2 * (size_t)pr.ntiles_v) * 256));
-    const size_t vbytes = sizeof(double2) * B * (2ull << pr.nvp);
-    HIP_OK(hipMalloc((void**)&pr.vm, vbytes));
+    if (pr.vsw.d_umat.alloc(B * nsubs * 12 * 64) || pr.vinv.d_umat.alloc(B * nsubs * 12 * 64)) return 1;
+    if (pr.vsw.d_rpart.alloc(B * nsubs * (2 * (size_t)pr.ntiles_v) * 256)) return 1;
+    const size_t velems = B * (2ull << pr.nvp), vbytes = sizeof(double2) * velems;
     pr.vy_copies = pr.us > 8 && pr.us <= 10 && pr.cb <= 4 ? 1 << (pr.us - 8) : 1;
-    HIP_OK(hipMalloc((void**)&pr.vy, vbytes * pr.vy_copies));
+    if (pr.vm.alloc(velems) || pr.vy.alloc(velems * pr.vy_copies)) return 1;
     HIP_OK(hipMemsetAsync(pr.vm, 0, vbytes, ws->stream));   // (entries beyond 2^nv -- a register padded to 8 qubits -- stay zero for good)
     HIP_OK(hipMemsetAsync(pr.vy, 0, vbytes * pr.vy_copies, ws->stream));
     pr.cpart_shares = 0;
@@ -133,30 +131,16 @@ int proj_alloc(aqc_ws* ws) {
         const int cap = env_int("AQC_PROJECTED_FUSED_MAX_SHARES", 64);   // (1: never split -- what large batches run; tests)
         while ((long)B * pr.vy_copies * shares < want_wgs && 2 * shares <= (1 << (pr.t - 4)) && 2 * shares <= cap) shares *= 2;
         if (shares > 1) {
-            HIP_OK(hipMalloc((void**)&pr.cpart, sizeof(double2) * (size_t)shares * 2 * B * (16ull << pr.us)));
+            if (pr.cpart.alloc((size_t)shares * 2 * B * (16ull << pr.us))) return 1;
             pr.cpart_shares = shares;
         }
     }
-    HIP_OK(hipMalloc((void**)&pr.vme, vbytes));
+    if (pr.vme.alloc(velems)) return 1;
     HIP_OK(hipMemsetAsync(pr.vme, 0, vbytes, ws->stream));
-    HIP_OK(hipMalloc((void**)&pr.d_tab, sizeof(unsigned) * pr.h_tab.size()));
-    HIP_OK(hipMemcpy(pr.d_tab, pr.h_tab.data(), sizeof(unsigned) * pr.h_tab.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMalloc((void**)&pr.d_items, sizeof(TileItem) * 2 * B * pr.ntiles_v));
-    HIP_OK(hipMalloc((void**)&pr.d_count, sizeof(int)));
+    if (pr.d_tab.upload(pr.h_tab) || pr.d_items.alloc(2 * B * pr.ntiles_v) || pr.d_count.alloc(1) || pr.d_lane_parts.alloc(B)) return 1;
     HIP_OK(hipMemsetAsync(pr.d_count, 0, sizeof(int), ws->stream));
-    HIP_OK(hipMalloc((void**)&pr.d_lane_parts, sizeof(int) * B));
     HIP_OK(hipMemsetAsync(pr.d_lane_parts, 0, sizeof(int) * B, ws->stream));
     return 0;
-}
-
-void proj_free(aqc_ws* ws) {
-    ProjRoute& pr = ws->proj;
-    free_plan(pr.vsw);
-    free_plan(pr.vinv);
-    for (void* q : {(void*)pr.vm, (void*)pr.vy, (void*)pr.vme, (void*)pr.cpart, (void*)pr.d_tab, (void*)pr.d_items, (void*)pr.d_count, (void*)pr.d_lane_parts})
-        if (q) (void)hipFree(q);
-    pr.vm = pr.vy = pr.vme = nullptr; pr.cpart = nullptr; pr.d_tab = nullptr; pr.d_items = nullptr; pr.d_count = nullptr; pr.d_lane_parts = nullptr;
-    pr.ok = false;
 }
 
 bool sweep_route_projected(const aqc_ws* ws, bool sparse) { return sparse && ws->proj.ok; }

@@ -26,10 +26,8 @@ int sk_kind_ok(int kind) {
 int sk_alloc(aqc_ws* ws) {
     const int B = ws->batch, k = ws->ncols, d = 1 << ws->ctx->prog.n;
     if (ws->sk.status) return 0;
-    HIP_OK(hipMalloc((void**)&ws->sk.qr_part, sizeof(double2) * (size_t)B * sk_qr_slabs(d) * k * k));
-    HIP_OK(hipMalloc((void**)&ws->sk.qr_rinv, sizeof(double2) * (size_t)B * k * k));
-    HIP_OK(hipMalloc((void**)&ws->sk.tmp, sizeof(double2) * (size_t)B * ws->lane_elems));
-    HIP_OK(hipMalloc((void**)&ws->sk.status, sizeof(int) * B));
+    if (ws->sk.qr_part.alloc((size_t)B * sk_qr_slabs(d) * k * k) || ws->sk.qr_rinv.alloc((size_t)B * k * k) ||
+        ws->sk.tmp.alloc((size_t)B * ws->lane_elems) || ws->sk.status.alloc(B)) return 1;
     HIP_OK(hipMemsetAsync(ws->sk.status, 0, sizeof(int) * B, ws->stream));
     return 0;
 }
@@ -40,12 +38,9 @@ int sk_upload_idx(aqc_ws* ws, const int32_t* idx, size_t sets) {
     const size_t n = sets * B * k;
     for (size_t i = 0; i < n; ++i)
         if (idx[i] < 0 || idx[i] >= d) return fail("alt column index %d out of range [0, %d)", (int)idx[i], d);
-    if (n > ws->sk.idx_cap) {
+    if (n > ws->sk.idx.capacity()) {
         HIP_OK(hipStreamSynchronize(ws->stream));
-        if (ws->sk.idx) HIP_OK(hipFree(ws->sk.idx));
-        ws->sk.idx = nullptr; ws->sk.idx_cap = 0;
-        HIP_OK(hipMalloc((void**)&ws->sk.idx, sizeof(int) * n));
-        ws->sk.idx_cap = n;
+        if (ws->sk.idx.reserve(n)) return 1;
     }
     HIP_OK(hipMemcpyAsync(ws->sk.idx, idx, sizeof(int) * n, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));   // the caller's array may go away
@@ -101,19 +96,16 @@ int aqc_qr(int device, int m, int k, const double* a, double* q_out, int32_t* st
     if (device < 0 || device >= ndev) return fail("device out of range");
     HIP_OK(hipSetDevice(device));
     const size_t na = sizeof(double2) * (size_t)m * k;
-    void *dA = nullptr, *dP = nullptr, *dR = nullptr, *dS = nullptr;
+    DevBuf<double2> dA, dP, dR;
+    DevBuf<int> dS;
     int st = 0;
-    hipError_t e = hipMalloc(&dA, na);
-    if (e == hipSuccess) e = hipMalloc(&dP, sizeof(double2) * (size_t)sk_qr_slabs(m) * k * k);
-    if (e == hipSuccess) e = hipMalloc(&dR, sizeof(double2) * (size_t)k * k);
-    if (e == hipSuccess) e = hipMalloc(&dS, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dA, a, na, hipMemcpyHostToDevice);
+    if (dA.alloc((size_t)m * k) || dP.alloc((size_t)sk_qr_slabs(m) * k * k) || dR.alloc((size_t)k * k) || dS.alloc(1)) return 1;
+    hipError_t e = hipMemcpy(dA, a, na, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(dS, 0, sizeof(int));
-    if (e == hipSuccess) e = launch_sk_qr(dA, 0, k, m, k, 1, 0.0, dP, dR, static_cast<int*>(dS), nullptr);
+    if (e == hipSuccess) e = launch_sk_qr(dA, 0, k, m, k, 1, 0.0, dP, dR, dS, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(q_out, dA, na, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(&st, dS, sizeof(int), hipMemcpyDeviceToHost);
-    for (void* p : {dA, dP, dR, dS}) if (p) (void)hipFree(p);
     if (e != hipSuccess) return fail("aqc_qr failed: %s", hipGetErrorString(e));
     if (status) *status = st;
     else if (st) return fail("aqc_qr: the matrix is rank deficient");
@@ -126,11 +118,8 @@ int aqc_ws_sketch_target(aqc_ws* ws, const double* U, int shared) {
     HIP_OK(hipSetDevice(ws->device));
     const size_t d = (size_t)1 << ws->ctx->prog.n, count = shared ? 1 : (size_t)ws->batch;
     HIP_OK(hipStreamSynchronize(ws->stream));
-    if (ws->sk.target && ws->sk.shared != (shared != 0) && ws->batch > 1) {
-        HIP_OK(hipFree(ws->sk.target));
-        ws->sk.target = nullptr;
-    }
-    if (!ws->sk.target) HIP_OK(hipMalloc((void**)&ws->sk.target, sizeof(double2) * count * d * d));
+    if (ws->sk.target && ws->sk.shared != (shared != 0) && ws->batch > 1 && ws->sk.target.release()) return 1;
+    if (!ws->sk.target && ws->sk.target.alloc(count * d * d)) return 1;
     ws->sk.shared = shared != 0;
     HIP_OK(hipMemcpyAsync(ws->sk.target, U, sizeof(double2) * count * d * d, hipMemcpyHostToDevice, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
@@ -190,22 +179,19 @@ int aqc_ws_sketch_adam(aqc_ws* ws, int kind, const double* x0, int niter, const 
     HIP_OK(hipSetDevice(ws->device));
     hipStream_t st = ws->stream;
     if (!ws->sk.adam) {
-        HIP_OK(hipMalloc((void**)&ws->sk.adam, sizeof(double) * (3 * BT + 2 * (size_t)B)));
-        HIP_OK(hipMalloc((void**)&ws->sk.adam_i, sizeof(int) * 3 * B));
+        if (ws->sk.adam.alloc(3 * BT + 2 * (size_t)B) || ws->sk.adam_i.alloc(3 * (size_t)B)) return 1;
         HIP_OK(hipMemsetAsync(ws->sk.adam, 0, sizeof(double) * (3 * BT + 2 * (size_t)B), st));
         HIP_OK(hipMemsetAsync(ws->sk.adam_i, 0, sizeof(int) * 3 * B, st));
     }
-    if (sets > ws->sk.profile_cap) {
+    if ((size_t)B * sets > ws->sk.profile.capacity()) {
         HIP_OK(hipStreamSynchronize(st));
-        if (ws->sk.profile) HIP_OK(hipFree(ws->sk.profile));
-        ws->sk.profile = nullptr; ws->sk.profile_cap = 0;
-        HIP_OK(hipMalloc((void**)&ws->sk.profile, sizeof(double) * (size_t)B * sets));
-        ws->sk.profile_cap = sets;
+        if (ws->sk.profile.reserve((size_t)B * sets)) return 1;
     }
+    const size_t profile_stride = ws->sk.profile.capacity() / B;   // what the buffer was last grown for
     if (kind == AQC_SKETCH_ALT && sk_upload_idx(ws, alt_idx, sets)) return 1;
     SkAdam s;
     memset(&s, 0, sizeof s);
-    s.B = B; s.T = T; s.k = k; s.profile_stride = (int)ws->sk.profile_cap;
+    s.B = B; s.T = T; s.k = k; s.profile_stride = (int)profile_stride;
     s.thetas = ws->d_thetas_own;
     s.grads = ws->d_grads;
     s.m = ws->sk.adam; s.v = s.m + BT; s.best_x = s.v + BT; s.best_f = s.best_x + BT;
@@ -248,7 +234,7 @@ int aqc_ws_sketch_adam(aqc_ws* ws, int kind, const double* x0, int niter, const 
     }
     std::vector<int> h_nit(B), h_status(B);
     HIP_OK(hipMemcpyAsync(x_out, ws->d_thetas_own, sizeof(double) * BT, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpy2DAsync(fobj_profile, sizeof(double) * sets, ws->sk.profile, sizeof(double) * ws->sk.profile_cap, sizeof(double) * sets, B,
+    HIP_OK(hipMemcpy2DAsync(fobj_profile, sizeof(double) * sets, ws->sk.profile, sizeof(double) * profile_stride, sizeof(double) * sets, B,
                             hipMemcpyDeviceToHost, st));
     if (best_f) HIP_OK(hipMemcpyAsync(best_f, s.best_f, sizeof(double) * B, hipMemcpyDeviceToHost, st));
     if (best_x) HIP_OK(hipMemcpyAsync(best_x, s.best_x, sizeof(double) * BT, hipMemcpyDeviceToHost, st));

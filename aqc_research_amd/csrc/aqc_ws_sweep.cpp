@@ -130,6 +130,7 @@ namespace {
 unsigned long long* g_stamps = nullptr;
 int stamps_begin(aqc_ws* ws, Stage3Args& a, size_t nwg) {
     if (env_int("AQC_STAMPS", 0) == 0 || nwg > 65536) return 0;
+    // process-lifetime, never freed: a static destructor must not call into HIP at exit, so this one block stays a raw pointer
     if (!g_stamps) HIP_OK(hipMalloc((void**)&g_stamps, sizeof(unsigned long long) * 65536 * kStampSlots));
     HIP_OK(hipMemsetAsync(g_stamps, 0, sizeof(unsigned long long) * nwg * kStampSlots, ws->stream));
     a.stamps = g_stamps;
@@ -312,7 +313,7 @@ static int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set
     if (ensure_umat(ws, p)) return 1;
     const size_t m = p.h_stages.size();
     const size_t per_lane = 2 + (size_t)ws->gather_count;
-    if (!ws->d_vd_items || ws->vd_items_cap < per_lane * ws->batch) return fail("objective V^H inside a captured graph without its preparation");
+    if (ws->d_vd_items.capacity() < per_lane * ws->batch) return fail("objective V^H inside a captured graph without its preparation");
     for (size_t s = 0; s + 1 < m; ++s) {
         Stage3Args a = stage3_args(ws, p, s);
         a.in0 = s == 0 ? ws->bufs[AQC_BUF_Y] : ws->bufs[AQC_BUF_ZW];
@@ -394,27 +395,20 @@ static int sweep_sparse_prepare(aqc_ws* ws) {
     const DevPlan& p = ws->sweep;
     const int B = ws->batch;
     if (!ws->d_sw_items) {
-        HIP_OK(hipMalloc((void**)&ws->d_sw_items, sizeof(TileItem) * 2 * B));
-        HIP_OK(hipMalloc((void**)&ws->d_sw_clear, sizeof(TileItem) * 2 * B));
-        HIP_OK(hipMalloc((void**)&ws->d_sw_counts, sizeof(int) * 4));
+        if (ws->d_sw_items.alloc(2 * (size_t)B) || ws->d_sw_clear.alloc(2 * (size_t)B) || ws->d_sw_counts.alloc(4)) return 1;
         HIP_OK(hipMemsetAsync(ws->d_sw_counts, 0, sizeof(int) * 4, ws->stream));
-        HIP_OK(hipMalloc((void**)&ws->d_sw_lane_parts, sizeof(int) * B));
-        HIP_OK(hipMalloc((void**)&ws->d_sw_prev_tiles, sizeof(int) * 2 * B));
+        if (ws->d_sw_lane_parts.alloc(B) || ws->d_sw_prev_tiles.alloc(2 * (size_t)B)) return 1;
         ws->w_clean = false;
     }
     // The second scratch pair: the stages from the second one on work on it, so that W stays zero outside the listed tiles and ZW keeps
     // the checkpoint.  Plans of two stages have no such stage, and the projected route runs them on its own small register.
     if (p.h_stages.size() >= 3 && !ws->w2 && !ws->proj.ok) {
-        HIP_OK(hipMalloc((void**)&ws->w2, sizeof(double2) * (size_t)B * ws->lane_elems));
-        HIP_OK(hipMalloc((void**)&ws->zw2, sizeof(double2) * (size_t)B * ws->lane_elems));
+        if (ws->w2.alloc((size_t)B * ws->lane_elems) || ws->zw2.alloc((size_t)B * ws->lane_elems)) return 1;
     }
     const size_t vd_need = (2 + (size_t)ws->gather_count) * B;
-    if (ws->lazy_z_enabled && ws->vd_items_cap < vd_need) {
+    if (ws->lazy_z_enabled && ws->d_vd_items.capacity() < vd_need) {
         HIP_OK(hipStreamSynchronize(ws->stream));
-        if (ws->d_vd_items) HIP_OK(hipFree(ws->d_vd_items));
-        ws->d_vd_items = nullptr; ws->vd_items_cap = 0;
-        HIP_OK(hipMalloc((void**)&ws->d_vd_items, sizeof(TileItem) * vd_need));
-        ws->vd_items_cap = vd_need;
+        if (ws->d_vd_items.reserve(vd_need)) return 1;
         ws->vd_key = ListKey{};
     }
     if (!ws->w_clean) {

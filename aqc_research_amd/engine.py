@@ -26,6 +26,13 @@ def default_device() -> int:
     return 0
 
 
+def live_buffers() -> tuple:
+    """(device, pinned) allocations the library's handles hold right now (aqc_live_buffers): equal before and after a handle's life."""
+    dev, pin = c_int64(0), c_int64(0)
+    check(_lib.lib().aqc_live_buffers(byref(dev), byref(pin)))
+    return dev.value, pin.value
+
+
 def _structure_key(circ) -> tuple:
     trotter = hasattr(circ, "is_second_order")
     blocks = np.ascontiguousarray(circ.blocks, dtype=np.int32)

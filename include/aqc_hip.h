@@ -63,6 +63,11 @@ const char* aqc_last_error(void);
 /* number of visible HIP devices (0 when HIP is unusable); the reference's counterpart is
  * joblib's worker count, job_executor.py:136-143 */
 int aqc_device_count(void);
+/* live allocations behind this library's handles (workspaces, contexts' one-shot workspaces, MPS engines, lockstep lanes and the
+ * calls' own temporaries): device blocks and pinned host blocks; either pointer may be null.  Every handle owns its memory, so
+ * both counts return to their earlier values when a handle is destroyed -- the check of a leak test.  Process-wide, all devices;
+ * the communicator's buffers are not counted. */
+int aqc_live_buffers(int64_t* device, int64_t* pinned);
 
 /* ---- ansatz description: ParametricCircuit / TrotterAnsatz
  *      (parametric_circuit.py:24-70,267-320; validity rules :234-254,391-423) */

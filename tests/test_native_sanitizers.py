@@ -1,6 +1,7 @@
 """CPU builds of the native host code under AddressSanitizer + UBSan (GPU sanitizers are not available on the
 pool; the reference has no sanitizer runs at all): the C restatement of the oracle, the HIP-free
-stage planner and the HIP-free gate walk of the MPS engines, each with a self-test driver from tests/native/."""
+stage planner, the HIP-free gate walk of the MPS engines and the owning buffer type over a counting allocator, each with a
+self-test driver from tests/native/."""
 import os
 import shutil
 import subprocess
@@ -36,6 +37,16 @@ def test_planner_under_asan_ubsan(tmp_path):
           os.path.join(ROOT, "aqc_research_amd", "csrc", "aqc_plan.cpp"), "-o", exe])
     out = _run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert " 0 failures" in out
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_devbuf_under_asan_ubsan(tmp_path):
+    """The owning buffer behind every handle (csrc/aqc_devbuf.h) over a malloc-backed counting policy: no path leaves a live block,
+    a failed allocation leaves an empty buffer, a half-created handle is released by its destructor."""
+    exe = str(tmp_path / "devbuf_selftest")
+    _run(["g++", "-std=c++17", *SAN, os.path.join(ROOT, "tests", "native", "devbuf_selftest.cpp"), "-o", exe])
+    out = _run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert " 0 live, 0 failures" in out
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
