@@ -320,11 +320,12 @@ hipError_t launch_mps_split(const void* W, const void* V, const int* ord, const 
 hipError_t launch_mps_colscale(void* t, const double* lam, size_t rows, int cols, int mul, hipStream_t s);
 
 // aqc_sketch.hip (sketched AQC on the device: generators, tall-skinny QR, ADAM)
-// CholeskyQR2 of `batch` (d x k) c128 matrices (row-major, leading dimension lda, lane_stride elements apart), in place; k a power of
-// two <= 64, k <= d.  partial: [batch][sk_qr_slabs(d)][k][k] c128, rinv: [batch][k][k] c128, status: [batch] ints (lanes with a non-zero
-// word are skipped; a pivot <= abs_floor, or negligible against its column, sets AQC_QR_RANK_DEFICIENT and leaves the lane untouched)
+// CholeskyQR2 of `batch` (d x k) c128 matrices (row-major, leading dimension lda, lane_stride elements apart): a <- Q; k a power of
+// two <= 64, k <= d.  scratch: the first pass's Q, laid out like a (overwritten); partial: [batch][sk_qr_slabs(d)][k][k] c128,
+// rinv: [batch][k][k] c128, status: [batch] ints (lanes with a non-zero word are skipped; a pivot <= abs_floor or negligible against its
+// column, or a first pass whose Q is not orthonormal to 1e-4, sets AQC_QR_RANK_DEFICIENT and leaves the lane of a untouched)
 int sk_qr_slabs(int d);
-hipError_t launch_sk_qr(void* a, size_t lane_stride, int lda, int d, int k, int batch, double abs_floor, void* partial, void* rinv, int* status,
+hipError_t launch_sk_qr(void* a, void* scratch, size_t lane_stride, int lda, int d, int k, int batch, double abs_floor, void* partial, void* rinv, int* status,
                         hipStream_t s);
 // x <- one-hot columns idx[lane][k], y <- u[:, idx]; u: [batch or 1][d][d] (u_stride 0: one target for all lanes)
 hipError_t launch_sk_alt(void* x, void* y, size_t lane_stride, int pitch, int d, int k, const void* u, size_t u_stride, const int* idx, int batch,

@@ -5,11 +5,16 @@
 //   gram : G = A^H A on v_mfma_f64_16x16x4_f64; every wave sums a slab of rows and stores its partial k x k block
 //   chol : one workgroup per lane adds the partials in slab order (no float atomics: bit-reproducible), factors G = L L^H in LDS
 //          and inverts L by forward substitution; R^-1 = L^-H goes to HBM
-//   apply: A <- A R^-1 on the matrix cores, each wave its own 16 rows, in place
-// and the QR is two passes.  k < 16 (and a row count that is no multiple of 4 or 16) is padded with zeros in registers.
-// A pivot that is not finite, not above kPivotRel times its diagonal entry of G, or not above the caller's absolute floor marks the
-// lane AQC_QR_RANK_DEFICIENT in its status word: nothing of that lane is written from then on.  kPivotRel = 1e-10 keeps the first
-// pass's Q within ~1e-5 of orthonormal, so a lane that passes the first factorisation passes the second.
+//   apply: Q <- A R^-1 on the matrix cores, each wave its own 16 rows
+// and the QR is two passes: the first writes Q1 = A R1^-1 to a scratch matrix of A's layout, the second reads Q1 and writes
+// Q = Q1 R2^-1 over A.  k < 16 (and a row count that is no multiple of 4 or 16) is padded with zeros in registers.
+// Status 0 means an orthonormal Q.  A lane is marked AQC_QR_RANK_DEFICIENT in its status word, and skipped by every later launch, when
+//   - a pivot of either factorisation is not finite, not above kPivotRel times its diagonal entry of that pass's G, or not above the
+//     caller's absolute floor: a (numerically) dependent column;
+//   - the second pass's Gram matrix G2 = Q1^H Q1 has an entry further than kOrthTol from I.  The per-column pivot test does not
+//     bound the condition number (Kahan matrices pass it with kappa = 1e16), and the first pass leaves |G2 - I| ~ eps kappa^2, kappa
+//     the condition number of A with its columns scaled to norm 1: when that is O(1) the second pass repairs nothing.
+// A is written by the second apply only, so a flagged lane keeps its matrix bit for bit whichever test flagged it.
 //
 // MFMA operand layout (as in aqc_mps.hip): lane l supplies A[l % 16][l / 16] and B[l / 16][l % 16] and receives
 // D[4 r + l / 16][l % 16] in accumulator register r.
@@ -27,6 +32,10 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr double kPivotRel = 1e-10;
+// |G2 - I| <= 1e-4 entrywise: |G2 - I|_2 <= 64e-4, so kappa(Q1) < 1.01 and the second pass ends at k eps.  eps kappa^2 = 1e-4 is
+// kappa = 7e5, the geometric middle between what the callers need accepted (kappa <= 1e4: eps kappa^2 = 2e-8) and the kappa = 7e7 from
+// which on 64 eps kappa > 1e-6 and a range in double precision is no longer one.  (tests/sketch_ref.py: ORTH_TOL)
+constexpr double kOrthTol = 1e-4;
 constexpr int kSlabRows = 64;   // rows of A one wave of the gram kernel sums
 
 __device__ __forceinline__ double4_t sk_mfma(double a, double b, double4_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
@@ -80,8 +89,8 @@ __global__ __launch_bounds__(256) void qr_gram_kernel(const cplx* __restrict__ a
 }
 
 // G = sum of the partials (slab order), G = L L^H, X = L^-1, rinv[lane][c][i] = conj(X[i][c]) (R^-1 = L^-H, upper triangular).
-// LDS: g[k][k] | x[k][k].
-__global__ __launch_bounds__(256) void qr_chol_kernel(const cplx* __restrict__ partial, int nslabs, int k, double abs_floor,
+// second: this is the second pass, whose G has to be I to kOrthTol.  LDS: g[k][k] | x[k][k].
+__global__ __launch_bounds__(256) void qr_chol_kernel(const cplx* __restrict__ partial, int nslabs, int k, double abs_floor, int second,
                                                       int* __restrict__ status, cplx* __restrict__ rinv) {
     extern __shared__ __attribute__((aligned(16))) char sk_smem[];
     __shared__ int s_bad;
@@ -91,18 +100,24 @@ __global__ __launch_bounds__(256) void qr_chol_kernel(const cplx* __restrict__ p
     cplx* g = reinterpret_cast<cplx*>(sk_smem);
     cplx* x = g + kk;
     const cplx* P = partial + (size_t)lane_id * nslabs * kk;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
     for (int e = tid; e < kk; e += 256) {
         double re = 0.0, im = 0.0;
         for (int s = 0; s < nslabs; ++s) { const cplx v = P[(size_t)s * kk + e]; re += v.x; im += v.y; }
         g[e] = make_double2(re, im);
         x[e] = make_double2(0.0, 0.0);
+        if (second) {   // (a flag: every writer stores the same value; a NaN fails the comparison)
+            const double dr = re - (e / k == e % k ? 1.0 : 0.0);
+            if (!(dr * dr + im * im <= kOrthTol * kOrthTol)) s_bad = 1;
+        }
     }
-    if (tid == 0) s_bad = 0;
     __syncthreads();
+    const int drifted = s_bad;   // (read between two barriers: the next writer is the pivot test below)
     if (tid < k) s_diag[tid] = g[tid * k + tid].x;   // the columns' squared norms: what the relative pivot test refers to
     __syncthreads();
     // right-looking Cholesky on the lower triangle
-    for (int j = 0; j < k; ++j) {
+    for (int j = 0; j < k && !drifted; ++j) {
         const double piv = g[j * k + j].x;
         if (tid == 0 && (!(piv > kPivotRel * s_diag[j]) || !(piv > abs_floor) || !isfinite(piv))) s_bad = 1;
         __syncthreads();
@@ -151,16 +166,17 @@ __global__ __launch_bounds__(256) void qr_chol_kernel(const cplx* __restrict__ p
     }
 }
 
-// A <- A R^-1: every wave its own 16 rows, all of them read before the first is written
+// out <- A R^-1 (out has A's layout and is another matrix): every wave its own 16 rows
 template <int NT>
-__global__ __launch_bounds__(256) void qr_apply_kernel(cplx* __restrict__ a, size_t lane_stride, int lda, int d, int k,
+__global__ __launch_bounds__(256) void qr_apply_kernel(const cplx* __restrict__ a, cplx* __restrict__ out, size_t lane_stride, int lda, int d, int k,
                                                        const int* __restrict__ status, const cplx* __restrict__ rinv) {
     const int lane_id = blockIdx.y;
     if (status[lane_id]) return;
     const int l = threadIdx.x & 63, row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
     if (row0 >= d) return;
     const int li = l & 15, lk = l >> 4;
-    cplx* A = a + (size_t)lane_id * lane_stride;
+    const cplx* A = a + (size_t)lane_id * lane_stride;
+    cplx* O = out + (size_t)lane_id * lane_stride;
     const cplx* R = rinv + (size_t)lane_id * k * k;
     double4_t cre[NT], cim[NT];
 #pragma unroll
@@ -186,7 +202,7 @@ __global__ __launch_bounds__(256) void qr_apply_kernel(cplx* __restrict__ a, siz
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int r = row0 + 4 * q + lk, c = 16 * t + li;
-            if (r < d && c < k) A[(size_t)r * lda + c] = make_double2(cre[t][q], cim[t][q]);
+            if (r < d && c < k) O[(size_t)r * lda + c] = make_double2(cre[t][q], cim[t][q]);
         }
 }
 
@@ -294,24 +310,25 @@ hipError_t grant_lds(K kernel, size_t bytes) {
 
 int sk_qr_slabs(int d) { return (d + kSlabRows - 1) / kSlabRows; }
 
-hipError_t launch_sk_qr(void* a, size_t lane_stride, int lda, int d, int k, int batch, double abs_floor, void* partial, void* rinv, int* status,
-                        hipStream_t s) {
+hipError_t launch_sk_qr(void* a, void* scratch, size_t lane_stride, int lda, int d, int k, int batch, double abs_floor, void* partial, void* rinv,
+                        int* status, hipStream_t s) {
     const int nslabs = sk_qr_slabs(d), nt = k <= 16 ? 1 : (k <= 32 ? 2 : 4);
-    cplx* A = static_cast<cplx*>(a);
     cplx* P = static_cast<cplx*>(partial);
     cplx* R = static_cast<cplx*>(rinv);
     const size_t lds = 2 * sizeof(cplx) * (size_t)k * k;
     hipError_t e = grant_lds(qr_chol_kernel, 2 * sizeof(cplx) * 64 * 64);
     if (e != hipSuccess) return e;
     const dim3 ggrid((nslabs + 3) / 4, batch), agrid((d + 63) / 64, batch);
-    for (int pass = 0; pass < 2; ++pass) {
+    for (int pass = 0; pass < 2; ++pass) {   // A -> scratch -> A
+        const cplx* A = static_cast<const cplx*>(pass == 0 ? a : scratch);
+        cplx* O = static_cast<cplx*>(pass == 0 ? scratch : a);
         if (nt == 1) qr_gram_kernel<1><<<ggrid, 256, 0, s>>>(A, lane_stride, lda, d, k, nslabs, status, P);
         else if (nt == 2) qr_gram_kernel<2><<<ggrid, 256, 0, s>>>(A, lane_stride, lda, d, k, nslabs, status, P);
         else qr_gram_kernel<4><<<ggrid, 256, 0, s>>>(A, lane_stride, lda, d, k, nslabs, status, P);
-        qr_chol_kernel<<<batch, 256, lds, s>>>(P, nslabs, k, abs_floor, status, R);
-        if (nt == 1) qr_apply_kernel<1><<<agrid, 256, 0, s>>>(A, lane_stride, lda, d, k, status, R);
-        else if (nt == 2) qr_apply_kernel<2><<<agrid, 256, 0, s>>>(A, lane_stride, lda, d, k, status, R);
-        else qr_apply_kernel<4><<<agrid, 256, 0, s>>>(A, lane_stride, lda, d, k, status, R);
+        qr_chol_kernel<<<batch, 256, lds, s>>>(P, nslabs, k, abs_floor, pass, status, R);
+        if (nt == 1) qr_apply_kernel<1><<<agrid, 256, 0, s>>>(A, O, lane_stride, lda, d, k, status, R);
+        else if (nt == 2) qr_apply_kernel<2><<<agrid, 256, 0, s>>>(A, O, lane_stride, lda, d, k, status, R);
+        else qr_apply_kernel<4><<<agrid, 256, 0, s>>>(A, O, lane_stride, lda, d, k, status, R);
     }
     return hipGetLastError();
 }

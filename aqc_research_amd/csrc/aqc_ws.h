@@ -284,7 +284,7 @@ struct aqc_ws {
         bool shared = false;
         DevBuf<double2> qr_part;        // gram partials [batch][slabs][k][k]
         DevBuf<double2> qr_rinv;        // [batch][k][k]
-        DevBuf<double2> tmp;            // [batch] lanes of scratch (U^H Omega)
+        DevBuf<double2> tmp;            // [batch] lanes of scratch (U^H Omega, then the QR's first-pass Q)
         DevBuf<int> status;             // [batch] QR status words
         DevBuf<int> idx;                // alt column indices [sets][batch][k] (grow-only)
         DevBuf<double> adam;            // m | v | best_x [batch][T] each, then best_f | lr [batch]

@@ -79,7 +79,7 @@ int sk_generate(aqc_ws* ws, int kind, unsigned long long seed, unsigned long lon
         if (before_write(ws, AQC_BUF_X) || before_write(ws, AQC_BUF_Y)) return 1;
     }
     ProfScope ps(ws, AQC_K_MISC);
-    HIP_OK(launch_sk_qr(X, ls, pitch, d, k, B, floor, ws->sk.qr_part, ws->sk.qr_rinv, ws->sk.status, ws->stream));
+    HIP_OK(launch_sk_qr(X, ws->sk.tmp, ls, pitch, d, k, B, floor, ws->sk.qr_part, ws->sk.qr_rinv, ws->sk.status, ws->stream));
     HIP_OK(launch_zgemm_batched(false, false, d, k, d, ws->sk.target, d, X, pitch, Y, pitch, us, ls, ls, B, ws->stream));
     return 0;
 }
@@ -96,13 +96,13 @@ int aqc_qr(int device, int m, int k, const double* a, double* q_out, int32_t* st
     if (device < 0 || device >= ndev) return fail("device out of range");
     HIP_OK(hipSetDevice(device));
     const size_t na = sizeof(double2) * (size_t)m * k;
-    DevBuf<double2> dA, dP, dR;
+    DevBuf<double2> dA, dT, dP, dR;
     DevBuf<int> dS;
     int st = 0;
-    if (dA.alloc((size_t)m * k) || dP.alloc((size_t)sk_qr_slabs(m) * k * k) || dR.alloc((size_t)k * k) || dS.alloc(1)) return 1;
+    if (dA.alloc((size_t)m * k) || dT.alloc((size_t)m * k) || dP.alloc((size_t)sk_qr_slabs(m) * k * k) || dR.alloc((size_t)k * k) || dS.alloc(1)) return 1;
     hipError_t e = hipMemcpy(dA, a, na, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(dS, 0, sizeof(int));
-    if (e == hipSuccess) e = launch_sk_qr(dA, 0, k, m, k, 1, 0.0, dP, dR, dS, nullptr);
+    if (e == hipSuccess) e = launch_sk_qr(dA, dT, 0, k, m, k, 1, 0.0, dP, dR, dS, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(q_out, dA, na, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(&st, dS, sizeof(int), hipMemcpyDeviceToHost);

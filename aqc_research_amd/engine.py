@@ -695,7 +695,8 @@ class RankDeficientSketch(RuntimeError):
 
 def qr(a: np.ndarray, device: Optional[int] = None) -> np.ndarray:
     """Orthonormal basis of the columns of ``a`` (m x k, k a power of two <= 64) by the device's CholeskyQR2 (aqc_qr): what
-    ``np.linalg.qr(a)[0]`` spans.  Raises RankDeficientSketch when a pivot vanishes."""
+    ``np.linalg.qr(a)[0]`` spans.  Raises RankDeficientSketch when a pivot vanishes or ``a`` is too ill-conditioned (from about 1e6
+    with its columns scaled to norm 1) for two passes to end orthonormal."""
     a = _lib.as_c128(a)
     if a.ndim != 2:
         raise ValueError("qr expects a matrix")

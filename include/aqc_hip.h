@@ -302,7 +302,9 @@ int aqc_mpsb_vh_bank(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas,
 int aqc_mpsb_gradient_of(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double trunc_thr, int max_bond, int block_from,
                          int block_to, int front_layer, double* grad /* [lanes][T] c128 */);
 /* one-sided Jacobi SVD on the device (the kernel behind aqc_mps_gate2): A (m x n row-major) = U diag(S) Vh,
- * k = min(m, n), S descending, U (m x k), Vh (k x n); *sweeps (optional) = Jacobi sweeps used */
+ * k = min(m, n), S descending, U (m x k), Vh (k x n); *sweeps (optional) = Jacobi sweeps used.  The input is not rescaled: the
+ * rotations work with squared column norms and |<x, y>|^2, which leave the double range when |A|_F is beyond about 2^+-250 (every
+ * rotation is skipped then); scalings by 2^+-100 are tested. */
 int aqc_svd(int device, int m, int n, const double* a, double* u, double* s, double* vh, int* sweeps);
 
 /* ---- coordinate descent (core_op_matrix.py:765  coord_descent_single_sweep(circ, thetas, target,
@@ -396,7 +398,10 @@ enum { AQC_SKETCH_RAND = 0, AQC_SKETCH_ALT = 1, AQC_SKETCH_EIGEN = 2 };
 enum { AQC_QR_OK = 0, AQC_QR_RANK_DEFICIENT = 1 };   /* per-matrix status word of the device QR */
 /* np.linalg.qr(a)[0] of sk_core.py:353,459 up to the choice of basis: q_out (m x k, row-major) has orthonormal columns spanning the
  * columns of a (m x k, k a power of two <= 64, m >= k), by CholeskyQR2 on the matrix cores; host pointers, one matrix, like the SVD entry.
- * A rank-deficient a sets *status = AQC_QR_RANK_DEFICIENT and q_out = a (status NULL: the call fails instead). */
+ * Status 0 means an orthonormal q_out.  *status = AQC_QR_RANK_DEFICIENT and q_out = a, bit for bit (status NULL: the call fails
+ * instead), when a is rank deficient -- a Cholesky pivot of either pass not finite or not above 1e-10 of its column's squared norm --
+ * or so ill-conditioned that the first pass's Q is not orthonormal to 1e-4 entrywise, which happens from a condition number
+ * (columns scaled to norm 1) of about 1e6 on: double precision determines no range to better than 1e-6 there. */
 int aqc_qr(int device, int m, int k, const double* a, double* q_out, int32_t* status);
 /* the target unitary of every lane (shared != 0: one for all), [batch or 1][2^n][2^n] c128, kept resident: what
  * SketchingVectorsBase holds as target_matrix (sk_core.py:34-91).  The buffer is allocated on first use. */
@@ -404,8 +409,8 @@ int aqc_ws_sketch_target(aqc_ws* ws, const double* U, int shared);
 /* SketchingVectorsBase.generate (sk_core.py:350-357 rand, :385-399 alt, :447-463 eigen) for every lane, on the device: AQC_BUF_X <- X,
  * AQC_BUF_Y <- U X, with the thetas in use (eigen).  `iteration` numbers the sketch (part of the Philox counter); omega, when not
  * NULL, is a host draw [batch][2^n][k] c128 used instead of the device's; alt_idx [batch][k] are the columns of `alt` (required
- * there).  status (optional, [batch]; synchronises): the QR's word per lane -- a rank-deficient lane keeps its un-orthonormalised
- * matrix in X, finite, and the other lanes are complete. */
+ * there).  status (optional, [batch]; synchronises): the QR's word per lane (see aqc_qr) -- a flagged lane keeps its
+ * un-orthonormalised matrix in X bit for bit, and the other lanes are complete. */
 int aqc_ws_sketch_generate(aqc_ws* ws, int kind, uint64_t seed, int64_t iteration, const int32_t* alt_idx, const double* omega,
                            int32_t* status);
 /* the draw alone: buf <- Omega of every lane for (kind = rand or eigen, seed, iteration), as the generate entry would draw it

@@ -36,6 +36,96 @@ def cholesky_qr2(a: np.ndarray) -> np.ndarray:
     return q
 
 
+PIVOT_REL = 1e-10      # kPivotRel of csrc/aqc_sketch.hip
+ORTH_TOL = 1e-4        # kOrthTol: the largest entry of G2 - I a lane may show in the second pass
+
+
+def cholesky_qr2_rule(a: np.ndarray, pivot_rel: float = PIVOT_REL, abs_floor: float = 0.0, orth_tol: float = ORTH_TOL) -> tuple:
+    """The device's QR with its status rule, (q, status): two passes of Gram matrix, right-looking Cholesky and triangular solve.
+    A pivot that is not finite, not above ``pivot_rel`` times its diagonal entry of that pass's Gram matrix or not above
+    ``abs_floor`` flags the matrix; so does a second Gram matrix with an entry of G2 - I above ``orth_tol`` in modulus, which is
+    what a first pass that lost its orthogonality to kappa^2 eps looks like.  A flagged matrix comes back unchanged."""
+    a = np.array(a, dtype=np.complex128)
+    q, k = a.copy(), a.shape[1]
+    for second in (False, True):
+        with np.errstate(all="ignore"):
+            g = np.conj(q.T) @ q
+            if second and not np.all(np.abs(g - np.eye(k)) <= orth_tol):
+                return a, QR_RANK_DEFICIENT
+            diag, low = np.real(np.diag(g)).copy(), np.zeros((k, k), dtype=np.complex128)
+            for j in range(k):
+                piv = g[j, j].real
+                if not (piv > pivot_rel * diag[j]) or not (piv > abs_floor) or not np.isfinite(piv):
+                    return a, QR_RANK_DEFICIENT
+                low[j, j] = np.sqrt(piv)
+                low[j + 1:, j] = g[j + 1:, j] / low[j, j]
+                g[j + 1:, j + 1:] -= np.outer(low[j + 1:, j], np.conj(low[j + 1:, j]))
+            x = np.zeros((k, k), dtype=np.complex128)          # L^-1 by forward substitution, a column at a time
+            for c in range(k):
+                x[c, c] = 1.0 / low[c, c]
+                for i in range(c + 1, k):
+                    x[i, c] = -(low[i, c:i] @ x[c:i, c]) / low[i, i]
+            q = q @ np.conj(x.T)
+    return q, 0
+
+
+def extended_range_basis(a: np.ndarray) -> np.ndarray:
+    """Orthonormal basis of the range of ``a`` by modified Gram-Schmidt, run twice, in x86 extended precision (np.clongdouble,
+    eps 1.1e-19: the range is good to ~1e-19 kappa), rounded to complex128 at the end."""
+    q = np.array(a, dtype=np.clongdouble)
+    for _ in range(2):
+        for j in range(q.shape[1]):
+            for i in range(j):
+                q[:, j] -= np.sum(np.conj(q[:, i]) * q[:, j]) * q[:, i]
+            q[:, j] /= np.sqrt(np.sum(np.real(q[:, j]) ** 2 + np.imag(q[:, j]) ** 2))
+    return q.astype(np.complex128)
+
+
+def haar_isometry(m: int, n: int, rng) -> np.ndarray:
+    """(m, n) with orthonormal columns, Haar: Q of a complex Gaussian with the phases of R's diagonal moved into Q."""
+    q, r = np.linalg.qr(rng.standard_normal((m, n)) + 1j * rng.standard_normal((m, n)))
+    ph = np.diag(r) / np.abs(np.diag(r))
+    return q * ph
+
+
+def kahan(d: int, k: int, theta: float, seed: int) -> np.ndarray:
+    """A (d, k) Kahan matrix: R = diag(s^0 .. s^(k-1)) (I - c strict_upper_ones), c, s = cos, sin theta, times a Haar isometry
+    from the left.  Its columns all have norm 1 to O(1), every Cholesky pivot ratio is benign, and its condition number grows
+    like (1 + c)^k: the matrices on which a per-column pivot test sees nothing."""
+    c, s = np.cos(theta), np.sin(theta)
+    r = (s ** np.arange(k))[:, None] * (np.eye(k) - c * np.triu(np.ones((k, k)), 1))
+    return np.ascontiguousarray(np.linalg.qr(_gauss(np.random.default_rng(seed), d, k))[0] @ r)
+
+
+def with_spectrum(m: int, n: int, s, rng) -> tuple:
+    """(a, U, V) with a = U diag(s) V^H, U (m, k) and V (n, k) Haar isometries, k = min(m, n) = len(s)."""
+    s = np.asarray(s, dtype=float)
+    u, v = haar_isometry(m, len(s), rng), haar_isometry(n, len(s), rng)
+    return np.ascontiguousarray((u * s) @ np.conj(v.T)), u, v
+
+
+def cond_equilibrated(a: np.ndarray) -> float:
+    """2-norm condition number of ``a`` with its columns scaled to norm 1 (in extended precision before the SVD)."""
+    al = np.array(a, dtype=np.clongdouble)
+    al = al / np.sqrt(np.sum(np.real(al) ** 2 + np.imag(al) ** 2, axis=0))
+    sv = np.linalg.svd(al.astype(np.complex128), compute_uv=False)
+    return float(sv[0] / sv[-1]) if sv[-1] > 0 else float("inf")
+
+
+def straddling_family():
+    """(name, matrix) over a family that crosses the QR's status rule: Kahan matrices at theta = 0.50 .. 1.40 in three shapes
+    (kappa_eq from 3e2 to beyond 1e17) and geometric spectra of condition 1e6 .. 1e12."""
+    for d, k in ((64, 64), (64, 32), (256, 64)):
+        for theta in np.arange(50, 141, 5) / 100.0:
+            yield f"kahan {d}x{k} theta={theta:.2f}", kahan(d, k, theta, seed=7)
+    for e in range(6, 13):
+        yield f"geometric 100x16 kappa=1e{e}", with_spectrum(100, 16, np.geomspace(1.0, 10.0 ** -e, 16), np.random.default_rng(e))[0]
+
+
+def _gauss(rng, *shape):
+    return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+
+
 def generate(kind: int, target: np.ndarray, k: int, *, om=None, idx=None, vh_mul=None) -> tuple:
     """(X, Y = U X) of one lane: ``om`` the draw (rand, eigen), ``idx`` the k column indices (alt), ``vh_mul`` the map
     M -> V(thetas)^H M (eigen).  Householder QR: the objective does not depend on the basis chosen for the range."""

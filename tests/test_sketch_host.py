@@ -71,6 +71,53 @@ def test_cholesky_qr2_reference(d, k):
     assert np.max(np.abs(q @ np.conj(q.T) - qh @ np.conj(qh.T))) < 1e-13
 
 
+EPS = 2.2e-16
+
+
+def _orth_and_range(q, a):
+    ref = sk.extended_range_basis(a)
+    return (float(np.max(np.abs(np.conj(q.T) @ q - np.eye(a.shape[1])))), float(np.max(np.abs(q @ np.conj(q.T) - ref @ np.conj(ref.T)))))
+
+
+@pytest.mark.parametrize("kappa", [1e2, 1e3, 1e4])
+@pytest.mark.parametrize("spectrum", ["geometric", "last"])
+@pytest.mark.parametrize("d,k", [(64, 16), (100, 16), (256, 64)])
+def test_qr_rule_on_the_conditioning_ladder(d, k, spectrum, kappa):
+    """The device's rule in NumPy accepts condition numbers up to 1e4 and returns the range to 64 eps kappa against the
+    extended-precision reference (the ladder of tests/test_hip_qr_conditioning.py)."""
+    s = np.geomspace(1.0, 1.0 / kappa, k) if spectrum == "geometric" else np.r_[np.ones(k - 1), 1.0 / kappa]
+    a = sk.with_spectrum(d, k, s, np.random.default_rng(int(d + k + np.log10(kappa))))[0]
+    q, st = sk.cholesky_qr2_rule(a)
+    assert st == 0
+    e_orth, e_proj = _orth_and_range(q, a)
+    assert e_orth < 1e-12 and e_proj <= 64 * EPS * kappa
+
+
+def test_qr_rule_status_contract_and_why_the_second_pass_is_tested():
+    """Over the straddling family, status 0 means an orthonormal Q of a range that double precision determines (64 eps kappa_eq
+    < 1e-6), and a flagged matrix comes back as it was.  With the test on G2 - I switched off -- pivots alone, as the kernel was --
+    the same family holds matrices that pass every pivot test of both passes and break that contract."""
+    silent, sides = [], {0: 0, sk.QR_RANK_DEFICIENT: 0}
+    must_accept = must_flag = 0
+    for name, a in sk.straddling_family():
+        keq = sk.cond_equilibrated(a)
+        q, st = sk.cholesky_qr2_rule(a)
+        sides[st] += 1
+        if st == 0:
+            e_orth, e_proj = _orth_and_range(q, a)
+            assert 64 * EPS * keq < 1e-6 and e_orth < 1e-12 and e_proj <= 64 * EPS * keq, (name, keq, e_orth, e_proj)
+        else:
+            assert np.array_equal(q, a), name
+        must_accept += keq <= 1e4
+        must_flag += keq >= 1e14
+        assert not (keq <= 1e4 and st != 0) and not (keq >= 1e14 and st == 0), (name, keq, st)
+        q_old, st_old = sk.cholesky_qr2_rule(a, orth_tol=np.inf)
+        if st_old == 0 and (64 * EPS * keq >= 1e-6 or _orth_and_range(q_old, a)[0] >= 1e-12):
+            silent.append(name)
+    assert must_accept > 0 and must_flag > 0 and sides[0] > 0 and sides[sk.QR_RANK_DEFICIENT] > 0
+    assert silent, "the pivot tests alone were expected to let an ill-conditioned matrix through"
+
+
 def test_alt_index_schedule_follows_the_reference_rule():
     from aqc_research_amd.model_sketching.aqc_sketching import AltIndexSchedule
 
