@@ -125,6 +125,8 @@ SIGNATURES = {
     "aqc_ws_plan_substages": (c_int, [_P, c_int]),
     "aqc_ws_lbfgs": (c_int, [_P, _D, c_int, c_int, c_double, c_double, c_double, c_int, c_int, c_int, c_int, _D, _D, _D, POINTER(c_int64),
                      POINTER(c_int64), _D, POINTER(c_int64)]),
+    "aqc_ws_lbfgs_mat": (c_int, [_P, _D, c_int, c_int, c_double, c_double, c_double, c_double, c_int, _D, _D, _D, POINTER(c_int64),
+                         POINTER(c_int64), POINTER(c_int32)]),
     "aqc_ws_surrogate_eval": (c_int, [_P, _D, c_int, _D, POINTER(c_int64), c_int, c_int, c_int, _D, _D, _D, _D, _D]),
     "aqc_qr": (c_int, [c_int, c_int, c_int, _D, _D, POINTER(c_int32)]),
     "aqc_ws_sketch_target": (c_int, [_P, _D, c_int]),

@@ -393,9 +393,13 @@ def batched_lbfgs(fun: Callable[[np.ndarray, bool], Tuple[np.ndarray, np.ndarray
 class BatchedSketchingObjective:
     """B lanes of the full-range AQC objective ``1 - Re<V, U_b>/d`` (``SketchingObjectiveEx`` +
     ``FullRangeSketchingVectors``, sk_core.py:167-326): random restarts and / or different target unitaries on one
-    workspace.  ``targets``: (B, d, d) complex128, or (d, d) shared by all ``lanes``."""
+    workspace.  ``targets``: (B, d, d) complex128, or (d, d) shared by all ``lanes``.
 
-    def __init__(self, circ, targets: np.ndarray, lanes: Optional[int] = None, device: Optional[int] = None):
+    ``x_mat`` -- (d, k), or (lanes, d, k) -- is a fixed sketching matrix X: the objective is then ``1 - Re tr(X^H V^H U X)/k`` on a
+    workspace of k columns (sk_core.py:189-197 with a generator that always returns X).  Default: the identity, i.e. full AQC."""
+
+    def __init__(self, circ, targets: np.ndarray, lanes: Optional[int] = None, device: Optional[int] = None,
+                 x_mat: Optional[np.ndarray] = None):
         t = np.ascontiguousarray(targets, dtype=np.complex128)
         d = circ.dimension
         if t.shape == (d, d):
@@ -405,9 +409,22 @@ class BatchedSketchingObjective:
         if t.ndim != 3 or t.shape[1:] != (d, d):
             raise ValueError("targets must have shape (lanes, 2^n, 2^n)")
         self.circ, self.batch, self.T, self._d = circ, t.shape[0], circ.num_thetas, d
-        self.ws = Workspace(HipContext.of(circ), batch=self.batch, ncols=d, device=device)
-        self.ws.upload(BUF_Y, t)
-        self.ws.set_identity(BUF_X)
+        if x_mat is None:
+            self._k = d
+            self.ws = Workspace(HipContext.of(circ), batch=self.batch, ncols=d, device=device)
+            self.ws.upload(BUF_Y, t)
+            self.ws.set_identity(BUF_X)
+        else:
+            x = np.asarray(x_mat, dtype=np.complex128)
+            if x.ndim == 2:
+                x = np.broadcast_to(x, (self.batch,) + x.shape)
+            if x.ndim != 3 or x.shape[:2] != (self.batch, d) or not 1 <= x.shape[2] <= d:
+                raise ValueError("x_mat must have shape (2^n, k) or (lanes, 2^n, k) with 1 <= k <= 2^n")
+            x = np.ascontiguousarray(x)
+            self._k = x.shape[2]
+            self.ws = Workspace(HipContext.of(circ), batch=self.batch, ncols=self._k, device=device)
+            self.ws.upload(BUF_Y, np.ascontiguousarray(t @ x))      # U X
+            self.ws.upload(BUF_X, x)
         self.num_evals = 0
 
     def value_and_grad(self, thetas: np.ndarray, update_state: bool = True) -> Tuple[np.ndarray, np.ndarray]:
@@ -419,7 +436,33 @@ class BatchedSketchingObjective:
         trace = self.ws.vdot(BUF_X, BUF_Z)                      # <I|V^H U>        (:192)
         self.ws.grad(None, True)                                # sweep            (:193)
         self.num_evals += self.batch
-        return 1.0 - trace.real / self._d, -self.ws.get_grads().real / self._d
+        return 1.0 - trace.real / self._k, -self.ws.get_grads().real / self._k
+
+    def minimize_on_device(self, x0: np.ndarray, *, maxiter: int = 100, memory: int = 10, gtol: float = 1e-7, ftol: float = 1e-12,
+                           fobj_thr: float = 0.0, fidelity_thr: float = 0.0, max_backtracks: int = 12) -> Dict:
+        """All lanes minimised by the device-resident L-BFGS (``aqc_ws_lbfgs_mat``): the algorithm of ``batched_lbfgs`` on
+        ``value_and_grad`` with thetas, gradients and history resident in HBM; the host reads one flag word per line-search
+        trial.  A lane stops early at ``fun <= fobj_thr`` or ``|tr|^2/k^2 >= fidelity_thr`` (0: off).  ``status``: per lane 0, or
+        1 where the value or the gradient was not finite -- that lane stays where it was, the others are not affected.
+        ``nfev`` counts evaluations of the batch; ``fidelity`` is ``|tr|^2/k^2`` (Hilbert-Schmidt with the identity)."""
+        import ctypes
+
+        from . import _lib
+
+        x = np.ascontiguousarray(x0, dtype=np.float64).reshape(self.batch, self.T)
+        xo = np.empty_like(x)
+        f = np.empty(self.batch)
+        fid = np.empty(self.batch)
+        nit = np.zeros(self.batch, dtype=np.int64)
+        status = np.zeros(self.batch, dtype=np.int32)
+        nfev = ctypes.c_int64()
+        self.ws._touch(_lib.BUF_Z, _lib.BUF_W, _lib.BUF_ZW)   # rewritten by the driver
+        _lib.check(self.ws._L.aqc_ws_lbfgs_mat(self.ws.handle, _lib.dptr(x), int(maxiter), int(memory), float(gtol), float(ftol),
+                                              float(fobj_thr), float(fidelity_thr), int(max_backtracks), _lib.dptr(xo), _lib.dptr(f),
+                                              _lib.dptr(fid), nit.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(nfev),
+                                              status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        self.num_evals += int(nfev.value) * self.batch
+        return {"x": xo, "fun": f, "nit": nit, "nfev": int(nfev.value), "fidelity": fid, "status": status}
 
     def close(self) -> None:
         self.ws.close()

@@ -209,6 +209,27 @@ hipError_t lb_armijo(const LbState& st, double c1, const double* thetas, const d
                      int* flags, hipStream_t s);
 hipError_t lb_copy_raw(const LbState& st, hipStream_t s);
 hipError_t lb_history(const LbState& st, int count, double ftol, const double* f_acc, const double* g_acc, hipStream_t s);
+// The state-free mode of the same step kernels (S = 0): L-BFGS on the matrix objective f = 1 - Re tr(X^H V^H Y) / k of full and
+// fixed-sketch AQC.  The objective has no state, so an accepted trial's value and gradient are final: no amplitude rows, no raw
+// copies, no probe / commit / second evaluation.  What the mode adds to LbState:
+struct LbMat {
+    int k;                                    // columns of the workspace (the trace's divisor)
+    double gtol, fobj_thr, fid_thr;           // a lane stops at max|g| <= gtol, f <= fobj_thr, |tr|^2/k^2 >= fid_thr (thresholds: 0 = off)
+    double *gmax;                             // max|g| at the current point (|tr|^2/k^2 there: LbState::fidelity)
+    double *ft, *gt, *gmax_t, *fid_t;         // the trial points' results
+    double *f_acc, *g_acc, *gmax_acc, *fid_acc;   // ... of the accepted points (the current point's for a lane that does not move)
+    int* status;                              // per lane, 0 = fine (kLbNonFinite: f or g was not finite; the lane stopped where it was)
+    int* flags;                               // ONE word per line-search trial: kLbNotDone | kLbAnyActive
+};
+enum { kLbNotDone = 1, kLbAnyActive = 2 };    // some lane still backtracks / some lane goes on to another iteration
+enum { kLbNonFinite = 1 };
+// f, g, max|g| and |tr|^2/k^2 of every lane from the trace and the complex gradient an evaluation leaves (init: at the start point, into
+// the current point's rows, with the first "any lane active" flag; else into the trial rows)
+hipError_t lb_mat_value(const LbState& st, const LbMat& m, const void* trace, const void* grads, int init, hipStream_t s);
+hipError_t lb_mat_direction(const LbState& st, const LbMat& m, int count, hipStream_t s);
+hipError_t lb_mat_armijo(const LbState& st, const LbMat& m, double c1, const double* thetas, hipStream_t s);
+// runs once no lane backtracks any more (the flag word Armijo has just written) or `last`; sets kLbAnyActive
+hipError_t lb_mat_history(const LbState& st, const LbMat& m, int count, double ftol, int last, hipStream_t s);
 
 // aqc_mps.hip
 hipError_t launch_mps_scale(void* g, const double* lam, int rows, int cols, hipStream_t s);

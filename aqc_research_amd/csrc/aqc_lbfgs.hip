@@ -118,6 +118,51 @@ __global__ void lb_commit0_kernel(LbState st, const cplx* hs, const cplx* raw_g,
     }
 }
 
+// State-free mode: does a lane at a point of value f, max|g| gm and |tr|^2/k^2 fid go on to another iteration?
+__device__ __forceinline__ bool lb_mat_goes_on(const LbMat& m, double f, double gm, double fid) {
+    if (!(gm > m.gtol)) return false;
+    if (m.fobj_thr > 0.0 && f <= m.fobj_thr) return false;
+    if (m.fid_thr > 0.0 && fid >= m.fid_thr) return false;
+    return true;
+}
+// The matrix objective of one lane from what an evaluation leaves (trace = <X|V^H Y>, grads = the complex gradient of the sweep
+// from X): f = 1 - Re tr / k, g = -Re grads / k (sk_core.py:192-197, as sk_adam_kernel takes them), max|g| and |tr|^2 / k^2 (the
+// Hilbert-Schmidt fidelity when X = I).  A lane whose trace or g is not finite gets its status word set and stops where it is (done,
+// inactive, step 0); lanes with a status word are skipped from then on.  init: the start point -- results into the current
+// point's rows and the first kLbAnyActive; else into the trial rows.
+__global__ __launch_bounds__(kLbThreads) void lb_mat_value_kernel(LbState st, LbMat m, const cplx* trace, const cplx* grads, int init) {
+    __shared__ double red[8];
+    const int b = blockIdx.x, t = threadIdx.x, T = st.T;
+    if (!init && b == 0 && t == 0) *m.flags = 0;   // a trial starts with a clear flag word (the start point's is cleared by the driver)
+    if (m.status[b]) return;
+    const size_t off = (size_t)b * T;
+    double* g_out = init ? st.g : m.gt;
+    const cplx tr = trace[b];
+    const double f = 1.0 - tr.x / m.k, fid = (tr.x * tr.x + tr.y * tr.y) / ((double)m.k * m.k);
+    double gm = 0.0, bad = (isfinite(f) && isfinite(fid)) ? 0.0 : 1.0;   // fid: the trace's imaginary part too
+    for (int i = t; i < T; i += blockDim.x) {
+        const double g = -grads[off + i].x / m.k;
+        g_out[off + i] = g;
+        gm = fmax(gm, fabs(g));
+        if (!isfinite(g)) bad = 1.0;
+    }
+    gm = block_max(gm, red);
+    bad = block_max(bad, red);
+    if (t == 0) {
+        (init ? st.f : m.ft)[b] = f;
+        (init ? st.fidelity : m.fid_t)[b] = fid;
+        (init ? m.gmax : m.gmax_t)[b] = gm;
+        if (bad > 0.0) {
+            m.status[b] = kLbNonFinite;
+            st.active[b] = 0; st.done[b] = 1; st.step[b] = 0.0;
+        } else if (init) {
+            const int a = lb_mat_goes_on(m, f, gm, fid) ? 1 : 0;
+            st.active[b] = a;
+            if (a) atomicOr(m.flags, (int)kLbAnyActive);
+        }
+    }
+}
+
 // active &= max|g| > gtol [and fidelity < thr]; flags[2] |= some lane is active
 __global__ __launch_bounds__(kLbThreads) void lb_active_kernel(LbState st, double gtol, double fid_thr, int* flags) {
     __shared__ double red[8];
@@ -134,11 +179,17 @@ __global__ __launch_bounds__(kLbThreads) void lb_active_kernel(LbState st, doubl
     }
 }
 
+// The step kernels below are written once, as bodies with a mode: kMat = false is the surrogate's state machine (amplitude rows, raw
+// copies of the complex gradient), kMat = true the state-free matrix objective (S = 0; see LbMat in aqc_launch.h).  Each mode is a
+// kernel of its own, so the surrogate's kernels are exactly the kMat = false instances.
+
 // Two-loop recursion, search direction, slope; step = active ? 1 : 0, done = !active, x_new = x
-__global__ __launch_bounds__(kLbThreads) void lb_direction_kernel(LbState st, int count) {
+template <bool kMat>
+__device__ __forceinline__ void lb_direction_body(const LbState& st, int count, const LbMat* mat) {
     __shared__ double red[8];
     __shared__ double alpha[32];
     const int b = blockIdx.x, t = threadIdx.x, T = st.T, m = st.memory;
+    if constexpr (kMat) { if (mat->status[b]) return; }   // a flagged lane is skipped (done and inactive since it was flagged)
     const size_t off = (size_t)b * T;
     const int k = count < m ? count : m;
     double* q = st.d + off;
@@ -187,6 +238,10 @@ __global__ __launch_bounds__(kLbThreads) void lb_direction_kernel(LbState st, in
         slope = -block_sum(gg, red);
     }
     for (int i = t; i < T; i += blockDim.x) st.x_new[off + i] = st.x[off + i];
+    if constexpr (kMat) {   // a lane that accepts nothing keeps the current point's results
+        for (int i = t; i < T; i += blockDim.x) mat->g_acc[off + i] = st.g[off + i];
+        if (t == 0) { mat->f_acc[b] = st.f[b]; mat->gmax_acc[b] = mat->gmax[b]; mat->fid_acc[b] = st.fidelity[b]; }
+    }
     if (t == 0) {
         const int a = st.active[b];
         st.slope[b] = slope;
@@ -194,6 +249,8 @@ __global__ __launch_bounds__(kLbThreads) void lb_direction_kernel(LbState st, in
         st.done[b] = a ? 0 : 1;
     }
 }
+__global__ __launch_bounds__(kLbThreads) void lb_direction_kernel(LbState st, int count) { lb_direction_body<false>(st, count, nullptr); }
+__global__ __launch_bounds__(kLbThreads) void lb_mat_direction_kernel(LbState st, LbMat mat, int count) { lb_direction_body<true>(st, count, &mat); }
 // trial point into the workspace's theta buffer
 __global__ void lb_trial_kernel(LbState st, double* thetas) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -201,23 +258,39 @@ __global__ void lb_trial_kernel(LbState st, double* thetas) {
     const int b = (int)(i / st.T);
     thetas[i] = st.x[i] + st.step[b] * st.d[i];
 }
-// Armijo test per lane; accepted lanes keep the trial point and its raw device results; flags[3] |= some lane not done
-__global__ __launch_bounds__(kLbThreads) void lb_armijo_kernel(LbState st, double c1, const double* thetas, const double* ft,
-                                                              const cplx* raw_hs_t, const cplx* raw_g0_t, int* flags) {
+// Armijo test per lane; accepted lanes keep the trial point and its raw device results (kMat: its value and gradient, which are
+// final); flags[3] |= some lane not done (kMat: kLbNotDone of the one flag word)
+template <bool kMat>
+__device__ __forceinline__ void lb_armijo_body(const LbState& st, double c1, const double* thetas, const double* ft, const cplx* raw_hs_t,
+                                               const cplx* raw_g0_t, int* flags, const LbMat* mat) {
     const int b = blockIdx.x, t = threadIdx.x;
     const size_t off = (size_t)b * st.T;
     const bool was_done = st.done[b] != 0;
     const double step = st.step[b];
     const bool ok = !was_done && ft[b] <= st.f[b] + c1 * step * st.slope[b];
     if (ok) {
-        for (int i = t; i < st.T; i += blockDim.x) { st.x_new[off + i] = thetas[off + i]; st.acc_g0[off + i] = raw_g0_t[off + i]; }
-        for (int i = t; i < st.S; i += blockDim.x) st.acc_hs[(size_t)b * st.S + i] = raw_hs_t[(size_t)b * st.S + i];
+        if constexpr (kMat) {
+            for (int i = t; i < st.T; i += blockDim.x) { st.x_new[off + i] = thetas[off + i]; mat->g_acc[off + i] = mat->gt[off + i]; }
+        } else {
+            for (int i = t; i < st.T; i += blockDim.x) { st.x_new[off + i] = thetas[off + i]; st.acc_g0[off + i] = raw_g0_t[off + i]; }
+            for (int i = t; i < st.S; i += blockDim.x) st.acc_hs[(size_t)b * st.S + i] = raw_hs_t[(size_t)b * st.S + i];
+        }
     }
     __syncthreads();
     if (t == 0) {
+        if constexpr (kMat) {
+            if (ok) { mat->f_acc[b] = ft[b]; mat->gmax_acc[b] = mat->gmax_t[b]; mat->fid_acc[b] = mat->fid_t[b]; }
+        }
         if (ok) st.done[b] = 1;
-        else if (!was_done) { st.step[b] = 0.5 * step; atomicOr(&flags[3], 1); }
+        else if (!was_done) { st.step[b] = 0.5 * step; atomicOr(kMat ? flags : &flags[3], kMat ? (int)kLbNotDone : 1); }
     }
+}
+__global__ __launch_bounds__(kLbThreads) void lb_armijo_kernel(LbState st, double c1, const double* thetas, const double* ft,
+                                                              const cplx* raw_hs_t, const cplx* raw_g0_t, int* flags) {
+    lb_armijo_body<false>(st, c1, thetas, ft, raw_hs_t, raw_g0_t, flags, nullptr);
+}
+__global__ __launch_bounds__(kLbThreads) void lb_mat_armijo_kernel(LbState st, LbMat mat, double c1, const double* thetas) {
+    lb_armijo_body<true>(st, c1, thetas, mat.ft, nullptr, nullptr, mat.flags, &mat);
 }
 // rows of lanes that will not move start as the current point's raw results
 __global__ void lb_copy_raw_kernel(LbState st) {
@@ -226,7 +299,10 @@ __global__ void lb_copy_raw_kernel(LbState st) {
     if (i < (size_t)st.B * st.S) st.acc_hs[i] = st.cur_hs[i];
 }
 // History update and convergence flags after the accepted points have been evaluated under the new state
-__global__ __launch_bounds__(kLbThreads) void lb_history_kernel(LbState st, int count, double ftol, const double* f_acc, const double* g_acc) {
+// (kMat: the accepted results are the trials' own, and the next iteration's "any lane active" test -- max|g| > gtol and the two
+// thresholds -- is taken here, into the flag word Armijo has just written, so that the host reads that one word and nothing else)
+template <bool kMat>
+__device__ __forceinline__ void lb_history_body(const LbState& st, int count, double ftol, const double* f_acc, const double* g_acc, const LbMat* mat) {
     __shared__ double red[8];
     const int b = blockIdx.x, t = threadIdx.x, T = st.T;
     const size_t off = (size_t)b * T;
@@ -246,17 +322,39 @@ __global__ __launch_bounds__(kLbThreads) void lb_history_kernel(LbState st, int 
     const bool good = moved && sy > 1e-12 * yy;
     if (!good) for (int i = t; i < T; i += blockDim.x) { s[i] = 0.0; y[i] = 0.0; }
     for (int i = t; i < T; i += blockDim.x) { st.x[off + i] = st.x_new[off + i]; st.g[off + i] = g_acc[off + i]; }
-    for (int i = t; i < T; i += blockDim.x) st.cur_g0[off + i] = st.acc_g0[off + i];
-    for (int i = t; i < st.S; i += blockDim.x) st.cur_hs[(size_t)b * st.S + i] = st.acc_hs[(size_t)b * st.S + i];
+    if constexpr (!kMat) {
+        for (int i = t; i < T; i += blockDim.x) st.cur_g0[off + i] = st.acc_g0[off + i];
+        for (int i = t; i < st.S; i += blockDim.x) st.cur_hs[(size_t)b * st.S + i] = st.acc_hs[(size_t)b * st.S + i];
+    }
     __syncthreads();
     if (t == 0) {
         st.rho[(size_t)slot * st.B + b] = good ? 1.0 / sy : 0.0;
         const double f = st.f[b], fa = f_acc[b];
         const bool small = fabs(f - fa) <= ftol * fmax(1.0, fabs(f));
         if (active) st.nit[b] += 1;
-        st.active[b] = (active && moved && !small) ? 1 : 0;
+        if constexpr (kMat) {
+            const double gm = mat->gmax_acc[b], fid = mat->fid_acc[b];
+            const int a = (active && moved && !small && lb_mat_goes_on(*mat, fa, gm, fid)) ? 1 : 0;
+            st.active[b] = a;
+            mat->gmax[b] = gm;
+            st.fidelity[b] = fid;
+            if (a) atomicOr(mat->flags, (int)kLbAnyActive);
+        } else {
+            st.active[b] = (active && moved && !small) ? 1 : 0;
+        }
         st.f[b] = fa;
     }
+}
+__global__ __launch_bounds__(kLbThreads) void lb_history_kernel(LbState st, int count, double ftol, const double* f_acc, const double* g_acc) {
+    lb_history_body<false>(st, count, ftol, f_acc, g_acc, nullptr);
+}
+// One launch per line-search trial, enqueued behind Armijo: it acts once no lane backtracks any more -- the flag word of that
+// trial, complete since the Armijo kernel has finished -- or after the last trial allowed.  (The word is only OR-ed into by this
+// kernel, and with another bit, so every workgroup reads the same kLbNotDone.)
+__global__ __launch_bounds__(kLbThreads) void lb_mat_history_kernel(LbState st, LbMat mat, int count, double ftol, int last) {
+    if (!last && (__atomic_load_n(mat.flags, __ATOMIC_RELAXED) & kLbNotDone)) return;
+    if (mat.status[blockIdx.x]) return;
+    lb_history_body<true>(st, count, ftol, mat.f_acc, mat.g_acc, &mat);
 }
 
 }  // namespace
@@ -304,6 +402,23 @@ hipError_t lb_copy_raw(const LbState& st, hipStream_t s) {
 }
 hipError_t lb_history(const LbState& st, int count, double ftol, const double* f_acc, const double* g_acc, hipStream_t s) {
     lb_history_kernel<<<st.B, kLbThreads, 0, s>>>(st, count, ftol, f_acc, g_acc);
+    return hipGetLastError();
+}
+
+hipError_t lb_mat_value(const LbState& st, const LbMat& m, const void* trace, const void* grads, int init, hipStream_t s) {
+    lb_mat_value_kernel<<<st.B, kLbThreads, 0, s>>>(st, m, (const cplx*)trace, (const cplx*)grads, init);
+    return hipGetLastError();
+}
+hipError_t lb_mat_direction(const LbState& st, const LbMat& m, int count, hipStream_t s) {
+    lb_mat_direction_kernel<<<st.B, kLbThreads, 0, s>>>(st, m, count);
+    return hipGetLastError();
+}
+hipError_t lb_mat_armijo(const LbState& st, const LbMat& m, double c1, const double* thetas, hipStream_t s) {
+    lb_mat_armijo_kernel<<<st.B, kLbThreads, 0, s>>>(st, m, c1, thetas);
+    return hipGetLastError();
+}
+hipError_t lb_mat_history(const LbState& st, const LbMat& m, int count, double ftol, int last, hipStream_t s) {
+    lb_mat_history_kernel<<<st.B, kLbThreads, 0, s>>>(st, m, count, ftol, last);
     return hipGetLastError();
 }
 

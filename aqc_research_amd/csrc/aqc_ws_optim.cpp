@@ -1,4 +1,4 @@
-// C ABI (include/aqc_hip.h): device-resident multi-start L-BFGS and the one-call surrogate evaluation.
+// C ABI (include/aqc_hip.h): device-resident multi-start L-BFGS (surrogate and matrix objectives) and the one-call surrogate evaluation.
 #include "aqc_ws.h"
 
 using namespace aqc;
@@ -131,6 +131,111 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
     if (max_no_out) HIP_OK(hipMemcpyAsync(h_max_no.data(), L.max_no, sizeof(int) * B, hipMemcpyDeviceToHost, st_));
     HIP_OK(hipStreamSynchronize(st_));
     if (max_no_out) for (int b = 0; b < B; ++b) max_no_out[b] = h_max_no[b];
+    if (nfev_out) *nfev_out = nfev;
+    return 0;
+}
+
+// ---- device-resident multi-start L-BFGS on the matrix objective of full / fixed-sketch AQC (aqc_lbfgs.hip, state-free mode) ----
+// f = 1 - Re tr(X^H V^H Y) / k per lane (sk_core.py:167-212 with a fixed X; X = I: full AQC, aqc_sketching.py:35-50).
+// Preconditions (what BatchedSketchingObjective sets up): Y = U X, X the sketching matrix (identity for full AQC).  One evaluation is
+// the chain of aqc_ws_sketch_adam without the generator: V^H Y into Z, the trace, the sweep from X, lb_mat_value.  The objective has
+// no state, so the accepted trial's f and g are final and an iteration is direction, then trial / evaluation / Armijo / history per
+// backtrack -- ordinary launches on the workspace's stream, one flag word read per trial, at most maxiter * max_backtracks of them.
+int aqc_ws_lbfgs_mat(aqc_ws* ws, const double* x0, int maxiter, int memory, double gtol, double ftol, double fobj_thr, double fidelity_thr,
+                     int max_backtracks, double* x_out, double* f_out, double* fidelity_out, int64_t* nit_out, int64_t* nfev_out,
+                     int32_t* status_out) {
+    if (!ws || !x0 || !x_out || !f_out) return fail("null argument");
+    if (memory < 1 || memory > 32) return fail("the L-BFGS memory must be in [1, 32] (got %d)", memory);
+    if (maxiter < 1 || max_backtracks < 1) return fail("maxiter and max_backtracks must be positive (got %d, %d)", maxiter, max_backtracks);
+    if (!(gtol >= 0.0) || !(ftol >= 0.0) || !(fobj_thr >= 0.0) || !(fidelity_thr >= 0.0)) return fail("tolerances and thresholds must not be negative");
+    if (ws->ctx->prog.trotter) return fail("matrix path does not support the Trotter ansatz");
+    HIP_OK(hipSetDevice(ws->device));
+    const Program& prog = ws->ctx->prog;
+    const int B = ws->batch, T = prog.num_thetas();
+    const size_t BT = (size_t)B * T;
+    hipStream_t st_ = ws->stream;
+    if (wait_result_copies(ws)) return 1;
+    // the call rewrites Z, W and ZW
+    if (before_write(ws, AQC_BUF_ZW) || before_write(ws, AQC_BUF_Z) || before_write(ws, AQC_BUF_W)) return 1;
+    HIP_OK(hipStreamSynchronize(st_));
+    // one allocation for all double arrays, one for the integers (the flag word last), one for the iteration counters
+    const size_t nd = BT * (6 + 2 * (size_t)memory) + (size_t)B * (11 + memory), ni = 3 * (size_t)B + 1;
+    DevBuf<double> dd;
+    DevBuf<int> di;
+    DevBuf<long long> dl;
+    PinBuf<int> h_flag;
+    if (dd.alloc(nd) || di.alloc(ni) || dl.alloc(B) || h_flag.alloc(1)) return 1;
+    HIP_OK(hipMemsetAsync(dd, 0, nd * sizeof(double), st_));
+    HIP_OK(hipMemsetAsync(di, 0, ni * sizeof(int), st_));
+    HIP_OK(hipMemsetAsync(dl, 0, sizeof(long long) * B, st_));
+    LbState L;
+    LbMat M;
+    memset(&L, 0, sizeof L);
+    memset(&M, 0, sizeof M);
+    double* p = dd;
+    auto take = [&](size_t n) { double* r = p; p += n; return r; };
+    L.B = B; L.T = T; L.S = 0; L.memory = memory;
+    L.x = take(BT); L.g = take(BT); L.d = take(BT); L.x_new = take(BT);
+    M.gt = take(BT); M.g_acc = take(BT);
+    L.Smem = take(BT * memory); L.Ymem = take(BT * memory);
+    L.f = take(B); L.slope = take(B); L.step = take(B); L.fidelity = take(B);
+    M.gmax = take(B); M.ft = take(B); M.gmax_t = take(B); M.fid_t = take(B);
+    M.f_acc = take(B); M.gmax_acc = take(B); M.fid_acc = take(B);
+    L.rho = take((size_t)B * memory);
+    L.active = di; L.done = di + B; M.status = di + 2 * B; M.flags = di + 3 * B;
+    L.nit = dl;
+    M.k = ws->ncols; M.gtol = gtol; M.fobj_thr = fobj_thr; M.fid_thr = fidelity_thr;
+    HIP_OK(hipMemcpyAsync(L.x, x0, sizeof(double) * BT, hipMemcpyHostToDevice, st_));
+    HIP_OK(hipMemcpyAsync(ws->d_thetas_own, L.x, sizeof(double) * BT, hipMemcpyDeviceToDevice, st_));
+    HIP_OK(hipStreamSynchronize(st_));   // x0 may go away
+    int64_t nfev = 0;
+    auto evaluate = [&](int init) -> int {   // at the point in the workspace's theta buffer
+        if (run_coef(ws, ws->d_thetas_own)) return 1;
+        if (run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)) return 1;        // V^H Y       (sk_core.py:191)
+        if (aqc_ws_vdot_launch(ws, AQC_BUF_X, AQC_BUF_Z)) return 1;     // <X|V^H Y>   (:192)
+        if (aqc_ws_grad_from(ws, AQC_BUF_X, -1, 0, 1)) return 1;        // the sweep   (:193)
+        ProfScope ps(ws, AQC_K_MISC);
+        HIP_OK(lb_mat_value(L, M, ws->d_vdot_out, ws->d_grads, init, st_));
+        ++nfev;
+        return 0;
+    };
+    auto read_flag = [&]() -> int {   // the one word the host reads per trial (and once for the start point)
+        HIP_OK(hipMemcpyAsync(h_flag, M.flags, sizeof(int), hipMemcpyDeviceToHost, st_));
+        HIP_OK(hipStreamSynchronize(st_));
+        return 0;
+    };
+    if (evaluate(1) || read_flag()) return 1;
+    bool go_on = (h_flag[0] & kLbAnyActive) != 0;
+    for (int count = 0; count < maxiter && go_on; ++count) {
+        {
+            ProfScope ps(ws, AQC_K_MISC);
+            HIP_OK(lb_mat_direction(L, M, count, st_));
+        }
+        for (int bt = 0; bt < max_backtracks; ++bt) {
+            const int last = bt + 1 == max_backtracks;
+            {
+                ProfScope ps(ws, AQC_K_MISC);
+                HIP_OK(lb_trial(L, ws->d_thetas_own, st_));
+            }
+            if (evaluate(0)) return 1;   // (lb_mat_value clears the flag word for this trial)
+            {
+                ProfScope ps(ws, AQC_K_MISC);
+                HIP_OK(lb_mat_armijo(L, M, 1e-4, ws->d_thetas_own, st_));
+                HIP_OK(lb_mat_history(L, M, count, ftol, last, st_));   // (acts once the line search is over: see the kernel)
+            }
+            if (read_flag()) return 1;
+            if (last || !(h_flag[0] & kLbNotDone)) break;
+        }
+        go_on = (h_flag[0] & kLbAnyActive) != 0;
+    }
+    std::vector<int> h_status(B, 0);
+    HIP_OK(hipMemcpyAsync(x_out, L.x, sizeof(double) * BT, hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipMemcpyAsync(f_out, L.f, sizeof(double) * B, hipMemcpyDeviceToHost, st_));
+    if (fidelity_out) HIP_OK(hipMemcpyAsync(fidelity_out, L.fidelity, sizeof(double) * B, hipMemcpyDeviceToHost, st_));
+    if (nit_out) HIP_OK(hipMemcpyAsync(nit_out, L.nit, sizeof(long long) * B, hipMemcpyDeviceToHost, st_));
+    if (status_out) HIP_OK(hipMemcpyAsync(h_status.data(), M.status, sizeof(int) * B, hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
+    if (status_out) for (int b = 0; b < B; ++b) status_out[b] = h_status[b];
     if (nfev_out) *nfev_out = nfev;
     return 0;
 }

@@ -111,7 +111,7 @@ def stochastic_aqc(circ, target: np.ndarray, skvecs_type: str, num_skvecs: int, 
     dictionary of ``SketchingObjectiveEx.optim_results`` plus ``exit_status`` ("normal" / "premature"), a list of them for
     ``(lanes, T)`` starts.  Raises RankDeficientSketch naming the lanes whose sketching matrix lost rank."""
     if skvecs_type not in ("rand", "alt", "eigen"):
-        raise ValueError(f"the device loop serves the 'rand', 'alt' and 'eigen' generators, got {skvecs_type!r} (full AQC: SketchingObjectiveEx)")
+        raise ValueError(f"the device loop serves the 'rand', 'alt' and 'eigen' generators, got {skvecs_type!r} (full AQC: full_aqc in this module)")
     if not (maxiter > 0 and 0 < learn_rate < 1 and chunk > 0):
         raise ValueError("maxiter and chunk must be positive and 0 < learn_rate < 1")
     th0 = np.array(thetas_0, dtype=np.float64)
@@ -170,4 +170,45 @@ def stochastic_aqc(circ, target: np.ndarray, skvecs_type: str, num_skvecs: int, 
                     "num_iters": p.evals_total, "thetas": (final_x[b] if normal else best_x[b]).copy(), "entangler": circ.entangler,
                     "blocks": circ.blocks.copy(), "exit_status": p.exit_status, "learn_rate": p.learn_rate, "corrections": p.corrections,
                     "stats": {"chunks": fed[b], "convergence_profile": np.concatenate(fed[b]).astype(np.float32)}})
+    return out[0] if single else out
+
+
+def full_aqc(circ, target: np.ndarray, thetas_0: np.ndarray, *, maxiter: int, device: Optional[int] = None, fobj_thr: float = 0.0):
+    """Full AQC, ``1 - Re<V(thetas), U>/d`` minimised by L-BFGS with every iteration on the device: the counterpart of ``_full_aqc``
+    (aqc_sketching.py:35-50) for one problem or a batch of lanes.  ``thetas_0``: (T,) or (lanes, T); ``target``: (d, d) shared by the
+    lanes or (lanes, d, d).  ``fobj_thr`` > 0 stops a lane once its cost is that small (the reference's SmallObjectiveStopper).
+    Returns the dictionary of ``SketchingObjectiveEx.optim_results`` plus ``exit_status``, and a list of them for ``(lanes, T)``
+    starts: the keys of ``stochastic_aqc`` without ``learn_rate``, ``corrections`` and ``stats``, which belong to ADAM and its
+    chunks (``_full_aqc`` has none of them either).  ``exit_status`` is "early" when the lane ended at a cost <= ``fobj_thr`` and
+    "normal" otherwise.  A lane stops at the first accepted point that small, whatever else holds there (gtol, ftol, the last
+    iteration), just as the reference's stopper fires on the first evaluation below its threshold before the optimiser tests
+    anything, so the final cost alone tells that the threshold ended the lane.  The optimiser is this package's L-BFGS
+    (``BatchedSketchingObjective.minimize_on_device``), not scipy's L-BFGS-B: same objective, not the same trajectory."""
+    from ..batched_optimizer import BatchedSketchingObjective
+
+    if not maxiter > 0:
+        raise ValueError("maxiter must be positive")
+    th0 = np.array(thetas_0, dtype=np.float64)
+    single = th0.ndim == 1
+    th0 = np.atleast_2d(th0)
+    if th0.ndim != 2 or th0.shape[1] != circ.num_thetas:
+        raise ValueError("thetas_0 does not match the circuit")
+    lanes = th0.shape[0]
+    tg = np.asarray(target)
+    if tg.ndim == 3 and tg.shape[0] != lanes:
+        raise ValueError("one target per lane, or one for all")
+    bo = BatchedSketchingObjective(circ, tg, lanes=lanes, device=device)
+    try:
+        res = bo.minimize_on_device(th0, maxiter=int(maxiter), fobj_thr=float(fobj_thr))
+    finally:
+        bo.close()
+    bad = np.flatnonzero(res["status"])
+    if bad.size:
+        raise FloatingPointError(f"the objective or its gradient is not finite on lanes {bad.tolist()}")
+    out = []
+    for b in range(lanes):
+        early = fobj_thr > 0 and res["fun"][b] <= fobj_thr
+        out.append({"cost": float(res["fun"][b]), "num_fun_ev": int(res["nfev"]), "num_grad_ev": int(res["nfev"]),
+                    "num_iters": int(res["nit"][b]), "thetas": res["x"][b].copy(), "entangler": circ.entangler,
+                    "blocks": circ.blocks.copy(), "exit_status": "early" if early else "normal"})
     return out[0] if single else out

@@ -388,6 +388,22 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
 int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double gtol, double ftol, double fid_thr,
                  int max_backtracks, int block_from, int block_to, int front_layer, double* x_out, double* f_out,
                  double* fidelity_out, int64_t* nit_out, int64_t* nfev_out, double* weight_out, int64_t* max_no_out);
+/* The same L-BFGS on the matrix objective of full / fixed-sketch AQC, f = 1 - Re tr(X^H V^H Y) / ncols per lane (stand-in for the
+ * L-BFGS-B run of _full_aqc, aqc_sketching.py:35-50, on SketchingObjectiveEx, sk_core.py:167-212).  Preconditions: buffer Y holds
+ * U X, buffer X the sketching matrix X (aqc_ws_set_identity for full AQC); any ncols the workspace supports (1: a state vector is
+ * a one-column matrix).  The objective has no state: an accepted trial's value and gradient are final, and the host reads one
+ * flag word per line-search trial.  A lane stops at max|g| <= gtol, at a relative decrease <= ftol, at f <= fobj_thr (the role
+ * of SmallObjectiveStopper; 0: off) or at |tr|^2 / ncols^2 >= fidelity_thr (the Hilbert-Schmidt fidelity when X = I; 0: off).
+ * memory in [1, 32].  x0 / x_out: [batch][T]; f / fidelity / nit / status: [batch]; *nfev_out: evaluations of the whole batch.
+ * status (may be NULL): 0, or 1 for a lane whose value or gradient was not finite -- it stops where it is (at x0 when the start
+ * point is the bad one) and the other lanes finish as if it were not there.  Rewrites buffers Z, W and ZW.  Refuses a Trotter
+ * ansatz, like every matrix path.  Sums run in a fixed order: a call repeated gives the same bits, and a lane of a batch gives the
+ * bits of the same problem run alone on a workspace with the same plan.  The plan does not depend on the batch below 2^8 elements
+ * per lane; above, the tile size may (aqc_ws_plan_info shows it), and AQC_TILE_BITS_APPLY / AQC_TILE_BITS_SWEEP or the tile
+ * arguments of aqc_ws_create pin it. */
+int aqc_ws_lbfgs_mat(aqc_ws* ws, const double* x0, int maxiter, int memory, double gtol, double ftol, double fobj_thr,
+                     double fidelity_thr, int max_backtracks, double* x_out, double* f_out, double* fidelity_out,
+                     int64_t* nit_out, int64_t* nfev_out, int32_t* status_out);
 
 /* ---- sketched AQC on the device: the stochastic optimisation of aqc_sketching.py:53-104 (ADAM on SketchingObjectiveEx with a fresh
  * set of `rand` / `alt` / `eigen` sketching vectors on every objective call, sk_core.py:329-464) with every iteration resident in HBM.
