@@ -61,6 +61,8 @@ SIGNATURES = {
     "aqc_ws_cd_sweep": (c_int, [_P, _D, _D]),
     "aqc_ws_cd_sweeps": (c_int, [_P, _D, _D, c_int, c_int]),
     "aqc_ws_cd_fits_one_launch": (c_int, [_P]),
+    "aqc_ws_cd_minimize": (c_int, [_P, _D, c_int, c_int, c_double, c_double, c_double, c_int, c_int, _D, _D, POINTER(c_int64), POINTER(c_int32),
+                           _D]),
     "aqc_zgemm": (c_int, [c_int, c_int, c_int, c_int, c_int, _D, c_int, _D, c_int, _D, c_int]),
     "aqc_gate_1q": (c_int, [c_int, c_int, c_int64, c_int, _D, _D, _D]),
     "aqc_gate_2q": (c_int, [c_int, c_int, c_int64, c_int, c_int, _D, _D, _D]),
@@ -172,6 +174,8 @@ def lib() -> ctypes.CDLL:
 LANES_REFUSED = 3   # AQC_LANES_REFUSED of include/aqc_hip.h
 SKETCH_KINDS = {"rand": 0, "alt": 1, "eigen": 2}   # AQC_SKETCH_*
 QR_RANK_DEFICIENT = 1   # AQC_QR_RANK_DEFICIENT
+CD_STATUS = {1: "normal", 2: "early", 3: "timeout"}   # AQC_CD_*
+CD_ROUTES = {"auto": 0, "persistent": 1, "wide": 2}     # AQC_CD_ROUTE_*
 
 
 class LanesRefused(RuntimeError):

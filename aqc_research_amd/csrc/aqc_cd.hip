@@ -6,6 +6,7 @@
 // with no host round trip in between.
 #include <hip/hip_runtime.h>
 
+#include "aqc_cd_rule.h"
 #include "aqc_lanes.h"
 #include "aqc_launch.h"
 
@@ -154,20 +155,7 @@ struct CdSeg {
     int32_t tindex[4];    // index of the parameter
 };
 
-__device__ __forceinline__ void cd_delta(int kind, double gr, double gi, double pr, double pi, double inv_d2n, double& dt_out) {
-    // grad = f * S with f = 0.5 (Y) or 0.5j (Z, X)   (core_op_matrix.py:284-389)
-    double g_re, g_im;
-    if (kind == 0) { g_re = 0.5 * gr; g_im = 0.5 * gi; } else { g_re = -0.5 * gi; g_im = 0.5 * gr; }
-    // _delta_theta (core_op_matrix.py:833-850); d^2 is a power of two: multiplying by its reciprocal IS the division
-    double d1 = (-2.0 * (pr * g_re + pi * g_im)) * inv_d2n;
-    const double d2 = (-2.0 * (g_re * g_re + g_im * g_im) + 0.5 * (pr * pr + pi * pi)) * inv_d2n;
-    const double tol = 1.4901161193847656e-08, lr = 0.19634954084936207, maxdt = 0.78539816339744831;
-    double dt;
-    if (d2 < tol) { d1 /= fmax(fabs(d1), 1.0); dt = -lr * d1; } else { dt = -d1 / d2; }
-    // |dt| <= max_delta_theta: dt / |dt / maxdt| is maxdt with the sign of dt (:849-850); NaN steps are left alone like there
-    if (fabs(dt) > maxdt) dt = copysign(maxdt, dt);
-    dt_out = dt;
-}
+// (the step rule, cd_delta, lives in aqc_cd_rule.h: the driver's close rule sits next to it and a host program tests both)
 
 // cos / sin of x for |x| <= pi / 8 (half of a step that is clamped to pi / 4): Taylor polynomials in x^2, remainders < 1e-20
 __device__ __forceinline__ void sincos_small(double x, double& s, double& c) {
@@ -253,11 +241,18 @@ __device__ __forceinline__ void cd_param(cplx (&ww)[G][4], cplx (&zz)[G][4], con
     if (sh.tid == 0) sh.th[tix] += dt;   // (read again at the start of the next sweep only)
 }
 
-template <int G>
+// RULE: the driver's stop rules (CdRule, aqc_launch.h; aqc_ws_cd_minimize) at the end of every sweep.  They are compiled in or out:
+// the instance without them is the plain "nsweeps sweeps, one objective value per sweep" of aqc_ws_cd_sweeps, the code it was before
+// the rules existed.  With them a lane that has ended is skipped, a sweep's largest step is max |theta - theta at its start| (the
+// lane's thetas in HBM are brought up to date after every sweep, so they are that start), and a lane leaves its loop when it ends.
+__device__ __forceinline__ double cd_max_nan(double a, double b) { return (b > a || b != b) ? b : a; }   // a NaN stays (np.amax)
+
+template <int G, bool RULE>
 __device__ __forceinline__ void cd_persistent_body(const CdSeg* __restrict__ prog, int nsegs, int nbits, int col_bits,
                                                    const cplx* __restrict__ target, size_t lane_stride, double* thetas, int T,
-                                                   double* fobj, int nsweeps, int max_steps) {
+                                                   double* fobj, int nsweeps, int max_steps, const CdRule& rule) {
     extern __shared__ double cd_lds[];
+    if (RULE && rule.status[blockIdx.x] != kCdRunning) return;   // a finished lane (workgroup-uniform, before any barrier)
     const int N = 1 << nbits, ngroups = N >> 2;
     cplx* w = reinterpret_cast<cplx*>(cd_lds);
     cplx* z = w + N;
@@ -369,57 +364,269 @@ __device__ __forceinline__ void cd_persistent_body(const CdSeg* __restrict__ pro
             pi += a.x * b.y - a.y * b.x;
         }
         pr = wsum(pr); pi = wsum(pi);
+        double dm = 0.0;
+        if (RULE) {
+            for (int t = tid; t < T; t += 256) dm = cd_max_nan(dm, fabs(th[t] - my_thetas[t]));
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) dm = cd_max_nan(dm, __shfl_xor(dm, o, 64));
+        }
         double* rd = sh.red + 16 * (sh.parity & 1);
         ++sh.parity;
-        if (sh.wl == 0) { rd[4 * sh.wave] = pr; rd[4 * sh.wave + 1] = pi; }
+        if (sh.wl == 0) { rd[4 * sh.wave] = pr; rd[4 * sh.wave + 1] = pi; if (RULE) rd[4 * sh.wave + 2] = dm; }
         __syncthreads();
         if (tid == 0) {
             const double a = (rd[0] + rd[4]) + (rd[8] + rd[12]), b = (rd[1] + rd[5]) + (rd[9] + rd[13]);
-            fobj[(size_t)lane * nsweeps + sweep] = 1.0 - (a * a + b * b) * sh.inv_d2n;
+            const double f = 1.0 - (a * a + b * b) * sh.inv_d2n;
+            if (!RULE) fobj[(size_t)lane * nsweeps + sweep] = f;
+            else {               // the close rule; its verdict goes to the other threads through two words of this parity's slots
+                const double dmax = cd_max_nan(cd_max_nan(rd[2], rd[6]), cd_max_nan(rd[10], rd[14]));
+                int nit = rule.nit[lane], status = kCdRunning;
+                double best = rule.best_f[lane];
+                const bool improved = cd_close(f, dmax, rule.fobj_thr, rule.dtheta_thr, rule.maxiter, rule.profile + (size_t)lane * rule.maxiter,
+                                               nit, best, status);
+                rule.nit[lane] = nit; rule.best_f[lane] = best; rule.status[lane] = status;
+                rd[2] = improved ? 1.0 : 0.0;
+                rd[3] = (double)status;
+            }
         }
         __syncthreads();
+        if (RULE) {              // (rd is written again two parameters later at the earliest: after the next sweep's barriers)
+            const bool improved = rd[2] != 0.0, done = rd[3] != 0.0;
+            for (int t = tid; t < T; t += 256) {   // (a thread reads and writes its own entries of my_thetas only)
+                my_thetas[t] = th[t];
+                if (improved) rule.best_thetas[(size_t)lane * T + t] = th[t];
+            }
+            if (done) break;
+        }
     }
     for (int t = tid; t < T; t += 256) my_thetas[t] = th[t];
 }
 
 // up to 5 qubits: one 4-element group per thread; three workgroups per CU (50 KiB of LDS each at 5 qubits and 735 parameters),
-// i.e. three waves per SIMD: the register budget is set accordingly
-__global__ __launch_bounds__(256, 3) void cd_persistent_kernel_g1(const CdSeg* __restrict__ prog, int nsegs, int nbits, int col_bits,
-                                                                  const cplx* __restrict__ target, size_t lane_stride, double* thetas, int T,
-                                                                  double* fobj, int nsweeps, int max_steps) {
-    cd_persistent_body<1>(prog, nsegs, nbits, col_bits, target, lane_stride, thetas, T, fobj, nsweeps, max_steps);
+// i.e. three waves per SIMD: the register budget is set accordingly.  6 qubits: four groups per thread, one workgroup per CU
+// (128 KiB of LDS).  Each with and without the driver's rules.
+#define AQC_CD_PERSISTENT_ARGS                                                                                                        \
+    const CdSeg* __restrict__ prog, int nsegs, int nbits, int col_bits, const cplx* __restrict__ target, size_t lane_stride, double* thetas, \
+        int T, double* fobj, int nsweeps, int max_steps, CdRule rule
+__global__ __launch_bounds__(256, 3) void cd_persistent_kernel_g1(AQC_CD_PERSISTENT_ARGS) {
+    cd_persistent_body<1, false>(prog, nsegs, nbits, col_bits, target, lane_stride, thetas, T, fobj, nsweeps, max_steps, rule);
 }
-// 6 qubits: four groups per thread, one workgroup per CU (128 KiB of LDS)
-__global__ __launch_bounds__(256) void cd_persistent_kernel_g4(const CdSeg* __restrict__ prog, int nsegs, int nbits, int col_bits,
-                                                               const cplx* __restrict__ target, size_t lane_stride, double* thetas, int T,
-                                                               double* fobj, int nsweeps, int max_steps) {
-    cd_persistent_body<4>(prog, nsegs, nbits, col_bits, target, lane_stride, thetas, T, fobj, nsweeps, max_steps);
+__global__ __launch_bounds__(256) void cd_persistent_kernel_g4(AQC_CD_PERSISTENT_ARGS) {
+    cd_persistent_body<4, false>(prog, nsegs, nbits, col_bits, target, lane_stride, thetas, T, fobj, nsweeps, max_steps, rule);
 }
+__global__ __launch_bounds__(256, 3) void cd_persistent_rule_kernel_g1(AQC_CD_PERSISTENT_ARGS) {
+    cd_persistent_body<1, true>(prog, nsegs, nbits, col_bits, target, lane_stride, thetas, T, fobj, nsweeps, max_steps, rule);
+}
+__global__ __launch_bounds__(256) void cd_persistent_rule_kernel_g4(AQC_CD_PERSISTENT_ARGS) {
+    cd_persistent_body<4, true>(prog, nsegs, nbits, col_bits, target, lane_stride, thetas, T, fobj, nsweeps, max_steps, rule);
+}
+#undef AQC_CD_PERSISTENT_ARGS
 
 size_t cd_persistent_lds_bytes(int nbits, int T) {
     return ((size_t)2 << nbits) * sizeof(cplx) + (size_t)((T + 1) & ~1) * sizeof(double) + (size_t)T * sizeof(double2) + 32 * sizeof(double);
 }
 
 hipError_t launch_cd_persistent(const void* prog, int nsegs, int nbits, int col_bits, const void* target, size_t lane_stride, double* thetas,
-                                int T, double* fobj, int nsweeps, int max_steps, int batch, hipStream_t s) {
+                                int T, double* fobj, int nsweeps, int max_steps, int batch, hipStream_t s, const CdRule* rule_in) {
+    const CdRule rule = rule_in ? *rule_in : CdRule{};
     const size_t lds = cd_persistent_lds_bytes(nbits, T);
     const bool big = ((size_t)1 << nbits) / 4 > 256;    // more than one 4-element group per thread (6 qubits: 4)
-    static size_t granted_all[64][2] = {};   // hipFuncSetAttribute applies to the current device: one record per device
+    typedef void (*Kernel)(const CdSeg*, int, int, int, const cplx*, size_t, double*, int, double*, int, int, CdRule);
+    static const Kernel kernels[4] = {cd_persistent_kernel_g1, cd_persistent_kernel_g4, cd_persistent_rule_kernel_g1, cd_persistent_rule_kernel_g4};
+    const int which = (big ? 1 : 0) + (rule_in ? 2 : 0);
+    static size_t granted_all[64][4] = {};   // hipFuncSetAttribute applies to the current device: one record per device
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    size_t (&granted)[2] = granted_all[dev];
-    if (lds > granted[big] || dev == 0) {   // (device 0 doubles as the catch-all slot: always set there -- the call is cheap)
-        hipError_t e = big ? hipFuncSetAttribute(reinterpret_cast<const void*>(cd_persistent_kernel_g4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                           : hipFuncSetAttribute(reinterpret_cast<const void*>(cd_persistent_kernel_g1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    size_t (&granted)[4] = granted_all[dev];
+    if (lds > granted[which] || dev == 0) {   // (device 0 doubles as the catch-all slot: always set there -- the call is cheap)
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[which]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        granted[big] = lds;
+        granted[which] = lds;
     }
-    if (big)
-        cd_persistent_kernel_g4<<<batch, 256, lds, s>>>(static_cast<const CdSeg*>(prog), nsegs, nbits, col_bits, static_cast<const cplx*>(target),
-                                                        lane_stride, thetas, T, fobj, nsweeps, max_steps);
-    else
-        cd_persistent_kernel_g1<<<batch, 256, lds, s>>>(static_cast<const CdSeg*>(prog), nsegs, nbits, col_bits, static_cast<const cplx*>(target),
-                                                        lane_stride, thetas, T, fobj, nsweeps, max_steps);
+    kernels[which]<<<batch, 256, lds, s>>>(static_cast<const CdSeg*>(prog), nsegs, nbits, col_bits, static_cast<const cplx*>(target), lane_stride, thetas,
+                                           T, fobj, nsweeps, max_steps, rule);
+    return hipGetLastError();
+}
+
+// ---- the walk for operands that do not fit LDS: plain launches, grid (nparts, lanes) ----------------------------------------------
+// Beyond 6 qubits w and z live in HBM.  The walk keeps the persistent kernel's segments: a thread takes the 4-element groups of w and
+// of z on the segment's two address bits into registers, and
+//   the OPENER (one launch per segment) applies the entangler as the same register permutation, writes the elements it moved and
+//     leaves the partial sums (grad, prod) of the segment's first parameter, one set of four doubles per workgroup;
+//   a STEP (one launch per parameter) has every workgroup add the lane's nparts partial sets in one fixed order (thread t takes sets
+//     t, t + 256, ... in index order, then the wave and workgroup sums of cd_param), derive the step with cd_delta, rotate z by the old
+//     angle and w by the new one, and -- unless the parameter closes the segment -- form the next parameter's partials from the same
+//     registers: one read and one write of w and z per parameter where the dot / update chain reads them twice.
+// Workgroup 0 of a lane stores the new theta and folds |theta_new - theta_old| into the lane's running maximum.  The old angle is read
+// from theta_in, which no launch of the walk writes (the close kernel copies theta_out over it when the sweep ends), and the partial
+// sets alternate between two buffers by the parity of the parameter: inside one launch some workgroups still read set p while others
+// already write set p + 1.  nparts depends on the lane's size alone, never on the batch, and no sum is atomic: a lane of a batch goes
+// through the same arithmetic as the same problem alone.  A lane whose status is not kCdRunning is skipped by every launch.
+int cd_wide_parts(size_t lane_elems) { return (int)std::min<size_t>(512, std::max<size_t>(1, ((lane_elems >> 2) + 255) / 256)); }
+
+template <int KIND, bool ON_B>
+__device__ __forceinline__ void cd_group_sums(const cplx (&ww)[4], const cplx (&zz)[4], double& gr, double& gi, double& pr, double& pi) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int i0 = ON_B ? p : 2 * p, i1 = ON_B ? p + 2 : 2 * p + 1;
+        const cplx w0 = ww[i0], w1 = ww[i1], z0 = zz[i0], z1 = zz[i1];
+        const double c00r = w0.x * z0.x + w0.y * z0.y, c00i = w0.x * z0.y - w0.y * z0.x;
+        const double c11r = w1.x * z1.x + w1.y * z1.y, c11i = w1.x * z1.y - w1.y * z1.x;
+        pr += c00r + c11r;
+        pi += c00i + c11i;
+        if (KIND == 1) {
+            gr += c00r - c11r;
+            gi += c00i - c11i;
+        } else {
+            const double c01r = w0.x * z1.x + w0.y * z1.y, c01i = w0.x * z1.y - w0.y * z1.x;
+            const double c10r = w1.x * z0.x + w1.y * z0.y, c10i = w1.x * z0.y - w1.y * z0.x;
+            if (KIND == 0) { gr += c01r - c10r; gi += c01i - c10i; } else { gr += c01r + c10r; gi += c01i + c10i; }
+        }
+    }
+}
+// (kind, on_b) are launch arguments: uniform branches to the five combinations a segment has
+__device__ __forceinline__ void cd_group_sums_rt(int kind, int on_b, const cplx (&ww)[4], const cplx (&zz)[4], double& gr, double& gi,
+                                                 double& pr, double& pi) {
+    if (!on_b) { if (kind == 0) cd_group_sums<0, false>(ww, zz, gr, gi, pr, pi); else cd_group_sums<1, false>(ww, zz, gr, gi, pr, pi); }
+    else if (kind == 0) cd_group_sums<0, true>(ww, zz, gr, gi, pr, pi);
+    else if (kind == 1) cd_group_sums<1, true>(ww, zz, gr, gi, pr, pi);
+    else cd_group_sums<2, true>(ww, zz, gr, gi, pr, pi);
+}
+__device__ __forceinline__ void cd_group_rot_rt(int kind, int on_b, cplx (&e)[4], double c, double s) {
+    if (on_b) { rot_pair(kind, e[0], e[2], c, s); rot_pair(kind, e[1], e[3], c, s); }
+    else      { rot_pair(kind, e[0], e[1], c, s); rot_pair(kind, e[2], e[3], c, s); }
+}
+// the workgroup's four sums -> out[0 gr, 1 pr, 2 gi, 3 pi]; red: 16 doubles of LDS.  Reached by all 256 threads.
+__device__ __forceinline__ void cd_wide_put(double gr, double gi, double pr, double pi, double* red, double* out) {
+    const int tid = threadIdx.x, wl = tid & 63;
+    const double v = wave_sum4(gr, gi, pr, pi, wl);
+    if (wl < 4) red[4 * (tid >> 6) + wl] = v;
+    __syncthreads();
+    if (tid < 4) out[tid] = (red[tid] + red[4 + tid]) + (red[8 + tid] + red[12 + tid]);
+}
+
+__global__ __launch_bounds__(256) void cd_wide_open_kernel(CdWide a) {
+    __shared__ double red[16];
+    const int lane = blockIdx.y;
+    if (a.status[lane] != kCdRunning) return;   // (workgroup-uniform, before the barrier)
+    cplx* w = static_cast<cplx*>(a.w) + (size_t)lane * a.lane_stride;
+    cplx* z = static_cast<cplx*>(a.z) + (size_t)lane * a.lane_stride;
+    const int lo = min(a.ha, a.hb), hi = max(a.ha, a.hb);
+    const size_t ia = (size_t)1 << a.ha, ib = (size_t)1 << a.hb;
+    double gr = 0, gi = 0, pr = 0, pi = 0;
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < (size_t)a.ngroups; g += (size_t)a.nparts * 256) {
+        const size_t base = pair_index(pair_index(g, lo), hi);
+        cplx ww[4] = {w[base], w[base + ia], w[base + ib], w[base + ia + ib]};
+        cplx zz[4] = {z[base], z[base + ia], z[base + ib], z[base + ia + ib]};
+        if (a.ent == 1) {          // CX: the control's 1-half swaps along the target
+            cplx t = zz[1]; zz[1] = zz[3]; zz[3] = t;
+            t = ww[1]; ww[1] = ww[3]; ww[3] = t;
+            w[base + ia] = ww[1]; w[base + ia + ib] = ww[3];
+            z[base + ia] = zz[1]; z[base + ia + ib] = zz[3];
+        } else if (a.ent == 2) {   // CZ
+            zz[3] = make_double2(-zz[3].x, -zz[3].y);
+            ww[3] = make_double2(-ww[3].x, -ww[3].y);
+            w[base + ia + ib] = ww[3];
+            z[base + ia + ib] = zz[3];
+        }
+        cd_group_sums_rt(a.next_kind, a.next_on_b, ww, zz, gr, gi, pr, pi);
+    }
+    cd_wide_put(gr, gi, pr, pi, red, a.part_out + 4 * ((size_t)lane * a.nparts + blockIdx.x));
+}
+
+__global__ __launch_bounds__(256) void cd_wide_step_kernel(CdWide a) {
+    __shared__ double red_in[16], red_out[16];
+    const int lane = blockIdx.y, tid = threadIdx.x, wl = tid & 63;
+    if (a.status[lane] != kCdRunning) return;   // (workgroup-uniform, before any barrier)
+    double gr = 0, gi = 0, pr = 0, pi = 0;
+    const double* part = a.part_in + 4 * (size_t)lane * a.nparts;
+    for (int i = tid; i < a.nparts; i += 256) { gr += part[4 * i]; pr += part[4 * i + 1]; gi += part[4 * i + 2]; pi += part[4 * i + 3]; }
+    const double v = wave_sum4(gr, gi, pr, pi, wl);
+    if (wl < 4) red_in[4 * (tid >> 6) + wl] = v;
+    __syncthreads();
+    gr = (red_in[0] + red_in[4]) + (red_in[8] + red_in[12]);
+    pr = (red_in[1] + red_in[5]) + (red_in[9] + red_in[13]);
+    gi = (red_in[2] + red_in[6]) + (red_in[10] + red_in[14]);
+    pi = (red_in[3] + red_in[7]) + (red_in[11] + red_in[15]);
+    double dt;
+    cd_delta(a.kind, gr, gi, pr, pi, a.inv_d2n, dt);   // every thread of every workgroup: the same numbers in the same order
+    const double t_old = a.theta_in[(size_t)lane * a.T + a.tindex], t_new = t_old + dt;
+    double so, co, sn, cn;
+    sincos(0.5 * t_old, &so, &co);
+    sincos(0.5 * t_new, &sn, &cn);
+    if (blockIdx.x == 0 && tid == 0) {
+        a.theta_out[(size_t)lane * a.T + a.tindex] = t_new;
+        a.dmax[lane] = cd_max_nan(a.dmax[lane], fabs(t_new - t_old));   // (launches of one stream: nobody else touches the word)
+    }
+    cplx* w = static_cast<cplx*>(a.w) + (size_t)lane * a.lane_stride;
+    cplx* z = static_cast<cplx*>(a.z) + (size_t)lane * a.lane_stride;
+    const int lo = min(a.ha, a.hb), hi = max(a.ha, a.hb);
+    const size_t ia = (size_t)1 << a.ha, ib = (size_t)1 << a.hb;
+    gr = gi = pr = pi = 0;
+    for (size_t g = (size_t)blockIdx.x * 256 + tid; g < (size_t)a.ngroups; g += (size_t)a.nparts * 256) {
+        const size_t base = pair_index(pair_index(g, lo), hi);
+        cplx ww[4] = {w[base], w[base + ia], w[base + ib], w[base + ia + ib]};
+        cplx zz[4] = {z[base], z[base + ia], z[base + ib], z[base + ia + ib]};
+        cd_group_rot_rt(a.kind, a.on_b, zz, co, so);   // z <- R(theta_old) z
+        cd_group_rot_rt(a.kind, a.on_b, ww, cn, sn);   // w <- R(theta_new) w
+        if (a.next_kind >= 0) cd_group_sums_rt(a.next_kind, a.next_on_b, ww, zz, gr, gi, pr, pi);
+        w[base] = ww[0]; w[base + ia] = ww[1]; w[base + ib] = ww[2]; w[base + ia + ib] = ww[3];
+        z[base] = zz[0]; z[base + ia] = zz[1]; z[base + ib] = zz[2]; z[base + ia + ib] = zz[3];
+    }
+    if (a.next_kind >= 0) cd_wide_put(gr, gi, pr, pi, red_out, a.part_out + 4 * ((size_t)lane * a.nparts + blockIdx.x));
+}
+
+// The end of a sweep on the wide route, one small workgroup per lane: fobj = 1 - |<w|z>|^2 / d^2 from the vdot launch's result, the
+// close rule (aqc_cd_rule.h), the sweep's thetas copied over the ones the next V^H reads -- and over the best ones when they are.
+__global__ __launch_bounds__(64) void cd_close_kernel(CdClose a) {
+    __shared__ int improved_s;
+    const int lane = blockIdx.x, tid = threadIdx.x;
+    if (a.rule.status[lane] != kCdRunning) return;
+    if (tid == 0) {
+        const double2 tr = a.trace[lane];
+        int nit = a.rule.nit[lane], status = kCdRunning;
+        double best = a.rule.best_f[lane];
+        improved_s = cd_close(1.0 - (tr.x * tr.x + tr.y * tr.y) * a.inv_d2n, a.dmax[lane], a.rule.fobj_thr, a.rule.dtheta_thr, a.rule.maxiter,
+                              a.rule.profile + (size_t)lane * a.rule.maxiter, nit, best, status) ? 1 : 0;
+        a.rule.nit[lane] = nit; a.rule.best_f[lane] = best; a.rule.status[lane] = status;
+        a.dmax[lane] = 0.0;
+    }
+    __syncthreads();
+    const bool improved = improved_s != 0;
+    for (int t = tid; t < a.T; t += 64) {
+        const double c = a.theta_cur[(size_t)lane * a.T + t];
+        a.theta_own[(size_t)lane * a.T + t] = c;
+        if (improved) a.rule.best_thetas[(size_t)lane * a.T + t] = c;
+    }
+}
+
+// lanes still running -> one int word, what the host reads between chunks; mark != 0: the time limit has passed, they become that first
+__global__ __launch_bounds__(256) void cd_count_kernel(int* status, int batch, int mark, int* running) {
+    __shared__ int cnt[4];
+    int c = 0;
+    for (int b = threadIdx.x; b < batch; b += 256)
+        if (status[b] == kCdRunning) { if (mark) status[b] = mark; else ++c; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) *running = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+}
+
+hipError_t launch_cd_wide_open(const CdWide& a, int batch, hipStream_t s) {
+    cd_wide_open_kernel<<<dim3(a.nparts, batch), 256, 0, s>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_cd_wide_step(const CdWide& a, int batch, hipStream_t s) {
+    cd_wide_step_kernel<<<dim3(a.nparts, batch), 256, 0, s>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_cd_close(const CdClose& a, int batch, hipStream_t s) {
+    cd_close_kernel<<<batch, 64, 0, s>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_cd_count(int* status, int batch, int mark, int* running, hipStream_t s) {
+    cd_count_kernel<<<1, 256, 0, s>>>(status, batch, mark, running);
     return hipGetLastError();
 }
 

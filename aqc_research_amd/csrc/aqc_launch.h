@@ -261,8 +261,52 @@ hipError_t launch_cd_entangle(void* w, void* z, size_t ngroups, int cbit, int tb
 // the whole walk as one persistent launch (a workgroup per lane, operands in LDS): segment list entry = CdSeg of aqc_cd.hip
 struct CdSegHost { int32_t ha, hb, ent, nrot, kind[4], on_b[4], tindex[4]; };
 size_t cd_persistent_lds_bytes(int nbits, int T);
+// The driver's state of every lane (aqc_ws_cd_minimize), as both routes see it; the rules themselves: aqc_cd_rule.h
+struct CdRule {
+    int* status;           // [batch] kCdRunning / kCdNormal / kCdEarly / kCdTimeout
+    int* nit;              // [batch] sweeps closed so far
+    double* best_f;        // [batch]
+    double* best_thetas;   // [batch][T]
+    double* profile;       // [batch][maxiter]
+    double fobj_thr, dtheta_thr;
+    int maxiter;
+};
+// rule: null for the plain sweeps of aqc_ws_cd_sweeps (fobj[batch][nsweeps] is written: the kernel instance without the rules); with a
+// rule the lanes that still run do up to nsweeps more sweeps, a lane leaves its loop when the rule ends it, and fobj is not used
 hipError_t launch_cd_persistent(const void* prog, int nsegs, int nbits, int col_bits, const void* target, size_t lane_stride, double* thetas,
-                                int T, double* fobj, int nsweeps, int max_steps, int batch, hipStream_t s);
+                                int T, double* fobj, int nsweeps, int max_steps, int batch, hipStream_t s, const CdRule* rule = nullptr);
+// the walk with the operands in HBM (beyond 6 qubits), grid (nparts, batch): one opener per segment, one step per parameter
+struct CdWide {
+    void* w; void* z;              // [batch][lane_stride] complex
+    size_t lane_stride;
+    int ngroups, nparts;           // 4-element groups of a lane; workgroups (= partial sets) per lane, cd_wide_parts(lane_elems)
+    int ha, hb, ent;               // the segment: address bits of its two qubits, 0 none / 1 CX / 2 CZ (opener)
+    int kind, on_b, tindex;        // the step's parameter: 0 Ry / 1 Rz / 2 Rx, on bit a or b, its index
+    int next_kind, next_on_b;      // the parameter whose partial sums the launch leaves (next_kind < 0: none, it closed the segment)
+    int T;
+    const double* theta_in;        // [batch][T] thetas at the start of the sweep: the old angles
+    double* theta_out;             // [batch][T] the sweep's thetas
+    double* dmax;                  // [batch] running max |theta_new - theta_old| of the sweep
+    const int* status;             // [batch]
+    const double* part_in;         // [batch][nparts][4] partial sums of this parameter ...
+    double* part_out;              // ... and of the next one (the other buffer of the pair)
+    double inv_d2n;
+};
+int cd_wide_parts(size_t lane_elems);
+hipError_t launch_cd_wide_open(const CdWide& a, int batch, hipStream_t s);
+hipError_t launch_cd_wide_step(const CdWide& a, int batch, hipStream_t s);
+struct CdClose {
+    CdRule rule;
+    const double2* trace;          // [batch] <w|z> of the vdot launch
+    double* dmax;                  // [batch], cleared for the next sweep
+    double* theta_own;             // [batch][T] <- theta_cur: what the next sweep's V^H and old angles read
+    const double* theta_cur;
+    int T;
+    double inv_d2n;
+};
+hipError_t launch_cd_close(const CdClose& a, int batch, hipStream_t s);
+// running <- lanes whose status is kCdRunning; mark != 0: those lanes get that status first (the time limit) and running <- 0
+hipError_t launch_cd_count(int* status, int batch, int mark, int* running, hipStream_t s);
 
 
 // aqc_gate.hip (gate-level building blocks, one pass per call)

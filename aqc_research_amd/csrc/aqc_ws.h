@@ -232,6 +232,13 @@ struct aqc_ws {
     int cd_nsteps = 0;
     DevBuf<double> d_cd_thetas;
     DevBuf<double> d_cd_fobj;           // (grow-only)
+    // the driver (aqc_ws_cd_minimize): best thetas [batch][T], best_f | dmax [batch] each, status | nit [batch] each and the running-lanes
+    // word, the profile [batch][maxiter] (grow-only), the wide walk's two sets of partial sums [2][batch][nparts][4] (grow-only)
+    DevBuf<double> d_cd_best;
+    DevBuf<double> d_cd_real;
+    DevBuf<int> d_cd_int;
+    DevBuf<double> d_cd_profile;
+    DevBuf<double> d_cd_part;
     MpsTabs mps_tabs[32];   // resident pointer-table sets (one per distinct chain: operands x lanes x bond dimensions)
     unsigned long long mps_tabs_tick = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, pev0 = nullptr, pev1 = nullptr;

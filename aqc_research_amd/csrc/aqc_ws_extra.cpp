@@ -1,7 +1,13 @@
 // C ABI (include/aqc_hip.h): dense zgemm, gate-level building blocks, coordinate descent, MPS helpers.
 #include "aqc_ws.h"
 
+#include <chrono>
+
+#include "aqc_cd_rule.h"
+
 using namespace aqc;
+
+static double wall_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 extern "C" {
 
@@ -107,6 +113,36 @@ static int cd_checks(const aqc_ws* ws) {
     return 0;
 }
 
+// the walk of core_op_matrix.py:852-912 cut into segments (address bits of this workspace): the persistent kernel reads the list on
+// the device, the wide walk issues its launches from the host copy
+static std::vector<aqc::CdSegHost> cd_segments(const aqc_ws* ws) {
+    const Program& prog = ws->ctx->prog;
+    std::vector<aqc::CdSegHost> segs;
+    for (const GateGroup& g : prog.groups) {
+        aqc::CdSegHost sg{};
+        if (g.type == GROUP_FRONT) {   // Rz(t2), Ry(t1), Rz(t0) on one qubit; the second bit of the 4-element groups: any other qubit
+            sg.ha = ws->col_bits + g.q0; sg.hb = ws->col_bits + (g.q0 + 1) % prog.n; sg.ent = 0; sg.nrot = 3;
+            const int kinds[3] = {1, 0, 1}, tix[3] = {g.theta0 + 2, g.theta0 + 1, g.theta0};
+            for (int r = 0; r < 3; ++r) { sg.kind[r] = kinds[r]; sg.on_b[r] = 0; sg.tindex[r] = tix[r]; }
+        } else {                       // entangler, Ry(t0) Rz(t1) on the control, Ry(t2) Rs(t3) on the target
+            sg.ha = ws->col_bits + g.q0; sg.hb = ws->col_bits + g.q1; sg.ent = prog.entangler == AQC_CX ? 1 : 2; sg.nrot = 4;
+            const int kinds[4] = {0, 1, 0, prog.entangler == AQC_CX ? 2 : 1};
+            for (int r = 0; r < 4; ++r) { sg.kind[r] = kinds[r]; sg.on_b[r] = r >= 2; sg.tindex[r] = g.theta0 + r; }
+        }
+        segs.push_back(sg);
+    }
+    return segs;
+}
+
+// ... on the device, with the thetas [batch][T] the persistent kernel and the driver keep there
+static int cd_ensure_prog(aqc_ws* ws) {
+    if (ws->d_cd_prog) return 0;
+    const std::vector<aqc::CdSegHost> segs = cd_segments(ws);
+    if (ws->d_cd_prog.upload(segs, 0)) return 1;
+    ws->cd_nsteps = (int)segs.size();
+    return ws->d_cd_thetas.reserve((size_t)ws->batch * ws->ctx->prog.num_thetas());
+}
+
 int aqc_ws_cd_fits_one_launch(const aqc_ws* ws) {
     if (!ws) return 0;
     return aqc::cd_persistent_lds_bytes(ws->nbits, ws->ctx->prog.num_thetas()) <= (size_t)160 * 1024 ? 1 : 0;
@@ -122,25 +158,7 @@ int aqc_ws_cd_sweeps(aqc_ws* ws, double* thetas_io, double* fobj, int nsweeps, i
     const Program& prog = ws->ctx->prog;
     const int T = prog.num_thetas();
     HIP_OK(hipSetDevice(ws->device));
-    if (!ws->d_cd_prog) {   // the walk of core_op_matrix.py:852-912 cut into segments (address bits of this workspace)
-        std::vector<aqc::CdSegHost> segs;
-        for (const GateGroup& g : prog.groups) {
-            aqc::CdSegHost sg{};
-            if (g.type == GROUP_FRONT) {   // Rz(t2), Ry(t1), Rz(t0) on one qubit; the second bit of the 4-element groups: any other qubit
-                sg.ha = ws->col_bits + g.q0; sg.hb = ws->col_bits + (g.q0 + 1) % prog.n; sg.ent = 0; sg.nrot = 3;
-                const int kinds[3] = {1, 0, 1}, tix[3] = {g.theta0 + 2, g.theta0 + 1, g.theta0};
-                for (int r = 0; r < 3; ++r) { sg.kind[r] = kinds[r]; sg.on_b[r] = 0; sg.tindex[r] = tix[r]; }
-            } else {                       // entangler, Ry(t0) Rz(t1) on the control, Ry(t2) Rs(t3) on the target
-                sg.ha = ws->col_bits + g.q0; sg.hb = ws->col_bits + g.q1; sg.ent = prog.entangler == AQC_CX ? 1 : 2; sg.nrot = 4;
-                const int kinds[4] = {0, 1, 0, prog.entangler == AQC_CX ? 2 : 1};
-                for (int r = 0; r < 4; ++r) { sg.kind[r] = kinds[r]; sg.on_b[r] = r >= 2; sg.tindex[r] = g.theta0 + r; }
-            }
-            segs.push_back(sg);
-        }
-        if (ws->d_cd_prog.upload(segs, 0)) return 1;
-        ws->cd_nsteps = (int)segs.size();
-        if (ws->d_cd_thetas.reserve((size_t)ws->batch * T)) return 1;
-    }
+    if (cd_ensure_prog(ws)) return 1;
     const size_t nf = (size_t)ws->batch * nsweeps;
     if (ws->d_cd_fobj.reserve(nf)) return 1;
     HIP_OK(hipMemcpyAsync(ws->d_cd_thetas, thetas_io, sizeof(double) * (size_t)ws->batch * T, hipMemcpyHostToDevice, ws->stream));
@@ -210,6 +228,132 @@ int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io, double* fobj) {
     }
     (void)hipStreamSynchronize(ws->stream);
     return rc;
+}
+
+// One sweep of the wide walk for all lanes, enqueued: z = V(theta)^H U and w = I by the workspace's own launches, the walk's
+// T + (n + L) launches, <w|z>, the close kernel.  d_thetas_own holds the thetas at the start of the sweep (the close kernel of the
+// previous one wrote them: run_coef announces that, as aqc_ws_sketch_adam does for its ADAM step), d_cd_thetas the sweep's.
+static int cd_wide_sweep(aqc_ws* ws, const std::vector<aqc::CdSegHost>& segs, const aqc::CdRule& rule, int max_steps) {
+    const int B = ws->batch, T = ws->ctx->prog.num_thetas(), dim = 1 << ws->ctx->prog.n;
+    if (run_coef(ws, ws->d_thetas_own)) return 1;
+    if (run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z)) return 1;                     // z = V^H U   (core_op_matrix.py:806-810)
+    if (aqc_ws_set_identity(ws, AQC_BUF_X)) return 1;                            // w = I
+    if (before_write(ws, AQC_BUF_X) || before_write(ws, AQC_BUF_Z)) return 1;    // the walk rewrites both in place
+    aqc::CdWide a;
+    memset(&a, 0, sizeof a);
+    a.w = ws->bufs[AQC_BUF_X]; a.z = ws->bufs[AQC_BUF_Z];
+    a.lane_stride = ws->lane_elems;
+    a.ngroups = (int)(ws->lane_elems >> 2);
+    a.nparts = aqc::cd_wide_parts(ws->lane_elems);
+    a.T = T;
+    a.theta_in = ws->d_thetas_own; a.theta_out = ws->d_cd_thetas;
+    a.dmax = ws->d_cd_real + B;
+    a.status = rule.status;
+    a.inv_d2n = 1.0 / ((double)dim * dim);
+    double* const part[2] = {ws->d_cd_part, ws->d_cd_part + 4 * (size_t)B * a.nparts};
+    int step = 0;                                                                // parameters walked so far: its parity picks the partial set
+    const int limit = max_steps >= 0 ? max_steps : 0x7fffffff;
+    for (const aqc::CdSegHost& sg : segs) {
+        if (step >= limit) break;
+        a.ha = sg.ha; a.hb = sg.hb; a.ent = sg.ent;
+        a.next_kind = sg.kind[0]; a.next_on_b = sg.on_b[0];
+        a.part_in = nullptr; a.part_out = part[step & 1];
+        {
+            ProfScope ps(ws, AQC_K_MISC);
+            HIP_OK(aqc::launch_cd_wide_open(a, B, ws->stream));
+        }
+        for (int r = 0; r < sg.nrot && step < limit; ++r, ++step) {
+            const bool last = r + 1 == sg.nrot || step + 1 >= limit;             // nothing reads the partials of a parameter that is not walked
+            a.kind = sg.kind[r]; a.on_b = sg.on_b[r]; a.tindex = sg.tindex[r];
+            a.next_kind = last ? -1 : sg.kind[r + 1]; a.next_on_b = last ? 0 : sg.on_b[r + 1];
+            a.part_in = part[step & 1]; a.part_out = part[(step + 1) & 1];
+            ProfScope ps(ws, AQC_K_MISC);
+            HIP_OK(aqc::launch_cd_wide_step(a, B, ws->stream));
+        }
+    }
+    if (aqc_ws_vdot_launch(ws, AQC_BUF_X, AQC_BUF_Z)) return 1;                  // <w|z>   (:917)
+    aqc::CdClose c;
+    memset(&c, 0, sizeof c);
+    c.rule = rule;
+    c.trace = ws->d_vdot_out;
+    c.dmax = a.dmax;
+    c.theta_own = ws->d_thetas_own; c.theta_cur = ws->d_cd_thetas;
+    c.T = T;
+    c.inv_d2n = a.inv_d2n;
+    ProfScope ps(ws, AQC_K_MISC);
+    HIP_OK(aqc::launch_cd_close(c, B, ws->stream));
+    return 0;
+}
+
+int aqc_ws_cd_minimize(aqc_ws* ws, const double* thetas0, int maxiter, int chunk, double dtheta_thr, double fobj_thr, double time_limit_s,
+                       int route, int max_steps, double* best_thetas, double* best_f, int64_t* nit, int32_t* status, double* profile) {
+    static_assert(AQC_CD_RUNNING == aqc::kCdRunning && AQC_CD_NORMAL == aqc::kCdNormal && AQC_CD_EARLY == aqc::kCdEarly &&
+                  AQC_CD_TIMEOUT == aqc::kCdTimeout, "the status words of the header and of the rule");
+    if (!ws || !thetas0 || !best_thetas || !best_f || !nit || !status || !profile) return fail("null argument");
+    if (maxiter < 1 || chunk < 1) return fail("maxiter and chunk must be positive");
+    if (route < AQC_CD_ROUTE_AUTO || route > AQC_CD_ROUTE_WIDE) return fail("unknown coordinate-descent route %d", route);
+    if (cd_checks(ws)) return 1;
+    const Program& prog = ws->ctx->prog;
+    if (prog.n < 2 || ws->nbits > 30) return fail("coordinate descent serves 2 to 15 qubits");
+    const bool fits = aqc_ws_cd_fits_one_launch(ws) != 0;
+    if (route == AQC_CD_ROUTE_PERSISTENT && !fits)
+        return fail("the operands of this coordinate descent (2 x %zu KiB) do not fit one workgroup's LDS: the persistent route is not available",
+                    (ws->lane_elems * sizeof(double2)) >> 10);
+    const bool persistent = route == AQC_CD_ROUTE_PERSISTENT || (route == AQC_CD_ROUTE_AUTO && fits);
+    const int B = ws->batch, T = prog.num_thetas();
+    const size_t BT = (size_t)B * T;
+    HIP_OK(hipSetDevice(ws->device));
+    hipStream_t st = ws->stream;
+    if (cd_ensure_prog(ws)) return 1;
+    const int nparts = aqc::cd_wide_parts(ws->lane_elems);
+    HIP_OK(hipStreamSynchronize(st));   // a buffer that grows lets its old block go
+    if (ws->d_cd_best.reserve(BT) || ws->d_cd_real.reserve(2 * (size_t)B) || ws->d_cd_int.reserve(2 * (size_t)B + 1) ||
+        ws->d_cd_profile.reserve((size_t)B * maxiter) || (!persistent && ws->d_cd_part.reserve(8 * (size_t)B * nparts))) return 1;
+    aqc::CdRule rule;
+    rule.status = ws->d_cd_int; rule.nit = rule.status + B;
+    int* d_running = rule.nit + B;
+    rule.best_f = ws->d_cd_real; rule.best_thetas = ws->d_cd_best; rule.profile = ws->d_cd_profile;
+    rule.fobj_thr = fobj_thr; rule.dtheta_thr = dtheta_thr; rule.maxiter = maxiter;
+    std::vector<double> real0(2 * (size_t)B, 0.0);   // best_f = inf | dmax = 0
+    for (int b = 0; b < B; ++b) real0[b] = HUGE_VAL;
+    HIP_OK(hipMemcpyAsync(ws->d_cd_real, real0.data(), sizeof(double) * 2 * B, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(ws->d_cd_int, 0, sizeof(int) * (2 * (size_t)B + 1), st));
+    HIP_OK(hipMemsetAsync(ws->d_cd_profile, 0, sizeof(double) * (size_t)B * maxiter, st));
+    HIP_OK(hipMemcpyAsync(ws->d_cd_thetas, thetas0, sizeof(double) * BT, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(ws->d_cd_best, thetas0, sizeof(double) * BT, hipMemcpyHostToDevice, st));
+    if (!persistent) HIP_OK(hipMemcpyAsync(ws->d_thetas_own, thetas0, sizeof(double) * BT, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st));   // thetas0 and real0 may go away
+    const std::vector<aqc::CdSegHost> segs = persistent ? std::vector<aqc::CdSegHost>() : cd_segments(ws);
+    const double t0 = wall_seconds();
+    for (int done = 0; done < maxiter;) {
+        const int n = std::min(chunk, maxiter - done);
+        if (persistent) {
+            ProfScope ps(ws, AQC_K_MISC);
+            HIP_OK(aqc::launch_cd_persistent(ws->d_cd_prog, ws->cd_nsteps, ws->nbits, ws->col_bits, ws->bufs[AQC_BUF_Y], ws->lane_elems, ws->d_cd_thetas,
+                                             T, nullptr, n, max_steps, B, st, &rule));
+        } else {
+            for (int i = 0; i < n; ++i)
+                if (cd_wide_sweep(ws, segs, rule, max_steps)) return 1;
+        }
+        done += n;
+        int running = 0;
+        HIP_OK(aqc::launch_cd_count(rule.status, B, 0, d_running, st));
+        HIP_OK(hipMemcpyAsync(&running, d_running, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (running == 0) break;
+        if (time_limit_s > 0 && wall_seconds() - t0 >= time_limit_s) {   // the reference's TimeoutStopper, between chunks
+            HIP_OK(aqc::launch_cd_count(rule.status, B, AQC_CD_TIMEOUT, d_running, st));
+            break;
+        }
+    }
+    std::vector<int> h_int(2 * (size_t)B);
+    HIP_OK(hipMemcpyAsync(best_thetas, ws->d_cd_best, sizeof(double) * BT, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(best_f, ws->d_cd_real, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(profile, ws->d_cd_profile, sizeof(double) * (size_t)B * maxiter, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h_int.data(), ws->d_cd_int, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b) { status[b] = h_int[b]; nit[b] = h_int[B + b]; }
+    return 0;
 }
 
 // ---- MPS helpers ------------------------------------------------------------------------------

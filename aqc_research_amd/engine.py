@@ -395,6 +395,27 @@ class Workspace:
         del keep
         return {"x": x, "profile": prof, "nit": nit, "cost": prof[np.arange(self.batch), nit], "best_f": best_f, "best_x": best_x, "status": st}
 
+    # -- coordinate-descent driver (aqc_ws_cd_minimize) ---------------------------
+    def cd_minimize(self, thetas0, maxiter: int, *, chunk: int = 64, dtheta_thr: float = 1e-8, fobj_thr: float = 1e-2,
+                    time_limit: float = -1.0, route: str = "auto", max_steps: int = -1) -> dict:
+        """Coordinate-descent sweeps of every lane from ``thetas0`` (batch, T) until the lane's stop rule ends it, targets in BUF_Y of
+        a square workspace: best-so-far value and thetas, the profile and the exit status are kept on the device and fetched once.
+        The host reads one word per ``chunk`` sweeps and checks ``time_limit`` (seconds; <= 0: none) there, so a timeout takes
+        effect between chunks, never inside one.  ``route``: "auto", "persistent" (operands in LDS, up to 6 qubits) or "wide".
+        Returns thetas (the best ones), cost, nit, status (int32: 1 normal, 2 early, 3 timeout) and profile (batch, maxiter)."""
+        self._touch(BUF_X, BUF_Z)
+        th = _lib.as_f64(thetas0, self.batch * self.T, "thetas0")
+        maxiter = int(maxiter)
+        if maxiter < 1:
+            raise ValueError("maxiter must be positive")
+        best_x, best_f = np.empty((self.batch, self.T)), np.empty(self.batch)
+        nit, st = np.zeros(self.batch, dtype=np.int64), np.zeros(self.batch, dtype=np.int32)
+        prof = np.zeros((self.batch, maxiter))
+        check(self._L.aqc_ws_cd_minimize(self.handle, dptr(th), maxiter, int(chunk), float(dtheta_thr), float(fobj_thr), float(time_limit),
+                                         _lib.CD_ROUTES[route], int(max_steps), dptr(best_x), dptr(best_f),
+                                         nit.ctypes.data_as(ctypes.POINTER(c_int64)), st.ctypes.data_as(ctypes.POINTER(c_int32)), dptr(prof)))
+        return {"thetas": best_x, "cost": best_f, "nit": nit, "status": st, "profile": prof}
+
     # -- measurement ---------------------------------------------------------
     def timer_start(self) -> None:
         check(self._L.aqc_ws_timer_start(self.handle))

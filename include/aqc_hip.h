@@ -320,6 +320,23 @@ int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io /* [T] */, double* fobj);
  * max_steps >= 0 stops every sweep's walk after that many parameters (tests pin single steps with it); -1 = all. */
 int aqc_ws_cd_sweeps(aqc_ws* ws, double* thetas_io /* [batch][T] */, double* fobj /* [batch][nsweeps] */, int nsweeps, int max_steps);
 int aqc_ws_cd_fits_one_launch(const aqc_ws* ws);
+/* The whole coordinate-descent driver (aqc_coord_descent.py:70-121, _single_simulation) for every lane, without a host visit per
+ * sweep: sweeps from thetas0 until a lane's rule ends it, the best objective value and its thetas kept on the device.  At the end of a
+ * sweep, in the reference's order: profile[lane][nit] = fobj, nit += 1, a value below best_f is recorded with the sweep's thetas, then
+ *   fobj < fobj_thr                 -> AQC_CD_EARLY    (SmallObjectiveStopper)
+ *   max |theta - theta_prev| < dtheta_thr, or nit == maxiter -> AQC_CD_NORMAL
+ * (csrc/aqc_cd_rule.h).  The host enqueues `chunk` sweeps at a time, reads ONE word (lanes still running) and looks at its clock:
+ * once time_limit_s (> 0; <= 0: none) has passed, the lanes still running end as AQC_CD_TIMEOUT -- the time limit acts between
+ * chunks, never inside one.  A finished lane is skipped by every later launch: its thetas and counters do not move.
+ * route: AQC_CD_ROUTE_AUTO (the persistent launch where aqc_ws_cd_fits_one_launch, else the wide walk), _PERSISTENT (an error where
+ * it does not fit), _WIDE: operands in HBM, T + (n + L) walk launches per sweep on a grid of (workgroups per lane, lanes), any
+ * number of qubits and lanes.  max_steps as in aqc_ws_cd_sweeps.  Square workspace, targets in AQC_BUF_Y, cx / cz, no Trotter.
+ * Outputs: best_thetas[batch][T], best_f[batch], nit[batch], status[batch], profile[batch][maxiter] (entries from nit on are 0). */
+enum { AQC_CD_RUNNING = 0, AQC_CD_NORMAL = 1, AQC_CD_EARLY = 2, AQC_CD_TIMEOUT = 3 };
+enum { AQC_CD_ROUTE_AUTO = 0, AQC_CD_ROUTE_PERSISTENT = 1, AQC_CD_ROUTE_WIDE = 2 };
+int aqc_ws_cd_minimize(aqc_ws* ws, const double* thetas0 /* [batch][T] */, int maxiter, int chunk, double dtheta_thr, double fobj_thr,
+                       double time_limit_s, int route, int max_steps, double* best_thetas, double* best_f, int64_t* nit, int32_t* status,
+                       double* profile);
 
 /* ---- measurement hooks (bench.py): HIP events on the workspace's own stream */
 int aqc_ws_timer_start(aqc_ws* ws);
