@@ -337,6 +337,13 @@ hipError_t launch_jacobi_block(void* W, int rows, void* V, int cols, const void*
                                const double* fro2, int* rot, unsigned* bar, int* status, hipStream_t s);
 hipError_t launch_svd_norms(const void* W, int rows, int cols, double* sigma, hipStream_t s);
 hipError_t launch_mps_theta(const void* theta0, const double* lam_left, int chil, int chir, const double* g16, int mode, void* work, hipStream_t s);
+// aqc_svd_batch.hip: block Jacobi on the matrix cores, a workgroup per matrix.  The device-pointer core behind aqc_svd_batch: a [count][m][n],
+// u [count][m][k], s [count][k], vh [count][k][n] (zeroed here, then the leading parts written), d_rows / d_cols / d_sweeps may be null;
+// work and vmat hold svd_batch_work_elems and svd_batch_v_elems complex numbers.  Enqueues on s; synchronises nothing.
+size_t svd_batch_work_elems(int count, int m, int n);
+size_t svd_batch_v_elems(int count, int m, int n);
+hipError_t launch_svd_batch(int count, int m, int n, const int* d_rows, const int* d_cols, const void* d_a, void* d_u, double* d_s, void* d_vh,
+                            int* d_sweeps, int* d_status, void* work, void* vmat, hipStream_t s);
 // ---- device-resident lanes (aqc_mps_batch.cpp): L MPS in flat storage whose bond dimensions live on the device.  A launch takes only
 // lane-independent arguments (site, gate kind, parameter indices); a lane's workgroup reads its own bond dimensions and thetas, so the
 // host never waits for a rank decision and the whole walk of an evaluation is one uninterrupted sequence of launches.

@@ -228,6 +228,46 @@ def svd(a: np.ndarray, device: Optional[int] = None):
     return u, s, vh, sweeps.value
 
 
+SVD_BATCH_MAX = 256   # kSvdbMaxDim of csrc/aqc_svd_blocks.h
+
+
+def svd_batch(a: np.ndarray, rows=None, cols=None, device: Optional[int] = None):
+    """(U, S, Vh, sweeps, status) of ``count`` complex matrices in one call (``aqc_svd_batch``: block Jacobi on the matrix cores, a
+    workgroup per matrix).  ``a`` is complex128 of shape (count, m, n), m, n <= 256; matrix i is active in its leading
+    ``rows[i] x cols[i]`` corner (None: all of it).  With k = min(m, n): U (count, m, k), S (count, k), Vh (count, k, n), zero outside
+    the leading rows[i] x k_i, k_i, k_i x cols[i] parts.  status: 0 converged, 1 sweep limit, 2 non-finite input (outputs zero)."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError("expects a numpy array")
+    if a.dtype != np.complex128:
+        raise TypeError("expects a complex128 array")
+    if a.ndim != 3:
+        raise ValueError("expects an array of shape (count, m, n)")
+    count, m, n = a.shape
+    if count < 1 or not (1 <= m <= SVD_BATCH_MAX and 1 <= n <= SVD_BATCH_MAX):
+        raise ValueError(f"expects count >= 1 and 1 <= m, n <= {SVD_BATCH_MAX}")
+    a = np.ascontiguousarray(a)
+
+    def sizes(v, top, name):
+        if v is None:
+            return None, None
+        v = np.asarray(v)
+        if v.shape != (count,) or not np.issubdtype(v.dtype, np.integer):
+            raise ValueError(f"{name} must hold one integer per matrix")
+        if np.any(v < 1) or np.any(v > top):
+            raise ValueError(f"{name} must lie in 1..{top}")
+        v = np.ascontiguousarray(v, dtype=np.int32)
+        return v, v.ctypes.data_as(POINTER(c_int32))
+
+    rows, prows = sizes(rows, m, "rows")
+    cols, pcols = sizes(cols, n, "cols")
+    k = min(m, n)
+    u, s, vh = np.empty((count, m, k), dtype=np.complex128), np.empty((count, k)), np.empty((count, k, n), dtype=np.complex128)
+    sweeps, status = np.zeros(count, dtype=np.int32), np.zeros(count, dtype=np.int32)
+    check(_lib.lib().aqc_svd_batch(_default_device() if device is None else int(device), count, m, n, prows, pcols, dptr(a), dptr(u), dptr(s), dptr(vh),
+                                   sweeps.ctypes.data_as(POINTER(c_int32)), status.ctypes.data_as(POINTER(c_int32))))
+    return u, s, vh, sweeps, status
+
+
 # ---- circuits on MPS ------------------------------------------------------------------------------------
 
 def _ent_matrix(entangler: str, angle: float) -> np.ndarray:

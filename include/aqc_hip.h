@@ -306,6 +306,19 @@ int aqc_mpsb_gradient_of(aqc_mpsb* b, const aqc_circuit* circ, const double* the
  * rotations work with squared column norms and |<x, y>|^2, which leave the double range when |A|_F is beyond about 2^+-250 (every
  * rotation is skipped then); scalings by 2^+-100 are tested. */
 int aqc_svd(int device, int m, int n, const double* a, double* u, double* s, double* vh, int* sweeps);
+/* the same factorisation for MANY matrices in one call, by block one-sided Jacobi on the fp64 matrix cores (csrc/aqc_svd_batch.hip), a
+ * workgroup per matrix: the SVD of the truncated two-qubit gate (mps_operations.py:252-257) for a batch of two-site tensors whose bonds
+ * differ.  The store has fixed strides, matrix i is active in its leading rows[i] x cols[i] corner (NULL: all m / all n; m, n <= 256);
+ * k = min(m, n), k_i = min(rows[i], cols[i]).  Only the leading rows[i] x k_i of u, k_i of s and k_i x cols[i] of vh are meaningful, the
+ * rest is written as zero.  status[i]: 0 converged, 1 sweep limit reached (results still written), 2 non-finite input (outputs zero, the
+ * other matrices unaffected).  The return value is non-zero only for argument errors (count < 1, sizes out of range, null pointers).
+ * A matrix's result does not depend on its position in the batch or on its neighbours.  Scaling as for aqc_svd. */
+int aqc_svd_batch(int device, int count, int m, int n, const int32_t* rows, const int32_t* cols /* NULL: all m / n */,
+                  const double* a /* [count][m][n] c128 row-major, host */, double* u /* [count][m][k] */, double* s /* [count][k] */,
+                  double* vh /* [count][k][n] */, int32_t* sweeps /* [count] or NULL */, int32_t* status /* [count] */);
+/* milliseconds the device core of this thread's last aqc_svd_batch call took (HIP events around the zeroing of the outputs and the
+ * kernel; uploads, downloads and allocations are outside), -1 if that call failed.  For tools/svd_batch_probe.py. */
+double aqc_svd_batch_core_ms(void);
 
 /* ---- coordinate descent (core_op_matrix.py:765  coord_descent_single_sweep(circ, thetas, target,
  * workspace)).  Square workspace (ncols == 2^n) with the target unitary in AQC_BUF_Y.  One
