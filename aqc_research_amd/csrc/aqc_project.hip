@@ -24,6 +24,11 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 // Y is streamed (read once): no reason to keep it in the caches the small operand lives in
 __device__ __forceinline__ cplx pj_stream(const cplx* p) { const double2_t v = __builtin_nontemporal_load(reinterpret_cast<const double2_t*>(p)); return make_double2(v.x, v.y); }
 
+// x where it is valid, 0 elsewhere -- a select per component, on a value already loaded (never `valid ? load : 0`, which branches
+// around the load, and never a product with 0, which keeps a NaN or an infinity of the target alive)
+// (MASKED = false: the launch has no invalid lane, the value as it is)
+template <bool MASKED>
+__device__ __forceinline__ cplx pj_keep(bool valid, cplx x) { return MASKED ? make_double2(valid ? x.x : 0.0, valid ? x.y : 0.0) : x; }
 __device__ __forceinline__ double4_t pj_mfma(double a, double b, double4_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ unsigned pj_off(const ProjMap& m, unsigned i) { return m.tab ? m.tab[i] : (i << m.shift); }
 __device__ __forceinline__ size_t pj_tile_bits(const ProjArgs& a, int tile) {   // element offset of a first-stage tile: the values of its non-local bits
@@ -254,7 +259,8 @@ hipError_t launch_project_init(const ProjArgs& a, hipStream_t s) {
 // with four blocks leave room for one; sixteen waves with one block each measured 0.36 ms against 0.35 and were dropped).  Complex products in the three-multiplication form: with a = conj(s),
 //     re = sr yr + si yi = A1 + A2,   im = sr yi - si yr = A3 + A1 - A2,   A3 = sum (sr + si)(yi - yr)
 // -- three MFMAs per K-step instead of four, the two extra sums are a handful of vector adds per block.
-template <int QB>
+// MASKED: some column c or block of u of the launch does not exist (2^cb < 16 or 2^us < 256); without it the selects are not compiled.
+template <int QB, bool MASKED>
 __global__ __launch_bounds__(64 * (16 / QB), 1) void project_fused_kernel(const ProjArgs a, const double2* __restrict__ mend, double2* __restrict__ ctile,
                                                                           double2* __restrict__ yout) {
     constexpr int NW = 16 / QB;
@@ -278,54 +284,78 @@ __global__ __launch_bounds__(64 * (16 / QB), 1) void project_fused_kernel(const 
     const cplx* wbase = a.s + real_base + ebits;          // psi: w after the first stage, on the item's tile
     const cplx* mbase = mend + vbase;                     // M_end, virtual layout: i_T + (c << t)
     yout += (size_t)blockIdx.y * a.part_stride;           // (the projection's partial sum over this workgroup's values of u)
+    // Every load below is unconditional: an invalid lane or wave reads index 0 of the same item and its value is replaced by 0 with
+    // a select afterwards (a load inside `valid ? load : 0` compiles to a branch around it and a full wait behind it, which puts
+    // the loads of a block one after the other).  uvalid is uniform over a wave, cvalid over a launch's lanes with the same r16.
     const bool cvalid = r16 < ncb;
-    // this lane's slice of psi: A operand of the second product, rows c = r16, k = u = 16 (QB wave + q) + 4 kg + jj
-    cplx pa[QB][4];
-    double ps[QB][4];
-    unsigned yoff[QB];   // element offset of u = 16 (QB wave + q) + r16: the lane's column of y in block q
+    const unsigned cidx = cvalid ? (unsigned)r16 : 0u;
     bool uvalid[QB];
+    int ubc[QB];   // the wave's block of u, or block 0 where it has none
 #pragma unroll
     for (int q = 0; q < QB; ++q) {
         const int ub = 16 * (int)blockIdx.y + QB * wave + q;   // (blockIdx.y: which 256 values of u -- more than 256: partial projections)
         uvalid[q] = ub * 16 < nu;
-        yoff[q] = uvalid[q] ? a.off_us[ub * 16 + r16] : 0u;
+        ubc[q] = uvalid[q] ? ub : 0;
+    }
+    // the offset tables first, together: u = 16 ub + r16 (the lane's column of y in block q), u = 16 ub + 4 kg + jj and c = r16 (its
+    // slice of psi), the rows i_T = 16 kb + 4 kg + jj of y, the first block of i_T and the one after it
+    unsigned yoff[QB], poff[QB][4], tlow[4];
+#pragma unroll
+    for (int q = 0; q < QB; ++q) {
+        yoff[q] = a.off_us[ubc[q] * 16 + r16];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) poff[q][jj] = a.off_us[ubc[q] * 16 + 4 * kg + jj];
+    }
+    const unsigned coff = a.off_cb[cidx];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) tlow[jj] = a.off_t[4 * kg + jj];
+    const unsigned tb0 = a.off_t[kb0 * 16];
+    // offset of the block after the next one requested: loaded a whole iteration before the request that needs it
+    unsigned tbn = a.off_t[min(kb0 + 1, nkb_all - 1) * 16];
+    // this lane's slice of psi: A operand of the second product, rows c = r16, k = u = 16 (QB wave + q) + 4 kg + jj
+    cplx pa[QB][4];
+    double ps[QB][4];
+#pragma unroll
+    for (int q = 0; q < QB; ++q)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) pa[q][jj] = wbase[poff[q][jj] + coff];
+    cplx yv[QB][4];
+#pragma unroll
+    for (int q = 0; q < QB; ++q)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) yv[q][jj] = pj_stream(ybase + yoff[q] + tb0 + tlow[jj]);
+    // M_end rows i_T = 16 kb + 4 kg + jj, column c = r16: A operand of the first product, fetched one block ahead (scattered 16-byte
+    // loads from L2: their latency would otherwise open every block)
+    const cplx* mcol = mbase + ((size_t)cidx << a.t);
+    cplx mn[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) mn[jj] = mcol[(size_t)(kb0 * 16 + 4 * kg + jj)];
+#pragma unroll
+    for (int q = 0; q < QB; ++q)
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-            pa[q][jj] = (uvalid[q] && cvalid) ? wbase[a.off_us[ub * 16 + 4 * kg + jj] + a.off_cb[r16]] : make_double2(0.0, 0.0);
+            pa[q][jj] = pj_keep<MASKED>(uvalid[q] && cvalid, pa[q][jj]);
             ps[q][jj] = pa[q][jj].x + pa[q][jj].y;
         }
-    }
     double4_t c1[QB], c2[QB], c3[QB];
 #pragma unroll
     for (int q = 0; q < QB; ++q) { c1[q] = double4_t{0.0, 0.0, 0.0, 0.0}; c2[q] = c1[q]; c3[q] = c1[q]; }
-    unsigned tlow[4];   // rows i_T = 16 kb + 4 kg + jj of y
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) tlow[jj] = a.off_t[4 * kg + jj];
-    cplx yv[QB][4];
-    {
-        const unsigned tb = a.off_t[kb0 * 16];
-#pragma unroll
-        for (int q = 0; q < QB; ++q)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) yv[q][jj] = uvalid[q] ? pj_stream(ybase + yoff[q] + tb + tlow[jj]) : make_double2(0.0, 0.0);
-    }
-    // M_end rows i_T = 16 kb + 4 kg + jj, column c = r16: A operand of the first product, fetched one block ahead (scattered 16-byte
-    // loads from L2: their latency would otherwise open every block)
-    cplx mn[4];
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) mn[jj] = cvalid ? mbase[(size_t)(kb0 * 16 + 4 * kg + jj) + ((size_t)r16 << a.t)] : make_double2(0.0, 0.0);
     for (int kb = kb0; kb < nkb; ++kb) {
+        const bool more = kb + 1 < nkb;
+        const unsigned tb = tbn;   // offset of block kb + 1
         cplx ma[4];
         double ms[4];
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-            ma[jj] = mn[jj];
+            ma[jj] = pj_keep<MASKED>(cvalid, mn[jj]);
             ms[jj] = ma[jj].x + ma[jj].y;
         }
-        if (kb + 1 < nkb) {
+        // (the last block asks for its own rows again and for one element of y per load: a load that only some iterations issue
+        // would make every wait behind it a full one)
+        const unsigned ymask = more ? ~0u : 0u;
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) mn[jj] = cvalid ? mbase[(size_t)((kb + 1) * 16 + 4 * kg + jj) + ((size_t)r16 << a.t)] : make_double2(0.0, 0.0);
-        }
+        for (int jj = 0; jj < 4; ++jj) mn[jj] = mcol[(size_t)(min(kb + 1, nkb - 1) * 16 + 4 * kg + jj)];
+        tbn = a.off_t[min(kb + 2, nkb_all - 1) * 16];
         double4_t y1 = {0.0, 0.0, 0.0, 0.0}, y2 = y1, y3 = y1;
 #pragma unroll
         for (int h0 = 0; h0 < QB; h0 += PB) {
@@ -333,26 +363,28 @@ __global__ __launch_bounds__(64 * (16 / QB), 1) void project_fused_kernel(const 
             for (int qq = 0; qq < PB; ++qq) {   // first product on the fetched layout; the block goes to its transposition tile
                 const int q = h0 + qq;
                 cplx* tq = tile + qq * (16 * kPjRow);
+                cplx yq[4];
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) tq[(4 * kg + jj) * kPjRow + r16] = yv[q][jj];   // [row = i_T in the block][col = u in the block]
+                for (int jj = 0; jj < 4; ++jj) yq[jj] = pj_keep<MASKED>(uvalid[q], yv[q][jj]);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) tq[(4 * kg + jj) * kPjRow + r16] = yq[jj];   // [row = i_T in the block][col = u in the block]
                 double yd[4];
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) yd[jj] = yv[q][jj].y - yv[q][jj].x;
+                for (int jj = 0; jj < 4; ++jj) yd[jj] = yq[jj].y - yq[jj].x;
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
-                    c1[q] = pj_mfma(ma[jj].x, yv[q][jj].x, c1[q]);
-                    c2[q] = pj_mfma(ma[jj].y, yv[q][jj].y, c2[q]);
+                    c1[q] = pj_mfma(ma[jj].x, yq[jj].x, c1[q]);
+                    c2[q] = pj_mfma(ma[jj].y, yq[jj].y, c2[q]);
                     c3[q] = pj_mfma(ms[jj], yd[jj], c3[q]);
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            if (h0 + PB >= QB && kb + 1 < nkb) {   // the fetched block is consumed: the next one is requested under the second product
-                const unsigned tb = a.off_t[(kb + 1) * 16];
+            if (h0 + PB >= QB) {   // the fetched block is consumed: the next one is requested under the second product
 #pragma unroll
                 for (int q = 0; q < QB; ++q)
 #pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) yv[q][jj] = uvalid[q] ? pj_stream(ybase + yoff[q] + tb + tlow[jj]) : make_double2(0.0, 0.0);
+                    for (int jj = 0; jj < 4; ++jj) yv[q][jj] = pj_stream(ybase + ((yoff[q] + tb + tlow[jj]) & ymask));
             }
 #pragma unroll
             for (int qq = 0; qq < PB; ++qq) {   // second product: B[k = u][col = i_T] = the tile read across
@@ -399,6 +431,9 @@ __global__ __launch_bounds__(64 * (16 / QB), 1) void project_fused_kernel(const 
         return;
     }
     cplx* obase = ctile + real_base + ebits;
+    unsigned ocb[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ocb[r] = a.off_cb[min(kg + 4 * r, ncb - 1)];
 #pragma unroll
     for (int q = 0; q < QB; ++q) {
         if (!uvalid[q]) continue;
@@ -406,7 +441,7 @@ __global__ __launch_bounds__(64 * (16 / QB), 1) void project_fused_kernel(const 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int c = kg + 4 * r;
-            if (c < ncb) orow[a.off_cb[c]] = make_double2(c1[q][r] + c2[q][r], c3[q][r] + c1[q][r] - c2[q][r]);
+            if (c < ncb) orow[ocb[r]] = make_double2(c1[q][r] + c2[q][r], c3[q][r] + c1[q][r] - c2[q][r]);
         }
     }
 }
@@ -449,8 +484,11 @@ hipError_t launch_project_fused(const ProjArgs& a, const void* mend, void* ctile
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     const size_t lds2 = (8 * 2 * 16 * kPjRow + 2 * 8 * 256) * sizeof(cplx), lds4 = (4 * 2 * 16 * kPjRow + 2 * 4 * 256) * sizeof(cplx);
     if (!attr_set[dev] || dev == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(project_fused_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(project_fused_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
+        hipError_t e = hipSuccess;
+        for (const void* f : {reinterpret_cast<const void*>(project_fused_kernel<2, false>), reinterpret_cast<const void*>(project_fused_kernel<2, true>)})
+            if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+        for (const void* f : {reinterpret_cast<const void*>(project_fused_kernel<4, false>), reinterpret_cast<const void*>(project_fused_kernel<4, true>)})
+            if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
         if (e != hipSuccess) return e;
         attr_set[dev] = true;
     }
@@ -462,8 +500,14 @@ hipError_t launch_project_fused(const ProjArgs& a, const void* mend, void* ctile
     const double2* m = static_cast<const double2*>(mend);
     double2* c = static_cast<double2*>(ctile);
     double2* y = static_cast<double2*>(yout);
-    if (qb == 2) project_fused_kernel<2><<<grid, 512, lds2, s>>>(a, m, c, y);
-    else project_fused_kernel<4><<<grid, 256, lds4, s>>>(a, m, c, y);
+    const bool masked = a.cb < 4 || a.us_bits < 8;   // (every column c and every wave's blocks of u exist otherwise)
+    if (qb == 2) {
+        if (masked) project_fused_kernel<2, true><<<grid, 512, lds2, s>>>(a, m, c, y);
+        else project_fused_kernel<2, false><<<grid, 512, lds2, s>>>(a, m, c, y);
+    } else {
+        if (masked) project_fused_kernel<4, true><<<grid, 256, lds4, s>>>(a, m, c, y);
+        else project_fused_kernel<4, false><<<grid, 256, lds4, s>>>(a, m, c, y);
+    }
     if (nparts > 1) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
