@@ -148,16 +148,19 @@ def test_device_resident_lbfgs_matches_the_host_version():
         assert abs(abs(np.vdot(orc.v_mul_vec(a, dev["x"][b], x), targets[b])) ** 2 - fid_dev[b]) < 1e-9
 
 
-def test_device_resident_lbfgs_with_leading_flip_state():
+def _leading_flip_state_case(depth):
     """Targets close to a flipped basis state: the surrogate's second sweep (leading state != |state_0>) runs inside the
-    device loop; the device result must agree with the host version lane by lane."""
+    device loop; the device result must agree with the host version lane by lane.  The CPU oracle has no evaluation under a
+    frozen state (its SurMaxOracle updates the state with every call, where a line-search trial must not), so for this branch
+    the host loop on the device's value_and_grad is the comparison; tests/test_hip_optimisers_wide.py compares the same
+    kernels with the oracle while |state_0> leads."""
     from aqc_research_amd import ParametricCircuit
     from aqc_research_amd.batched_optimizer import BatchedSurrogateObjective, batched_lbfgs
     from aqc_research_amd.circuit_structures import create_ansatz_structure
 
     n, B = 8, 3
     rng = np.random.default_rng(808)
-    circ = ParametricCircuit(n, "cx", create_ansatz_structure(n, "spin", "full", 10))
+    circ = ParametricCircuit(n, "cx", create_ansatz_structure(n, "spin", "full", depth))
     targets = []
     for b in range(B):   # mostly the state with qubit b flipped, a little of everything else
         t = 0.05 * (rng.standard_normal(1 << n) + 1j * rng.standard_normal(1 << n))
@@ -171,6 +174,22 @@ def test_device_resident_lbfgs_with_leading_flip_state():
     bo.close()
     bo = BatchedSurrogateObjective(circ, targets)
     dev = bo.minimize_on_device(starts, maxiter=15)
+    lead_dev = bo.max_no.copy()
     bo.close()
+    df, dx = np.max(np.abs(dev["fun"] - f_host)), np.max(np.abs(dev["x"] - host["x"]))
+    print(f"T = {circ.num_thetas}: leading states {lead_host}, |f_dev - f_host| = {df:.2e}, |x_dev - x_host| = {dx:.2e}, nit {dev['nit']} / {host['nit']}")
     assert (lead_host != 0).any()                      # the case this test is about really occurs
-    assert np.max(np.abs(dev["fun"] - f_host)) < 1e-6 and np.max(np.abs(dev["x"] - host["x"])) < 1e-5
+    assert df < 1e-6 and dx < 1e-5
+    return circ, host, dev, lead_host, lead_dev
+
+
+def test_device_resident_lbfgs_with_leading_flip_state():
+    _leading_flip_state_case(10)
+
+
+def test_device_resident_lbfgs_with_leading_flip_state_past_256_parameters():
+    """Depth 60 at 8 qubits, T = 264: the kMat = false step kernels, lb_copy_raw and the second evaluation of accepted points
+    with more than one parameter per thread.  The same bounds, and the same leading states and iteration counts besides."""
+    circ, host, dev, lead_host, lead_dev = _leading_flip_state_case(60)
+    assert circ.num_thetas == 264
+    assert (lead_dev == lead_host).all() and (dev["nit"] == host["nit"]).all()

@@ -172,7 +172,8 @@ def test_device_draws_equal_the_numpy_philox_call():
 
 # ---- the ADAM run ---------------------------------------------------------------------------------------------------------
 
-ADAM_CASES = {"n3": (3, "cz", 6, 2), "n5": (5, "cx", 12, 8)}
+# the last two: T = 257 and T = 529, so sk_adam_kernel's strided update and its tree reduction of |step|^2 take more than one pass
+ADAM_CASES = {"n3": (3, "cz", 6, 2), "n5": (5, "cx", 12, 8), "w257": (3, "cx", 62, 2), "w529": (3, "cx", 130, 2)}
 NITER, LR = 6, 0.1
 
 
@@ -239,6 +240,60 @@ def test_adam_tolerance_flag_freezes_the_lane(adam_case):
     assert [int(v) for v in four["nit"]] == [1] * c["lanes"]
     assert np.array_equal(four["x"], one["x"]) and not np.array_equal(four["x"], c["thetas"])
     assert np.array_equal(four["cost"], four["profile"][:, 1]) and np.array_equal(four["profile"][:, :2], one["profile"])
+
+
+def test_adam_step_norm_counts_every_parameter(adam_case):
+    """The tol stop compares sqrt(sum step^2) over all T parameters with tol, and the fixture's runs never reach it.  Here one
+    sketch is kept for all iterations, so the gradient hardly changes, every |step_i| is about lr (ADAM's lr sign(g)) and the norm
+    about lr sqrt(T).  At lr = 1.2e-6 / sqrt(T) it is 1.2e-6: above tol = 1e-6 when every parameter is counted, below it when a
+    pass of 256 is lost (T = 529: 0.83e-6), which would freeze the lane after one iteration.  At lr = 0.8e-6 / sqrt(T) the lane
+    must freeze after one.  The CPU walk says what happens, and its step norms are compared with the device's points.
+
+    Only T = 529 pins the reduction itself: at T = 257 the one element of the second pass is 1 / 257 of the sum, which no lr can
+    put across tol with room to spare, and the step norms taken from the device's points check the update of every parameter,
+    not the reduced value.  The other cases check that update and the two outcomes of the stop."""
+    from aqc_research_amd.engine import HipContext, Workspace
+
+    c = adam_case
+    T = c["circ"].num_thetas
+    tol, niter = 1e-6, 4
+    idx = np.ascontiguousarray(np.repeat(c["idx"][:1], niter + 1, axis=0))
+
+    def walk(lr):
+        out = []
+        for b in range(c["lanes"]):
+            def fun_grad(x, s, b=b):
+                xm, ym = sk.generate(sk.SKETCH_ALT, c["targets"][b], c["k"], idx=idx[s - 1, b])
+                return orc.sketching_objective_and_gradient(c["circ"], x, xm, ym)
+            out.append(sk.adam_walk(fun_grad, c["thetas"][b], niter, lr, tol=tol))
+        return out
+
+    lr, lr_small = 1.2e-6 / np.sqrt(T), 0.8e-6 / np.sqrt(T)
+    walks, stopped = walk(lr), walk(lr_small)
+    assert all(w[2] == niter for w in walks) and all(w[2] == 1 for w in stopped)
+    norms = np.array([[np.linalg.norm(w[3][i + 1] - w[3][i]) for i in range(niter)] for w in walks])
+    print(f"T = {T}: CPU step norms {np.array2string(norms, precision=4)}")
+    assert (norms > 1.05 * tol).all()                                                 # nowhere near the edge
+    assert all(np.linalg.norm(w[3][1] - w[3][0]) < 0.95 * tol for w in stopped)
+    if T > 512:
+        assert all(np.linalg.norm((w[3][1] - w[3][0])[:256]) < 0.95 * tol for w in walks)   # the first pass alone would stop it
+    ws = Workspace(HipContext.of(c["circ"]), batch=c["lanes"], ncols=c["k"])
+    ws.sketch_target(c["targets"])
+    xs = [np.array(c["thetas"])]
+    for i in range(niter):          # one iteration per call: the points in between
+        one = ws.sketch_adam("alt", c["thetas"] if i == 0 else None, 1, lr, tol=tol, iter0=i, reset=1 if i == 0 else 0, alt_idx=idx[i:i + 2])
+        assert [int(v) for v in one["nit"]] == [1] * c["lanes"], i
+        xs.append(one["x"].copy())
+    whole = ws.sketch_adam("alt", c["thetas"], niter, lr, tol=tol, reset=1, alt_idx=idx)
+    frozen = ws.sketch_adam("alt", c["thetas"], niter, lr_small, tol=tol, reset=1, alt_idx=idx)
+    ws.close()
+    assert [int(v) for v in whole["nit"]] == [niter] * c["lanes"] and np.array_equal(whole["x"], xs[-1])
+    assert [int(v) for v in frozen["nit"]] == [1] * c["lanes"]
+    dev_norms = np.array([[np.linalg.norm(xs[i + 1][b] - xs[i][b]) for i in range(niter)] for b in range(c["lanes"])])
+    print(f"  device step norms {np.array2string(dev_norms, precision=4)}")
+    assert np.max(np.abs(dev_norms - norms)) < 1e-4 * tol      # one parameter lost of 529 would be 1e-3 of the norm
+    for b in range(c["lanes"]):
+        assert maxdiff(whole["x"][b], walks[b][0]) < 1e-9 and maxdiff(frozen["x"][b], stopped[b][0]) < 1e-9
 
 
 # ---- the driver -----------------------------------------------------------------------------------------------------------
