@@ -42,7 +42,9 @@ enum { AQC_CX = 0, AQC_CZ = 1, AQC_CP = 2 };
  * work -- the code a caller falls back on.  Every other failure is some other non-zero code and is final. */
 enum { AQC_LANES_REFUSED = 3 };
 /* device buffers of a workspace, each [batch][2^n][ncols] complex128: Y target, Z = V^H Y, X / X2 lhs states of the sweep,
- * W / ZW scratch of the sweep.  ZW doubles as the checkpoint of V^H: aqc_ws_apply(inverse, Y -> Z) leaves there the state before
+ * W / ZW scratch of the sweep: what a sweep leaves there is unspecified (the register-blocked sweep, for one, walks w and z without
+ * the lane sign that the cos >= 0 normalisation of the half angles drops -- it cancels in every inner product -- so its final w is
+ * +-V x).  ZW doubles as the checkpoint of V^H: aqc_ws_apply(inverse, Y -> Z) leaves there the state before
  * its last stage, which is what the sweep's second stage takes as z when the lhs state is sparse (aqc_ws_set_basis /
  * aqc_ws_set_combo; grad_of_dot_product, core_operations.py:892-935, copies x into w: a one-hot x leaves w zero outside one tile
  * during the first stage).  One-call evaluations (aqc_ws_eval, aqc_ws_objective_launch, aqc_ws_surrogate_eval, aqc_ws_lbfgs) may

@@ -13,6 +13,7 @@ Import accommodations (no reference code is modified or copied):
     exercised below is pure reference NumPy arithmetic.
 
 Usage:  python tests/golden/make_golden.py   (writes tests/golden/*.npz)
+        python tests/golden/make_golden.py --angles-only [DIR]   (angles.npz alone, into DIR if given: the other files stay as they are)
 """
 
 import os
@@ -336,9 +337,68 @@ def gen_primitives():
     np.savez_compressed(os.path.join(HERE, "primitives.npz"), **data)
 
 
+def gen_angles(out_dir=HERE):
+    """The hot-path functions at thetas outside [-pi, pi] (patterns of tests/angle_cases.py): every other section draws
+    pi (2u - 1), on which no half-angle cosine is negative.  Circuits of 5 qubits; `one_flip` adds 2 pi to one angle of a
+    tail record where the ansatz has a tail (second-order Trotter), else to one of a block.  The reference's
+    coord_descent_single_sweep refuses the cp entangler (core_op_matrix.py:819), so the sweep is held for cx and cz."""
+    from tests import angle_cases as ac
+
+    n = 5
+    circs = [(f"{ent}_spin_n{n}", ParametricCircuit(n, ent, create_ansatz_structure(n, "spin", "full", 9))) for ent in ("cx", "cz", "cp")]
+    circs += [(f"trot{2 if o2 else 1}_n{n}", TrotterAnsatz(n, make_trotter_like_circuit(n, 2), second_order=o2)) for o2 in (False, True)]
+    seeds = (100, 104, 103, 105, 104)   # per circuit: the draw of `wide` has odd parity (angle_cases.check_reaches_sign_path)
+    rng = np.random.default_rng(8642)
+    data, names = {}, []
+    for (cname, circ), seed in zip(circs, seeds):
+        dim, nb = circ.dimension, circ.num_blocks
+        trot = isinstance(circ, TrotterAnsatz)
+        tail = trot and circ.is_second_order
+        br = (2, circ.bpl + 1) if trot else (1, max(2, nb - 1))
+        for pattern in ("wide", "exact", "one_flip"):
+            role = ("tail" if tail else "block") if pattern == "one_flip" else None
+            th, par = ac.thetas(circ, pattern, seed, role=role)
+            ac.check_reaches_sign_path(circ, pattern, th, par, role)
+            key = f"{cname}_{pattern}"
+            x, y = rand_vec(dim, rng), rand_vec(dim, rng)
+            ws = np.zeros((3, dim), dtype=np.complex128)
+            vx = cop.v_mul_vec(circ, th, x, np.zeros(dim, np.complex128), ws[:2]).copy()
+            vhy = cop.v_dagger_mul_vec(circ, th, y, np.zeros(dim, np.complex128), ws[:2]).copy()
+            for k, v in describe(circ).items():
+                data[f"{key}/{k}"] = v
+            data[f"{key}/thetas"], data[f"{key}/parity"] = th, np.int64(par)
+            data[f"{key}/x"], data[f"{key}/y"], data[f"{key}/v_x"], data[f"{key}/vh_y"] = x, y, vx, vhy
+            data[f"{key}/grad_full"] = cop.grad_of_dot_product(circ, th, x, vhy, ws).copy()
+            data[f"{key}/block_range"] = np.asarray(br, np.int64)
+            data[f"{key}/grad_part"] = cop.grad_of_dot_product(circ, th, x, vhy, ws, block_range=br, front_layer=False).copy()
+            names.append(key)
+            if trot or pattern != "wide":
+                continue
+            k = 3
+            xm = rng.standard_normal((dim, k)) + 1j * rng.standard_normal((dim, k))
+            ym = rng.standard_normal((dim, k)) + 1j * rng.standard_normal((dim, k))
+            wsm = np.zeros((dim, k), np.complex128)
+            data[f"{key}/xm"], data[f"{key}/ym"] = xm, ym
+            data[f"{key}/v_xm"] = com.v_mul_mat(circ, th, xm.copy(), wsm).copy()
+            vhym = com.v_dagger_mul_mat(circ, th, ym.copy(), wsm).copy()
+            data[f"{key}/vh_ym"] = vhym
+            data[f"{key}/grad_m"] = com.grad_of_matrix_dot_product(circ, th, xm.copy(), vhym.copy(), wsm).copy()
+            if circ.entangler != "cp":
+                q, _ = np.linalg.qr(rng.standard_normal((dim, dim)) + 1j * rng.standard_normal((dim, dim)))
+                th_io = th.copy()
+                f1 = com.coord_descent_single_sweep(circ, th_io, q, np.zeros((3, dim, dim), np.complex128))
+                data[f"{key}/cd_target"], data[f"{key}/cd_thetas_1"], data[f"{key}/cd_fobj_1"] = q, th_io.copy(), np.float64(f1)
+    data["names"] = np.array(names)
+    np.savez_compressed(os.path.join(out_dir, "angles.npz"), **data)
+
+
 if __name__ == "__main__":
     if "--primitives-only" in sys.argv:   # added later: leaves the earlier fixture files byte-identical
         gen_primitives()
+        sys.exit(0)
+    if "--angles-only" in sys.argv:       # likewise; an optional directory after the flag receives the file instead
+        rest = sys.argv[sys.argv.index("--angles-only") + 1:]
+        gen_angles(rest[0] if rest else HERE)
         sys.exit(0)
     gen_state_vector()
     gen_gate2x2()
@@ -346,6 +406,7 @@ if __name__ == "__main__":
     gen_objectives()
     gen_mps()
     gen_primitives()
+    gen_angles()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")

@@ -91,3 +91,28 @@ def test_c_coordinate_descent_matches_the_golden_sweeps_and_the_numpy_restatemen
             t1, f1 = orc.coord_descent_single_sweep(a, th[b], us[b])
             t2, f2 = orc.coord_descent_single_sweep(a, t1, us[b])
             assert abs(f[b, 0] - f1) < 1e-9 and abs(f[b, 1] - f2) < 1e-8 and np.abs(got[b] - t2).max() < 1e-8
+
+
+ANG = load("angles.npz")
+
+
+@pytest.mark.parametrize("key", [str(k) for k in ANG["names"]])
+def test_angles_outside_the_principal_range_golden(key):
+    """Thetas outside [-pi, pi] (tests/angle_cases.py; make_golden.py::gen_angles)."""
+    a = ansatz_from(ANG, key)
+    th, x, y = ANG[f"{key}/thetas"], ANG[f"{key}/x"], ANG[f"{key}/y"]
+    assert maxdiff(ref.v_mul_vec(a, th, x), ANG[f"{key}/v_x"]) < TOL
+    vhy = ref.v_dagger_mul_vec(a, th, y)
+    assert maxdiff(vhy, ANG[f"{key}/vh_y"]) < TOL
+    assert maxdiff(ref.grad_of_dot_product(a, th, x, vhy), ANG[f"{key}/grad_full"]) < TOL
+    br = tuple(int(v) for v in ANG[f"{key}/block_range"])
+    assert maxdiff(ref.grad_of_dot_product(a, th, x, vhy, br, False), ANG[f"{key}/grad_part"]) < TOL
+    if f"{key}/xm" in ANG.files:
+        xm, ym = ANG[f"{key}/xm"], ANG[f"{key}/ym"]
+        assert maxdiff(ref.v_mul_mat(a, th, xm), ANG[f"{key}/v_xm"]) < TOL
+        vhym = ref.v_dagger_mul_mat(a, th, ym)
+        assert maxdiff(vhym, ANG[f"{key}/vh_ym"]) < TOL
+        assert maxdiff(ref.grad_of_matrix_dot_product(a, th, xm, vhym), ANG[f"{key}/grad_m"]) < TOL
+    if f"{key}/cd_target" in ANG.files:
+        t1, f1 = ref.coord_descent_sweeps(a, th, ANG[f"{key}/cd_target"], 1)
+        assert maxdiff(t1[0], ANG[f"{key}/cd_thetas_1"]) < 1e-9 and abs(f1[0, 0] - float(ANG[f"{key}/cd_fobj_1"])) < 1e-9

@@ -146,3 +146,31 @@ def test_primitives_golden():
                 v = m.copy().ravel()
                 orc._entangle(v, k << c, k << t, name, 0.83)
                 assert maxdiff(v.reshape(m.shape), PRIM[f"mat{k}/{name}"][i]) < TOL
+
+
+ANG = load("angles.npz")
+
+
+@pytest.mark.parametrize("key", [str(k) for k in ANG["names"]])
+def test_angles_outside_the_principal_range(key):
+    """Thetas outside [-pi, pi] (tests/angle_cases.py; make_golden.py::gen_angles): every other fixture draws pi (2u - 1)."""
+    from tests import angle_cases as ac
+
+    a = ansatz_from(ANG, key)
+    th, x, y = ANG[f"{key}/thetas"], ANG[f"{key}/x"], ANG[f"{key}/y"]
+    assert np.abs(th).max() > np.pi and int(ANG[f"{key}/parity"]) == ac.parity(a, th)
+    assert maxdiff(orc.v_mul_vec(a, th, x), ANG[f"{key}/v_x"]) < TOL
+    vhy = orc.v_dagger_mul_vec(a, th, y)
+    assert maxdiff(vhy, ANG[f"{key}/vh_y"]) < TOL
+    assert maxdiff(orc.grad_of_dot_product(a, th, x, vhy), ANG[f"{key}/grad_full"]) < TOL
+    br = tuple(int(v) for v in ANG[f"{key}/block_range"])
+    assert maxdiff(orc.grad_of_dot_product(a, th, x, vhy, block_range=br, front_layer=False), ANG[f"{key}/grad_part"]) < TOL
+    if f"{key}/xm" in ANG.files:
+        xm, ym = ANG[f"{key}/xm"], ANG[f"{key}/ym"]
+        assert maxdiff(orc.v_mul_mat(a, th, xm), ANG[f"{key}/v_xm"]) < TOL
+        vhym = orc.v_dagger_mul_mat(a, th, ym)
+        assert maxdiff(vhym, ANG[f"{key}/vh_ym"]) < TOL
+        assert maxdiff(orc.grad_of_matrix_dot_product(a, th, xm, vhym), ANG[f"{key}/grad_m"]) < TOL
+    if f"{key}/cd_target" in ANG.files:
+        t1, f1 = orc.coord_descent_single_sweep(a, th, ANG[f"{key}/cd_target"])
+        assert maxdiff(t1, ANG[f"{key}/cd_thetas_1"]) < 1e-9 and abs(f1 - float(ANG[f"{key}/cd_fobj_1"])) < 1e-9
