@@ -158,7 +158,8 @@ def coord_descent_single_sweep(circ, thetas: np.ndarray, target: np.ndarray, wor
     """One Gauss-Seidel sweep over all parameters of ``1 - |<V,U>|^2 / d^2``
     (core_op_matrix.py:765-917).  ``thetas`` is updated in place; returns the objective at the
     end of the sweep.  The whole sweep runs on the device: ONE persistent launch while the two d x d operands fit a
-    workgroup's LDS (up to 6 qubits; ``aqc_ws_cd_sweeps``), a chain of 2 launches per parameter beyond."""
+    workgroup's LDS (up to 6 qubits; ``aqc_ws_cd_sweeps``), one sweep of the wide walk of ``Workspace.cd_minimize`` beyond (operands
+    in HBM, one launch per parameter and one per front-layer qubit or block)."""
     from . import _lib
     from ._lib import check, dptr
 
@@ -174,7 +175,7 @@ def coord_descent_single_sweep(circ, thetas: np.ndarray, target: np.ndarray, wor
     ws = HipContext.of(circ).workspace(1, target.shape[1])
     ws.upload(BUF_Y, target)
     fobj = np.zeros(1)
-    ws._touch(_lib.BUF_X, _lib.BUF_Z, _lib.BUF_W, _lib.BUF_ZW)   # rewritten by the sweep
+    ws._touch(_lib.BUF_X, _lib.BUF_Z, _lib.BUF_ZW)   # the wide walk rewrites X and Z in place; its V^H leaves a checkpoint in ZW
     check(_lib.lib().aqc_ws_cd_sweep(ws.handle, dptr(thetas), dptr(fobj)))
     return float(fobj[0])
 

@@ -253,11 +253,6 @@ struct MpsSites {            // site table of one MPS (by value in the kernel ar
 hipError_t launch_mps_scale_all(void* t, const double* lam, const MpsSites& sites, hipStream_t s);
 
 // aqc_cd.hip
-int cd_num_parts(size_t npairs);
-hipError_t launch_cd_dot(const void* w, const void* z, size_t npairs, int hbit, int kind, void* part, hipStream_t s);
-hipError_t launch_cd_update(void* w, void* z, size_t npairs, int hbit, int kind, const void* part, int nparts,
-                            const double* theta_in, double* theta_out, int tindex, double dim, hipStream_t s);
-hipError_t launch_cd_entangle(void* w, void* z, size_t ngroups, int cbit, int tbit, int ent, hipStream_t s);
 // the whole walk as one persistent launch (a workgroup per lane, operands in LDS): segment list entry = CdSeg of aqc_cd.hip
 struct CdSegHost { int32_t ha, hb, ent, nrot, kind[4], on_b[4], tindex[4]; };
 size_t cd_persistent_lds_bytes(int nbits, int T);

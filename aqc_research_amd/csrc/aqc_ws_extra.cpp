@@ -11,7 +11,7 @@ static double wall_seconds() { return std::chrono::duration<double>(std::chrono:
 
 extern "C" {
 
-// the workspace's grow-only scratch (coordinate descent chain, MPS helpers)
+// the workspace's grow-only scratch (MPS helpers)
 static int mps_scratch(aqc_ws* ws, size_t n_cplx) {
     if (n_cplx <= ws->d_mps_scratch.capacity()) return 0;
     HIP_OK(hipStreamSynchronize(ws->stream));   // launches in flight may still read the block that goes
@@ -153,7 +153,7 @@ int aqc_ws_cd_sweeps(aqc_ws* ws, double* thetas_io, double* fobj, int nsweeps, i
     if (nsweeps < 1) return fail("nsweeps must be positive");
     if (cd_checks(ws)) return 1;
     if (!aqc_ws_cd_fits_one_launch(ws))
-        return fail("the operands of this coordinate descent (2 x %zu KiB) do not fit one workgroup's LDS: use aqc_ws_cd_sweep (launch chain, one lane)",
+        return fail("the operands of this coordinate descent (2 x %zu KiB) do not fit one workgroup's LDS: use aqc_ws_cd_minimize (the wide walk, any number of lanes)",
                     (ws->lane_elems * sizeof(double2)) >> 10);
     const Program& prog = ws->ctx->prog;
     const int T = prog.num_thetas();
@@ -171,63 +171,6 @@ int aqc_ws_cd_sweeps(aqc_ws* ws, double* thetas_io, double* fobj, int nsweeps, i
     HIP_OK(hipMemcpyAsync(fobj, ws->d_cd_fobj, sizeof(double) * nf, hipMemcpyDeviceToHost, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
     return 0;
-}
-
-int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io, double* fobj) {
-    if (!ws || !thetas_io || !fobj) return fail("null argument");
-    if (cd_checks(ws)) return 1;
-    const char* chain = getenv("AQC_CD_CHAIN");   // "1": the launch chain below even where one launch would do (cross-check, timing)
-    if (ws->batch != 1) return fail("aqc_ws_cd_sweep takes thetas_io[T] and one objective value: a single-lane workspace (aqc_ws_cd_sweeps serves lanes)");
-    if (aqc_ws_cd_fits_one_launch(ws) && !(chain && chain[0] == '1')) return aqc_ws_cd_sweeps(ws, thetas_io, fobj, 1, -1);
-    const Program& prog = ws->ctx->prog;
-    const int dim = 1 << prog.n;
-    HIP_OK(hipSetDevice(ws->device));
-    const int T = prog.num_thetas();
-    if (aqc_ws_set_thetas(ws, thetas_io)) return 1;                  // theta_in = d_thetas_own
-    if (aqc_ws_apply(ws, 1, AQC_BUF_Y, AQC_BUF_Z)) return 1;          // z = V^H U      (core_op_matrix.py:806-810)
-    if (aqc_ws_set_identity(ws, AQC_BUF_X)) return 1;                 // w = I
-    if (before_write(ws, AQC_BUF_X) || before_write(ws, AQC_BUF_Z)) return 1;   // the chain below rewrites both in place
-    DevBuf<double> d_theta_out;   // (every return releases it; the chain's own exit synchronises first)
-    if (d_theta_out.alloc(T)) return 1;
-    HIP_OK(hipMemcpyAsync(d_theta_out, ws->d_thetas_own, sizeof(double) * T, hipMemcpyDeviceToDevice, ws->stream));
-    double2* w = ws->bufs[AQC_BUF_X];
-    double2* z = ws->bufs[AQC_BUF_Z];
-    const size_t npairs = ws->lane_elems >> 1, ngroups = ws->lane_elems >> 2;
-    const int nparts = cd_num_parts(npairs);
-    if (mps_scratch(ws, 2 * (size_t)nparts)) return 1;
-    double2* part = ws->d_mps_scratch;
-    int rc = 0;
-    auto step = [&](int qubit, int kind, int tindex) -> int {
-        const int hbit = ws->col_bits + qubit;
-        ProfScope ps(ws, AQC_K_MISC);
-        HIP_OK(launch_cd_dot(w, z, npairs, hbit, kind, part, ws->stream));
-        HIP_OK(launch_cd_update(w, z, npairs, hbit, kind, part, nparts, ws->d_thetas_own, d_theta_out, tindex, (double)dim, ws->stream));
-        return 0;
-    };
-    for (const GateGroup& g : prog.groups) {
-        if (g.type == GROUP_FRONT) {
-            rc = step(g.q0, 1, g.theta0 + 2) || step(g.q0, 0, g.theta0 + 1) || step(g.q0, 1, g.theta0 + 0);
-        } else {
-            hipError_t e = launch_cd_entangle(w, z, ngroups, ws->col_bits + g.q0, ws->col_bits + g.q1, prog.entangler, ws->stream);
-            if (e != hipSuccess) { rc = fail("cd_entangle launch failed: %s", hipGetErrorString(e)); }
-            else rc = step(g.q0, 0, g.theta0) || step(g.q0, 1, g.theta0 + 1) || step(g.q1, 0, g.theta0 + 2) ||
-                      step(g.q1, prog.entangler == AQC_CX ? 2 : 1, g.theta0 + 3);
-        }
-        if (rc) break;
-    }
-    if (!rc) {
-        double prod[2] = {0, 0};
-        rc = aqc_ws_vdot(ws, AQC_BUF_X, AQC_BUF_Z, prod);
-        if (!rc) {
-            const double a = std::hypot(prod[0], prod[1]) / dim;
-            *fobj = 1.0 - a * a;
-            hipError_t e = hipMemcpyAsync(thetas_io, d_theta_out, sizeof(double) * T, hipMemcpyDeviceToHost, ws->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
-            if (e != hipSuccess) rc = fail("theta download failed: %s", hipGetErrorString(e));
-        }
-    }
-    (void)hipStreamSynchronize(ws->stream);
-    return rc;
 }
 
 // One sweep of the wide walk for all lanes, enqueued: z = V(theta)^H U and w = I by the workspace's own launches, the walk's
@@ -285,21 +228,15 @@ static int cd_wide_sweep(aqc_ws* ws, const std::vector<aqc::CdSegHost>& segs, co
     return 0;
 }
 
-int aqc_ws_cd_minimize(aqc_ws* ws, const double* thetas0, int maxiter, int chunk, double dtheta_thr, double fobj_thr, double time_limit_s,
-                       int route, int max_steps, double* best_thetas, double* best_f, int64_t* nit, int32_t* status, double* profile) {
-    static_assert(AQC_CD_RUNNING == aqc::kCdRunning && AQC_CD_NORMAL == aqc::kCdNormal && AQC_CD_EARLY == aqc::kCdEarly &&
-                  AQC_CD_TIMEOUT == aqc::kCdTimeout, "the status words of the header and of the rule");
-    if (!ws || !thetas0 || !best_thetas || !best_f || !nit || !status || !profile) return fail("null argument");
-    if (maxiter < 1 || chunk < 1) return fail("maxiter and chunk must be positive");
-    if (route < AQC_CD_ROUTE_AUTO || route > AQC_CD_ROUTE_WIDE) return fail("unknown coordinate-descent route %d", route);
-    if (cd_checks(ws)) return 1;
+static int cd_wide_size_check(const aqc_ws* ws) {
+    if (ws->ctx->prog.n < 2 || ws->nbits > 30) return fail("coordinate descent serves 2 to 15 qubits");
+    return 0;
+}
+
+// The driver on a workspace and arguments that have passed the checks of its two callers below.
+static int cd_minimize_checked(aqc_ws* ws, const double* thetas0, int maxiter, int chunk, double dtheta_thr, double fobj_thr, double time_limit_s,
+                               bool persistent, int max_steps, double* best_thetas, double* best_f, int64_t* nit, int32_t* status, double* profile) {
     const Program& prog = ws->ctx->prog;
-    if (prog.n < 2 || ws->nbits > 30) return fail("coordinate descent serves 2 to 15 qubits");
-    const bool fits = aqc_ws_cd_fits_one_launch(ws) != 0;
-    if (route == AQC_CD_ROUTE_PERSISTENT && !fits)
-        return fail("the operands of this coordinate descent (2 x %zu KiB) do not fit one workgroup's LDS: the persistent route is not available",
-                    (ws->lane_elems * sizeof(double2)) >> 10);
-    const bool persistent = route == AQC_CD_ROUTE_PERSISTENT || (route == AQC_CD_ROUTE_AUTO && fits);
     const int B = ws->batch, T = prog.num_thetas();
     const size_t BT = (size_t)B * T;
     HIP_OK(hipSetDevice(ws->device));
@@ -346,6 +283,7 @@ int aqc_ws_cd_minimize(aqc_ws* ws, const double* thetas0, int maxiter, int chunk
             break;
         }
     }
+    if (!persistent && run_coef(ws, ws->d_thetas_own)) return 1;   // the last close kernel wrote them: what the workspace derived from the thetas is stale
     std::vector<int> h_int(2 * (size_t)B);
     HIP_OK(hipMemcpyAsync(best_thetas, ws->d_cd_best, sizeof(double) * BT, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(best_f, ws->d_cd_real, sizeof(double) * B, hipMemcpyDeviceToHost, st));
@@ -353,6 +291,43 @@ int aqc_ws_cd_minimize(aqc_ws* ws, const double* thetas0, int maxiter, int chunk
     HIP_OK(hipMemcpyAsync(h_int.data(), ws->d_cd_int, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     for (int b = 0; b < B; ++b) { status[b] = h_int[b]; nit[b] = h_int[B + b]; }
+    return 0;
+}
+
+int aqc_ws_cd_minimize(aqc_ws* ws, const double* thetas0, int maxiter, int chunk, double dtheta_thr, double fobj_thr, double time_limit_s,
+                       int route, int max_steps, double* best_thetas, double* best_f, int64_t* nit, int32_t* status, double* profile) {
+    static_assert(AQC_CD_RUNNING == aqc::kCdRunning && AQC_CD_NORMAL == aqc::kCdNormal && AQC_CD_EARLY == aqc::kCdEarly &&
+                  AQC_CD_TIMEOUT == aqc::kCdTimeout, "the status words of the header and of the rule");
+    if (!ws || !thetas0 || !best_thetas || !best_f || !nit || !status || !profile) return fail("null argument");
+    if (maxiter < 1 || chunk < 1) return fail("maxiter and chunk must be positive");
+    if (route < AQC_CD_ROUTE_AUTO || route > AQC_CD_ROUTE_WIDE) return fail("unknown coordinate-descent route %d", route);
+    if (cd_checks(ws) || cd_wide_size_check(ws)) return 1;
+    const bool fits = aqc_ws_cd_fits_one_launch(ws) != 0;
+    if (route == AQC_CD_ROUTE_PERSISTENT && !fits)
+        return fail("the operands of this coordinate descent (2 x %zu KiB) do not fit one workgroup's LDS: the persistent route is not available",
+                    (ws->lane_elems * sizeof(double2)) >> 10);
+    const bool persistent = route == AQC_CD_ROUTE_PERSISTENT || (route == AQC_CD_ROUTE_AUTO && fits);
+    return cd_minimize_checked(ws, thetas0, maxiter, chunk, dtheta_thr, fobj_thr, time_limit_s, persistent, max_steps, best_thetas, best_f, nit,
+                               status, profile);
+}
+
+int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io, double* fobj) {
+    if (!ws || !thetas_io || !fobj) return fail("null argument");
+    if (cd_checks(ws)) return 1;
+    const char* chain = getenv("AQC_CD_CHAIN");   // "1": the multi-launch route (the wide walk) even where one launch would do (cross-check, timing)
+    if (ws->batch != 1) return fail("aqc_ws_cd_sweep takes thetas_io[T] and one objective value: a single-lane workspace (aqc_ws_cd_sweeps serves lanes)");
+    if (aqc_ws_cd_fits_one_launch(ws) && !(chain && chain[0] == '1')) return aqc_ws_cd_sweeps(ws, thetas_io, fobj, 1, -1);
+    if (cd_wide_size_check(ws)) return 1;
+    // One sweep of the driver on the wide route, stop rules off.  The sweep's own thetas and value (profile[0]) go back, not the best
+    // ones: the close rule records a best value only below best_f, so a NaN sweep would come back as the start and inf.
+    const int T = ws->ctx->prog.num_thetas();
+    std::vector<double> best_thetas(T);
+    double best_f = 0;
+    int64_t nit = 0;
+    int32_t status = 0;
+    if (cd_minimize_checked(ws, thetas_io, 1, 1, 0.0, 0.0, 0.0, false, -1, best_thetas.data(), &best_f, &nit, &status, fobj)) return 1;
+    HIP_OK(hipMemcpyAsync(thetas_io, ws->d_cd_thetas, sizeof(double) * T, hipMemcpyDeviceToHost, ws->stream));
+    HIP_OK(hipStreamSynchronize(ws->stream));
     return 0;
 }
 

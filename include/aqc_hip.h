@@ -325,13 +325,16 @@ double aqc_svd_batch_core_ms(void);
 /* ---- coordinate descent (core_op_matrix.py:765  coord_descent_single_sweep(circ, thetas, target,
  * workspace)).  Square workspace (ncols == 2^n) with the target unitary in AQC_BUF_Y.  One
  * Gauss-Seidel sweep over all parameters of 1 - |<V,U>|^2/d^2; thetas are updated in place and
- * the objective at the end of the sweep is returned.  cx / cz entanglers only (:818-827). */
+ * the objective at the end of the sweep is returned.  cx / cz entanglers only (:818-827).
+ * A single-lane workspace (batch == 1).  Where aqc_ws_cd_fits_one_launch this is aqc_ws_cd_sweeps(ws, thetas_io, fobj, 1, -1);
+ * larger problems, and every problem where the environment has AQC_CD_CHAIN=1 (cross-checks, timing), take one sweep of the
+ * wide walk of aqc_ws_cd_minimize. */
 int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io /* [T] */, double* fobj);
 /* The same walk for EVERY lane of the workspace (lane = an independent problem: a random restart of the ansatz and / or its
  * own target in AQC_BUF_Y) and for `nsweeps` consecutive sweeps, as ONE persistent launch: a workgroup per lane keeps the two
  * d x d operands in LDS, re-derives z = V(theta)^H U at the start of every sweep (:806-810) and walks all parameters (:852-912)
  * without leaving the kernel.  Needs 2 d^2 16 B + 24 T B <= 160 KiB (up to 6 qubits; aqc_ws_cd_fits_one_launch); larger
- * problems keep the launch chain of aqc_ws_cd_sweep (one lane).  fobj[lane][s] = the objective at the end of sweep s (:917).
+ * problems are refused here: lanes beyond LDS are served by aqc_ws_cd_minimize.  fobj[lane][s] = the objective at the end of sweep s (:917).
  * max_steps >= 0 stops every sweep's walk after that many parameters (tests pin single steps with it); -1 = all. */
 int aqc_ws_cd_sweeps(aqc_ws* ws, double* thetas_io /* [batch][T] */, double* fobj /* [batch][nsweeps] */, int nsweeps, int max_steps);
 int aqc_ws_cd_fits_one_launch(const aqc_ws* ws);

@@ -211,10 +211,10 @@ def test_refused_gather_setup_keeps_the_registered_set(monkeypatch):
     _run(monkeypatch, "cx12_t10", FORCED, ops)
 
 
-def test_coordinate_descent_chain_leaves_no_stale_checkpoint(monkeypatch):
-    """aqc_ws_extra.cpp aqc_ws_cd_sweep: beyond 6 qubits the sweep is a chain of gate launches that rewrites X and Z in place,
-    after its aqc_ws_apply has left V^H's checkpoint of the old Z in ZW.  A gradient from a basis state afterwards must read Z
-    as the chain left it: the sparse route (z of the second stage from the checkpoint) agrees with the dense one."""
+def test_coordinate_descent_wide_walk_leaves_no_stale_checkpoint(monkeypatch):
+    """aqc_ws_extra.cpp aqc_ws_cd_sweep: beyond 6 qubits the sweep is the wide walk, launches that rewrite X and Z in place
+    after its V^H (run_apply) has left the checkpoint of the old Z in ZW.  A gradient from a basis state afterwards must read Z
+    as the walk left it: the sparse route (z of the second stage from the checkpoint) agrees with the dense one."""
     from aqc_research_amd import _lib
     from aqc_research_amd._lib import check, dptr
     from aqc_research_amd.engine import HipContext, Workspace

@@ -107,6 +107,77 @@ def test_wide_lane_of_a_batch_equals_the_solo_run_and_a_repeat_bit_for_bit(lanes
         assert np.array_equal(a[key][1], solo[key][0]), key
 
 
+def test_single_sweep_beyond_lds_is_one_sweep_of_the_wide_walk(lanes7):
+    """coord_descent_single_sweep at 7 qubits (no persistent launch) twice in a row follows the oracle's consecutive sweeps within the
+    whole-sweep bounds above, and its first call is cd_minimize(maxiter=1, route="wide", thresholds off) on a one-lane workspace bit
+    for bit: the call is that one by construction."""
+    from aqc_research_amd.core_op_matrix import coord_descent_single_sweep
+
+    circ, ths, us, ref = lanes7
+    t1, f1, t2, f2 = ref[0]
+    th = ths[0].copy()
+    g1 = coord_descent_single_sweep(circ, th, us[0], None)
+    first = th.copy()
+    g2 = coord_descent_single_sweep(circ, th, us[0], None)
+    print(abs(g1 - f1), abs(g2 - f2), maxdiff(th, t2))
+    assert abs(g1 - f1) < 1e-8 and abs(g2 - f2) < 1e-7 and maxdiff(th, t2) < 1e-7
+    assert f2 < f1 < 1.0
+    res = _minimize(circ, ths[0], us[0], 1, route="wide", fobj_thr=0, dtheta_thr=0)
+    assert np.array_equal(first, res["thetas"][0]) and g1 == res["profile"][0, 0]
+
+
+def test_workspace_follows_the_thetas_a_wide_sweep_left(lanes7):
+    """The close kernel writes the sweep's thetas over the workspace's own on the device, and the driver announces them when it returns:
+    a V^H asked of the workspace afterwards, with no set_thetas in between, is V(thetas after the sweep)^H, with nothing in it that was
+    built for the thetas at the sweep's start."""
+    from aqc_research_amd.engine import BUF_Y, BUF_Z, HipContext, Workspace
+
+    circ, ths, us, _ = lanes7
+    ws = Workspace(HipContext.of(circ), batch=1, ncols=circ.dimension)
+    try:
+        ws.upload(BUF_Y, us[:1])
+        res = ws.cd_minimize(ths[:1], 1, route="wide", fobj_thr=0.0, dtheta_thr=0.0)
+        ws.apply(True, BUF_Y, BUF_Z)
+        z = ws.download(BUF_Z)[0]
+    finally:
+        ws.close()
+    assert maxdiff(z, orc.v_dagger_mul_mat(circ, res["thetas"][0], us[0])) < TOL
+
+
+def test_single_sweep_refusals(lanes7):
+    """aqc_ws_cd_sweep keeps its contract beyond LDS: one lane, cx / cz, a square workspace."""
+    from aqc_research_amd import ParametricCircuit, _lib
+    from aqc_research_amd.core_op_matrix import coord_descent_single_sweep
+    from aqc_research_amd.engine import BUF_Y, HipContext, Workspace, live_buffers
+
+    circ, ths, us, _ = lanes7
+    d = circ.dimension
+    before = live_buffers()
+    fobj = np.zeros(1)
+    for batch, ncols, msg in ((2, d, "single-lane workspace"), (1, d // 2, "square workspace")):
+        ws = Workspace(HipContext.of(circ), batch=batch, ncols=ncols)
+        try:
+            ws.upload(BUF_Y, np.ascontiguousarray(np.broadcast_to(us[0][:, :ncols], (batch, d, ncols))))
+            th = ths[0].copy()
+            with pytest.raises(RuntimeError, match=msg):
+                _lib.check(ws._L.aqc_ws_cd_sweep(ws.handle, _lib.dptr(th), _lib.dptr(fobj)))
+            assert np.array_equal(th, ths[0])
+        finally:
+            ws.close()
+    assert live_buffers() == before
+    cp = ParametricCircuit(7, "cp", circ.blocks)
+    with pytest.raises(NotImplementedError, match="CPhase"):
+        coord_descent_single_sweep(cp, ths[0].copy(), us[0], None)
+    ws = Workspace(HipContext.of(cp), batch=1, ncols=d)
+    try:
+        ws.upload(BUF_Y, us[:1])
+        with pytest.raises(RuntimeError, match="CPhase"):
+            _lib.check(ws._L.aqc_ws_cd_sweep(ws.handle, _lib.dptr(ths[0].copy()), _lib.dptr(fobj)))
+    finally:
+        ws.close()
+    assert live_buffers() == before
+
+
 @pytest.fixture(scope="module")
 def lanes5():
     n, lanes = 5, 3
@@ -119,7 +190,7 @@ def lanes5():
 
 
 def test_routes_agree_on_five_qubits(lanes5):
-    """One sweep, the wide walk forced where the persistent launch would do: 1e-8, the bound of the launch chain against it."""
+    """One sweep, the wide walk forced where the persistent launch would do: 1e-8, the bound of a whole sweep against the oracle."""
     circ, ths, us = lanes5
     p = _minimize(circ, ths, us, 1, route="persistent")
     w = _minimize(circ, ths, us, 1, route="wide")

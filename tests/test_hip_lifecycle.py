@@ -142,7 +142,7 @@ def _coordinate_descent(monkeypatch, rng):
     ws.upload(BUF_Y, np.linalg.qr(rng.standard_normal((d, d)) + 1j * rng.standard_normal((d, d)))[0][None])
     th, fobj = orc.rand_thetas(circ.num_thetas, rng), np.zeros(2)
     _lib.check(ws._L.aqc_ws_cd_sweeps(ws.handle, _lib.dptr(th), _lib.dptr(fobj), 2, -1))
-    monkeypatch.setenv("AQC_CD_CHAIN", "1")   # the launch chain, with its call-scoped theta buffer
+    monkeypatch.setenv("AQC_CD_CHAIN", "1")   # the wide walk: the driver's buffers belong to the workspace
     _lib.check(ws._L.aqc_ws_cd_sweep(ws.handle, _lib.dptr(th), _lib.dptr(fobj)))
     return ctx, ws
 

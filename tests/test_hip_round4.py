@@ -264,7 +264,8 @@ def test_coordinate_descent_one_launch_lanes_and_sweeps(monkeypatch):
     """aqc_ws_cd_sweeps: lanes = random restarts and their own targets, several sweeps in one launch (z = V^H U re-derived in
     the kernel at the start of each, core_op_matrix.py:806-810).  Every lane follows the oracle's consecutive single sweeps
     (full sweeps: rounding is amplified along ~T sequential steps, hence 1e-8 after the first and 1e-7 after the second),
-    the reference-signature single-lane call gives the same numbers, and so does the launch chain it replaced."""
+    the reference-signature single-lane call gives the same numbers, and so does the wide walk (operands in HBM) forced onto
+    this size.  Beyond 6 qubits the reference-signature call is the wide walk: the oracle's sweep at 1e-8."""
     from aqc_research_amd.core_op_matrix import coord_descent_single_sweep, coord_descent_sweeps
 
     n, lanes = 5, 5
@@ -284,7 +285,7 @@ def test_coordinate_descent_one_launch_lanes_and_sweeps(monkeypatch):
     g1 = coord_descent_single_sweep(circ, one, us[1], None)
     g2 = coord_descent_single_sweep(circ, one, us[1], None)
     assert abs(g1 - f[1, 0]) < 1e-12 and abs(g2 - f[1, 1]) < 1e-10 and maxdiff(one, got[1]) < 1e-10
-    monkeypatch.setenv("AQC_CD_CHAIN", "1")              # the launch chain (what problems beyond 6 qubits still use)
+    monkeypatch.setenv("AQC_CD_CHAIN", "1")              # the multi-launch route: the wide walk (what problems beyond 6 qubits use)
     chain = ths[1].copy()
     c1 = coord_descent_single_sweep(circ, chain, us[1], None)
     assert abs(c1 - f[1, 0]) < 1e-8
@@ -296,8 +297,9 @@ def test_coordinate_descent_one_launch_lanes_and_sweeps(monkeypatch):
     big, thb, ub, _ = _cd_problem(7, "spin", 8, 78)
     with pytest.raises(RuntimeError, match="do not fit"):
         coord_descent_sweeps(big, thb.copy(), ub, 1)
-    fb = coord_descent_single_sweep(big, thb, ub, None)   # ... while the reference-signature call runs it on the chain
-    assert 0.0 < fb < 1.0
+    tb, fo = orc.coord_descent_single_sweep(big, thb, ub)
+    fb = coord_descent_single_sweep(big, thb, ub, None)   # ... while the reference-signature call runs it on the wide walk
+    assert 0.0 < fb < 1.0 and abs(fb - fo) < 1e-8 and maxdiff(thb, tb) < 1e-8
 
 
 def test_jacobi_svd_on_a_graded_two_site_tensor_that_did_not_converge():
