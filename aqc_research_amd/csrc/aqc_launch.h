@@ -311,6 +311,27 @@ int gate_dot_parts(int n, size_t ncols, int kind);
 hipError_t launch_gate_dot(const void* w, const void* z, int n, size_t ncols, int kind, int q0, int q1, void* partial, void* out,
                            hipStream_t s);
 
+// aqc_xxz.hip (matrix-free XXZ Hamiltonian and the Chebyshev step of exp(-iHt); rules: aqc_xxz_rule.h)
+constexpr int kXxzThreads = 256, kXxzTileBits = 11;   // a tile = 2^min(n, 11) amplitudes = at most 32 KiB of LDS
+struct XxzArgs {
+    int n, tile_bits, lanes;       // tile_bits = xxz_tile_bits(n); grid (2^(n - tile_bits), lanes)
+    double delta;
+    const double2* cur;            // the vector whose neighbours are read; lane l at cur + l * cur_stride (0: one state for all lanes)
+    size_t cur_stride;
+    const double2* prev;           // step: T_{k-1}, lane l at prev + l * prev_stride (not read by the first step)
+    size_t prev_stride;
+    double2* next;                 // mul: H cur; step: T_{k+1} -- [lanes][2^n]; may be prev
+    double2* out;                  // step: the running sum [lanes][2^n]
+    const double2* coef;           // step: c_k of every lane, [lanes]
+    const double2* coef0;          // first step: c_0 of every lane
+    double scale;                  // step: 1/R (first) or 2/R
+    int first;                     // step: next = scale H cur, out = c_0 cur + c_1 next
+    double* partial;               // energy: [lanes][tiles]
+};
+int xxz_tile_bits(int n);
+hipError_t launch_xxz_mul(const XxzArgs& a, hipStream_t s);
+hipError_t launch_xxz_step(const XxzArgs& a, hipStream_t s);
+hipError_t launch_xxz_energy(const XxzArgs& a, double* energy /* [lanes] */, hipStream_t s);   // partials, then their fixed-order sum
 
 // aqc_api.cpp: thread-local message behind aqc_last_error(); returns 1
 int set_error(const std::string& msg);

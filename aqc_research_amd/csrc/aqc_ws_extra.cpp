@@ -4,6 +4,7 @@
 #include <chrono>
 
 #include "aqc_cd_rule.h"
+#include "aqc_xxz_rule.h"
 
 using namespace aqc;
 
@@ -100,6 +101,109 @@ int aqc_gate_dot(int device, int n, int64_t ncols, int kind, int q0, int q1, con
     HIP_OK(launch_gate_dot(dw, dz, n, (size_t)ncols, kind, q0, q1, parts + 1, parts, nullptr));
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(out, parts, sizeof(double2), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- matrix-free XXZ Hamiltonian and exact evolution (one-shot, host pointers; kernels: aqc_xxz.hip) -------------
+
+namespace {
+
+int xxz_args_ok(int device, int n, int lanes, double delta) {
+    if (n < kXxzMinQubits || n > kXxzMaxQubits || lanes < 1 || ((size_t)lanes << n) > ((size_t)1 << kMaxBits))
+        return fail("invalid state shape: %d lanes of %d qubits", lanes, n);
+    if (!std::isfinite(delta)) return fail("delta is not finite");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: the aqc_hip path has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail("device out of range");
+    return 0;
+}
+
+XxzArgs xxz_args(int n, int lanes, double delta) {
+    XxzArgs a{};
+    a.n = n; a.tile_bits = xxz_tile_bits(n); a.lanes = lanes; a.delta = delta;
+    return a;
+}
+
+}  // namespace
+
+int aqc_xxz_mul_vec(int device, int n, int lanes, double delta, const double* src, double* dst) {
+    if (!src || !dst) return fail("null argument");
+    if (xxz_args_ok(device, n, lanes, delta)) return 1;
+    HIP_OK(hipSetDevice(device));
+    const size_t count = (size_t)lanes << n, bytes = sizeof(double2) * count;
+    DevBuf<double2> d_src, d_dst;
+    if (d_src.alloc(count) || d_dst.alloc(count)) return 1;
+    HIP_OK(hipMemcpy(d_src, src, bytes, hipMemcpyHostToDevice));
+    XxzArgs a = xxz_args(n, lanes, delta);
+    a.cur = d_src; a.cur_stride = (size_t)1 << n; a.next = d_dst;
+    HIP_OK(launch_xxz_mul(a, nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(dst, d_dst, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int aqc_xxz_energy(int device, int n, int lanes, double delta, const double* src, double* energy) {
+    if (!src || !energy) return fail("null argument");
+    if (xxz_args_ok(device, n, lanes, delta)) return 1;
+    HIP_OK(hipSetDevice(device));
+    const size_t count = (size_t)lanes << n, ntiles = (size_t)1 << (n - xxz_tile_bits(n));
+    DevBuf<double2> d_src;
+    DevBuf<double> d_part, d_energy;
+    if (d_src.alloc(count) || d_part.alloc(ntiles * (size_t)lanes) || d_energy.alloc((size_t)lanes)) return 1;
+    HIP_OK(hipMemcpy(d_src, src, sizeof(double2) * count, hipMemcpyHostToDevice));
+    XxzArgs a = xxz_args(n, lanes, delta);
+    a.cur = d_src; a.cur_stride = (size_t)1 << n; a.partial = d_part;
+    HIP_OK(launch_xxz_energy(a, d_energy, nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(energy, d_energy, sizeof(double) * (size_t)lanes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int aqc_xxz_evolve(int device, int n, int lanes, int shared_src, double delta, const double* times, const double* src, double* dst,
+                   int32_t* terms_out) {
+    if (!times || !src || !dst) return fail("null argument");
+    if (xxz_args_ok(device, n, lanes, delta)) return 1;
+    for (int l = 0; l < lanes; ++l)
+        if (!std::isfinite(times[l])) return fail("evolution time of lane %d is not finite", l);
+    // the series of every lane: c_k = 2 (-i)^k J_k(R t), table [k][lane], zero beyond a lane's own length
+    const double radius = xxz_radius(n, delta);
+    std::vector<std::vector<double>> bessel((size_t)lanes);
+    int kmax = 0;
+    for (int l = 0; l < lanes; ++l) {
+        const int k = xxz_series(std::fabs(radius * times[l]), bessel[(size_t)l]);
+        if (k < 0) return fail("lane %d: |R t| = %g needs more than %d terms", l, std::fabs(radius * times[l]), (int)kXxzMaxTerms);
+        if (terms_out) terms_out[l] = k;
+        kmax = std::max(kmax, k);
+    }
+    std::vector<double2> coef((size_t)(kmax + 1) * (size_t)lanes, make_double2(0.0, 0.0));
+    for (int l = 0; l < lanes; ++l) {
+        const std::vector<double>& j = bessel[(size_t)l];
+        for (size_t k = 0; k < j.size(); ++k) {
+            double2& c = coef[k * (size_t)lanes + (size_t)l];
+            xxz_coefficient((int)k, j[k], times[l] < 0.0, c.x, c.y);
+        }
+    }
+    HIP_OK(hipSetDevice(device));
+    const size_t dim = (size_t)1 << n, count = (size_t)lanes << n, src_count = shared_src ? dim : count;
+    DevBuf<double2> d_src, d_a, d_b, d_out, d_coef;
+    if (d_src.alloc(src_count) || d_a.alloc(count) || d_b.alloc(count) || d_out.alloc(count) || d_coef.upload(coef)) return 1;
+    HIP_OK(hipMemcpy(d_src, src, sizeof(double2) * src_count, hipMemcpyHostToDevice));
+    XxzArgs a = xxz_args(n, lanes, delta);
+    a.out = d_out; a.coef0 = d_coef;
+    const size_t src_stride = shared_src ? 0 : dim;
+    double2 *pa = d_a, *pb = d_b;
+    for (int k = 1; k <= kmax; ++k) {   // T_k = (2/R) H T_{k-1} - T_{k-2} into the buffer of T_{k-2}; out += c_k T_k
+        a.coef = static_cast<const double2*>(d_coef) + (size_t)k * (size_t)lanes;
+        a.first = k == 1;
+        a.scale = (k == 1 ? 1.0 : 2.0) / radius;
+        if (k == 1) { a.cur = d_src; a.cur_stride = src_stride; a.prev = nullptr; a.prev_stride = 0; a.next = pa; }
+        else if (k == 2) { a.cur = pa; a.cur_stride = dim; a.prev = d_src; a.prev_stride = src_stride; a.next = pb; }
+        else if (k & 1) { a.cur = pb; a.cur_stride = dim; a.prev = pa; a.prev_stride = dim; a.next = pa; }
+        else { a.cur = pa; a.cur_stride = dim; a.prev = pb; a.prev_stride = dim; a.next = pb; }
+        HIP_OK(launch_xxz_step(a, nullptr));
+    }
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(dst, d_out, sizeof(double2) * count, hipMemcpyDeviceToHost));
     return 0;
 }
 

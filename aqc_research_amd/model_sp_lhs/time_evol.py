@@ -4,7 +4,8 @@ ASP time-evolution driver on top of the HIP objectives -- the hori
 
 * per time horizon a pair of targets (``target_states.py:373-455``): the *ground truth* ``|t1_gt>`` (Trotter circuit with
   ``precise_multiplier()`` = 10x the steps) and the *reference* ``|t1>`` (the plain number of steps), both synthesised on the
-  device with the path's own ``V|ini>`` kernel (``trotter.trotter_state``) or, beyond dense reach, on the native MPS engine;
+  device with the path's own ``V|ini>`` kernel (``trotter.trotter_state``) or, beyond dense reach, on the native MPS engine
+  (``UserOptions.ground_truth = "exact"``: ``|t1_gt>`` is exp(-iHt)|ini> itself, ``xxz.xxz_evolve``, within dense reach);
 * the fidelity threshold derived from them (``_calc_fidelity_threshold``, ``time_evol_best_init.py:118-140``);
 * ``_model_function`` (``:143-218``): TrotterAnsatz of ``num_layers`` layers, Trotter initial point, objective picked by
   ``opts.objective`` in {``sur_max``, ``sur_fast_mps_trotter``} (``_create_objective``, ``:64-115``), L-BFGS under
@@ -70,7 +71,10 @@ class UserOptions:
         self.theta_jitter = 0.1            # restart s > 0 starts from Trotter angles + jitter * pi * U(-1, 1)
         self.vectorised_lbfgs = False      # restarts driven by ONE vectorised L-BFGS (batched_optimizer.py) instead of scipy per lane
         self.device_lbfgs = False          # ... and that L-BFGS resident on the device (aqc_ws_lbfgs), thetas never leave HBM
+        self.ground_truth = "trotter"      # |t1_gt>: "trotter" (10x the steps, as the reference) or "exact" (exp(-iHt)|ini> by xxz.xxz_evolve)
         self.__dict__.update(kw)
+        if self.ground_truth not in ("trotter", "exact"):
+            raise ValueError(f"ground_truth must be 'trotter' or 'exact', got {self.ground_truth!r}")
         if self.trotter_steps is None:
             self.trotter_steps = (1 + np.arange(self.num_horizons)) * int(self.trotter_steps_per_horizon)
         if self.evol_times is None:
@@ -128,10 +132,26 @@ def _evolved_state(opts: UserOptions, circ, thetas: np.ndarray, trunc_thr: float
 
 def generate_target(opts: UserOptions, my_id: int) -> TargetState:
     """|t1_gt> = precise_Trotter(t)|ini>, |t1> = reference_Trotter(t)|ini> (generate_classic_target /
-    generate_mps_target, target_states.py:373-455,458-540): the Trotter circuit is the ansatz itself at its Trotter angles."""
+    generate_mps_target, target_states.py:373-455,458-540): the Trotter circuit is the ansatz itself at its Trotter angles.
+
+    With ``opts.ground_truth == "exact"`` |t1_gt> is exp(-iHt)|ini> itself, by the Chebyshev series of ``xxz.xxz_evolve`` from the
+    basis state ``opts.ini_state_index()``: a dense vector, or -- ``use_mps`` -- a ``DenseBackedMPS`` of it up to 24 qubits (beyond,
+    no dense state exists: ValueError).  |t1> stays the Trotter state.  The Trotter states here come from ``v_mul_vec`` and lack
+    ``trotter_global_phase``; the exact state carries the phase of exp(-iHt).  Fidelities do not see the difference; comparisons of
+    amplitudes do (``trotter_state(..., with_global_phase=True)`` is the Trotter state to compare amplitudes with)."""
     n, steps, t = opts.num_qubits, int(opts.trotter_steps[my_id]), float(opts.evol_times[my_id])
     states = []
-    for num_steps in (steps * precise_multiplier(), steps):
+    exact = opts.ground_truth == "exact"
+    if exact:
+        if opts.use_mps and n > _DENSE_MAX_QUBITS:
+            raise ValueError(f"ground_truth='exact' needs a dense state: at most {_DENSE_MAX_QUBITS} qubits with an MPS objective")
+        from ..xxz import xxz_evolve
+
+        ini = np.zeros(1 << n, dtype=np.complex128)
+        ini[opts.ini_state_index()] = 1
+        vec = xxz_evolve(ini, float(opts.delta), t, device=opts.device)
+        states.append(DenseBackedMPS(vec, opts.trunc_thr_target) if opts.use_mps else vec)
+    for num_steps in ((steps,) if exact else (steps * precise_multiplier(), steps)):
         if opts.use_mps:
             circ = trotter_ansatz(n, num_steps, opts.second_order_trotter)
             th = init_ansatz_to_trotter(circ, np.zeros(circ.num_thetas), evol_time=t, delta=opts.delta)

@@ -167,3 +167,64 @@ def make_hamiltonian(num_qubits: int, delta: float) -> np.ndarray:
     for i in range(num_qubits - 1):
         h += two(sx, i) + two(sy, i) + delta * two(sz, i)
     return -0.25 * h
+
+
+class XXZHamiltonian:
+    """The Hamiltonian of ``make_hamiltonian`` by its two numbers.  ``exact_evolution`` applies it without a matrix on the device
+    (``xxz.xxz_evolve``), up to 30 qubits; ``matrix()`` is the dense form for small n."""
+
+    def __init__(self, num_qubits: int, delta: float):
+        if not (isinstance(num_qubits, (int, np.integer)) and 2 <= num_qubits <= 30):
+            raise ValueError("num_qubits must be an integer in [2, 30]")
+        if not np.isfinite(float(delta)):
+            raise ValueError("delta must be finite")
+        self.num_qubits, self.delta = int(num_qubits), float(delta)
+
+    def matrix(self) -> np.ndarray:
+        return make_hamiltonian(self.num_qubits, self.delta)
+
+
+def exact_evolution(hamiltonian, ini_state, evol_time: float, device: Optional[int] = None) -> np.ndarray:
+    """exp(-i H evol_time)|ini_state> (exact_evolution, trotter.py:233-266, same argument order).
+
+    A dense ndarray ``hamiltonian`` takes the reference's own route, ``scipy.linalg.expm`` on the host (no GPU; small n only).
+    An ``XXZHamiltonian`` takes the Chebyshev series on the device.  ``ini_state``: a complex vector, an ``int`` basis index, or a
+    preparation circuit of X gates acting on |0> (resolved with ``basis_mask_of_circuit``; no circuit is simulated)."""
+    dense = isinstance(hamiltonian, np.ndarray)
+    if dense:
+        if hamiltonian.ndim != 2 or hamiltonian.shape[0] != hamiltonian.shape[1]:
+            raise ValueError("expects a square Hamiltonian matrix")
+        dim = int(hamiltonian.shape[0])
+        num_qubits = dim.bit_length() - 1
+        if dim < 2 or (1 << num_qubits) != dim:
+            raise ValueError("the dimension of the Hamiltonian must be a power of two")
+    elif isinstance(hamiltonian, XXZHamiltonian):
+        num_qubits = hamiltonian.num_qubits
+        dim = 1 << num_qubits
+    else:
+        raise TypeError("hamiltonian: expects a dense matrix or an XXZHamiltonian")
+    if isinstance(ini_state, np.ndarray):
+        vec = np.ascontiguousarray(ini_state, dtype=np.complex128)
+        if vec.shape != (dim,):
+            raise ValueError(f"ini_state: expected a vector of {dim} amplitudes, got shape {ini_state.shape}")
+    else:
+        if isinstance(ini_state, (int, np.integer)):
+            index = int(ini_state)
+        else:
+            from ..objective_base import basis_mask_of_circuit
+
+            index = basis_mask_of_circuit(ini_state, num_qubits)
+        if not 0 <= index < dim:
+            raise ValueError("ini_state: basis index out of range")
+        vec = np.zeros(dim, dtype=np.complex128)
+        vec[index] = 1
+    evol_time = float(evol_time)
+    if not np.isfinite(evol_time):
+        raise ValueError("evol_time must be finite")
+    if dense:
+        from scipy.linalg import expm
+
+        return np.matmul(expm((-1.0j * evol_time) * hamiltonian), vec)
+    from ...xxz import xxz_evolve
+
+    return xxz_evolve(vec, hamiltonian.delta, evol_time, device=device)

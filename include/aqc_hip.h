@@ -208,6 +208,20 @@ int aqc_gate_2q(int device, int n, int64_t ncols, int ctrl, int targ, const doub
 int aqc_gate_dot(int device, int n, int64_t ncols, int kind, int q0, int q1, const double* w, const double* z,
                  double* out /* 1 c128 */);
 
+/* ---- XXZ chain Hamiltonian, matrix-free, and exact time evolution by a Chebyshev series: one-shot calls over [lanes][2^n] c128
+ * state vectors in HOST memory (qubit q = index bit q), 2 <= n <= 30; dst may equal src.
+ *   H = -1/4 sum_i (X_i X_i+1 + Y_i Y_i+1 + delta Z_i Z_i+1), open chain  (make_hamiltonian, trotter.py:183-230, without the matrix)
+ *   exp(-i H t) psi = sum_k c_k T_k(H / R) psi,  R = (n - 1)(1/2 + |delta| / 4),  c_0 = J_0(R t),  c_k = 2 (-i)^k J_k(R t);
+ *   the series ends at the smallest K >= ceil(|R t|) + 20 with |J_K| <= 1e-17: exact to rounding where the reference's
+ *   exact_evolution (trotter.py:233-266, a dense expm) ends near 12 qubits.  The Bessel values are computed by the library
+ *   (csrc/aqc_xxz_rule.h); one kernel launch per term; lanes with different times share the launches.
+ * aqc_xxz_energy: energy[l] = Re <src_l| H |src_l>, summed in a fixed order.
+ * aqc_xxz_evolve: dst[l] = exp(-i H times[l]) src[shared_src ? 0 : l]; terms_out (may be NULL) receives K per lane. */
+int aqc_xxz_mul_vec(int device, int n, int lanes, double delta, const double* src, double* dst);
+int aqc_xxz_energy(int device, int n, int lanes, double delta, const double* src, double* energy /* [lanes] f64 */);
+int aqc_xxz_evolve(int device, int n, int lanes, int shared_src, double delta, const double* times /* [lanes] */, const double* src,
+                   double* dst, int32_t* terms_out);
+
 /* ---- device-resident MPS with truncated 2-qubit gates: the arithmetic the reference hands to qiskit-aer's
  * matrix_product_state simulator (mps_operations.py:216-298 mps_from_circuit / qcircuit_mul_mps; gate level:
  * mps_dot_objective.py:245-468).  Qiskit MPS format in and out (mps_operations.py:33): `dims` = n+1 bond
