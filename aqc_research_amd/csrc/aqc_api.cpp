@@ -168,7 +168,8 @@ int aqc_plan_projected(aqc_ctx* ctx, int tile_bits, int low_bits, int32_t* info)
         if (cand.stages.size() < best.stages.size()) best = cand;
     }
     lower_plan(prog, best, tmp.sweep, 4, true, true);
-    tmp.sparse_enabled = true;
+    tmp.sw = read_switches();
+    tmp.sw.sparse_sweep = 1;
     tmp.inv_mirrored = tmp.sweep.v3 && tmp.sweep.plan.stages.size() >= 2;
     proj_plan(&tmp, low_bits);
     const int rc = aqc_ws_projected_info(&tmp, info);
@@ -207,19 +208,19 @@ static int ws_decide(aqc_ws* ws, int tile_bits_apply, int tile_bits_sweep) {
     aqc_ctx* ctx = ws->ctx;
     const Program& prog = ctx->prog;
     const int batch = ws->batch;
+    const Switches& sw = ws->sw = read_switches();   // the only read of the environment in a workspace's life
     // Kernel family and tile size.  Throughput regime (enough tiles x lanes to give every CU >= 1 workgroup of
     // the largest tile): register-blocked kernels on 2^12 / 2^13 tiles.  Latency regime (few lanes): the
     // per-gate-group kernels on small tiles, where all threads of a workgroup share every gate group and the
-    // serial chain per launch is short.  AQC_KERNEL_V2 = 0 / 1 forces a family, AQC_TILE_BITS_* a tile size.
-    const int low_bits = env_int("AQC_LOW_BITS", 3);
-    int ka = tile_bits_apply > 0 ? tile_bits_apply : env_int("AQC_TILE_BITS_APPLY", 0);
-    int ks = tile_bits_sweep > 0 ? tile_bits_sweep : env_int("AQC_TILE_BITS_SWEEP", 0);
+    // serial chain per launch is short.  The family and tile-size switches force either.
+    const int low_bits = (int)sw.low_bits;
+    int ka = tile_bits_apply > 0 ? tile_bits_apply : (int)sw.tile_bits_apply;
+    int ks = tile_bits_sweep > 0 ? tile_bits_sweep : (int)sw.tile_bits_sweep;
     // Kernel family.  Default: the matrix-core kernels (family 3) whenever the lane has at least 2^8 elements (16 chunks
     // x 16 register-bit values per MFMA group); they won every measured workload, throughput and single-evaluation
     // latency alike (profiles/r02_family_comparison.txt).  Smaller registers run the per-group kernels.
-    // AQC_KERNEL_FAMILY = 1 (per-group) | 2 (register-blocked VALU) | 3 forces a family (tests run every family);
-    // AQC_KERNEL_V2 = 0 / 1 is the older spelling of 1 / 2.
-    const int family = env_int("AQC_KERNEL_FAMILY", env_int("AQC_KERNEL_V2", -1) >= 0 ? env_int("AQC_KERNEL_V2", -1) + 1 : 0);
+    // The family switch (1 per-group | 2 register-blocked VALU | 3) forces one; tests run every family.
+    const int family = (int)sw.kernel_family;
     if (family < 0 || family > 3) return fail("AQC_KERNEL_FAMILY must be 1 (per-group), 2 (register-blocked) or 3 (matrix cores)");
     const bool want_v3 = (family == 3 || family == 0) && ws->nbits >= 8;
     const int force_v2 = family == 3 ? 0 : (family ? family - 1 : -1);
@@ -248,7 +249,7 @@ static int ws_decide(aqc_ws* ws, int tile_bits_apply, int tile_bits_sweep) {
     if (ks <= 0) ks = pick(12);
     ka = std::min(std::min(ka, 13), ws->nbits);
     ks = std::min(std::min(ks, 12), ws->nbits);
-    ws->threads = env_int("AQC_THREADS", 0);
+    ws->threads = (int)sw.threads;
     if (ws->threads <= 0) ws->threads = std::min(256, std::max(64, 1 << (std::min(ka, ks) - 2)));
     if (ws->threads < 64 || ws->threads > 512 || ws->threads % 64) return fail("AQC_THREADS must be a multiple of 64 in [64, 512]");
 
@@ -278,31 +279,21 @@ static int ws_decide(aqc_ws* ws, int tile_bits_apply, int tile_bits_sweep) {
                [&](HostPlan& fresh) { lower_plan(prog, best_plan(k, inverse), fresh, reg_bits, dots, want_v3); });
     };
     cached_plan(2, ka, false, (want_v2 || want_v3) ? 4 : 0, false, ws->fwd);
-    cached_plan(1, ks, false, want_v3 ? 4 : (want_v2 ? (env_int("AQC_SWEEP_REG_BITS", 4) == 3 ? 3 : 4) : 0), true, ws->sweep);
+    cached_plan(1, ks, false, want_v3 ? 4 : (want_v2 ? (sw.sweep_reg_bits == 3 ? 3 : 4) : 0), true, ws->sweep);
     // V^H: on the matrix-core path with equal tile sizes, the SWEEP's plan walked backwards (same stages, same sub-stages, same
     // cost), so that the states between its stages are the states z takes between the sweep's stages -- see aqc_ws_sweep.cpp
-    ws->inv_mirrored = want_v3 && ka == ks && ws->sweep.v3 && ws->sweep.plan.stages.size() >= 2 && env_int("AQC_MIRROR_PLAN", 1) != 0;
+    ws->inv_mirrored = want_v3 && ka == ks && ws->sweep.v3 && ws->sweep.plan.stages.size() >= 2 && sw.mirror_plan != 0;
     if (ws->inv_mirrored)
         cached({3, ws->col_bits, ks, low_bits, 4, 0, 1}, ws->inv,
                [&](HostPlan& fresh) { lower_plan(prog, mirror_plan(ws->sweep.plan), fresh, 4, false, true, true); });
     else
         cached_plan(0, ka, true, (want_v2 || want_v3) ? 4 : 0, false, ws->inv);
-    ws->sparse_enabled = env_int("AQC_SPARSE_SWEEP", 1) != 0;
-    ws->sparse_min_items = env_int("AQC_SPARSE_MIN_ITEMS", 512);
-    ws->lazy_z_enabled = env_int("AQC_LAZY_Z", 1) != 0;
-    ws->r_only_enabled = env_int("AQC_R_ONLY_LAST", 1) != 0;
-    ws->r_only_max_subs = env_int("AQC_R_ONLY_MAX_SUBS", 12);
-    ws->proj_vdag_enabled = env_int("AQC_PROJECTED_VDAG", 1) != 0;
-    ws->proj_fused_enabled = env_int("AQC_PROJECTED_FUSED", 1) != 0;
-    ws->proj_pairs_enabled = env_int("AQC_PROJECTED_PAIRS", 1) != 0;
-    ws->proj_vdag_min_elems = (long long)env_int("AQC_PROJECTED_VDAG_MIN_ELEMS", 1 << 24);
-    ws->skipw_enabled = env_int("AQC_SKIP_ZERO_W", 0) != 0;   // (measured slower than multiplying the zeros: opt-in, see sweep_mfma_kernel)
     for (DevPlan* p : {&ws->fwd, &ws->inv, &ws->sweep}) {
         const std::string err = check_plan(prog, p->plan);
         if (!err.empty()) return fail("planner produced an invalid plan: %s", err.c_str());
     }
     proj_plan(ws, low_bits);   // the sweep's later stages on a virtual register, where the plan allows (aqc_ws_project.cpp)
-    if (env_int("AQC_VERBOSE", 0) && want_v3)
+    if (sw.verbose && want_v3)
         fprintf(stderr, "aqc_hip: matrix-core kernels, tiles 2^%d (V / V^H, %d workgroups per CU) / 2^%d (sweep, %d per CU), sub-stages %zu / %zu / %zu\n",
                 ws->inv.k, mfma_occupancy(ws->inv.k, false), ws->sweep.k, mfma_occupancy(ws->sweep.k, true), ws->fwd.h_subs3.size(),
                 ws->inv.h_subs3.size(), ws->sweep.h_subs3.size());
@@ -337,7 +328,7 @@ static SlotTables ws_slot_tables(aqc_ws* ws) {
         }
     }
     t.slot_theta.assign((size_t)std::max(ws->nslots, 1), -1);
-    ws->grads_direct = ws->sweep.v3 && T > 0 && env_int("AQC_GRADS_DIRECT", 1) != 0;
+    ws->grads_direct = ws->sweep.v3 && T > 0 && ws->sw.grads_direct != 0;
     for (int th = 0; th < T; ++th) {
         if (t.theta_slots[2 * th] < 0 || t.theta_slots[2 * th + 1] >= 0) { ws->grads_direct = false; break; }
         t.slot_theta[t.theta_slots[2 * th]] = th;
@@ -354,7 +345,7 @@ static int ws_upload_ujobs(aqc_ws* ws) {
     size_t n_vdag_sweep = 0;   // jobs of [V^H | sweep | virtual sweep]: what a reader of everything launches (V's jobs run on their own)
     DevPlan* vsw = ws->proj.ok ? &ws->proj.vsw : nullptr;
     const int nsw = ws->sweep.v3 ? (int)ws->sweep.h_subs3.size() : 0;
-    ws->ujobs_mirror = ws->inv_mirrored && ws->inv.v3 && (int)ws->inv.h_subs3.size() == nsw && env_int("AQC_UBUILD_MIRROR", 1) != 0;
+    ws->ujobs_mirror = ws->inv_mirrored && ws->inv.v3 && (int)ws->inv.h_subs3.size() == nsw && ws->sw.ubuild_mirror != 0;
     for (DevPlan* p : {&ws->inv, &ws->sweep, vsw, &ws->fwd})
         if (p && p->v3)
             for (size_t i = 0; i < p->h_subs3.size(); ++i) {
@@ -371,7 +362,7 @@ static int ws_upload_ujobs(aqc_ws* ws) {
                 if (vsw && ((p == &ws->inv && (int)i >= p->h_stages.back().sub_begin) || (p == &ws->sweep && (int)i < p->h_stages[0].nsubs) || p == vsw))
                     route_jobs.push_back(j);
             }
-    if (vsw && !route_jobs.empty() && route_jobs.size() < n_vdag_sweep && env_int("AQC_UBUILD_SUBSET", 1) != 0) {
+    if (vsw && !route_jobs.empty() && route_jobs.size() < n_vdag_sweep && ws->sw.ubuild_subset != 0) {
         if (ws->d_ujobs_route.upload(route_jobs)) return 1;
         ws->n_ujobs_route = (int)route_jobs.size();
     }
@@ -399,7 +390,7 @@ static int ws_device_side(aqc_ws* ws, const SlotTables& t) {
         if (p->v3 && p->d_umat.alloc(B * std::max<size_t>(p->h_subs3.size(), 1) * 12 * 64)) return 1;
     if (ws_upload_ujobs(ws)) return 1;
     if (ws->sweep.v3 && ws->sweep.d_rpart.alloc(B * std::max<size_t>(ws->sweep.h_subs3.size(), 1) *
-                                                sweep3_nparts(ws->sweep.ntiles, ws->batch, ws->sweep.k) * 256)) return 1;
+                                                sweep3_nparts(ws->sweep.ntiles, ws->batch, ws->sweep.k, ws->sw.sweep_grid) * 256)) return 1;
     if (ws->d_grads.alloc(B * T1)) return 1;
     if (ws->d_theta_slots.upload(t.theta_slots) || ws->d_slot_ntiles.upload(t.slot_ntiles) || ws->d_slot_theta.upload(t.slot_theta)) return 1;
     ws->pin_thetas = B * T1;
@@ -857,7 +848,7 @@ int aqc_ws_plan_skips(aqc_ws* ws, int which, int stage, int* out, int max_subs) 
     if (stage < 0 || stage >= (int)p.h_stages.size()) return fail("stage index out of range");
     const DevStage& ds = p.h_stages[stage];
     for (int i = 0; i < ds.nsubs && i < max_subs; ++i) {
-        const uint32_t info = p.v3 && ws->skipw_enabled ? p.h_subs3[ds.sub_begin + i].skipinfo : 0u;
+        const uint32_t info = p.v3 && ws->sw.skip_zero_w ? p.h_subs3[ds.sub_begin + i].skipinfo : 0u;
         out[2 * i] = -__builtin_popcount(info & 15u);
         out[2 * i + 1] = -__builtin_popcount((info >> 6) & 3u);
     }
@@ -875,6 +866,22 @@ int aqc_ws_sparse_counts(aqc_ws* ws, int64_t* counts) {
     if (ws->sw_lists_built & 1) { counts[0] = h[0]; counts[1] = h[1]; }
     if (ws->sw_lists_built & 2) counts[2] = h[2];
     return 0;
+}
+
+int aqc_switch_info(int index, const char** name, const char** dflt, const char** when, const char** reader, const char** doc) {
+    if (index < 0 || index >= kNumSwitches) return 1;
+    const SwitchInfo& e = kSwitchTable[index];
+    if (name) *name = e.name;
+    if (dflt) *dflt = e.dflt;
+    if (when) *when = e.when;
+    if (reader) *reader = e.reader;
+    if (doc) *doc = e.doc;
+    return 0;
+}
+
+int aqc_ws_switch(const aqc_ws* ws, const char* name, int64_t* value) {
+    if (!ws || !name || !value) return fail("null argument");
+    return ws->sw.get(name, value) ? 0 : fail("%s is not a switch a workspace reads at creation (include/aqc_switches.def)", name);
 }
 
 int aqc_ws_projected_info(aqc_ws* ws, int32_t* info) {
@@ -916,7 +923,7 @@ static int oneshot_ws(aqc_ctx* ctx, int ncols, aqc_ws** out) {
     auto it = ctx->oneshot.find(ncols);
     if (it != ctx->oneshot.end()) { *out = it->second; return 0; }
     aqc_ws* ws = nullptr;
-    if (aqc_ws_create(ctx, env_int("AQC_DEVICE", 0), 1, ncols, 0, 0, &ws)) return 1;
+    if (aqc_ws_create(ctx, (int)switch_now("AQC_DEVICE"), 1, ncols, 0, 0, &ws)) return 1;
     ctx->oneshot[ncols] = ws;
     *out = ws;
     return 0;

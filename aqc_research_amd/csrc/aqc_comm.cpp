@@ -118,12 +118,7 @@ int ensure_cap(aqc_comm* c, size_t doubles) {
 // kernel forever; after AQC_COMM_TIMEOUT_S seconds (default 300) -- or as soon as RCCL reports the failure -- the
 // communicator is aborted (ncclCommAbort), marked broken and the call returns an error, so that a job list fails
 // instead of hanging (the reference's run_jobs reports failed jobs, job_executor.py:149-159; it never waits on the dead).
-double env_seconds(const char* name, double fallback) {
-    const char* e = getenv(name);
-    const double v = e ? atof(e) : 0.0;
-    return v > 0.0 ? v : fallback;
-}
-double comm_timeout_s() { return env_seconds("AQC_COMM_TIMEOUT_S", 300.0); }
+double comm_timeout_s() { return aqc::switch_now_seconds("AQC_COMM_TIMEOUT_S"); }
 
 int wait_collective(aqc_comm* c, const char* what) {
     Rccl& r = rccl();
@@ -190,7 +185,7 @@ int aqc_comm_create(const char* id128, int nranks, int rank, int device, aqc_com
         else st->rc = init(&st->comm, nranks, id, rank);
         st->done.store(1, std::memory_order_release);
     }).detach();
-    const double limit = env_seconds("AQC_COMM_INIT_TIMEOUT_S", 180.0);
+    const double limit = aqc::switch_now_seconds("AQC_COMM_INIT_TIMEOUT_S");
     const auto t0 = std::chrono::steady_clock::now();
     while (!st->done.load(std::memory_order_acquire)) {
         if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit) {

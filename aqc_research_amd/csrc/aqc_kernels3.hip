@@ -1224,7 +1224,8 @@ int mfma_occupancy(int k, bool sweep) {   // resident workgroups per CU for the 
     return e == hipSuccess ? n : -1;
 }
 // workgroups of the persistent 2^12 sweep: one per CU of the current device (the occupancy its 144 KiB of LDS allows)
-static long persistent_sweep_grid() {
+static long persistent_sweep_grid(long sweep_grid) {   // sweep_grid > 0: the workspace's override (experiments)
+    if (sweep_grid > 0) return sweep_grid;
     static int cus[64] = {0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -1232,12 +1233,7 @@ static long persistent_sweep_grid() {
         int n = 0;
         cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
     }
-    if (const char* e = getenv("AQC_SWEEP_GRID")) { const long v = atol(e); if (v > 0) return v; }   // experiments
     return cus[dev];
-}
-static long apply_persist() {   // persistent V / V^H on 2^12 tiles: workgroups per CU, 0 = off
-    static const long persist = []() { const char* e = getenv("AQC_APPLY_PERSIST"); return e ? atol(e) : 2L; }();
-    return persist;
 }
 // What the four launchers ask of a member: a complete item list (need_list: an item list at all), and on 2^12 tiles lane offsets
 // that fit the prefetch (a 32-bit byte offset per lane) and -- need_subs: the launch takes the persistent form there -- a sub-stage
@@ -1249,54 +1245,54 @@ static bool stage3_launchable(int k, const Stage3Args& a, bool need_list, bool n
         if (a.stage.dlo[l] >= (1u << 28)) return false;
     return true;
 }
-hipError_t launch_apply3(int k, hipStream_t s, const Stage3Args& a) {
+hipError_t launch_apply3(int k, hipStream_t s, const Stage3Args& a, const Switches& sw) {
     const bool list = a.items != nullptr;
-    const long persist = apply_persist();
+    const long persist = sw.apply_persist;   // persistent V / V^H on 2^12 tiles: workgroups per CU, 0 = off
     if (!stage3_launchable(k, a, false, list) || (list && k >= 12 && persist <= 0)) return hipErrorInvalidValue;   // (a list launch of 2^12 tiles is persistent)
     // 2^12 tiles: persistent workgroups, two per CU, walking over (tile, lane) items; smaller tiles: one item per workgroup
     const long nwork = list ? (long)a.max_items : (long)a.ntiles * a.batch;
-    const dim3 grid = (k >= 12 && persist > 0 && a.stage.nsubs > 0) ? dim3((unsigned)std::min<long>(nwork, persist * persistent_sweep_grid()))
+    const dim3 grid = (k >= 12 && persist > 0 && a.stage.nsubs > 0) ? dim3((unsigned)std::min<long>(nwork, persist * persistent_sweep_grid(sw.sweep_grid)))
                                                                      : ((k >= 12 || list) ? dim3((unsigned)nwork) : dim3(a.ntiles, a.batch));
     return with_tile_size(k, [&](auto kk) { return launch3(apply_variant<decltype(kk)::value>(list), grid, k, false, s, a); });
 }
 // Two list launches of the same tile size as one (apply_pair_kernel).  2^12 tiles: the persistent grid of the single launches, sized for
 // the longer list; smaller tiles: a's workgroups, then b's.
 static_assert(2 * sizeof(Stage3Args) + 16 <= 3840, "two argument blocks must fit the kernel-argument segment");
-hipError_t launch_apply3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b) {
-    const long persist = apply_persist();
+hipError_t launch_apply3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b, const Switches& sw) {
+    const long persist = sw.apply_persist;
     if (!stage3_launchable(k, a, true, true) || !stage3_launchable(k, b, true, true) || (k >= 12 && persist <= 0)) return hipErrorInvalidValue;
     const long longer = std::max(a.max_items, b.max_items);
-    const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persist * persistent_sweep_grid()) : (long)a.max_items + b.max_items));
+    const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persist * persistent_sweep_grid(sw.sweep_grid)) : (long)a.max_items + b.max_items));
     return with_tile_size(k, [&](auto kk) { return launch3(apply_pair_variant<decltype(kk)::value>(), grid, k, false, s, a, b, a.max_items); });
 }
 // persistent sweep: items per workgroup (contiguous, lane-major) and partial slots per (lane, sub-stage); 0 / ntiles otherwise
-int sweep3_chunk(int ntiles, int batch, int k) {
+int sweep3_chunk(int ntiles, int batch, int k, long sweep_grid) {
     if (k < 12) return 0;
-    const long nwork = (long)ntiles * batch, g = std::min<long>(nwork, persistent_sweep_grid());
+    const long nwork = (long)ntiles * batch, g = std::min<long>(nwork, persistent_sweep_grid(sweep_grid));
     return (int)((nwork + g - 1) / g);
 }
-int sweep3_nparts(int ntiles, int batch, int k) {
-    const int chunk = sweep3_chunk(ntiles, batch, k);
+int sweep3_nparts(int ntiles, int batch, int k, long sweep_grid) {
+    const int chunk = sweep3_chunk(ntiles, batch, k, sweep_grid);
     return chunk > 0 ? std::min(ntiles, (ntiles + chunk - 1) / chunk + 1) : ntiles;
 }
-hipError_t launch_sweep3(int k, hipStream_t s, const Stage3Args& a) {
+hipError_t launch_sweep3(int k, hipStream_t s, const Stage3Args& a, const Switches& sw) {
     const bool list = a.items != nullptr;
     if (!stage3_launchable(k, a, false, true)) return hipErrorInvalidValue;   // (the persistent form feeds the first sub-stage from registers)
-    if (a.nparts < 1 || (!list && (a.nparts != sweep3_nparts(a.ntiles, a.batch, k) || a.chunk != sweep3_chunk(a.ntiles, a.batch, k)))) return hipErrorInvalidValue;   // (a list names its slots)
+    if (a.nparts < 1 || (!list && (a.nparts != sweep3_nparts(a.ntiles, a.batch, k, sw.sweep_grid) || a.chunk != sweep3_chunk(a.ntiles, a.batch, k, sw.sweep_grid)))) return hipErrorInvalidValue;   // (a list names its slots)
     // 2^12 tiles: one persistent workgroup per CU walking over its items (see the kernel); smaller tiles: one item each
     const long nwork = list ? (long)a.max_items : (long)a.ntiles * a.batch;
-    const dim3 grid((unsigned)(k >= 12 ? (list ? std::min<long>(nwork, persistent_sweep_grid()) : (nwork + a.chunk - 1) / a.chunk) : nwork));
+    const dim3 grid((unsigned)(k >= 12 ? (list ? std::min<long>(nwork, persistent_sweep_grid(sw.sweep_grid)) : (nwork + a.chunk - 1) / a.chunk) : nwork));
     const bool skipw = !list && a.supp != nullptr;
     const bool rlast = !skipw && a.r_only_last != 0;
     return with_tile_size(k, [&](auto kk) { return launch3(sweep_variant<decltype(kk)::value>(list, skipw, rlast), grid, k, true, s, a); });
 }
 
 // Two list launches of the sweep as one (sweep_pair_kernel): a may be the R-only form of its stage, b is not.
-hipError_t launch_sweep3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b) {
+hipError_t launch_sweep3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b, const Switches& sw) {
     if (!stage3_launchable(k, a, true, true) || !stage3_launchable(k, b, true, true)) return hipErrorInvalidValue;
     if (a.nparts < 1 || b.nparts < 1 || a.supp || b.supp || b.r_only_last) return hipErrorInvalidValue;
     const long longer = std::max(a.max_items, b.max_items);
-    const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persistent_sweep_grid()) : (long)a.max_items + b.max_items));
+    const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persistent_sweep_grid(sw.sweep_grid)) : (long)a.max_items + b.max_items));
     return with_tile_size(k, [&](auto kk) { return launch3(sweep_pair_variant<decltype(kk)::value>(a.r_only_last != 0), grid, k, true, s, a, b, a.max_items); });
 }
 

@@ -8,6 +8,7 @@
 
 #include "aqc_device.h"
 #include "aqc_mps_walk.h"
+#include "aqc_switches.h"
 
 namespace aqc {
 
@@ -27,7 +28,7 @@ struct StageArgs {
     int nslots, ntiles_max;
     int from, to, front;    // block_range / front_layer (core_operations.py:829-830)
     int final_stage;        // register-blocked V / V^H: last launch applies the lane's overall sign
-    int debug;              // AQC_DEBUG_SKIP bits (timing experiments only): 1 skip micro-op bodies, 2 skip reductions
+    int debug;              // work-skipping bits (tuning builds, timing experiments only): 1 skip micro-op bodies, 2 skip reductions
 };
 
 size_t apply_lds_bytes(int k);
@@ -89,16 +90,18 @@ void stage3_first_offsets(Stage3Args& a, const DevSub3& first_sub);   // host: f
 hipError_t init_kernels3();
 int mfma_threads(int k, bool sweep);
 int mfma_occupancy(int k, bool sweep);
-hipError_t launch_apply3(int k, hipStream_t s, const Stage3Args& a);   // k: tile size, 8..12
-hipError_t launch_sweep3(int k, hipStream_t s, const Stage3Args& a);
+// k: tile size, 8..12; sw: the workspace's switches (the persistent grids of 2^12 tiles: sweep_grid, apply_persist) -- host arguments,
+// never part of a kernel's argument block
+hipError_t launch_apply3(int k, hipStream_t s, const Stage3Args& a, const Switches& sw);
+hipError_t launch_sweep3(int k, hipStream_t s, const Stage3Args& a, const Switches& sw);
 // Two independent item-list launches of the same tile size k in one grid: every workgroup walks its share of a's list, then of b's, each
 // item exactly as the single launch computes it (apply_pair_kernel / sweep_pair_kernel).  The lists, partial-R slots and lane_parts are
 // the single launches' own.
-hipError_t launch_apply3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b);
-hipError_t launch_sweep3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b);
+hipError_t launch_apply3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b, const Switches& sw);
+hipError_t launch_sweep3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b, const Switches& sw);
 void rgrad_print_stamps(int nsubs);   // tuning builds only
-int sweep3_chunk(int ntiles, int batch, int k);
-int sweep3_nparts(int ntiles, int batch, int k);
+int sweep3_chunk(int ntiles, int batch, int k, long sweep_grid);    // sweep_grid: the workspace's (<= 0: one workgroup per CU); what sized
+int sweep3_nparts(int ntiles, int batch, int k, long sweep_grid);   // d_rpart, what the sweep fills in and what launch_sweep3 checks
 // Projected dense stages of the sparse-lhs sweep (aqc_project.hip, aqc_ws_project.cpp): the state that enters the stages after the
 // first is psi (x) |e> on (first stage's local bits) x (the other bits), and those stages touch the qubits T only, so everything the
 // gradient needs of z there is its projection y0[i_T, c] = sum_u conj(psi[u, c]) z[u, i_T] (u: local bits of the first stage outside T,
@@ -137,7 +140,7 @@ struct ProjArgs {
     int batch;
 };
 hipError_t launch_project_init(const ProjArgs& a, hipStream_t s);
-hipError_t launch_project_fused(const ProjArgs& a, const void* mend, void* ctile, void* yout, hipStream_t s);   // both products of the objective by projection, one fetch of y
+hipError_t launch_project_fused(const ProjArgs& a, const void* mend, void* ctile, void* yout, hipStream_t s, int qb);   // qb: 2 or 4 blocks of u per wave; both products of the objective by projection, one fetch of y
 hipError_t launch_project_amps(const ProjArgs& a, const long long* gather, int ngather, const long long* supp, void* small, const void* vy, const void* z,
                                hipStream_t s);   // the whole gather of an evaluation by projection: inside the lhs tile from z, outside from the virtual z
 hipError_t launch_project(const ProjArgs& a, hipStream_t s);
@@ -350,7 +353,7 @@ hipError_t launch_jacobi_small(void* W, int rows, void* V, int cols, double tol,
 bool svd_fits_block(int rows, int cols);
 int svd_block_size();
 hipError_t launch_jacobi_block(void* W, int rows, void* V, int cols, const void* bpairs, int rounds, int per_round, double tol, int max_sweeps,
-                               const double* fro2, int* rot, unsigned* bar, int* status, hipStream_t s);
+                               const double* fro2, int* rot, unsigned* bar, int* status, hipStream_t s, int debug = 0);   // debug: tuning builds
 hipError_t launch_svd_norms(const void* W, int rows, int cols, double* sigma, hipStream_t s);
 hipError_t launch_mps_theta(const void* theta0, const double* lam_left, int chil, int chir, const double* g16, int mode, void* work, hipStream_t s);
 // aqc_svd_batch.hip: block Jacobi on the matrix cores, a workgroup per matrix.  The device-pointer core behind aqc_svd_batch: a [count][m][n],

@@ -84,8 +84,7 @@ void block_tournament(int nblocks, std::vector<int>& pairs, int& rounds, int& pe
 // Orthogonalises the columns of the column-major W (rows x cols) in place, accumulating V (cols x cols);
 // returns the column norms in h_sigma.  `sweeps_out` reports the number of sweeps used.
 int jacobi_svd(SvdWork& sw, void* W, int rows, void* V, int cols, hipStream_t st, std::vector<double>& h_sigma, int* sweeps_out) {
-    const char* env_blocked = getenv("AQC_SVD_BLOCKED");   // 0: round-per-launch cross-check
-    const bool blocked_ok = !(env_blocked && atoi(env_blocked) == 0);
+    const bool blocked_ok = switch_now("AQC_SVD_BLOCKED") != 0;   // (0: round-per-launch cross-check)
     const bool small = svd_fits_small(rows, cols);
     const bool blocked = !small && blocked_ok && svd_fits_block(rows, cols);
     if (!small && (sw.cached_cols != cols || sw.cached_blocked != (int)blocked)) {   // (the one-workgroup kernel works its pairing out itself)
@@ -110,7 +109,11 @@ int jacobi_svd(SvdWork& sw, void* W, int rows, void* V, int cols, hipStream_t st
         HIP_OK(launch_svd_identity(V, cols, st));
         HIP_OK(launch_svd_fro2(W, (size_t)rows * cols, fro2, st));
         HIP_OK(hipMemsetAsync(flag, 0, sizeof(int) * kFlagInts, st));
-        HIP_OK(launch_jacobi_block(W, rows, V, cols, sw.pairs, sw.rounds, sw.per_round, tol, 60, fro2, flag, reinterpret_cast<unsigned*>(flag + 64), flag + 65, st));
+        int debug = 0;
+#ifdef AQC_TUNING
+        debug = (int)switch_now("AQC_SVD_DEBUG");
+#endif
+        HIP_OK(launch_jacobi_block(W, rows, V, cols, sw.pairs, sw.rounds, sw.per_round, tol, 60, fro2, flag, reinterpret_cast<unsigned*>(flag + 64), flag + 65, st, debug));
         HIP_OK(hipMemcpyAsync(status, flag + 65, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     } else {
         HIP_OK(launch_svd_identity(V, cols, st));

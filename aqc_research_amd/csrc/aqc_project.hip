@@ -475,10 +475,9 @@ __global__ __launch_bounds__(256) void project_csum_kernel(const ProjArgs a, dou
     }
     ctile[(size_t)it.lane * a.lane_stride + ebits + a.off_us[u] + a.off_cb[c]] = acc;
 }
-hipError_t launch_project_fused(const ProjArgs& a, const void* mend, void* ctile, void* yout, hipStream_t s) {
-    if (a.t < 4 || a.us_bits < 4 || a.us_bits > 10 || (a.us_bits > 8 && a.part_stride == 0) || a.cb < 0 || a.cb > 4 || a.batch < 1 || !a.y || !a.s || !mend || !ctile || !yout || !a.off_us)
+hipError_t launch_project_fused(const ProjArgs& a, const void* mend, void* ctile, void* yout, hipStream_t s, int qb) {
+    if (a.t < 4 || a.us_bits < 4 || a.us_bits > 10 || (a.us_bits > 8 && a.part_stride == 0) || a.cb < 0 || a.cb > 4 || a.batch < 1 || !a.y || !a.s || !mend || !ctile || !yout || !a.off_us || (qb != 2 && qb != 4))
         return hipErrorInvalidValue;
-    static const int qb = []() { const char* e = getenv("AQC_PROJECTED_FUSED_QB"); return e && atoi(e) == 4 ? 4 : 2; }();
     static bool attr_set[64] = {};   // (per device: the eight-wave form needs more than the default 64 KiB of LDS)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;

@@ -367,7 +367,7 @@ hipError_t launch_svd_fro2(const void* W, size_t n, double* out, hipStream_t s) 
 }
 
 hipError_t launch_jacobi_block(void* W, int rows, void* V, int cols, const void* bpairs, int rounds, int per_round, double tol, int max_sweeps,
-                               const double* fro2, int* rot, unsigned* bar, int* status, hipStream_t s) {
+                               const double* fro2, int* rot, unsigned* bar, int* status, hipStream_t s, int debug) {
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -376,10 +376,7 @@ hipError_t launch_jacobi_block(void* W, int rows, void* V, int cols, const void*
         attr_set = true;
     }
     if (max_sweeps > kBlockMaxSweeps) max_sweeps = kBlockMaxSweeps;
-    BlockJacobi a{static_cast<cplx*>(W), static_cast<cplx*>(V), static_cast<const int2*>(bpairs), rows, cols, rounds, per_round, max_sweeps, tol, fro2, rot, bar, status, 0};
-#ifdef AQC_TUNING
-    if (const char* e = getenv("AQC_SVD_DEBUG")) a.debug = atoi(e);
-#endif
+    BlockJacobi a{static_cast<cplx*>(W), static_cast<cplx*>(V), static_cast<const int2*>(bpairs), rows, cols, rounds, per_round, max_sweeps, tol, fro2, rot, bar, status, debug};
     void* args[] = {&a};
     const size_t lds = sizeof(cplx) * ((size_t)kBlk2 * (((rows + 63) >> 6) << 6) + kBlk2 * kBlk2);
     // cooperative: the runtime refuses the launch unless all workgroups are resident together (the barrier needs that)

@@ -38,11 +38,6 @@ int fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));   // sets 
         if (e_ != hipSuccess) return ::aqc::fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-inline int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
 inline int ceil_log2(int v) {
     int b = 0;
     while ((1 << b) < v) ++b;
@@ -111,7 +106,7 @@ struct EvalRoute {
     // how (eval_route's part)
     bool sparse = false;           // the sweep's first stage over the tiles of the lhs state only (head of aqc_ws_sweep.cpp)
     enum VdagKind { kStages, kRestricted, kProjected } vdag_kind = kStages;   // all stages / last stage where it is read / by projection
-    bool skip_zero_w = false;      // AQC_SKIP_ZERO_W
+    bool skip_zero_w = false;      // zero groups of w skipped inside a stage (opt-in switch)
     int key_bits() const {         // what a captured graph's key must tell apart
         static_assert(AQC_NUM_BUFS <= 8, "x_buf takes the low three bits");
         return x_buf | (vdag ? 8 : 0) | (gather ? 16 : 0) | (gather_rides ? 32 : 0) | (grads ? 64 : 0) | (sparse ? 128 : 0) |
@@ -166,6 +161,7 @@ struct aqc_ctx {
 
 struct aqc_ws {
     aqc_ctx* ctx = nullptr;
+    aqc::Switches sw;       // the create switches (include/aqc_switches.def), read once by aqc_ws_create
     int device = 0, batch = 1, ncols = 1, pitch = 1, col_bits = 0, nbits = 0, threads = 256;
     size_t lane_elems = 0;  // 2^nbits
     hipStream_t stream = nullptr;
@@ -214,7 +210,7 @@ struct aqc_ws {
     DevBuf<UJob> d_ujobs;             // family 3: [V^H subs | sweep subs | virtual sweep subs | V subs]; ujobs_mirror: no V^H jobs, the sweep's write both operand sets
     bool ujobs_mirror = false;
     // The jobs the objective-by-projection route reads, as a compact list of their own: [V^H's last stage (its own jobs only) | the
-    // sweep's first stage | virtual sweep].  Null: the route builds everything (no projected route, or AQC_UBUILD_SUBSET=0).
+    // sweep's first stage | virtual sweep].  Null: the route builds everything (no projected route, or switched off).
     DevBuf<UJob> d_ujobs_route;
     int n_ujobs_route = 0;
     struct MpsSlot {
@@ -252,11 +248,6 @@ struct aqc_ws {
     bool inv_mirrored = false;     // inv = the sweep plan walked backwards: V^H into Z leaves the state before its last stage in ZW ...
     bool ckpt_valid = false;       // ... and ZW holds it for the thetas in use and the present contents of Z
     bool w_clean = true;           // W is zero outside the tiles named in d_sw_prev_tiles
-    bool sparse_enabled = true;    // AQC_SPARSE_SWEEP=0: always the dense route
-    bool r_only_enabled = true;    // AQC_R_ONLY_LAST=0: the sweep's very last sub-stage runs its U products like every other
-    int r_only_max_subs = 12;      // ... and so it does when the last stage has more sub-stages than this (AQC_R_ONLY_MAX_SUBS)
-    bool skipw_enabled = false;    // AQC_SKIP_ZERO_W=1: skip zero groups / K-steps of w inside a stage (exact; measured slower, off by default)
-    long sparse_min_items = 512;   // the sparse route pays from this many (tile, lane) items per stage launch (AQC_SPARSE_MIN_ITEMS)
     unsigned long long supp_version[AQC_NUM_BUFS] = {0, 0, 0, 0, 0, 0};   // bumped whenever d_combo_prev[buf] (the support of a sparse lhs) changes
     DevBuf<aqc::TileItem> d_sw_items;       // first-stage items of the sparse sweep [2 batch], and the tiles to clear in W
     DevBuf<aqc::TileItem> d_sw_clear;
@@ -269,17 +260,12 @@ struct aqc_ws {
     DevBuf<double2> zw2;
     // "objective" V^H: the last stage of the mirrored V^H runs only over the tiles its readers touch -- the registered gather
     // indices and the support of the lhs state -- and Z is completed on demand (ensure_z_full) while the checkpoint is valid
-    bool lazy_z_enabled = true;             // AQC_LAZY_Z=0: V^H always writes all of Z
     bool z_full = true;                     // Z holds V^H y everywhere (false: on the tiles of d_vd_items only)
     DevBuf<aqc::TileItem> d_vd_items;       // [batch][2 + gather_count] (grow-only)
     unsigned long long gather_gen = 0;      // bumped by aqc_ws_gather_setup
     aqc::ListKey vd_key;                    // what d_vd_items was built from
     aqc::ListKey z_key;                     // what the tiles of a partial Z were chosen for
-    aqc::ProjRoute proj;                    // dense stages of the sparse route on a virtual register (AQC_PROJECTED=0: off)
-    bool proj_vdag_enabled = true;          // AQC_PROJECTED_VDAG=0: V^H of a one-call evaluation always by its stages
-    long long proj_vdag_min_elems = 1ll << 24;   // ... and from this many amplitudes per batch (fewer: its extra launches cost more than V^H's stages; AQC_PROJECTED_VDAG_MIN_ELEMS)
-    bool proj_fused_enabled = true;         // AQC_PROJECTED_FUSED=0: its two products as two launches (two fetches of the target)
-    bool proj_pairs_enabled = true;         // AQC_PROJECTED_PAIRS=0: its independent tile launches one by one instead of in pairs (projected_pairs)
+    aqc::ProjRoute proj;                    // dense stages of the sparse route on a virtual register
     bool proj_y0_ready = false;             // the virtual z (proj.vy) holds Y_0 for the sweep that follows in the same call (run_vdag_projected)
     bool z_from_y = false;                  // a partial Z without a checkpoint: completed by a full V^H from Y (thetas and Y unchanged since)
     std::vector<long long> h_gather;        // host copy of the registered gather indices (elements)

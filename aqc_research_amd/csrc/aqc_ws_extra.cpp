@@ -418,9 +418,8 @@ int aqc_ws_cd_minimize(aqc_ws* ws, const double* thetas0, int maxiter, int chunk
 int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io, double* fobj) {
     if (!ws || !thetas_io || !fobj) return fail("null argument");
     if (cd_checks(ws)) return 1;
-    const char* chain = getenv("AQC_CD_CHAIN");   // "1": the multi-launch route (the wide walk) even where one launch would do (cross-check, timing)
     if (ws->batch != 1) return fail("aqc_ws_cd_sweep takes thetas_io[T] and one objective value: a single-lane workspace (aqc_ws_cd_sweeps serves lanes)");
-    if (aqc_ws_cd_fits_one_launch(ws) && !(chain && chain[0] == '1')) return aqc_ws_cd_sweeps(ws, thetas_io, fobj, 1, -1);
+    if (aqc_ws_cd_fits_one_launch(ws) && !switch_now("AQC_CD_CHAIN")) return aqc_ws_cd_sweeps(ws, thetas_io, fobj, 1, -1);
     if (cd_wide_size_check(ws)) return 1;
     // One sweep of the driver on the wide route, stop rules off.  The sweep's own thetas and value (profile[0]) go back, not the best
     // ones: the close rule records a best value only below best_f, so a NaN sweep would come back as the start and inf.

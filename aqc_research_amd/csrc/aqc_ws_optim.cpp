@@ -333,8 +333,7 @@ int aqc_ws_surrogate_eval(aqc_ws* ws, const double* thetas, int update_state, do
         }
         return 0;
     };
-    static const bool graphs_on = env_int("AQC_GRAPH", 1) != 0;
-    if (graphs_on && !ws->profile) {   // the launch sequence is replayed as a graph, as in aqc_ws_eval
+    if (ws->sw.graph && !ws->profile) {   // the launch sequence is replayed as a graph, as in aqc_ws_eval
         const long long tag = 1000 + update_state + (zero_copy ? 10 : 0) + (real_only ? 20 : 0);   // (1000: no key of aqc_ws_eval)
         if (run_graph(ws, route, {tag, block_from, block_to, front_layer, (long long)S, (long long)(size_t)(double*)ws->d_sur_real, (long long)(size_t)(char*)ws->d_sur,
                                   (long long)(size_t)(char*)ws->h_sur}, enqueue)) return 1;

@@ -36,7 +36,7 @@ void proj_plan(aqc_ws* ws, int low_bits) {
     pr.ok = false;
     const Program& prog = ws->ctx->prog;
     const DevPlan& p = ws->sweep;
-    if (env_int("AQC_PROJECTED", 1) == 0 || !ws->sparse_enabled || !ws->inv_mirrored || !p.v3 || ws->col_bits != 0 || ws->ncols != 1 ||
+    if (!ws->sw.projected || !ws->sw.sparse_sweep || !ws->inv_mirrored || !p.v3 || ws->col_bits != 0 || ws->ncols != 1 ||
         p.plan.stages.size() < 2 || prog.n > 30)
         return;
     const int n = prog.n;
@@ -79,7 +79,7 @@ void proj_plan(aqc_ws* ws, int low_bits) {
         if (best.stages.empty() || cand.stages.size() < best.stages.size()) best = cand;
     }
     // (a narrow sub-stage search: the virtual stages are a small share of an evaluation, planning them must not cost what planning the real ones does)
-    lower_plan(pr.vprog, best, pr.vsw, 4, true, true, false, env_int("AQC_PROJECTED_BEAM", 8));
+    lower_plan(pr.vprog, best, pr.vsw, 4, true, true, false, (int)ws->sw.projected_beam);
     if (!pr.vsw.v3 || !check_plan(pr.vprog, pr.vsw.plan, &pr.rest).empty()) return;
     lower_plan(pr.vprog, mirror_plan(pr.vsw.plan), pr.vinv, 4, false, true, true);
     if (!pr.vinv.v3 || pr.vinv.h_subs3.size() != pr.vsw.h_subs3.size()) return;
@@ -105,7 +105,7 @@ void proj_plan(aqc_ws* ws, int low_bits) {
         pr.h_tab.push_back(it);
     }
     pr.ok = true;
-    if (env_int("AQC_VERBOSE", 0))
+    if (ws->sw.verbose)
         fprintf(stderr, "aqc_hip: projected route: the sweep's stages after the first run on %d virtual qubits (%d touched, %d shared with the first "
                 "stage) instead of %d: %zu stage(s) of 2^%d tiles, %zu sub-stages\n", pr.nv, pr.t, pr.cb, n, pr.vsw.h_stages.size(), pr.kv,
                 pr.vsw.h_subs3.size());
@@ -125,10 +125,10 @@ int proj_alloc(aqc_ws* ws) {
     HIP_OK(hipMemsetAsync(pr.vm, 0, vbytes, ws->stream));   // (entries beyond 2^nv -- a register padded to 8 qubits -- stay zero for good)
     HIP_OK(hipMemsetAsync(pr.vy, 0, vbytes * pr.vy_copies, ws->stream));
     pr.cpart_shares = 0;
-    const long want_wgs = env_int("AQC_PROJECTED_FUSED_WGS", 512);
+    const long want_wgs = ws->sw.projected_fused_wgs;
     if (pr.us <= 10 && pr.cb <= 4 && (long)B < want_wgs) {   // the fused pass of a small batch splits its walk over the touched bits (launch_project_fused)
         int shares = 1;
-        const int cap = env_int("AQC_PROJECTED_FUSED_MAX_SHARES", 64);   // (1: never split -- what large batches run; tests)
+        const long cap = ws->sw.projected_fused_max_shares;   // (1: never split -- what large batches run; tests)
         while ((long)B * pr.vy_copies * shares < want_wgs && 2 * shares <= (1 << (pr.t - 4)) && 2 * shares <= cap) shares *= 2;
         if (shares > 1) {
             if (pr.cpart.alloc((size_t)shares * 2 * B * (16ull << pr.us))) return 1;
@@ -214,7 +214,7 @@ int run_projected_stages(aqc_ws* ws) {
     for (size_t s = 0; s < pr.vsw.h_stages.size(); ++s) {
         const Stage3Args a = projected_sweep_stage(ws, s);
         ProfScope ps(ws, AQC_K_SWEEP_VIRTUAL);
-        HIP_OK(launch_sweep3(pr.kv, ws->stream, a));
+        HIP_OK(launch_sweep3(pr.kv, ws->stream, a, ws->sw));
     }
     return 0;
 }
@@ -241,10 +241,10 @@ Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s) {
 
 // Objective by projection: its six tile launches are three pairs of independent launches over disjoint buffers (psi with M_end, V^H's
 // last stage with Y_0, the sweep's first stage with the virtual stage), and each pair runs as ONE launch (launch_apply3_pair /
-// launch_sweep3_pair) when the virtual plan has a single stage of the real plans' tile size.  AQC_PROJECTED_PAIRS=0: single launches.
+// launch_sweep3_pair) when the virtual plan has a single stage of the real plans' tile size (unless switched off).
 bool projected_pairs(const aqc_ws* ws) {
     const ProjRoute& pr = ws->proj;
-    return pr.ok && ws->proj_pairs_enabled && !ws->capturing && pr.vsw.h_stages.size() == 1 && pr.vinv.h_stages.size() == 1 &&
+    return pr.ok && ws->sw.projected_pairs && !ws->capturing && pr.vsw.h_stages.size() == 1 && pr.vinv.h_stages.size() == 1 &&
            ws->sweep.k == pr.kv && ws->inv.k == pr.kv;
 }
 
@@ -271,7 +271,7 @@ RgradSecond projected_rgrad_plan(aqc_ws* ws) {
 // <g|V^H y> = sum_c Y_0[(c, g on T n F), c] for the gather indices outside the tile.
 bool vdag_route_projected(aqc_ws* ws, int x_buf) {
     ProjRoute& pr = ws->proj;
-    if (!pr.ok || !ws->proj_vdag_enabled || ws->capturing || (long long)ws->lane_elems * ws->batch < ws->proj_vdag_min_elems) return false;
+    if (!pr.ok || !ws->sw.projected_vdag || ws->capturing || (long long)ws->lane_elems * ws->batch < ws->sw.projected_vdag_min_elems) return false;
     const ListKey key = key_of(ws, x_buf, true);
     if (ws->projb_key == key) return ws->projb_ok;
     ws->projb_key = key;
@@ -307,14 +307,14 @@ static Stage3Args virtual_apply_stage(aqc_ws* ws, const VirtualRun& v, size_t s)
 static int enqueue_couple(aqc_ws* ws, int k, const Stage3Args* real, const VirtualRun* v) {
     if (real && v) {
         ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
-        HIP_OK(launch_apply3_pair(k, ws->stream, *real, virtual_apply_stage(ws, *v, 0)));
+        HIP_OK(launch_apply3_pair(k, ws->stream, *real, virtual_apply_stage(ws, *v, 0), ws->sw));
     } else if (real) {
         ProfScope ps(ws, AQC_K_APPLY_LIST);
-        HIP_OK(launch_apply3(k, ws->stream, *real));
+        HIP_OK(launch_apply3(k, ws->stream, *real, ws->sw));
     } else {
         for (size_t s = 0; s < v->plan.h_stages.size(); ++s) {
             ProfScope ps(ws, AQC_K_APPLY_VIRTUAL);
-            HIP_OK(launch_apply3(ws->proj.kv, ws->stream, virtual_apply_stage(ws, *v, s)));
+            HIP_OK(launch_apply3(ws->proj.kv, ws->stream, virtual_apply_stage(ws, *v, s), ws->sw));
         }
     }
     return 0;
@@ -343,13 +343,13 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // for a route eval_route has 
     if (!pairs && enqueue_couple(ws, p.k, &psi, nullptr)) return 1;          // psi
     if (ensure_pattern(ws, a)) return 1;                                      // M_0
     if (enqueue_couple(ws, p.k, pairs ? &psi : nullptr, &mend)) return 1;     // M_end (pairs: with psi)
-    if (ws->proj_fused_enabled && pr.us <= 10 && pr.cb <= 4 && (pr.us <= 8 || pr.vy_copies == 1 << (pr.us - 8))) {   // both products from one fetch of the target
+    if (ws->sw.projected_fused && pr.us <= 10 && pr.cb <= 4 && (pr.us <= 8 || pr.vy_copies == 1 << (pr.us - 8))) {   // both products from one fetch of the target
         ProjArgs q = a;
         q.part_stride = (size_t)ws->batch * (2ull << pr.nvp);
         q.cpart = pr.cpart; q.cpart_shares = pr.cpart_shares;
         q.y = ws->bufs[AQC_BUF_Y]; q.s = ws->bufs[AQC_BUF_W];
         ProfScope ps(ws, AQC_K_PROJECT);
-        HIP_OK(launch_project_fused(q, pr.vme, ws->bufs[AQC_BUF_ZW], pr.vy, ws->stream));
+        HIP_OK(launch_project_fused(q, pr.vme, ws->bufs[AQC_BUF_ZW], pr.vy, ws->stream, ws->sw.projected_fused_qb == 4 ? 4 : 2));
     } else {
         {   // Y_end = proj(y)
             ProfScope ps(ws, AQC_K_PROJECT);

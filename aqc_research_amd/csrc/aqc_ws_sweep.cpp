@@ -129,7 +129,7 @@ int run_coef(aqc_ws* ws, double* d_thetas) {
 namespace {
 unsigned long long* g_stamps = nullptr;
 int stamps_begin(aqc_ws* ws, Stage3Args& a, size_t nwg) {
-    if (env_int("AQC_STAMPS", 0) == 0 || nwg > 65536) return 0;
+    if (!ws->sw.stamps || nwg > 65536) return 0;
     // process-lifetime, never freed: a static destructor must not call into HIP at exit, so this one block stays a raw pointer
     if (!g_stamps) HIP_OK(hipMalloc((void**)&g_stamps, sizeof(unsigned long long) * 65536 * kStampSlots));
     HIP_OK(hipMemsetAsync(g_stamps, 0, sizeof(unsigned long long) * nwg * kStampSlots, ws->stream));
@@ -255,7 +255,7 @@ int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
 #endif
             {
                 ProfScope ps(ws, AQC_K_APPLY);
-                HIP_OK(launch_apply3(p.k, ws->stream, a));
+                HIP_OK(launch_apply3(p.k, ws->stream, a, ws->sw));
             }
 #ifdef AQC_TUNING
             if (stamps_apply(ws, a, s, nwg)) return 1;
@@ -284,7 +284,7 @@ int run_apply(aqc_ws* ws, bool inverse, int src_buf, int dst_buf) {
 // of its four flips on qubits 12..15); everything before it is needed in full (it is the second sweep stage's z).  Z is
 // completed on demand -- the checkpoint in ZW is all it takes -- as long as the thetas have not changed.
 static bool vdag_route_restricted(const aqc_ws* ws) {   // asked of a sparse route whose V^H is part of the call (eval_route)
-    return ws->lazy_z_enabled && 2 + ws->gather_count <= kMaxTileCands;
+    return ws->sw.lazy_z && 2 + ws->gather_count <= kMaxTileCands;
 }
 static Stage3Args last_vdag_stage(aqc_ws* ws) {
     DevPlan& p = ws->inv;
@@ -319,7 +319,7 @@ static int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set
         a.in0 = s == 0 ? ws->bufs[AQC_BUF_Y] : ws->bufs[AQC_BUF_ZW];
         a.out0 = ws->bufs[AQC_BUF_ZW];
         ProfScope ps(ws, AQC_K_APPLY);
-        HIP_OK(launch_apply3(p.k, ws->stream, a));
+        HIP_OK(launch_apply3(p.k, ws->stream, a, ws->sw));
     }
     const bool gather_only = support_in_gather_set && ws->gather_count > 0;
     const ListKey key = key_of(ws, gather_only ? ListKey::kGatherOnly : x_buf, true);
@@ -336,7 +336,7 @@ static int run_vdag_restricted(aqc_ws* ws, int x_buf, bool support_in_gather_set
     ws->sw_lists_built |= 2;
     {
         ProfScope ps(ws, AQC_K_APPLY_LIST);
-        HIP_OK(launch_apply3(p.k, ws->stream, a));
+        HIP_OK(launch_apply3(p.k, ws->stream, a, ws->sw));
     }
     vdag_restricted_state_after(ws, x_buf);
     return 0;
@@ -348,7 +348,7 @@ static int ensure_z_full(aqc_ws* ws, bool reader) {
         if (ensure_umat(ws, ws->inv)) return 1;
         Stage3Args a = last_vdag_stage(ws);
         ProfScope ps(ws, AQC_K_APPLY);
-        HIP_OK(launch_apply3(ws->inv.k, ws->stream, a));
+        HIP_OK(launch_apply3(ws->inv.k, ws->stream, a, ws->sw));
         ws->z_full = true;
         return 0;
     }
@@ -370,10 +370,10 @@ void drop_graphs(aqc_ws* ws) {
 // Route of the next sweep from x_buf.  will_vdag: a V^H from Y into Z precedes it inside the same call.
 static bool sweep_route_sparse(const aqc_ws* ws, int x_buf, bool will_vdag) {
     const DevPlan& p = ws->sweep;
-    if (!ws->sparse_enabled || !p.v3 || !ws->inv_mirrored || p.h_stages.size() < 2) return false;
+    if (!ws->sw.sparse_sweep || !p.v3 || !ws->inv_mirrored || p.h_stages.size() < 2) return false;
     if (!ws->combo_valid[x_buf] || !ws->d_combo_prev[x_buf]) return false;          // support of the lhs state known on the device
     if (!(will_vdag ? keeps_checkpoint(ws, true, AQC_BUF_Y, AQC_BUF_Z) : (ws->ckpt_valid || ws->proj_y0_ready))) return false;   // z of stage 1 available in ZW (or projected already)
-    return (long)p.ntiles * ws->batch >= ws->sparse_min_items;   // (fewer items than CUs: a stage takes one item's time either way)
+    return (long)p.ntiles * ws->batch >= ws->sw.sparse_min_items;   // (fewer items than CUs: a stage takes one item's time either way)
 }
 // The last sub-stage of the last stage is taken from its inputs alone (R = U (Z W^H) U^H, see sweep_mfma_kernel) unless it is also the
 // FIRST sub-stage of a persistent stage, whose operands sit in the prefetch registers in the other layout, and unless the stage is
@@ -381,14 +381,14 @@ static bool sweep_route_sparse(const aqc_ws* ws, int x_buf, bool will_vdag) {
 // saving is 2/3 of ONE sub-stage.  Returns the sub-stage's index over all stages, or -1.
 int sweep_r_only_sub(const aqc_ws* ws) {
     const DevPlan& p = ws->sweep;
-    if (!p.v3 || !ws->r_only_enabled || p.h_stages.empty()) return -1;
+    if (!p.v3 || !ws->sw.r_only_last || p.h_stages.empty()) return -1;
     const DevStage& last = p.h_stages.back();
-    if (last.nsubs < 1 || last.nsubs > ws->r_only_max_subs || (p.k >= 12 && last.nsubs == 1)) return -1;
+    if (last.nsubs < 1 || last.nsubs > ws->sw.r_only_max_subs || (p.k >= 12 && last.nsubs == 1)) return -1;
     return last.sub_begin + last.nsubs - 1;
 }
 // Inside a stage the same knowledge goes further (any number of stages, either route): see sweep_mfma_kernel<K, false, true>.
 static bool sweep_skips_zero_w(const aqc_ws* ws, int x_buf) {
-    return ws->skipw_enabled && ws->sweep.v3 && ws->combo_valid[x_buf] && ws->d_combo_prev[x_buf] != nullptr;
+    return ws->sw.skip_zero_w && ws->sweep.v3 && ws->combo_valid[x_buf] && ws->d_combo_prev[x_buf] != nullptr;
 }
 // Allocations and one-off clears of the sparse route: everything that must not sit inside a captured graph.
 static int sweep_sparse_prepare(aqc_ws* ws) {
@@ -406,7 +406,7 @@ static int sweep_sparse_prepare(aqc_ws* ws) {
         if (ws->w2.alloc((size_t)B * ws->lane_elems) || ws->zw2.alloc((size_t)B * ws->lane_elems)) return 1;
     }
     const size_t vd_need = (2 + (size_t)ws->gather_count) * B;
-    if (ws->lazy_z_enabled && ws->d_vd_items.capacity() < vd_need) {
+    if (ws->sw.lazy_z && ws->d_vd_items.capacity() < vd_need) {
         HIP_OK(hipStreamSynchronize(ws->stream));
         if (ws->d_vd_items.reserve(vd_need)) return 1;
         ws->vd_key = ListKey{};
@@ -521,18 +521,18 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
     const int x_buf = route.x_buf;
     const int nsubs = (int)p.h_subs3.size();
     const size_t m = p.h_stages.size();
-    const int nparts = sweep3_nparts(p.ntiles, ws->batch, p.k), chunk = sweep3_chunk(p.ntiles, ws->batch, p.k);
+    const int nparts = sweep3_nparts(p.ntiles, ws->batch, p.k, ws->sw.sweep_grid), chunk = sweep3_chunk(p.ntiles, ws->batch, p.k, ws->sw.sweep_grid);
     const bool sparse = route.sparse, skipw = route.skip_zero_w;
     const bool projected = sweep_route_projected(ws, sparse);   // the stages after the first on the virtual register (aqc_ws_project.cpp)
     if (ensure_umat(ws, p, projected ? kURoute : kUAll)) return 1;   // (projected: its first stage and the virtual plan are all it reads)
     int r_only_sub = skipw || projected ? -1 : sweep_r_only_sub(ws);   // (the zero-w variant of the kernel has no R-only form)
     // objective by projection: psi is in W already and nobody reads the first stage's z': ITS last sub-stage is the R-only one
-    const bool first_stage_r_only = projected && ws->proj_y0_ready && ws->r_only_enabled && p.h_stages[0].nsubs >= 2 &&
-                                    p.h_stages[0].nsubs <= ws->r_only_max_subs;
+    const bool first_stage_r_only = projected && ws->proj_y0_ready && ws->sw.r_only_last && p.h_stages[0].nsubs >= 2 &&
+                                    p.h_stages[0].nsubs <= ws->sw.r_only_max_subs;
     if (first_stage_r_only) r_only_sub = p.h_stages[0].sub_begin + p.h_stages[0].nsubs - 1;
     bool pair_virtual = projected && ws->proj_y0_ready && projected_pairs(ws);   // the first stage and the virtual stage as one launch
 #ifdef AQC_TUNING
-    if (env_int("AQC_STAMPS", 0) != 0) pair_virtual = false;
+    if (ws->sw.stamps) pair_virtual = false;
 #endif
     // a partial Z covers the sparse route's reads when its tiles were chosen for this lhs state (or for a gather set the
     // state was picked from); anything else reads all of Z
@@ -568,16 +568,16 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
         stage3_sweep_fields(a, p, nparts, chunk);
 #ifdef AQC_TUNING
         const size_t nwg = (size_t)p.ntiles * ws->batch;
-        a.debug = env_int("AQC_DEBUG_SKIP", 0);
+        a.debug = (int)ws->sw.debug_skip;
         if (stamps_begin(ws, a, nwg)) return 1;
 #endif
         if (pair_virtual) {   // ... with the virtual stage (Y_0 is there already: nothing of it waits for this stage)
             const Stage3Args b = projected_sweep_stage(ws, 0);
             ProfScope ps(ws, AQC_K_SWEEP_LIST);
-            HIP_OK(launch_sweep3_pair(p.k, ws->stream, a, b));
+            HIP_OK(launch_sweep3_pair(p.k, ws->stream, a, b, ws->sw));
         } else {
             ProfScope ps(ws, a.items ? AQC_K_SWEEP_LIST : AQC_K_SWEEP);
-            HIP_OK(launch_sweep3(p.k, ws->stream, a));
+            HIP_OK(launch_sweep3(p.k, ws->stream, a, ws->sw));
         }
 #ifdef AQC_TUNING
         if (stamps_sweep(ws, a, s, nwg)) return 1;
@@ -597,7 +597,7 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
                         sparse ? p.h_stages[0].nsubs : 0, sparse ? ws->d_sw_lane_parts : nullptr, r_only_sub, p.d_umat,
                         projected ? p.h_stages[0].nsubs : -1, projected ? &vwalk : nullptr));
 #ifdef AQC_TUNING
-    if (env_int("AQC_STAMPS", 0) != 0) { HIP_OK(hipStreamSynchronize(ws->stream)); rgrad_print_stamps(nsubs); }
+    if (ws->sw.stamps) { HIP_OK(hipStreamSynchronize(ws->stream)); rgrad_print_stamps(nsubs); }
 #endif
     if (!ws->grads_direct)   // some theta collects two slots (2nd-order Trotter half-layers, core_operations.py:966-968)
         HIP_OK(launch_finalize(ws->d_partial, ws->d_theta_slots, ws->d_slot_ntiles, ws->d_grads, prog.num_thetas(), ws->nslots,
@@ -618,7 +618,7 @@ static int sweep_valu(aqc_ws* ws, int x_buf, int block_from, int block_to, int f
         a.out1 = ws->bufs[AQC_BUF_ZW];
         a.partial = ws->d_partial; a.nslots = ws->nslots; a.ntiles_max = p.ntiles;
 #ifdef AQC_TUNING   // timing experiments only (tools/tune.py); never part of the shipped library
-        a.debug = env_int("AQC_DEBUG_SKIP", 0);
+        a.debug = (int)ws->sw.debug_skip;
 #endif
         a.from = block_from; a.to = block_to; a.front = front_layer ? 1 : 0;
         ProfScope ps(ws, AQC_K_SWEEP);
@@ -743,8 +743,7 @@ int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered,
         return 0;
     };
     if (thetas) memcpy(pin_th, thetas, sizeof(double) * nth);
-    static const bool graphs_on = env_int("AQC_GRAPH", 1) != 0;
-    if (thetas && graphs_on && !ws->profile) {
+    if (thetas && ws->sw.graph && !ws->profile) {
         if (run_graph(ws, route, {0, block_from, block_to, front_layer, (long long)ws->gather_count}, enqueue)) return 1;
     } else if (enqueue()) {
         return 1;

@@ -468,6 +468,12 @@ class Workspace:
         check(self._L.aqc_ws_sparse_counts(self.handle, c))
         return int(c[0]), int(c[1]), int(c[2])
 
+    def switch(self, name: str) -> int:
+        """The value of a ``create`` switch (include/aqc_switches.def) this workspace was created with."""
+        v = c_int64()
+        check(self._L.aqc_ws_switch(self.handle, name.encode(), ctypes.byref(v)))
+        return int(v.value)
+
     def projected_info(self) -> dict:
         """The projected route of the sparse-lhs sweep (its stages after the first on a virtual register), or {} without it."""
         c = (ctypes.c_int32 * 16)()

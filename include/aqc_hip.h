@@ -341,7 +341,7 @@ double aqc_svd_batch_core_ms(void);
  * Gauss-Seidel sweep over all parameters of 1 - |<V,U>|^2/d^2; thetas are updated in place and
  * the objective at the end of the sweep is returned.  cx / cz entanglers only (:818-827).
  * A single-lane workspace (batch == 1).  Where aqc_ws_cd_fits_one_launch this is aqc_ws_cd_sweeps(ws, thetas_io, fobj, 1, -1);
- * larger problems, and every problem where the environment has AQC_CD_CHAIN=1 (cross-checks, timing), take one sweep of the
+ * larger problems, and every problem where the switch AQC_CD_CHAIN is on (cross-checks, timing), take one sweep of the
  * wide walk of aqc_ws_cd_minimize. */
 int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io /* [T] */, double* fobj);
 /* The same walk for EVERY lane of the workspace (lane = an independent problem: a random restart of the ansatz and / or its
@@ -397,6 +397,13 @@ int aqc_ws_sparse_counts(aqc_ws* ws, int64_t* counts);
 int aqc_ws_projected_info(aqc_ws* ws, int32_t* info);
 /* host-only (no GPU needed): the same for the state-vector workspace a context would get at this tiling */
 int aqc_plan_projected(aqc_ctx* ctx, int tile_bits, int low_bits, int32_t* info);
+/* ---- run-time switches: the AQC_* environment variables.  aqc_switches.def, next to this file, is the one table of them: name,
+ * default, when each is read (import / create / call), who reads it, what it selects.  Both calls are host-only (no GPU needed).
+ * Line `index` of the table; returns 1 past the end.  Any output pointer may be NULL. */
+int aqc_switch_info(int index, const char** name, const char** dflt, const char** when, const char** reader, const char** doc);
+/* the value the workspace was created with (a workspace reads its switches once, in aqc_ws_create); an error for a name that is not
+ * a `create` switch read by the library */
+int aqc_ws_switch(const aqc_ws* ws, const char* name, int64_t* value);
 /* plan introspection: number of fused stages (kernel launches) of V^H and of the sweep */
 int aqc_ws_plan_info(aqc_ws* ws, int which /*0 apply-inverse, 1 sweep, 2 apply-forward*/,
                      int* num_stages, int* tile_bits, int* num_tiles);
@@ -448,7 +455,7 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
  * point is the bad one) and the other lanes finish as if it were not there.  Rewrites buffers Z, W and ZW.  Refuses a Trotter
  * ansatz, like every matrix path.  Sums run in a fixed order: a call repeated gives the same bits, and a lane of a batch gives the
  * bits of the same problem run alone on a workspace with the same plan.  The plan does not depend on the batch below 2^8 elements
- * per lane; above, the tile size may (aqc_ws_plan_info shows it), and AQC_TILE_BITS_APPLY / AQC_TILE_BITS_SWEEP or the tile
+ * per lane; above, the tile size may (aqc_ws_plan_info shows it), and the tile-size switches or the tile
  * arguments of aqc_ws_create pin it. */
 int aqc_ws_lbfgs_mat(aqc_ws* ws, const double* x0, int maxiter, int memory, double gtol, double ftol, double fobj_thr,
                      double fidelity_thr, int max_backtracks, double* x_out, double* f_out, double* fidelity_out,

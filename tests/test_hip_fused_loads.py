@@ -128,7 +128,7 @@ def test_fused_pass_masks_and_grid_shapes(case):
 
 
 def test_fused_pass_with_four_blocks_per_wave():
-    """project_fused_kernel<4> shares the source (AQC_PROJECTED_FUSED_QB=4, read once per process: a fresh one)."""
+    """project_fused_kernel<4> shares the source (AQC_PROJECTED_FUSED_QB=4), in a process of its own."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("from tests.test_hip_fused_loads import _CASES, _check\n"
             "for c in ('uvalid_mask', 'partial_projections'):\n"

@@ -1,7 +1,7 @@
 """CPU builds of the native host code under AddressSanitizer + UBSan (GPU sanitizers are not available on the
 pool; the reference has no sanitizer runs at all): the C restatement of the oracle, the HIP-free
-stage planner, the HIP-free gate walk of the MPS engines and the owning buffer type over a counting allocator, each with a
-self-test driver from tests/native/."""
+stage planner, the HIP-free gate walk of the MPS engines, the owning buffer type over a counting allocator and the run-time
+switches, each with a self-test driver from tests/native/."""
 import os
 import shutil
 import subprocess
@@ -74,3 +74,13 @@ def test_mps_walk_under_asan_ubsan(tmp_path):
         for name, arr in got.items():
             err = maxdiff(arr, sv[f"{key}/{name}"])
             assert err < TOL, f"{key}/{name}: {err:g}"
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_switches_under_asan_ubsan(tmp_path):
+    """The run-time switches (csrc/aqc_switches.h over include/aqc_switches.def): defaults when unset and when empty, the one parsing
+    rule (negative and 64-bit values, trailing garbage), the older spelling of the kernel family, the seconds, the listing."""
+    exe = str(tmp_path / "switches_selftest")
+    _run(["g++", "-std=c++17", *SAN, os.path.join(ROOT, "tests", "native", "switches_selftest.cpp"), "-o", exe])
+    out = _run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert "44 in the table" in out and " 0 failures" in out
