@@ -69,6 +69,8 @@ SIGNATURES = {
     "aqc_xxz_mul_vec": (c_int, [c_int, c_int, c_int, c_double, _D, _D]),
     "aqc_xxz_energy": (c_int, [c_int, c_int, c_int, c_double, _D, _D]),
     "aqc_xxz_evolve": (c_int, [c_int, c_int, c_int, c_int, c_double, _D, _D, _D, POINTER(c_int32)]),
+    "aqc_obs_plan": (c_int, [c_int, c_int, POINTER(c_int32), c_int, c_int] + [POINTER(c_int32)] * 6),
+    "aqc_obs_rdm": (c_int, [c_int, c_int, c_int, _D, c_int, c_int, POINTER(c_int32), _D]),
     "aqc_mps_create": (c_int, [c_int, c_int, POINTER(c_int32), _D, _D, POINTER(_P)]),
     "aqc_mps_destroy": (c_int, [_P]),
     "aqc_mps_clone": (c_int, [_P, POINTER(_P)]),

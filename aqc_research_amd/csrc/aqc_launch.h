@@ -336,6 +336,22 @@ hipError_t launch_xxz_mul(const XxzArgs& a, hipStream_t s);
 hipError_t launch_xxz_step(const XxzArgs& a, hipStream_t s);
 hipError_t launch_xxz_energy(const XxzArgs& a, double* energy /* [lanes] */, hipStream_t s);   // partials, then their fixed-order sum
 
+// aqc_obs.hip (reduced density matrices of 4-qubit sets on the matrix cores, one launch per pass of the plan; rules: aqc_obs_rule.h)
+constexpr int kObsThreads = 256, kObsSubsetCap = 16, kObsGridCap = 512;
+struct ObsArgs {
+    int n, tile_bits, lanes, nsub;     // tile_bits = min(n, kObsTileBits) = |bits|; nsub <= kObsSubsetCap
+    int ksplit;                        // = obs_ksplit(nsub): the waves that share a subset's columns
+    uint32_t bits;                     // the pass's bit set B, a mask of qubits
+    uint16_t subsets[kObsSubsetCap];   // masks of 4 tile-local positions (below max(tile_bits, 4)) each
+    const double2* src;                // [lanes][2^n]
+    double* partial;                   // [lanes][obs_grid_x][nsub][3][16][16]
+};
+int obs_ksplit(int nsub);                    // 4, 2, 1 for 1, 2, more subsets: nsub * ksplit <= kObsSubsetCap units of work, 4 per wave
+unsigned obs_grid_x(int n, int tile_bits);   // blocks per lane: min(2^(n - tile_bits), kObsGridCap), whatever the number of lanes
+hipError_t launch_obs_pass(const ObsArgs& a, hipStream_t s);
+// rho[lane * lane_stride + subset * 256 + 16 a + b] <- the partials added in block order, exactly Hermitian
+hipError_t launch_obs_final(const double* partial, unsigned nblocks, int nsub, int lanes, double2* rho, size_t lane_stride, hipStream_t s);
+
 // aqc_api.cpp: thread-local message behind aqc_last_error(); returns 1
 int set_error(const std::string& msg);
 

@@ -1,9 +1,10 @@
-// C ABI (include/aqc_hip.h): dense zgemm, gate-level building blocks, coordinate descent, MPS helpers.
+// C ABI (include/aqc_hip.h): dense zgemm, gate-level building blocks, the XXZ chain, reduced density matrices, coordinate descent, MPS helpers.
 #include "aqc_ws.h"
 
 #include <chrono>
 
 #include "aqc_cd_rule.h"
+#include "aqc_obs_rule.h"
 #include "aqc_xxz_rule.h"
 
 using namespace aqc;
@@ -204,6 +205,125 @@ int aqc_xxz_evolve(int device, int n, int lanes, int shared_src, double delta, c
     }
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(dst, d_out, sizeof(double2) * count, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- reduced density matrices (one-shot, host pointers; kernels: aqc_obs.hip, plan and partial trace: aqc_obs_rule.h) ----
+
+namespace {
+
+static_assert(AQC_OBS_TILE_BITS == kObsTileBits && AQC_OBS_LOW_BITS == kObsLowBits && AQC_OBS_MAX_SUBSETS == kObsMaxSubsets,
+              "the constants of the header and of the rule");
+
+// requests [count][k] -> masks of qubits (a single qubit is paired with another one: the plan covers sets of 2 to 4)
+int obs_requests(int n, int k, int count, const int32_t* qubits, std::vector<uint32_t>& req) {
+    if (n < kObsMinQubits || n > kObsMaxQubits) return fail("invalid number of qubits %d (%d to %d)", n, (int)kObsMinQubits, (int)kObsMaxQubits);
+    if (count < 1) return fail("expects at least one set of qubits");
+    if (k < 1 || k > kObsSetBits || k > n) return fail("a set holds 1 to min(4, n) qubits, not %d", k);
+    if (!qubits) return fail("null argument");
+    req.assign((size_t)count, 0);
+    for (int s = 0; s < count; ++s) {
+        uint32_t m = 0;
+        for (int i = 0; i < k; ++i) {
+            const int q = qubits[(size_t)s * k + i];
+            if (q < 0 || q >= n) return fail("set %d: qubit %d out of range (%d qubits)", s, q, n);
+            if ((m >> q) & 1u) return fail("set %d: qubit %d is listed twice", s, q);
+            m |= 1u << q;
+        }
+        if (k == 1) m |= (m & 1u) ? 2u : 1u;
+        req[(size_t)s] = m;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int aqc_obs_plan(int n, int npairs, const int32_t* pairs, int max_passes, int max_subsets, int32_t* npasses, int32_t* nsubsets,
+                 int32_t* pass_bits, int32_t* pass_nsub, int32_t* subsets, int32_t* serves) {
+    if (!npasses || !nsubsets) return fail("null argument");
+    std::vector<uint32_t> req;
+    if (obs_requests(n, 2, npairs, pairs, req)) return 1;
+    const ObsPlan plan = obs_plan(n, req);
+    size_t total = 0;
+    for (const ObsPass& p : plan.passes) total += p.subsets.size();
+    *npasses = (int32_t)plan.passes.size();
+    *nsubsets = (int32_t)total;
+    if ((size_t)std::max(max_passes, 0) < plan.passes.size() || (size_t)std::max(max_subsets, 0) < total)
+        return fail("the plan has %zu passes and %zu subsets: the arrays hold %d and %d", plan.passes.size(), total, max_passes, max_subsets);
+    if (!pass_bits || !pass_nsub || !subsets || !serves) return fail("null argument");
+    size_t at = 0;
+    for (size_t p = 0; p < plan.passes.size(); ++p) {
+        const ObsPass& ps = plan.passes[p];
+        int32_t* row = pass_bits + p * kObsTileBits;
+        int filled = 0;
+        for (int q = 0; q < n; ++q)
+            if ((ps.bits >> q) & 1u) row[filled++] = q;
+        for (; filled < kObsTileBits; ++filled) row[filled] = -1;
+        pass_nsub[p] = (int32_t)ps.subsets.size();
+        for (const uint16_t S : ps.subsets) {
+            int m = 0;
+            for (int b = 0; b < kObsTileBits; ++b)
+                if ((S >> b) & 1u) subsets[4 * at + m++] = b;
+            ++at;
+        }
+    }
+    for (int r = 0; r < npairs; ++r) {
+        serves[2 * r] = plan.serve_pass[(size_t)r];
+        serves[2 * r + 1] = plan.serve_subset[(size_t)r];
+    }
+    return 0;
+}
+
+int aqc_obs_rdm(int device, int n, int lanes, const double* src, int k, int nsets, const int32_t* qubits, double* out) {
+    if (!src || !out) return fail("null argument");
+    std::vector<uint32_t> req;
+    if (obs_requests(n, k, nsets, qubits, req)) return 1;
+    if (xxz_args_ok(device, n, lanes, 0.0)) return 1;
+    const ObsPlan plan = obs_plan(n, req);
+    std::vector<size_t> first(plan.passes.size() + 1, 0);
+    size_t max_sub = 0;
+    for (size_t p = 0; p < plan.passes.size(); ++p) {
+        first[p + 1] = first[p] + plan.passes[p].subsets.size();
+        max_sub = std::max(max_sub, plan.passes[p].subsets.size());
+    }
+    for (size_t r = 0; r < req.size(); ++r)
+        if (plan.serve_pass[r] < 0) return fail("set %zu has no place in the plan", r);
+    HIP_OK(hipSetDevice(device));
+    const int tb = std::min(n, (int)kObsTileBits);
+    const unsigned gx = obs_grid_x(n, tb);
+    const size_t count = (size_t)lanes << n, total = first.back();
+    DevBuf<double2> d_src, d_rho;
+    DevBuf<double> d_part;
+    if (d_src.alloc(count) || d_rho.alloc((size_t)lanes * total * 256) || d_part.alloc((size_t)lanes * gx * max_sub * 768)) return 1;
+    HIP_OK(hipMemcpy(d_src, src, sizeof(double2) * count, hipMemcpyHostToDevice));
+    for (size_t p = 0; p < plan.passes.size(); ++p) {
+        const ObsPass& ps = plan.passes[p];
+        ObsArgs a{};
+        a.n = n; a.tile_bits = tb; a.lanes = lanes; a.nsub = (int)ps.subsets.size(); a.ksplit = obs_ksplit(a.nsub); a.bits = ps.bits;
+        for (size_t s = 0; s < ps.subsets.size(); ++s) a.subsets[s] = ps.subsets[s];
+        a.src = d_src; a.partial = d_part;
+        HIP_OK(launch_obs_pass(a, nullptr));
+        HIP_OK(launch_obs_final(d_part, gx, a.nsub, lanes, static_cast<double2*>(d_rho) + first[p] * 256, total * 256, nullptr));
+    }
+    HIP_OK(hipDeviceSynchronize());
+    std::vector<double2> rho((size_t)lanes * total * 256);
+    HIP_OK(hipMemcpy(rho.data(), d_rho, sizeof(double2) * rho.size(), hipMemcpyDeviceToHost));
+    // the partial traces, on the host: the place of every listed qubit in its subset's row index
+    const size_t msize = (size_t)2 << (2 * k);   // doubles of a 2^k x 2^k matrix
+    for (int s = 0; s < nsets; ++s) {
+        const ObsPass& ps = plan.passes[(size_t)plan.serve_pass[(size_t)s]];
+        const uint32_t S = ps.subsets[(size_t)plan.serve_subset[(size_t)s]];
+        int pos[kObsSetBits];
+        for (int m = 0; m < k; ++m) {
+            const int q = qubits[(size_t)s * k + m];
+            const int local = __builtin_popcount(ps.bits & ((1u << q) - 1));
+            pos[m] = __builtin_popcount(S & ((1u << local) - 1));
+        }
+        const size_t which = first[(size_t)plan.serve_pass[(size_t)s]] + (size_t)plan.serve_subset[(size_t)s];
+        for (int l = 0; l < lanes; ++l)
+            obs_partial_trace(reinterpret_cast<const double*>(rho.data() + ((size_t)l * total + which) * 256), k, pos,
+                              out + ((size_t)l * nsets + (size_t)s) * msize);
+    }
     return 0;
 }
 

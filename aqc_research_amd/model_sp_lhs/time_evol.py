@@ -72,6 +72,7 @@ class UserOptions:
         self.vectorised_lbfgs = False      # restarts driven by ONE vectorised L-BFGS (batched_optimizer.py) instead of scipy per lane
         self.device_lbfgs = False          # ... and that L-BFGS resident on the device (aqc_ws_lbfgs), thetas never leave HBM
         self.ground_truth = "trotter"      # |t1_gt>: "trotter" (10x the steps, as the reference) or "exact" (exp(-iHt)|ini> by xxz.xxz_evolve)
+        self.observables = False           # True: every horizon's record gains "observables" (magnetisation, bond energies; dense states only)
         self.__dict__.update(kw)
         if self.ground_truth not in ("trotter", "exact"):
             raise ValueError(f"ground_truth must be 'trotter' or 'exact', got {self.ground_truth!r}")
@@ -142,6 +143,8 @@ def generate_target(opts: UserOptions, my_id: int) -> TargetState:
     n, steps, t = opts.num_qubits, int(opts.trotter_steps[my_id]), float(opts.evol_times[my_id])
     states = []
     exact = opts.ground_truth == "exact"
+    if opts.observables and opts.use_mps and n > _DENSE_MAX_QUBITS:
+        raise ValueError(f"observables=True needs dense states: at most {_DENSE_MAX_QUBITS} qubits with an MPS objective")
     if exact:
         if opts.use_mps and n > _DENSE_MAX_QUBITS:
             raise ValueError(f"ground_truth='exact' needs a dense state: at most {_DENSE_MAX_QUBITS} qubits with an MPS objective")
@@ -172,6 +175,25 @@ def fidelity(state1: State, state2: State) -> float:
     if not (check_mps(state1) and check_mps(state2)):
         raise ValueError("fidelity: expects two vectors or two MPS")
     return float(np.abs(mps_dot(state1, state2)) ** 2)
+
+
+def _dense_of(state: State) -> np.ndarray:
+    if isinstance(state, DenseBackedMPS):
+        return state.dense_state
+    if isinstance(state, np.ndarray):
+        return state
+    raise ValueError("observables=True covers dense states only (vectors or DenseBackedMPS)")
+
+
+def _observables_entry(opts: UserOptions, a1: State, t1_gt: State) -> Dict:
+    """<Z_i> and the bond energies of the compiled state and of the ground truth (observables.py), both states as two lanes of one call
+    each; the figures of the ground truth carry the suffix ``_gt``."""
+    from ..observables import bond_energies, magnetisation
+
+    both = np.ascontiguousarray(np.stack([_dense_of(a1), _dense_of(t1_gt)]), dtype=np.complex128)
+    mag = magnetisation(both, "z", device=opts.device)
+    bonds = bond_energies(both, float(opts.delta), device=opts.device)
+    return {"magnetisation": mag[0], "bond_energies": bonds[0], "magnetisation_gt": mag[1], "bond_energies_gt": bonds[1]}
 
 
 def _create_objective(*, opts: UserOptions, circ, target: State, layer_range: Optional[Tuple[int, int]]):
@@ -246,7 +268,9 @@ def _time_evolution(*, opts: UserOptions, num_layers: int, num_expansions: int, 
     if opts.use_mps:                   # the final figures are recomputed without truncation (:301-310)
         a1 = _evolved_state(opts, circ, a_state_result["thetas"], no_truncation_threshold())
         fid_a1_vs_gt = fidelity(a1, target.t1_gt)
+    extras = {"observables": _observables_entry(opts, a1, target.t1_gt)} if opts.observables else {}
     return {
+        **extras,
         "fid_a1_vs_gt": fid_a1_vs_gt, "fid_t1_vs_gt": fid_t1_vs_gt, "fid_a1_vs_t1": fidelity(a1, target.t1),
         "num_qubits": opts.num_qubits, "num_layers": num_layers, "block_reps": 3, "entangler": str(a_state_result["entangler"]),
         "num_trotter_steps": target.num_trot_steps, "evol_time1": target.evol_time, "thetas": a_state_result["thetas"].copy(),
@@ -318,6 +342,12 @@ def _seeded_horizon_job(job_index: int, cfg: Dict) -> Dict:
 
     common = {"horizon": h, "evol_time": evol_time, "num_layers": circ.num_layers, "num_thetas": circ.num_thetas,
               "fid_t1_vs_gt": fid_t1_vs_gt, "fidelity_thr": fid_thr}
+
+    def finish(record: Dict) -> Dict:
+        if opts.observables:   # of the best restart's state at its final thetas
+            record["observables"] = _observables_entry(opts, _evolved_state(opts, circ, record["thetas"], no_truncation_threshold()), target)
+        return record
+
     if opts.vectorised_lbfgs or opts.device_lbfgs:   # all restarts as lanes of one batched objective, one optimizer for all of them
         from ..batched_optimizer import BatchedSurrogateObjective, batched_lbfgs
 
@@ -348,9 +378,9 @@ def _seeded_horizon_job(job_index: int, cfg: Dict) -> Dict:
                         objv, circ, starts[s_no], stopper=EarlyStopper(fidelity_thr=fid_thr), timeout=TimeoutChecker(time_limit=opts.time_limit))
                     recs.append(r)
                 best = int(np.argmax([r["fidelity"] for r in recs]))
-                return dict(common, fidelity=float(recs[best]["fidelity"]), cost=float(recs[best]["cost"]), thetas=recs[best]["thetas"].copy(),
-                            best_restart=best, fidelities=[float(r["fidelity"]) for r in recs], num_fun_ev=int(sum(r["num_fun_ev"] for r in recs)),
-                            route="single-lane engine, one restart after the other")
+                return finish(dict(common, fidelity=float(recs[best]["fidelity"]), cost=float(recs[best]["cost"]), thetas=recs[best]["thetas"].copy(),
+                                   best_restart=best, fidelities=[float(r["fidelity"]) for r in recs],
+                                   num_fun_ev=int(sum(r["num_fun_ev"] for r in recs)), route="single-lane engine, one restart after the other"))
         else:
             dense = (target.dense_state if isinstance(target, DenseBackedMPS) else mps_to_vector(target)) if opts.use_mps else target
             bo = BatchedSurrogateObjective(circ, np.tile(dense, (opts.num_seeds, 1)), base_index=ini, device=opts.device)
@@ -362,14 +392,14 @@ def _seeded_horizon_job(job_index: int, cfg: Dict) -> Dict:
         evals = bo.num_evals
         bo.close()
         best = int(np.argmax(fids))
-        return dict(common, fidelity=float(fids[best]), cost=float(res["fun"][best]), thetas=res["x"][best].copy(), best_restart=best,
-                    fidelities=[float(v) for v in fids], num_fun_ev=int(evals))
+        return finish(dict(common, fidelity=float(fids[best]), cost=float(res["fun"][best]), thetas=res["x"][best].copy(), best_restart=best,
+                           fidelities=[float(v) for v in fids], num_fun_ev=int(evals)))
     recs = run_jobs_lockstep(circ, [{} for _ in range(opts.num_seeds)], opts.seed + 1000 * h, restart,
                              nlanes=min(64, opts.num_seeds), device=opts.device)
     ok = [r for r in recs if r["status"] == "ok"]
     best = max(ok, key=lambda r: r["fidelity"])
-    return dict(common, fidelity=best["fidelity"], cost=best["cost"], thetas=best["thetas"], best_restart=best["restart"],
-                fidelities=[r["fidelity"] for r in ok], num_fun_ev=int(sum(r["num_fun_ev"] for r in ok)))
+    return finish(dict(common, fidelity=best["fidelity"], cost=best["cost"], thetas=best["thetas"], best_restart=best["restart"],
+                       fidelities=[r["fidelity"] for r in ok], num_fun_ev=int(sum(r["num_fun_ev"] for r in ok))))
 
 
 def run_simulation(opts: Optional[UserOptions] = None) -> List[Dict]:

@@ -222,6 +222,26 @@ int aqc_xxz_energy(int device, int n, int lanes, double delta, const double* src
 int aqc_xxz_evolve(int device, int n, int lanes, int shared_src, double delta, const double* times /* [lanes] */, const double* src,
                    double* dst, int32_t* terms_out);
 
+/* ---- reduced density matrices of up to 4 qubits of [lanes][2^n] c128 state vectors in HOST memory, 2 <= n <= 30 (inputs are only
+ * read).  Convention: index bit q is qubit q; for listed qubits (q_0 .. q_k-1) the matrix's row index has bit m = the value of q_m,
+ * rho[a][b] = sum_rest psi(rest, a) conj psi(rest, b).  Every matrix is a partial trace of the 16 x 16 matrix of a set of 4 qubits,
+ * a Gram product on the fp64 matrix cores; the plan (csrc/aqc_obs_rule.h) groups the sets into passes over the state: a pass is a
+ * set of min(n, AQC_OBS_TILE_BITS) tile bits (the low AQC_OBS_LOW_BITS among them when n is larger) and carries at most
+ * AQC_OBS_MAX_SUBSETS 4-subsets of it.  Sums run in a fixed order: two calls give the same bits, whatever the number of lanes.
+ * aqc_obs_plan: host only, needs no device.  pairs [npairs][2] (two different qubits each, either order).  Outputs: *npasses and
+ *   *nsubsets always; with max_passes >= *npasses and max_subsets >= *nsubsets (else an error) also pass_bits
+ *   [max_passes][AQC_OBS_TILE_BITS] (the qubits of the pass ascending, -1 beyond), pass_nsub [max_passes], subsets [max_subsets][4]
+ *   (tile-local positions ascending -- position j is the j-th lowest qubit of the pass; with n < 4 the positions n .. 3 are virtual
+ *   qubits that are always 0 -- the subsets of pass 0 first) and serves [npairs][2] = the (pass, subset within the pass) a pair is
+ *   read from, the first in plan order that holds it.
+ * aqc_obs_rdm: out [lanes][nsets][2^k][2^k] c128 for the nsets >= 1 sets qubits [nsets][k] of 1 <= k <= min(4, n) different qubits. */
+#define AQC_OBS_TILE_BITS 11
+#define AQC_OBS_LOW_BITS 5
+#define AQC_OBS_MAX_SUBSETS 16
+int aqc_obs_plan(int n, int npairs, const int32_t* pairs, int max_passes, int max_subsets, int32_t* npasses, int32_t* nsubsets,
+                 int32_t* pass_bits, int32_t* pass_nsub, int32_t* subsets, int32_t* serves);
+int aqc_obs_rdm(int device, int n, int lanes, const double* src, int k, int nsets, const int32_t* qubits, double* out);
+
 /* ---- device-resident MPS with truncated 2-qubit gates: the arithmetic the reference hands to qiskit-aer's
  * matrix_product_state simulator (mps_operations.py:216-298 mps_from_circuit / qcircuit_mul_mps; gate level:
  * mps_dot_objective.py:245-468).  Qiskit MPS format in and out (mps_operations.py:33): `dims` = n+1 bond
