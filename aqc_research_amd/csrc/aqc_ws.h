@@ -371,6 +371,9 @@ void drop_graphs(aqc_ws* ws);
 // aqc_ws_project.cpp
 void proj_plan(aqc_ws* ws, int low_bits);   // decides the route and lowers the virtual plan (host only)
 int proj_alloc(aqc_ws* ws);                 // its device side (plan tables, buffers, offset tables)
+// Launches over a tile list (the sparse route, its restricted V^H, the projected route) are persistent on 2^12 tiles: without the
+// persistent V / V^H (AQC_APPLY_PERSIST <= 0) such a workspace has none of them and every evaluation takes the dense route
+bool list_launches_allowed(const aqc_ws* ws);
 bool sweep_route_projected(const aqc_ws* ws, bool sparse);
 bool projected_pairs(const aqc_ws* ws);      // the route's independent tile launches run in pairs
 Stage3Args virtual_stage3_args(aqc_ws* ws, const DevPlan& v, size_t s);   // stage s of a virtual plan (vsw, vinv) on the virtual register, over its item list

@@ -37,7 +37,7 @@ void proj_plan(aqc_ws* ws, int low_bits) {
     const Program& prog = ws->ctx->prog;
     const DevPlan& p = ws->sweep;
     if (!ws->sw.projected || !ws->sw.sparse_sweep || !ws->inv_mirrored || !p.v3 || ws->col_bits != 0 || ws->ncols != 1 ||
-        p.plan.stages.size() < 2 || prog.n > 30)
+        p.plan.stages.size() < 2 || prog.n > 30 || !list_launches_allowed(ws))
         return;
     const int n = prog.n;
     uint64_t L0 = 0, T = 0;
@@ -143,6 +143,7 @@ int proj_alloc(aqc_ws* ws) {
     return 0;
 }
 
+bool list_launches_allowed(const aqc_ws* ws) { return ws->sweep.k < 12 || ws->sw.apply_persist > 0; }   // (mirrored V^H: the sweep's tile size)
 bool sweep_route_projected(const aqc_ws* ws, bool sparse) { return sparse && ws->proj.ok; }
 
 static ProjArgs proj_args(aqc_ws* ws);

@@ -371,6 +371,7 @@ void drop_graphs(aqc_ws* ws) {
 static bool sweep_route_sparse(const aqc_ws* ws, int x_buf, bool will_vdag) {
     const DevPlan& p = ws->sweep;
     if (!ws->sw.sparse_sweep || !p.v3 || !ws->inv_mirrored || p.h_stages.size() < 2) return false;
+    if (!list_launches_allowed(ws)) return false;   // (every launch of the route over a tile list, lazy Z and the projected route included, hangs on this answer)
     if (!ws->combo_valid[x_buf] || !ws->d_combo_prev[x_buf]) return false;          // support of the lhs state known on the device
     if (!(will_vdag ? keeps_checkpoint(ws, true, AQC_BUF_Y, AQC_BUF_Z) : (ws->ckpt_valid || ws->proj_y0_ready))) return false;   // z of stage 1 available in ZW (or projected already)
     return (long)p.ntiles * ws->batch >= ws->sw.sparse_min_items;   // (fewer items than CUs: a stage takes one item's time either way)

@@ -95,7 +95,9 @@ class LaneView:
 
     # A lane's objective()/gradient() pair as ONE request (Workspace.surrogate_eval): with it every lane of a round files the
     # same kind of request whatever state leads, so a round is one native call.
-    prefers_surrogate_eval = os.environ.get("AQC_LOCKSTEP_SURROGATE_EVAL", "1") != "0"   # 0: the per-call requests of round 2 (cross-check)
+    @property
+    def prefers_surrogate_eval(self) -> bool:   # read by every evaluation that asks (a `call` switch); 0: the per-call requests (cross-check)
+        return os.environ.get("AQC_LOCKSTEP_SURROGATE_EVAL", "1") != "0"
 
     def surrogate_eval(self, thetas, weight: np.ndarray, max_no: np.ndarray, update_state=True,
                        block_range: Optional[Tuple[int, int]] = None, front_layer: bool = True):
