@@ -72,14 +72,15 @@ struct aqc_mpsb {
     PinBuf<double> h_thetas;     // pinned staging of the same
     int T_cap = 0;               // thetas per lane the two are laid out for (a shape, like nvals)
     DevBuf<int> status;          // [L] status bits | [L] largest bond a gate has produced
-    // environments of the pair (w, z), see aqc_mps_engine.cpp
+    // environments of the pair (w, z): which of them are current (aqc_mps_gradwalk.h), and their buffers
+    PairEnvs envs;
     DevBuf<double2> env_l;       // [L][n + 1][kLaneEnv]
     DevBuf<double2> env_r;       // [L][n][kLaneEnv]
     DevBuf<double2> e0;          // [L][kLaneEnv]
     DevBuf<double2> e1;
     DevBuf<double2> vals;        // [L][nvals]
     PinBuf<char> h_out;          // pinned: vals | status+peak | discarded | dims of vh
-    int nvals = 0, valid_l = 0, valid_r = 0;
+    int nvals = 0;
     int hint = kLaneCap;         // bonds the launches are sized for
     int peak_vh = 0, peak_grad = 0;   // largest bond the gates of the last V^H / gradient phase produced (0: none yet)
     int active = 0;              // lanes the gate launches cover (all, or the first half while V^H runs for lanes that repeat it)
@@ -241,97 +242,61 @@ int apply_circuit_all(aqc_mpsb* b, Lanes& s, const aqc_circuit* c, int T, bool i
     return 0;
 }
 
-// ---- environments of the pair (w, z), all lanes per launch (same scheme as struct Environments of aqc_mps_engine.cpp) -------------------------
+// ---- the lanes' executor of the gradient walk (aqc_mps_gradwalk.h), all lanes per launch: w = lhs, z = vh (both consumed) ------------------
 constexpr size_t kEnvL(int n) { return (size_t)(n + 1) * kLaneEnv; }
 constexpr size_t kEnvR(int n) { return (size_t)n * kLaneEnv; }
 
-int env_init(aqc_mpsb* b) {
-    HIP_OK(launch_lanes_env_init(b->env_l, kEnvL(b->n), b->env_r + (size_t)(b->n - 1) * kLaneEnv, kEnvR(b->n), b->L, b->st));
-    b->valid_l = 0;
-    b->valid_r = b->n - 1;
-    return 0;
-}
-void env_touched(aqc_mpsb* b, int lo, int hi) { b->valid_l = std::min(b->valid_l, lo); b->valid_r = std::max(b->valid_r, hi); }
-
-// out[u][v] = sum_bit sum_xy conj(A_p[bit][x][u]) in[x][y] B_p[bit][y][v]; `op` (may be null) sits on w's side of site p
-int step_left_all(aqc_mpsb* b, int p, const double2* in, size_t in_stride, const M2* op, double2* out, size_t out_stride) {
-    double g8[8];
-    if (op) pack(adjoint(*op), g8);
-    HIP_OK(launch_lanes_env_left(b->w.dev, b->z.dev, p, in, in_stride, out, out_stride, op ? g8 : nullptr, b->L, b->st));
-    return 0;
-}
-// left environments up to site lo, right environments down to site hi
-int env_advance(aqc_mpsb* b, int lo, int hi) {
-    const int n = b->n;
-    for (; b->valid_l < lo; ++b->valid_l) {
-        const int p = b->valid_l;
-        if (step_left_all(b, p, b->env_l + (size_t)p * kLaneEnv, kEnvL(n), nullptr, b->env_l + (size_t)(p + 1) * kLaneEnv, kEnvL(n))) return 1;
+struct LanesExec {
+    aqc_mpsb* b;
+    int T; double trunc_thr; int max_bond;   // what the gates of a walk run with
+    double2* env_l(int p) const { return b->env_l + (size_t)p * kLaneEnv; }
+    double2* env_r(int p) const { return b->env_r + (size_t)p * kLaneEnv; }
+    double2* scratch(int k) const { return k ? b->e1 : b->e0; }
+    // out[u][v] = sum_bit sum_xy conj(A_p[bit][x][u]) in[x][y] B_p[bit][y][v]; `op` (may be null) sits on w's side of site p
+    int step_left(int p, const double2* in, size_t in_stride, const M2* op, double2* out, size_t out_stride) {
+        double g8[8];
+        if (op) pack(adjoint(*op), g8);
+        HIP_OK(launch_lanes_env_left(b->w.dev, b->z.dev, p, in, in_stride, out, out_stride, op ? g8 : nullptr, b->L, b->st));
+        return 0;
     }
-    for (; b->valid_r > hi; --b->valid_r) {   // Rc[p - 1][x][y] = sum_bit A_p[bit][x][u] (Rc[p] B_p[bit]^H)[u][y]
-        const int p = b->valid_r;
-        HIP_OK(launch_lanes_env_right(b->w.dev, b->z.dev, p, b->env_r + (size_t)p * kLaneEnv, kEnvR(n), b->env_r + (size_t)(p - 1) * kLaneEnv, kEnvR(n), b->L,
-                                      b->st));
+    int left(int p) { return step_left(p, env_l(p), kEnvL(b->n), nullptr, env_l(p + 1), kEnvL(b->n)); }
+    int right(int p) {   // Rc[p - 1][x][y] = sum_bit A_p[bit][x][u] (Rc[p] B_p[bit]^H)[u][y]
+        HIP_OK(launch_lanes_env_right(b->w.dev, b->z.dev, p, env_r(p), kEnvR(b->n), env_r(p - 1), kEnvR(b->n), b->L, b->st));
+        return 0;
     }
-    return 0;
-}
-// vals[l][slot] = <(G_1 on q_1)(G_2 on q_2) w_l | z_l>, q_1 < q_2 (nops = 1: only q_1)
-int dot_all(aqc_mpsb* b, int slot, int nops, const int* q, const M2* const* g) {
-    if (slot >= b->nvals) return failf("inner-product slot out of range");
-    const int lo = q[0], hi = q[nops - 1], n = b->n;
-    if (env_advance(b, lo, hi)) return 1;
-    const double2* cur = b->env_l + (size_t)lo * kLaneEnv;
-    size_t cur_stride = kEnvL(n);
-    double2* pp[2] = {b->e0, b->e1};
-    for (int p = lo; p <= hi; ++p) {
-        const M2* op = p == q[0] ? g[0] : (nops > 1 && p == q[1] ? g[1] : nullptr);
-        double2* out = pp[(p - lo) & 1];
-        if (step_left_all(b, p, cur, cur_stride, op, out, kLaneEnv)) return 1;
-        cur = out;
-        cur_stride = kLaneEnv;
+    int chain(int p, bool first, int k, const M2* op) {
+        return step_left(p, first ? env_l(p) : scratch(k ^ 1), first ? kEnvL(b->n) : kLaneEnv, op, scratch(k), kLaneEnv);
     }
-    HIP_OK(launch_lanes_env_dot(b->w.dev, b->z.dev, hi, cur, cur_stride, b->env_r + (size_t)hi * kLaneEnv, kEnvR(n), b->vals, b->nvals, slot, b->L, b->st));
-    return 0;
-}
-
-// the gate-by-gate gradient walk (gradient_steps of aqc_mps_walk.h) on every lane: w = lhs, z = vh (both consumed); the inner products go
-// to slots slot0, slot0 + 1, ... of vals; rec = (theta index, factor) per slot
-int gradient_all(aqc_mpsb* b, const aqc_circuit* c, int T, double trunc_thr, int max_bond, int lo_blk, int hi_blk, bool front_layer, int slot0,
-                 std::vector<std::pair<int, cd>>& rec) {
-    const int n = b->n;
-    rec.clear();
-    for (const GradStep& s : gradient_steps(c, n, lo_blk, hi_blk, front_layer)) {
-        if (s.kind == GradStep::RecordP11) {
-            const int qq[2] = {s.q, s.q2};
-            const M2* gg[2] = {&kProj1, &kProj1};
-            if (dot_all(b, slot0 + (int)rec.size(), 2, qq, gg)) return 1;
-            rec.emplace_back(s.tindex, s.factor);
-        } else if (s.kind == GradStep::Entangle) {
-            if (gate2_pair_all(b, b->z, &b->w, s.q, s.q2, s.ent, T, trunc_thr, max_bond)) return 1;
-            env_touched(b, std::min(s.q, s.q2), std::max(s.q, s.q2));
-        } else if (!s.recorded) {
-            for (int k = 0; k < s.count; ++k) {
-                if (gate1_all(b, b->w, s.q, s.r[k].g, T, &b->z)) return 1;
-                env_touched(b, s.q, s.q);
-            }
-        } else {
-            // consecutive parameters on one site: per parameter the rotation on both operands + its inner product <P w|z>, up to three of
-            // them in one launch (the environments do not involve the site: they are advanced once, in front)
-            const int slot = slot0 + (int)rec.size();
-            if (slot + s.count > b->nvals) return failf("inner-product slot out of range");
-            if (env_advance(b, s.q, s.q)) return 1;
-            LaneSteps st{};
-            st.count = s.count;
-            for (int k = 0; k < s.count; ++k) {
-                st.g[k] = s.r[k].g;
-                pack(adjoint(pauli_of(s.r[k].pauli)), st.gh[k]);
-            }
-            HIP_OK(launch_lanes_grad_step(b->w.dev, b->z.dev, s.q, st, b->thetas, T, b->env_l + (size_t)s.q * kLaneEnv, kEnvL(n), b->env_r + (size_t)s.q * kLaneEnv,
-                                          kEnvR(n), b->e0, b->vals, b->nvals, slot, b->L, b->st));
-            env_touched(b, s.q, s.q);
-            for (int k = 0; k < s.count; ++k) rec.emplace_back(s.r[k].tindex, s.factor);
+    int close(int hi, int k, int slot) {
+        if (slot >= b->nvals) return failf("inner-product slot out of range");
+        HIP_OK(launch_lanes_env_dot(b->w.dev, b->z.dev, hi, scratch(k), kLaneEnv, env_r(hi), kEnvR(b->n), b->vals, b->nvals, slot, b->L, b->st));
+        return 0;
+    }
+    int entangle(const GradStep& s) { return gate2_pair_all(b, b->z, &b->w, s.q, s.q2, s.ent, T, trunc_thr, max_bond); }
+    int rotate(int q, const LaneGate1& g) { return gate1_all(b, b->w, q, g, T, &b->z); }
+    // consecutive parameters on one site: per parameter the rotation on both operands + its inner product <P w|z>, up to three of
+    // them in one launch (the environments do not involve the site: they are advanced once, in front)
+    int rotate_recorded(PairEnvs& env, const GradStep& s, int slot) {
+        if (slot + s.count > b->nvals) return failf("inner-product slot out of range");
+        if (env_advance(*this, env, s.q, s.q)) return 1;
+        LaneSteps st{};
+        st.count = s.count;
+        for (int k = 0; k < s.count; ++k) {
+            st.g[k] = s.r[k].g;
+            pack(adjoint(pauli_of(s.r[k].pauli)), st.gh[k]);
         }
+        HIP_OK(launch_lanes_grad_step(b->w.dev, b->z.dev, s.q, st, b->thetas, T, env_l(s.q), kEnvL(b->n), env_r(s.q), kEnvR(b->n), b->e0, b->vals, b->nvals, slot,
+                                      b->L, b->st));
+        env.touched(s.q, s.q);
+        return 0;
     }
-    return 0;
+};
+
+// the gate-by-gate gradient walk on every lane; the inner products go to slots slot0, slot0 + 1, ... of vals; rec = (theta index, factor) per slot
+int gradient_all(aqc_mpsb* b, const aqc_circuit* c, int T, double trunc_thr, int max_bond, int lo_blk, int hi_blk, bool front_layer, int slot0,
+                 GradRecords& rec) {
+    LanesExec ex{b, T, trunc_thr, max_bond};
+    return gradient_walk(ex, b->envs, gradient_steps(c, b->n, lo_blk, hi_blk, front_layer), slot0, rec);
 }
 
 int load_lanes(aqc_mpsb* b, Lanes& dst, aqc_mps* const* src, int shared) {   // dst.L states (the lanes', or the bank's K)
@@ -398,8 +363,9 @@ int begin(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, double tru
     if (!(trunc_thr >= 0.0)) return failf("trunc_thr must be non-negative");
     if (max_bond > kLaneCap) return refuse("the lockstep lanes keep bonds up to %d", kLaneCap);
     HIP_OK(hipSetDevice(b->device));
-    const int n = b->n, L = b->L, tpb = thetas_per_block(circ), T = 3 * n + tpb * circ->num_blocks;
-    const int need = num_amps + 3 * n + tpb * (int)blocks_of(circ).size();
+    const int n = b->n, L = b->L;
+    const WalkSizes sz = walk_sizes(circ, n);
+    const int T = sz.T, need = num_amps + sz.max_records;
     const auto out_size = [&](int nv) { return sizeof(double2) * (size_t)L * nv + sizeof(int) * 2 * (size_t)L + sizeof(double) * (size_t)L + sizeof(int) * (size_t)L * (n + 1); };
     if (need > b->nvals || T > b->T_cap) {
         HIP_OK(hipStreamSynchronize(b->st));
@@ -442,21 +408,24 @@ int form_vh(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half, bool inverse
 // (w, z) = (lhs, zsrc) with fresh environments: where a gradient walk and the amplitudes start
 int start_pair(aqc_mpsb* b, const Lanes& zsrc) {
     if (clone(b, b->lhs, b->w) || clone(b, zsrc, b->z)) return 1;
-    return env_init(b);
+    HIP_OK(launch_lanes_env_init(b->env_l, kEnvL(b->n), b->env_r + (size_t)(b->n - 1) * kLaneEnv, kEnvR(b->n), b->L, b->st));
+    b->envs.reset(b->n);
+    return 0;
 }
 
 // vh as above, (w, z) = (lhs, vh), and the amplitudes <lhs|vh> (slot 0), <X_q lhs|vh> (slots 1 + q)
 int enqueue_vh(aqc_mpsb* b, const aqc_circuit* circ, int T, bool half, int num_amps) {
     if (form_vh(b, circ, T, half) || start_pair(b, b->vh)) return 1;
+    LanesExec ex{b, T, b->cur_trunc, b->cur_max_bond};
     for (int k = 1; k < num_amps; ++k) {   // flips first: site 0 upwards, the right environments are built once on the way down to site 0
         const int q = k - 1;
         const M2* g = &kPauliX;
-        if (dot_all(b, k, 1, &q, &g)) return 1;
+        if (env_dot(ex, b->envs, k, 1, &q, &g)) return 1;
     }
     const int q = b->n - 1;
     const M2 eye = {{1.0, 0.0, 0.0, 1.0}};
     const M2* g = &eye;
-    return dot_all(b, 0, 1, &q, &g);
+    return env_dot(ex, b->envs, 0, 1, &q, &g);
 }
 
 // The same for a bank of lhs states (aqc_mpsb_vh_bank): vh as above, then amps[l][k] = <bank_k|vh_l> in slots k of vals, one launch for all
@@ -513,12 +482,8 @@ Readback readback(const aqc_mpsb* b) {
     return Readback{reinterpret_cast<const cd*>(h_vals), reinterpret_cast<const double*>(h_disc), reinterpret_cast<const int*>(h_disc + sizeof(double) * L)};
 }
 // grad[lane][T] from the recorded inner products (slots slot0, slot0 + 1, ...)
-void assemble(const aqc_mpsb* b, const Readback& r, const std::vector<std::pair<int, cd>>& rec, int slot0, int T, cd* grad) {
-    for (int l = 0; l < b->L; ++l) {
-        cd* g = grad + (size_t)l * T;
-        std::fill(g, g + T, cd(0.0, 0.0));
-        for (size_t i = 0; i < rec.size(); ++i) g[rec[i].first] += rec[i].second * r.vals[(size_t)l * b->nvals + slot0 + i];
-    }
+void assemble(const aqc_mpsb* b, const Readback& r, const GradRecords& rec, int slot0, int T, cd* grad) {
+    for (int l = 0; l < b->L; ++l) assemble_gradient(rec, r.vals + (size_t)l * b->nvals + slot0, T, grad + (size_t)l * T);
 }
 
 // One phase of work on all lanes, the skeleton of every evaluating entry point: the status words cleared, `enqueue` (the entry point's
@@ -739,10 +704,11 @@ int aqc_mpsb_grad(aqc_mpsb* b, const aqc_circuit* circ, int block_from, int bloc
     if (!b->have_lhs) return failf("set the lhs states of the lanes first");
     if (check_circuit(circ, b->n)) return 1;
     HIP_OK(hipSetDevice(b->device));
-    const int n = b->n, tpb = thetas_per_block(circ), T = 3 * n + tpb * circ->num_blocks;
-    if (T != b->cur_T || 3 * n + tpb * (int)blocks_of(circ).size() > b->nvals) return failf("aqc_mpsb_grad: not the circuit of the last aqc_mpsb_vh");
+    const WalkSizes sz = walk_sizes(circ, b->n);
+    const int T = sz.T;
+    if (T != b->cur_T || sz.max_records > b->nvals) return failf("aqc_mpsb_grad: not the circuit of the last aqc_mpsb_vh");
     if (check_block_range(circ, block_from, block_to)) return 1;
-    std::vector<std::pair<int, cd>> rec;
+    GradRecords rec;
     b->hint = next_hint(b);
     if (const int rc = run_phase(b, &b->peak_grad, true, nullptr, nullptr, [&] {
             return start_pair(b, b->vh) || gradient_all(b, circ, T, b->cur_trunc, b->cur_max_bond, block_from, block_to, front_layer != 0, 0, rec);
@@ -761,7 +727,7 @@ int aqc_mpsb_gradient_of(aqc_mpsb* b, const aqc_circuit* circ, const double* the
     int T = 0;
     if (const int rc = begin(b, circ, thetas, trunc_thr, max_bond, 0, &T)) return rc;
     if (check_block_range(circ, block_from, block_to)) return 1;
-    std::vector<std::pair<int, cd>> rec;
+    GradRecords rec;
     if (const int rc = run_phase(b, &b->peak_grad, false, nullptr, nullptr, [&] {   // (vh is not involved: z starts from the states given as targets)
             return start_pair(b, b->target) || gradient_all(b, circ, T, trunc_thr, max_bond, block_from, block_to, front_layer != 0, 0, rec);
         }))
@@ -778,7 +744,7 @@ int aqc_mpsb_eval(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, do
     int T = 0;
     if (const int rc = begin(b, circ, thetas, trunc_thr, max_bond, 1, &T)) return rc;
     if (check_block_range(circ, block_from, block_to)) return 1;
-    std::vector<std::pair<int, cd>> rec;
+    GradRecords rec;
     if (const int rc = run_phase(b, &b->peak_vh, true, discarded_out, max_bond_out, [&] {   // enqueue_vh leaves (w, z) = (lhs, vh), environments started
             return enqueue_vh(b, circ, T, false, 1) || gradient_all(b, circ, T, trunc_thr, max_bond, block_from, block_to, front_layer != 0, 1, rec);
         }))

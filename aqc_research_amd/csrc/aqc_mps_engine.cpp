@@ -324,27 +324,26 @@ int apply_circuit(aqc_mps* m, const aqc_circuit* c, const double* th, bool inver
     return 0;
 }
 
-// Environments of the pair (w, z) for <(ops) w|z>: L[q] = contraction of the sites < q ([chi_w][chi_z]), Rc[q] = the
-// CONJUGATE of the contraction of the sites > q.  A gate on sites [lo, hi] leaves L[<= lo] and Rc[>= hi] valid, so
-// the ~T inner products of one gradient cost a few site steps each instead of a full chain of n.
+// The single-lane executor of the gradient walk (aqc_mps_gradwalk.h: validity of the environments, the chain of an inner product and
+// the step driver are stated there): the buffers of L[q] ([chi_w][chi_z]) and Rc[q] (the CONJUGATE of the contraction of the sites > q),
+// the two site steps and the gates of a step.
 struct Environments {
     aqc_mps* w; aqc_mps* z;
-    int n, valid_l, valid_r;
+    const aqc_circuit* c; const double* th; double trunc_thr; int max_bond;   // what the gates of a walk run with
+    int n, nvals;
     std::vector<DevBuf<double2>> L, R;
-    DevBuf<double2> t, e0, e1, bsite, vals;
+    DevBuf<double2> t, e[2], bsite, vals;
     hipStream_t st;
-    int init(aqc_mps* w_, aqc_mps* z_, int nvals) {
-        w = w_; z = z_; n = w->n; st = w->stream;
+    int init(aqc_mps* w_, aqc_mps* z_, int nvals_) {
+        w = w_; z = z_; n = w->n; st = w->stream; nvals = std::max(nvals_, 1);
         L.resize(n + 1); R.resize(n);
-        valid_l = 0; valid_r = n - 1;
         const double one[2] = {1.0, 0.0};
-        if (L[0].reserve(1) || R[n - 1].reserve(1) || vals.reserve(std::max(nvals, 1))) return 1;
+        if (L[0].reserve(1) || R[n - 1].reserve(1) || vals.reserve(nvals)) return 1;
         HIP_OK(hipMemcpyAsync(L[0], one, sizeof one, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(R[n - 1], one, sizeof one, hipMemcpyHostToDevice, st));
         HIP_OK(hipStreamSynchronize(st));
         return 0;
     }
-    void touched(int lo, int hi) { valid_l = std::min(valid_l, lo); valid_r = std::max(valid_r, hi); }
     // site p of z, seen through G^H when an operator G sits on w's side there (<G w|z> = <w|G^H z>)
     int z_site(int p, const M2* op, const double2** out) {
         *out = z->t[p];
@@ -375,8 +374,9 @@ struct Environments {
         }
         return 0;
     }
+    int left(int p) { return step_left(p, L[p], nullptr, L[p + 1]); }
     // Rc[p-1][x][y] = sum_bit A_p[bit][x][u] (Rc[p] B_p[bit]^H)[u][y]
-    int step_right(int p) {
+    int right(int p) {
         const int xa = w->dims[p], ua = w->dims[p + 1], yb = z->dims[p], vb = z->dims[p + 1];
         if (mps_env_fits_small(xa, ua, yb, vb)) {
             if (R[p - 1].reserve((size_t)xa * yb)) return 1;
@@ -390,77 +390,41 @@ struct Environments {
         }
         return 0;
     }
-    // vals[slot] = <(G_1 on q_1)(G_2 on q_2) w | z>, q_1 < q_2 (nops = 1: only q_1)
-    int dot(int slot, int nops, const int* q, const M2* const* g) {
-        const int lo = q[0], hi = q[nops - 1];
-        for (; valid_l < lo; ++valid_l)
-            if (step_left(valid_l, L[valid_l], nullptr, L[valid_l + 1])) return 1;
-        for (; valid_r > hi; --valid_r)
-            if (step_right(valid_r)) return 1;
-        const void* cur = L[lo];
-        DevBuf<double2>* pp[2] = {&e0, &e1};
-        for (int p = lo; p <= hi; ++p) {
-            const M2* op = p == q[0] ? g[0] : (nops > 1 && p == q[1] ? g[1] : nullptr);
-            DevBuf<double2>& out = *pp[(p - lo) & 1];
-            if (step_left(p, cur, op, out)) return 1;
-            cur = out;
-        }
-        HIP_OK(launch_mps_env_dot(cur, R[hi], (size_t)w->dims[hi + 1] * z->dims[hi + 1], vals + slot, st));
+    int chain(int p, bool first, int k, const M2* op) { return step_left(p, first ? L[p] : e[k ^ 1], op, e[k]); }
+    int close(int hi, int k, int slot) {
+        if (slot >= nvals) return failf("inner-product slot out of range");
+        HIP_OK(launch_mps_env_dot(e[k], R[hi], (size_t)w->dims[hi + 1] * z->dims[hi + 1], vals + slot, st));
         return 0;
     }
+    int entangle(const GradStep& s) {   // z takes it before w
+        double ent[32];
+        entangler_matrix(c->entangler, s.ent.idx >= 0 ? s.ent.scale * th[s.ent.idx] : 0.0, ent);
+        return gate2_pair(z, s.q, s.q2, ent, trunc_thr, max_bond) || gate2_pair(w, s.q, s.q2, ent, trunc_thr, max_bond);
+    }
+    int rotate(int q, const LaneGate1& g1) {
+        const M2 g = gate1_matrix(g1, th);
+        return gate1(w, q, g) || gate1(z, q, g);
+    }
+    int rotate_recorded(PairEnvs& env, const GradStep& s, int slot) { return rotate_recorded_stepwise(*this, env, s, slot); }
 };
 
 int fast_dot_gradient(const aqc_circuit* c, aqc_mps* w, aqc_mps* z, const double* th, double trunc_thr, int max_bond, int lo_blk, int hi_blk,
                       bool front_layer, double* grad) {
-    const int n = w->n, T = 3 * n + thetas_per_block(c) * c->num_blocks;
-    const std::vector<GradStep> steps = gradient_steps(c, n, lo_blk, hi_blk, front_layer);
-    // every recorded inner product: (theta index, factor); several may add into one theta (Trotter tail)
-    std::vector<std::pair<int, cd>> rec;
-    const int nrec = 3 * n + thetas_per_block(c) * (int)blocks_of(c).size();   // at most
-    rec.reserve(nrec);
-    Environments env;
-    if (env.init(w, z, nrec)) return 1;
-    auto record = [&](int tindex, cd factor, int nops, const int* q, const M2* const* g) -> int {
-        if (env.dot((int)rec.size(), nops, q, g)) return 1;
-        rec.emplace_back(tindex, factor);
-        return 0;
-    };
-    auto run = [&](const GradStep& s) -> int {
-        if (s.kind == GradStep::RecordP11) {
-            const int qq[2] = {s.q, s.q2};
-            const M2* gg[2] = {&kProj1, &kProj1};
-            return record(s.tindex, s.factor, 2, qq, gg);
-        }
-        if (s.kind == GradStep::Entangle) {
-            double ent[32];
-            entangler_matrix(c->entangler, s.ent.idx >= 0 ? s.ent.scale * th[s.ent.idx] : 0.0, ent);
-            if (gate2_pair(z, s.q, s.q2, ent, trunc_thr, max_bond) || gate2_pair(w, s.q, s.q2, ent, trunc_thr, max_bond)) return 1;
-            env.touched(std::min(s.q, s.q2), std::max(s.q, s.q2));
-            return 0;
-        }
-        for (int k = 0; k < s.count; ++k) {
-            const M2 g = gate1_matrix(s.r[k].g, th);
-            if (gate1(w, s.q, g) || gate1(z, s.q, g)) return 1;
-            env.touched(s.q, s.q);
-            const M2* op = &pauli_of(s.r[k].pauli);
-            if (s.recorded && record(s.r[k].tindex, s.factor, 1, &s.q, &op)) return 1;
-        }
-        return 0;
-    };
-    int rc = 1;
-    do {
-        bool bad = false;
-        for (size_t i = 0; i < steps.size() && !bad; ++i) bad = run(steps[i]) != 0;
-        if (bad) break;
-        std::vector<cd> vals(rec.size());
-        if (!rec.empty() && hipMemcpyAsync(vals.data(), env.vals, sizeof(cd) * rec.size(), hipMemcpyDeviceToHost, env.st) != hipSuccess) { failf("gradient download failed"); break; }
-        if (hipStreamSynchronize(env.st) != hipSuccess) { failf("stream synchronisation failed"); break; }
-        std::vector<cd> g(T, cd(0.0, 0.0));
-        for (size_t i = 0; i < rec.size(); ++i) g[rec[i].first] += rec[i].second * vals[i];
-        std::memcpy(grad, g.data(), sizeof(cd) * T);
-        rc = 0;
-    } while (false);
-    return rc;
+    const int n = w->n;
+    const WalkSizes sz = walk_sizes(c, n);
+    GradRecords rec;
+    rec.reserve(sz.max_records);
+    Environments ex;
+    ex.c = c; ex.th = th; ex.trunc_thr = trunc_thr; ex.max_bond = max_bond;
+    if (ex.init(w, z, sz.max_records)) return 1;
+    PairEnvs env;
+    env.reset(n);
+    if (gradient_walk(ex, env, gradient_steps(c, n, lo_blk, hi_blk, front_layer), 0, rec)) return 1;
+    std::vector<cd> vals(rec.size());
+    if (!rec.empty() && hipMemcpyAsync(vals.data(), ex.vals, sizeof(cd) * rec.size(), hipMemcpyDeviceToHost, ex.st) != hipSuccess) return failf("gradient download failed");
+    if (hipStreamSynchronize(ex.st) != hipSuccess) return failf("stream synchronisation failed");
+    assemble_gradient(rec, vals.data(), sz.T, reinterpret_cast<cd*>(grad));
+    return 0;
 }
 
 }  // namespace

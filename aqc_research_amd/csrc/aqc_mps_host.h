@@ -1,6 +1,7 @@
 // Host-side helpers shared by the single-lane MPS engine (aqc_mps_engine.cpp) and the lockstep lanes (aqc_mps_batch.cpp): error
 // reporting, the checks of a circuit description and of a block range.  The gates themselves -- 2 x 2 algebra, entangler matrices, the block list and the walk of
-// an ansatz -- are stated in aqc_mps_walk.h (included through aqc_launch.h).  Private to csrc/ (everything has internal linkage).
+// an ansatz -- are stated in aqc_mps_walk.h (included through aqc_launch.h), the skeleton that executes a gradient walk in
+// aqc_mps_gradwalk.h.  Private to csrc/ (everything has internal linkage).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -9,6 +10,7 @@
 
 #include "../../include/aqc_hip.h"
 #include "aqc_launch.h"
+#include "aqc_mps_gradwalk.h"
 
 namespace aqc {
 // device pointers of site q of a single-lane MPS (T_q, and the Schmidt vector of bond q when q < n - 1) after its stream has drained:

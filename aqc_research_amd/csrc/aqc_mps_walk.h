@@ -2,7 +2,8 @@
 // gate-by-gate gradient walk (mps_dot_objective.py:41-242, core_operations.py:921-935, core_op_matrix.py:430-477) as plain lists
 // that the single-lane engine (aqc_mps_engine.cpp) and the lockstep lanes (aqc_mps_batch.cpp) execute, each with its own launches.
 // Gate order, signs, theta indices, the Trotter pre / post rotations, the Rx / Rz choice, the CPhase rule, the swap routing of
-// long-range entanglers and the block-range rule live here and nowhere else on the MPS side.
+// long-range entanglers and the block-range rule live here and nowhere else on the MPS side.  HOW a gradient walk is executed
+// (environments, slots, the final sum) is stated once as well, in aqc_mps_gradwalk.h.
 // HIP-free (a plain C++ compiler builds it: tests/native/walk_selftest.cpp evaluates both lists on a dense state vector against
 // the reference's golden outputs).  Private to csrc/; the functions have internal linkage.
 #pragma once

@@ -123,6 +123,42 @@ def test_native_gradient_and_circuit_against_oracle(kind):
     assert maxdiff(_dense(vhy), _dense(eng._apply_circuit_gatewise(circ, th, ym.clone(), True, 0.0, 0))) < TOL
 
 
+@pytest.mark.parametrize("kind", ["cx", "cz", "cp", "trotter2"])
+def test_gradient_walk_of_both_engines_against_the_gatewise_walk(kind):
+    """The two executors of the one gradient-walk skeleton (csrc/aqc_mps_gradwalk.h) against the gate-per-call walk with full chains, on
+    the smallest shapes with swap routing in both orientations ((0,3): control below, (4,1): control above), P11 records (cp), the
+    Trotter decorations and a block range that leaves slots out.  What the walk does not record is exactly zero."""
+    from aqc_research_amd import ParametricCircuit, TrotterAnsatz
+    from aqc_research_amd import mps_engine as eng
+    from aqc_research_amd.mps_engine import DeviceMPS, fast_dot_gradient_mps, v_dagger_mul_mps
+
+    n = 5
+    rng = np.random.default_rng(500 + len(kind))
+    if kind == "trotter2":
+        a = orc.Ansatz(n, "cx", orc.trotter_blocks(n, 1), True, True)
+        circ = TrotterAnsatz(n, a.blocks, second_order=True)
+    else:
+        blocks = np.array([[0, 4, 1, 2], [3, 1, 2, 4]], dtype=np.int64)
+        a = orc.Ansatz(n, kind, blocks)
+        circ = ParametricCircuit(n, kind, blocks)
+    th = orc.rand_thetas(a.num_thetas, rng)
+    xm = DeviceMPS.from_qiskit(orc.random_mps(n, 2, rng))
+    vhy = v_dagger_mul_mps(circ, th, DeviceMPS.from_qiskit(orc.random_mps(n, 3, rng)))
+    tpb = 5 if kind == "cp" else 4
+    for kw in ({}, {"block_range": (1, 3), "front_layer": False}):
+        ref = eng.fast_dot_gradient_mps_gatewise(circ, th, xm, vhy, **kw)
+        unrecorded = np.zeros(a.num_thetas, dtype=bool)
+        if kw:
+            unrecorded[:3 * n] = True
+            unrecorded[3 * n:3 * n + tpb] = True          # block 0
+            unrecorded[3 * n + 3 * tpb:] = True          # blocks 3, 4, ...
+        assert np.all(ref[~unrecorded] != 0) and np.all(ref[unrecorded] == 0)
+        for method in ("single", "lockstep"):
+            g = fast_dot_gradient_mps(circ, th, xm, vhy, trunc_thr=0, max_bond=0, method=method, **kw)
+            assert maxdiff(g, ref) < TOL, (method, kw)
+            assert np.all(g[unrecorded] == 0), (method, kw)
+
+
 def test_truncation_contract_and_large_register():
     """trunc_thr > 0: bonds shrink, the norm is kept, the error is of the order of the discarded weight;
     and a 40-qubit register (2^40 amplitudes dense) runs with small bonds."""

@@ -52,7 +52,9 @@ def test_devbuf_under_asan_ubsan(tmp_path):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_mps_walk_under_asan_ubsan(tmp_path):
     """The one statement of the MPS engines' gate walk (csrc/aqc_mps_walk.h: circuit_ops, gradient_steps, route_pair) evaluated on a
-    dense state vector against the reference's own outputs, on every golden state-vector case."""
+    dense state vector against the reference's own outputs, on every golden state-vector case.  The gradients go through the engines'
+    own skeleton (csrc/aqc_mps_gradwalk.h: gradient_walk, env_dot) with version stamps for environments: a read of a stale one ends
+    the program with a non-zero status and "stale environment" (9 of the cases, the *_rand_n3 / n5 / n6, route an entangler between non-adjacent qubits)."""
     exe = str(tmp_path / "walk_selftest")
     _run(["g++", "-std=c++17", *SAN, os.path.join(ROOT, "tests", "native", "walk_selftest.cpp"), "-o", exe])
     sv = load("state_vector.npz")
@@ -67,7 +69,7 @@ def test_mps_walk_under_asan_ubsan(tmp_path):
         for vec in (sv[f"{key}/x"], sv[f"{key}/y"]):
             words += [repr(float(v)) for v in vec.view(np.float64)]
         words += [int(v) for v in sv[f"{key}/block_range"]]
-        out = np.array(_run([exe], env=env, input=" ".join(str(w) for w in words)).split(), dtype=np.float64).view(np.complex128)
+        out = np.array(_run([exe, key], env=env, input=" ".join(str(w) for w in words)).split(), dtype=np.float64).view(np.complex128)
         dim = 1 << n
         assert out.size == 2 * dim + 2 * th.size, key
         got = {"v_x": out[:dim], "vh_y": out[dim:2 * dim], "grad_full": out[2 * dim:2 * dim + th.size], "grad_part": out[2 * dim + th.size:]}
