@@ -82,6 +82,9 @@ SIGNATURES = {
     "aqc_mps_gate2": (c_int, [_P, c_int, c_int, _D, c_double, c_int]),
     "aqc_mps_dot": (c_int, [_P, _P, _D]),
     "aqc_mps_dot_ops": (c_int, [_P, _P, c_int, POINTER(c_int32), _D, _D]),
+    "aqc_mps_obs_plan": (c_int, [c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "aqc_mps_obs_route": (c_int, [c_int, POINTER(c_int32)]),
+    "aqc_mps_obs_pairs": (c_int, [POINTER(_P), c_int, c_int, POINTER(c_int32), c_int, _D]),
     "aqc_svd": (c_int, [c_int, c_int, c_int, _D, _D, _D, _D, POINTER(c_int)]),
     "aqc_svd_batch": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), _D, _D, _D, _D, POINTER(c_int32), POINTER(c_int32)]),
     "aqc_svd_batch_core_ms": (c_double, []),

@@ -245,6 +245,9 @@ hipError_t launch_zgemm_batched(bool conj_t, bool accum, int M, int N, int K, co
                                 void* C, int ldc, size_t stride_a, size_t stride_b, size_t stride_c, int nbatch, hipStream_t s);
 hipError_t launch_zgemm_tables(int M, int N, int K, const void* const* a_tab, int lda, const void* const* b_tab, int ldb, void* const* c_tab, int ldc,
                                size_t stride_a, size_t stride_b, size_t stride_c, int outer, int inner, hipStream_t s, int b_transposed = 0);
+// the same with op(A) = A^H (A stored K x M) and / or accumulation into C
+hipError_t launch_zgemm_tables_op(bool conj_t, bool accum, int M, int N, int K, const void* const* a_tab, int lda, const void* const* b_tab, int ldb,
+                                  void* const* c_tab, int ldc, size_t stride_a, size_t stride_b, size_t stride_c, int outer, int inner, hipStream_t s);
 hipError_t launch_mps_product(const void* const* t_tab, void* const* out_tab, int n, int count, hipStream_t s);
 struct MpsSites {            // site table of one MPS (by value in the kernel arguments)
     int n;
@@ -351,6 +354,25 @@ unsigned obs_grid_x(int n, int tile_bits);   // blocks per lane: min(2^(n - tile
 hipError_t launch_obs_pass(const ObsArgs& a, hipStream_t s);
 // rho[lane * lane_stride + subset * 256 + 16 a + b] <- the partials added in block order, exactly Hermitian
 hipError_t launch_obs_final(const double* partial, unsigned nblocks, int nsub, int lanes, double2* rho, size_t lane_stride, hipStream_t s);
+
+// aqc_mps_obs.hip (pair density matrices of MPS states; rules: aqc_mps_obs_rule.h)
+struct MpsObsFusedArgs {
+    int n;
+    const double2* const* sites;   // [n] site tensors [2][dims[q]][dims[q+1]]
+    const int* dims;               // [n + 1], every one <= kMpsObsFusedCap
+    const size_t* env_off;         // [n + 1] element offset of L_q in env_l and of R_q in env_r
+    double2* env_l;                // written by launch_mps_obs_env (L_0 and R_n by the host), read by launch_mps_obs_fused
+    double2* env_r;
+    const int* chain_start;        // [chains]
+    const int* chain_last;
+    const int* emit_of;            // [chains][n] emission index of (chain, site), -1: none
+    double2* sums;                 // [emissions][3][4]
+};
+hipError_t launch_mps_obs_env(const MpsObsFusedArgs& a, hipStream_t s);                  // two workgroups: the left and the right sweep
+hipError_t launch_mps_obs_fused(const MpsObsFusedArgs& a, int nchains, hipStream_t s);   // grid (3 components, chains)
+// one workgroup per emission of a site: E of chain slot slots[e] ([slot][3][slot_stride], chi x chi each) against K [3][k_stride]
+hipError_t launch_mps_obs_sums(const void* e_base, const int* slots, const int* emits, int count, size_t slot_stride, const void* k_base, size_t k_stride,
+                               int chi, void* sums, hipStream_t s);
 
 // aqc_api.cpp: thread-local message behind aqc_last_error(); returns 1
 int set_error(const std::string& msg);

@@ -167,6 +167,12 @@ hipError_t launch_zgemm_tables(int M, int N, int K, const void* const* a_tab, in
     return zgemm_launch(false, false, M, N, K, nullptr, lda, nullptr, ldb, nullptr, ldc, sa, sb, sc, outer * inner, b_transposed ? 2 : 0, s, tab);
 }
 
+hipError_t launch_zgemm_tables_op(bool conj_t, bool accum, int M, int N, int K, const void* const* a_tab, int lda, const void* const* b_tab, int ldb,
+                                  void* const* c_tab, int ldc, size_t sa, size_t sb, size_t sc, int outer, int inner, hipStream_t s) {
+    const ZTables tab{reinterpret_cast<const cplx* const*>(a_tab), reinterpret_cast<const cplx* const*>(b_tab), reinterpret_cast<cplx* const*>(c_tab), inner};
+    return zgemm_launch(conj_t, accum, M, N, K, nullptr, lda, nullptr, ldb, nullptr, ldc, sa, sb, sc, outer * inner, 0, s, tab);
+}
+
 // product states (every bond dimension 1): out[i] = prod_q t_q[bit q of i], t_q = the two numbers of site q (2 q, 2 q + 1 of the
 // lane's packed tensors); one launch per batch instead of the whole contraction chain
 __global__ void mps_product_kernel(const cplx* const* t_tab, cplx* const* out_tab, int n) {

@@ -437,6 +437,8 @@ int aqc::mps_peek(const aqc_mps* m, int q, const void** site, const double** lam
     return 0;
 }
 
+hipStream_t aqc::mps_stream(const aqc_mps* m) { return m->stream; }
+
 int aqc::mps_adopt(int device, int n, const int* dims, const void* const* sites, const double* const* lams, double discarded, aqc_mps** out) {
     aqc_mps* m = nullptr;
     if (new_mps(device, n, &m)) return 1;

@@ -19,6 +19,8 @@ int mps_peek(const aqc_mps* m, int q, const void** site, const double** lam);
 // the reverse: a new single-lane MPS from tensors that live on the device (site q: [2][dims[q]][dims[q+1]] complex, T_q = Gamma_q lambda_q;
 // lams[q]: the dims[q+1] Schmidt values of bond q), copied
 int mps_adopt(int device, int n, const int* dims, const void* const* sites, const double* const* lams, double discarded, aqc_mps** out);
+// the stream a single-lane MPS orders its work on (aqc_mps_obs_api.cpp enqueues on the first state's, as aqc_mps_dot_ops does)
+hipStream_t mps_stream(const aqc_mps* m);
 }  // namespace aqc
 
 namespace {

@@ -72,10 +72,15 @@ class UserOptions:
         self.vectorised_lbfgs = False      # restarts driven by ONE vectorised L-BFGS (batched_optimizer.py) instead of scipy per lane
         self.device_lbfgs = False          # ... and that L-BFGS resident on the device (aqc_ws_lbfgs), thetas never leave HBM
         self.ground_truth = "trotter"      # |t1_gt>: "trotter" (10x the steps, as the reference) or "exact" (exp(-iHt)|ini> by xxz.xxz_evolve)
-        self.observables = False           # True: every horizon's record gains "observables" (magnetisation, bond energies; dense states only)
+        self.observables = False           # True: every horizon's record gains "observables" (magnetisation, bond energies; dense states only);
+                                           # "mps": the same entry read from the MPS states themselves (mps_observables.py), any register size
         self.__dict__.update(kw)
         if self.ground_truth not in ("trotter", "exact"):
             raise ValueError(f"ground_truth must be 'trotter' or 'exact', got {self.ground_truth!r}")
+        if self.observables not in (False, True, "mps"):
+            raise ValueError(f"observables must be False, True or 'mps', got {self.observables!r}")
+        if self.observables == "mps" and not self.use_mps:
+            raise ValueError("observables='mps' needs an MPS objective")
         if self.trotter_steps is None:
             self.trotter_steps = (1 + np.arange(self.num_horizons)) * int(self.trotter_steps_per_horizon)
         if self.evol_times is None:
@@ -143,7 +148,7 @@ def generate_target(opts: UserOptions, my_id: int) -> TargetState:
     n, steps, t = opts.num_qubits, int(opts.trotter_steps[my_id]), float(opts.evol_times[my_id])
     states = []
     exact = opts.ground_truth == "exact"
-    if opts.observables and opts.use_mps and n > _DENSE_MAX_QUBITS:
+    if opts.observables and opts.observables != "mps" and opts.use_mps and n > _DENSE_MAX_QUBITS:
         raise ValueError(f"observables=True needs dense states: at most {_DENSE_MAX_QUBITS} qubits with an MPS objective")
     if exact:
         if opts.use_mps and n > _DENSE_MAX_QUBITS:
@@ -188,6 +193,20 @@ def _dense_of(state: State) -> np.ndarray:
 def _observables_entry(opts: UserOptions, a1: State, t1_gt: State) -> Dict:
     """<Z_i> and the bond energies of the compiled state and of the ground truth (observables.py), both states as two lanes of one call
     each; the figures of the ground truth carry the suffix ``_gt``."""
+    if opts.observables == "mps":   # from the MPS states themselves: no dense vector, any register size
+        from ..mps_engine import DeviceMPS
+        from ..mps_observables import bond_energies as mps_bond_energies, magnetisation as mps_magnetisation
+
+        if not (check_mps(a1) and check_mps(t1_gt)):
+            raise ValueError("observables='mps' covers MPS states only")
+        lanes = [DeviceMPS.from_qiskit(s, device=opts.device, assume_canonical=True) for s in (a1, t1_gt)]
+        try:
+            mag = mps_magnetisation(lanes, "z")
+            bonds = mps_bond_energies(lanes, float(opts.delta))
+        finally:
+            for m in lanes:
+                m.close()
+        return {"magnetisation": mag[0], "bond_energies": bonds[0], "magnetisation_gt": mag[1], "bond_energies_gt": bonds[1]}
     from ..observables import bond_energies, magnetisation
 
     both = np.ascontiguousarray(np.stack([_dense_of(a1), _dense_of(t1_gt)]), dtype=np.complex128)

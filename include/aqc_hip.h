@@ -267,6 +267,28 @@ int aqc_mps_dot(aqc_mps* a, aqc_mps* b, double* out /* 1 c128 */);
 /* <(prod_i G_i on qubits[i]) a|b> without forming G.a: dot_{x,y,z} (mps_dot_objective.py:471-516) up to the factor
  * 0.5j with one Pauli; two projectors |1><1| give the CPhase derivative term.  gates: nops 2x2 matrices (4 c128 each) */
 int aqc_mps_dot_ops(aqc_mps* a, aqc_mps* b, int nops, const int32_t* qubits, const double* gates, double* out);
+/* Two-qubit reduced density matrices of one or several MPS states in one call (rules: csrc/aqc_mps_obs_rule.h, kernels:
+ * csrc/aqc_mps_obs.hip).  Convention of aqc_obs_rdm: for the pair (i, j) the row index is value(i) + 2 value(j),
+ * rho[a][b] = sum_rest psi(rest, a) conj psi(rest, b); no normalisation (tr rho = <psi|psi>); states are taken in whatever gauge they
+ * are in and are not modified.  All pairs with the same lower qubit i share one chain that walks from site i to the farthest
+ * requested partner and emits a matrix at every requested j; a pair given as (j, i), j > i, is the matrix of (i, j) with its two
+ * index bits transposed.  Every matrix is exactly Hermitian with an exactly real diagonal, sums run in a fixed order, and a pair's
+ * matrix does not depend on which other pairs or states are in the call.
+ * aqc_mps_obs_plan: host only, needs no device.  pairs [npairs][2].  Outputs: chain_last [n] = the last site the chain that starts
+ *   at a site walks to (-1: none starts there), *nemits = the number of different (chain, site) emissions, serves [npairs][3] =
+ *   (chain, emitting site, 1 if the pair was given as (higher, lower)).
+ * aqc_mps_obs_route: the route the rule picks for bond dimensions dims [n + 1]: AQC_MPS_OBS_FUSED when every one is at most
+ *   AQC_MPS_OBS_FUSED_CAP, else AQC_MPS_OBS_GEMM (-1: invalid argument).
+ * aqc_mps_obs_pairs: out [nstates][npairs][4][4] c128.  method: AQC_MPS_OBS_BY_RULE (per state), AQC_MPS_OBS_FUSED (an error when a
+ *   bond exceeds the cap) or AQC_MPS_OBS_GEMM.  The states share n >= 2 and the device; the work is ordered on the first state's
+ *   stream after the others' have drained. */
+#define AQC_MPS_OBS_BY_RULE 0
+#define AQC_MPS_OBS_FUSED 1
+#define AQC_MPS_OBS_GEMM 2
+#define AQC_MPS_OBS_FUSED_CAP 64
+int aqc_mps_obs_plan(int n, int npairs, const int32_t* pairs, int32_t* chain_last, int32_t* nemits, int32_t* serves);
+int aqc_mps_obs_route(int n, const int32_t* dims);
+int aqc_mps_obs_pairs(aqc_mps* const* states, int nstates, int npairs, const int32_t* pairs, int method, double* out);
 /* ansatz description for the MPS entry points (ParametricCircuit / TrotterAnsatz, parametric_circuit.py:24-70,267-333);
  * unlike aqc_ctx it is not limited to dense-reachable registers.  blocks: int32[2][num_blocks], row 0 = control */
 typedef struct aqc_circuit {
