@@ -28,6 +28,7 @@
 
 #include <type_traits>
 
+#include "aqc_backwalk.h"
 #include "aqc_device.h"
 #include "aqc_launch.h"
 #include "aqc_math.h"
@@ -505,9 +506,15 @@ __device__ __forceinline__ void skip_masks(const DevStage& st, unsigned info, lo
 }
 // RLAST: the launch of the LAST stage when its last sub-stage is taken from its inputs alone (Stage3Args::r_only_last); a variant of
 // its own because the explicit copies it needs cost the plain loop 3 % (see `substage` below).
-template <int K, bool LIST, bool SKIPW, bool RLAST>
+// BACK: the backward walk of a sweep stage (objective by projection) -- a list launch over a stage of the MIRRORED plan
+// with (w, z) = (psi, C), the states the forward walk of that stage ends in.  Its first sub-stage is the forward body with U^H (operands
+// from the prefetch registers in the persistent form; its R, formed from the outputs, is the "inputs" form of the forward sub-stage's R
+// and rgrad_kernel conjugates it: conj_sub); every later sub-stage takes R from its inputs and runs the U^H products afterwards, the
+// last one on z alone (AQC_SS_BACK in aqc_sweep_substage.inc).  Every R goes to the row of the forward sub-stage (aqc_backwalk.h).
+template <int K, bool LIST, bool SKIPW, bool RLAST, bool BACK = false>
 __device__ __forceinline__ void sweep_mfma_body(const Stage3Args& a, const int wg, const int nwg) {   // (wg, nwg: see apply_mfma_body)
     using TS = TileShape<K, true>;
+    static_assert(!BACK || (LIST && !SKIPW && !RLAST), "the backward walk is a list launch with a form of its own");
     constexpr int kSlots = TS::kWaves > 4 ? 4 : TS::kWaves;   // scratch slots; 8 waves reduce in pairs first
     constexpr unsigned tsize = 1u << K;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -607,7 +614,7 @@ __device__ __forceinline__ void sweep_mfma_body(const Stage3Args& a, const int w
     // tiles of the lane
     const int part = LIST ? it.slot : (kPersist ? wg - (bl * a.ntiles) / chunk : tile);
     const bool seg_first = LIST || !kPersist || wi == wi_first || tile == 0;   // nothing accumulated yet in this segment
-    cplx* rpart = a.rpart + (((size_t)bl * a.nsubs_total + st.sub_begin) * a.nparts + part) * 256;
+    cplx* rpart = a.rpart + (((size_t)bl * a.nsubs_total + (BACK ? 0 : st.sub_begin)) * a.nparts + part) * 256;
     const int nwi = wi + 1;
     const bool more = reg_first && nwi < wi_end;   // (launch_sweep3 refuses a persistent stage without sub-stages)
     const ItemAt nit = more ? item_at<LIST>(a, nwi) : ItemAt{0, 0, 0};
@@ -640,37 +647,75 @@ __device__ __forceinline__ void sweep_mfma_body(const Stage3Args& a, const int w
     // The sub-stage body lives in aqc_sweep_substage.inc (see there).  RLAST: the very last sub-stage is taken from its inputs alone
     // (R = U (Z W^H) U^H), which needs explicit copies: first sub-stage of an item / the others / the R-only one.
     const int nmain = RLAST && a.r_only_last && st.nsubs >= 1 && !(kPersist && st.nsubs == 1) ? st.nsubs - 1 : st.nsubs;
-    if (!RLAST) {
-        for (int si = 0; si < st.nsubs; ++si) {
-#define AQC_SS_FROM_REGS (reg_first && si == 0)
+    if constexpr (BACK) {   // first / middle / last sub-stage, see above (launch_sweep3: there are at least two)
+        {
+            const int si = 0;
+#define AQC_SS_FROM_REGS reg_first
 #define AQC_SS_RONLY false
+#define AQC_SS_BACK 0
 #include "aqc_sweep_substage.inc"
 #undef AQC_SS_FROM_REGS
 #undef AQC_SS_RONLY
+#undef AQC_SS_BACK
+        }
+        for (int si = 1; si + 1 < st.nsubs; ++si) {
+#define AQC_SS_FROM_REGS false
+#define AQC_SS_RONLY false
+#define AQC_SS_BACK 1
+#include "aqc_sweep_substage.inc"
+#undef AQC_SS_FROM_REGS
+#undef AQC_SS_RONLY
+#undef AQC_SS_BACK
+        }
+        {
+            const int si = st.nsubs - 1;
+#define AQC_SS_FROM_REGS false
+#define AQC_SS_RONLY false
+#define AQC_SS_BACK 2
+#include "aqc_sweep_substage.inc"
+#undef AQC_SS_FROM_REGS
+#undef AQC_SS_RONLY
+#undef AQC_SS_BACK
+        }
+    } else if (!RLAST) {
+        for (int si = 0; si < st.nsubs; ++si) {
+#define AQC_SS_FROM_REGS (reg_first && si == 0)
+#define AQC_SS_RONLY false
+#define AQC_SS_BACK 0
+#include "aqc_sweep_substage.inc"
+#undef AQC_SS_FROM_REGS
+#undef AQC_SS_RONLY
+#undef AQC_SS_BACK
         }
     } else {
         if (nmain > 0) {
             const int si = 0;
 #define AQC_SS_FROM_REGS reg_first
 #define AQC_SS_RONLY false
+#define AQC_SS_BACK 0
 #include "aqc_sweep_substage.inc"
 #undef AQC_SS_FROM_REGS
 #undef AQC_SS_RONLY
+#undef AQC_SS_BACK
         }
         for (int si = 1; si < nmain; ++si) {
 #define AQC_SS_FROM_REGS false
 #define AQC_SS_RONLY false
+#define AQC_SS_BACK 0
 #include "aqc_sweep_substage.inc"
 #undef AQC_SS_FROM_REGS
 #undef AQC_SS_RONLY
+#undef AQC_SS_BACK
         }
         if (nmain < st.nsubs) {
             const int si = nmain;
 #define AQC_SS_FROM_REGS false
 #define AQC_SS_RONLY true
+#define AQC_SS_BACK 0
 #include "aqc_sweep_substage.inc"
 #undef AQC_SS_FROM_REGS
 #undef AQC_SS_RONLY
+#undef AQC_SS_BACK
         }
     }
     AQC_STAMP(kStampSlots - 2);
@@ -695,23 +740,23 @@ __device__ __forceinline__ void sweep_mfma_body(const Stage3Args& a, const int w
     }
     AQC_STAMP(kStampSlots - 4);
 }
-template <int K, bool LIST = false, bool SKIPW = false, bool RLAST = false>
+template <int K, bool LIST = false, bool SKIPW = false, bool RLAST = false, bool BACK = false>
 __global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void sweep_mfma_kernel(const Stage3Args a) {
-    sweep_mfma_body<K, LIST, SKIPW, RLAST>(a, (int)blockIdx.x, (int)gridDim.x);
+    sweep_mfma_body<K, LIST, SKIPW, RLAST, BACK>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 // The sweep's pair (see apply_pair_kernel): the real plan's first stage on the lhs tiles with the virtual plan's stage on the virtual
-// register.  Each member keeps its own item list, partial-R slots and R-only form (RLAST_A / RLAST_B); a workgroup walks its contiguous
+// register.  Each member keeps its own item list, partial-R slots and form (RLAST_A / RLAST_B; BACK_A: A walks backwards); a workgroup walks its contiguous
 // share of A and then of B.  The change of list is the plain one -- A's last stores, a barrier, B's first operands; carrying B's
 // prefetch through A's last item (as apply_mfma_body<K, true, true> does) has not been built here: this kernel runs one wave per SIMD
 // with every architectural register taken, and the prefetch registers are the first sub-stage's operands in a per-stage layout.
-template <int K, bool RLAST_A, bool RLAST_B>
+template <int K, bool RLAST_A, bool RLAST_B, bool BACK_A = false>
 __global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void sweep_pair_kernel(const Stage3Args a, const Stage3Args b, const int grid_a) {
     if (K >= 12) {
-        sweep_mfma_body<K, true, false, RLAST_A>(a, (int)blockIdx.x, (int)gridDim.x);
+        sweep_mfma_body<K, true, false, RLAST_A, BACK_A>(a, (int)blockIdx.x, (int)gridDim.x);
         __syncthreads();   // A's last sub-stage and stores have read the LDS tiles and scratch that B's first sub-stage writes
         sweep_mfma_body<K, true, false, RLAST_B>(b, (int)blockIdx.x, (int)gridDim.x);
     } else if ((int)blockIdx.x < grid_a) {
-        sweep_mfma_body<K, true, false, RLAST_A>(a, (int)blockIdx.x, grid_a);
+        sweep_mfma_body<K, true, false, RLAST_A, BACK_A>(a, (int)blockIdx.x, grid_a);
     } else {
         sweep_mfma_body<K, true, false, RLAST_B>(b, (int)blockIdx.x - grid_a, (int)gridDim.x - grid_a);
     }
@@ -1184,13 +1229,14 @@ static hipError_t with_tile_size(int k, F&& f) {
 using Stage3Kernel = void (*)(Stage3Args);
 using Pair3Kernel = void (*)(Stage3Args, Stage3Args, int);
 template <int K> static Stage3Kernel apply_variant(bool list) { return list ? apply_mfma_kernel<K, true> : apply_mfma_kernel<K, false>; }
-template <int K> static Stage3Kernel sweep_variant(bool list, bool skipw, bool rlast) {   // (a list launch has no zero-w form, the zero-w form no R-only one)
+template <int K> static Stage3Kernel sweep_variant(bool list, bool skipw, bool rlast, bool back = false) {   // (a list launch has no zero-w form, the zero-w form no R-only one,
+    if (back) return backwalk_tile(K) ? sweep_mfma_kernel<K, true, false, false, backwalk_tile(K)> : nullptr;   // the backward walk is a list launch without either)
     if (list) return rlast ? sweep_mfma_kernel<K, true, false, true> : sweep_mfma_kernel<K, true, false, false>;
     if (skipw) return sweep_mfma_kernel<K, false, true, false>;
     return rlast ? sweep_mfma_kernel<K, false, false, true> : sweep_mfma_kernel<K, false, false, false>;
 }
 template <int K> static Pair3Kernel apply_pair_variant() { return apply_pair_kernel<K>; }
-template <int K> static Pair3Kernel sweep_pair_variant(bool rlast_a) { return rlast_a ? sweep_pair_kernel<K, true, false> : sweep_pair_kernel<K, false, false>; }
+template <int K> static Pair3Kernel sweep_pair_variant(bool rlast_a, bool back_a = false) { return back_a ? (backwalk_tile(K) ? sweep_pair_kernel<K, false, false, backwalk_tile(K)> : nullptr) : rlast_a ? sweep_pair_kernel<K, true, false> : sweep_pair_kernel<K, false, false>; }
 
 template <typename F>
 static hipError_t big_lds(F kernel) {
@@ -1204,6 +1250,8 @@ hipError_t init_kernels3() {   // eager: a launch may sit inside a graph capture
             hipError_t e = big_lds(apply_pair_variant<K>());
             for (int f = 0; f < 2 && e == hipSuccess; ++f) e = big_lds(apply_variant<K>(f));
             for (int f = 0; f < 2 && e == hipSuccess; ++f) e = big_lds(sweep_pair_variant<K>(f));
+            if (backwalk_tile(K) && e == hipSuccess) e = big_lds(sweep_pair_variant<K>(false, true));
+            if (backwalk_tile(K) && e == hipSuccess) e = big_lds(sweep_variant<K>(true, false, false, true));
             for (int f = 0; f < 8 && e == hipSuccess; ++f) e = big_lds(sweep_variant<K>(f & 1, f & 2, f & 4));   // (flag combinations that share a kernel: set twice)
             return e;
         });
@@ -1275,6 +1323,8 @@ int sweep3_nparts(int ntiles, int batch, int k, long sweep_grid) {
     const int chunk = sweep3_chunk(ntiles, batch, k, sweep_grid);
     return chunk > 0 ? std::min(ntiles, (ntiles + chunk - 1) / chunk + 1) : ntiles;
 }
+// the backward walk (Stage3Args::backwalk): a list launch, its first / middle / last sub-stages are different code
+static bool backwalk_launchable(int k, const Stage3Args& a) { return backwalk_tile(k) && a.items && !a.supp && !a.r_only_last && a.stage.nsubs >= 2; }
 hipError_t launch_sweep3(int k, hipStream_t s, const Stage3Args& a, const Switches& sw) {
     const bool list = a.items != nullptr;
     if (!stage3_launchable(k, a, false, true)) return hipErrorInvalidValue;   // (the persistent form feeds the first sub-stage from registers)
@@ -1284,16 +1334,18 @@ hipError_t launch_sweep3(int k, hipStream_t s, const Stage3Args& a, const Switch
     const dim3 grid((unsigned)(k >= 12 ? (list ? std::min<long>(nwork, persistent_sweep_grid(sw.sweep_grid)) : (nwork + a.chunk - 1) / a.chunk) : nwork));
     const bool skipw = !list && a.supp != nullptr;
     const bool rlast = !skipw && a.r_only_last != 0;
-    return with_tile_size(k, [&](auto kk) { return launch3(sweep_variant<decltype(kk)::value>(list, skipw, rlast), grid, k, true, s, a); });
+    const bool back = a.backwalk != 0;
+    if (back && !backwalk_launchable(k, a)) return hipErrorInvalidValue;
+    return with_tile_size(k, [&](auto kk) { return launch3(sweep_variant<decltype(kk)::value>(list, skipw, rlast, back), grid, k, true, s, a); });
 }
 
-// Two list launches of the sweep as one (sweep_pair_kernel): a may be the R-only form of its stage, b is not.
+// Two list launches of the sweep as one (sweep_pair_kernel): a may be the R-only form of its stage or its backward walk, b is neither.
 hipError_t launch_sweep3_pair(int k, hipStream_t s, const Stage3Args& a, const Stage3Args& b, const Switches& sw) {
     if (!stage3_launchable(k, a, true, true) || !stage3_launchable(k, b, true, true)) return hipErrorInvalidValue;
-    if (a.nparts < 1 || b.nparts < 1 || a.supp || b.supp || b.r_only_last) return hipErrorInvalidValue;
+    if (a.nparts < 1 || b.nparts < 1 || a.supp || b.supp || b.r_only_last || b.backwalk || (a.backwalk && !backwalk_launchable(k, a))) return hipErrorInvalidValue;
     const long longer = std::max(a.max_items, b.max_items);
     const dim3 grid((unsigned)(k >= 12 ? std::min<long>(longer, persistent_sweep_grid(sw.sweep_grid)) : (long)a.max_items + b.max_items));
-    return with_tile_size(k, [&](auto kk) { return launch3(sweep_pair_variant<decltype(kk)::value>(a.r_only_last != 0), grid, k, true, s, a, b, a.max_items); });
+    return with_tile_size(k, [&](auto kk) { return launch3(sweep_pair_variant<decltype(kk)::value>(a.r_only_last != 0, a.backwalk != 0), grid, k, true, s, a, b, a.max_items); });
 }
 
 // ---- tile lists ------------------------------------------------------------------------------------------------

@@ -74,7 +74,10 @@ struct Stage3Args {
     int store_out;           // sweep: bit 0 store w, bit 1 store z; 0 for the last stage (its w and z are never read again)
     int r_only_last;         // sweep, last stage: its last sub-stage computes R from its INPUTS alone (no U products); the gradient walk
                              // conjugates that R by the sub-stage's U (launch_rgrad: conj_sub)
-    const long long* supp;   // sweep from basis states: supp[lane][2] = element index of the lane's (<= 2) basis states (-1: none), or null.
+    int backwalk;            // sweep over an item list: the stage is the mirrored plan's (U^H of a sweep stage, walked backwards from the
+                             // states the forward walk ends in); every sub-stage's R goes to the slot of the forward sub-stage it mirrors
+                             // (aqc_backwalk.h), rpart is the SWEEP plan's buffer.  At least two sub-stages, no R-only form
+    const long long* supp;  // sweep from basis states: supp[lane][2] = element index of the lane's (<= 2) basis states (-1: none), or null.
                              // The kernel then skips the W and R products of 16-chunk groups (and K-steps of the W product) where w is
                              // zero by construction (DevSub3::skipinfo, DevStage::fresh_nonlocal) -- exact zeros, so the results do not change
     const TileItem* items;   // launch over a subset of the (tile, lane) pairs: device table + its length on the device (null: all pairs);

@@ -1,10 +1,15 @@
 // One sub-stage of sweep_mfma_kernel (aqc_kernels3.hip), textually included where the kernel needs a copy of it:
 //   AQC_SS_FROM_REGS   expression: the sub-stage's operands sit in the prefetch registers (first sub-stage of an item of the persistent form)
 //   AQC_SS_RONLY       constant: the R-only form of the very last sub-stage (R from the sub-stage's inputs, no U products)
+//   AQC_SS_BACK        constant: a sub-stage of the backward walk (BACK) behind the stage's first -- R from the sub-stage's inputs, THEN the
+//                      U products of 1: w and z, 2: z alone (the stage's last sub-stage: its w is the basis state and nobody reads it)
 // The plain kernel includes it once inside its loop (the compiler peels the first iteration by itself); the RLAST variant three
 // times with constants.  Hand-made copies through a lambda cost the plain loop its peeling -- hence an include, not a lambda.
 {
         constexpr bool kROnly = AQC_SS_RONLY;
+        constexpr int kBack = AQC_SS_BACK;
+        // this sub-stage's row of the partial-R buffer (BACK: the forward sub-stage it mirrors, rpart starts at the plan's row 0)
+        cplx* const rps = rpart + (size_t)(BACK ? backwalk_r_slot(a.nsubs_total, st.sub_begin + si) : si) * a.nparts * 256;
         const bool from_regs = AQC_SS_FROM_REGS;
         unsigned nzmask = ~0u, kneed = 15u;
         if (SKIPW) {
@@ -23,7 +28,7 @@
                 if (si == (1 + c < st.nsubs ? 1 + c : st.nsubs - 1)) prefetch(c);
         }
         if (kPersist && !seg_first)
-            asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 sc0 sc1" : "=a"(racc) : "v"(e16), "s"(uniform_ptr(rpart + (size_t)si * a.nparts * 256)) : "memory");
+            asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 sc0 sc1" : "=a"(racc) : "v"(e16), "s"(uniform_ptr(rps)) : "memory");
         double4_t t1 = {0.0, 0.0, 0.0, 0.0}, t2 = t1, t3 = t1;
         // Software pipeline over the wave's groups, written as CLUSTERS that the compiler may not interleave
         // (sched_barrier): on gfx950 an fp64 MFMA and vector-ALU instructions of the same SIMD do not overlap, and every
@@ -207,6 +212,97 @@
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
+        } else if (kBack != 0) {
+            // Backward walk, behind the stage's first sub-stage: the R of the forward sub-stage this one mirrors is Z W^H of this
+            // sub-stage's INPUTS on its own register bits (the outputs are laid out for another sub-stage's bits) -- the R-only product
+            // above, operands in L2 --, then U^H w and U^H z by the instruction sequence of apply_mfma_body (the z tile is bit for bit
+            // what V^H's last stage writes).  Per iteration j: L1 reads of group j + 1 | adds: operand sums of group j, complex results
+            // of group j - 1 | 12 MFMAs: R of group j; its L2 operands are dead, group j + 1's are requested into the same registers
+            // under the 24 (12) MFMAs of U^H w and U^H z (U^H z), in which the LDS writes of group j - 1 ride as in the forward loop.
+            // (Not on 2^11 tiles, whose two waves per SIMD have 256 registers each: both layouts of a group next to the next group's
+            // operands need scratch memory there -- sweep_variant has no such kernel and the route keeps the forward launches.)
+            constexpr bool kBoth = kBack == 1;
+            cplx rw[4], rz[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { rw[r] = lds_get(ad.a2 ^ ad.k2[0][r]); rz[r] = lds_get(a2z ^ ad.k2[0][r]); }
+            Acc3 aw, az;
+#pragma unroll
+            for (int j = 0; j <= TS::kGpw; ++j) {
+                if (j + 1 < TS::kGpw) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        if (kBoth) vw[(j + 1) & 1][s] = lds_get(ad.a1 ^ ad.k1[j + 1][s]);
+                        vz[(j + 1) & 1][s] = lds_get(a1z ^ ad.k1[j + 1][s]);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                double sw[4], sz[4], zs2[4], wd2[4];
+                cplx ow[4], oz[4];
+                if (j < TS::kGpw) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        if (kBoth) sw[s] = vw[j & 1][s].x + vw[j & 1][s].y;
+                        sz[s] = vz[j & 1][s].x + vz[j & 1][s].y;
+                        zs2[s] = rz[s].x + rz[s].y; wd2[s] = rw[s].x - rw[s].y;
+                    }
+                }
+                if (j > 0) {
+                    if (kBoth) u_combine(aw, ow);
+                    u_combine(az, oz);
+                }
+                if (j < TS::kGpw) {   // (pinned, as in the forward loop)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        if (kBoth) asm volatile("" : "+v"(sw[s]));
+                        asm volatile("" : "+v"(sz[s])); asm volatile("" : "+v"(zs2[s])); asm volatile("" : "+v"(wd2[s]));
+                    }
+                }
+                unsigned wa[4], za[4];
+                if (j > 0) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (kBoth) { wa[r] = ad.a2 ^ ad.k2[j - 1][r]; asm volatile("" : "+v"(wa[r])); }
+                        za[r] = a2z ^ ad.k2[j - 1][r]; asm volatile("" : "+v"(za[r]));
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (j < TS::kGpw) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        t1 = mfma(rz[r].x, rw[r].x, t1);
+                        t2 = mfma(rz[r].y, rw[r].y, t2);
+                        t3 = mfma(zs2[r], wd2[r], t3);
+                    }
+                    if (j + 1 < TS::kGpw) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { rw[r] = lds_get(ad.a2 ^ ad.k2[j + 1][r]); rz[r] = lds_get(a2z ^ ad.k2[j + 1][r]); }
+                    }
+                    az.k1 = double4_t{0.0, 0.0, 0.0, 0.0}; az.k2 = az.k1; az.k3 = az.k1; aw.k1 = az.k1; aw.k2 = az.k1; aw.k3 = az.k1;
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        if (kBoth) {
+                            aw.k1 = mfma(sw[s], cur.u0[s], aw.k1);
+                            aw.k2 = mfma(vw[j & 1][s].x, cur.u1[s], aw.k2);
+                            aw.k3 = mfma(vw[j & 1][s].y, cur.u2[s], aw.k3);
+                        }
+                        az.k1 = mfma(sz[s], cur.u0[s], az.k1);
+                        az.k2 = mfma(vz[j & 1][s].x, cur.u1[s], az.k2);
+                        az.k3 = mfma(vz[j & 1][s].y, cur.u2[s], az.k3);
+                    }
+                }
+                if (j > 0) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { if (kBoth) lds_put(wa[r], ow[r]); lds_put(za[r], oz[r]); }
+                    if (j < TS::kGpw) {
+#pragma unroll
+                        for (int i = 0; i < (kBoth ? 8 : 4); ++i) {
+                            __builtin_amdgcn_sched_group_barrier(0x008, kSweepSpread, 0);   // MFMA
+                            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);              // DS write
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
         } else {
             group_loop();
         }
@@ -263,7 +359,7 @@
                 asm volatile("s_waitcnt vmcnt(0)" : "+a"(racc) : : "memory");   // the load is not tracked by the compiler; the
                 re += racc.x; im += racc.y;                                      // operand ties every later read of racc to this wait
             }
-            rpart[(size_t)si * a.nparts * 256 + threadIdx.x] = make_double2(re, im);
+            rps[threadIdx.x] = make_double2(re, im);
             if (!kDouble) __syncthreads();
         } else {
             for (int e = threadIdx.x; e < 256; e += TS::kWaves * 64) {
@@ -273,7 +369,7 @@
                 double re = p[0].x, im = p[0].y;
 #pragma unroll
                 for (int w = 1; w < kSlots; ++w) { re += p[w].x; im += p[w].y; }
-                rpart[(size_t)si * a.nparts * 256 + e] = make_double2(re, im);
+                rps[e] = make_double2(re, im);
             }
             if (!kDouble) __syncthreads();
             if (go_on) cur = nxt;

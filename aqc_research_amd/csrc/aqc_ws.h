@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/aqc_hip.h"
+#include "aqc_backwalk.h"
 #include "aqc_devbuf.h"
 #include "aqc_device.h"
 #include "aqc_launch.h"
@@ -376,6 +377,8 @@ int proj_alloc(aqc_ws* ws);                 // its device side (plan tables, buf
 bool list_launches_allowed(const aqc_ws* ws);
 bool sweep_route_projected(const aqc_ws* ws, bool sparse);
 bool projected_pairs(const aqc_ws* ws);      // the route's independent tile launches run in pairs
+bool backwalk_keeps_vdag_stage(const aqc_ws* ws);   // ... as single launches (pairs switched off): V^H's last stage still writes that tile, the walk stores nothing
+bool projected_backwalk(const aqc_ws* ws);   // objective by projection: the sweep's first stage walks back from (psi, C) and writes the Z tile (no V^H stage at all)
 Stage3Args virtual_stage3_args(aqc_ws* ws, const DevPlan& v, size_t s);   // stage s of a virtual plan (vsw, vinv) on the virtual register, over its item list
 Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s);   // arguments of stage s of the virtual sweep plan
 int run_projected_stages(aqc_ws* ws);       // projection + the virtual stage launches (after the sweep's first stage)

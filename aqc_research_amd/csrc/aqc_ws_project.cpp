@@ -241,13 +241,33 @@ Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s) {
 }
 
 // Objective by projection: its six tile launches are three pairs of independent launches over disjoint buffers (psi with M_end, V^H's
-// last stage with Y_0, the sweep's first stage with the virtual stage), and each pair runs as ONE launch (launch_apply3_pair /
+// last stage with Y_0 -- Y_0 alone where the sweep walks backwards, projected_backwalk --, the sweep's first stage with the virtual stage), and each pair runs as ONE launch (launch_apply3_pair /
 // launch_sweep3_pair) when the virtual plan has a single stage of the real plans' tile size (unless switched off).
-bool projected_pairs(const aqc_ws* ws) {
+static bool plan_has_pairs(const aqc_ws* ws) {   // the plans allow them: one virtual stage of the real plans' tile size
     const ProjRoute& pr = ws->proj;
-    return pr.ok && ws->sw.projected_pairs && !ws->capturing && pr.vsw.h_stages.size() == 1 && pr.vinv.h_stages.size() == 1 &&
-           ws->sweep.k == pr.kv && ws->inv.k == pr.kv;
+    return pr.ok && pr.vsw.h_stages.size() == 1 && pr.vinv.h_stages.size() == 1 && ws->sweep.k == pr.kv && ws->inv.k == pr.kv;
 }
+bool projected_pairs(const aqc_ws* ws) { return plan_has_pairs(ws) && ws->sw.projected_pairs && !ws->capturing; }
+
+// Objective by projection: the sweep's first stage walks BACK from (psi, C) -- the states V^H's last stage on the lhs tiles would start
+// from and the forward walk would end in -- over the mirrored plan's last stage: one walk instead of two, every R from the sub-stage's
+// inputs (sweep_mfma_body<..., BACK>).  run_vdag_projected then does not launch V^H's last stage and the sweep writes the Z tile, so
+// both ask here, and the gather follows the sweep.  Static per workspace: the plans mirror each other sub-stage by sub-stage, the tile
+// size has the form (aqc_backwalk.h), the stage has a first and a last sub-stage, and the R of its first one may arrive in the "inputs"
+// form that the gradient walk conjugates (the R-only sub-stage's mechanism and switch).
+bool projected_backwalk(const aqc_ws* ws) {
+    const DevPlan& p = ws->sweep;
+    const DevPlan& iv = ws->inv;
+    return ws->proj.ok && ws->inv_mirrored && p.v3 && iv.v3 && ws->sw.r_only_last && iv.k == p.k && backwalk_tile(p.k) &&
+           iv.h_subs3.size() == p.h_subs3.size() && !iv.h_stages.empty() && p.h_stages[0].nsubs >= 2 &&
+           iv.h_stages.back().nsubs == p.h_stages[0].nsubs && iv.h_stages.back().sub_begin + iv.h_stages.back().nsubs == (int)iv.h_subs3.size();
+}
+
+// AQC_PROJECTED_PAIRS=0 on a plan that has pairs splits every pair into the single launches it was made of, V^H's last stage on the
+// lhs tiles among them (tests/test_hip_pairs.py pins their kinds): that launch writes the Z tile and the walk -- the same body, the
+// same R -- stores nothing.  A plan without pairs has nothing to split, and neither has a captured graph of a workspace whose pairs
+// are on: there the stage is not launched and the walk writes the tile.
+bool backwalk_keeps_vdag_stage(const aqc_ws* ws) { return projected_backwalk(ws) && plan_has_pairs(ws) && ws->sw.projected_pairs == 0; }
 
 // the gradient entries of the virtual plan's gate groups: its walk rides in the launch of the real plan's (which stops after its first stage)
 RgradSecond projected_rgrad_plan(aqc_ws* ws) {
@@ -270,6 +290,8 @@ RgradSecond projected_rgrad_plan(aqc_ws* ws) {
 // -- two passes over y (the target is read twice, V^H's first stage read and wrote the whole state and ran 4 sub-stages over it) --,
 // then V^H's last stage on the lhs tile alone (Z there), the sweep's first stage as ever, the virtual stages from (M_0, Y_0), and
 // <g|V^H y> = sum_c Y_0[(c, g on T n F), c] for the gather indices outside the tile.
+// Where projected_backwalk holds, V^H's last stage and the sweep's first stage are ONE launch: the sweep walks back from (psi, C), writes
+// the Z tile on its way and enqueues the gather itself.
 bool vdag_route_projected(aqc_ws* ws, int x_buf) {
     ProjRoute& pr = ws->proj;
     if (!pr.ok || !ws->sw.projected_vdag || ws->capturing || (long long)ws->lane_elems * ws->batch < ws->sw.projected_vdag_min_elems) return false;
@@ -340,6 +362,7 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // for a route eval_route has 
     const VirtualRun y0{pr.vinv, pr.vy, pr.vy};     // Y_0 = (later stages)^H Y_end
     const ProjArgs a = proj_args(ws);
     const bool pairs = projected_pairs(ws);
+    const bool back = projected_backwalk(ws);   // the sweep of this call takes C -> Z on the lhs tiles along its walk back from (psi, C)
 
     if (!pairs && enqueue_couple(ws, p.k, &psi, nullptr)) return 1;          // psi
     if (ensure_pattern(ws, a)) return 1;                                      // M_0
@@ -366,13 +389,13 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // for a route eval_route has 
         ProfScope ps(ws, AQC_K_PROJECT);
         HIP_OK(launch_project(q, ws->stream));
     }
-    if (!pairs && enqueue_couple(ws, iv.k, nullptr, &y0)) return 1;           // Y_0
-    if (enqueue_couple(ws, iv.k, &last, pairs ? &y0 : nullptr)) return 1;     // V^H's last stage (pairs: with Y_0)
+    if ((!pairs || back) && enqueue_couple(ws, iv.k, nullptr, &y0)) return 1;          // Y_0
+    if ((!back || backwalk_keeps_vdag_stage(ws)) && enqueue_couple(ws, iv.k, &last, pairs && !back ? &y0 : nullptr)) return 1;   // V^H's last stage (pairs: with Y_0)
     vdag_projected_state_after(ws, x_buf);
     return 0;
 }
 
-// the registered gather of a Z that run_vdag_projected has left: the indices inside the lhs tiles from Z, the others from the virtual z
+// the registered gather of a Z that run_vdag_projected (projected_backwalk: and the sweep behind it) has left: the indices inside the lhs tiles from Z, the others from the virtual z
 int proj_fix_amplitudes(aqc_ws* ws, int x_buf) {
     ProjRoute& pr = ws->proj;
     if (results_guard(ws)) return 1;

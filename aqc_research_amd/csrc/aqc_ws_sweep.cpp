@@ -448,6 +448,11 @@ int enqueue_vdag(aqc_ws* ws, const EvalRoute& r) {
     if (r.vdag_kind == EvalRoute::kRestricted) return run_vdag_restricted(ws, r.x_buf, r.support_in_gather_set);
     return run_apply(ws, true, AQC_BUF_Y, AQC_BUF_Z);
 }
+// objective by projection with the backward walk: the lhs tiles of Z are written by the sweep's first stage, so the sweep itself enqueues
+// the gather right behind that launch (sweep_mfma) -- before the virtual stages, which work in place on the virtual z it also reads
+static bool gather_follows_sweep(const aqc_ws* ws, const EvalRoute& r) {
+    return r.vdag && r.grads && r.vdag_kind == EvalRoute::kProjected && projected_backwalk(ws);
+}
 int enqueue_gather(aqc_ws* ws, const EvalRoute& r) {
     return r.vdag_kind == EvalRoute::kProjected ? proj_fix_amplitudes(ws, r.x_buf) : aqc_ws_gather_launch(ws, AQC_BUF_Z);
 }
@@ -528,9 +533,17 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
     if (ensure_umat(ws, p, projected ? kURoute : kUAll)) return 1;   // (projected: its first stage and the virtual plan are all it reads)
     int r_only_sub = skipw || projected ? -1 : sweep_r_only_sub(ws);   // (the zero-w variant of the kernel has no R-only form)
     // objective by projection: psi is in W already and nobody reads the first stage's z': ITS last sub-stage is the R-only one
-    const bool first_stage_r_only = projected && ws->proj_y0_ready && ws->sw.r_only_last && p.h_stages[0].nsubs >= 2 &&
+    // ... and run_vdag_projected has left C in ZW without running V^H's last stage (projected_backwalk): the first stage is walked
+    // BACK from (psi, C) over the mirrored plan's last stage, Z on the listed tiles comes out of that walk, and the R of its first
+    // sub-stage -- the forward stage's last -- arrives in the same "inputs" form
+    const bool backwalk = projected && ws->proj_y0_ready && projected_backwalk(ws);
+    const bool first_stage_r_only = !backwalk && projected && ws->proj_y0_ready && ws->sw.r_only_last && p.h_stages[0].nsubs >= 2 &&
                                     p.h_stages[0].nsubs <= ws->sw.r_only_max_subs;
     if (first_stage_r_only) r_only_sub = p.h_stages[0].sub_begin + p.h_stages[0].nsubs - 1;
+    if (backwalk) {
+        if (ensure_umat(ws, ws->inv, kURoute)) return 1;
+        r_only_sub = backwalk_conj_sub(nsubs, ws->inv.h_stages.back().sub_begin);
+    }
     bool pair_virtual = projected && ws->proj_y0_ready && projected_pairs(ws);   // the first stage and the virtual stage as one launch
 #ifdef AQC_TUNING
     if (ws->sw.stamps) pair_virtual = false;
@@ -545,8 +558,15 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
         if (ensure_sweep_items(ws, x_buf)) return 1;
     }
     for (size_t s = 0; s < (projected ? 1 : m); ++s) {
-        Stage3Args a = stage3_args(ws, p, s);
-        if (sparse) {
+        Stage3Args a = backwalk ? stage3_args(ws, ws->inv, ws->inv.h_stages.size() - 1) : stage3_args(ws, p, s);
+        if (backwalk) {   // (psi, C) on the listed tiles -> Z there; W keeps psi
+            a.in0 = ws->bufs[AQC_BUF_W];
+            a.in1 = ws->bufs[AQC_BUF_ZW];
+            a.out1 = ws->bufs[AQC_BUF_Z];
+            a.store_out = backwalk_keeps_vdag_stage(ws) ? 0 : 2;   // (single launches: V^H's last stage has written the same tile)
+            a.backwalk = 1;
+            stage3_first_list(ws, a);
+        } else if (sparse) {
             // stage 0: (x, Z) on the listed tiles -> W there; stage 1: (W, checkpoint in ZW) -> the second pair; then in place
             double2* w2 = m >= 3 ? ws->w2 : nullptr;
             double2* z2 = m >= 3 ? ws->zw2 : nullptr;
@@ -565,8 +585,9 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
             a.store_out = s + 1 < m ? 3 : 0;
         }
         if (skipw && !a.items) a.supp = ws->d_combo_prev[x_buf];
-        if (s + 1 == m && r_only_sub >= 0) a.r_only_last = 1;
-        stage3_sweep_fields(a, p, nparts, chunk);
+        if (s + 1 == m && r_only_sub >= 0 && !backwalk) a.r_only_last = 1;
+        stage3_sweep_fields(a, backwalk ? ws->inv : p, nparts, chunk);
+        if (backwalk) a.rpart = p.d_rpart;   // every R to the sweep plan's rows (aqc_backwalk.h)
 #ifdef AQC_TUNING
         const size_t nwg = (size_t)p.ntiles * ws->batch;
         a.debug = (int)ws->sw.debug_skip;
@@ -584,6 +605,9 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
         if (stamps_sweep(ws, a, s, nwg)) return 1;
 #endif
     }
+    // the backward walk has written Z on the lhs tiles and Y_0 is still on the virtual register (several virtual stages work in place
+    // on it): the call's gather, which reads both, goes here
+    if (backwalk && route.gather && !route.gather_rides && proj_fix_amplitudes(ws, x_buf)) return 1;
     if (projected && !pair_virtual && run_projected_stages(ws)) return 1;
     sweep_state_after(ws, sparse);
     ProfScope ps(ws, AQC_K_FINALIZE);
@@ -688,7 +712,7 @@ int aqc_ws_objective_launch(aqc_ws* ws, int x_buf, int block_from, int block_to,
     route.x_buf = x_buf; route.vdag = route.grads = true; route.gather = ws->gather_count > 0;
     if (eval_route(ws, route)) return 1;
     if (enqueue_vdag(ws, route)) return 1;
-    if (route.gather && enqueue_gather(ws, route)) return 1;
+    if (route.gather && !gather_follows_sweep(ws, route) && enqueue_gather(ws, route)) return 1;
     return grad_from_impl(ws, route, block_from, block_to, front_layer);
 }
 
@@ -732,7 +756,8 @@ int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered,
             ws->theta_host = direct ? pin_th : nullptr;
         }
         if (route.vdag && enqueue_vdag(ws, route)) return 1;
-        if (route.gather && !route.gather_rides) {
+        const bool gather_alone = route.gather && !route.gather_rides, gather_late = gather_follows_sweep(ws, route);
+        if (gather_alone && !gather_late) {
             if (enqueue_gather(ws, route)) return 1;
             if (!zero_copy) HIP_OK(hipMemcpyAsync(pin_sm, ws->d_small, sizeof(double2) * nsm, hipMemcpyDeviceToHost, ws->stream));
         }
@@ -740,6 +765,8 @@ int aqc_ws_eval(aqc_ws* ws, const double* thetas, int do_vdag, double* gathered,
             if (grad_from_impl(ws, route, block_from, block_to, front_layer)) return 1;
             if (!zero_copy) HIP_OK(hipMemcpyAsync(pin_gr, ws->d_grads, sizeof(double2) * nth, hipMemcpyDeviceToHost, ws->stream));
         }
+        if (gather_alone && gather_late && !zero_copy)   // (the sweep has enqueued the gather)
+            HIP_OK(hipMemcpyAsync(pin_sm, ws->d_small, sizeof(double2) * nsm, hipMemcpyDeviceToHost, ws->stream));
         ws->theta_host = nullptr;
         return 0;
     };
