@@ -206,6 +206,11 @@ def dptr(arr: np.ndarray):
     return arr.ctypes.data_as(_D)
 
 
+def iptr(arr: np.ndarray):
+    """Pointer to the elements of an int32 array."""
+    return arr.ctypes.data_as(POINTER(c_int32))
+
+
 def as_c128(a, shape=None, name="array") -> np.ndarray:
     a = np.ascontiguousarray(a, dtype=np.complex128)
     if shape is not None and a.shape != tuple(shape):

@@ -344,51 +344,21 @@ struct Environments {
         HIP_OK(hipStreamSynchronize(st));
         return 0;
     }
-    // site p of z, seen through G^H when an operator G sits on w's side there (<G w|z> = <w|G^H z>)
-    int z_site(int p, const M2* op, const double2** out) {
-        *out = z->t[p];
-        if (!op) return 0;
-        const size_t ne = (size_t)z->dims[p] * z->dims[p + 1];
-        if (bsite.reserve(2 * ne)) return 1;
-        double g8[8]; pack(adjoint(*op), g8);
-        HIP_OK(launch_gate1q(z->t[p], bsite, 1, ne, 0, g8, st));
-        *out = bsite;
-        return 0;
-    }
-    // out[u][v] = sum_bit sum_xy conj(A_p[bit][x][u]) in[x][y] B_p[bit][y][v]
-    int step_left(int p, const void* in, const M2* op, DevBuf<double2>& out) {
-        const int xa = w->dims[p], ua = w->dims[p + 1], yb = z->dims[p], vb = z->dims[p + 1];
-        if (mps_env_fits_small(xa, ua, yb, vb)) {   // small bonds: one launch, the operator folded in
-            if (out.reserve((size_t)ua * vb)) return 1;
-            double g8[8];
-            if (op) pack(adjoint(*op), g8);
-            HIP_OK(launch_mps_env_left(in, w->t[p], z->t[p], xa, ua, yb, vb, op ? g8 : nullptr, out, st));
-            return 0;
-        }
-        const double2* bq = nullptr;
-        if (z_site(p, op, &bq)) return 1;
-        if (t.reserve((size_t)xa * vb) || out.reserve((size_t)ua * vb)) return 1;
-        for (int bit = 0; bit < 2; ++bit) {
-            HIP_OK(launch_zgemm(false, false, xa, vb, yb, in, yb, bq + (size_t)bit * yb * vb, vb, t, vb, st));
-            HIP_OK(launch_zgemm(true, bit == 1, ua, vb, xa, w->t[p] + (size_t)bit * xa * ua, ua, t, vb, out, vb, st));
-        }
-        return 0;
+    // the two site steps (env_left / env_right of aqc_mps_host.h), `op` an operator on w's side; the gemm form alone takes t and bsite
+    int step_left(int p, const double2* in, const M2* op, DevBuf<double2>& out) {
+        const SiteDims d = site_dims(w->dims.data(), z->dims.data(), p);
+        const bool gemm = !mps_env_fits_small(d.xa, d.ua, d.yb, d.vb);
+        if (gemm && ((op && bsite.reserve((size_t)2 * d.yb * d.vb)) || t.reserve((size_t)d.xa * d.vb))) return 1;
+        if (out.reserve((size_t)d.ua * d.vb)) return 1;
+        double g8[8];
+        return env_left(st, in, w->t[p], z->t[p], d, adjoint8(op, g8), bsite, t, out);
     }
     int left(int p) { return step_left(p, L[p], nullptr, L[p + 1]); }
-    // Rc[p-1][x][y] = sum_bit A_p[bit][x][u] (Rc[p] B_p[bit]^H)[u][y]
     int right(int p) {
-        const int xa = w->dims[p], ua = w->dims[p + 1], yb = z->dims[p], vb = z->dims[p + 1];
-        if (mps_env_fits_small(xa, ua, yb, vb)) {
-            if (R[p - 1].reserve((size_t)xa * yb)) return 1;
-            HIP_OK(launch_mps_env_right(R[p], w->t[p], z->t[p], xa, ua, yb, vb, R[p - 1], st));
-            return 0;
-        }
-        if (t.reserve((size_t)ua * yb) || R[p - 1].reserve((size_t)xa * yb)) return 1;
-        for (int bit = 0; bit < 2; ++bit) {
-            HIP_OK(launch_zgemm_bh(false, false, ua, yb, vb, R[p], vb, z->t[p] + (size_t)bit * yb * vb, vb, t, yb, st));
-            HIP_OK(launch_zgemm(false, bit == 1, xa, yb, ua, w->t[p] + (size_t)bit * xa * ua, ua, t, yb, R[p - 1], yb, st));
-        }
-        return 0;
+        const SiteDims d = site_dims(w->dims.data(), z->dims.data(), p);
+        if (!mps_env_fits_small(d.xa, d.ua, d.yb, d.vb) && t.reserve((size_t)d.ua * d.yb)) return 1;
+        if (R[p - 1].reserve((size_t)d.xa * d.yb)) return 1;
+        return env_right(st, R[p], w->t[p], z->t[p], d, t, R[p - 1]);
     }
     int chain(int p, bool first, int k, const M2* op) { return step_left(p, first ? L[p] : e[k ^ 1], op, e[k]); }
     int close(int hi, int k, int slot) {
@@ -613,40 +583,23 @@ int aqc_mps_dot_ops(aqc_mps* a, aqc_mps* b, int nops, const int32_t* qubits, con
         if (qubits[i] < 0 || qubits[i] >= n || op_of[qubits[i]] >= 0) return failf("operator qubits must be distinct and in range");
         op_of[qubits[i]] = i;
     }
-    size_t need = 1, site_max = 1;
-    for (int q = 0; q <= n; ++q) need = std::max(need, (size_t)a->dims[q] * b->dims[q]);
-    for (int q = 0; q < n; ++q) {
-        need = std::max(need, (size_t)a->dims[q] * b->dims[q + 1]);
+    const size_t need = overlap_scratch_elems(n, a->dims.data(), b->dims.data());
+    size_t site_max = 1;
+    for (int q = 0; q < n; ++q)
         if (op_of[q] >= 0) site_max = std::max(site_max, site_elems(b, q));
-    }
     if (a->tmp.reserve((3 * need + site_max))) return 1;
     double2* e = a->tmp;
-    double2* en = e + need;
-    double2* t = en + need;
-    double2* bsite = t + need;
-    auto b_site = [&](int q, const double2** ptr) -> int {   // site q of b, seen through G^H when an operator sits there
-        *ptr = b->t[q];
-        if (op_of[q] < 0) return 0;
-        const double* g = gates + 8 * (size_t)op_of[q];
-        const double gh[8] = {g[0], -g[1], g[4], -g[5], g[2], -g[3], g[6], -g[7]};   // conjugate transpose of the 2x2
-        HIP_OK(launch_gate1q(b->t[q], bsite, 1, (size_t)b->dims[q] * b->dims[q + 1], 0, gh, st));
-        *ptr = bsite;
-        return 0;
+    double2* bsite = e + 3 * need;
+    StreamOps ops{st};
+    auto a_site = [&](int q) { return (const double2*)a->t[q]; };
+    auto b_site = [&](int q) {   // site q of b, seen through G^H when an operator sits there
+        const M2 g = op_of[q] >= 0 ? unpack(gates + 8 * (size_t)op_of[q]) : M2{};
+        double gh8[8];
+        return site_through(st, b->t[q], (size_t)b->dims[q] * b->dims[q + 1], adjoint8(op_of[q] >= 0 ? &g : nullptr, gh8), bsite);
     };
-    const double2* bq = nullptr;
-    if (b_site(0, &bq)) return 1;
-    // E[x][y] = sum_bit conj(A_0[bit][0][x]) B_0[bit][0][y]
-    HIP_OK(launch_zgemm(true, false, a->dims[1], b->dims[1], 2, a->t[0], a->dims[1], bq, b->dims[1], e, b->dims[1], st));
-    for (int q = 1; q < n; ++q) {
-        const int xa = a->dims[q], ua = a->dims[q + 1], yb = b->dims[q], vb = b->dims[q + 1];
-        if (b_site(q, &bq)) return 1;
-        for (int bit = 0; bit < 2; ++bit) {
-            HIP_OK(launch_zgemm(false, false, xa, vb, yb, e, yb, bq + (size_t)bit * yb * vb, vb, t, vb, st));
-            HIP_OK(launch_zgemm(true, bit == 1, ua, vb, xa, a->t[q] + (size_t)bit * xa * ua, ua, t, vb, en, vb, st));
-        }
-        std::swap(e, en);
-    }
-    HIP_OK(hipMemcpyAsync(out, e, sizeof(double2), hipMemcpyDeviceToHost, st));
+    const double2* res = overlap_chain(ops, n, a->dims.data(), b->dims.data(), a_site, b_site, e, e + need, e + 2 * need);
+    if (!res) return 1;
+    HIP_OK(hipMemcpyAsync(out, res, sizeof(double2), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return 0;
 }

@@ -13,6 +13,7 @@
 //   ex.entangle(step)       the routed entangler of an Entangle step on both operands
 //   ex.rotate(q, g)         the 1-qubit gate g on site q of both operands
 //   ex.rotate_recorded(env, step, slot)   a recorded Rotate step: slots slot, slot + 1, ... (rotate_recorded_stepwise below, or fused)
+// The site steps behind left / right / chain of the single-lane executors are stated in aqc_mps_contract.h.
 #pragma once
 #include <utility>
 #include <vector>

@@ -1,7 +1,8 @@
 // Host-side helpers shared by the single-lane MPS engine (aqc_mps_engine.cpp) and the lockstep lanes (aqc_mps_batch.cpp): error
 // reporting, the checks of a circuit description and of a block range.  The gates themselves -- 2 x 2 algebra, entangler matrices, the block list and the walk of
 // an ansatz -- are stated in aqc_mps_walk.h (included through aqc_launch.h), the skeleton that executes a gradient walk in
-// aqc_mps_gradwalk.h.  Private to csrc/ (everything has internal linkage).
+// aqc_mps_gradwalk.h, the site step of a pair of states in aqc_mps_contract.h; its device executor and the small-or-gemm choice of an
+// environment step are here.  Private to csrc/ (everything has internal linkage).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -10,6 +11,7 @@
 
 #include "../../include/aqc_hip.h"
 #include "aqc_launch.h"
+#include "aqc_mps_contract.h"
 #include "aqc_mps_gradwalk.h"
 
 namespace aqc {
@@ -40,6 +42,54 @@ namespace {
         if (e_ != hipSuccess) return failf("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// ---- the site steps of aqc_mps_contract.h on the device: the products on one stream
+struct StreamOps {
+    hipStream_t st;
+    int gemm(bool conj_t, bool accum, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc) {
+        HIP_OK(launch_zgemm(conj_t, accum, M, N, K, A, lda, B, ldb, C, ldc, st));
+        return 0;
+    }
+    int gemm_bh(bool conj_t, bool accum, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc) {
+        HIP_OK(launch_zgemm_bh(conj_t, accum, M, N, K, A, lda, B, ldb, C, ldc, st));
+        return 0;
+    }
+};
+
+// An operator G on A's side is read off B's: <G a|b> = <a|G^H b>.  The packed G^H, or null without an operator ...
+[[maybe_unused]] const double* adjoint8(const M2* op, double* g8) {
+    if (!op) return nullptr;
+    pack(adjoint(*op), g8);
+    return g8;
+}
+// ... and site p of B seen through it: B_p itself without an operator, else `scratch` ([2][ne]) after one launch; null after a failure
+[[maybe_unused]] const double2* site_through(hipStream_t st, const double2* b_p, size_t ne, const double* gh8, double2* scratch) {
+    if (!gh8) return b_p;
+    const hipError_t e = launch_gate1q(b_p, scratch, 1, ne, 0, gh8, st);
+    if (e == hipSuccess) return scratch;
+    failf("launch_gate1q failed: %s", hipGetErrorString(e));
+    return nullptr;
+}
+
+// An environment step through site p (gh8: an operator on A's side): ONE launch when the bonds are small, the operator folded in;
+// else the products of contract_left / contract_right (tmp as they size it), the site of B first taken through G^H into `bsite`.
+[[maybe_unused]] int env_left(hipStream_t st, const double2* in, const double2* a_p, const double2* b_p, const SiteDims& d, const double* gh8,
+                              double2* bsite, double2* tmp, double2* out) {
+    if (mps_env_fits_small(d.xa, d.ua, d.yb, d.vb)) {
+        HIP_OK(launch_mps_env_left(in, a_p, b_p, d.xa, d.ua, d.yb, d.vb, gh8, out, st));
+        return 0;
+    }
+    b_p = site_through(st, b_p, (size_t)d.yb * d.vb, gh8, bsite);
+    StreamOps ops{st};
+    return !b_p || contract_left(ops, in, a_p, b_p, d, tmp, out);
+}
+[[maybe_unused]] int env_right(hipStream_t st, const double2* rc, const double2* a_p, const double2* b_p, const SiteDims& d, double2* tmp, double2* out) {
+    if (mps_env_fits_small(d.xa, d.ua, d.yb, d.vb)) {
+        HIP_OK(launch_mps_env_right(rc, a_p, b_p, d.xa, d.ua, d.yb, d.vb, out, st));
+        return 0;
+    }
+    StreamOps ops{st};
+    return contract_right(ops, rc, a_p, b_p, d, tmp, out);
+}
 
 [[maybe_unused]] int check_circuit(const aqc_circuit* c, int n) {
     if (!c || !c->blocks) return failf("null circuit description");

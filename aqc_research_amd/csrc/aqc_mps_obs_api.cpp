@@ -26,7 +26,7 @@ struct StateWork {
     std::vector<double2> h_sums;
 };
 
-// L_0 .. L_{n-1} and R_n .. R_1 of <psi|psi>; gemm route: with the engine's environment steps (one launch per site at bonds <= 64, else two zgemm per bit)
+// L_0 .. L_{n-1} and R_n .. R_1 of <psi|psi>; gemm route: with the engine's environment steps on the pair (psi, psi) (env_left / env_right of aqc_mps_host.h)
 int environments(StateWork& w, hipStream_t st, bool fused) {
     const int n = w.n;
     const size_t total = w.off[n + 1];
@@ -37,34 +37,11 @@ int environments(StateWork& w, hipStream_t st, bool fused) {
     HIP_OK(hipMemcpyAsync(w.env_l + w.off[0], one, sizeof one, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(w.env_r + w.off[n], one, sizeof one, hipMemcpyHostToDevice, st));
     if (fused) return 0;   // the fused route sweeps them on the matrix cores (run_fused)
-    for (int q = 0; q + 1 < n; ++q) {
-        const int x = w.dims[q], u = w.dims[q + 1];
-        const double2* in = w.env_l + w.off[q];
-        double2* out = w.env_l + w.off[q + 1];
-        if (mps_env_fits_small(x, u, x, u)) {
-            HIP_OK(launch_mps_env_left(in, w.t[q], w.t[q], x, u, x, u, nullptr, out, st));
-        } else {
-            for (int bit = 0; bit < 2; ++bit) {
-                const double2* tq = w.t[q] + (size_t)bit * x * u;
-                HIP_OK(launch_zgemm(false, false, x, u, x, in, x, tq, u, w.tmp, u, st));
-                HIP_OK(launch_zgemm(true, bit == 1, u, u, x, tq, u, w.tmp, u, out, u, st));
-            }
-        }
-    }
-    for (int q = n - 1; q >= 1; --q) {
-        const int x = w.dims[q], u = w.dims[q + 1];
-        const double2* in = w.env_r + w.off[q + 1];
-        double2* out = w.env_r + w.off[q];
-        if (mps_env_fits_small(x, u, x, u)) {
-            HIP_OK(launch_mps_env_right(in, w.t[q], w.t[q], x, u, x, u, out, st));
-        } else {
-            for (int bit = 0; bit < 2; ++bit) {
-                const double2* tq = w.t[q] + (size_t)bit * x * u;
-                HIP_OK(launch_zgemm_bh(false, false, u, x, u, in, u, tq, u, w.tmp, x, st));
-                HIP_OK(launch_zgemm(false, bit == 1, x, x, u, tq, u, w.tmp, x, out, x, st));
-            }
-        }
-    }
+    const int* dims = w.dims.data();
+    for (int q = 0; q + 1 < n; ++q)
+        if (env_left(st, w.env_l + w.off[q], w.t[q], w.t[q], site_dims(dims, dims, q), nullptr, nullptr, w.tmp, w.env_l + w.off[q + 1])) return 1;
+    for (int q = n - 1; q >= 1; --q)
+        if (env_right(st, w.env_r + w.off[q + 1], w.t[q], w.t[q], site_dims(dims, dims, q), w.tmp, w.env_r + w.off[q])) return 1;
     return 0;
 }
 

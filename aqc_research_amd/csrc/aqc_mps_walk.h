@@ -39,6 +39,7 @@ struct M2 { cd m[4]; };   // row-major 2x2
 [[maybe_unused]] M2 rx_m(double t) { const double c = std::cos(0.5 * t), s = std::sin(0.5 * t); return {{c, cd(0, -s), cd(0, -s), c}}; }
 [[maybe_unused]] const M2 kPauliX = {{0.0, 1.0, 1.0, 0.0}}, kPauliY = {{0.0, cd(0, -1), cd(0, 1), 0.0}}, kPauliZ = {{1.0, 0.0, 0.0, -1.0}}, kProj1 = {{0.0, 0.0, 0.0, 1.0}};
 [[maybe_unused]] void pack(const M2& g, double* out8) { for (int i = 0; i < 4; ++i) { out8[2 * i] = g.m[i].real(); out8[2 * i + 1] = g.m[i].imag(); } }
+[[maybe_unused]] M2 unpack(const double* g8) { return {{cd(g8[0], g8[1]), cd(g8[2], g8[3]), cd(g8[4], g8[5]), cd(g8[6], g8[7])}}; }
 
 constexpr int RZ = 1, RY = 2, RX = 3;   // LaneRot::kind; also names the Pauli generator of a recorded rotation
 [[maybe_unused]] const M2& pauli_of(int kind) { return kind == RZ ? kPauliZ : (kind == RY ? kPauliY : kPauliX); }

@@ -3,7 +3,7 @@
 //   aqc_ws_plan.cpp    lowering of stage plans to device tables (micro-ops, sub-stage slot tables), mirrored V^H plans
 //   aqc_ws_sweep.cpp   V / V^H launches, the w/z sweep (dense and sparse-lhs routes), the route of an evaluation (eval_route), aqc_ws_eval
 //   aqc_ws_optim.cpp   device-resident L-BFGS (surrogate and matrix objectives) and the one-call surrogate evaluation
-//   aqc_ws_extra.cpp   zgemm, gate-level building blocks, coordinate descent, MPS helpers
+//   aqc_ws_extra.cpp   zgemm, gate-level building blocks, the XXZ chain, reduced density matrices, coordinate descent, MPS helpers
 //   aqc_ws_sketch.cpp  sketched AQC: resident targets, sketching-vector generators, device-resident ADAM, aqc_qr
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -4,6 +4,7 @@
 #include <chrono>
 
 #include "aqc_cd_rule.h"
+#include "aqc_mps_contract.h"
 #include "aqc_obs_rule.h"
 #include "aqc_xxz_rule.h"
 
@@ -779,6 +780,22 @@ static int mps_to_vec_batch_uniform(aqc_ws* ws, int count, const int32_t* slots,
     return 0;
 }
 
+namespace {
+
+// the left steps of aqc_mps_contract.h on the workspace's stream, every launch an AQC_K_MISC event of the profile (the overlap chain is
+// all the workspace runs: it needs no gemm_bh)
+struct WsOps {
+    aqc_ws* ws;
+    int gemm(bool conj_t, bool accum, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc) {
+        ProfScope ps(ws, AQC_K_MISC);
+        HIP_OK(launch_zgemm(conj_t, accum, M, N, K, A, lda, B, ldb, C, ldc, ws->stream));
+        return 0;
+    }
+};
+
+}  // namespace
+
+// <a|b> of two MPS slots: the overlap chain of aqc_mps_contract.h
 int aqc_ws_mps_dot(aqc_ws* ws, int slot_a, int slot_b, double* out) {
     if (check_mps_slot(ws, slot_a, true) || check_mps_slot(ws, slot_b, true)) return 1;
     if (!out) return fail("null output");
@@ -786,31 +803,14 @@ int aqc_ws_mps_dot(aqc_ws* ws, int slot_a, int slot_b, double* out) {
     const aqc_ws::MpsSlot& a = ws->mps[slot_a];
     const aqc_ws::MpsSlot& b = ws->mps[slot_b];
     const int n = ws->ctx->prog.n;
-    size_t need = 1;
-    for (int q = 0; q <= n; ++q) need = std::max(need, (size_t)a.dims[q] * b.dims[q]);
-    for (int q = 0; q < n; ++q) need = std::max(need, (size_t)a.dims[q] * b.dims[q + 1]);
+    const size_t need = overlap_scratch_elems(n, a.dims.data(), b.dims.data());
     if (mps_scratch(ws, 3 * need)) return 1;
-    double2* e0 = ws->d_mps_scratch;
-    double2* e1 = e0 + need;
-    double2* t = e1 + need;
-    {   // E[x][y] = sum_b conj(A0[b][x]) B0[b][y]
-        ProfScope ps(ws, AQC_K_MISC);
-        HIP_OK(launch_zgemm(true, false, a.dims[1], b.dims[1], 2, a.d_t, a.dims[1], b.d_t, b.dims[1], e0, b.dims[1], ws->stream));
-    }
-    double2* e = e0;
-    double2* en = e1;
-    for (int q = 1; q < n; ++q) {
-        const int xa = a.dims[q], ua = a.dims[q + 1], yb = b.dims[q], vb = b.dims[q + 1];
-        for (int bit = 0; bit < 2; ++bit) {
-            ProfScope ps(ws, AQC_K_MISC);
-            // T = E B_q[bit]            (xa x vb)
-            HIP_OK(launch_zgemm(false, false, xa, vb, yb, e, yb, b.d_t + b.offset[q] + (size_t)bit * yb * vb, vb, t, vb, ws->stream));
-            // E' (+)= A_q[bit]^H T      (ua x vb)
-            HIP_OK(launch_zgemm(true, bit == 1, ua, vb, xa, a.d_t + a.offset[q] + (size_t)bit * xa * ua, ua, t, vb, en, vb, ws->stream));
-        }
-        std::swap(e, en);
-    }
-    HIP_OK(hipMemcpyAsync(out, e, sizeof(double2), hipMemcpyDeviceToHost, ws->stream));
+    double2* e = ws->d_mps_scratch;
+    WsOps ops{ws};
+    const double2* res = overlap_chain(ops, n, a.dims.data(), b.dims.data(), [&](int q) { return (const double2*)(a.d_t + a.offset[q]); },
+                                       [&](int q) { return (const double2*)(b.d_t + b.offset[q]); }, e, e + need, e + 2 * need);
+    if (!res) return 1;
+    HIP_OK(hipMemcpyAsync(out, res, sizeof(double2), hipMemcpyDeviceToHost, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
     return 0;
 }

@@ -16,7 +16,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _lib, gates
-from ._lib import LanesRefused, check, dptr
+from ._lib import LanesRefused, check, dptr, iptr
 
 _X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
 _Y = np.array([[0, -1j], [1j, 0]], dtype=np.complex128)
@@ -110,7 +110,7 @@ class DeviceMPS:
         n, dims, g, lm = _pack(qiskit_mps)
         h = c_void_p()
         dev = _default_device() if device is None else int(device)
-        check(_lib.lib().aqc_mps_create(dev, n, dims.ctypes.data_as(POINTER(c_int32)), dptr(g), dptr(lm), byref(h)))
+        check(_lib.lib().aqc_mps_create(dev, n, iptr(dims), dptr(g), dptr(lm), byref(h)))
         m = cls(h)
         if trunc_thr > 1e-12 and not assume_canonical and not _canonical_verdict(qiskit_mps):
             m.canonicalize()
@@ -147,7 +147,7 @@ class DeviceMPS:
     @property
     def bond_dims(self) -> np.ndarray:
         d = np.zeros(self.num_qubits + 1, dtype=np.int32)
-        check(self._L.aqc_mps_dims(self.handle, d.ctypes.data_as(POINTER(c_int32))))
+        check(self._L.aqc_mps_dims(self.handle, iptr(d)))
         return d
 
     @property
@@ -200,7 +200,7 @@ class DeviceMPS:
         qs = np.ascontiguousarray([q for q, _ in ops], dtype=np.int32)
         gs = np.ascontiguousarray(np.stack([np.asarray(g, dtype=np.complex128) for _, g in ops]))
         out = np.empty(1, dtype=np.complex128)
-        check(self._L.aqc_mps_dot_ops(self.handle, other.handle, len(ops), qs.ctypes.data_as(POINTER(c_int32)), dptr(gs), dptr(out)))
+        check(self._L.aqc_mps_dot_ops(self.handle, other.handle, len(ops), iptr(qs), dptr(gs), dptr(out)))
         return np.complex128(out[0])
 
     def close(self) -> None:
@@ -256,7 +256,7 @@ def svd_batch(a: np.ndarray, rows=None, cols=None, device: Optional[int] = None)
         if np.any(v < 1) or np.any(v > top):
             raise ValueError(f"{name} must lie in 1..{top}")
         v = np.ascontiguousarray(v, dtype=np.int32)
-        return v, v.ctypes.data_as(POINTER(c_int32))
+        return v, iptr(v)
 
     rows, prows = sizes(rows, m, "rows")
     cols, pcols = sizes(cols, n, "cols")
@@ -264,7 +264,7 @@ def svd_batch(a: np.ndarray, rows=None, cols=None, device: Optional[int] = None)
     u, s, vh = np.empty((count, m, k), dtype=np.complex128), np.empty((count, k)), np.empty((count, k, n), dtype=np.complex128)
     sweeps, status = np.zeros(count, dtype=np.int32), np.zeros(count, dtype=np.int32)
     check(_lib.lib().aqc_svd_batch(_default_device() if device is None else int(device), count, m, n, prows, pcols, dptr(a), dptr(u), dptr(s), dptr(vh),
-                                   sweeps.ctypes.data_as(POINTER(c_int32)), status.ctypes.data_as(POINTER(c_int32))))
+                                   iptr(sweeps), iptr(status)))
     return u, s, vh, sweeps, status
 
 
@@ -299,7 +299,7 @@ def _describe(circ):
     blocks = np.ascontiguousarray(circ.blocks, dtype=np.int32)
     trotter = hasattr(circ, "is_second_order")
     desc = _CircuitDesc(circ.num_qubits, _lib.ENTANGLERS[circ.entangler], circ.num_blocks, int(trotter),
-                        int(trotter and circ.is_second_order), blocks.ctypes.data_as(POINTER(c_int32)))
+                        int(trotter and circ.is_second_order), iptr(blocks))
     return desc, blocks
 
 
@@ -602,7 +602,7 @@ class LockstepLanes:
             c.th = th
             c.disc = np.zeros(self.lanes, dtype=np.float64)
             c.bonds = np.zeros(self.lanes, dtype=np.int32)
-            c.details = (dptr(c.disc), c.bonds.ctypes.data_as(POINTER(c_int32)))
+            c.details = (dptr(c.disc), iptr(c.bonds))
         c.desc, c.keep = _describe(circ)
         c.circ = byref(c.desc)
         c.lo, c.hi = _block_range(circ, block_range)

@@ -19,23 +19,20 @@ list equals the one-state call bit for bit.
 Device calls: ``pair_density_matrices``, ``reduced_density_matrix`` (and ``plan``, which needs no device).  The rest is NumPy on
 their results.
 """
-from ctypes import POINTER, c_int32, c_void_p
+from ctypes import c_void_p
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from ._lib import check, dptr
+from ._lib import check, dptr, iptr
 from .mps_engine import DeviceMPS
-from .observables import _single_axis, pauli_expectation, pauli_matrix
+from .observables import (_bond_energies_of, _bond_pairs, _correlation_letters, _correlation_of, _correlation_pairs, _magnetisation_of,
+                          _magnetisation_pairs, _single_axis, pauli_expectation, pauli_matrix)  # noqa: F401  (the last two: for callers)
 from .xxz import _finite
 
 FUSED_CAP = 64   # AQC_MPS_OBS_FUSED_CAP of include/aqc_hip.h
 _METHODS = {None: 0, "fused": 1, "gemm": 2}   # AQC_MPS_OBS_*
-
-
-def _i32(a: np.ndarray):
-    return a.ctypes.data_as(POINTER(c_int32))
 
 
 def _pairs(pairs, n: int) -> np.ndarray:
@@ -60,7 +57,7 @@ def plan(num_qubits: int, pairs: Sequence[Sequence[int]]) -> dict:
     last = np.zeros(n, np.int32)
     nemits = np.zeros(1, np.int32)
     serves = np.zeros((arr.shape[0], 3), np.int32)
-    check(_lib.lib().aqc_mps_obs_plan(n, arr.shape[0], _i32(arr), _i32(last), _i32(nemits), _i32(serves)))
+    check(_lib.lib().aqc_mps_obs_plan(n, arr.shape[0], iptr(arr), iptr(last), iptr(nemits), iptr(serves)))
     return {
         "chains": {int(i): int(e) for i, e in enumerate(last) if e >= 0},
         "emissions": int(nemits[0]),
@@ -71,7 +68,7 @@ def plan(num_qubits: int, pairs: Sequence[Sequence[int]]) -> dict:
 def route(bond_dims) -> str:
     """The route the rule picks for a state with these n + 1 bond dimensions: ``"fused"`` or ``"gemm"``."""
     d = np.ascontiguousarray(bond_dims, dtype=np.int32)
-    r = _lib.lib().aqc_mps_obs_route(d.size - 1, _i32(d))
+    r = _lib.lib().aqc_mps_obs_route(d.size - 1, iptr(d))
     if r not in (1, 2):
         raise ValueError("expects the n + 1 bond dimensions of a state")
     return "fused" if r == 1 else "gemm"
@@ -132,7 +129,7 @@ def _rdms(lanes: _Lanes, arr: np.ndarray, method: Optional[str]) -> np.ndarray:
                 raise ValueError(f"the fused route takes bond dimensions up to {FUSED_CAP}, not {int(m.bond_dims.max())}")
     handles = (c_void_p * len(lanes.lanes))(*[m.handle for m in lanes.lanes])
     out = np.empty((len(lanes.lanes), arr.shape[0], 4, 4), dtype=np.complex128)
-    check(_lib.lib().aqc_mps_obs_pairs(handles, len(lanes.lanes), arr.shape[0], _i32(arr), _METHODS[method], dptr(out)))
+    check(_lib.lib().aqc_mps_obs_pairs(handles, len(lanes.lanes), arr.shape[0], iptr(arr), _METHODS[method], dptr(out)))
     return out[0] if lanes.single else out
 
 
@@ -171,58 +168,33 @@ def reduced_density_matrix(states, qubits: Sequence[int], *, method: Optional[st
         return r[..., 0, :, 0, :] + r[..., 1, :, 1, :]
 
 
-def _num_qubits(lanes: _Lanes) -> int:
-    return lanes.lanes[0].num_qubits
+
+
+def _rho_of(states, pairs_of, method: Optional[str]):
+    """``(rho, n)``: the matrices of the pairs ``pairs_of(n)`` that a derived observable of ``observables.py`` asks for."""
+    with _Lanes(states) as lanes:
+        n = lanes.lanes[0].num_qubits
+        return _rdms(lanes, _pairs(pairs_of(n), n), method), n
 
 
 def magnetisation(states, axis: str = "z", *, method: Optional[str] = None) -> np.ndarray:
     """<sigma_i> along ``axis`` for every qubit: ``(n,)`` or ``(lanes, n)``.  Read from the ceil(n / 2) pairs (0, 1), (2, 3), ...
     (the last qubit of an odd chain with its left neighbour).  Not divided by <psi|psi>."""
     a = _single_axis(axis)
-    with _Lanes(states) as lanes:
-        n = _num_qubits(lanes)
-        pairs = [(q, q + 1) for q in range(0, n - 1, 2)] + ([(n - 2, n - 1)] if n % 2 else [])
-        rho = _rdms(lanes, _pairs(pairs, n), method)
-    first, second = pauli_expectation(rho, a + "i"), pauli_expectation(rho, "i" + a)
-    first, second = np.atleast_1d(first), np.atleast_1d(second)
-    out = np.empty(rho.shape[:-3] + (n,), dtype=np.float64)
-    half = n // 2
-    out[..., 0:2 * half:2] = first[..., :half]
-    out[..., 1:2 * half:2] = second[..., :half]
-    if n % 2:
-        out[..., n - 1] = second[..., half]
-    return out
+    rho, n = _rho_of(states, _magnetisation_pairs, method)
+    return _magnetisation_of(rho, n, a)
 
 
 def correlation_matrix(states, letters: str = "zz", connected: bool = False, *, method: Optional[str] = None) -> np.ndarray:
     """C[i][j] = <a_i b_j> for ``letters = "ab"`` out of x, y, z, over all pairs: ``(n, n)`` or ``(lanes, n, n)``.  The diagonal is 1
     for equal letters and 0 otherwise, as in ``observables.correlation_matrix``.  ``connected``: minus <a_i><b_j>."""
-    if not isinstance(letters, str) or len(letters) != 2:
-        raise ValueError("letters must name two axes, such as 'zz'")
-    a, b = _single_axis(letters[0]), _single_axis(letters[1])
-    with _Lanes(states) as lanes:
-        n = _num_qubits(lanes)
-        pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
-        rho = _rdms(lanes, _pairs(pairs, n), method)
-    upper, lower = np.atleast_1d(pauli_expectation(rho, a + b)), np.atleast_1d(pauli_expectation(rho, b + a))
-    out = np.empty(rho.shape[:-3] + (n, n), dtype=np.float64)
-    iu = np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs])
-    out[..., iu[0], iu[1]] = upper
-    out[..., iu[1], iu[0]] = lower
-    out[..., np.arange(n), np.arange(n)] = 1.0 if a == b else 0.0
-    if connected:
-        lead = rho[..., : n - 1, :, :]   # the pairs (0, 1) .. (0, n - 1): qubit 0 from the first, qubit q from (0, q)
-        ma = np.concatenate((np.atleast_1d(pauli_expectation(lead[..., :1, :, :], a + "i")), np.atleast_1d(pauli_expectation(lead, "i" + a))), axis=-1)
-        mb = np.concatenate((np.atleast_1d(pauli_expectation(lead[..., :1, :, :], b + "i")), np.atleast_1d(pauli_expectation(lead, "i" + b))), axis=-1)
-        out = out - ma[..., :, None] * mb[..., None, :]
-    return out
+    a, b = _correlation_letters(letters)
+    rho, n = _rho_of(states, _correlation_pairs, method)
+    return _correlation_of(rho, n, a, b, connected)
 
 
 def bond_energies(states, delta: float, *, method: Optional[str] = None) -> np.ndarray:
     """-1/4 tr rho_{i,i+1} (XX + YY + delta ZZ) for the n - 1 bonds of the open XXZ chain: ``(n - 1,)`` or ``(lanes, n - 1)``."""
     delta = _finite(delta, "delta")
-    with _Lanes(states) as lanes:
-        n = _num_qubits(lanes)
-        rho = _rdms(lanes, _pairs([(q, q + 1) for q in range(n - 1)], n), method)
-    op = -0.25 * (pauli_matrix("xx") + pauli_matrix("yy") + delta * pauli_matrix("zz"))
-    return np.einsum("...ab,ba->...", rho, op).real
+    rho, _ = _rho_of(states, _bond_pairs, method)
+    return _bond_energies_of(rho, delta)

@@ -15,13 +15,12 @@ for bit.  The matrices are exactly Hermitian.
 Device calls: ``pair_density_matrices``, ``reduced_density_matrix`` (and ``plan``, which needs no device).  The rest is NumPy on their
 results: ``pauli_expectation``, ``magnetisation``, ``correlation_matrix``, ``bond_energies``.
 """
-from ctypes import POINTER, c_int32
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from ._lib import check, dptr
+from ._lib import check, dptr, iptr
 from .gates import _dev
 from .xxz import _finite, _lanes_of
 
@@ -33,10 +32,6 @@ _PAULI = {
     "y": np.array([[0, -1j], [1j, 0]], dtype=np.complex128),
     "z": np.array([[1, 0], [0, -1]], dtype=np.complex128),
 }
-
-
-def _i32(a: np.ndarray):
-    return a.ctypes.data_as(POINTER(c_int32))
 
 
 def _qubit_sets(qubits, n: int, k: Optional[int] = None) -> np.ndarray:
@@ -70,8 +65,8 @@ def plan(num_qubits: int, pairs: Sequence[Sequence[int]]) -> dict:
     pass_nsub = np.zeros(cap, np.int32)
     subsets = np.zeros((cap, 4), np.int32)
     serves = np.zeros((npairs, 2), np.int32)
-    check(_lib.lib().aqc_obs_plan(int(num_qubits), npairs, _i32(sets), cap, cap, _i32(npasses), _i32(nsubsets), _i32(pass_bits),
-                                  _i32(pass_nsub), _i32(subsets), _i32(serves)))
+    check(_lib.lib().aqc_obs_plan(int(num_qubits), npairs, iptr(sets), cap, cap, iptr(npasses), iptr(nsubsets), iptr(pass_bits),
+                                  iptr(pass_nsub), iptr(subsets), iptr(serves)))
     first = np.concatenate(([0], np.cumsum(pass_nsub[: npasses[0]])))
     return {
         "passes": [[int(q) for q in row if q >= 0] for row in pass_bits[: npasses[0]]],
@@ -84,7 +79,7 @@ def _rdm(states: np.ndarray, sets: np.ndarray, device: Optional[int]) -> np.ndar
     n, lanes = _lanes_of(states)
     nsets, k = sets.shape
     out = np.empty((lanes or 1, nsets, 1 << k, 1 << k), dtype=np.complex128)
-    check(_lib.lib().aqc_obs_rdm(_dev(device), n, lanes or 1, dptr(states), int(k), int(nsets), _i32(sets), dptr(out)))
+    check(_lib.lib().aqc_obs_rdm(_dev(device), n, lanes or 1, dptr(states), int(k), int(nsets), iptr(sets), dptr(out)))
     return out[0] if lanes is None else out
 
 
@@ -133,14 +128,14 @@ def _single_axis(axis: str) -> str:
     return axis.lower()
 
 
-def magnetisation(states: np.ndarray, axis: str = "z", *, device: Optional[int] = None) -> np.ndarray:
-    """<sigma_i> along ``axis`` for every qubit: ``(n,)`` or ``(lanes, n)``.  Read from the ceil(n / 2) pairs (0, 1), (2, 3), ...
-    (the last qubit of an odd chain with its left neighbour)."""
-    a = _single_axis(axis)
-    n, _ = _lanes_of(states)
-    pairs = [(q, q + 1) for q in range(0, n - 1, 2)] + ([(n - 2, n - 1)] if n % 2 else [])
-    rho = pair_density_matrices(states, pairs, device=device)
-    first, second = pauli_expectation(rho, a + "i"), pauli_expectation(rho, "i" + a)
+# ---- derived observables: which pairs each one asks for, and the arithmetic on the matrices that come back.  Stated once, for the
+# dense states here and for the matrix-product states of mps_observables.py: the two modules differ only in how rho is obtained.
+def _magnetisation_pairs(n: int) -> list:
+    return [(q, q + 1) for q in range(0, n - 1, 2)] + ([(n - 2, n - 1)] if n % 2 else [])
+
+
+def _magnetisation_of(rho: np.ndarray, n: int, a: str) -> np.ndarray:
+    first, second = np.atleast_1d(pauli_expectation(rho, a + "i")), np.atleast_1d(pauli_expectation(rho, "i" + a))
     out = np.empty(rho.shape[:-3] + (n,), dtype=np.float64)
     half = n // 2
     out[..., 0:2 * half:2] = first[..., :half]
@@ -150,16 +145,13 @@ def magnetisation(states: np.ndarray, axis: str = "z", *, device: Optional[int] 
     return out
 
 
-def correlation_matrix(states: np.ndarray, letters: str = "zz", connected: bool = False, *, device: Optional[int] = None) -> np.ndarray:
-    """C[i][j] = <a_i b_j> for ``letters = "ab"`` out of x, y, z, over all pairs: ``(n, n)`` or ``(lanes, n, n)``.  The diagonal is 1
-    (a_i a_i = 1; for two different letters a_i b_i = +-i c_i, whose real part is 0).  ``connected``: minus <a_i><b_j>."""
-    if not isinstance(letters, str) or len(letters) != 2:
-        raise ValueError("letters must name two axes, such as 'zz'")
-    a, b = _single_axis(letters[0]), _single_axis(letters[1])
-    n, _ = _lanes_of(states)
-    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
-    rho = pair_density_matrices(states, pairs, device=device)
-    upper, lower = pauli_expectation(rho, a + b), pauli_expectation(rho, b + a)   # <a_i b_j> and <b_i a_j> for i < j
+def _correlation_pairs(n: int) -> list:
+    return [(i, j) for i in range(n) for j in range(i + 1, n)]
+
+
+def _correlation_of(rho: np.ndarray, n: int, a: str, b: str, connected: bool) -> np.ndarray:
+    pairs = _correlation_pairs(n)
+    upper, lower = np.atleast_1d(pauli_expectation(rho, a + b)), np.atleast_1d(pauli_expectation(rho, b + a))   # <a_i b_j> and <b_i a_j> for i < j
     out = np.empty(rho.shape[:-3] + (n, n), dtype=np.float64)
     iu = np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs])
     out[..., iu[0], iu[1]] = upper
@@ -168,10 +160,41 @@ def correlation_matrix(states: np.ndarray, letters: str = "zz", connected: bool 
     if connected:
         # single-site values from the leading pairs (0, 1), (0, 2), ..., (0, n - 1): qubit 0 from the first, qubit q from (0, q)
         lead = rho[..., : n - 1, :, :]
-        ma = np.concatenate((pauli_expectation(lead[..., :1, :, :], a + "i"), pauli_expectation(lead, "i" + a)), axis=-1)
-        mb = np.concatenate((pauli_expectation(lead[..., :1, :, :], b + "i"), pauli_expectation(lead, "i" + b)), axis=-1)
+        ma, mb = (np.concatenate((np.atleast_1d(pauli_expectation(lead[..., :1, :, :], c + "i")), np.atleast_1d(pauli_expectation(lead, "i" + c))), axis=-1)
+                  for c in (a, b))
         out = out - ma[..., :, None] * mb[..., None, :]
     return out
+
+
+def _correlation_letters(letters: str):
+    if not isinstance(letters, str) or len(letters) != 2:
+        raise ValueError("letters must name two axes, such as 'zz'")
+    return _single_axis(letters[0]), _single_axis(letters[1])
+
+
+def _bond_pairs(n: int) -> list:
+    return [(q, q + 1) for q in range(n - 1)]
+
+
+def _bond_energies_of(rho: np.ndarray, delta: float) -> np.ndarray:
+    op = -0.25 * (pauli_matrix("xx") + pauli_matrix("yy") + delta * pauli_matrix("zz"))
+    return np.einsum("...ab,ba->...", rho, op).real
+
+
+def magnetisation(states: np.ndarray, axis: str = "z", *, device: Optional[int] = None) -> np.ndarray:
+    """<sigma_i> along ``axis`` for every qubit: ``(n,)`` or ``(lanes, n)``.  Read from the ceil(n / 2) pairs (0, 1), (2, 3), ...
+    (the last qubit of an odd chain with its left neighbour)."""
+    a = _single_axis(axis)
+    n, _ = _lanes_of(states)
+    return _magnetisation_of(pair_density_matrices(states, _magnetisation_pairs(n), device=device), n, a)
+
+
+def correlation_matrix(states: np.ndarray, letters: str = "zz", connected: bool = False, *, device: Optional[int] = None) -> np.ndarray:
+    """C[i][j] = <a_i b_j> for ``letters = "ab"`` out of x, y, z, over all pairs: ``(n, n)`` or ``(lanes, n, n)``.  The diagonal is 1
+    (a_i a_i = 1; for two different letters a_i b_i = +-i c_i, whose real part is 0).  ``connected``: minus <a_i><b_j>."""
+    a, b = _correlation_letters(letters)
+    n, _ = _lanes_of(states)
+    return _correlation_of(pair_density_matrices(states, _correlation_pairs(n), device=device), n, a, b, connected)
 
 
 def bond_energies(states: np.ndarray, delta: float, *, device: Optional[int] = None) -> np.ndarray:
@@ -179,6 +202,4 @@ def bond_energies(states: np.ndarray, delta: float, *, device: Optional[int] = N
     sum is the energy ``xxz.xxz_energy(states, delta)``."""
     delta = _finite(delta, "delta")
     n, _ = _lanes_of(states)
-    rho = pair_density_matrices(states, [(q, q + 1) for q in range(n - 1)], device=device)
-    op = -0.25 * (pauli_matrix("xx") + pauli_matrix("yy") + delta * pauli_matrix("zz"))
-    return np.einsum("...ab,ba->...", rho, op).real
+    return _bond_energies_of(pair_density_matrices(states, _bond_pairs(n), device=device), delta)

@@ -9,13 +9,12 @@ States are C-contiguous complex128 arrays in host memory, ``(2^n,)`` or ``(lanes
 Inputs are never modified and results are fresh arrays.  The series is exact to rounding at any time the drivers use, where the
 reference's ``exact_evolution`` (a dense ``expm``) ends near 12 qubits.
 """
-from ctypes import POINTER, c_int32
 from typing import Optional
 
 import numpy as np
 
 from . import _lib
-from ._lib import check, dptr
+from ._lib import check, dptr, iptr
 from .gates import _dev
 
 MIN_QUBITS, MAX_QUBITS = 2, 30
@@ -97,7 +96,7 @@ def xxz_evolve(states: np.ndarray, delta: float, evol_time, *, device: Optional[
     out = np.empty(out_shape, dtype=np.complex128)
     terms = np.zeros(times.size, dtype=np.int32)
     check(_lib.lib().aqc_xxz_evolve(_dev(device), n, int(times.size), int(shared), delta, dptr(times), dptr(states), dptr(out),
-                                    terms.ctypes.data_as(POINTER(c_int32))))
+                                    iptr(terms)))
     if details:
         return out, {"terms": terms, "radius": spectral_radius(n, delta)}
     return out

@@ -89,6 +89,24 @@ def test_gates_exact_against_dense():
     assert m.bond_dims.max() <= 2 ** (n // 2)
 
 
+def test_dot_ops_with_generic_operators_against_dense():
+    """<(prod G_i) a|b> with random complex 2x2 operators -- neither Hermitian nor unitary, so reading b through anything but G^H shows --
+    on the first, a middle and the last site, then on two sites.  Bonds 4 against 3 at 5 qubits: the smallest shape at which all four bond
+    dimensions of an inner site step differ."""
+    from aqc_research_amd.mps_engine import DeviceMPS
+
+    n = 5
+    rng = np.random.default_rng(71)
+    a, b = DeviceMPS.from_qiskit(orc.random_mps(n, 4, rng)), DeviceMPS.from_qiskit(orc.random_mps(n, 3, rng))
+    va, vb = _dense(a), _dense(b)
+    for qubits in ((0,), (2,), (4,), (1, 3)):
+        ops = [(q, rng.standard_normal((2, 2)) + 1j * rng.standard_normal((2, 2))) for q in qubits]
+        ga = va.copy()
+        for q, g in ops:
+            orc.gate2x2(ga, 1 << q, g)
+        assert abs(a.dot_ops(b, ops) - np.vdot(ga, vb)) < TOL, qubits
+
+
 @pytest.mark.parametrize("kind", ["cx", "cz", "cp", "trotter2"])
 def test_native_gradient_and_circuit_against_oracle(kind):
     from aqc_research_amd import ParametricCircuit, TrotterAnsatz
