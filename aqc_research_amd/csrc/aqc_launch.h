@@ -377,6 +377,41 @@ hipError_t launch_mps_obs_fused(const MpsObsFusedArgs& a, int nchains, hipStream
 hipError_t launch_mps_obs_sums(const void* e_base, const int* slots, const int* emits, int count, size_t slot_stride, const void* k_base, size_t k_stride,
                                int chi, void* sums, hipStream_t s);
 
+// aqc_mps_sample.hip (measurement of MPS states: shots and amplitudes; rules: aqc_mps_sample_rule.h)
+struct MpsSampleState {            // one state of a fused launch: entry blockIdx.y of a device table
+    const double2* const* sites;   // [n] site tensors [2][dims[q]][dims[q+1]]
+    const int* dims;               // [n + 1], every one <= kMpsSampleFusedCap
+    const size_t* env_off;         // [n + 1] element offset of R_q in env_r (shots only)
+    const double2* env_r;
+    unsigned char* bits;           // shots: [shots][n], written
+    double2* amps;                 // [shots] psi(b) of every row
+    unsigned char* status;         // shots: [shots], set to 1 where m_0 + m_1 is not finite or not positive (cleared by the host)
+    double* norm2;                 // shots: [1] <psi|psi> = m_0 + m_1 of site 0
+    unsigned long long lane;       // the position of the state in the call: part of the Philox counter
+};
+struct MpsSampleArgs {
+    int n;
+    long long shots;               // rows of the call
+    unsigned long long first_shot, seed;
+    const MpsSampleState* states;
+    const unsigned char* bits_in;  // amplitudes: [shots][n], shared by the states
+};
+hipError_t launch_mps_sample_fused(const MpsSampleArgs& a, int nstates, bool amplitudes, hipStream_t s);   // grid (ceil(shots / 64), states)
+struct MpsSampleRowArgs {          // gemm route, site q of a chunk of `rows` shots that begins at shot `shot0` of the call
+    int q, n, chi;                 // chi = dims[q + 1]
+    long long rows, shot0;
+    unsigned long long first_shot, seed, lane;
+    const double2 *w0, *w1, *g0, *g1;   // [rows][chi]; g: shots only
+    double2* v;                    // [rows][chi] <- the chosen w
+    const unsigned char* bits_in;  // amplitudes: [shots of the call][n]
+    unsigned char* bits;           // the remaining fields as in MpsSampleState, for all shots of the call
+    double2* amps;
+    unsigned char* status;
+    double* norm2;
+};
+hipError_t launch_mps_sample_rows(const MpsSampleRowArgs& a, bool amplitudes, hipStream_t s);
+hipError_t launch_mps_sample_ones(void* v, long long rows, hipStream_t s);   // v[0 .. rows) = 1
+
 // aqc_api.cpp: thread-local message behind aqc_last_error(); returns 1
 int set_error(const std::string& msg);
 

@@ -203,6 +203,18 @@ class DeviceMPS:
         check(self._L.aqc_mps_dot_ops(self.handle, other.handle, len(ops), iptr(qs), dptr(gs), dptr(out)))
         return np.complex128(out[0])
 
+    def sample(self, shots: int, *, seed: int, first_shot: int = 0, method=None, details: bool = False):
+        """Shots drawn from |psi(b)|^2: ``mps_sampling.sample`` of this state."""
+        from .mps_sampling import sample
+
+        return sample(self, shots, seed=seed, first_shot=first_shot, method=method, details=details)
+
+    def amplitudes(self, bits, *, method=None) -> np.ndarray:
+        """psi(b) of the given bit strings: ``mps_sampling.amplitudes`` of this state."""
+        from .mps_sampling import amplitudes
+
+        return amplitudes(self, bits, method=method)
+
     def close(self) -> None:
         if self.handle:
             self._L.aqc_mps_destroy(self.handle)

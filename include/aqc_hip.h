@@ -289,6 +289,31 @@ int aqc_mps_dot_ops(aqc_mps* a, aqc_mps* b, int nops, const int32_t* qubits, con
 int aqc_mps_obs_plan(int n, int npairs, const int32_t* pairs, int32_t* chain_last, int32_t* nemits, int32_t* serves);
 int aqc_mps_obs_route(int n, const int32_t* dims);
 int aqc_mps_obs_pairs(aqc_mps* const* states, int nstates, int npairs, const int32_t* pairs, int method, double* out);
+/* Measurement of one or several MPS states in the computational basis (rules: csrc/aqc_mps_sample_rule.h, kernels:
+ * csrc/aqc_mps_sample.hip): shots drawn from |psi(b)|^2 by perfect sampling along the chain, and the amplitudes psi(b) of given bit
+ * strings.  bits[s][q] is the value of qubit q (= site q = index bit q of the dense vector).  Nothing is rescaled: an amplitude is that
+ * of the state as it is, and p(b) = |psi(b)|^2 / norm2 with norm2 = <psi|psi>.  The uniform of shot s, qubit q of lane l (the position
+ * of the state in the call) is word q % 4 of philox4x64_10(counter = {1 + q / 4, first_shot + s, l, 0}, key = {seed,
+ * AQC_SAMPLE_STREAM}) as a double of [0, 1): a shot depends on (state, seed, lane, shot number) alone.  A branch of zero weight is
+ * never taken; weights that do not add up to a finite positive number fail the call with the lane and the shot named.  States are taken
+ * in whatever gauge they are in and are not modified; they share n >= 1 and the device; the work is ordered on the first state's stream
+ * after the others' have drained.
+ * sample_route: the route the rule picks for bond dimensions dims [n + 1]: AQC_MPS_SAMPLE_FUSED (64 shots per workgroup walk the whole
+ *   chain inside one launch) when every one is at most AQC_MPS_SAMPLE_FUSED_CAP, else AQC_MPS_SAMPLE_GEMM (-1: invalid argument).
+ * sample: 1 <= shots <= 2^24.  bits [nstates][shots][n]; amps [nstates][shots] c128 (psi of the sampled strings) and norm2 [nstates] may
+ *   be NULL.  method: AQC_MPS_SAMPLE_BY_RULE (per state), _FUSED (an error when a bond exceeds the cap) or _GEMM.
+ * amplitudes: bits [count][n] of 0 / 1, shared by the states; amps [nstates][count] c128. */
+#define AQC_MPS_SAMPLE_BY_RULE 0
+#define AQC_MPS_SAMPLE_FUSED 1
+#define AQC_MPS_SAMPLE_GEMM 2
+#define AQC_MPS_SAMPLE_FUSED_CAP 64
+#define AQC_SAMPLE_STREAM 16 /* Philox key word of the measurement draws; the sketching generators use AQC_SKETCH_* = 0, 1, 2 */
+int aqc_mps_sample_route(int n, const int32_t* dims);
+int aqc_mps_sample(aqc_mps* const* states, int nstates, int64_t shots, uint64_t first_shot, uint64_t seed, int method,
+                   uint8_t* bits /* [nstates][shots][n] */, double* amps /* [nstates][shots] c128, may be null */,
+                   double* norm2 /* [nstates], may be null */);
+int aqc_mps_amplitudes(aqc_mps* const* states, int nstates, int64_t count, const uint8_t* bits /* [count][n], shared by the states */,
+                       int method, double* amps /* [nstates][count] c128 */);
 /* ansatz description for the MPS entry points (ParametricCircuit / TrotterAnsatz, parametric_circuit.py:24-70,267-333);
  * unlike aqc_ctx it is not limited to dense-reachable registers.  blocks: int32[2][num_blocks], row 0 = control */
 typedef struct aqc_circuit {
