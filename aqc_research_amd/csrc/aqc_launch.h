@@ -412,6 +412,30 @@ struct MpsSampleRowArgs {          // gemm route, site q of a chunk of `rows` sh
 hipError_t launch_mps_sample_rows(const MpsSampleRowArgs& a, bool amplitudes, hipStream_t s);
 hipError_t launch_mps_sample_ones(void* v, long long rows, hipStream_t s);   // v[0 .. rows) = 1
 
+// aqc_mps_pauli.hip (Pauli strings between MPS states; rules: aqc_mps_pauli_rule.h)
+struct MpsPauliState {             // one state of a fused launch
+    const double2* const* sites;   // [n] site tensors [2][dims[q]][dims[q+1]]
+    const int* dims;               // [n + 1], every one <= kMpsPauliFusedCap
+    const size_t* env_off;         // [n + 1] element offset of L_q in env_l and of R_q in env_r (expectation mode)
+    const double2* env_l;
+    const double2* env_r;
+};
+struct MpsPauliFusedArgs {
+    int n, nstrings, expectation;
+    const MpsPauliState* kets;     // [pairs]
+    const MpsPauliState* bras;     // [pairs]; expectation mode: unused
+    const unsigned char* strings;  // [nstrings][n]
+    const int* first;              // [nstrings] the support of each string (expectation mode)
+    const int* last;
+    double2* const* out;           // [pairs] -> [nstrings]
+};
+hipError_t launch_mps_pauli_fused(const MpsPauliFusedArgs& a, int npairs, hipStream_t s);   // grid (strings, pairs)
+// the three dressed copies D[c] = conj(ph(c)) B[c ^ f] of every site of a bra: out [3 (X, Y, Z)][total], site q at site_off[q]
+hipError_t launch_mps_pauli_dress(const double2* const* sites, const int* dims, const size_t* site_off, int n, size_t total, int max_site_elems,
+                                  void* out, hipStream_t s);
+// out[idx[k]] = sum_uv M_k[u][v] R_k[v][u] over chi x chi, one workgroup per job k (m_tab, r_tab: `count` device pointers each)
+hipError_t launch_mps_pauli_close(const void* const* m_tab, const void* const* r_tab, const int* idx, int count, int chi, void* out, hipStream_t s);
+
 // aqc_api.cpp: thread-local message behind aqc_last_error(); returns 1
 int set_error(const std::string& msg);
 

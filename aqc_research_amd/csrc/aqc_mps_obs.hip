@@ -31,37 +31,6 @@ namespace aqc {
 
 namespace {
 
-// sum over the workgroup (4 waves) in a fixed order; every thread gets the result.  red: 8 doubles of LDS
-__device__ __forceinline__ cplx block_sum(double re, double im, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { re += __shfl_xor(re, off, 64); im += __shfl_xor(im, off, 64); }
-    __syncthreads();   // (the previous sum's readers are done with red)
-    if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = re; red[2 * (threadIdx.x >> 6) + 1] = im; }
-    __syncthreads();
-    return make_double2((red[0] + red[2]) + (red[4] + red[6]), (red[1] + red[3]) + (red[5] + red[7]));
-}
-
-// sum_uv W[u][v] R[v][u]  (adj: sum_uv conj(W[u][v]) R[u][v]) over the chi x chi corner, this thread's share
-__device__ __forceinline__ void acc_dot(const Acc& w, const cplx* __restrict__ R, int chi, bool adj, double& re, double& im) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
-    re = 0.0; im = 0.0;
-    if (16 * wave >= chi) return;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        if (16 * t >= chi) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int u = 16 * wave + 4 * r + lk, v = 16 * t + li;
-            if (u < chi && v < chi) {
-                const double wr = w.re[t][r], wi = adj ? -w.im[t][r] : w.im[t][r];
-                const cplx b = adj ? R[(size_t)u * chi + v] : R[(size_t)v * chi + u];
-                re += wr * b.x - wi * b.y;
-                im += wr * b.y + wi * b.x;
-            }
-        }
-    }
-}
-
 // the chi x chi corner of acc to memory, row-major (cj: conjugated)
 __device__ __forceinline__ void acc_store_global(const Acc& acc, cplx* __restrict__ out, int chi, bool cj) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;

@@ -215,6 +215,18 @@ class DeviceMPS:
 
         return amplitudes(self, bits, method=method)
 
+    def pauli_strings(self, strings, *, bra=None, method=None) -> np.ndarray:
+        """<self|P_s|self> (with ``bra``: <bra|P_s|self>) of the given Pauli strings: ``mps_observables.pauli_strings`` of this state."""
+        from .mps_observables import pauli_strings
+
+        return pauli_strings(self, strings, bras=bra, method=method)
+
+    def overlaps(self, kets, *, method=None) -> np.ndarray:
+        """<self|psi_b> for a list of states, ``(len(kets),)``: row 0 of ``mps_observables.overlaps``."""
+        from .mps_observables import overlaps
+
+        return overlaps([self], kets, method=method)[0]
+
     def close(self) -> None:
         if self.handle:
             self._L.aqc_mps_destroy(self.handle)

@@ -18,8 +18,12 @@ list equals the one-state call bit for bit.
 
 Device calls: ``pair_density_matrices``, ``reduced_density_matrix`` (and ``plan``, which needs no device).  The rest is NumPy on
 their results.
+
+Operators on more than two sites, and anything between two different states, are Pauli strings (aqc_mps_pauli; kernels:
+csrc/aqc_mps_pauli.hip, rules: csrc/aqc_mps_pauli_rule.h): ``pauli_strings`` gives <phi|P|psi> for many strings and pairs of states in
+one call, ``overlaps`` the matrix <phi_a|psi_b>, ``energy`` a weighted sum of expectation values.
 """
-from ctypes import c_void_p
+from ctypes import POINTER, c_uint8, c_void_p
 from typing import Optional, Sequence
 
 import numpy as np
@@ -198,3 +202,146 @@ def bond_energies(states, delta: float, *, method: Optional[str] = None) -> np.n
     delta = _finite(delta, "delta")
     rho, _ = _rho_of(states, _bond_pairs, method)
     return _bond_energies_of(rho, delta)
+
+
+# ---- Pauli strings: <phi|P|psi> for many strings and pairs of states per call (aqc_mps_pauli; rules: csrc/aqc_mps_pauli_rule.h)
+
+_PAULI_METHODS = {None: 0, "fused": 1, "gemm": 2}   # AQC_MPS_PAULI_*
+_LETTERS = {"I": 0, "X": 1, "Y": 2, "Z": 3}
+
+
+def pauli_route(bra_dims, ket_dims) -> str:
+    """The route the rule picks for a pair with these n + 1 bond dimensions each (``bra_dims`` None: the ket's): ``"fused"`` when every
+    bond of both is at most ``FUSED_CAP``, else ``"gemm"``."""
+    k = np.ascontiguousarray(ket_dims, dtype=np.int32)
+    b = None if bra_dims is None else np.ascontiguousarray(bra_dims, dtype=np.int32)
+    if k.ndim != 1 or k.size < 2 or (b is not None and b.shape != k.shape):
+        raise ValueError("expects the n + 1 bond dimensions of the bra and of the ket")
+    r = _lib.lib().aqc_mps_pauli_route(k.size - 1, None if b is None else iptr(b), iptr(k))
+    if r not in (1, 2):
+        raise ValueError("expects the n + 1 bond dimensions of the bra and of the ket")
+    return "fused" if r == 1 else "gemm"
+
+
+def _shape_of(states):
+    """``(single, count, n)`` of what ``_Lanes`` would take, read on the host: no upload is made for a call that is then refused."""
+    single = isinstance(states, DeviceMPS) or _is_tuple_state(states)
+    if not single and not isinstance(states, list):
+        raise ValueError("states is a DeviceMPS, a QiskitMPS tuple or a list of those")
+    items = [states] if single else states
+    if not items:
+        raise ValueError("expects at least one state")
+    ns = set()
+    for s in items:
+        if isinstance(s, DeviceMPS):
+            if not s.handle:
+                raise ValueError("a closed DeviceMPS")
+            ns.add(s.num_qubits)
+        elif _is_tuple_state(s):
+            ns.add(len(s[0]))
+        else:
+            raise ValueError("a state is a DeviceMPS or a QiskitMPS tuple")
+    if len(ns) != 1:
+        raise ValueError("the states differ in the number of qubits")
+    return single, len(items), ns.pop()
+
+
+def _strings(strings, n: int) -> np.ndarray:
+    """uint8 (S, n) of 0, 1, 2, 3 = I, X, Y, Z from an array, a list of ``str`` of length n or a list of sparse ``(letters, qubits)``."""
+    if isinstance(strings, np.ndarray):
+        arr = strings
+        if arr.ndim != 2 or arr.shape[0] < 1 or arr.shape[1] != n or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"expects a non-empty (S, {n}) array of letters 0, 1, 2, 3")
+        if arr.min() < 0 or arr.max() > 3:
+            raise ValueError("a letter is 0, 1, 2 or 3 (I, X, Y, Z)")
+        return np.ascontiguousarray(arr, dtype=np.uint8)
+    if not isinstance(strings, (list, tuple)) or len(strings) < 1:
+        raise ValueError("expects a non-empty list of Pauli strings")
+    arr = np.zeros((len(strings), n), dtype=np.uint8)
+    for k, s in enumerate(strings):
+        if isinstance(s, str):
+            if len(s) != n:
+                raise ValueError(f"string {k} has {len(s)} letters for {n} qubits")
+            letters, qubits = s, range(n)
+        elif isinstance(s, tuple) and len(s) == 2 and isinstance(s[0], str):
+            letters, qubits = s[0], tuple(s[1])
+            if len(letters) != len(qubits) or len(set(qubits)) != len(qubits):
+                raise ValueError(f"string {k}: one letter per listed qubit, every qubit once")
+        else:
+            raise ValueError(f"string {k} is neither a str over IXYZ nor a (letters, qubits) tuple")
+        for ch, q in zip(letters, qubits):
+            if ch not in _LETTERS:
+                raise ValueError(f"string {k}: {ch!r} is no letter out of IXYZ")
+            if not (isinstance(q, (int, np.integer)) and 0 <= q < n):
+                raise ValueError(f"string {k}: qubit out of range: {n} qubits")
+            arr[k, q] = _LETTERS[ch]
+    return arr
+
+
+def _pauli_call(bras, kets, arr: np.ndarray, method: Optional[str]) -> np.ndarray:
+    """``(len(kets), S)``: <bras[p]| P_s |kets[p]> (``bras`` None: expectation mode) for lists of open DeviceMPS."""
+    if method not in _PAULI_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
+    if method == "fused":
+        for m in {id(m): m for m in kets + (bras or [])}.values():   # (a state may be listed many times: overlaps)
+            if int(m.bond_dims.max()) > FUSED_CAP:
+                raise ValueError(f"the fused route takes bond dimensions up to {FUSED_CAP}, not {int(m.bond_dims.max())}")
+    kh = (c_void_p * len(kets))(*[m.handle for m in kets])
+    bh = None if bras is None else (c_void_p * len(bras))(*[m.handle for m in bras])
+    out = np.empty((len(kets), arr.shape[0]), dtype=np.complex128)
+    check(_lib.lib().aqc_mps_pauli(bh, kh, len(kets), arr.shape[0], arr.ctypes.data_as(POINTER(c_uint8)), _PAULI_METHODS[method], dptr(out)))
+    return out
+
+
+def pauli_strings(states, strings, *, bras=None, method: Optional[str] = None) -> np.ndarray:
+    """<psi| P_s |psi> for every string: ``(S,)`` complex128 for one state, ``(lanes, S)`` for a list; nothing is normalised.  With
+    ``bras`` (a state, or a list as long as ``states``) entry l is <bras[l]| P_s |states[l]>.
+
+    ``strings``: a ``uint8 (S, n)`` array of 0, 1, 2, 3 = I, X, Y, Z, a list of ``str`` over ``IXYZ`` of length n, or a list of sparse
+    ``("XZ", (3, 7))`` tuples (X on qubit 3, Z on qubit 7).  Character q of a ``str`` and column q of the array act on qubit q, which is
+    index bit q of the dense vector: the project's qubit order, NOT the order in which Qiskit prints a Pauli label (which is reversed).
+
+    Without bras a string is walked over its support only, between the environments of the state, so a local term costs its support and
+    not the chain.  ``method``: ``None`` lets the rule choose per pair (``pauli_route``).  A value does not depend on which other
+    strings or states are in the call."""
+    if method not in _PAULI_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
+    single, count, n = _shape_of(states)
+    arr = _strings(strings, n)
+    if bras is not None and _shape_of(bras) != (single, count, n):
+        raise ValueError("bras is one state for one state, or a list as long as states, of the same number of qubits")
+    with _Lanes(states) as kets:
+        if bras is None:
+            out = _pauli_call(None, kets.lanes, arr, method)
+        else:
+            with _Lanes(bras) as b:
+                out = _pauli_call(b.lanes, kets.lanes, arr, method)
+    return out[0] if single else out
+
+
+def overlaps(bras, kets, *, method: Optional[str] = None) -> np.ndarray:
+    """The ``(len(bras), len(kets))`` matrix <phi_a|psi_b> in one call (the identity string between all pairs)."""
+    if method not in _PAULI_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
+    if not isinstance(bras, list) or not isinstance(kets, list):
+        raise ValueError("bras and kets are lists of states")
+    (_, nb, n), (_, nk, n2) = _shape_of(bras), _shape_of(kets)
+    if n != n2:
+        raise ValueError("the states differ in the number of qubits")
+    with _Lanes(bras) as b, _Lanes(kets) as k:
+        pb = [m for m in b.lanes for _ in k.lanes]
+        pk = [m for _ in b.lanes for m in k.lanes]
+        out = _pauli_call(pb, pk, np.zeros((1, n), dtype=np.uint8), method)
+    return out[:, 0].reshape(nb, nk)
+
+
+def energy(states, terms, *, method: Optional[str] = None) -> np.ndarray:
+    """sum_k w_k Re <P_k> for ``terms = [(weight, string), ...]`` (strings as ``pauli_strings`` takes them in a list): ``()`` for one
+    state, ``(lanes,)`` for a list."""
+    if not isinstance(terms, (list, tuple)) or len(terms) < 1 or any(not (isinstance(t, tuple) and len(t) == 2) for t in terms):
+        raise ValueError("terms is a non-empty list of (weight, string)")
+    w = np.array([_finite(t[0], "weight") for t in terms], dtype=np.float64)
+    strings = [t[1] for t in terms]
+    if isinstance(strings[0], np.ndarray):
+        strings = np.stack(strings)
+    return pauli_strings(states, strings, method=method).real @ w

@@ -314,6 +314,27 @@ int aqc_mps_sample(aqc_mps* const* states, int nstates, int64_t shots, uint64_t 
                    double* norm2 /* [nstates], may be null */);
 int aqc_mps_amplitudes(aqc_mps* const* states, int nstates, int64_t count, const uint8_t* bits /* [count][n], shared by the states */,
                        int method, double* amps /* [nstates][count] c128 */);
+/* Pauli strings between MPS states, many strings and pairs of states per call (rules: csrc/aqc_mps_pauli_rule.h, kernels:
+ * csrc/aqc_mps_pauli.hip): out[p][s] = <bras[p]| P_s |kets[p]> with no normalisation.  strings [nstrings][n] of 0, 1, 2, 3 = I, X, Y, Z;
+ * entry q acts on qubit q (= site q = index bit q of the dense vector).  bras NULL is expectation mode, <kets[p]| P_s |kets[p]>: a
+ * string is walked over its support only, between the environments of the ket (one sweep per distinct ket).  States are taken in
+ * whatever gauge they are in and are not modified; a state may be listed many times; they share n >= 1 and the device; the work is
+ * ordered on the first ket's stream after the others' have drained.  A value does not depend on which other strings or pairs are in the
+ * call.
+ * pauli_route: the route the rule picks for a pair with bond dimensions bra_dims, ket_dims [n + 1] (bra_dims NULL: the ket's):
+ *   AQC_MPS_PAULI_FUSED (one workgroup walks a whole string inside one launch) when every bond of both is at most
+ *   AQC_MPS_PAULI_FUSED_CAP, else AQC_MPS_PAULI_GEMM (-1: invalid argument).
+ * pauli_support: host only, needs no device.  first / last [nstrings]: the first and last non-identity site of each string (all
+ *   identity: 0, 0).
+ * pauli: method AQC_MPS_PAULI_BY_RULE (per pair), _FUSED (an error when a bond exceeds the cap) or _GEMM. */
+#define AQC_MPS_PAULI_BY_RULE 0
+#define AQC_MPS_PAULI_FUSED 1
+#define AQC_MPS_PAULI_GEMM 2
+#define AQC_MPS_PAULI_FUSED_CAP 64
+int aqc_mps_pauli_route(int n, const int32_t* bra_dims /* null: the ket's */, const int32_t* ket_dims);
+int aqc_mps_pauli_support(int n, int nstrings, const uint8_t* strings, int32_t* first, int32_t* last);
+int aqc_mps_pauli(aqc_mps* const* bras /* null: expectation mode */, aqc_mps* const* kets, int npairs, int nstrings,
+                  const uint8_t* strings /* [nstrings][n] */, int method, double* out /* [npairs][nstrings] c128 */);
 /* ansatz description for the MPS entry points (ParametricCircuit / TrotterAnsatz, parametric_circuit.py:24-70,267-333);
  * unlike aqc_ctx it is not limited to dense-reachable registers.  blocks: int32[2][num_blocks], row 0 = control */
 typedef struct aqc_circuit {
