@@ -175,7 +175,7 @@ def coord_descent_single_sweep(circ, thetas: np.ndarray, target: np.ndarray, wor
     ws = HipContext.of(circ).workspace(1, target.shape[1])
     ws.upload(BUF_Y, target)
     fobj = np.zeros(1)
-    ws._touch(_lib.BUF_X, _lib.BUF_Z, _lib.BUF_ZW)   # the wide walk rewrites X and Z in place; its V^H leaves a checkpoint in ZW
+    ws._touch(_lib.BUF_X, _lib.BUF_Z, _lib.BUF_W, _lib.BUF_ZW)   # unspecified afterwards (the wide walk rewrites X and Z, its V^H leaves a checkpoint in ZW)
     check(_lib.lib().aqc_ws_cd_sweep(ws.handle, dptr(thetas), dptr(fobj)))
     return float(fobj[0])
 

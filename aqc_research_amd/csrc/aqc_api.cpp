@@ -553,10 +553,11 @@ int aqc_ws_set_basis(aqc_ws* ws, int buf, const int64_t* index) {
 }
 
 int aqc_ws_set_identity(aqc_ws* ws, int buf) {
-    if (check_buf(ws, buf) || before_write(ws, buf)) return 1;
+    if (check_buf(ws, buf)) return 1;
     const int dim = 1 << ws->ctx->prog.n;
-    if (ws->ncols != dim) return fail("identity needs a square workspace (ncols == 2^n)");
+    if (ws->ncols != dim) return fail("identity needs a square workspace (ncols == 2^n)");   // (before the record of `buf` moves: a partial Z stays known as partial)
     HIP_OK(hipSetDevice(ws->device));
+    if (before_write(ws, buf)) return 1;
     HIP_OK(hipMemsetAsync(ws->bufs[buf], 0, sizeof(double2) * (size_t)ws->batch * ws->lane_elems, ws->stream));
     ProfScope ps(ws, AQC_K_MISC);
     HIP_OK(launch_set_identity(ws->bufs[buf], ws->lane_elems, dim, ws->pitch, ws->batch, ws->stream));
@@ -614,13 +615,14 @@ int aqc_ws_gather(aqc_ws* ws, int buf, const int64_t* index, int count, double* 
     if (check_buf(ws, buf)) return 1;
     if (!index || !out || count < 1) return fail("invalid gather arguments");
     HIP_OK(hipSetDevice(ws->device));
-    if (before_read(ws, buf)) return 1;
-    const int64_t dim = (int64_t)1 << ws->ctx->prog.n;
+    // index[i] is a flat element index of the lane's [2^n][ncols] matrix (ncols = 1: the amplitude index)
+    const int64_t dim = (int64_t)1 << ws->ctx->prog.n, ncols = ws->ncols;
     std::vector<long long> elem(count);
     for (int i = 0; i < count; ++i) {
-        if (index[i] < 0 || index[i] >= dim) return fail("gather index out of range");
-        elem[i] = (long long)index[i] << ws->col_bits;
+        if (index[i] < 0 || index[i] >= dim * ncols) return fail("gather index out of range");
+        elem[i] = ((long long)(index[i] / ncols) << ws->col_bits) + (long long)(index[i] % ncols);
     }
+    if (before_read(ws, buf)) return 1;
     HIP_OK(hipStreamSynchronize(ws->stream));   // the temporaries may be re-allocated
     if (ws->d_tmp_index.reserve(count) || ws->d_tmp_small.reserve((size_t)ws->batch * count)) return 1;
     HIP_OK(hipMemcpyAsync(ws->d_tmp_index, elem.data(), sizeof(long long) * count, hipMemcpyHostToDevice, ws->stream));

@@ -283,6 +283,7 @@ struct aqc_ws {
         DevBuf<int> idx;                // alt column indices [sets][batch][k] (grow-only)
         DevBuf<double> adam;            // m | v | best_x [batch][T] each, then best_f | lr [batch]
         DevBuf<int> adam_i;             // t | nit | flag [batch]
+        DevBuf<double> adam_x;          // [batch][T] the run's own last point: what reset = 0 resumes from, whatever thetas other calls put in use
         DevBuf<double> profile;         // [batch][capacity / batch] (grow-only)
         bool adam_started = false;
     } sk;

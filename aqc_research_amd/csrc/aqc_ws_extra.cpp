@@ -368,6 +368,14 @@ static int cd_ensure_prog(aqc_ws* ws) {
     return ws->d_cd_thetas.reserve((size_t)ws->batch * ws->ctx->prog.num_thetas());
 }
 
+// The thetas in use when a coordinate-descent call returns are the point it returns, on either route: one device-to-device copy
+// and one coefficient launch (what the workspace derived from the thetas in use before is stale after it).
+static int cd_use_thetas(aqc_ws* ws, const double* d_point) {
+    const size_t BT = (size_t)ws->batch * ws->ctx->prog.num_thetas();
+    HIP_OK(hipMemcpyAsync(ws->d_thetas_own, d_point, sizeof(double) * BT, hipMemcpyDeviceToDevice, ws->stream));
+    return run_coef(ws, ws->d_thetas_own);
+}
+
 int aqc_ws_cd_fits_one_launch(const aqc_ws* ws) {
     if (!ws) return 0;
     return aqc::cd_persistent_lds_bytes(ws->nbits, ws->ctx->prog.num_thetas()) <= (size_t)160 * 1024 ? 1 : 0;
@@ -392,6 +400,7 @@ int aqc_ws_cd_sweeps(aqc_ws* ws, double* thetas_io, double* fobj, int nsweeps, i
         HIP_OK(aqc::launch_cd_persistent(ws->d_cd_prog, ws->cd_nsteps, ws->nbits, ws->col_bits, ws->bufs[AQC_BUF_Y], ws->lane_elems, ws->d_cd_thetas,
                                          T, ws->d_cd_fobj, nsweeps, max_steps, ws->batch, ws->stream));
     }
+    if (cd_use_thetas(ws, ws->d_cd_thetas)) return 1;   // the point the call returns is the one in use
     HIP_OK(hipMemcpyAsync(thetas_io, ws->d_cd_thetas, sizeof(double) * (size_t)ws->batch * T, hipMemcpyDeviceToHost, ws->stream));
     HIP_OK(hipMemcpyAsync(fobj, ws->d_cd_fobj, sizeof(double) * nf, hipMemcpyDeviceToHost, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
@@ -460,7 +469,8 @@ static int cd_wide_size_check(const aqc_ws* ws) {
 
 // The driver on a workspace and arguments that have passed the checks of its two callers below.
 static int cd_minimize_checked(aqc_ws* ws, const double* thetas0, int maxiter, int chunk, double dtheta_thr, double fobj_thr, double time_limit_s,
-                               bool persistent, int max_steps, double* best_thetas, double* best_f, int64_t* nit, int32_t* status, double* profile) {
+                               bool persistent, int max_steps, double* best_thetas, double* best_f, int64_t* nit, int32_t* status, double* profile,
+                               bool sweep_point = false) {
     const Program& prog = ws->ctx->prog;
     const int B = ws->batch, T = prog.num_thetas();
     const size_t BT = (size_t)B * T;
@@ -508,7 +518,9 @@ static int cd_minimize_checked(aqc_ws* ws, const double* thetas0, int maxiter, i
             break;
         }
     }
-    if (!persistent && run_coef(ws, ws->d_thetas_own)) return 1;   // the last close kernel wrote them: what the workspace derived from the thetas is stale
+    // The wide route's last close kernel left the last sweep's thetas in the workspace's buffer, the persistent launch never touched
+    // it: either way the point the caller gets back goes into use (best_thetas; the sweep's own for aqc_ws_cd_sweep)
+    if (cd_use_thetas(ws, sweep_point ? ws->d_cd_thetas : ws->d_cd_best)) return 1;
     std::vector<int> h_int(2 * (size_t)B);
     HIP_OK(hipMemcpyAsync(best_thetas, ws->d_cd_best, sizeof(double) * BT, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(best_f, ws->d_cd_real, sizeof(double) * B, hipMemcpyDeviceToHost, st));
@@ -549,7 +561,7 @@ int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io, double* fobj) {
     double best_f = 0;
     int64_t nit = 0;
     int32_t status = 0;
-    if (cd_minimize_checked(ws, thetas_io, 1, 1, 0.0, 0.0, 0.0, false, -1, best_thetas.data(), &best_f, &nit, &status, fobj)) return 1;
+    if (cd_minimize_checked(ws, thetas_io, 1, 1, 0.0, 0.0, 0.0, false, -1, best_thetas.data(), &best_f, &nit, &status, fobj, true)) return 1;
     HIP_OK(hipMemcpyAsync(thetas_io, ws->d_cd_thetas, sizeof(double) * T, hipMemcpyDeviceToHost, ws->stream));
     HIP_OK(hipStreamSynchronize(ws->stream));
     return 0;

@@ -228,6 +228,10 @@ int aqc_ws_lbfgs_mat(aqc_ws* ws, const double* x0, int maxiter, int memory, doub
         }
         go_on = (h_flag[0] & kLbAnyActive) != 0;
     }
+    // The theta buffer holds the last trial, which is not x_out on a lane that rejected it or had stopped before: the point the call
+    // returns goes back into use (Z, W and ZW keep what that trial left: unspecified)
+    HIP_OK(hipMemcpyAsync(ws->d_thetas_own, L.x, sizeof(double) * BT, hipMemcpyDeviceToDevice, st_));
+    if (run_coef(ws, ws->d_thetas_own)) return 1;
     std::vector<int> h_status(B, 0);
     HIP_OK(hipMemcpyAsync(x_out, L.x, sizeof(double) * BT, hipMemcpyDeviceToHost, st_));
     HIP_OK(hipMemcpyAsync(f_out, L.f, sizeof(double) * B, hipMemcpyDeviceToHost, st_));

@@ -183,6 +183,10 @@ int aqc_ws_sketch_adam(aqc_ws* ws, int kind, const double* x0, int niter, const 
         HIP_OK(hipMemsetAsync(ws->sk.adam, 0, sizeof(double) * (3 * BT + 2 * (size_t)B), st));
         HIP_OK(hipMemsetAsync(ws->sk.adam_i, 0, sizeof(int) * 3 * B, st));
     }
+    if (!ws->sk.adam_x) {   // (a lane parked before it ever ran sits at the thetas in use now)
+        if (ws->sk.adam_x.alloc(BT)) return 1;
+        HIP_OK(hipMemcpyAsync(ws->sk.adam_x, ws->d_thetas, sizeof(double) * BT, hipMemcpyDeviceToDevice, st));
+    }
     if ((size_t)B * sets > ws->sk.profile.capacity()) {
         HIP_OK(hipStreamSynchronize(st));
         if (ws->sk.profile.reserve((size_t)B * sets)) return 1;
@@ -212,8 +216,9 @@ int aqc_ws_sketch_adam(aqc_ws* ws, int kind, const double* x0, int niter, const 
             HIP_OK(hipMemcpyAsync(s.t + b, &kZero, sizeof(int), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(s.flag + b, &kZero, sizeof(int), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(ws->d_thetas_own + (size_t)b * T, x0 + (size_t)b * T, sizeof(double) * T, hipMemcpyHostToDevice, st));
-        } else if (r == 2) {
-            HIP_OK(hipMemcpyAsync(s.flag + b, &kDone, sizeof(int), hipMemcpyHostToDevice, st));
+        } else {   // the run's own last point, not whatever set_thetas, an evaluation or another driver has put in use since
+            HIP_OK(hipMemcpyAsync(ws->d_thetas_own + (size_t)b * T, ws->sk.adam_x + (size_t)b * T, sizeof(double) * T, hipMemcpyDeviceToDevice, st));
+            if (r == 2) HIP_OK(hipMemcpyAsync(s.flag + b, &kDone, sizeof(int), hipMemcpyHostToDevice, st));
         }
     }
     HIP_OK(hipMemsetAsync(s.nit, 0, sizeof(int) * B, st));
@@ -232,6 +237,7 @@ int aqc_ws_sketch_adam(aqc_ws* ws, int kind, const double* x0, int niter, const 
         ProfScope ps(ws, AQC_K_MISC);
         HIP_OK(launch_sk_adam(s, (int)e, e + 1 < sets ? 1 : 0, st));
     }
+    HIP_OK(hipMemcpyAsync(ws->sk.adam_x, ws->d_thetas_own, sizeof(double) * BT, hipMemcpyDeviceToDevice, st));   // kept with m, v and t
     std::vector<int> h_nit(B), h_status(B);
     HIP_OK(hipMemcpyAsync(x_out, ws->d_thetas_own, sizeof(double) * BT, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpy2DAsync(fobj_profile, sizeof(double) * sets, ws->sk.profile, sizeof(double) * profile_stride, sizeof(double) * sets, B,

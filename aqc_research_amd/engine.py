@@ -211,7 +211,7 @@ class Workspace:
 
     # -- compute -------------------------------------------------------------
     def apply(self, inverse: bool, src: int = BUF_Y, dst: int = BUF_Z) -> None:
-        self._touch(dst)
+        self._touch(dst, *([BUF_ZW] if inverse and dst == BUF_Z else []))   # (V^H into Z leaves its checkpoint in ZW)
         check(self._L.aqc_ws_apply(self.handle, int(bool(inverse)), src, dst))
 
     def grad(self, block_range: Optional[Tuple[int, int]] = None, front_layer: bool = True) -> None:
@@ -223,7 +223,7 @@ class Workspace:
              block_range: Optional[Tuple[int, int]] = None, front_layer: bool = True):
         """One native call, one host synchronisation: [thetas ->] [Z = V^H Y] [gather from Z] [sweep].
         Returns (gathered or None, grads or None)."""
-        self._touch(*(([BUF_Z] if vdag else []) + ([BUF_W, BUF_ZW] if grad else [])))
+        self._touch(*(([BUF_Z, BUF_ZW] if vdag else []) + ([BUF_W, BUF_ZW] if grad else [])))
         th = None if thetas is None else _lib.as_f64(thetas, self.batch * self.T, "thetas")
         hs = np.empty((self.batch, self._gather_count), dtype=np.complex128) if gather else None
         g = np.empty((self.batch, self.T), dtype=np.complex128) if grad else None
@@ -354,7 +354,7 @@ class Workspace:
         """X, Y = U X of every lane into BUF_X / BUF_Y on the device, with the thetas in use (``eigen``).  ``omega``: a host
         draw (batch, d, k) instead of the device's Philox draw; ``alt_idx``: (batch, k) columns for ``alt``.  Returns the QR's
         status word per lane (int32[batch]; 0 = fine), or None with ``status=False`` (nothing is waited for then)."""
-        self._touch(BUF_X, BUF_Y)
+        self._touch(BUF_X, BUF_Y, BUF_W, BUF_ZW)   # X and Y: the result; W and ZW: unspecified afterwards
         keep, idx = self._alt_idx(alt_idx, 1)
         om = None
         if omega is not None:
@@ -403,7 +403,7 @@ class Workspace:
         The host reads one word per ``chunk`` sweeps and checks ``time_limit`` (seconds; <= 0: none) there, so a timeout takes
         effect between chunks, never inside one.  ``route``: "auto", "persistent" (operands in LDS, up to 6 qubits) or "wide".
         Returns thetas (the best ones), cost, nit, status (int32: 1 normal, 2 early, 3 timeout) and profile (batch, maxiter)."""
-        self._touch(BUF_X, BUF_Z)
+        self._touch(BUF_X, BUF_Z, BUF_W, BUF_ZW)   # unspecified afterwards on every route (the wide walk's V^H leaves a checkpoint in ZW)
         th = _lib.as_f64(thetas0, self.batch * self.T, "thetas0")
         maxiter = int(maxiter)
         if maxiter < 1:
@@ -415,6 +415,39 @@ class Workspace:
                                          _lib.CD_ROUTES[route], int(max_steps), dptr(best_x), dptr(best_f),
                                          nit.ctypes.data_as(ctypes.POINTER(c_int64)), st.ctypes.data_as(ctypes.POINTER(c_int32)), dptr(prof)))
         return {"thetas": best_x, "cost": best_f, "nit": nit, "status": st, "profile": prof}
+
+    def cd_sweeps(self, thetas, nsweeps: int = 1, max_steps: int = -1):
+        """``nsweeps`` coordinate-descent sweeps of every lane in one persistent launch (aqc_ws_cd_sweeps; up to 6 qubits), targets
+        in BUF_Y.  Returns (thetas after the last sweep (batch, T) -- the thetas in use afterwards --, fobj (batch, nsweeps))."""
+        th = _lib.as_f64(thetas, self.batch * self.T, "thetas").reshape(self.batch, self.T).copy()
+        fobj = np.zeros((self.batch, int(nsweeps)))
+        self._touch(BUF_X, BUF_Z, BUF_W, BUF_ZW)
+        check(self._L.aqc_ws_cd_sweeps(self.handle, dptr(th), dptr(fobj), int(nsweeps), int(max_steps)))
+        return th, fobj
+
+    def cd_sweep(self, thetas):
+        """One sweep on a one-lane workspace (aqc_ws_cd_sweep: the persistent launch where it fits, else one sweep of the wide walk).
+        Returns (thetas after the sweep (T,) -- the thetas in use afterwards --, the objective there)."""
+        th = _lib.as_f64(thetas, self.T, "thetas").copy()
+        fobj = np.zeros(1)
+        self._touch(BUF_X, BUF_Z, BUF_W, BUF_ZW)
+        check(self._L.aqc_ws_cd_sweep(self.handle, dptr(th), dptr(fobj)))
+        return th, float(fobj[0])
+
+    # -- device-resident L-BFGS on the matrix objective (aqc_ws_lbfgs_mat) ---------
+    def lbfgs_mat(self, x0, *, maxiter: int = 100, memory: int = 10, gtol: float = 1e-7, ftol: float = 1e-12, fobj_thr: float = 0.0,
+                  fidelity_thr: float = 0.0, max_backtracks: int = 12) -> dict:
+        """L-BFGS on f = 1 - Re tr(X^H V^H Y) / ncols of every lane, X and Y as the buffers hold them.  Z, W and ZW are unspecified
+        afterwards; the thetas in use are the returned ``x``.  Returns x, fun, fidelity, nit, nfev (of the batch) and status."""
+        x = _lib.as_f64(x0, self.batch * self.T, "x0")
+        xo = np.empty((self.batch, self.T))
+        f, fid = np.empty(self.batch), np.empty(self.batch)
+        nit, status, nfev = np.zeros(self.batch, dtype=np.int64), np.zeros(self.batch, dtype=np.int32), c_int64()
+        self._touch(BUF_Z, BUF_W, BUF_ZW)
+        check(self._L.aqc_ws_lbfgs_mat(self.handle, dptr(x), int(maxiter), int(memory), float(gtol), float(ftol), float(fobj_thr),
+                                       float(fidelity_thr), int(max_backtracks), dptr(xo), dptr(f), dptr(fid),
+                                       nit.ctypes.data_as(ctypes.POINTER(c_int64)), byref(nfev), status.ctypes.data_as(ctypes.POINTER(c_int32))))
+        return {"x": xo, "fun": f, "fidelity": fid, "nit": nit, "nfev": int(nfev.value), "status": status}
 
     # -- measurement ---------------------------------------------------------
     def timer_start(self) -> None:

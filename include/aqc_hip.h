@@ -123,14 +123,17 @@ int aqc_ws_set_basis(aqc_ws* ws, int buf, const int64_t* index /* [batch] */);
  * flip state, objective_lhs_sur_max.py:147-155,167-175) combined as c_0 g_0 + c_max g_max are ONE sweep from
  * x = conj(c_0) |state_0> + conj(c_max) |state_max>. */
 int aqc_ws_set_combo(aqc_ws* ws, int buf, const int64_t* index /* [batch][2] */, const double* coef /* [batch][2] c128 */);
-/* X <- identity matrix (FullRangeSketchingVectors.generate, sk_core.py:317-326); needs ncols == 2^n */
+/* X <- identity matrix (FullRangeSketchingVectors.generate, sk_core.py:317-326); needs ncols == 2^n (any other workspace is
+ * refused: the buffer and the record of what it holds stay as they were) */
 int aqc_ws_set_identity(aqc_ws* ws, int buf);
 /* dst <- V src (inverse=0) or V^H src (inverse=1), per lane, with the lane's thetas */
 int aqc_ws_apply(aqc_ws* ws, int inverse, int src_buf, int dst_buf);
 /* grads <- complex gradient of <V X|Y> from X and Z = V^H Y (kept intact); W/ZW are scratch */
 int aqc_ws_grad(aqc_ws* ws, int block_from, int block_to, int front_layer);
 int aqc_ws_get_grads(aqc_ws* ws, double* grads /* [batch][T] c128 */);
-/* out[lane][i] = buf[lane][index[i]]  (ThinStateHandler.state_dot_vector, objective_base.py:166-177) */
+/* out[lane][i] = buf[lane][index[i]], index[i] a flat element index of the lane's row-major [2^n][ncols] matrix, 0 <= index[i] <
+ * 2^n ncols (ncols = 1: the amplitude index; ThinStateHandler.state_dot_vector, objective_base.py:166-177).  The registered set of
+ * aqc_ws_gather_setup names rows: amplitudes of a state vector, column 0 of a matrix. */
 int aqc_ws_gather(aqc_ws* ws, int buf, const int64_t* index, int count, double* out);
 /* out[lane] = <a_lane|b_lane> (np.vdot; GenericStateHandler.state_dot_vector, sk_core.py:192) */
 int aqc_ws_vdot(aqc_ws* ws, int buf_a, int buf_b, double* out /* [batch] c128 */);
@@ -430,14 +433,19 @@ double aqc_svd_batch_core_ms(void);
  * the objective at the end of the sweep is returned.  cx / cz entanglers only (:818-827).
  * A single-lane workspace (batch == 1).  Where aqc_ws_cd_fits_one_launch this is aqc_ws_cd_sweeps(ws, thetas_io, fobj, 1, -1);
  * larger problems, and every problem where the switch AQC_CD_CHAIN is on (cross-checks, timing), take one sweep of the
- * wide walk of aqc_ws_cd_minimize. */
+ * wide walk of aqc_ws_cd_minimize.
+ * Side effects, the same on either route: AQC_BUF_X, Z, W and ZW are unspecified afterwards (the wide walk rewrites X and Z in place
+ * and leaves a checkpoint in ZW; the persistent launch touches none of them), Y and X2 are kept, and the thetas in use when it returns
+ * are thetas_io as returned, with the coefficients derived from them valid. */
 int aqc_ws_cd_sweep(aqc_ws* ws, double* thetas_io /* [T] */, double* fobj);
 /* The same walk for EVERY lane of the workspace (lane = an independent problem: a random restart of the ansatz and / or its
  * own target in AQC_BUF_Y) and for `nsweeps` consecutive sweeps, as ONE persistent launch: a workgroup per lane keeps the two
  * d x d operands in LDS, re-derives z = V(theta)^H U at the start of every sweep (:806-810) and walks all parameters (:852-912)
  * without leaving the kernel.  Needs 2 d^2 16 B + 24 T B <= 160 KiB (up to 6 qubits; aqc_ws_cd_fits_one_launch); larger
  * problems are refused here: lanes beyond LDS are served by aqc_ws_cd_minimize.  fobj[lane][s] = the objective at the end of sweep s (:917).
- * max_steps >= 0 stops every sweep's walk after that many parameters (tests pin single steps with it); -1 = all. */
+ * max_steps >= 0 stops every sweep's walk after that many parameters (tests pin single steps with it); -1 = all.
+ * Side effects: AQC_BUF_X, Z, W and ZW are unspecified afterwards (as for aqc_ws_cd_sweep), Y and X2 are kept, and the thetas in use
+ * when it returns are thetas_io as returned, with the coefficients derived from them valid. */
 int aqc_ws_cd_sweeps(aqc_ws* ws, double* thetas_io /* [batch][T] */, double* fobj /* [batch][nsweeps] */, int nsweeps, int max_steps);
 int aqc_ws_cd_fits_one_launch(const aqc_ws* ws);
 /* The whole coordinate-descent driver (aqc_coord_descent.py:70-121, _single_simulation) for every lane, without a host visit per
@@ -451,7 +459,10 @@ int aqc_ws_cd_fits_one_launch(const aqc_ws* ws);
  * route: AQC_CD_ROUTE_AUTO (the persistent launch where aqc_ws_cd_fits_one_launch, else the wide walk), _PERSISTENT (an error where
  * it does not fit), _WIDE: operands in HBM, T + (n + L) walk launches per sweep on a grid of (workgroups per lane, lanes), any
  * number of qubits and lanes.  max_steps as in aqc_ws_cd_sweeps.  Square workspace, targets in AQC_BUF_Y, cx / cz, no Trotter.
- * Outputs: best_thetas[batch][T], best_f[batch], nit[batch], status[batch], profile[batch][maxiter] (entries from nit on are 0). */
+ * Outputs: best_thetas[batch][T], best_f[batch], nit[batch], status[batch], profile[batch][maxiter] (entries from nit on are 0).
+ * Side effects, the same on every route: AQC_BUF_X, Z, W and ZW are unspecified afterwards (the wide route rewrites X and Z and leaves
+ * a checkpoint in ZW, the persistent route touches none of them: a caller may rely on neither), Y and X2 are kept, and the thetas in
+ * use when it returns are best_thetas -- not the last sweep's -- with the coefficients derived from them valid. */
 enum { AQC_CD_RUNNING = 0, AQC_CD_NORMAL = 1, AQC_CD_EARLY = 2, AQC_CD_TIMEOUT = 3 };
 enum { AQC_CD_ROUTE_AUTO = 0, AQC_CD_ROUTE_PERSISTENT = 1, AQC_CD_ROUTE_WIDE = 2 };
 int aqc_ws_cd_minimize(aqc_ws* ws, const double* thetas0 /* [batch][T] */, int maxiter, int chunk, double dtheta_thr, double fobj_thr,
@@ -540,8 +551,10 @@ int aqc_ws_lbfgs(aqc_ws* ws, const double* x0, int maxiter, int memory, double g
  * of SmallObjectiveStopper; 0: off) or at |tr|^2 / ncols^2 >= fidelity_thr (the Hilbert-Schmidt fidelity when X = I; 0: off).
  * memory in [1, 32].  x0 / x_out: [batch][T]; f / fidelity / nit / status: [batch]; *nfev_out: evaluations of the whole batch.
  * status (may be NULL): 0, or 1 for a lane whose value or gradient was not finite -- it stops where it is (at x0 when the start
- * point is the bad one) and the other lanes finish as if it were not there.  Rewrites buffers Z, W and ZW.  Refuses a Trotter
- * ansatz, like every matrix path.  Sums run in a fixed order: a call repeated gives the same bits, and a lane of a batch gives the
+ * point is the bad one) and the other lanes finish as if it were not there.
+ * Side effects: rewrites AQC_BUF_Z, W and ZW, which are unspecified afterwards (they belong to the last line-search trial, accepted
+ * or not); X, Y and X2 are kept; the thetas in use when it returns are x_out -- not that trial -- with the coefficients derived from
+ * them valid.  Refuses a Trotter ansatz, like every matrix path, and changes nothing then.  Sums run in a fixed order: a call repeated gives the same bits, and a lane of a batch gives the
  * bits of the same problem run alone on a workspace with the same plan.  The plan does not depend on the batch below 2^8 elements
  * per lane; above, the tile size may (aqc_ws_plan_info shows it), and the tile-size switches or the tile
  * arguments of aqc_ws_create pin it. */
@@ -570,7 +583,9 @@ int aqc_ws_sketch_target(aqc_ws* ws, const double* U, int shared);
  * AQC_BUF_Y <- U X, with the thetas in use (eigen).  `iteration` numbers the sketch (part of the Philox counter); omega, when not
  * NULL, is a host draw [batch][2^n][k] c128 used instead of the device's; alt_idx [batch][k] are the columns of `alt` (required
  * there).  status (optional, [batch]; synchronises): the QR's word per lane (see aqc_qr) -- a flagged lane keeps its
- * un-orthonormalised matrix in X bit for bit, and the other lanes are complete. */
+ * un-orthonormalised matrix in X bit for bit, and the other lanes are complete.
+ * Side effects: rewrites AQC_BUF_X and Y (the result); Z and X2 are kept, W and ZW are unspecified afterwards; the thetas in use are
+ * read (eigen) and not changed. */
 int aqc_ws_sketch_generate(aqc_ws* ws, int kind, uint64_t seed, int64_t iteration, const int32_t* alt_idx, const double* omega,
                            int32_t* status);
 /* the draw alone: buf <- Omega of every lane for (kind = rand or eigen, seed, iteration), as the generate entry would draw it
@@ -582,8 +597,12 @@ int aqc_ws_sketch_draw(aqc_ws* ws, int kind, uint64_t seed, int64_t iteration, i
  * falls below tol stops moving; its nit counts the steps it took in this call, and fobj_profile[lane][nit] is the cost at its final
  * point, as ADAM's result reports fun(x).  fobj_profile: [batch][niter + 1].  best_f / best_x: the smallest value seen since the
  * lane's last restart and its thetas (sk_core.py:198-200).  lr: [batch].  reset (NULL: restart all on the first call, continue
- * after): per lane 0 = continue with the m / v / t state and thetas left on the device (x0 ignored), 1 = restart from x0[lane],
- * 2 = parked (no further steps).  alt_idx: [niter + 1][batch][k].  status: [batch] QR words, OR over the call. */
+ * after): per lane 0 = continue with the m / v / t state and from the point this lane's run reached in the last aqc_ws_sketch_adam
+ * call -- kept with that state, so whatever put other thetas in use in between (aqc_ws_set_thetas, an evaluation, a theta set,
+ * another driver) does not move it; x0 ignored -- 1 = restart from x0[lane], 2 = parked (no further steps, at that same point).
+ * alt_idx: [niter + 1][batch][k].  status: [batch] QR words, OR over the call.
+ * Side effects: rewrites AQC_BUF_X and Y (the last sketch) and Z, W, ZW, all of which are unspecified afterwards; X2 is kept; the
+ * thetas in use when it returns are x_out, with the coefficients derived from them valid. */
 int aqc_ws_sketch_adam(aqc_ws* ws, int kind, const double* x0, int niter, const double* lr, double beta1, double beta2, double eps,
                        double tol, uint64_t seed, int64_t iter0, const int32_t* reset, const int32_t* alt_idx, double* x_out,
                        double* fobj_profile, double* best_f, double* best_x, int64_t* nit, int32_t* status);

@@ -177,6 +177,32 @@ def test_lane_writer_of_a_stale_partial_z_refuses(monkeypatch, writer):
         src.close()
 
 
+def test_refused_identity_leaves_a_partial_z_known_as_partial(monkeypatch):
+    """aqc_api.cpp aqc_ws_set_identity: a state-vector workspace is no square one, so the call is refused -- after it had announced
+    its write, which marked a Z that objective_launch left partial as complete.  The readers of Z must still complete it."""
+    from aqc_research_amd.engine import Workspace
+
+    circ, ctx, tile, batch, oracle = _shape("cz13_t8")
+    rng = np.random.default_rng(708)
+    _configure(monkeypatch, dict(FORCED, AQC_PROJECTED_VDAG="0"))
+    tg = np.stack([orc.rand_state(circ.num_qubits, rng) for _ in range(batch)])
+    th = np.stack([orc.rand_thetas(circ.num_thetas, rng) for _ in range(batch)])
+    ws = Workspace(ctx, batch=batch, tile_bits_apply=tile, tile_bits_sweep=tile)
+    try:
+        ws.upload(BUF_Y, tg)
+        ws.set_basis(BUF_X, 0)
+        ws.gather_setup([0])
+        ws.set_thetas(th)
+        ws.objective_launch(BUF_X)
+        with pytest.raises(RuntimeError, match="square"):
+            ws.set_identity(BUF_Z)
+        z = ws.download(BUF_Z)
+    finally:
+        ws.close()
+    for b in range(batch):
+        assert wm.maxdiff(z[b], oracle.vdag(th[b], tg[b])) < wm.TOL, b
+
+
 @pytest.mark.parametrize("call", ["objective_launch", "eval", "surrogate_eval"])
 def test_refused_block_range_enqueues_nothing(monkeypatch, call):
     """aqc_ws_sweep.cpp aqc_ws_objective_launch / aqc_ws_eval, aqc_ws_optim.cpp aqc_ws_surrogate_eval: a block_range the ABI

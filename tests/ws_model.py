@@ -727,36 +727,69 @@ def maxdiff(a, b) -> float:
     return float(np.max(np.abs(a - b))) if a.size else 0.0
 
 
-def run_sequence(make_ws, circ, batch, ops, orc=None, tol=TOL):
+class VectorKit:
+    """What the runner needs to know about one kind of workspace: the pair of models, the state the second workspace (the other
+    end of copy_lane) starts from, and the operation catalogue.  This one: state-vector workspaces (tests/ws_model_mat.py has the
+    matrix one)."""
+
+    @staticmethod
+    def models(orc, batch, circ):
+        return Model(orc, batch, circ.num_qubits), Model(orc, batch, circ.num_qubits)
+
+    @staticmethod
+    def prepare_second(ws2, model2, batch, circ):
+        n = circ.num_qubits
+        rng2 = np.random.default_rng(12345)
+        y2 = rng2.standard_normal((batch, 1 << n)) + 1j * rng2.standard_normal((batch, 1 << n))
+        y2 /= np.linalg.norm(y2, axis=1, keepdims=True)
+        th2 = np.pi * (2 * rng2.random((batch, circ.num_thetas)) - 1)
+        ws2.upload(BUF_Y, y2); model2.write(BUF_Y, y2)
+        ws2.set_basis(BUF_X, [3] * batch)
+        x2 = np.zeros((batch, 1 << n), complex); x2[:, 3] = 1; model2.write(BUF_X, x2)
+        ws2.gather_setup([3, 5]); model2.gather = np.array([3, 5])
+        ws2.set_thetas(th2); model2.new_thetas(th2)
+        ws2.objective_launch(BUF_X); model2.evaluation_writes_z(); model2.sweep(BUF_X, None, True)
+
+    apply_op = staticmethod(apply_op)
+
+
+def run_sequence(make_ws, circ, batch, ops, orc=None, tol=TOL, kit=VectorKit, residuals=False):
     """Play `ops` on a workspace from make_ws() (and a second one on the same context for copy_lane), compare every read
-    with the model.  Returns the list of (step, label, got) of every read, for comparisons across configurations."""
+    with the model.  A read is (label, got, expected) or (label, got, expected, its own tolerance) -- the outputs of a long-running
+    call against its reference.  Where the model names the buffers an operation rewrote (`model.rewritten`) and the workspace
+    counts generations, every one of them must have moved.  Returns the list of (step, label, got) of every read, for
+    comparisons across configurations; with `residuals`, (step, label, got - expected) of the reads held to `tol` -- what is left
+    to compare where the expected values themselves depend on the configuration (an optimiser's returned point does, in its last
+    digits times whatever the optimiser amplifies them by)."""
     orc = orc or Oracle(circ)
     ws, ws2 = make_ws(), make_ws()
-    n = circ.num_qubits
-    model, model2 = Model(orc, batch, n), Model(orc, batch, n)
-    rng2 = np.random.default_rng(12345)
-    y2 = rng2.standard_normal((batch, 1 << n)) + 1j * rng2.standard_normal((batch, 1 << n))
-    y2 /= np.linalg.norm(y2, axis=1, keepdims=True)
-    th2 = np.pi * (2 * rng2.random((batch, circ.num_thetas)) - 1)
-    ws2.upload(BUF_Y, y2); model2.write(BUF_Y, y2)
-    ws2.set_basis(BUF_X, [3] * batch)
-    x2 = np.zeros((batch, 1 << n), complex); x2[:, 3] = 1; model2.write(BUF_X, x2)
-    ws2.gather_setup([3, 5]); model2.gather = np.array([3, 5])
-    ws2.set_thetas(th2); model2.new_thetas(th2)
-    ws2.objective_launch(BUF_X); model2.evaluation_writes_z(); model2.sweep(BUF_X, None, True)
+    model, model2 = kit.models(orc, batch, circ)
     out = []
     try:
+        kit.prepare_second(ws2, model2, batch, circ)
         for step, op in enumerate(ops):
+            gens = {b: ws.generation(b) for b in NAMES} if hasattr(ws, "generation") else None
+            if hasattr(model, "rewritten"):
+                model.rewritten = set()
             try:
-                reads = apply_op(ws, model, op, ws2, model2)
+                reads = kit.apply_op(ws, model, op, ws2, model2)
             except AssertionError:
                 raise
             except Exception as e:
                 raise AssertionError(f"step {step} {op[0]}: {type(e).__name__}: {e}\n{describe(ops, step)}") from e
-            for label, got, exp in reads:
+            for label, got, exp, *own in reads:
                 d = maxdiff(got, exp)
-                assert d < tol, f"step {step} {op[0]} -> {label}: differs from the model by {d:.3g}\n{describe(ops, step)}"
-                out.append((step, label, np.array(got)))
+                bound = own[0] if own else tol
+                assert d < bound, (f"step {step} {op[0]} -> {label}: differs from the model by {d:.3g} (bound {bound:g})\n"
+                                   f"{describe(ops, step)}")
+                if not residuals:
+                    out.append((step, label, np.array(got)))
+                elif not own:
+                    out.append((step, label, np.asarray(got) - np.asarray(exp)))
+            if gens is not None:
+                for b in getattr(model, "rewritten", ()):
+                    assert ws.generation(b) != gens[b], (f"step {step} {op[0]}: rewrote {NAMES[b]} and left its generation() at {gens[b]}\n"
+                                                         f"{describe(ops, step)}")
     finally:
         ws.close()
         ws2.close()
