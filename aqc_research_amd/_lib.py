@@ -91,6 +91,9 @@ SIGNATURES = {
     "aqc_mps_pauli_route": (c_int, [c_int, POINTER(c_int32), POINTER(c_int32)]),
     "aqc_mps_pauli_support": (c_int, [c_int, c_int, POINTER(c_uint8), POINTER(c_int32), POINTER(c_int32)]),
     "aqc_mps_pauli": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, POINTER(c_uint8), c_int, _D]),
+    "aqc_mps_ent_route": (c_int, [c_int, POINTER(c_int32)]),
+    "aqc_mps_ent_schmidt": (c_int, [POINTER(_P), c_int, c_int, c_int, _D, POINTER(c_int32), POINTER(c_int32), _D]),
+    "aqc_mps_rank_rule": (c_int, [c_int, _D, c_double, c_int, POINTER(c_int32), _D]),
     "aqc_svd": (c_int, [c_int, c_int, c_int, _D, _D, _D, _D, POINTER(c_int)]),
     "aqc_svd_batch": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), _D, _D, _D, _D, POINTER(c_int32), POINTER(c_int32)]),
     "aqc_svd_batch_core_ms": (c_double, []),

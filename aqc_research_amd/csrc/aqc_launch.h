@@ -436,6 +436,29 @@ hipError_t launch_mps_pauli_dress(const double2* const* sites, const int* dims, 
 // out[idx[k]] = sum_uv M_k[u][v] R_k[v][u] over chi x chi, one workgroup per job k (m_tab, r_tab: `count` device pointers each)
 hipError_t launch_mps_pauli_close(const void* const* m_tab, const void* const* r_tab, const int* idx, int count, int chi, void* out, hipStream_t s);
 
+// aqc_mps_ent.hip (Schmidt spectra of MPS states, fused route; rules: aqc_mps_ent_rule.h)
+struct MpsEntState {               // one distinct state of a call
+    const double2* const* sites;   // [n] site tensors [2][dims[q]][dims[q+1]]
+    const int* dims;               // [n + 1], every one <= kMpsEntFusedCap
+    const size_t* fac_off;         // [n + 1] element offset of the factor of bond q = 1 .. n - 1 in a block, entry n: the size of a block
+    double2* factors;              // the block of C_1 .. C_{n-1}, then the block of D_1 .. D_{n-1}
+};
+struct MpsEntChainArgs {
+    int n;
+    const MpsEntState* states;     // [states]
+};
+hipError_t launch_mps_ent_chain(const MpsEntChainArgs& a, int nstates, hipStream_t s);   // grid (2 walks, states)
+struct MpsEntCutArgs {
+    int n, k, first;               // k: leading dimension of a matrix of the SVD batch; first: the chunk's first entry of state / cut
+    const int* state;              // per matrix of the call: index into states ...
+    const int* cut;                // ... and the cut q = 1 .. n - 1
+    const MpsEntState* states;
+    double2* a;                    // [count][k][k] <- S_q = C_q D_q^T in the leading chi_q x chi_q
+    int* rows;                     // [count] <- chi_q
+    int* cols;
+};
+hipError_t launch_mps_ent_cut(const MpsEntCutArgs& a, int count, hipStream_t s);         // grid (matrices of the chunk)
+
 // aqc_api.cpp: thread-local message behind aqc_last_error(); returns 1
 int set_error(const std::string& msg);
 

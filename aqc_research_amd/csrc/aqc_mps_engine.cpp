@@ -28,6 +28,7 @@
 #include "../../include/aqc_hip.h"
 #include "aqc_devbuf.h"
 #include "aqc_launch.h"
+#include "aqc_mps_ent_rule.h"
 #include "aqc_mps_host.h"
 
 using namespace aqc;
@@ -252,19 +253,13 @@ int gate_adjacent(aqc_mps* m, int q, const double* g16, double trunc_thr, int ma
     std::vector<int> ord(wcols);
     std::iota(ord.begin(), ord.end(), 0);
     std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return sigma[a] > sigma[b]; });
-    const double smax = sigma[ord[0]];
-    if (!(smax > 0.0) || !std::isfinite(smax)) return failf("2-qubit gate produced a zero or non-finite state");
+    std::vector<double> sorted(wcols);
+    for (int j = 0; j < wcols; ++j) sorted[j] = sigma[ord[j]];
     int k = 0;
+    double dropped = 0.0;   // floor, max_bond, tail: the rule of aqc_mps_ent_rule.h
+    if (!mps_rank_rule(wcols, sorted.data(), trunc_thr, max_bond, &k, &dropped)) return failf("2-qubit gate produced a zero or non-finite state");
     double total = 0.0;
-    for (int j = 0; j < wcols; ++j) {
-        total += sigma[ord[j]] * sigma[ord[j]];
-        if (sigma[ord[j]] > 1e-14 * smax) k = j + 1;          // drop numerically zero values (rank deficiency)
-    }
-    if (max_bond > 0) k = std::min(k, max_bond);
-    double dropped = 0.0;
-    if (trunc_thr > 0.0) {                                     // discard the tail while its weight stays below the threshold
-        while (k > 1 && dropped + sigma[ord[k - 1]] * sigma[ord[k - 1]] < trunc_thr) { dropped += sigma[ord[k - 1]] * sigma[ord[k - 1]]; --k; }
-    }
+    for (int j = 0; j < wcols; ++j) total += sorted[j] * sorted[j];
     double kept = 0.0;
     for (int j = 0; j < k; ++j) kept += sigma[ord[j]] * sigma[ord[j]];
     const double rescale = kept > 0.0 ? std::sqrt(total / kept) : 1.0;   // keep the norm of the state

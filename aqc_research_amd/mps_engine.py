@@ -227,6 +227,18 @@ class DeviceMPS:
 
         return overlaps([self], kets, method=method)[0]
 
+    def schmidt_values(self, *, method=None, details: bool = False):
+        """The singular values of every cut, ``(n - 1, K)``: ``mps_observables.schmidt_values`` of this state (which it leaves as it is)."""
+        from .mps_observables import schmidt_values
+
+        return schmidt_values(self, method=method, details=details)
+
+    def entropies(self, alpha: float = 1.0, *, method=None) -> np.ndarray:
+        """The entanglement entropy of every cut, ``(n - 1,)``: ``mps_observables.entanglement_entropies`` of this state."""
+        from .mps_observables import entanglement_entropies
+
+        return entanglement_entropies(self, alpha, method=method)
+
     def close(self) -> None:
         if self.handle:
             self._L.aqc_mps_destroy(self.handle)

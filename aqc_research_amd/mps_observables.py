@@ -22,6 +22,11 @@ their results.
 Operators on more than two sites, and anything between two different states, are Pauli strings (aqc_mps_pauli; kernels:
 csrc/aqc_mps_pauli.hip, rules: csrc/aqc_mps_pauli_rule.h): ``pauli_strings`` gives <phi|P|psi> for many strings and pairs of states in
 one call, ``overlaps`` the matrix <phi_a|psi_b>, ``energy`` a weighted sum of expectation values.
+
+Entanglement across the cuts of the chain (aqc_mps_ent_schmidt; kernels: csrc/aqc_mps_ent.hip, rules: csrc/aqc_mps_ent_rule.h):
+``schmidt_values`` gives the singular values of every cut of one or many states per call, ``entanglement_entropies`` their entropies
+(``entropies_of``: NumPy), ``bond_dims_needed`` the bond dimensions the engine's rank rule would keep at a given ``trunc_thr`` /
+``max_bond``.
 """
 from ctypes import POINTER, c_uint8, c_void_p
 from typing import Optional, Sequence
@@ -345,3 +350,150 @@ def energy(states, terms, *, method: Optional[str] = None) -> np.ndarray:
     if isinstance(strings[0], np.ndarray):
         strings = np.stack(strings)
     return pauli_strings(states, strings, method=method).real @ w
+
+
+# ---- entanglement: the Schmidt spectra of every cut (aqc_mps_ent_schmidt; rules: csrc/aqc_mps_ent_rule.h, kernels: csrc/aqc_mps_ent.hip)
+
+_ENT_METHODS = {None: 0, "fused": 1, "canonical": 2}   # AQC_MPS_ENT_*
+_ENT_ROUTES = {1: "fused", 2: "canonical"}
+_ENT_SWEEP_LIMIT = 1                                    # status of a cut whose SVD did not converge
+
+
+def entanglement_route(bond_dims) -> str:
+    """The route the rule picks for a state with these n + 1 bond dimensions: ``"fused"`` when every bond is at most ``FUSED_CAP``,
+    else ``"canonical"``."""
+    d = np.ascontiguousarray(bond_dims, dtype=np.int32)
+    if d.ndim != 1 or d.size < 2:
+        raise ValueError("expects the n + 1 bond dimensions of a state")
+    r = _lib.lib().aqc_mps_ent_route(d.size - 1, iptr(d))
+    if r not in _ENT_ROUTES:
+        raise ValueError("expects the n + 1 bond dimensions of a state")
+    return _ENT_ROUTES[r]
+
+
+def _ent_method(method):
+    if method not in _ENT_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'canonical', not {method!r}")
+    return _ENT_METHODS[method]
+
+
+def _schmidt_call(lanes, method: Optional[str], factors: bool = False):
+    """``(values (L, max(n - 1, 1), K), sweeps, status, routes, factors or None)`` for a list of open DeviceMPS."""
+    dims = [m.bond_dims for m in lanes]
+    n = lanes[0].num_qubits
+    routes = [method or entanglement_route(d) for d in dims]
+    for d, r in zip(dims, routes):
+        if r == "fused" and int(d.max()) > FUSED_CAP:
+            raise ValueError(f"the fused route takes bond dimensions up to {FUSED_CAP}, not {int(d.max())}")
+        if factors and r != "fused":
+            raise ValueError("the factors are those of the fused route")
+    kmax = max([1] + [int(d[1:n].max()) for d in dims if n > 1])
+    rows = max(n - 1, 1)
+    handles = (c_void_p * len(lanes))(*[m.handle for m in lanes])
+    s = np.zeros((len(lanes), rows, kmax), dtype=np.float64)
+    sweeps, status = np.zeros((len(lanes), rows), dtype=np.int32), np.zeros((len(lanes), rows), dtype=np.int32)
+    fac = np.zeros(max(1, sum(2 * int((d[1:n].astype(np.int64) ** 2).sum()) for d in dims)), dtype=np.complex128) if factors else None
+    check(_lib.lib().aqc_mps_ent_schmidt(handles, len(lanes), _ENT_METHODS[method], kmax, dptr(s), iptr(sweeps), iptr(status),
+                                         None if fac is None else dptr(fac)))
+    hit = np.argwhere(status == _ENT_SWEEP_LIMIT)
+    if hit.size:
+        raise RuntimeError(f"state {int(hit[0, 0])}, cut {int(hit[0, 1]) + 1}: the SVD of the cut reached its sweep limit")
+    return s, sweeps, status, routes, fac
+
+
+def schmidt_values(states, *, method: Optional[str] = None, details: bool = False):
+    """The singular values of every cut q = 1 .. n - 1 (qubits 0 .. q-1 | q .. n-1), descending: float64 ``(n - 1, K)`` for one state,
+    ``(lanes, n - 1, K)`` for a list, K the largest inner bond dimension of the call; a row is zero beyond its bond dimension.  Nothing
+    is normalised: the squares of a row add up to <psi|psi>.  States are taken in whatever gauge they are in and are not modified.
+
+    ``method``: ``None`` lets the rule choose per state (``entanglement_route``): ``"fused"`` takes R factors of the left and right
+    halves by QR chains on the device and the singular values of their product for all cuts of all states in one batch, so values far
+    below the largest are kept to rounding of the largest; ``"canonical"`` (any bond dimension) runs the engine's identity sweeps on a
+    clone and reads the bond vectors, where values below 1e-14 of the largest come back as 0.  A state that is not finite gives NaN
+    rows and raises nothing; a cut whose SVD reaches its sweep limit raises ``RuntimeError``.  A state's values do not depend on which
+    other states are in the call.  ``details``: ``(values, {"sweeps", "status", "route"})``."""
+    _ent_method(method)
+    _shape_of(states)
+    with _Lanes(states) as lanes:
+        n = lanes.lanes[0].num_qubits
+        s, sweeps, status, routes, _ = _schmidt_call(lanes.lanes, method)
+        cut = slice(0, n - 1)
+        s, sweeps, status = s[:, cut], sweeps[:, cut], status[:, cut]
+        if lanes.single:
+            s, sweeps, status, routes = s[0], sweeps[0], status[0], routes[0]
+        return (s, {"sweeps": sweeps, "status": status, "route": routes}) if details else s
+
+
+def schmidt_factors(state):
+    """``(values, C, D)`` of one state on the fused route: lists of the left factors C_q and the right factors D_q of the bonds
+    q = 1 .. n - 1 (chi_q x chi_q, upper triangular): C_q^H C_q is the left environment of bond q, D_q^H D_q the conjugate of the right
+    one, and the values of cut q are the singular values of C_q D_q^T."""
+    single, _, _ = _shape_of(state)
+    if not single:
+        raise ValueError("expects one state")
+    with _Lanes(state) as lanes:
+        m = lanes.lanes[0]
+        n, d = m.num_qubits, m.bond_dims
+        s, _, _, _, fac = _schmidt_call(lanes.lanes, "fused", factors=True)
+        block = int((d[1:n].astype(np.int64) ** 2).sum())
+        out = []
+        for base in (0, block):
+            at, mats = base, []
+            for q in range(1, n):
+                mats.append(fac[at:at + int(d[q]) ** 2].reshape(int(d[q]), int(d[q])).copy())
+                at += int(d[q]) ** 2
+            out.append(mats)
+        return s[0, :n - 1], out[0], out[1]
+
+
+def entropies_of(values, alpha: float = 1.0) -> np.ndarray:
+    """Entanglement entropies of Schmidt values (last axis), natural logarithm, of p = s^2 / sum s^2 with 0 ln 0 = 0: von Neumann at
+    ``alpha`` = 1, Renyi otherwise, ``np.inf`` the min-entropy.  Pure NumPy."""
+    alpha = float(alpha)
+    if not alpha >= 0.0:
+        raise ValueError("alpha must be a non-negative number or np.inf")
+    s = np.asarray(values, dtype=np.float64)
+    w = s * s
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = w / w.sum(axis=-1, keepdims=True)
+        if alpha == 1.0:
+            return -np.where(p > 0.0, p * np.log(np.where(p > 0.0, p, 1.0)), p * 0.0).sum(axis=-1)
+        if np.isinf(alpha):
+            return -np.log(p.max(axis=-1))
+        if alpha == 0.0:   # the logarithm of the rank
+            return np.log(np.where(np.isnan(p).any(axis=-1), np.nan, (p > 0.0).sum(axis=-1)))
+        return np.log((p ** alpha).sum(axis=-1)) / (1.0 - alpha)
+
+
+def entanglement_entropies(states, alpha: float = 1.0, *, method: Optional[str] = None) -> np.ndarray:
+    """``entropies_of(schmidt_values(states, method=method), alpha)``: ``(n - 1,)`` or ``(lanes, n - 1)``."""
+    return entropies_of(schmidt_values(states, method=method), alpha)
+
+
+def rank_rule(values, trunc_thr: float = 0.0, max_bond: int = 0):
+    """``(rank, dropped weight)`` of one descending spectrum by the engine's rank decision (aqc_mps_rank_rule; no device needed): the
+    floor 1e-14 s_max, then ``max_bond`` (> 0), then the tail dropped while its weight stays below ``trunc_thr``."""
+    s = np.ascontiguousarray(values, dtype=np.float64)
+    if s.ndim != 1 or s.size < 1:
+        raise ValueError("expects a flat, non-empty spectrum")
+    rank, dropped = np.zeros(1, np.int32), np.zeros(1, np.float64)
+    check(_lib.lib().aqc_mps_rank_rule(s.size, dptr(s), float(trunc_thr), int(max_bond), iptr(rank), dptr(dropped)))
+    return int(rank[0]), float(dropped[0])
+
+
+def bond_dims_needed(states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None):
+    """``(ranks, dropped)`` per cut: the bond dimension the engine's rank rule keeps of each cut's spectrum at ``trunc_thr`` /
+    ``max_bond`` and the weight it drops: int ``(n - 1,)`` and float64 ``(n - 1,)``, with a leading lanes axis for a list."""
+    trunc_thr = _finite(trunc_thr, "trunc_thr")
+    if trunc_thr < 0.0 or int(max_bond) < 0:
+        raise ValueError("trunc_thr and max_bond must be non-negative")
+    _ent_method(method)
+    single, _, _ = _shape_of(states)
+    with _Lanes(states) as lanes:
+        dims = [m.bond_dims for m in lanes.lanes]
+        s = schmidt_values(lanes.lanes, method=method)
+    ranks, dropped = np.zeros(s.shape[:2], dtype=np.int64), np.zeros(s.shape[:2], dtype=np.float64)
+    for lane in range(s.shape[0]):
+        for cut in range(s.shape[1]):
+            ranks[lane, cut], dropped[lane, cut] = rank_rule(s[lane, cut, :int(dims[lane][cut + 1])], trunc_thr, max_bond)
+    return (ranks[0], dropped[0]) if single else (ranks, dropped)

@@ -338,6 +338,31 @@ int aqc_mps_pauli_route(int n, const int32_t* bra_dims /* null: the ket's */, co
 int aqc_mps_pauli_support(int n, int nstrings, const uint8_t* strings, int32_t* first, int32_t* last);
 int aqc_mps_pauli(aqc_mps* const* bras /* null: expectation mode */, aqc_mps* const* kets, int npairs, int nstrings,
                   const uint8_t* strings /* [nstrings][n] */, int method, double* out /* [npairs][nstrings] c128 */);
+/* Schmidt spectra of MPS states: the singular values of every cut q = 1 .. n - 1 (qubits 0 .. q-1 | q .. n-1) of one or many states per
+ * call (rules: csrc/aqc_mps_ent_rule.h, kernels: csrc/aqc_mps_ent.hip).  States are taken in whatever gauge they are in and are not
+ * modified; nothing is normalised: the squares of a cut's values add up to <psi|psi>.  A state may be listed many times; the states
+ * share n >= 1 and the device; the fused work is ordered on the first state's stream after the others' have drained.  A state's values
+ * do not depend on which other states are in the call.
+ * ent_route: the route the rule picks for bond dimensions dims [n + 1]: AQC_MPS_ENT_FUSED (QR chains of the left and right factors
+ *   inside one launch, then all cuts' SVDs in one batch) when every bond is at most AQC_MPS_ENT_FUSED_CAP, else AQC_MPS_ENT_CANONICAL (the
+ *   engine's identity sweeps on a clone; the bond vectors, zero-padded) (-1: invalid argument).
+ * ent_schmidt: method AQC_MPS_ENT_BY_RULE (per state), _FUSED (an error when a bond exceeds the cap) or _CANONICAL.  kmax: at least the
+ *   largest bond dimension of the states.  s: descending, zero beyond chi_q; the whole row NaN where the state is not finite (status 2).
+ *   status: 0 converged, 1 the SVD of the cut reached its sweep limit (without status that is an error), 2 not finite.  factors: per state
+ *   in call order the block C_1 .. C_{n-1} then the block D_1 .. D_{n-1} (chi_q x chi_q c128 each, back to back), states of the fused
+ *   route only: C_q^H C_q is the left environment of bond q, D_q^H D_q the conjugate of the right one.
+ * rank_rule: host only, needs no device.  The engine's rank decision on a descending spectrum: the floor 1e-14 s[0], then max_bond
+ *   (> 0), then the tail dropped while its weight stays below trunc_thr; dropped: the weight of that tail. */
+#define AQC_MPS_ENT_BY_RULE 0
+#define AQC_MPS_ENT_FUSED 1
+#define AQC_MPS_ENT_CANONICAL 2
+#define AQC_MPS_ENT_FUSED_CAP 64
+int aqc_mps_ent_route(int n, const int32_t* dims);
+int aqc_mps_ent_schmidt(aqc_mps* const* states, int nstates, int method, int kmax,
+                        double* s /* [nstates][max(n-1,1)][kmax], zero beyond chi_q */,
+                        int32_t* sweeps, int32_t* status /* [nstates][max(n-1,1)], may be null */,
+                        double* factors /* may be null: C_q then D_q per state, fused route only */);
+int aqc_mps_rank_rule(int count, const double* s /* descending */, double trunc_thr, int max_bond, int32_t* rank, double* dropped);
 /* ansatz description for the MPS entry points (ParametricCircuit / TrotterAnsatz, parametric_circuit.py:24-70,267-333);
  * unlike aqc_ctx it is not limited to dense-reachable registers.  blocks: int32[2][num_blocks], row 0 = control */
 typedef struct aqc_circuit {
