@@ -94,6 +94,9 @@ SIGNATURES = {
     "aqc_mps_ent_route": (c_int, [c_int, POINTER(c_int32)]),
     "aqc_mps_ent_schmidt": (c_int, [POINTER(_P), c_int, c_int, c_int, _D, POINTER(c_int32), POINTER(c_int32), _D]),
     "aqc_mps_rank_rule": (c_int, [c_int, _D, c_double, c_int, POINTER(c_int32), _D]),
+    "aqc_mps_compress_route": (c_int, [c_int, POINTER(c_int32)]),
+    "aqc_mps_compress_svd_budget": (c_int64, [c_int64]),
+    "aqc_mps_compress": (c_int, [POINTER(_P), c_int, c_double, c_int, c_int, POINTER(_P), POINTER(c_int32), _D, POINTER(c_int32), POINTER(c_int32)]),
     "aqc_svd": (c_int, [c_int, c_int, c_int, _D, _D, _D, _D, POINTER(c_int)]),
     "aqc_svd_batch": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), _D, _D, _D, _D, POINTER(c_int32), POINTER(c_int32)]),
     "aqc_svd_batch_core_ms": (c_double, []),

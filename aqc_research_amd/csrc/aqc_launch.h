@@ -446,8 +446,10 @@ struct MpsEntState {               // one distinct state of a call
 struct MpsEntChainArgs {
     int n;
     const MpsEntState* states;     // [states]
+    int walk0;                     // the walk of block x = 0: 0 left (then x = 1 walks right), 1 right
 };
 hipError_t launch_mps_ent_chain(const MpsEntChainArgs& a, int nstates, hipStream_t s);   // grid (2 walks, states)
+hipError_t launch_mps_ent_chain_right(const MpsEntChainArgs& a, int nstates, hipStream_t s);   // grid (1, states): D_{n-1} .. D_1 only
 struct MpsEntCutArgs {
     int n, k, first;               // k: leading dimension of a matrix of the SVD batch; first: the chunk's first entry of state / cut
     const int* state;              // per matrix of the call: index into states ...
@@ -458,6 +460,36 @@ struct MpsEntCutArgs {
     int* cols;
 };
 hipError_t launch_mps_ent_cut(const MpsEntCutArgs& a, int count, hipStream_t s);         // grid (matrices of the chunk)
+
+// aqc_mps_compress.hip (MPS compression, fused route; rules: aqc_mps_compress_rule.h)
+struct MpsCompressState {          // one distinct state of a call
+    MpsEntState in;                // the input and its right factors (the D block of in.factors)
+    const size_t* site_off;        // [n] element offset of the new site q in out_sites (sized by the input's bonds, packed at the new ranks)
+    const size_t* lam_off;         // [n - 1] offset of the new bond vector q in out_lam
+    double2* out_sites;
+    double* out_lam;
+    int* ranks;                    // [n - 1] <- r_{q+1}, zero from a failed cut on
+    double* dropped;               // [n - 1] <- total - kept of the cut
+    int* sweeps;                   // [n - 1] <- sweeps of the cut's SVD
+    int* status;                   // [1] <- kMpsCompress*: set once, by the state's own workgroup, at the cut that fails
+};
+struct MpsCompressArgs {
+    int n, q, k, first;            // the step; k: columns of a matrix of the SVD batch (2 k rows); first: the chunk's first state
+    const MpsCompressState* states;
+    double2* carry;                // [chunk][kCap * kCap]      W_q, r_q x chi_q packed
+    double2* m;                    // [chunk][2 * kCap * kCap]  M, 2 r_q x chi_{q+1} packed
+    double2* a;                    // [chunk][2 k][k]           B
+    int* rows;                     // [chunk] <- 2 r_q (0: the state has failed, its SVD is skipped)
+    int* cols;                     // [chunk] <- chi_{q+1}
+    const double2* u;              // [chunk][2 k][k]
+    const double* s;               // [chunk][k]
+    const int* svd_sweeps;
+    const int* svd_status;
+    double trunc_thr;
+    int max_bond;
+};
+hipError_t launch_mps_compress_form(const MpsCompressArgs& a, int count, hipStream_t s);    // grid (states of the chunk); q = n - 1: the last site
+hipError_t launch_mps_compress_split(const MpsCompressArgs& a, int count, hipStream_t s);
 
 // aqc_api.cpp: thread-local message behind aqc_last_error(); returns 1
 int set_error(const std::string& msg);

@@ -1,0 +1,312 @@
+// C ABI (include/aqc_hip.h): compression of single-lane MPS states: canonical form and truncation of every bond, many states per call.
+// Rules: aqc_mps_compress_rule.h; kernels: aqc_mps_compress.hip, the right factors by aqc_mps_ent.hip, the SVDs of a step by the
+// device-pointer core of aqc_svd_batch.hip.
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <vector>
+
+#include "aqc_devbuf.h"
+#include "aqc_mps_compress_rule.h"
+#include "aqc_mps_host.h"
+
+using namespace aqc;
+
+namespace {
+
+constexpr size_t kSvdBudget = (size_t)256 << 20;   // bytes the SVD's stores (a, u, vh, work, vmat) of a chunk of states may take
+std::atomic<size_t> g_svd_budget{kSvdBudget};      // aqc_mps_compress_svd_budget: tests lower it to run many chunks on few states
+constexpr int kMaxGridY = 65535;
+constexpr int kPlaneElems = kMpsEntFusedCap * kMpsEntFusedCap;
+
+// one distinct state of the call
+struct StateWork {
+    aqc_mps* h = nullptr;
+    int route = 0, fused_index = -1, status = kMpsCompressOk;
+    std::vector<int> dims, ranks, sweeps;
+    std::vector<double> dropped;
+    std::vector<const double2*> t;
+    std::vector<size_t> fac_off, site_off, lam_off;
+    size_t fac_at = 0, site_at = 0, lam_at = 0;   // element offsets of this state's blocks in the call's stores
+    aqc_mps* made = nullptr;                      // canonical route: the compressed clone, handed to the state's first lane
+};
+
+struct Call {
+    int n = 0, cuts = 0, k = 1;
+    double trunc_thr = 0.0;
+    int max_bond = 0;
+    std::vector<StateWork> states;    // distinct, in order of first appearance
+    std::vector<int> lane_state;      // per lane: index into states
+    DevBuf<unsigned long long> d_tables;   // per fused state: site pointers | factor offsets | site offsets | bond offsets | dims, 8-byte words
+    DevBuf<MpsEntState> d_in;
+    DevBuf<MpsCompressState> d_states;
+    DevBuf<double2> d_factors, d_sites, d_carry, d_m, d_a, d_u, d_vh, d_work, d_vmat;
+    DevBuf<double> d_lam, d_dropped, d_s;
+    DevBuf<int> d_results, d_ints;         // per fused state: ranks | sweeps | status; per state of a chunk: rows | cols | sweeps | status
+    std::vector<int> h_results;
+    std::vector<double> h_dropped;
+};
+
+int run_fused(Call& c, const std::vector<int>& fused, hipStream_t st) {
+    static_assert(sizeof(unsigned long long) == sizeof(size_t) && sizeof(unsigned long long) == sizeof(const double2*), "8-byte words");
+    const size_t n = (size_t)c.n, cuts = (size_t)c.cuts, per = n + (n + 1) + n + n + (n + 2) / 2, res = 2 * cuts + 1;
+    std::vector<unsigned long long> words(per * fused.size(), 0);
+    size_t fac_total = 0, site_total = 0, lam_total = 0;
+    for (size_t i = 0; i < fused.size(); ++i) {
+        StateWork& w = c.states[fused[i]];
+        unsigned long long* p = words.data() + i * per;
+        memcpy(p, w.t.data(), n * 8);
+        memcpy(p + n, w.fac_off.data(), (n + 1) * 8);
+        memcpy(p + 2 * n + 1, w.site_off.data(), n * 8);
+        memcpy(p + 3 * n + 1, w.lam_off.data(), n * 8);
+        memcpy(p + 4 * n + 1, w.dims.data(), (n + 1) * sizeof(int));
+        w.fac_at = fac_total; w.site_at = site_total; w.lam_at = lam_total;
+        fac_total += 2 * w.fac_off[n];
+        site_total += w.site_off[n];
+        for (size_t q = 1; q < n; ++q) lam_total += (size_t)w.dims[q];
+    }
+    const int K = c.k, chunk = mps_compress_chunk(K, fused.size(), g_svd_budget.load());
+    const size_t mat = (size_t)2 * K * K;
+    if (c.d_tables.upload(words) || c.d_factors.alloc(std::max<size_t>(fac_total, 1)) || c.d_sites.alloc(site_total) ||
+        c.d_lam.alloc(std::max<size_t>(lam_total, 1)) || c.d_results.alloc(res * fused.size()) || c.d_dropped.alloc(cuts * fused.size()) ||
+        c.d_carry.alloc((size_t)chunk * kPlaneElems) || c.d_m.alloc((size_t)chunk * 2 * kPlaneElems) || c.d_ints.alloc((size_t)4 * chunk) ||
+        c.d_s.alloc((size_t)chunk * K) || c.d_a.alloc(chunk * mat) || c.d_u.alloc(chunk * mat) || c.d_vh.alloc((size_t)chunk * K * K) ||
+        c.d_work.alloc(svd_batch_work_elems(chunk, 2 * K, K)) || c.d_vmat.alloc(svd_batch_v_elems(chunk, 2 * K, K))) return 1;
+    std::vector<MpsEntState> hin(fused.size());
+    std::vector<MpsCompressState> hs(fused.size());
+    for (size_t i = 0; i < fused.size(); ++i) {
+        const StateWork& w = c.states[fused[i]];
+        const unsigned long long* p = c.d_tables + i * per;
+        hin[i].sites = reinterpret_cast<const double2* const*>(p);
+        hin[i].fac_off = reinterpret_cast<const size_t*>(p + n);
+        hin[i].dims = reinterpret_cast<const int*>(p + 4 * n + 1);
+        hin[i].factors = c.d_factors + w.fac_at;
+        hs[i].in = hin[i];
+        hs[i].site_off = reinterpret_cast<const size_t*>(p + 2 * n + 1);
+        hs[i].lam_off = reinterpret_cast<const size_t*>(p + 3 * n + 1);
+        hs[i].out_sites = c.d_sites + w.site_at;
+        hs[i].out_lam = c.d_lam + w.lam_at;
+        hs[i].ranks = c.d_results + i * res;
+        hs[i].sweeps = hs[i].ranks + cuts;
+        hs[i].status = hs[i].sweeps + cuts;
+        hs[i].dropped = c.d_dropped + i * cuts;
+    }
+    if (c.d_in.upload(hin) || c.d_states.upload(hs)) return 1;
+    HIP_OK(hipMemsetAsync(c.d_results, 0, sizeof(int) * res * fused.size(), st));
+    HIP_OK(hipMemsetAsync(c.d_dropped, 0, sizeof(double) * cuts * fused.size(), st));
+    for (size_t s0 = 0; s0 < fused.size(); s0 += kMaxGridY) {
+        MpsEntChainArgs a{c.n, c.d_in + s0, 1};
+        HIP_OK(launch_mps_ent_chain_right(a, (int)std::min<size_t>(kMaxGridY, fused.size() - s0), st));
+    }
+    int* d_rows = c.d_ints;
+    int* d_cols = d_rows + chunk;
+    int* d_sweeps = d_cols + chunk;
+    int* d_status = d_sweeps + chunk;
+    for (size_t first = 0; first < fused.size(); first += chunk) {   // the chunks share the step's stores: one stream orders them
+        const int count = (int)std::min<size_t>(chunk, fused.size() - first);
+        MpsCompressArgs a{c.n, 0, K, (int)first, c.d_states, c.d_carry, c.d_m, c.d_a, d_rows, d_cols, c.d_u, c.d_s, d_sweeps, d_status, c.trunc_thr, c.max_bond};
+        for (int q = 0; q + 1 < c.n; ++q) {
+            a.q = q;
+            HIP_OK(launch_mps_compress_form(a, count, st));
+            HIP_OK(launch_svd_batch(count, 2 * K, K, d_rows, d_cols, c.d_a, c.d_u, c.d_s, c.d_vh, d_sweeps, d_status, c.d_work, c.d_vmat, st));
+            HIP_OK(launch_mps_compress_split(a, count, st));
+        }
+        a.q = c.n - 1;
+        HIP_OK(launch_mps_compress_form(a, count, st));
+    }
+    c.h_results.resize(res * fused.size());
+    c.h_dropped.resize(std::max<size_t>(cuts * fused.size(), 1));
+    HIP_OK(hipMemcpyAsync(c.h_results.data(), c.d_results, sizeof(int) * res * fused.size(), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(c.h_dropped.data(), c.d_dropped, sizeof(double) * cuts * fused.size(), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// a fused state's lane: a new engine state from the tensors the sweep left on the device
+int adopt_fused(const Call& c, const StateWork& w, int device, aqc_mps** out) {
+    const int n = c.n;
+    std::vector<int> dims(n + 1, 1);
+    double discarded = aqc_mps_discarded_weight(w.h);
+    for (int q = 1; q < n; ++q) { dims[q] = w.ranks[q - 1]; discarded += w.dropped[q - 1]; }
+    std::vector<const void*> sites(n);
+    std::vector<const double*> lams(std::max(n - 1, 1), nullptr);
+    for (int q = 0; q < n; ++q) {
+        sites[q] = c.d_sites + w.site_at + w.site_off[q];
+        if (q < n - 1) lams[q] = c.d_lam + w.lam_at + w.lam_off[q];
+    }
+    return mps_adopt(device, n, dims.data(), sites.data(), lams.data(), discarded, out);
+}
+
+// canonical route: on a clone, the identity sweeps of the engine, then its truncating sweep left to right.  The engine reports an SVD at
+// its sweep limit as an error of the gate, and so does this route: of the statuses it gives only 0 and 2
+int run_canonical(const Call& c, StateWork& w) {
+    const int n = c.n;
+    std::vector<double2> host;
+    bool finite = true, zero = false;
+    for (int q = 0; q < n && finite; ++q) {   // a state that is not finite (or has a zero site) gets the status of the fused route
+        host.resize((size_t)2 * w.dims[q] * w.dims[q + 1]);
+        HIP_OK(hipMemcpy(host.data(), w.t[q], sizeof(double2) * host.size(), hipMemcpyDeviceToHost));
+        bool all_zero = true;
+        for (const double2& x : host) {
+            if (!(std::isfinite(x.x) && std::isfinite(x.y))) { finite = false; break; }
+            if (x.x != 0.0 || x.y != 0.0) all_zero = false;
+        }
+        zero = zero || all_zero;
+    }
+    if (!finite || zero) { w.status = kMpsCompressNonFinite; return 0; }
+    aqc_mps* m = nullptr;
+    if (aqc_mps_clone(w.h, &m)) return 1;
+    static const double eye[32] = {1, 0, 0, 0, 0, 0, 0, 0,  0, 0, 1, 0, 0, 0, 0, 0,  0, 0, 0, 0, 1, 0, 0, 0,  0, 0, 0, 0, 0, 0, 1, 0};
+    int rc = 0;
+    for (int q = n - 2; q >= 0 && !rc; --q) rc = aqc_mps_gate2(m, q, q + 1, eye, 0.0, 0);
+    for (int q = 0; q + 1 < n && !rc; ++q) rc = aqc_mps_gate2(m, q, q + 1, eye, 0.0, 0);
+    for (int q = 0; q + 1 < n && !rc; ++q) {
+        const double before = aqc_mps_discarded_weight(m);
+        rc = aqc_mps_gate2(m, q, q + 1, eye, c.trunc_thr, c.max_bond);
+        w.dropped[q] = aqc_mps_discarded_weight(m) - before;
+    }
+    std::vector<int> dims(n + 1);
+    if (!rc) rc = aqc_mps_dims(m, dims.data());
+    if (rc) { (void)aqc_mps_destroy(m); return 1; }
+    for (int q = 1; q < n; ++q) w.ranks[q - 1] = dims[q];
+    w.made = m;
+    return 0;
+}
+
+void drop_outputs(Call& c, aqc_mps** out, int nstates) {
+    for (int i = 0; i < nstates; ++i) {
+        if (out[i]) (void)aqc_mps_destroy(out[i]);
+        out[i] = nullptr;
+    }
+    for (StateWork& w : c.states) {
+        if (w.made) (void)aqc_mps_destroy(w.made);
+        w.made = nullptr;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int aqc_mps_compress_route(int n, const int32_t* dims) {
+    if (!dims || n < 1) return -1;
+    for (int q = 0; q <= n; ++q)
+        if (dims[q] < 1) return -1;
+    return mps_compress_route(n, dims);
+}
+
+int64_t aqc_mps_compress_svd_budget(int64_t bytes) {
+    const size_t before = g_svd_budget.exchange(bytes > 0 ? (size_t)bytes : kSvdBudget);
+    return (int64_t)before;
+}
+
+int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int max_bond, int method, aqc_mps** out, int32_t* ranks,
+                     double* dropped, int32_t* sweeps, int32_t* status) {
+    if (!states || !out) return failf("null argument");
+    if (nstates < 1) return failf("at least one state is needed");
+    for (int i = 0; i < nstates; ++i) out[i] = nullptr;   // whatever follows, the caller finds null or a state it owns
+    if (!mps_ent_method_ok(method)) return failf("unknown method %d", method);
+    if (!(trunc_thr >= 0.0) || !std::isfinite(trunc_thr)) return failf("trunc_thr must be a non-negative number");
+    if (max_bond < 0) return failf("max_bond must be non-negative");
+    for (int i = 0; i < nstates; ++i)
+        if (!states[i]) return failf("null state");
+    const int n = aqc_mps_num_qubits(states[0]), device = aqc_mps_device(states[0]);
+    if (n < 1) return failf("a state needs at least 1 qubit");
+    for (int i = 0; i < nstates; ++i)
+        if (aqc_mps_num_qubits(states[i]) != n || aqc_mps_device(states[i]) != device) return failf("MPS states differ in size or device");
+    Call c;
+    c.n = n;
+    c.cuts = n - 1;
+    c.trunc_thr = trunc_thr;
+    c.max_bond = max_bond;
+    if ((size_t)nstates * (size_t)std::max(c.cuts, 1) > (size_t)1 << 28) return failf("too many cuts in one call: %d states x %d cuts", nstates, c.cuts);
+    std::map<const aqc_mps*, int> seen;
+    for (int i = 0; i < nstates; ++i) {
+        auto it = seen.find(states[i]);
+        if (it == seen.end()) {
+            it = seen.emplace(states[i], (int)c.states.size()).first;
+            c.states.emplace_back();
+            StateWork& w = c.states.back();
+            w.h = states[i];
+            w.dims.resize(n + 1);
+            if (aqc_mps_dims(states[i], w.dims.data())) return 1;
+            w.route = method == kMpsEntByRule ? mps_compress_route(n, w.dims.data()) : method;
+            const int maxb = mps_ent_max_bond(n, w.dims.data());
+            if (w.route == kMpsEntFused && maxb > kMpsEntFusedCap)
+                return failf("the fused route takes bond dimensions up to %d; state %d has %d", (int)kMpsEntFusedCap, i, maxb);
+            w.fac_off = mps_ent_factor_offsets(n, w.dims.data());
+            w.site_off = mps_compress_site_offsets(n, w.dims.data());
+            w.lam_off = mps_compress_lam_offsets(n, w.dims.data());
+            w.ranks.assign(c.cuts, 0);
+            w.sweeps.assign(c.cuts, 0);
+            w.dropped.assign(c.cuts, 0.0);
+        }
+        c.lane_state.push_back(it->second);
+    }
+    HIP_OK(hipSetDevice(device));
+    if (n == 1) {   // nothing to cut: copies
+        for (int i = 0; i < nstates; ++i) {
+            if (aqc_mps_clone(states[i], &out[i])) { drop_outputs(c, out, nstates); return 1; }
+            if (status) status[i] = kMpsCompressOk;
+        }
+        return 0;
+    }
+    for (StateWork& w : c.states) {   // (mps_peek drains the state's own stream: what aqc_mps_dot_ops does for its second operand)
+        w.t.resize(n);
+        for (int q = 0; q < n; ++q) {
+            const void* site = nullptr;
+            const double* lam = nullptr;
+            if (mps_peek(w.h, q, &site, &lam)) return 1;
+            w.t[q] = static_cast<const double2*>(site);
+        }
+    }
+    std::vector<int> fused;
+    for (size_t k = 0; k < c.states.size(); ++k)
+        if (c.states[k].route == kMpsEntFused) {
+            c.states[k].fused_index = (int)fused.size();
+            fused.push_back((int)k);
+            c.k = std::max(c.k, mps_ent_max_bond(n, c.states[k].dims.data()));
+        }
+    if (!fused.empty()) {
+        hipStream_t st = mps_stream(states[0]);
+        const int rc = run_fused(c, fused, st);
+        const hipError_t e = hipStreamSynchronize(st);   // the one synchronisation of the sweep; before any buffer goes, also after a failure
+        if (rc) return 1;
+        if (e != hipSuccess) return failf("compression failed: %s", hipGetErrorString(e));
+        const size_t cuts = (size_t)c.cuts, res = 2 * cuts + 1;
+        for (size_t i = 0; i < fused.size(); ++i) {
+            StateWork& w = c.states[fused[i]];
+            const int* r = c.h_results.data() + i * res;
+            w.ranks.assign(r, r + cuts);
+            w.sweeps.assign(r + cuts, r + 2 * cuts);
+            w.status = r[2 * cuts];
+            w.dropped.assign(c.h_dropped.begin() + i * cuts, c.h_dropped.begin() + (i + 1) * cuts);
+        }
+    }
+    for (StateWork& w : c.states)
+        if (w.route != kMpsEntFused && run_canonical(c, w)) { drop_outputs(c, out, nstates); return 1; }
+    for (int i = 0; i < nstates; ++i) {
+        StateWork& w = c.states[c.lane_state[i]];
+        if (w.status == kMpsCompressOk) {
+            int rc = 0;
+            if (w.route == kMpsEntFused) rc = adopt_fused(c, w, device, &out[i]);
+            else if (w.made) { out[i] = w.made; w.made = nullptr; }
+            else {   // a later listing of a canonical state: a copy of the lane that took the clone
+                for (int j = 0; j < i && !out[i] && !rc; ++j)
+                    if (c.lane_state[j] == c.lane_state[i]) rc = aqc_mps_clone(out[j], &out[i]);
+            }
+            if (rc || !out[i]) { drop_outputs(c, out, nstates); return rc ? 1 : failf("compression lost a state"); }
+        }
+        for (int q = 0; q < c.cuts; ++q) {
+            const size_t at = (size_t)i * c.cuts + q;
+            if (ranks) ranks[at] = w.ranks[q];
+            if (dropped) dropped[at] = w.dropped[q];
+            if (sweeps) sweeps[at] = w.sweeps[q];
+        }
+        if (status) status[i] = w.status;
+    }
+    return 0;
+}
+
+}  // extern "C"

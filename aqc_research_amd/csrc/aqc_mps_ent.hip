@@ -1,7 +1,7 @@
 // Schmidt spectra of MPS states, fused route (rules and notation: aqc_mps_ent_rule.h; host side: aqc_mps_ent_api.cpp).
 //
 // mps_ent_chain_kernel, grid (2, states): block x = 0 walks the left factors C_1 .. C_{n-1}, block x = 1 the right factors
-// D_{n-1} .. D_1, each its whole chain inside one launch.  The factor (chi x chi, upper triangular) lives in the E planes of
+// D_{n-1} .. D_1 (grid (1, states) with walk0 = 1: the right walk alone, what aqc_mps_compress.hip starts from), each its whole chain inside one launch.  The factor (chi x chi, upper triangular) lives in the E planes of
 // aqc_mps_planes.h.  The step across site q with chi_in bonds on the factor's side and chi_out on the other:
 //     P_0 = F T_q[0], P_1 = F T_q[1]        (MFMA, A operand = the factor from LDS, B operand = the site streamed from memory; the right
 //                                            walk reads the site transposed) into two accumulator sets;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void mps_ent_chain_kernel(MpsEntChainArgs a) {
     double* ei = er + kPlane;
     double* fr = ei + kPlane;
     double* fi = fr + kPlane;
-    const bool right = blockIdx.x == 1;
+    const bool right = blockIdx.x + a.walk0 == 1;
     const MpsEntState st = a.states[blockIdx.y];
     const int n = a.n, tid = threadIdx.x;
     cplx* out_base = st.factors + (right ? st.fac_off[n] : 0);
@@ -219,6 +219,16 @@ hipError_t launch_mps_ent_chain(const MpsEntChainArgs& a, int nstates, hipStream
     if (e != hipSuccess) return e;
     if (nstates <= 0 || a.n < 2) return hipSuccess;
     mps_ent_chain_kernel<<<dim3(2, nstates), 256, kFusedLds, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mps_ent_chain_right(const MpsEntChainArgs& a, int nstates, hipStream_t s) {
+    hipError_t e = ent_attributes();
+    if (e != hipSuccess) return e;
+    if (nstates <= 0 || a.n < 2) return hipSuccess;
+    MpsEntChainArgs r = a;
+    r.walk0 = 1;
+    mps_ent_chain_kernel<<<dim3(1, nstates), 256, kFusedLds, s>>>(r);
     return hipGetLastError();
 }
 

@@ -239,6 +239,18 @@ class DeviceMPS:
 
         return entanglement_entropies(self, alpha, method=method)
 
+    def compressed(self, trunc_thr: float = 0.0, max_bond: int = 0, *, method=None, details: bool = False):
+        """A new state: this one in canonical form with every bond truncated (``compress`` of this state, which it leaves as it is)."""
+        return compress(self, trunc_thr, max_bond, method=method, details=details)
+
+    def compress(self, trunc_thr: float = 0.0, max_bond: int = 0, *, method=None) -> "DeviceMPS":
+        """The same in place: this object takes over the compressed state (copies held elsewhere go stale, ``version`` counts it)."""
+        new = compress(self, trunc_thr, max_bond, method=method)
+        old, self.handle, new.handle = self.handle, new.handle, None
+        self._L.aqc_mps_destroy(old)
+        self.version += 1
+        return self
+
     def close(self) -> None:
         if self.handle:
             self._L.aqc_mps_destroy(self.handle)
@@ -249,6 +261,89 @@ class DeviceMPS:
             self.close()
         except Exception:
             pass
+
+
+# ---- compression: canonical form and truncation of every bond (aqc_mps_compress; rules: csrc/aqc_mps_compress_rule.h, kernels:
+# csrc/aqc_mps_compress.hip)
+
+COMPRESS_FUSED_CAP = 64                                       # AQC_MPS_ENT_FUSED_CAP
+_COMPRESS_METHODS = {None: 0, "fused": 1, "canonical": 2}     # AQC_MPS_ENT_*
+_COMPRESS_ROUTES = {1: "fused", 2: "canonical"}
+_COMPRESS_STATUS = {1: "the SVD of the cut reached its sweep limit", 2: "the state is zero or not finite"}
+
+
+def compress_route(bond_dims) -> str:
+    """The route ``compress`` picks for a state with these n + 1 bond dimensions: ``"fused"`` when every bond is at most
+    ``COMPRESS_FUSED_CAP``, else ``"canonical"``."""
+    d = np.ascontiguousarray(bond_dims, dtype=np.int32)
+    if d.ndim != 1 or d.size < 2:
+        raise ValueError("expects the n + 1 bond dimensions of a state")
+    r = _lib.lib().aqc_mps_compress_route(d.size - 1, iptr(d))
+    if r not in _COMPRESS_ROUTES:
+        raise ValueError("expects the n + 1 bond dimensions of a state")
+    return _COMPRESS_ROUTES[r]
+
+
+def compress(states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
+    """New states: the given ones in the engine's canonical gauge (site tensors Gamma_q lambda_q, the bond vectors the Schmidt values),
+    every bond truncated left to right by the engine's rank rule at ``trunc_thr`` / ``max_bond`` with the rescaling of a truncating
+    gate -- the decisions of ``clone().canonicalize()`` followed by a sweep of truncating identity ``gate2`` calls, in one call for one
+    or many states.  ``states``: a DeviceMPS, a QiskitMPS tuple or a list of those, any gauge, one qubit count; they are not modified.
+    Returns a DeviceMPS for one state, a list for a list; ``discarded_weight`` is the input's plus what the cuts dropped.  At
+    ``trunc_thr`` = 0 (and no binding ``max_bond``) the bond vectors are the state's Schmidt values and the state itself is unchanged;
+    with truncation a bond vector holds the values of its cut when it was decided, as after the loop of gates.
+
+    ``method``: ``None`` lets the rule choose per state (``compress_route``): ``"fused"`` (bonds up to ``COMPRESS_FUSED_CAP``) sweeps all
+    states of the call together on the device, the rank decisions included, with one synchronisation per call; ``"canonical"`` (any
+    bond) runs the engine's sweeps on a clone.  A state's result does not depend on which other states are in the call.
+
+    A state that is zero or not finite, or whose SVD reaches its sweep limit, fails alone: without ``details`` that raises
+    ``RuntimeError`` naming the lane and the cut; with ``details`` its entry is ``None`` and the second return value
+    ``{"ranks", "dropped", "sweeps", "status", "route"}`` tells why (ranks are 0 from the failed cut on)."""
+    from .mps_observables import _Lanes
+
+    if method not in _COMPRESS_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'canonical', not {method!r}")
+    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
+    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
+        raise ValueError("trunc_thr and max_bond must be non-negative")
+    items = [states] if isinstance(states, (DeviceMPS, tuple)) else states
+    if isinstance(items, list):   # refused before anything is uploaded: tuples that differ in size, the fused route beyond its cap
+        shapes = []
+        for s in items:
+            if isinstance(s, DeviceMPS) and s.handle:
+                shapes.append(s.bond_dims)
+            elif isinstance(s, tuple) and len(s) == 2:
+                shapes.append(_pack(s)[1])
+        if len({d.size for d in shapes}) > 1:
+            raise ValueError("the states differ in the number of qubits")
+        if method == "fused" and any(int(d.max()) > COMPRESS_FUSED_CAP for d in shapes):
+            raise ValueError(f"the fused route takes bond dimensions up to {COMPRESS_FUSED_CAP}")
+    with _Lanes(states) as lanes:
+        count, n = len(lanes.lanes), lanes.lanes[0].num_qubits
+        routes = [method or compress_route(m.bond_dims) for m in lanes.lanes]
+        handles = (c_void_p * count)(*[m.handle for m in lanes.lanes])
+        out = (c_void_p * count)()
+        ranks, sweeps = np.zeros((count, n - 1), dtype=np.int32), np.zeros((count, n - 1), dtype=np.int32)
+        dropped, status = np.zeros((count, n - 1), dtype=np.float64), np.zeros(count, dtype=np.int32)
+        check(_lib.lib().aqc_mps_compress(handles, count, trunc_thr, max_bond, _COMPRESS_METHODS[method], out, iptr(ranks), dptr(dropped),
+                                          iptr(sweeps), iptr(status)))
+        made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
+        single = lanes.single
+    bad = np.flatnonzero(status)
+    if bad.size and not details:
+        lane = int(bad[0])
+        cut = int(np.flatnonzero(ranks[lane] == 0)[0]) + 1 if n > 1 else 0
+        for m in made:
+            if m is not None:
+                m.close()
+        raise RuntimeError(f"state {lane}, cut {cut}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
+    if not details:
+        return made[0] if single else made
+    info = {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes}
+    if single:
+        info = {k: v[0] for k, v in info.items()}
+    return (made[0] if single else made), info
 
 
 def svd(a: np.ndarray, device: Optional[int] = None):

@@ -363,6 +363,31 @@ int aqc_mps_ent_schmidt(aqc_mps* const* states, int nstates, int method, int kma
                         int32_t* sweeps, int32_t* status /* [nstates][max(n-1,1)], may be null */,
                         double* factors /* may be null: C_q then D_q per state, fused route only */);
 int aqc_mps_rank_rule(int count, const double* s /* descending */, double trunc_thr, int max_bond, int32_t* rank, double* dropped);
+/* Compression of MPS states: canonical form and truncation of every bond, one or many states per call (rules:
+ * csrc/aqc_mps_compress_rule.h, kernels: csrc/aqc_mps_compress.hip).  The states may be in any gauge, share n >= 1 and the device, and are
+ * left as they are; out[i] is a NEW state (the caller destroys it) in the engine's gauge, its bond vectors the Schmidt values, every
+ * bond cut left to right by the engine's rank rule at trunc_thr / max_bond (aqc_mps_rank_rule) with the rescaling of a truncating gate:
+ * the sequence of decisions of canonicalisation followed by a sweep of truncating identity gates.  Its discarded weight is the
+ * input's plus the weights the cuts dropped.  A state listed many times is compressed once; a state's result does not depend on
+ * which other states are in the call.  n = 1 gives copies.
+ * compress_route: AQC_MPS_ENT_FUSED (every state of the call advances through the sweep together, a workgroup per state, the rank
+ *   decisions on the device, one synchronisation per call) when every bond is at most AQC_MPS_ENT_FUSED_CAP, else AQC_MPS_ENT_CANONICAL
+ *   (the engine's identity sweeps and its truncating sweep on a clone) (-1: invalid argument).
+ * compress: method AQC_MPS_ENT_BY_RULE (per state), _FUSED (an error when a bond exceeds the cap) or _CANONICAL.  ranks: the new bond
+ *   dimension of every cut, 0 from the cut on at which a state failed; dropped: the weight each cut dropped (what the floor and max_bond
+ *   took included); sweeps: of the cut's SVD (fused route; 0 on the canonical one); status per state: 0 compressed, 1 an SVD reached
+ *   its sweep limit (fused route; on the canonical route the engine's gate reports that as an error and the call returns 1), 2 a zero
+ *   or non-finite state -- such a state gets a null handle in out and the call still returns 0.  out is nulled before anything else
+ *   can fail, so after an error it holds nothing to destroy.  ranks,
+ *   dropped, sweeps and status may be null.  Argument errors (a negative or non-finite trunc_thr, a negative max_bond, states that differ
+ *   in size or device, the fused route beyond its cap) are reported before any device work. */
+int aqc_mps_compress_route(int n, const int32_t* dims);
+/* bytes the stores of a step's batched SVD may take (default 256 MiB): the states of a call are swept in chunks that fit.  Sets it
+ * (bytes <= 0: the default) and returns the earlier value; results do not depend on it.  For tests of the chunked sweep. */
+int64_t aqc_mps_compress_svd_budget(int64_t bytes);
+int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int max_bond, int method, aqc_mps** out /* [nstates] */,
+                     int32_t* ranks /* [nstates][n-1] */, double* dropped /* [nstates][n-1] */, int32_t* sweeps /* [nstates][n-1] */,
+                     int32_t* status /* [nstates] */);
 /* ansatz description for the MPS entry points (ParametricCircuit / TrotterAnsatz, parametric_circuit.py:24-70,267-333);
  * unlike aqc_ctx it is not limited to dense-reachable registers.  blocks: int32[2][num_blocks], row 0 = control */
 typedef struct aqc_circuit {
