@@ -1,33 +1,28 @@
 // C ABI (include/aqc_hip.h): compression of single-lane MPS states: canonical form and truncation of every bond, many states per call.
 // Rules: aqc_mps_compress_rule.h; kernels: aqc_mps_compress.hip, the right factors by aqc_mps_ent.hip, the SVDs of a step by the
-// device-pointer core of aqc_svd_batch.hip.
+// device-pointer core of aqc_svd_batch.hip.  The skeleton of the call: aqc_mps_call.h.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstring>
-#include <map>
 #include <vector>
 
-#include "aqc_devbuf.h"
+#include "aqc_mps_call.h"
 #include "aqc_mps_compress_rule.h"
-#include "aqc_mps_host.h"
 
 using namespace aqc;
 
 namespace {
 
-constexpr size_t kSvdBudget = (size_t)256 << 20;   // bytes the SVD's stores (a, u, vh, work, vmat) of a chunk of states may take
-std::atomic<size_t> g_svd_budget{kSvdBudget};      // aqc_mps_compress_svd_budget: tests lower it to run many chunks on few states
-constexpr int kMaxGridY = 65535;
+static_assert(kMpsEntByRule == kMpsByRule && kMpsEntFused == kMpsFused, "resolve_route");
+std::atomic<size_t> g_svd_budget{kMpsCallBudget};   // aqc_mps_compress_svd_budget: tests lower it to run many chunks on few states
 constexpr int kPlaneElems = kMpsEntFusedCap * kMpsEntFusedCap;
+enum { kSites, kFacOff, kSiteOff, kLamOff, kDims };   // the sections of a fused state's record in Call::table
 
-// one distinct state of the call
+// what the call adds to the view of one distinct state
 struct StateWork {
-    aqc_mps* h = nullptr;
-    int route = 0, fused_index = -1, status = kMpsCompressOk;
-    std::vector<int> dims, ranks, sweeps;
+    int route = 0, status = kMpsCompressOk;
+    std::vector<int> ranks, sweeps;
     std::vector<double> dropped;
-    std::vector<const double2*> t;
     std::vector<size_t> fac_off, site_off, lam_off;
     size_t fac_at = 0, site_at = 0, lam_at = 0;   // element offsets of this state's blocks in the call's stores
     aqc_mps* made = nullptr;                      // canonical route: the compressed clone, handed to the state's first lane
@@ -37,9 +32,10 @@ struct Call {
     int n = 0, cuts = 0, k = 1;
     double trunc_thr = 0.0;
     int max_bond = 0;
-    std::vector<StateWork> states;    // distinct, in order of first appearance
-    std::vector<int> lane_state;      // per lane: index into states
-    DevBuf<unsigned long long> d_tables;   // per fused state: site pointers | factor offsets | site offsets | bond offsets | dims, 8-byte words
+    std::vector<MpsView> views;       // distinct, in order of first appearance
+    std::vector<StateWork> states;    // one per view
+    std::vector<int> lane_state;      // per lane: index into views / states
+    MpsTable table;                        // per fused state: site pointers | factor offsets | site offsets | bond offsets | dims
     DevBuf<MpsEntState> d_in;
     DevBuf<MpsCompressState> d_states;
     DevBuf<double2> d_factors, d_sites, d_carry, d_m, d_a, d_u, d_vh, d_work, d_vmat;
@@ -50,26 +46,25 @@ struct Call {
 };
 
 int run_fused(Call& c, const std::vector<int>& fused, hipStream_t st) {
-    static_assert(sizeof(unsigned long long) == sizeof(size_t) && sizeof(unsigned long long) == sizeof(const double2*), "8-byte words");
-    const size_t n = (size_t)c.n, cuts = (size_t)c.cuts, per = n + (n + 1) + n + n + (n + 2) / 2, res = 2 * cuts + 1;
-    std::vector<unsigned long long> words(per * fused.size(), 0);
+    const size_t n = (size_t)c.n, cuts = (size_t)c.cuts, res = 2 * cuts + 1;
+    c.table = MpsTable({mps_table_words(n), mps_table_words(n + 1), mps_table_words(n), mps_table_words(n), mps_table_ints(n + 1)}, fused.size());
     size_t fac_total = 0, site_total = 0, lam_total = 0;
     for (size_t i = 0; i < fused.size(); ++i) {
         StateWork& w = c.states[fused[i]];
-        unsigned long long* p = words.data() + i * per;
-        memcpy(p, w.t.data(), n * 8);
-        memcpy(p + n, w.fac_off.data(), (n + 1) * 8);
-        memcpy(p + 2 * n + 1, w.site_off.data(), n * 8);
-        memcpy(p + 3 * n + 1, w.lam_off.data(), n * 8);
-        memcpy(p + 4 * n + 1, w.dims.data(), (n + 1) * sizeof(int));
+        const MpsView& v = c.views[fused[i]];
+        c.table.put(i, kSites, v.t, n);
+        c.table.put(i, kFacOff, w.fac_off, n + 1);
+        c.table.put(i, kSiteOff, w.site_off, n);
+        c.table.put(i, kLamOff, w.lam_off, w.lam_off.size());
+        c.table.put(i, kDims, v.dims, n + 1);
         w.fac_at = fac_total; w.site_at = site_total; w.lam_at = lam_total;
         fac_total += 2 * w.fac_off[n];
         site_total += w.site_off[n];
-        for (size_t q = 1; q < n; ++q) lam_total += (size_t)w.dims[q];
+        for (size_t q = 1; q < n; ++q) lam_total += (size_t)v.dims[q];
     }
     const int K = c.k, chunk = mps_compress_chunk(K, fused.size(), g_svd_budget.load());
     const size_t mat = (size_t)2 * K * K;
-    if (c.d_tables.upload(words) || c.d_factors.alloc(std::max<size_t>(fac_total, 1)) || c.d_sites.alloc(site_total) ||
+    if (c.table.upload() || c.d_factors.alloc(std::max<size_t>(fac_total, 1)) || c.d_sites.alloc(site_total) ||
         c.d_lam.alloc(std::max<size_t>(lam_total, 1)) || c.d_results.alloc(res * fused.size()) || c.d_dropped.alloc(cuts * fused.size()) ||
         c.d_carry.alloc((size_t)chunk * kPlaneElems) || c.d_m.alloc((size_t)chunk * 2 * kPlaneElems) || c.d_ints.alloc((size_t)4 * chunk) ||
         c.d_s.alloc((size_t)chunk * K) || c.d_a.alloc(chunk * mat) || c.d_u.alloc(chunk * mat) || c.d_vh.alloc((size_t)chunk * K * K) ||
@@ -78,14 +73,13 @@ int run_fused(Call& c, const std::vector<int>& fused, hipStream_t st) {
     std::vector<MpsCompressState> hs(fused.size());
     for (size_t i = 0; i < fused.size(); ++i) {
         const StateWork& w = c.states[fused[i]];
-        const unsigned long long* p = c.d_tables + i * per;
-        hin[i].sites = reinterpret_cast<const double2* const*>(p);
-        hin[i].fac_off = reinterpret_cast<const size_t*>(p + n);
-        hin[i].dims = reinterpret_cast<const int*>(p + 4 * n + 1);
+        hin[i].sites = c.table.at<const double2*>(i, kSites);
+        hin[i].fac_off = c.table.at<size_t>(i, kFacOff);
+        hin[i].dims = c.table.at<int>(i, kDims);
         hin[i].factors = c.d_factors + w.fac_at;
         hs[i].in = hin[i];
-        hs[i].site_off = reinterpret_cast<const size_t*>(p + 2 * n + 1);
-        hs[i].lam_off = reinterpret_cast<const size_t*>(p + 3 * n + 1);
+        hs[i].site_off = c.table.at<size_t>(i, kSiteOff);
+        hs[i].lam_off = c.table.at<size_t>(i, kLamOff);
         hs[i].out_sites = c.d_sites + w.site_at;
         hs[i].out_lam = c.d_lam + w.lam_at;
         hs[i].ranks = c.d_results + i * res;
@@ -124,10 +118,10 @@ int run_fused(Call& c, const std::vector<int>& fused, hipStream_t st) {
 }
 
 // a fused state's lane: a new engine state from the tensors the sweep left on the device
-int adopt_fused(const Call& c, const StateWork& w, int device, aqc_mps** out) {
+int adopt_fused(const Call& c, const MpsView& v, const StateWork& w, int device, aqc_mps** out) {
     const int n = c.n;
     std::vector<int> dims(n + 1, 1);
-    double discarded = aqc_mps_discarded_weight(w.h);
+    double discarded = aqc_mps_discarded_weight(v.h);
     for (int q = 1; q < n; ++q) { dims[q] = w.ranks[q - 1]; discarded += w.dropped[q - 1]; }
     std::vector<const void*> sites(n);
     std::vector<const double*> lams(std::max(n - 1, 1), nullptr);
@@ -139,31 +133,18 @@ int adopt_fused(const Call& c, const StateWork& w, int device, aqc_mps** out) {
 }
 
 // canonical route: on a clone, the identity sweeps of the engine, then its truncating sweep left to right.  The engine reports an SVD at
-// its sweep limit as an error of the gate, and so does this route: of the statuses it gives only 0 and 2
-int run_canonical(const Call& c, StateWork& w) {
+// its sweep limit as an error of the gate, and so does this route: of the statuses it gives only 0 and 2.  A state that is not finite
+// (or has a zero site) gets the status of the fused route
+int run_canonical(const Call& c, const MpsView& v, StateWork& w) {
     const int n = c.n;
-    std::vector<double2> host;
     bool finite = true, zero = false;
-    for (int q = 0; q < n && finite; ++q) {   // a state that is not finite (or has a zero site) gets the status of the fused route
-        host.resize((size_t)2 * w.dims[q] * w.dims[q + 1]);
-        HIP_OK(hipMemcpy(host.data(), w.t[q], sizeof(double2) * host.size(), hipMemcpyDeviceToHost));
-        bool all_zero = true;
-        for (const double2& x : host) {
-            if (!(std::isfinite(x.x) && std::isfinite(x.y))) { finite = false; break; }
-            if (x.x != 0.0 || x.y != 0.0) all_zero = false;
-        }
-        zero = zero || all_zero;
-    }
-    if (!finite || zero) { w.status = kMpsCompressNonFinite; return 0; }
     aqc_mps* m = nullptr;
-    if (aqc_mps_clone(w.h, &m)) return 1;
-    static const double eye[32] = {1, 0, 0, 0, 0, 0, 0, 0,  0, 0, 1, 0, 0, 0, 0, 0,  0, 0, 0, 0, 1, 0, 0, 0,  0, 0, 0, 0, 0, 0, 1, 0};
+    if (canonical_clone(v, true, &finite, &zero, &m)) return 1;
+    if (!m) { w.status = kMpsCompressNonFinite; return 0; }
     int rc = 0;
-    for (int q = n - 2; q >= 0 && !rc; --q) rc = aqc_mps_gate2(m, q, q + 1, eye, 0.0, 0);
-    for (int q = 0; q + 1 < n && !rc; ++q) rc = aqc_mps_gate2(m, q, q + 1, eye, 0.0, 0);
     for (int q = 0; q + 1 < n && !rc; ++q) {
         const double before = aqc_mps_discarded_weight(m);
-        rc = aqc_mps_gate2(m, q, q + 1, eye, c.trunc_thr, c.max_bond);
+        rc = aqc_mps_gate2(m, q, q + 1, kIdentityGate2, c.trunc_thr, c.max_bond);
         w.dropped[q] = aqc_mps_discarded_weight(m) - before;
     }
     std::vector<int> dims(n + 1);
@@ -197,7 +178,7 @@ int aqc_mps_compress_route(int n, const int32_t* dims) {
 }
 
 int64_t aqc_mps_compress_svd_budget(int64_t bytes) {
-    const size_t before = g_svd_budget.exchange(bytes > 0 ? (size_t)bytes : kSvdBudget);
+    const size_t before = g_svd_budget.exchange(bytes > 0 ? (size_t)bytes : kMpsCallBudget);
     return (int64_t)before;
 }
 
@@ -209,41 +190,14 @@ int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int 
     if (!mps_ent_method_ok(method)) return failf("unknown method %d", method);
     if (!(trunc_thr >= 0.0) || !std::isfinite(trunc_thr)) return failf("trunc_thr must be a non-negative number");
     if (max_bond < 0) return failf("max_bond must be non-negative");
-    for (int i = 0; i < nstates; ++i)
-        if (!states[i]) return failf("null state");
-    const int n = aqc_mps_num_qubits(states[0]), device = aqc_mps_device(states[0]);
-    if (n < 1) return failf("a state needs at least 1 qubit");
-    for (int i = 0; i < nstates; ++i)
-        if (aqc_mps_num_qubits(states[i]) != n || aqc_mps_device(states[i]) != device) return failf("MPS states differ in size or device");
+    int n = 0, device = 0;
+    if (check_states(states, nullptr, nstates, 1, &n, &device)) return 1;
     Call c;
     c.n = n;
     c.cuts = n - 1;
     c.trunc_thr = trunc_thr;
     c.max_bond = max_bond;
     if ((size_t)nstates * (size_t)std::max(c.cuts, 1) > (size_t)1 << 28) return failf("too many cuts in one call: %d states x %d cuts", nstates, c.cuts);
-    std::map<const aqc_mps*, int> seen;
-    for (int i = 0; i < nstates; ++i) {
-        auto it = seen.find(states[i]);
-        if (it == seen.end()) {
-            it = seen.emplace(states[i], (int)c.states.size()).first;
-            c.states.emplace_back();
-            StateWork& w = c.states.back();
-            w.h = states[i];
-            w.dims.resize(n + 1);
-            if (aqc_mps_dims(states[i], w.dims.data())) return 1;
-            w.route = method == kMpsEntByRule ? mps_compress_route(n, w.dims.data()) : method;
-            const int maxb = mps_ent_max_bond(n, w.dims.data());
-            if (w.route == kMpsEntFused && maxb > kMpsEntFusedCap)
-                return failf("the fused route takes bond dimensions up to %d; state %d has %d", (int)kMpsEntFusedCap, i, maxb);
-            w.fac_off = mps_ent_factor_offsets(n, w.dims.data());
-            w.site_off = mps_compress_site_offsets(n, w.dims.data());
-            w.lam_off = mps_compress_lam_offsets(n, w.dims.data());
-            w.ranks.assign(c.cuts, 0);
-            w.sweeps.assign(c.cuts, 0);
-            w.dropped.assign(c.cuts, 0.0);
-        }
-        c.lane_state.push_back(it->second);
-    }
     HIP_OK(hipSetDevice(device));
     if (n == 1) {   // nothing to cut: copies
         for (int i = 0; i < nstates; ++i) {
@@ -252,28 +206,29 @@ int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int 
         }
         return 0;
     }
-    for (StateWork& w : c.states) {   // (mps_peek drains the state's own stream: what aqc_mps_dot_ops does for its second operand)
-        w.t.resize(n);
-        for (int q = 0; q < n; ++q) {
-            const void* site = nullptr;
-            const double* lam = nullptr;
-            if (mps_peek(w.h, q, &site, &lam)) return 1;
-            w.t[q] = static_cast<const double2*>(site);
+    if (view_states(states, (size_t)nstates, n, c.views, c.lane_state)) return 1;
+    c.states.resize(c.views.size());
+    std::vector<int> fused;
+    for (int i = 0; i < nstates; ++i) {
+        const int k = c.lane_state[i];
+        StateWork& w = c.states[k];
+        if (w.route) continue;   // (not the state's first lane)
+        const MpsView& v = c.views[k];
+        if ((w.route = resolve_route(method, mps_compress_route(n, v.dims.data()), v.max_bond, kMpsEntFusedCap, "state", i)) < 0) return 1;
+        w.fac_off = mps_ent_factor_offsets(n, v.dims.data());
+        w.site_off = mps_site_offsets(n, v.dims.data());
+        w.lam_off = mps_compress_lam_offsets(n, v.dims.data());
+        w.ranks.assign(c.cuts, 0);
+        w.sweeps.assign(c.cuts, 0);
+        w.dropped.assign(c.cuts, 0.0);
+        if (w.route == kMpsEntFused) {
+            fused.push_back(k);
+            c.k = std::max(c.k, v.max_bond);
         }
     }
-    std::vector<int> fused;
-    for (size_t k = 0; k < c.states.size(); ++k)
-        if (c.states[k].route == kMpsEntFused) {
-            c.states[k].fused_index = (int)fused.size();
-            fused.push_back((int)k);
-            c.k = std::max(c.k, mps_ent_max_bond(n, c.states[k].dims.data()));
-        }
     if (!fused.empty()) {
         hipStream_t st = mps_stream(states[0]);
-        const int rc = run_fused(c, fused, st);
-        const hipError_t e = hipStreamSynchronize(st);   // the one synchronisation of the sweep; before any buffer goes, also after a failure
-        if (rc) return 1;
-        if (e != hipSuccess) return failf("compression failed: %s", hipGetErrorString(e));
+        if (finish_call(st, run_fused(c, fused, st), "compression")) return 1;   // the one synchronisation of the sweep
         const size_t cuts = (size_t)c.cuts, res = 2 * cuts + 1;
         for (size_t i = 0; i < fused.size(); ++i) {
             StateWork& w = c.states[fused[i]];
@@ -284,13 +239,13 @@ int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int 
             w.dropped.assign(c.h_dropped.begin() + i * cuts, c.h_dropped.begin() + (i + 1) * cuts);
         }
     }
-    for (StateWork& w : c.states)
-        if (w.route != kMpsEntFused && run_canonical(c, w)) { drop_outputs(c, out, nstates); return 1; }
+    for (size_t k = 0; k < c.states.size(); ++k)
+        if (c.states[k].route != kMpsEntFused && run_canonical(c, c.views[k], c.states[k])) { drop_outputs(c, out, nstates); return 1; }
     for (int i = 0; i < nstates; ++i) {
         StateWork& w = c.states[c.lane_state[i]];
         if (w.status == kMpsCompressOk) {
             int rc = 0;
-            if (w.route == kMpsEntFused) rc = adopt_fused(c, w, device, &out[i]);
+            if (w.route == kMpsEntFused) rc = adopt_fused(c, c.views[c.lane_state[i]], w, device, &out[i]);
             else if (w.made) { out[i] = w.made; w.made = nullptr; }
             else {   // a later listing of a canonical state: a copy of the lane that took the clone
                 for (int j = 0; j < i && !out[i] && !rc; ++j)

@@ -32,21 +32,10 @@ inline int mps_compress_route(int n, const int* dims) { return mps_ent_route(n, 
 
 // states per chunk of the sweep: the five stores of the batched SVD of 2k x k matrices (a, u, work: 2 k^2; vh, vmat: k^2 complex
 // numbers each) stay within budget_bytes; at least one
-inline int mps_compress_chunk(int k, size_t total, size_t budget_bytes) {
-    const size_t per = (size_t)8 * 16 * (size_t)k * (size_t)k;
-    size_t g = per ? budget_bytes / per : total;
-    if (g > total) g = total;
-    if (g > (size_t)1 << 16) g = (size_t)1 << 16;
-    return (int)(g < 1 ? 1 : g);
-}
+inline int mps_compress_chunk(int k, size_t total, size_t budget_bytes) { return mps_svd_chunk(2 * k, k, total, budget_bytes, (size_t)1 << 16); }
 
-// element offsets of the new site tensors (n + 1 entries) and bond vectors (n entries) of one state, sized by the input's bond
-// dimensions (a rank never exceeds the bond it replaces); the last entry is the total
-inline std::vector<size_t> mps_compress_site_offsets(int n, const int* dims) {
-    std::vector<size_t> off(n + 1, 0);
-    for (int q = 0; q < n; ++q) off[q + 1] = off[q] + (size_t)2 * dims[q] * dims[q + 1];
-    return off;
-}
+// element offsets of the new site tensors (mps_site_offsets of aqc_mps_states_rule.h, n + 1 entries) and bond vectors (n entries) of one
+// state, sized by the input's bond dimensions (a rank never exceeds the bond it replaces); the last entry is the total
 inline std::vector<size_t> mps_compress_lam_offsets(int n, const int* dims) {
     std::vector<size_t> off(n > 0 ? n : 1, 0);
     for (int q = 0; q + 1 < n; ++q) off[q + 1] = off[q] + (size_t)dims[q + 1];

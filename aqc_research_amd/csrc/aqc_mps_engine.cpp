@@ -402,6 +402,14 @@ int aqc::mps_peek(const aqc_mps* m, int q, const void** site, const double** lam
     return 0;
 }
 
+int aqc::mps_view(const aqc_mps* m, int* dims, const double2** sites) {
+    if (!m || !dims || !sites) return failf("mps_view: invalid argument");
+    HIP_OK(hipStreamSynchronize(m->stream));
+    for (int q = 0; q <= m->n; ++q) dims[q] = m->dims[q];
+    for (int q = 0; q < m->n; ++q) sites[q] = m->t[q];
+    return 0;
+}
+
 hipStream_t aqc::mps_stream(const aqc_mps* m) { return m->stream; }
 
 int aqc::mps_adopt(int device, int n, const int* dims, const void* const* sites, const double* const* lams, double discarded, aqc_mps** out) {

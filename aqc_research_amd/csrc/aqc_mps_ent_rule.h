@@ -24,6 +24,8 @@
 #include <complex>
 #include <vector>
 
+#include "aqc_mps_states_rule.h"
+
 namespace aqc {
 
 enum { kMpsEntFusedCap = 64 };
@@ -32,13 +34,7 @@ enum { kMpsEntConverged = 0, kMpsEntSweepLimit = 1, kMpsEntNonFinite = 2 };   //
 constexpr double kMpsRankFloor = 1e-14;
 
 inline bool mps_ent_method_ok(int method) { return method == kMpsEntByRule || method == kMpsEntFused || method == kMpsEntCanonical; }
-// dims: the n + 1 bond dimensions
-inline int mps_ent_max_bond(int n, const int* dims) {
-    int m = 1;
-    for (int q = 0; q <= n; ++q) m = dims[q] > m ? dims[q] : m;
-    return m;
-}
-inline int mps_ent_route(int n, const int* dims) { return mps_ent_max_bond(n, dims) <= kMpsEntFusedCap ? kMpsEntFused : kMpsEntCanonical; }
+inline int mps_ent_route(int n, const int* dims) { return mps_max_bond(n, dims) <= kMpsEntFusedCap ? kMpsEntFused : kMpsEntCanonical; }
 inline int mps_ent_cuts(int n) { return n > 1 ? n - 1 : 0; }
 // the factors of one state, C_1 .. C_{n-1} (and in a second block of the same size D_1 .. D_{n-1}) packed back to back: element offset of
 // the factor of bond q, q = 1 .. n - 1, and (entry n) the size of a block; entry 0 is unused
@@ -105,14 +101,7 @@ inline void mps_ent_householder_r(int rows, int cols, std::complex<double>* m) {
 }
 
 // ---- chunks of the batched SVD: matrices of k x k whose five stores (a, u, vh, work, vmat) stay within budget_bytes; at least one
-inline int mps_ent_chunk(int k, size_t total, size_t budget_bytes) {
-    const size_t per = (size_t)5 * 16 * (size_t)k * (size_t)k;
-    size_t g = per ? budget_bytes / per : total;
-    if (g < 1) g = 1;
-    if (g > total) g = total;
-    if (g > (size_t)1 << 20) g = (size_t)1 << 20;
-    return (int)(g < 1 ? 1 : g);
-}
+inline int mps_ent_chunk(int k, size_t total, size_t budget_bytes) { return mps_svd_chunk(k, k, total, budget_bytes, (size_t)1 << 20); }
 
 // ---- the engine's rank decision on s[0 .. count), descending: false when s[0] is zero or not finite (rank and dropped untouched)
 inline bool mps_rank_rule(int count, const double* s, double trunc_thr, int max_bond, int* rank, double* dropped) {

@@ -1,54 +1,34 @@
 // C ABI (include/aqc_hip.h): pair density matrices of single-lane MPS states.  Rules: aqc_mps_obs_rule.h; kernels: aqc_mps_obs.hip.
+// The skeleton of the call: aqc_mps_call.h.
 #include <memory>
 #include <vector>
 
-#include "aqc_devbuf.h"
-#include "aqc_mps_host.h"
+#include "aqc_mps_call.h"
 #include "aqc_mps_obs_rule.h"
 
 using namespace aqc;
 
 namespace {
 
-constexpr size_t kGroupBudget = (size_t)256 << 20;   // bytes of chain scratch a group of chains of the gemm route may take
+static_assert(kMpsObsByRule == kMpsByRule && kMpsObsFused == kMpsFused, "resolve_route");
+enum { kSites, kEnvOff, kDims };                      // the sections of a state's record in the call's table
 
-// everything one state's launches read or write; alive until the call's last synchronisation
+// everything one lane's launches read or write; alive until the call's last synchronisation
 struct StateWork {
     int n = 0;
-    std::vector<int> dims;
-    std::vector<const double2*> t;
+    const MpsView* v = nullptr;                       // the lane's state
     std::vector<size_t> off;                          // env offsets, n + 2 entries (the last = total)
-    DevBuf<double2> env_l, env_r, tmp, chains, close, sums;
-    DevBuf<const double2*> d_sites;
+    NormEnvs env;
+    DevBuf<double2> chains, close, sums;
     DevBuf<int> d_ints;
-    DevBuf<size_t> d_off;
     DevBuf<void*> d_ptrs;
     std::vector<double2> h_sums;
 };
 
-// L_0 .. L_{n-1} and R_n .. R_1 of <psi|psi>; gemm route: with the engine's environment steps on the pair (psi, psi) (env_left / env_right of aqc_mps_host.h)
-int environments(StateWork& w, hipStream_t st, bool fused) {
+// the chains after the environments (norm_environments: the copies of one, then the sweep on the matrix cores)
+int run_fused(StateWork& w, const MpsObsPlan& plan, const MpsTable& table, size_t state, hipStream_t st) {
     const int n = w.n;
-    const size_t total = w.off[n + 1];
-    size_t tmax = 1;
-    for (int q = 0; q < n; ++q) tmax = std::max(tmax, (size_t)w.dims[q] * w.dims[q + 1]);
-    if (w.env_l.alloc(total) || w.env_r.alloc(total) || w.tmp.alloc(tmax)) return 1;
-    static const double one[2] = {1.0, 0.0};
-    HIP_OK(hipMemcpyAsync(w.env_l + w.off[0], one, sizeof one, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(w.env_r + w.off[n], one, sizeof one, hipMemcpyHostToDevice, st));
-    if (fused) return 0;   // the fused route sweeps them on the matrix cores (run_fused)
-    const int* dims = w.dims.data();
-    for (int q = 0; q + 1 < n; ++q)
-        if (env_left(st, w.env_l + w.off[q], w.t[q], w.t[q], site_dims(dims, dims, q), nullptr, nullptr, w.tmp, w.env_l + w.off[q + 1])) return 1;
-    for (int q = n - 1; q >= 1; --q)
-        if (env_right(st, w.env_r + w.off[q + 1], w.t[q], w.t[q], site_dims(dims, dims, q), w.tmp, w.env_r + w.off[q])) return 1;
-    return 0;
-}
-
-int run_fused(StateWork& w, const MpsObsPlan& plan, hipStream_t st) {
-    const int n = w.n;
-    std::vector<int> ints;                                   // dims | chain_start | chain_last | emit_of
-    ints.insert(ints.end(), w.dims.begin(), w.dims.end());
+    std::vector<int> ints;                                   // chain_start | chain_last | emit_of
     std::vector<int> chain_of(n, -1), starts;
     for (int i = 0; i < n; ++i)
         if (plan.last[i] >= 0) { chain_of[i] = (int)starts.size(); starts.push_back(i); }
@@ -58,33 +38,31 @@ int run_fused(StateWork& w, const MpsObsPlan& plan, hipStream_t st) {
     const size_t emit_at = ints.size();
     ints.resize(emit_at + (size_t)nchains * n, -1);
     for (size_t e = 0; e < plan.emits.size(); ++e) ints[emit_at + (size_t)chain_of[plan.emits[e].chain] * n + plan.emits[e].site] = (int)e;
-    std::vector<const double2*> sites(w.t.begin(), w.t.end());
-    if (w.d_ints.upload(ints) || w.d_sites.upload(sites) || w.d_off.upload(w.off)) return 1;
+    if (w.d_ints.upload(ints)) return 1;
     MpsObsFusedArgs a;
     a.n = n;
-    a.sites = w.d_sites;
-    a.dims = w.d_ints;
-    a.env_off = w.d_off;
-    a.env_l = w.env_l;
-    a.env_r = w.env_r;
-    a.chain_start = w.d_ints + (n + 1);
-    a.chain_last = w.d_ints + (n + 1) + nchains;
+    a.sites = table.at<const double2*>(state, kSites);
+    a.dims = table.at<int>(state, kDims);
+    a.env_off = table.at<size_t>(state, kEnvOff);
+    a.env_l = w.env.l;
+    a.env_r = w.env.r;
+    a.chain_start = w.d_ints;
+    a.chain_last = w.d_ints + nchains;
     a.emit_of = w.d_ints + emit_at;
     a.sums = w.sums;
-    HIP_OK(launch_mps_obs_env(a, st));
     HIP_OK(launch_mps_obs_fused(a, nchains, st));
     return 0;
 }
 
 int run_gemm(StateWork& w, const MpsObsPlan& plan, hipStream_t st) {
     const int n = w.n;
-    const int* dims = w.dims.data();
+    const int* dims = w.v->dims.data();
     const size_t S = mps_obs_slot_elems(n, dims);
     std::vector<int> starts;
     for (int i = 0; i < n; ++i)
         if (plan.last[i] >= 0) starts.push_back(i);
     const int nchains = (int)starts.size();
-    const int gsize = mps_obs_group_size(n, dims, nchains, kGroupBudget);
+    const int gsize = mps_obs_group_size(n, dims, nchains, kMpsCallBudget);
     // per chain: E [3][S] and F [3][2 S]; closing: H [2][S] and K [3][S]
     if (w.chains.alloc((size_t)gsize * 3 * kMpsObsComps * S) || w.close.alloc(5 * S)) return 1;
     double2* e_base = w.chains;
@@ -116,8 +94,8 @@ int run_gemm(StateWork& w, const MpsObsPlan& plan, hipStream_t st) {
             job.nstep = (int)stepping.size();
             // tables [5][nstep]: E slots | T_q[0] | T_q[1] | F slots | F slots + one site matrix
             for (int s : stepping) ptrs.push_back(e_slot(s));
-            for (int k = 0; k < job.nstep; ++k) ptrs.push_back(const_cast<double2*>(w.t[q]));
-            for (int k = 0; k < job.nstep; ++k) ptrs.push_back(const_cast<double2*>(w.t[q] + lr));
+            for (int k = 0; k < job.nstep; ++k) ptrs.push_back(const_cast<double2*>(w.v->t[q]));
+            for (int k = 0; k < job.nstep; ++k) ptrs.push_back(const_cast<double2*>(w.v->t[q] + lr));
             for (int s : stepping) ptrs.push_back(f_slot(s));
             for (int s : stepping) ptrs.push_back(f_slot(s) + lr);
             std::vector<int> slots, idx;
@@ -139,10 +117,10 @@ int run_gemm(StateWork& w, const MpsObsPlan& plan, hipStream_t st) {
         for (const SiteJob& job : group) {
             const int q = job.q, x = dims[q], u = dims[q + 1];
             const size_t lr = (size_t)x * u;
-            const double2* t0 = w.t[q];
+            const double2* t0 = w.v->t[q];
             const double2* t1 = t0 + lr;
             if (job.nemit) {   // K^{cd} = T_c (R_{q+1} T_d^H), components 00, 01, 11; then the sums of every chain that emits here
-                const double2* r = w.env_r + w.off[q + 1];
+                const double2* r = w.env.r + w.off[q + 1];
                 HIP_OK(launch_zgemm_bh(false, false, u, x, u, r, u, t0, u, hbuf, x, st));
                 HIP_OK(launch_zgemm_bh(false, false, u, x, u, r, u, t1, u, hbuf + S, x, st));
                 HIP_OK(launch_zgemm(false, false, x, x, u, t0, u, hbuf, x, kbuf, x, st));
@@ -159,7 +137,7 @@ int run_gemm(StateWork& w, const MpsObsPlan& plan, hipStream_t st) {
                 HIP_OK(launch_zgemm_tables_op(true, false, u, u, 2 * x, ctab(1), u, ctab(3), u, tab, u, 0, 2 * S, S, m, kMpsObsComps, st));
             }
             if (job.open_slot >= 0) {   // G_a = L_q T_a into the chain's F; E^{00} = T_0^H G_0, E^{01} = T_1^H G_0, E^{11} = T_1^H G_1
-                const double2* l = w.env_l + w.off[q];
+                const double2* l = w.env.l + w.off[q];
                 double2* g = f_slot(job.open_slot);
                 double2* e = e_slot(job.open_slot);
                 HIP_OK(launch_zgemm(false, false, x, u, x, l, x, t0, u, g, u, st));
@@ -217,49 +195,55 @@ int aqc_mps_obs_pairs(aqc_mps* const* states, int nstates, int npairs, const int
     if (nstates < 1) return failf("at least one state is needed");
     if (npairs < 1) return failf("at least one pair is needed");
     if (method != kMpsObsByRule && method != kMpsObsFused && method != kMpsObsGemm) return failf("unknown method %d", method);
-    for (int s = 0; s < nstates; ++s)
-        if (!states[s]) return failf("null state");
-    const int n = aqc_mps_num_qubits(states[0]), device = aqc_mps_device(states[0]);
-    if (n < 2) return failf("pair density matrices need at least 2 qubits");
-    for (int s = 1; s < nstates; ++s)
-        if (aqc_mps_num_qubits(states[s]) != n || aqc_mps_device(states[s]) != device) return failf("MPS states differ in size or device");
+    int n = 0, device = 0;
+    if (check_states(states, nullptr, nstates, 2, &n, &device)) return 1;
     MpsObsPlan plan;
     if (!mps_obs_plan(n, npairs, pairs, plan)) return failf("a pair needs two different qubits below %d", n);
     HIP_OK(hipSetDevice(device));
     hipStream_t st = mps_stream(states[0]);
     const size_t nemit = plan.emits.size();
+    std::vector<MpsView> views;
+    std::vector<int> lane_state;
+    if (view_states(states, (size_t)nstates, n, views, lane_state)) return 1;
+    std::vector<int> routes(views.size(), 0);
+    bool any_fused = false;
+    for (int s = 0; s < nstates; ++s) {
+        const MpsView& v = views[lane_state[s]];
+        int& route = routes[lane_state[s]];
+        if (!route && (route = resolve_route(method, mps_obs_route(n, v.dims.data()), v.max_bond, kMpsObsFusedCap, "state", s)) < 0) return 1;
+        any_fused = any_fused || route == kMpsObsFused;
+    }
+    MpsTable table;   // what the fused route reads of the states
+    if (any_fused) {
+        table = MpsTable({mps_table_words((size_t)n), mps_table_words((size_t)n + 2), mps_table_ints((size_t)n + 1)}, views.size());
+        for (size_t k = 0; k < views.size(); ++k) {
+            table.put(k, kSites, views[k].t, n);
+            table.put(k, kEnvOff, mps_obs_env_offsets(n, views[k].dims.data()), n + 2);
+            table.put(k, kDims, views[k].dims, n + 1);
+        }
+        if (table.upload()) return 1;
+    }
     std::vector<std::unique_ptr<StateWork>> work;
     int rc = 0;
-    for (int s = 0; s < nstates && !rc; ++s) {
+    for (int s = 0; s < nstates && !rc; ++s) {   // the work is per lane: a state listed twice is walked twice, its block written twice
+        const size_t k = (size_t)lane_state[s];
+        const MpsView& v = views[k];
         work.emplace_back(new StateWork());
         StateWork& w = *work.back();
         w.n = n;
-        w.dims.resize(n + 1);
-        w.t.resize(n);
-        if (aqc_mps_dims(states[s], w.dims.data())) { rc = 1; break; }
-        for (int q = 0; q < n && !rc; ++q) {   // (mps_peek drains the state's own stream: what aqc_mps_dot_ops does for its second operand)
-            const void* site = nullptr;
-            const double* lam = nullptr;
-            rc = mps_peek(states[s], q, &site, &lam);
-            w.t[q] = static_cast<const double2*>(site);
-        }
-        if (rc) break;
-        w.off = mps_obs_env_offsets(n, w.dims.data());
-        int route = method == kMpsObsByRule ? mps_obs_route(n, w.dims.data()) : method;
-        if (route == kMpsObsFused && mps_obs_max_bond(n, w.dims.data()) > kMpsObsFusedCap) {
-            rc = failf("the fused route takes bond dimensions up to %d; state %d has %d", (int)kMpsObsFusedCap, s, mps_obs_max_bond(n, w.dims.data()));
-            break;
-        }
+        w.v = &v;
+        w.off = mps_obs_env_offsets(n, v.dims.data());
         if (w.sums.alloc(nemit * kMpsObsComps * 4)) { rc = 1; break; }
-        rc = environments(w, st, route == kMpsObsFused) || (route == kMpsObsFused ? run_fused(w, plan, st) : run_gemm(w, plan, st));
+        const bool fused = routes[k] == kMpsObsFused;
+        rc = norm_environments(w.env, v, w.off, st, fused, kEnvLeft | kEnvRight, table.at<const double2*>(k, kSites), table.at<int>(k, kDims),
+                               table.at<size_t>(k, kEnvOff)) ||
+             (fused ? run_fused(w, plan, table, k, st) : run_gemm(w, plan, st));
         if (rc) break;
         w.h_sums.resize(nemit * kMpsObsComps * 4);
         if (hipMemcpyAsync(w.h_sums.data(), w.sums, sizeof(double2) * w.h_sums.size(), hipMemcpyDeviceToHost, st) != hipSuccess)
             rc = failf("download of the sums failed");
     }
-    const hipError_t e = hipStreamSynchronize(st);   // before any buffer goes, also after a failure
-    if (rc) return 1;
-    if (e != hipSuccess) return failf("pair density matrices failed: %s", hipGetErrorString(e));
+    if (finish_call(st, rc, "pair density matrices")) return 1;
     for (int s = 0; s < nstates; ++s)
         for (int p = 0; p < npairs; ++p) {
             double m[32];

@@ -21,6 +21,8 @@
 
 #include <vector>
 
+#include "aqc_mps_states_rule.h"
+
 namespace aqc {
 
 enum { kMpsObsComps = 3, kMpsObsUpper = 10, kMpsObsFusedCap = 64 };
@@ -86,13 +88,7 @@ inline bool mps_obs_plan(int n, int npairs, const int32_t* pairs, MpsObsPlan& pl
     return true;
 }
 
-// dims: the n + 1 bond dimensions
-inline int mps_obs_max_bond(int n, const int* dims) {
-    int m = 1;
-    for (int q = 0; q <= n; ++q) m = dims[q] > m ? dims[q] : m;
-    return m;
-}
-inline int mps_obs_route(int n, const int* dims) { return mps_obs_max_bond(n, dims) <= kMpsObsFusedCap ? kMpsObsFused : kMpsObsGemm; }
+inline int mps_obs_route(int n, const int* dims) { return mps_max_bond(n, dims) <= kMpsObsFusedCap ? kMpsObsFused : kMpsObsGemm; }
 
 // the pair's matrix from its emission: out[r][s] = m[r][s], or with the two index bits of r and of s swapped (complex numbers as pairs)
 inline void mps_obs_place(const double* m, int transposed, double* out) {
@@ -113,7 +109,7 @@ inline std::vector<size_t> mps_obs_env_offsets(int n, const int* dims) {
     return off;
 }
 // gemm route: a chain holds kMpsObsComps matrices E and, during a step, kMpsObsComps stacked products [E T_0; E T_1]
-inline size_t mps_obs_slot_elems(int n, const int* dims) { const size_t m = (size_t)mps_obs_max_bond(n, dims); return m * m; }
+inline size_t mps_obs_slot_elems(int n, const int* dims) { const size_t m = (size_t)mps_max_bond(n, dims); return m * m; }
 inline size_t mps_obs_chain_elems(int n, const int* dims) { return 3 * (size_t)kMpsObsComps * mps_obs_slot_elems(n, dims); }
 // chains walked together (a group) so that their scratch stays below budget_bytes; at least one
 inline int mps_obs_group_size(int n, const int* dims, int nchains, size_t budget_bytes) {

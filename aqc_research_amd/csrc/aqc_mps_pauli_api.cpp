@@ -1,12 +1,11 @@
 // C ABI (include/aqc_hip.h): Pauli strings between single-lane MPS states.  Rules: aqc_mps_pauli_rule.h; kernels: aqc_mps_pauli.hip.
+// The skeleton of the call: aqc_mps_call.h.
 #include <algorithm>
-#include <cstring>
 #include <map>
 #include <memory>
 #include <vector>
 
-#include "aqc_devbuf.h"
-#include "aqc_mps_host.h"
+#include "aqc_mps_call.h"
 #include "aqc_mps_obs_rule.h"
 #include "aqc_mps_pauli_rule.h"
 
@@ -14,23 +13,21 @@ using namespace aqc;
 
 namespace {
 
-constexpr size_t kGroupBudget = (size_t)256 << 20;   // bytes of scratch a group of jobs of the gemm route may take
-constexpr int kMaxGridY = 65535;
+static_assert(kMpsPauliByRule == kMpsByRule && kMpsPauliFused == kMpsFused, "resolve_route");
+enum { kSites, kEnvOff, kSiteOff, kDims };            // the sections of a state's record in Call::table
 
-// everything the launches read of one distinct state; alive until the call's last synchronisation
+// what the call adds to the view of one distinct state; alive until the call's last synchronisation
 struct StateWork {
-    int n = 0;
-    std::vector<int> dims;
-    std::vector<const double2*> t;
+    const MpsView* v = nullptr;
     std::vector<size_t> off;                          // env offsets, n + 2 entries (the last = total)
     std::vector<size_t> site_off;                     // element offset of site q in one dressed copy, n + 1 entries (the last = total)
-    DevBuf<double2> env_l, env_r, tmp, dressed;
-    // the same on the device, inside the call's one table (Call::d_tables)
+    NormEnvs env;                                     // expectation mode: of the kets, built once
+    DevBuf<double2> dressed;
+    // the same on the device, inside the call's one table
     const double2* const* d_sites = nullptr;
     const size_t* d_off = nullptr;
     const size_t* d_site_off = nullptr;
     const int* d_dims = nullptr;
-    bool has_env = false;
 };
 
 // one walk of the gemm route: the pairs of the call that share their bond dimensions
@@ -45,10 +42,11 @@ struct Call {
     bool expectation = false;
     const uint8_t* strings = nullptr;
     std::vector<int> first, last;
-    std::map<const aqc_mps*, std::unique_ptr<StateWork>> states;
+    std::vector<MpsView> views;                       // distinct, in order of first appearance
+    std::vector<StateWork> states;                    // one per view
     std::vector<std::unique_ptr<WalkWork>> walks;
     DevBuf<double2> d_out, d_one;
-    DevBuf<unsigned long long> d_tables;              // per distinct state: site pointers | env offsets | site offsets | dims, 8-byte words
+    MpsTable table;                                   // per distinct state: site pointers | env offsets | site offsets | dims
     DevBuf<unsigned char> d_strings;
     DevBuf<int> d_support;
     DevBuf<MpsPauliState> d_kets, d_bras;
@@ -57,73 +55,33 @@ struct Call {
 
 // what the kernels read of every distinct state, in one upload for the call
 int tables(Call& c) {
-    static_assert(sizeof(unsigned long long) == sizeof(size_t) && sizeof(unsigned long long) == sizeof(const double2*), "8-byte words");
-    const size_t n = (size_t)c.n, per = n + (n + 2) + (n + 1) + (n + 2) / 2;
-    std::vector<unsigned long long> words(per * c.states.size(), 0);
-    size_t at = 0;
-    for (auto& kv : c.states) {
-        StateWork& w = *kv.second;
-        unsigned long long* p = words.data() + at;
-        memcpy(p, w.t.data(), n * 8);
-        memcpy(p + n, w.off.data(), (n + 2) * 8);
-        memcpy(p + 2 * n + 2, w.site_off.data(), (n + 1) * 8);
-        memcpy(p + 3 * n + 3, w.dims.data(), (n + 1) * sizeof(int));
-        at += per;
+    const size_t n = (size_t)c.n;
+    c.table = MpsTable({mps_table_words(n), mps_table_words(n + 2), mps_table_words(n + 1), mps_table_ints(n + 1)}, c.states.size());
+    for (size_t k = 0; k < c.states.size(); ++k) {
+        c.table.put(k, kSites, c.views[k].t, n);
+        c.table.put(k, kEnvOff, c.states[k].off, n + 2);
+        c.table.put(k, kSiteOff, c.states[k].site_off, n + 1);
+        c.table.put(k, kDims, c.views[k].dims, n + 1);
     }
-    if (c.d_tables.upload(words)) return 1;
-    at = 0;
-    for (auto& kv : c.states) {
-        StateWork& w = *kv.second;
-        const unsigned long long* p = c.d_tables + at;
-        w.d_sites = reinterpret_cast<const double2* const*>(p);
-        w.d_off = reinterpret_cast<const size_t*>(p + n);
-        w.d_site_off = reinterpret_cast<const size_t*>(p + 2 * n + 2);
-        w.d_dims = reinterpret_cast<const int*>(p + 3 * n + 3);
-        at += per;
+    if (c.table.upload()) return 1;
+    for (size_t k = 0; k < c.states.size(); ++k) {
+        StateWork& w = c.states[k];
+        w.d_sites = c.table.at<const double2*>(k, kSites);
+        w.d_off = c.table.at<size_t>(k, kEnvOff);
+        w.d_site_off = c.table.at<size_t>(k, kSiteOff);
+        w.d_dims = c.table.at<int>(k, kDims);
     }
-    return 0;
-}
-
-// L_0 .. L_{n-1} and R_n .. R_1 of <psi|psi>: fused route with the sweep of the observables on the matrix cores, gemm route with the
-// engine's environment steps on the pair (psi, psi)
-int environments(StateWork& w, hipStream_t st, bool fused) {
-    if (w.has_env) return 0;
-    const int n = w.n;
-    const size_t total = w.off[n + 1];
-    if (w.env_l.alloc(total) || w.env_r.alloc(total)) return 1;
-    static const double one[2] = {1.0, 0.0};
-    HIP_OK(hipMemcpyAsync(w.env_l + w.off[0], one, sizeof one, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(w.env_r + w.off[n], one, sizeof one, hipMemcpyHostToDevice, st));
-    w.has_env = true;
-    if (fused) {
-        MpsObsFusedArgs a{};
-        a.n = n;
-        a.sites = w.d_sites;
-        a.dims = w.d_dims;
-        a.env_off = w.d_off;
-        a.env_l = w.env_l;
-        a.env_r = w.env_r;
-        HIP_OK(launch_mps_obs_env(a, st));
-        return 0;
-    }
-    size_t tmax = 1;
-    for (int q = 0; q < n; ++q) tmax = std::max(tmax, (size_t)w.dims[q] * w.dims[q + 1]);
-    if (w.tmp.alloc(tmax)) return 1;
-    const int* dims = w.dims.data();
-    for (int q = 0; q + 1 < n; ++q)
-        if (env_left(st, w.env_l + w.off[q], w.t[q], w.t[q], site_dims(dims, dims, q), nullptr, nullptr, w.tmp, w.env_l + w.off[q + 1])) return 1;
-    for (int q = n - 1; q >= 1; --q)
-        if (env_right(st, w.env_r + w.off[q + 1], w.t[q], w.t[q], site_dims(dims, dims, q), w.tmp, w.env_r + w.off[q])) return 1;
     return 0;
 }
 
 int dress(StateWork& w, hipStream_t st) {   // the X, Y, Z copies of every site, once per bra and call
     if (w.dressed) return 0;
-    const size_t total = w.site_off[w.n];
+    const int n = (int)w.v->t.size();
+    const size_t total = w.site_off[n];
     size_t smax = 1;
-    for (int q = 0; q < w.n; ++q) smax = std::max(smax, 2 * (size_t)w.dims[q] * w.dims[q + 1]);
+    for (int q = 0; q < n; ++q) smax = std::max(smax, 2 * (size_t)w.v->dims[q] * w.v->dims[q + 1]);
     if (w.dressed.alloc(3 * total)) return 1;
-    HIP_OK(launch_mps_pauli_dress(w.d_sites, w.d_dims, w.d_site_off, w.n, total, (int)smax, w.dressed, st));
+    HIP_OK(launch_mps_pauli_dress(w.d_sites, w.d_dims, w.d_site_off, n, total, (int)smax, w.dressed, st));
     return 0;
 }
 
@@ -132,15 +90,15 @@ int dress(StateWork& w, hipStream_t st) {   // the X, Y, Z copies of every site,
 int run_gemm(Call& c, const std::vector<int>& pairs, const std::vector<StateWork*>& bras, const std::vector<StateWork*>& kets, hipStream_t st) {
     const int n = c.n, S = c.nstrings;
     const size_t njobs = pairs.size() * (size_t)S;
-    const int* bd = bras[pairs[0]]->dims.data();
-    const int* kd = kets[pairs[0]]->dims.data();
+    const int* bd = bras[pairs[0]]->v->dims.data();
+    const int* kd = kets[pairs[0]]->v->dims.data();
     const size_t melems = mps_pauli_m_elems(n, bd, kd), felems = mps_pauli_f_elems(n, bd, kd);
-    const size_t gsize = (size_t)mps_pauli_group_size(melems + felems, (int)std::min<size_t>(njobs, (size_t)kMpsPauliGroupMax), kGroupBudget);
+    const size_t gsize = (size_t)mps_pauli_group_size(melems + felems, (int)std::min<size_t>(njobs, (size_t)kMpsPauliGroupMax), kMpsCallBudget);
     c.walks.emplace_back(new WalkWork());
     WalkWork& w = *c.walks.back();
     if (w.scratch.alloc(gsize * (melems + felems))) return 1;
     for (int p : pairs)
-        if (dress(*bras[p], st) || (c.expectation && environments(*kets[p], st, false))) return 1;
+        if (dress(*bras[p], st) || (c.expectation && norm_environments(kets[p]->env, *kets[p]->v, kets[p]->off, st, false, kEnvLeft | kEnvRight))) return 1;
     double2* m_base = w.scratch;
     double2* f_base = m_base + gsize * melems;
     // the tables of every group and site, built first and uploaded once: pointers (7 per job that crosses the site, 2 per job that ends
@@ -167,24 +125,24 @@ int run_gemm(Call& c, const std::vector<int>& pairs, const std::vector<StateWork
             auto ket_of = [&](size_t k) -> const StateWork& { return *kets[pairs[k / S]]; };
             // tables [7][nstep]: M in | T_q[0] | T_q[1] | F | F + one product | D | M out
             for (size_t k : active) {
-                const double2* in = q > first_of(k) ? m_slot(k) : c.expectation ? ket_of(k).env_l + ket_of(k).off[q] : (double2*)c.d_one;
+                const double2* in = q > first_of(k) ? m_slot(k) : c.expectation ? ket_of(k).env.l + ket_of(k).off[q] : (double2*)c.d_one;
                 ptrs.push_back(const_cast<double2*>(in));
             }
-            for (size_t k : active) ptrs.push_back(const_cast<double2*>(ket_of(k).t[q]));
-            for (size_t k : active) ptrs.push_back(const_cast<double2*>(ket_of(k).t[q] + tsize));
+            for (size_t k : active) ptrs.push_back(const_cast<double2*>(ket_of(k).v->t[q]));
+            for (size_t k : active) ptrs.push_back(const_cast<double2*>(ket_of(k).v->t[q] + tsize));
             for (size_t k : active) ptrs.push_back(f_slot(k));
             for (size_t k : active) ptrs.push_back(f_slot(k) + half);
             for (size_t k : active) {
                 const StateWork& bra = *bras[pairs[k / S]];
                 const int letter = c.strings[(k % S) * n + q];
-                const double2* d = letter == kMpsPauliI ? bra.t[q] : bra.dressed + (size_t)(letter - 1) * bra.site_off[n] + bra.site_off[q];
+                const double2* d = letter == kMpsPauliI ? bra.v->t[q] : bra.dressed + (size_t)(letter - 1) * bra.site_off[n] + bra.site_off[q];
                 ptrs.push_back(const_cast<double2*>(d));
             }
             for (size_t k : active) ptrs.push_back(m_slot(k));
             job.close_at = ptrs.size();
             for (size_t k : closing) ptrs.push_back(m_slot(k));
             for (size_t k : closing) {
-                ptrs.push_back(c.expectation ? ket_of(k).env_r + ket_of(k).off[q + 1] : (double2*)c.d_one);
+                ptrs.push_back(c.expectation ? ket_of(k).env.r + ket_of(k).off[q + 1] : (double2*)c.d_one);
                 ints.push_back((int)((size_t)pairs[k / S] * S + k % S));
             }
             jobs.push_back(job);
@@ -215,12 +173,13 @@ int run_fused(Call& c, const std::vector<int>& fused, const std::vector<StateWor
     std::vector<double2*> outs;
     auto entry = [](const StateWork& w) {
         MpsPauliState e{};
-        e.sites = w.d_sites; e.dims = w.d_dims; e.env_off = w.d_off; e.env_l = w.env_l; e.env_r = w.env_r;
+        e.sites = w.d_sites; e.dims = w.d_dims; e.env_off = w.d_off; e.env_l = w.env.l; e.env_r = w.env.r;
         return e;
     };
     for (int p : fused) {
-        if (c.expectation && environments(*kets[p], st, true)) return 1;
-        hk.push_back(entry(*kets[p]));
+        StateWork& k = *kets[p];
+        if (c.expectation && norm_environments(k.env, *k.v, k.off, st, true, kEnvLeft | kEnvRight, k.d_sites, k.d_dims, k.d_off)) return 1;
+        hk.push_back(entry(k));
         hb.push_back(entry(*bras[p]));
         outs.push_back(c.d_out + (size_t)p * c.nstrings);
     }
@@ -239,37 +198,26 @@ int run_fused(Call& c, const std::vector<int>& fused, const std::vector<StateWor
 
 int run(Call& c, aqc_mps* const* bras, aqc_mps* const* kets, int method, double* out, hipStream_t st) {
     const int n = c.n;
+    std::vector<aqc_mps*> listed;   // bra and ket of every pair (expectation mode: the ket twice)
+    for (int p = 0; p < c.npairs; ++p) listed.insert(listed.end(), {bras ? bras[p] : kets[p], kets[p]});
+    std::vector<int> listed_state;
+    if (view_states(listed.data(), listed.size(), n, c.views, listed_state)) return 1;
+    c.states.resize(c.views.size());
+    for (size_t k = 0; k < c.states.size(); ++k) {
+        StateWork& w = c.states[k];
+        w.v = &c.views[k];
+        w.off = mps_obs_env_offsets(n, w.v->dims.data());
+        w.site_off = mps_site_offsets(n, w.v->dims.data());
+    }
     std::vector<StateWork*> wb(c.npairs), wk(c.npairs);
-    for (int p = 0; p < c.npairs; ++p)
-        for (int side = 0; side < 2; ++side) {
-            aqc_mps* h = side || !bras ? kets[p] : bras[p];
-            std::unique_ptr<StateWork>& slot = c.states[h];
-            if (!slot) {
-                slot.reset(new StateWork());
-                StateWork& w = *slot;
-                w.n = n;
-                w.dims.resize(n + 1);
-                w.t.resize(n);
-                if (aqc_mps_dims(h, w.dims.data())) return 1;
-                for (int q = 0; q < n; ++q) {   // (mps_peek drains the state's own stream: what aqc_mps_dot_ops does for its second operand)
-                    const void* site = nullptr;
-                    const double* lam = nullptr;
-                    if (mps_peek(h, q, &site, &lam)) return 1;
-                    w.t[q] = static_cast<const double2*>(site);
-                }
-                w.off = mps_obs_env_offsets(n, w.dims.data());
-                w.site_off.assign(n + 1, 0);
-                for (int q = 0; q < n; ++q) w.site_off[q + 1] = w.site_off[q] + 2 * (size_t)w.dims[q] * w.dims[q + 1];
-            }
-            (side ? wk : wb)[p] = slot.get();
-        }
     std::vector<int> fused, gemm;
     for (int p = 0; p < c.npairs; ++p) {
-        const int* bd = wb[p] == wk[p] ? nullptr : wb[p]->dims.data();
-        const int route = method == kMpsPauliByRule ? mps_pauli_route(n, bd, wk[p]->dims.data()) : method;
-        const int maxb = mps_pauli_max_bond(n, bd, wk[p]->dims.data());
-        if (route == kMpsPauliFused && maxb > kMpsPauliFusedCap)
-            return failf("the fused route takes bond dimensions up to %d; pair %d has %d", (int)kMpsPauliFusedCap, p, maxb);
+        wb[p] = &c.states[listed_state[2 * p]];
+        wk[p] = &c.states[listed_state[2 * p + 1]];
+        const int* bd = wb[p] == wk[p] ? nullptr : wb[p]->v->dims.data();
+        const int* kd = wk[p]->v->dims.data();
+        const int route = resolve_route(method, mps_pauli_route(n, bd, kd), mps_pauli_max_bond(n, bd, kd), kMpsPauliFusedCap, "pair", p);
+        if (route < 0) return 1;
         (route == kMpsPauliFused ? fused : gemm).push_back(p);
     }
     if (tables(c) || c.d_out.alloc((size_t)c.npairs * c.nstrings)) return 1;
@@ -280,7 +228,7 @@ int run(Call& c, aqc_mps* const* bras, aqc_mps* const* kets, int method, double*
     }
     if (!fused.empty() && run_fused(c, fused, wb, wk, st)) return 1;
     std::map<std::pair<std::vector<int>, std::vector<int>>, std::vector<int>> walks;   // pairs with the same bonds share a walk
-    for (int p : gemm) walks[{wb[p]->dims, wk[p]->dims}].push_back(p);
+    for (int p : gemm) walks[{wb[p]->v->dims, wk[p]->v->dims}].push_back(p);
     for (const auto& walk : walks)
         if (run_gemm(c, walk.second, wb, wk, st)) return 1;
     HIP_OK(hipMemcpyAsync(out, c.d_out, sizeof(double2) * (size_t)c.npairs * c.nstrings, hipMemcpyDeviceToHost, st));
@@ -313,13 +261,8 @@ int aqc_mps_pauli(aqc_mps* const* bras, aqc_mps* const* kets, int npairs, int ns
     if (npairs < 1) return failf("at least one pair of states is needed");
     if (nstrings < 1) return failf("at least one string is needed");
     if (!mps_pauli_method_ok(method)) return failf("unknown method %d", method);
-    for (int p = 0; p < npairs; ++p)
-        if (!kets[p] || (bras && !bras[p])) return failf("null state");
-    const int n = aqc_mps_num_qubits(kets[0]), device = aqc_mps_device(kets[0]);
-    if (n < 1) return failf("a state needs at least 1 qubit");
-    for (int p = 0; p < npairs; ++p)
-        for (aqc_mps* h : {kets[p], bras ? bras[p] : kets[p]})
-            if (aqc_mps_num_qubits(h) != n || aqc_mps_device(h) != device) return failf("MPS states differ in size or device");
+    int n = 0, device = 0;
+    if (check_states(kets, bras, npairs, 1, &n, &device)) return 1;
     if ((size_t)npairs * (size_t)nstrings > (size_t)1 << 30) return failf("too many values in one call: %d pairs x %d strings", npairs, nstrings);
     Call c;
     c.n = n;
@@ -332,11 +275,7 @@ int aqc_mps_pauli(aqc_mps* const* bras, aqc_mps* const* kets, int npairs, int ns
     if (aqc_mps_pauli_support(n, nstrings, strings, c.first.data(), c.last.data())) return 1;
     HIP_OK(hipSetDevice(device));
     hipStream_t st = mps_stream(kets[0]);
-    const int rc = run(c, bras, kets, method, out, st);
-    const hipError_t e = hipStreamSynchronize(st);   // before any buffer goes, also after a failure
-    if (rc) return 1;
-    if (e != hipSuccess) return failf("Pauli strings failed: %s", hipGetErrorString(e));
-    return 0;
+    return finish_call(st, run(c, bras, kets, method, out, st), "Pauli strings");
 }
 
 }  // extern "C"

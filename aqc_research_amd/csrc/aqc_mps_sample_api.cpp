@@ -1,73 +1,43 @@
 // C ABI (include/aqc_hip.h): shots and amplitudes of single-lane MPS states.  Rules: aqc_mps_sample_rule.h; kernels: aqc_mps_sample.hip.
+// The skeleton of the call: aqc_mps_call.h.
 #include <algorithm>
 #include <memory>
 #include <vector>
 
-#include "aqc_devbuf.h"
-#include "aqc_mps_host.h"
+#include "aqc_mps_call.h"
 #include "aqc_mps_sample_rule.h"
 
 using namespace aqc;
 
 namespace {
 
-// everything one state's launches read or write; alive until the call's last synchronisation
+static_assert(kMpsSampleByRule == kMpsByRule && kMpsSampleFused == kMpsFused, "resolve_route");
+enum { kSites, kEnvOff, kDims };                      // the sections of a state's record in the call's table
+
+// everything one lane's launches read or write; alive until the call's last synchronisation
 struct StateWork {
     int n = 0, route = 0;
-    std::vector<int> dims;
-    std::vector<const double2*> t;
+    const MpsView* v = nullptr;                       // the lane's state
     std::vector<size_t> off;                          // env offsets, n + 2 entries (the last = total)
-    DevBuf<double2> env_l, env_r, tmp, mats, amps;
+    NormEnvs env;                                     // shots: R_n .. R_1 (the fused sweep brings the left half with it)
+    DevBuf<double2> mats, amps;
     DevBuf<unsigned char> bits, status;
     DevBuf<double> norm2;
-    DevBuf<const double2*> d_sites;
-    DevBuf<int> d_dims;
-    DevBuf<size_t> d_off;
     std::vector<unsigned char> h_status;
 };
 
 struct Call {
-    int n = 0, nstates = 0;
+    int n = 0, nstates = 0, device = 0;
     int64_t count = 0;                                // shots, or bit strings
     uint64_t first_shot = 0, seed = 0;
     bool amplitudes = false;
     const unsigned char* d_bits_in = nullptr;         // amplitudes: [count][n] on the device
 };
 
-// R_n .. R_1 of <psi|psi>: fused route on the matrix cores (the sweep of the observables, whose left half comes with it), gemm route
-// with the engine's environment step on the pair (psi, psi)
-int environments(StateWork& w, hipStream_t st) {
-    const int n = w.n;
-    const size_t total = w.off[n + 1];
-    static const double one[2] = {1.0, 0.0};
-    if (w.env_r.alloc(total)) return 1;
-    HIP_OK(hipMemcpyAsync(w.env_r + w.off[n], one, sizeof one, hipMemcpyHostToDevice, st));
-    const int* dims = w.dims.data();
-    if (w.route == kMpsSampleFused) {
-        if (w.env_l.alloc(total)) return 1;
-        HIP_OK(hipMemcpyAsync(w.env_l + w.off[0], one, sizeof one, hipMemcpyHostToDevice, st));
-        MpsObsFusedArgs a{};
-        a.n = n;
-        a.sites = w.d_sites;
-        a.dims = w.d_dims;
-        a.env_off = w.d_off;
-        a.env_l = w.env_l;
-        a.env_r = w.env_r;
-        HIP_OK(launch_mps_obs_env(a, st));
-        return 0;
-    }
-    size_t tmax = 1;
-    for (int q = 0; q < n; ++q) tmax = std::max(tmax, (size_t)dims[q] * dims[q + 1]);
-    if (w.tmp.alloc(tmax)) return 1;
-    for (int q = n - 1; q >= 1; --q)
-        if (env_right(st, w.env_r + w.off[q + 1], w.t[q], w.t[q], site_dims(dims, dims, q), w.tmp, w.env_r + w.off[q])) return 1;
-    return 0;
-}
-
 // the shots walked in chunks: per site V T_0, V T_1, W_0 R, W_1 R and the row kernel
 int run_gemm(StateWork& w, const Call& c, int lane, hipStream_t st) {
     const int n = w.n;
-    const int maxb = mps_obs_max_bond(n, w.dims.data());
+    const int maxb = w.v->max_bond;
     const int64_t chunk = mps_sample_chunk(maxb, c.count);
     const size_t mat = (size_t)chunk * maxb;
     if (w.mats.alloc(kMpsSampleGemmMats * mat)) return 1;
@@ -76,13 +46,13 @@ int run_gemm(StateWork& w, const Call& c, int lane, hipStream_t st) {
         const int rows = (int)std::min<int64_t>(chunk, c.count - s0);
         HIP_OK(launch_mps_sample_ones(v, rows, st));
         for (int q = 0; q < n; ++q) {
-            const int x = w.dims[q], u = w.dims[q + 1];
-            const double2* t0 = w.t[q];
+            const int x = w.v->dims[q], u = w.v->dims[q + 1];
+            const double2* t0 = w.v->t[q];
             const double2* t1 = t0 + (size_t)x * u;
             HIP_OK(launch_zgemm(false, false, rows, u, x, v, x, t0, u, w0, u, st));
             HIP_OK(launch_zgemm(false, false, rows, u, x, v, x, t1, u, w1, u, st));
             if (!c.amplitudes) {
-                const double2* r = w.env_r + w.off[q + 1];
+                const double2* r = w.env.r + w.off[q + 1];
                 HIP_OK(launch_zgemm(false, false, rows, u, u, w0, u, r, u, g0, u, st));
                 HIP_OK(launch_zgemm(false, false, rows, u, u, w1, u, r, u, g1, u, st));
             }
@@ -102,8 +72,29 @@ int run_gemm(StateWork& w, const Call& c, int lane, hipStream_t st) {
 // what both entry points do once their arguments have passed; outputs may be null where the entry point allows it
 int run(aqc_mps* const* states, const Call& c, int method, const unsigned char* bits_in, unsigned char* bits, double* amps, double* norm2) {
     const int n = c.n, nstates = c.nstates;
-    HIP_OK(hipSetDevice(aqc_mps_device(states[0])));
+    HIP_OK(hipSetDevice(c.device));
     hipStream_t st = mps_stream(states[0]);
+    std::vector<MpsView> views;
+    std::vector<int> lane_state;
+    if (view_states(states, (size_t)nstates, n, views, lane_state)) return 1;
+    std::vector<int> routes(views.size(), 0);
+    bool any_fused = false;
+    for (int s = 0; s < nstates; ++s) {
+        const MpsView& v = views[lane_state[s]];
+        int& route = routes[lane_state[s]];
+        if (!route && (route = resolve_route(method, mps_sample_route(n, v.dims.data()), v.max_bond, kMpsSampleFusedCap, "state", s)) < 0) return 1;
+        any_fused = any_fused || route == kMpsSampleFused;
+    }
+    MpsTable dev;   // what the fused route reads of the states
+    if (any_fused) {
+        dev = MpsTable({mps_table_words((size_t)n), mps_table_words((size_t)n + 2), mps_table_ints((size_t)n + 1)}, views.size());
+        for (size_t k = 0; k < views.size(); ++k) {
+            dev.put(k, kSites, views[k].t, n);
+            dev.put(k, kEnvOff, mps_obs_env_offsets(n, views[k].dims.data()), n + 2);
+            dev.put(k, kDims, views[k].dims, n + 1);
+        }
+        if (dev.upload()) return 1;
+    }
     std::vector<std::unique_ptr<StateWork>> work;
     DevBuf<unsigned char> d_bits_in;
     DevBuf<MpsSampleState> d_table;
@@ -114,40 +105,27 @@ int run(aqc_mps* const* states, const Call& c, int method, const unsigned char* 
         call.d_bits_in = d_bits_in;
     }
     std::vector<MpsSampleState> table;
-    for (int s = 0; s < nstates && !rc; ++s) {
+    for (int s = 0; s < nstates && !rc; ++s) {   // the work is per lane: the lane is part of the Philox counter
+        const size_t k = (size_t)lane_state[s];
+        const MpsView& v = views[k];
         work.emplace_back(new StateWork());
         StateWork& w = *work.back();
         w.n = n;
-        w.dims.resize(n + 1);
-        w.t.resize(n);
-        if (aqc_mps_dims(states[s], w.dims.data())) { rc = 1; break; }
-        for (int q = 0; q < n && !rc; ++q) {   // (mps_peek drains the state's own stream)
-            const void* site = nullptr;
-            const double* lam = nullptr;
-            rc = mps_peek(states[s], q, &site, &lam);
-            w.t[q] = static_cast<const double2*>(site);
-        }
-        if (rc) break;
-        w.off = mps_obs_env_offsets(n, w.dims.data());
-        const int maxb = mps_obs_max_bond(n, w.dims.data());
-        w.route = method == kMpsSampleByRule ? mps_sample_route(n, w.dims.data()) : method;
-        if (w.route == kMpsSampleFused && maxb > kMpsSampleFusedCap) {
-            rc = failf("the fused route takes bond dimensions up to %d; state %d has %d", (int)kMpsSampleFusedCap, s, maxb);
-            break;
-        }
+        w.v = &v;
+        w.off = mps_obs_env_offsets(n, v.dims.data());
+        w.route = routes[k];
         if (w.amps.alloc((size_t)c.count)) { rc = 1; break; }
         if (!c.amplitudes) {
             if (w.bits.alloc((size_t)c.count * n) || w.status.alloc((size_t)c.count) || w.norm2.alloc(1)) { rc = 1; break; }
             if (hipMemsetAsync(w.status, 0, (size_t)c.count, st) != hipSuccess) { rc = failf("clearing the status failed"); break; }
         }
-        if (w.route == kMpsSampleFused) {
-            std::vector<const double2*> sites(w.t.begin(), w.t.end());
-            if (w.d_sites.upload(sites) || w.d_dims.upload(w.dims) || w.d_off.upload(w.off)) { rc = 1; break; }
-        }
-        if (!c.amplitudes && (rc = environments(w, st))) break;
+        const double2* const* d_sites = dev.at<const double2*>(k, kSites);
+        const int* d_dims = dev.at<int>(k, kDims);
+        const size_t* d_off = dev.at<size_t>(k, kEnvOff);
+        if (!c.amplitudes && (rc = norm_environments(w.env, v, w.off, st, w.route == kMpsSampleFused, kEnvRight, d_sites, d_dims, d_off))) break;
         if (w.route == kMpsSampleFused) {
             MpsSampleState e{};
-            e.sites = w.d_sites; e.dims = w.d_dims; e.env_off = w.d_off; e.env_r = w.env_r;
+            e.sites = d_sites; e.dims = d_dims; e.env_off = d_off; e.env_r = w.env.r;
             e.bits = w.bits; e.amps = w.amps; e.status = w.status; e.norm2 = w.norm2;
             e.lane = (unsigned long long)s;
             table.push_back(e);
@@ -177,26 +155,12 @@ int run(aqc_mps* const* states, const Call& c, int method, const unsigned char* 
         }
         if (e != hipSuccess) rc = failf("download of the results failed: %s", hipGetErrorString(e));
     }
-    const hipError_t e = hipStreamSynchronize(st);   // before any buffer goes, also after a failure
-    if (rc) return 1;
-    if (e != hipSuccess) return failf("%s failed: %s", c.amplitudes ? "amplitudes" : "sampling", hipGetErrorString(e));
+    if (finish_call(st, rc, c.amplitudes ? "amplitudes" : "sampling")) return 1;
     for (int s = 0; s < nstates; ++s)
         for (size_t k = 0; k < work[s]->h_status.size(); ++k)
             if (work[s]->h_status[k])
                 return failf("lane %d, shot %llu: the weights of the two branches do not add up to a finite positive number", s,
                              (unsigned long long)(c.first_shot + k));
-    return 0;
-}
-
-// the checks on the states that both entry points share; *n_out = the number of qubits
-int check_states(aqc_mps* const* states, int nstates, int* n_out) {
-    for (int s = 0; s < nstates; ++s)
-        if (!states[s]) return failf("null state");
-    const int n = aqc_mps_num_qubits(states[0]), device = aqc_mps_device(states[0]);
-    if (n < 1) return failf("a state needs at least 1 qubit");
-    for (int s = 1; s < nstates; ++s)
-        if (aqc_mps_num_qubits(states[s]) != n || aqc_mps_device(states[s]) != device) return failf("MPS states differ in size or device");
-    *n_out = n;
     return 0;
 }
 
@@ -215,7 +179,7 @@ int aqc_mps_sample(aqc_mps* const* states, int nstates, int64_t shots, uint64_t 
     if (const char* msg = mps_sample_check_counts(nstates, shots)) return failf("%s", msg);
     if (!mps_sample_method_ok(method)) return failf("unknown method %d", method);
     Call c;
-    if (check_states(states, nstates, &c.n)) return 1;
+    if (check_states(states, nullptr, nstates, 1, &c.n, &c.device)) return 1;
     c.nstates = nstates;
     c.count = shots;
     c.first_shot = first_shot;
@@ -228,7 +192,7 @@ int aqc_mps_amplitudes(aqc_mps* const* states, int nstates, int64_t count, const
     if (const char* msg = mps_sample_check_counts(nstates, count)) return failf("%s", msg);
     if (!mps_sample_method_ok(method)) return failf("unknown method %d", method);
     Call c;
-    if (check_states(states, nstates, &c.n)) return 1;
+    if (check_states(states, nullptr, nstates, 1, &c.n, &c.device)) return 1;
     const int64_t bad = mps_sample_bad_bit(bits, (size_t)count * c.n);
     if (bad >= 0) return failf("bit string %lld, qubit %lld: a bit is 0 or 1, not %d", (long long)(bad / c.n), (long long)(bad % c.n), (int)bits[bad]);
     c.nstates = nstates;

@@ -34,7 +34,7 @@ enum { kMpsSampleFusedCap = 64, kMpsSampleBlockShots = 64 };
 enum { kMpsSampleByRule = 0, kMpsSampleFused = 1, kMpsSampleGemm = 2 };
 constexpr uint64_t kMpsSampleStream = 16;                       // AQC_SAMPLE_STREAM of include/aqc_hip.h
 constexpr int64_t kMpsSampleMaxShots = (int64_t)1 << 24;        // per call
-constexpr size_t kMpsSampleScratch = (size_t)256 << 20;         // bytes of shots x chi matrices a chunk of the gemm route may take
+constexpr size_t kMpsSampleScratch = kMpsCallBudget;            // bytes of shots x chi matrices a chunk of the gemm route may take
 constexpr int64_t kMpsSampleMaxChunk = (int64_t)1 << 20;        // rows of one zgemm launch
 enum { kMpsSampleGemmMats = 5 };                                // V, W_0, W_1, G_0, G_1
 
@@ -56,7 +56,7 @@ AQC_PHILOX_FN bool mps_sample_weights_ok(double m0, double m1) {
 }
 
 // dims: the n + 1 bond dimensions
-inline int mps_sample_route(int n, const int* dims) { return mps_obs_max_bond(n, dims) <= kMpsSampleFusedCap ? kMpsSampleFused : kMpsSampleGemm; }
+inline int mps_sample_route(int n, const int* dims) { return mps_max_bond(n, dims) <= kMpsSampleFusedCap ? kMpsSampleFused : kMpsSampleGemm; }
 
 // shots walked together by the gemm route: as many as keep the kMpsSampleGemmMats matrices [chunk][max_bond] within the scratch,
 // at least 64, at most what one launch takes and no more than the call has

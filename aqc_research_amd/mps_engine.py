@@ -322,11 +322,10 @@ def compress(states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optio
     with _Lanes(states) as lanes:
         count, n = len(lanes.lanes), lanes.lanes[0].num_qubits
         routes = [method or compress_route(m.bond_dims) for m in lanes.lanes]
-        handles = (c_void_p * count)(*[m.handle for m in lanes.lanes])
         out = (c_void_p * count)()
         ranks, sweeps = np.zeros((count, n - 1), dtype=np.int32), np.zeros((count, n - 1), dtype=np.int32)
         dropped, status = np.zeros((count, n - 1), dtype=np.float64), np.zeros(count, dtype=np.int32)
-        check(_lib.lib().aqc_mps_compress(handles, count, trunc_thr, max_bond, _COMPRESS_METHODS[method], out, iptr(ranks), dptr(dropped),
+        check(_lib.lib().aqc_mps_compress(lanes.handles(), count, trunc_thr, max_bond, _COMPRESS_METHODS[method], out, iptr(ranks), dptr(dropped),
                                           iptr(sweeps), iptr(status)))
         made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
         single = lanes.single

@@ -128,17 +128,24 @@ class _Lanes:
         self.own = []
         return False
 
+    def handles(self):
+        """The lanes as the handle array that the native calls take."""
+        return (c_void_p * len(self.lanes))(*[m.handle for m in self.lanes])
+
+    def check_fused_cap(self, method, cap: int = FUSED_CAP) -> None:
+        """Refuses ``method="fused"`` for a lane beyond the cap, before the native call."""
+        if method == "fused":
+            for m in self.lanes:
+                if int(m.bond_dims.max()) > cap:
+                    raise ValueError(f"the fused route takes bond dimensions up to {cap}, not {int(m.bond_dims.max())}")
+
 
 def _rdms(lanes: _Lanes, arr: np.ndarray, method: Optional[str]) -> np.ndarray:
     if method not in _METHODS:
         raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
-    if method == "fused":
-        for m in lanes.lanes:
-            if int(m.bond_dims.max()) > FUSED_CAP:
-                raise ValueError(f"the fused route takes bond dimensions up to {FUSED_CAP}, not {int(m.bond_dims.max())}")
-    handles = (c_void_p * len(lanes.lanes))(*[m.handle for m in lanes.lanes])
+    lanes.check_fused_cap(method)
     out = np.empty((len(lanes.lanes), arr.shape[0], 4, 4), dtype=np.complex128)
-    check(_lib.lib().aqc_mps_obs_pairs(handles, len(lanes.lanes), arr.shape[0], iptr(arr), _METHODS[method], dptr(out)))
+    check(_lib.lib().aqc_mps_obs_pairs(lanes.handles(), len(lanes.lanes), arr.shape[0], iptr(arr), _METHODS[method], dptr(out)))
     return out[0] if lanes.single else out
 
 

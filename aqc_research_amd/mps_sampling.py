@@ -17,7 +17,7 @@ axis.  Tuples are uploaded for the call and closed afterwards; states are taken 
 ``method``: ``None`` lets the rule choose per state (``"fused"`` -- 64 shots per workgroup walk the whole chain inside one launch on the
 fp64 matrix cores -- when every bond dimension is at most ``FUSED_CAP``, else ``"gemm"``).
 """
-from ctypes import POINTER, c_uint8, c_void_p
+from ctypes import POINTER, c_uint8
 from typing import Optional
 
 import numpy as np
@@ -56,14 +56,6 @@ def _check_method(method) -> None:
         raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
 
 
-def _method(method, lanes: _Lanes) -> int:
-    if method == "fused":
-        for m in lanes.lanes:
-            if int(m.bond_dims.max()) > FUSED_CAP:
-                raise ValueError(f"the fused route takes bond dimensions up to {FUSED_CAP}, not {int(m.bond_dims.max())}")
-    return _METHODS[method]
-
-
 def sample(states, shots: int, *, seed: int, first_shot: int = 0, method: Optional[str] = None, details: bool = False):
     """``shots`` measurements of every state: ``bits``, uint8 of shape ``(shots, n)`` for one state, ``(lanes, shots, n)`` for a list.
     Row s is shot number ``first_shot + s``.  ``details``: a dict of ``bits``, ``amplitudes`` (psi of every sampled string),
@@ -73,13 +65,12 @@ def sample(states, shots: int, *, seed: int, first_shot: int = 0, method: Option
     first_shot = _count(first_shot, "first_shot", 0, 2 ** 64 - 1 - MAX_SHOTS)
     _check_method(method)
     with _Lanes(states) as lanes:
-        how = _method(method, lanes)
+        lanes.check_fused_cap(method, FUSED_CAP)
         count, n = len(lanes.lanes), lanes.lanes[0].num_qubits
-        handles = (c_void_p * count)(*[m.handle for m in lanes.lanes])
         bits = np.empty((count, shots, n), dtype=np.uint8)
         amps = np.empty((count, shots), dtype=np.complex128) if details else None
         norm2 = np.empty(count, dtype=np.float64) if details else None
-        check(_lib.lib().aqc_mps_sample(handles, count, shots, first_shot, seed, how, _u8ptr(bits), dptr(amps) if details else None,
+        check(_lib.lib().aqc_mps_sample(lanes.handles(), count, shots, first_shot, seed, _METHODS[method], _u8ptr(bits), dptr(amps) if details else None,
                                         dptr(norm2) if details else None))
         single = lanes.single
     if not details:
@@ -102,13 +93,12 @@ def amplitudes(states, bits, *, method: Optional[str] = None) -> np.ndarray:
     arr = np.ascontiguousarray(arr, dtype=np.uint8)
     _check_method(method)
     with _Lanes(states) as lanes:
-        how = _method(method, lanes)
+        lanes.check_fused_cap(method, FUSED_CAP)
         count, n = len(lanes.lanes), lanes.lanes[0].num_qubits
         if arr.shape[1] != n:
             raise ValueError(f"the bit strings have {arr.shape[1]} bits, the states {n} qubits")
-        handles = (c_void_p * count)(*[m.handle for m in lanes.lanes])
         out = np.empty((count, arr.shape[0]), dtype=np.complex128)
-        check(_lib.lib().aqc_mps_amplitudes(handles, count, arr.shape[0], _u8ptr(arr), how, dptr(out)))
+        check(_lib.lib().aqc_mps_amplitudes(lanes.handles(), count, arr.shape[0], _u8ptr(arr), _METHODS[method], dptr(out)))
         return out[0] if lanes.single else out
 
 

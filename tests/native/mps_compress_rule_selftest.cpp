@@ -152,10 +152,10 @@ int main() {
         const int small[] = {1, 2, 64, 64, 2, 1}, large[] = {1, 2, 65, 2, 1}, one[] = {1, 1};
         CHECK(mps_compress_route(5, small) == kMpsEntFused && mps_compress_route(4, large) == kMpsEntCanonical && mps_compress_route(1, one) == kMpsEntFused);
         const int dims[] = {1, 2, 3, 2, 1};
-        const std::vector<size_t> so = mps_compress_site_offsets(4, dims), lo = mps_compress_lam_offsets(4, dims);
+        const std::vector<size_t> so = mps_site_offsets(4, dims), lo = mps_compress_lam_offsets(4, dims);
         CHECK(so.size() == 5 && so[0] == 0 && so[1] == 4 && so[2] == 16 && so[3] == 28 && so[4] == 32);
         CHECK(lo.size() == 4 && lo[0] == 0 && lo[1] == 2 && lo[2] == 5 && lo[3] == 7);
-        CHECK(mps_compress_lam_offsets(1, one).size() == 1 && mps_compress_site_offsets(1, one)[1] == 2);
+        CHECK(mps_compress_lam_offsets(1, one).size() == 1 && mps_site_offsets(1, one)[1] == 2);
         const size_t budget = (size_t)256 << 20;
         CHECK(mps_compress_chunk(64, 16, budget) == 16 && mps_compress_chunk(64, 100000, budget) == 512 && mps_compress_chunk(1, 5, 1) == 1);
         CHECK((size_t)mps_compress_chunk(64, 100000, budget) * 8 * 16 * 64 * 64 <= budget);

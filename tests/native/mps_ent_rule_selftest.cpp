@@ -99,7 +99,7 @@ int main() {
     {   // route, offsets, chunks
         static_assert(kMpsEntFusedCap <= 64, "the chain kernel keeps the stacked matrix in four 64-row planes");
         std::vector<int> a = {1, 2, 4, 64, 64, 7, 1}, b = {1, 2, 65, 2, 1}, one = {1, 1};
-        CHECK(mps_ent_route(6, a.data()) == kMpsEntFused && mps_ent_max_bond(6, a.data()) == 64);
+        CHECK(mps_ent_route(6, a.data()) == kMpsEntFused && mps_max_bond(6, a.data()) == 64);
         CHECK(mps_ent_route(4, b.data()) == kMpsEntCanonical && mps_ent_route(1, one.data()) == kMpsEntFused);
         CHECK(mps_ent_method_ok(0) && mps_ent_method_ok(1) && mps_ent_method_ok(2) && !mps_ent_method_ok(3) && !mps_ent_method_ok(-1));
         CHECK(mps_ent_cuts(1) == 0 && mps_ent_cuts(2) == 1 && mps_ent_cuts(40) == 39);

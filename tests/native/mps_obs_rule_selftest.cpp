@@ -88,7 +88,7 @@ int main() {
     {   // the route rule at the cap
         static_assert(kMpsObsFusedCap <= 64, "the fused kernel keeps E in two 64 x 64 complex planes");
         std::vector<int> dims = {1, 2, 4, 64, 64, 7, 1};
-        CHECK(mps_obs_route(6, dims.data()) == kMpsObsFused && mps_obs_max_bond(6, dims.data()) == 64);
+        CHECK(mps_obs_route(6, dims.data()) == kMpsObsFused && mps_max_bond(6, dims.data()) == 64);
         dims[4] = 65;
         CHECK(mps_obs_route(6, dims.data()) == kMpsObsGemm);
         const std::vector<int> ones(14, 1);

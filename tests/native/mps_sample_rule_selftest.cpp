@@ -64,8 +64,8 @@ int main() {
     // route: fused up to the cap, on every bond
     {
         const int a[] = {1, 2, 64, 64, 2, 1}, b[] = {1, 2, 65, 2, 1}, c[] = {1, 1}, d[] = {1, 64, 1, 100, 1};
-        CHECK(mps_sample_route(5, a) == kMpsSampleFused && mps_obs_max_bond(5, a) == 64);
-        CHECK(mps_sample_route(4, b) == kMpsSampleGemm && mps_obs_max_bond(4, b) == 65);
+        CHECK(mps_sample_route(5, a) == kMpsSampleFused && mps_max_bond(5, a) == 64);
+        CHECK(mps_sample_route(4, b) == kMpsSampleGemm && mps_max_bond(4, b) == 65);
         CHECK(mps_sample_route(1, c) == kMpsSampleFused);
         CHECK(mps_sample_route(4, d) == kMpsSampleGemm);
     }
