@@ -97,6 +97,14 @@ SIGNATURES = {
     "aqc_mps_compress_route": (c_int, [c_int, POINTER(c_int32)]),
     "aqc_mps_compress_svd_budget": (c_int64, [c_int64]),
     "aqc_mps_compress": (c_int, [POINTER(_P), c_int, c_double, c_int, c_int, POINTER(_P), POINTER(c_int32), _D, POINTER(c_int32), POINTER(c_int32)]),
+    "aqc_mps_apply_route": (c_int, [c_int, POINTER(c_int32), c_int]),
+    "aqc_mps_apply_svd_budget": (c_int64, [c_int64]),
+    "aqc_mps_apply_plan": (c_int, [c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "aqc_mps_apply_gates": (c_int, [POINTER(_P), c_int, c_int, POINTER(c_int32), POINTER(c_int32), _D, c_int, c_double, c_int, c_int, POINTER(_P),
+                                    POINTER(c_int32), _D, POINTER(c_int32), POINTER(c_int32)]),
+    "aqc_mps_apply_circuit_plan": (c_int, [_P, c_int, POINTER(c_int32)]),
+    "aqc_mps_apply_circuit_many": (c_int, [_P, _D, c_int, c_int, POINTER(_P), c_int, c_int, c_double, c_int, c_int, POINTER(_P), POINTER(c_int32), _D,
+                                           POINTER(c_int32), POINTER(c_int32)]),
     "aqc_svd": (c_int, [c_int, c_int, c_int, _D, _D, _D, _D, POINTER(c_int)]),
     "aqc_svd_batch": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), _D, _D, _D, _D, POINTER(c_int32), POINTER(c_int32)]),
     "aqc_svd_batch_core_ms": (c_double, []),

@@ -491,6 +491,46 @@ struct MpsCompressArgs {
 hipError_t launch_mps_compress_form(const MpsCompressArgs& a, int count, hipStream_t s);    // grid (states of the chunk); q = n - 1: the last site
 hipError_t launch_mps_compress_split(const MpsCompressArgs& a, int count, hipStream_t s);
 
+// aqc_mps_layers.hip (gate layers on MPS states, fused route; rules: aqc_mps_layers_rule.h).  A unit is one evolved state: its working
+// copy lives in the call's flat stores, every unit at the same offsets (sized by the call's bounds), the bond dimensions on the device.
+// Matrix i of a layer is (unit i / gates, gate i % gates); a chunk takes the matrices [first, first + count).
+struct MpsLayersArgs {
+    int n, m;                      // qubits; the side of a matrix of the SVD batch (2 K, K the largest bound)
+    int layer, gates, first;       // the layer, its number of gates, the chunk's first matrix
+    int ngates;                    // folded gates of the whole program (stride of mats and sweeps)
+    const int* gate_q;             // [gates] site of each gate of the layer
+    const int* gate_id;            // [gates] its index in the program
+    const double2* mats;           // [sets][ngates][16] the folded 4 x 4 matrices, row-major on 2 a + b
+    const int* unit_set;           // [units] the set of matrices a unit takes
+    const unsigned long long* table;   // the input states: per unit `per` words, site pointers at at_sites, bond vectors at at_lams, dims at at_dims
+    size_t per, at_sites, at_lams, at_dims;
+    const size_t* site_off;        // [n + 1] element offset of site q in a unit's block of `sites`
+    const size_t* lam_off;         // [n] offset of bond vector q in a unit's block of `lam`
+    const int* bounds;             // [n + 1]
+    size_t site_total, lam_total;
+    double2* sites;                // [units][site_total] sites packed at the current dims
+    double* lam;                   // [units][lam_total]
+    int* dims;                     // [units][n + 1]
+    double* dropped;               // [units][n - 1] total - kept, summed per bond layer by layer
+    int* sweeps;                   // [units][ngates]
+    int* failed;                   // [units] 1 + the layer that failed the unit (0: none): skipped in every later layer
+    int* fail_code;                // [units][n - 1] kMpsLayers* of the gate on bond q that failed the state ...
+    int* fail_layer;               // [units][n - 1] ... and its layer
+    double2* a;                    // [chunk][m][m] theta
+    int* rows;                     // [chunk] <- 2 chi_q (0: the unit has failed, its SVD is skipped)
+    int* cols;                     // [chunk] <- 2 chi_{q+2}
+    const double2* u;              // [chunk][m][m]
+    const double* s;               // [chunk][m]
+    const double2* vh;             // [chunk][m][m]
+    const int* svd_sweeps;
+    const int* svd_status;
+    double trunc_thr;
+    int max_bond;
+};
+hipError_t launch_mps_layer_load(const MpsLayersArgs& a, int units, hipStream_t s);    // grid (units, n)
+hipError_t launch_mps_layer_form(const MpsLayersArgs& a, int count, hipStream_t s);    // grid (matrices of the chunk)
+hipError_t launch_mps_layer_split(const MpsLayersArgs& a, int count, hipStream_t s);
+
 // aqc_api.cpp: thread-local message behind aqc_last_error(); returns 1
 int set_error(const std::string& msg);
 

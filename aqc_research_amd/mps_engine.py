@@ -251,6 +251,10 @@ class DeviceMPS:
         self.version += 1
         return self
 
+    def applied(self, gates, trunc_thr: float = 0.0, max_bond: int = 0, *, method=None, details: bool = False):
+        """A new state: the program ``gates`` applied to this one (``apply_gates`` of this state, which it leaves as it is)."""
+        return apply_gates(self, gates, trunc_thr, max_bond, method=method, details=details)
+
     def close(self) -> None:
         if self.handle:
             self._L.aqc_mps_destroy(self.handle)
@@ -557,6 +561,183 @@ def v_mul_mps(circ, thetas, mps: DeviceMPS, trunc_thr: float = 0.0, max_bond: in
 def v_dagger_mul_mps(circ, thetas, mps: DeviceMPS, trunc_thr: float = 0.0, max_bond: int = 0, method: Optional[str] = None) -> DeviceMPS:
     """V(thetas)^H|mps> on a copy (mps_operations.py:349-371); ``method`` as in ``v_mul_mps``."""
     return _apply(circ, thetas, mps, True, trunc_thr, max_bond, method)
+
+
+# ---- gate layers: whole programs on one or many states per call (aqc_mps_apply_gates / aqc_mps_apply_circuit_many; rules:
+# csrc/aqc_mps_layers_rule.h, kernels: csrc/aqc_mps_layers.hip)
+
+APPLY_FUSED_CAP = 64                                          # AQC_MPS_ENT_FUSED_CAP
+_APPLY_METHODS = {None: 0, "fused": 1, "gatewise": 2}         # AQC_MPS_ENT_BY_RULE, AQC_MPS_ENT_FUSED, AQC_MPS_APPLY_GATEWISE
+_APPLY_ROUTES = {1: "fused", 2: "gatewise"}
+_APPLY_STATUS = {1: "the SVD of the gate reached its sweep limit", 2: "the state is zero or not finite",
+                 3: "a rank passed the static bound of its bond"}
+
+
+def apply_route(bond_dims, max_bond: int = 0) -> str:
+    """The route ``apply_gates`` picks for a state with these n + 1 bond dimensions at this ``max_bond``: ``"fused"`` when no bond can
+    pass ``APPLY_FUSED_CAP`` (``max_bond`` in 1 .. 64, or at most 13 qubits, and no input bond above the cap), else ``"gatewise"``."""
+    d = np.ascontiguousarray(bond_dims, dtype=np.int32)
+    if d.ndim != 1 or d.size < 2 or int(max_bond) < 0:
+        raise ValueError("expects the n + 1 bond dimensions of a state and a non-negative max_bond")
+    r = _lib.lib().aqc_mps_apply_route(d.size - 1, iptr(d), int(max_bond))
+    if r not in _APPLY_ROUTES:
+        raise ValueError("expects the n + 1 bond dimensions of a state and a non-negative max_bond")
+    return _APPLY_ROUTES[r]
+
+
+def _apply_arguments(states, trunc_thr, max_bond, method):
+    """What is refused before anything is uploaded; returns (trunc_thr, max_bond, the bond dimensions that are known already)."""
+    if method not in _APPLY_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'gatewise', not {method!r}")
+    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
+    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
+        raise ValueError("trunc_thr and max_bond must be non-negative")
+    items = [states] if isinstance(states, (DeviceMPS, tuple)) else states
+    shapes = []
+    if isinstance(items, list):
+        for s in items:
+            if isinstance(s, DeviceMPS) and s.handle:
+                shapes.append(s.bond_dims)
+            elif isinstance(s, tuple) and len(s) == 2:
+                shapes.append(_pack(s)[1])
+        if len({d.size for d in shapes}) > 1:
+            raise ValueError("the states differ in the number of qubits")
+        if method == "fused" and any(apply_route(d, max_bond) != "fused" for d in shapes):
+            raise ValueError(f"the fused route takes bond dimensions up to {APPLY_FUSED_CAP}: max_bond in 1 .. {APPLY_FUSED_CAP} or at most 13 qubits, "
+                             f"and no input bond above {APPLY_FUSED_CAP}")
+    return trunc_thr, max_bond
+
+
+def _apply_results(lanes, call, plan, n, method, max_bond, details):
+    """The outputs of one native call of the two entry points, as ``apply_gates`` returns them."""
+    count = len(lanes.lanes)
+    layers, ngates = int(plan[0]), int(plan[1])
+    route = method
+    if route is None:
+        route = "fused" if all(apply_route(m.bond_dims, max_bond) == "fused" for m in lanes.lanes) else "gatewise"
+    out = (c_void_p * count)()
+    ranks, sweeps = np.zeros((count, n + 1), dtype=np.int32), np.zeros((count, max(ngates, 1)), dtype=np.int32)
+    dropped, status = np.zeros(count, dtype=np.float64), np.zeros((count, 3), dtype=np.int32)
+    check(call(lanes.handles(), count, out, iptr(ranks), dptr(dropped), iptr(sweeps), iptr(status)))
+    made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
+    single = lanes.single
+    bad = np.flatnonzero(status[:, 0])
+    if bad.size and not details:
+        lane = int(bad[0])
+        for m in made:
+            if m is not None:
+                m.close()
+        raise RuntimeError(f"lane {lane}, layer {int(status[lane, 1])}, site {int(status[lane, 2])}: {_APPLY_STATUS.get(int(status[lane, 0]), 'failed')}")
+    if not details:
+        return made[0] if single else made
+    info = {"bonds": ranks, "dropped": dropped, "sweeps": sweeps[:, :ngates], "status": status[:, 0].copy(), "failed_at": status[:, 1:].copy()}
+    if single:
+        info = {k: v[0] for k, v in info.items()}
+    info["layers"], info["route"] = layers, route
+    return (made[0] if single else made), info
+
+
+def apply_gates(states, gates, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
+    """New states: the program ``gates`` applied to the given ones, a whole program and one or many states per call.
+
+    ``gates``: a list of ``(matrix, qubit)`` (2 x 2) and ``(matrix, (a, b))`` (4 x 4 on the index 2 bit_a + bit_b; any pair, routed by
+    swaps as ``gate2`` routes it), applied in order.  A matrix may carry a leading axis of length ``len(states)``: the same program with
+    other numbers for every state (then every matrix that is not given per state is shared, and every listing of a state is a lane of
+    its own).  ``states``: a DeviceMPS, a QiskitMPS tuple (uploaded for the call) or a list of those, one qubit count; they are not
+    modified.  Returns a DeviceMPS for one state, a list for a list; ``discarded_weight`` is the input's plus what the splits dropped.
+
+    1-qubit gates are folded into neighbouring 2-qubit gates (exact), the 2-qubit gates are scheduled into layers of gates on disjoint
+    sites, and every split is decided by the engine's rank rule at ``trunc_thr`` / ``max_bond``: the results are those of the loop of
+    ``gate1`` / ``gate2`` calls up to rounding (at ``trunc_thr`` = 0) and up to the order in which gates of one layer meet the rule.
+
+    ``method``: ``None`` lets the rule choose for the call (``apply_route``): ``"fused"`` keeps the working copies on the device and runs
+    a layer for all states at once, the rank decisions included, with one synchronisation per call; ``"gatewise"`` (any bond) runs the
+    engine's gate on a clone, folded gate by folded gate in layer order.  A lane's result does not depend on the other lanes.
+
+    A lane whose state is zero or not finite, or whose SVD reaches its sweep limit, fails alone: without ``details`` that raises
+    ``RuntimeError`` naming lane, layer and site; with ``details`` its entry is ``None`` and the second return value
+    ``{"layers", "bonds", "dropped", "sweeps", "status", "failed_at", "route"}`` tells why."""
+    from .mps_observables import _Lanes
+
+    trunc_thr, max_bond = _apply_arguments(states, trunc_thr, max_bond, method)
+    if not isinstance(gates, (list, tuple)):
+        raise ValueError("gates is a list of (matrix, qubit) and (matrix, (a, b))")
+    count = 1 if isinstance(states, (DeviceMPS, tuple)) else (len(states) if isinstance(states, list) else 0)
+    qubits, kinds, mats, per_state = np.zeros((len(gates), 2), dtype=np.int32), np.zeros(len(gates), dtype=np.int32), [], False
+    for i, item in enumerate(gates):
+        if not (isinstance(item, (list, tuple)) and len(item) == 2):
+            raise ValueError(f"gate {i}: expects (matrix, qubit) or (matrix, (a, b))")
+        m = np.asarray(item[0], dtype=np.complex128)
+        two = not np.isscalar(item[1]) and np.ndim(item[1]) == 1
+        side = 4 if two else 2
+        if m.shape == (count, side, side) and m.ndim == 3:
+            per_state = True
+        elif m.shape != (side, side):
+            raise ValueError(f"gate {i}: expects a {side} x {side} matrix, or one per state")
+        if not np.all(np.isfinite(m)):
+            raise ValueError(f"gate {i}: the matrix is not finite")
+        qs = [int(x) for x in item[1]] if two else [int(item[1]), int(item[1])]
+        if len(qs) != 2 or (two and qs[0] == qs[1]) or min(qs) < 0:
+            raise ValueError(f"gate {i}: invalid qubits")
+        qubits[i], kinds[i] = qs, 2 if two else 1
+        mats.append(m)
+    if per_state:
+        mats = [m if m.ndim == 3 else np.broadcast_to(m, (count,) + m.shape) for m in mats]
+        flat = np.concatenate([m.reshape(count, -1) for m in mats], axis=1) if mats else np.zeros((count, 1), dtype=np.complex128)
+    else:
+        flat = np.concatenate([m.ravel() for m in mats]) if mats else np.zeros(1, dtype=np.complex128)
+    flat = np.ascontiguousarray(flat, dtype=np.complex128)
+    with _Lanes(states) as lanes:
+        n = lanes.lanes[0].num_qubits
+        if len(gates) and int(qubits.max()) >= n:
+            raise ValueError("a qubit is out of range")
+        plan = np.zeros(2, dtype=np.int32)
+        check(_lib.lib().aqc_mps_apply_plan(n, len(gates), iptr(qubits), iptr(kinds), iptr(plan), None, None))
+
+        def call(handles, nstates, out, ranks, dropped, sweeps, status):
+            return _lib.lib().aqc_mps_apply_gates(handles, nstates, len(gates), iptr(qubits), iptr(kinds), dptr(flat), int(per_state), trunc_thr, max_bond,
+                                                  _APPLY_METHODS[method], out, ranks, dropped, sweeps, status)
+
+        return _apply_results(lanes, call, plan, n, method, max_bond, details)
+
+
+def _circuit_many(circ, thetas, states, inverse: bool, trunc_thr, max_bond, method, details):
+    from .mps_observables import _Lanes
+
+    trunc_thr, max_bond = _apply_arguments(states, trunc_thr, max_bond, method)
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    count = 1 if isinstance(states, (DeviceMPS, tuple)) else (len(states) if isinstance(states, list) else 0)
+    if th.shape not in ((circ.num_thetas,), (count, circ.num_thetas)):
+        raise ValueError(f"expected {circ.num_thetas} thetas, or [{count}, {circ.num_thetas}], got an array of shape {th.shape}")
+    if not np.all(np.isfinite(th)):
+        raise ValueError("thetas must be finite")
+    desc, keep = _describe(circ)
+    with _Lanes(states) as lanes:
+        n = lanes.lanes[0].num_qubits
+        if n != circ.num_qubits:
+            raise ValueError("circuit and states differ in the number of qubits")
+        plan = np.zeros(2, dtype=np.int32)
+        check(_lib.lib().aqc_mps_apply_circuit_plan(byref(desc), int(inverse), iptr(plan)))
+
+        def call(handles, nstates, out, ranks, dropped, sweeps, status):
+            return _lib.lib().aqc_mps_apply_circuit_many(byref(desc), dptr(th), circ.num_thetas, int(th.ndim == 2), handles, nstates, int(inverse), trunc_thr,
+                                                         max_bond, _APPLY_METHODS[method], out, ranks, dropped, sweeps, status)
+
+        result = _apply_results(lanes, call, plan, n, method, max_bond, details)
+    del keep
+    return result
+
+
+def v_mul_mps_many(circ, thetas, states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
+    """V(thetas)|state> for one or many states in one call, as ``apply_gates`` applies a program (``v_mul_mps`` of every state up to
+    rounding and the order of a layer's decisions).  ``thetas``: 1-D (shared) or ``[states, num_thetas]``; ``method`` and ``details``
+    as in ``apply_gates``."""
+    return _circuit_many(circ, thetas, states, False, trunc_thr, max_bond, method, details)
+
+
+def v_dagger_mul_mps_many(circ, thetas, states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
+    """V(thetas)^H|state> for one or many states in one call; see ``v_mul_mps_many``."""
+    return _circuit_many(circ, thetas, states, True, trunc_thr, max_bond, method, details)
 
 
 def fast_dot_gradient_mps(circ, thetas, lvec: DeviceMPS, vh_phi: DeviceMPS, *, trunc_thr: float = 0.0, max_bond: int = 0,

@@ -388,6 +388,40 @@ int64_t aqc_mps_compress_svd_budget(int64_t bytes);
 int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int max_bond, int method, aqc_mps** out /* [nstates] */,
                      int32_t* ranks /* [nstates][n-1] */, double* dropped /* [nstates][n-1] */, int32_t* sweeps /* [nstates][n-1] */,
                      int32_t* status /* [nstates] */);
+/* Whole programs of gates on MPS states, layer by layer, one or many states per call (rules: csrc/aqc_mps_layers_rule.h, kernels:
+ * csrc/aqc_mps_layers.hip).  A program is nops ops in order: kinds[i] = 1, a 2 x 2 matrix on qubit qubits[i][0], or kinds[i] = 2, a 4 x 4
+ * matrix (index 2 bit_a + bit_b) on the pair (qubits[i][0], qubits[i][1]), adjacent or not (routed as aqc_mps_gate2 routes it).  mats:
+ * the matrices back to back in the order of the ops (4 or 16 c128 each), once for all states (per_state = 0) or one such set per listed
+ * state (per_state = 1: the same structure, different numbers).  1-qubit ops are folded into neighbouring 2-qubit ops (exact), the
+ * 2-qubit ops are scheduled into layers of gates on disjoint sites as soon as possible, and every layer runs for all states at once.
+ * The states share n >= 1 and the device and are left as they are; out[i] is a NEW state (the caller destroys it) in the engine's gauge,
+ * every split decided by the engine's rank rule at trunc_thr / max_bond (aqc_mps_rank_rule) with the rescaling of a truncating gate.  Its
+ * discarded weight is the input's plus what the splits dropped.  With per_state = 0 a state listed many times is evolved once; with
+ * per_state = 1 every listing is its own lane.  A lane's result does not depend on which other lanes are in the call.
+ * apply_route: AQC_MPS_ENT_FUSED when no bond can pass AQC_MPS_ENT_FUSED_CAP (max_bond in 1 .. 64, or n <= 13, and no input bond above
+ *   the cap; dims may be null): the working copies stay on the device, the rank decisions are made there, the host waits once per call.
+ *   Else AQC_MPS_APPLY_GATEWISE: the engine's 2-qubit gate, folded matrix by folded matrix in layer order, on a clone (-1: invalid argument).
+ * apply_plan: counts[0] = layers, counts[1] = folded 2-qubit gates of the program; gate_sites / gate_layers (may be null): site q and
+ *   layer of every folded gate, in program order.  apply_circuit_plan: the counts of an ansatz.
+ * apply_gates: method AQC_MPS_ENT_BY_RULE (the route of the call by the rule), AQC_MPS_ENT_FUSED (an error where the rule does not allow
+ *   it) or AQC_MPS_APPLY_GATEWISE.  ranks: the n + 1 bond dimensions of every new state (0 for a failed lane); dropped: the weight the
+ *   call dropped per lane; sweeps: of every folded gate's SVD (0 on the gatewise route); status per lane: {code, layer, site} with code
+ *   0 done, 1 an SVD reached its sweep limit, 2 a zero or non-finite state, 3 a rank passed the static bound of its bond (hand-made
+ *   states; never a silent cut) -- such a lane gets a null handle in out and the call still returns 0.  out is nulled before anything
+ *   else can fail.  ranks, dropped, sweeps and status may be null.  Argument errors (a negative or non-finite trunc_thr, a negative
+ *   max_bond, states that differ in size or device, a qubit out of range, a matrix that is not finite, the fused route where the rule
+ *   refuses it) are reported before any device work.
+ * apply_circuit_many: V(thetas) (inverse = 1: its conjugate transpose) of an ansatz on every state; thetas: num_thetas numbers for all
+ *   states (per_state = 0) or [nstates][num_thetas]. */
+#define AQC_MPS_APPLY_GATEWISE 2
+int aqc_mps_apply_route(int n, const int32_t* dims, int max_bond);
+int64_t aqc_mps_apply_svd_budget(int64_t bytes);   /* as aqc_mps_compress_svd_budget, for the stores of a layer's batched SVD */
+int aqc_mps_apply_plan(int n, int nops, const int32_t* qubits /* [nops][2] */, const int32_t* kinds /* [nops] */, int32_t* counts /* [2] */,
+                       int32_t* gate_sites, int32_t* gate_layers);
+int aqc_mps_apply_gates(aqc_mps* const* states, int nstates, int nops, const int32_t* qubits /* [nops][2] */, const int32_t* kinds /* [nops] */,
+                        const double* mats, int per_state, double trunc_thr, int max_bond, int method, aqc_mps** out /* [nstates] */,
+                        int32_t* ranks /* [nstates][n+1] */, double* dropped /* [nstates] */, int32_t* sweeps /* [nstates][gates] */,
+                        int32_t* status /* [nstates][3] */);
 /* ansatz description for the MPS entry points (ParametricCircuit / TrotterAnsatz, parametric_circuit.py:24-70,267-333);
  * unlike aqc_ctx it is not limited to dense-reachable registers.  blocks: int32[2][num_blocks], row 0 = control */
 typedef struct aqc_circuit {
@@ -397,6 +431,10 @@ typedef struct aqc_circuit {
 /* v_mul_mps / v_dagger_mul_mps(circ, thetas, mps, trunc_thr) (mps_operations.py:326-371): the whole ansatz (inverse = 1:
  * its conjugate transpose) applied in place, one call instead of one per gate */
 int aqc_mps_apply_circuit(aqc_mps* mps, const aqc_circuit* circ, const double* thetas, int inverse, double trunc_thr, int max_bond);
+int aqc_mps_apply_circuit_plan(const aqc_circuit* circ, int inverse, int32_t* counts /* [2] */);
+int aqc_mps_apply_circuit_many(const aqc_circuit* circ, const double* thetas, int num_thetas, int per_state, aqc_mps* const* states, int nstates,
+                               int inverse, double trunc_thr, int max_bond, int method, aqc_mps** out, int32_t* ranks, double* dropped,
+                               int32_t* sweeps, int32_t* status);
 /* fast_dot_gradient(circ, thetas, lvec, vh_phi, trunc_thr, block_range, front_layer) (mps_dot_objective.py:41-242):
  * complex gradient (c128[num_thetas]) of <V lvec|phi> from vh_phi = V^H|phi>.  One call walks all gates on device copies
  * of both operands; the ~num_thetas inner products 0.5j<P w|z> reuse cached left / right environments of the pair and
