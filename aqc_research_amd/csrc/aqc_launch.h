@@ -491,6 +491,44 @@ struct MpsCompressArgs {
 hipError_t launch_mps_compress_form(const MpsCompressArgs& a, int count, hipStream_t s);    // grid (states of the chunk); q = n - 1: the last site
 hipError_t launch_mps_compress_split(const MpsCompressArgs& a, int count, hipStream_t s);
 
+// aqc_mps_fromvec.hip (dense vectors into MPS states, fused route; rules: aqc_mps_fromvec_rule.h).  A lane is one vector; the lanes of a
+// chunk share two ping-pong work buffers of 2^n complex numbers per lane; the bond dimensions live on the device.  Every store of a
+// lane of the call is at (first + lane of the chunk) x the per-lane size; the stores of a chunk at the lane of the chunk.
+struct MpsFromVecArgs {
+    int n, q, first, kc;           // qubits; the site; the chunk's first lane; the side of a matrix of the SVD batch (2 x the largest bound)
+    size_t lane_elems, nr;         // 2^n; N_r = 2^(n-1-q), the rows of A_q
+    const double2* src;            // [chunk][2^n] A_q of every lane, [N_r][2 r_q] row-major
+    double2* dst;                  // [chunk][2^n] <- A_{q+1} = Y, [N_r][r_{q+1}] row-major
+    int* bonds;                    // [lanes][n + 1] r_0 = 1, r_{q+1} <- the split of site q, zero from a failed site on
+    int* status;                   // [lanes] kMpsCompress*, set once by the lane's own workgroup
+    int* failed_at;                // [lanes] the site (-1: none)
+    int* sweeps;                   // [lanes][n - 1]
+    double* dropped;               // [lanes][n - 1] total - kept of every cut
+    double2* sites;                // [lanes][site_total] the new site q at site_off[q], packed at the ranks decided
+    double* lam;                   // [lanes][lam_total] the new bond vector q at lam_off[q]
+    const size_t* site_off;        // [n + 1], sized by the bounds of the bonds
+    const size_t* lam_off;         // [n]
+    // partial factors: level 0 reads A_q in blocks of 64 rows, level > 0 the factors of the level before, one factor a block
+    int level, blocks_per_part, max_parts, last;   // last: the level that leaves one factor per lane
+    size_t in_blocks;              // blocks of the level's input (level > 0: the factors of the level before)
+    const double2* fac_in;         // [chunk][max_parts][64 x 64] factor p of a lane packed at p c^2, c = 2 r_q
+    double2* fac_out;
+    double2* a;                    // [chunk][kc][kc] <- R^T in the leading 2 r_q x min(2 r_q, N_r) (the last level)
+    int* rows;                     // [chunk] <- 2 r_q (0: the lane has failed, its SVD is skipped)
+    int* cols;                     // [chunk] <- min(2 r_q, N_r)
+    const double2* u;              // [chunk][kc][kc]
+    const double* s;               // [chunk][kc]
+    const int* svd_sweeps;
+    const int* svd_status;
+    double2* w;                    // [chunk][64 x 32] W = rescale conj(U[:, :r]), 2 r_q x r_{q+1} packed
+    double trunc_thr;
+    int max_bond;
+};
+hipError_t launch_mps_fromvec_qr(const MpsFromVecArgs& a, int parts, int count, hipStream_t s);       // grid (parts, lanes of the chunk)
+hipError_t launch_mps_fromvec_split(const MpsFromVecArgs& a, int count, hipStream_t s);                // grid (lanes of the chunk)
+hipError_t launch_mps_fromvec_project(const MpsFromVecArgs& a, int count, hipStream_t s);              // grid (row groups, lanes of the chunk)
+hipError_t launch_mps_fromvec_last(const MpsFromVecArgs& a, int count, hipStream_t s);                 // grid (lanes of the chunk); q = n - 1
+
 // aqc_mps_layers.hip (gate layers on MPS states, fused route; rules: aqc_mps_layers_rule.h).  A unit is one evolved state: its working
 // copy lives in the call's flat stores, every unit at the same offsets (sized by the call's bounds), the bond dimensions on the device.
 // Matrix i of a layer is (unit i / gates, gate i % gates); a chunk takes the matrices [first, first + count).

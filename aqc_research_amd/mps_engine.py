@@ -135,6 +135,13 @@ class DeviceMPS:
                for q in range(num_qubits)]
         return cls.from_qiskit((gam, [np.ones(1) for _ in range(num_qubits - 1)]), device)
 
+    @classmethod
+    def from_vector(cls, vec, trunc_thr: float = 0.0, max_bond: int = 0, *, device: Optional[int] = None, method=None, details: bool = False):
+        """The MPS of one dense vector of 2^n amplitudes (index bit q is site q), every bond truncated: ``from_vectors`` of this vector."""
+        if np.ndim(vec) != 1:
+            raise ValueError("expects one vector of 2^n amplitudes")
+        return from_vectors(np.asarray(vec), trunc_thr, max_bond, device=device, method=method, details=details)
+
     def clone(self) -> "DeviceMPS":
         h = c_void_p()
         check(self._L.aqc_mps_clone(self.handle, byref(h)))
@@ -738,6 +745,111 @@ def v_mul_mps_many(circ, thetas, states, trunc_thr: float = 0.0, max_bond: int =
 def v_dagger_mul_mps_many(circ, thetas, states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
     """V(thetas)^H|state> for one or many states in one call; see ``v_mul_mps_many``."""
     return _circuit_many(circ, thetas, states, True, trunc_thr, max_bond, method, details)
+
+
+# ---- dense vectors into MPS states (aqc_mps_from_vec; rules: csrc/aqc_mps_fromvec_rule.h, kernels: csrc/aqc_mps_fromvec.hip)
+
+FROM_VECTOR_FUSED_CAP = 32                                    # AQC_MPS_FROM_VEC_CAP
+_FROM_VECTOR_METHODS = {None: 0, "fused": 1, "host": 2}       # AQC_MPS_FROM_VEC_*
+_FROM_VECTOR_ROUTES = {1: "fused", 2: "host"}
+
+
+def from_vector_route(num_qubits: int, max_bond: int = 0) -> str:
+    """The route ``from_vectors`` picks: ``"fused"`` for 2 .. 30 qubits when no bond can pass ``FROM_VECTOR_FUSED_CAP`` (``max_bond`` in
+    1 .. 32, or at most 11 qubits), else ``"host"``."""
+    r = _lib.lib().aqc_mps_from_vec_route(int(num_qubits), int(max_bond))
+    if r not in _FROM_VECTOR_ROUTES:
+        raise ValueError("expects a positive number of qubits and a non-negative max_bond")
+    return _FROM_VECTOR_ROUTES[r]
+
+
+def _from_vectors_arguments(vecs, trunc_thr, max_bond, method):
+    """What is refused before any device call; returns (lanes x 2^n array, single, n, trunc_thr, max_bond, route)."""
+    if method not in _FROM_VECTOR_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'host', not {method!r}")
+    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
+    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
+        raise ValueError("trunc_thr and max_bond must be non-negative")
+    if isinstance(vecs, (list, tuple)):
+        rows = [np.asarray(v) for v in vecs]
+        if not rows or any(v.ndim != 1 for v in rows):
+            raise ValueError("expects a vector of 2^n amplitudes, an array [lanes][2^n] or a list of vectors")
+        if len({v.size for v in rows}) > 1:
+            raise ValueError("the vectors differ in size")
+        single, arr = False, np.stack(rows)
+    else:
+        arr = np.asarray(vecs)
+        if arr.ndim not in (1, 2) or arr.size == 0:
+            raise ValueError("expects a vector of 2^n amplitudes, an array [lanes][2^n] or a list of vectors")
+        single, arr = arr.ndim == 1, np.atleast_2d(arr)
+    if arr.dtype.kind not in "fciu":
+        raise ValueError("expects numbers")
+    size = int(arr.shape[1])
+    n = size.bit_length() - 1
+    if size != 1 << n or n < 2:
+        raise ValueError(f"a vector holds 2^n amplitudes, n >= 2; got {size}")
+    arr = np.array(arr, dtype=np.complex128, order="C")   # a copy: the inputs stay untouched
+    route = method or from_vector_route(n, max_bond)
+    if method == "fused" and from_vector_route(n, max_bond) != "fused":
+        raise ValueError(f"the fused route takes 2 .. 30 qubits and bonds up to {FROM_VECTOR_FUSED_CAP}: max_bond in 1 .. {FROM_VECTOR_FUSED_CAP} "
+                         f"or at most 11 qubits")
+    return arr, single, n, trunc_thr, max_bond, route
+
+
+def from_vectors(vecs, trunc_thr: float = 0.0, max_bond: int = 0, *, device: Optional[int] = None, method: Optional[str] = None,
+                 details: bool = False):
+    """New states from dense vectors: ``vecs`` is one vector of 2^n complex amplitudes (index bit q is site q), an array ``[lanes][2^n]``
+    or a list of vectors of one size; any norm; they are not modified.  Returns a DeviceMPS for a 1-D input, else a list, in the
+    engine's gauge as ``compress`` returns them: every bond cut left to right by the engine's rank rule at ``trunc_thr`` / ``max_bond``
+    with the rescaling of a truncating gate, ``discarded_weight`` what the cuts dropped (fused route; ``details["dropped"]`` on both).
+
+    ``method``: ``None`` lets the rule choose (``from_vector_route``).  ``"fused"`` keeps the remainder of every vector on the device: per
+    site R-only Householder factors of its tall-skinny matrix, the SVD of R^T, the rank decision and the projection on the matrix
+    cores, all lanes together, one synchronisation per call.  ``"host"`` is ``mps_operations.vector_to_canonical_mps`` (a loop of LAPACK
+    SVDs) and an upload, vector by vector.  A lane's result does not depend on the other lanes.
+
+    A vector that is zero or not finite, or whose SVD reaches its sweep limit, fails alone: without ``details`` that raises
+    ``RuntimeError`` naming the lane and the site; with ``details`` its entry is ``None`` and the second return value
+    ``{"route", "bonds", "dropped", "sweeps", "status", "failed_at", "parts"}`` tells why."""
+    arr, single, n, trunc_thr, max_bond, route = _from_vectors_arguments(vecs, trunc_thr, max_bond, method)
+    lanes = arr.shape[0]
+    dev = _default_device() if device is None else int(device)
+    bonds, sweeps = np.zeros((lanes, n + 1), dtype=np.int32), np.zeros((lanes, n - 1), dtype=np.int32)
+    dropped, status = np.zeros((lanes, n - 1), dtype=np.float64), np.zeros(lanes, dtype=np.int32)
+    failed_at, parts = np.full(lanes, -1, dtype=np.int32), np.ones(n - 1, dtype=np.int32)
+    if route == "fused":
+        out = (c_void_p * lanes)()
+        check(_lib.lib().aqc_mps_from_vec(dev, n, lanes, dptr(arr), trunc_thr, max_bond, _FROM_VECTOR_METHODS[method], out, iptr(bonds), dptr(dropped),
+                                          iptr(sweeps), iptr(status), iptr(failed_at), iptr(parts)))
+        made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
+    else:
+        from .mps_operations import _canonical_sweep
+
+        made = []
+        for i in range(lanes):
+            if not np.all(np.isfinite(arr[i])) or not np.any(arr[i]):
+                status[i], failed_at[i] = 2, 0
+                bonds[i, 0] = 1
+                made.append(None)
+                continue
+            gam, lam, weights = _canonical_sweep(arr[i], trunc_thr, max_bond)
+            made.append(DeviceMPS.from_qiskit((gam, lam), dev, assume_canonical=True))
+            bonds[i] = [1] + [v.size for v in lam] + [1]
+            dropped[i] = weights
+    bad = np.flatnonzero(status)
+    if bad.size and not details:
+        lane = int(bad[0])
+        for m in made:
+            if m is not None:
+                m.close()
+        raise RuntimeError(f"lane {lane}, site {int(failed_at[lane])}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
+    if not details:
+        return made[0] if single else made
+    info = {"bonds": bonds, "dropped": dropped, "sweeps": sweeps, "status": status, "failed_at": failed_at}
+    if single:
+        info = {k: v[0] for k, v in info.items()}
+    info["route"], info["parts"] = route, parts
+    return (made[0] if single else made), info
 
 
 def fast_dot_gradient_mps(circ, thetas, lvec: DeviceMPS, vh_phi: DeviceMPS, *, trunc_thr: float = 0.0, max_bond: int = 0,

@@ -144,19 +144,25 @@ def _svd(a: np.ndarray):
         return scipy.linalg.svd(a, full_matrices=False, lapack_driver="gesvd")
 
 
-def vector_to_canonical_mps(vec: np.ndarray, trunc_thr: float = _NO_TRUNCATION_THR) -> QiskitMPS:
+def vector_to_canonical_mps(vec: np.ndarray, trunc_thr: float = _NO_TRUNCATION_THR, max_bond: int = 0) -> QiskitMPS:
     """Canonical Vidal form (Gamma, lambda) of a dense state by successive SVDs -- the form Aer hands the reference
     (mps_operations.py:216-243) -- truncated by the native engine's stated rule (aqc_mps_engine.cpp, gate_adjacent), so that a
     ``DenseBackedMPS`` and the engine's own result describe the same state: at every bond, Schmidt values descending, those not
     above 1e-14 of the largest go; then, for ``trunc_thr`` > 0, the smallest ones go while the sum of their squares stays
     strictly below ``trunc_thr`` (an absolute weight, at least one value stays); the kept values are scaled by
-    sqrt(total / kept), so the tensors keep the norm of ``vec`` (normalised or not)."""
+    sqrt(total / kept), so the tensors keep the norm of ``vec`` (normalised or not).  ``max_bond`` > 0 caps every bond between the
+    floor and the tail, as the engine's rule does.  The host route of ``mps_engine.from_vectors``."""
+    return _canonical_sweep(vec, trunc_thr, max_bond)[:2]
+
+
+def _canonical_sweep(vec: np.ndarray, trunc_thr: float, max_bond: int = 0):
+    """``vector_to_canonical_mps`` with the weight every cut dropped (total - kept) as a third result."""
     vec = np.asarray(vec, dtype=np.complex128).ravel()
     n = int(round(np.log2(vec.size)))
     if vec.size != 1 << n or n < 2:
         raise ValueError("expects a vector of size 2^n, n >= 2")
     rest = vec.reshape([2] * n).transpose(list(range(n - 1, -1, -1))).reshape(1, -1)   # axes (b_0, ..., b_{n-1})
-    gam, lam, prev = [], [], np.ones(1)
+    gam, lam, prev, weights = [], [], np.ones(1), []
     for _ in range(n - 1):
         chi_l = rest.shape[0]
         u, sv, vh = _svd(rest.reshape(chi_l * 2, -1))
@@ -165,6 +171,8 @@ def vector_to_canonical_mps(vec: np.ndarray, trunc_thr: float = _NO_TRUNCATION_T
             total += s * s
             if s > 1e-14 * sv[0]:
                 keep = j + 1
+        if max_bond > 0:
+            keep = min(keep, int(max_bond))
         if trunc_thr > 0.0:
             while keep > 1 and dropped + sv[keep - 1] ** 2 < trunc_thr:
                 dropped += sv[keep - 1] ** 2
@@ -175,11 +183,12 @@ def vector_to_canonical_mps(vec: np.ndarray, trunc_thr: float = _NO_TRUNCATION_T
         a = u.reshape(chi_l, 2, keep)
         gam.append((np.ascontiguousarray(a[:, 0, :] / prev[:, None]), np.ascontiguousarray(a[:, 1, :] / prev[:, None])))
         lam.append(sv.copy())
+        weights.append(total - kept)
         prev = sv
         rest = sv[:, None] * vh
     a = rest.reshape(rest.shape[0], 2, 1)
     gam.append((np.ascontiguousarray(a[:, 0, :] / prev[:, None]), np.ascontiguousarray(a[:, 1, :] / prev[:, None])))
-    return gam, lam
+    return gam, lam, weights
 
 
 class DenseBackedMPS(tuple):

@@ -388,6 +388,33 @@ int64_t aqc_mps_compress_svd_budget(int64_t bytes);
 int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int max_bond, int method, aqc_mps** out /* [nstates] */,
                      int32_t* ranks /* [nstates][n-1] */, double* dropped /* [nstates][n-1] */, int32_t* sweeps /* [nstates][n-1] */,
                      int32_t* status /* [nstates] */);
+/* Dense vectors into MPS states: one or many vectors of 2^n c128 amplitudes (index bit q is site q, any norm, left as they are) per call
+ * (rules: csrc/aqc_mps_fromvec_rule.h, kernels: csrc/aqc_mps_fromvec.hip).  out[i] is a NEW state (the caller destroys it) in the engine's
+ * gauge, as aqc_mps_compress returns it: every bond cut left to right by the engine's rank rule at trunc_thr / max_bond
+ * (aqc_mps_rank_rule) with the rescaling of a truncating gate; its discarded weight is what the cuts dropped.  A lane's result does not
+ * depend on which other vectors are in the call.
+ * from_vec_route: host only, needs no device.  AQC_MPS_FROM_VEC_FUSED when 2 <= n <= 30 and every bond bound min(2^b, 2^(n-b), max_bond
+ *   if > 0) is at most AQC_MPS_FROM_VEC_CAP (max_bond in 1 .. 32, or n <= 11): the remainder stays on the device, R-only Householder
+ *   factors of its tall-skinny matrix, the SVD of R^T, the rank decision and the projection per site, one synchronisation per call.
+ *   Else AQC_MPS_FROM_VEC_HOST: the caller's loop of LAPACK SVDs (mps_operations.vector_to_canonical_mps) (-1: invalid argument).
+ * from_vec_budget: bytes the two ping-pong work buffers (2 x lanes x 2^n x 16) may take (default 8 GiB): the lanes of a call go in chunks
+ *   that fit; one lane that does not fit is an error that names the size.  Sets it (bytes <= 0: the default) and returns the earlier
+ *   value; results do not depend on it.
+ * from_vec: method AQC_MPS_FROM_VEC_BY_RULE or _FUSED (an error where the rule answers _HOST: that route is the caller's).  bonds: the
+ *   n + 1 bond dimensions of every new state, 0 from the site on at which a lane failed; dropped: the weight each cut dropped; sweeps: of
+ *   the site's SVD; status per lane: 0 converted, 1 an SVD reached its sweep limit, 2 a zero or non-finite spectrum -- such a lane gets
+ *   a null handle in out, failed_at names its site (else -1), and the call still returns 0.  parts: the partial R factors of every
+ *   site, a function of n alone.  out is nulled before anything else can fail.  bonds, dropped, sweeps, status, failed_at and parts may
+ *   be null.  Argument errors are reported before any device work and before anything is allocated. */
+#define AQC_MPS_FROM_VEC_BY_RULE 0
+#define AQC_MPS_FROM_VEC_FUSED 1
+#define AQC_MPS_FROM_VEC_HOST 2
+#define AQC_MPS_FROM_VEC_CAP 32
+int aqc_mps_from_vec_route(int n, int max_bond);
+int64_t aqc_mps_from_vec_budget(int64_t bytes);
+int aqc_mps_from_vec(int device, int n, int lanes, const double* vecs /* [lanes][2^n] c128 */, double trunc_thr, int max_bond, int method,
+                     aqc_mps** out /* [lanes] */, int32_t* bonds /* [lanes][n+1] */, double* dropped /* [lanes][n-1] */,
+                     int32_t* sweeps /* [lanes][n-1] */, int32_t* status /* [lanes] */, int32_t* failed_at /* [lanes] */, int32_t* parts /* [n-1] */);
 /* Whole programs of gates on MPS states, layer by layer, one or many states per call (rules: csrc/aqc_mps_layers_rule.h, kernels:
  * csrc/aqc_mps_layers.hip).  A program is nops ops in order: kinds[i] = 1, a 2 x 2 matrix on qubit qubits[i][0], or kinds[i] = 2, a 4 x 4
  * matrix (index 2 bit_a + bit_b) on the pair (qubits[i][0], qubits[i][1]), adjacent or not (routed as aqc_mps_gate2 routes it).  mats:
