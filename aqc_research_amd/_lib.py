@@ -158,6 +158,7 @@ SIGNATURES = {
     "aqc_ws_switch": (c_int, [_P, c_char_p, POINTER(c_int64)]),
     "aqc_ws_plan_skips": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int]),
     "aqc_ws_sweep_r_only_sub": (c_int, [_P]),
+    "aqc_ws_virtual_backwalk": (c_int, [_P]),
     "aqc_ws_plan_info": (c_int, [_P, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "aqc_ws_kernel_family": (c_int, [_P, c_int]),
     "aqc_ws_plan_substages": (c_int, [_P, c_int]),

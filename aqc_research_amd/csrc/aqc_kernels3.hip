@@ -745,7 +745,7 @@ __global__ __launch_bounds__(SweepShape<K>::kWaves * 64, K >= 12 ? 1 : 2) void s
     sweep_mfma_body<K, LIST, SKIPW, RLAST, BACK>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 // The sweep's pair (see apply_pair_kernel): the real plan's first stage on the lhs tiles with the virtual plan's stage on the virtual
-// register.  Each member keeps its own item list, partial-R slots and form (RLAST_A / RLAST_B; BACK_A: A walks backwards); a workgroup walks its contiguous
+// register (plans whose virtual stage is swept forwards: where it walks back inside the Y_0 launch, projected_virtual_backwalk, the real walk is launched alone).  Each member keeps its own item list, partial-R slots and form (RLAST_A / RLAST_B; BACK_A: A walks backwards); a workgroup walks its contiguous
 // share of A and then of B.  The change of list is the plain one -- A's last stores, a barrier, B's first operands; carrying B's
 // prefetch through A's last item (as apply_mfma_body<K, true, true> does) has not been built here: this kernel runs one wave per SIMD
 // with every architectural register taken, and the prefetch registers are the first sub-stage's operands in a per-stage layout.
@@ -1013,7 +1013,7 @@ __global__ __launch_bounds__(64 * WAVES) void rgrad_kernel(const DevSub3* subs, 
     if (si >= nsubs_run) {   // a sub-stage of the second plan of the launch (projected route: the virtual plan's walk rides along)
         si -= nsubs_run;
         subs = second.subs; grps = second.grps; rpart = second.rpart; ntiles = second.nparts; nsubs_total = second.nsubs_total;
-        tiles_per_lane = second.nparts; chunk = 0; sparse_subs = second.nsubs_total; lane_parts = second.lane_parts; conj_sub = -1; umat = second.umat;
+        tiles_per_lane = second.nparts; chunk = 0; sparse_subs = second.nsubs_total; lane_parts = second.lane_parts; conj_sub = second.conj_sub; umat = second.umat;
     }
     RG_STAMP(0);
     const DevSub3 sub = subs[si];
@@ -1447,6 +1447,7 @@ hipError_t launch_rgrad(const DevSub3* subs, const DevGrp* grps, int entangler, 
     if (nsubs_run < 0 || nsubs_run > nsubs_total) nsubs_run = nsubs_total;
     RgradSecond second;
     memset(&second, 0, sizeof second);
+    second.conj_sub = -1;
     if (second_plan) second = *second_plan;
     const int extra = (gather.count > 0 && gather.buf ? 1 : 0) + second.count;
     if (nsubs_run + extra < 1) return hipSuccess;

@@ -161,12 +161,13 @@ struct GatherJob {           // optional passenger of the gradient walk: out[lan
     const void* buf; size_t lane_stride; const long long* elem; int count; void* out; void* mirror;
 };
 struct RgradSecond {         // a second plan whose gradient walk rides in the same launch (projected route: the virtual sweep plan); all of its
-    const DevSub3* subs;     // sub-stages hold lane_parts[lane] partials (item-list launches), none is R-only
+    const DevSub3* subs;     // sub-stages hold lane_parts[lane] partials (item-list launches)
     const DevGrp* grps;
     const double2* rpart;
     const int* lane_parts;
     const double* umat;
     int nparts, nsubs_total, count;   // partial slots per (lane, sub-stage); sub-stages of the plan; how many of them walk here (0: none)
+    int conj_sub;            // the plan's sub-stage whose R arrives as Z W^H of its INPUTS (the virtual stage walked backwards: aqc_backwalk.h), or -1
 };
 hipError_t launch_rgrad(const DevSub3* subs, const DevGrp* grps, int entangler, const double* thetas, int T, const void* rpart,
                         int ntiles, int nsubs_total, void* partial, int nslots, int from, int to, int front, int batch, hipStream_t s,

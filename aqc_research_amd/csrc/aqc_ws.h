@@ -268,6 +268,7 @@ struct aqc_ws {
     aqc::ListKey z_key;                     // what the tiles of a partial Z were chosen for
     aqc::ProjRoute proj;                    // dense stages of the sparse route on a virtual register
     bool proj_y0_ready = false;             // the virtual z (proj.vy) holds Y_0 for the sweep that follows in the same call (run_vdag_projected)
+    bool proj_vr_ready = false;             // ... and the virtual plan's partial-R rows hold this call's R: that launch walked the virtual stage back (projected_virtual_backwalk)
     bool z_from_y = false;                  // a partial Z without a checkpoint: completed by a full V^H from Y (thetas and Y unchanged since)
     std::vector<long long> h_gather;        // host copy of the registered gather indices (elements)
     aqc::ListKey projb_key;                 // what the verdict below was taken for
@@ -383,7 +384,8 @@ bool projected_backwalk(const aqc_ws* ws);   // objective by projection: the swe
 Stage3Args virtual_stage3_args(aqc_ws* ws, const DevPlan& v, size_t s);   // stage s of a virtual plan (vsw, vinv) on the virtual register, over its item list
 Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s);   // arguments of stage s of the virtual sweep plan
 int run_projected_stages(aqc_ws* ws);       // projection + the virtual stage launches (after the sweep's first stage)
-aqc::RgradSecond projected_rgrad_plan(aqc_ws* ws);   // the virtual plan's gradient walk, to ride in the real plan's launch
+bool projected_virtual_backwalk(const aqc_ws* ws);   // ... and the virtual stage walks back from (M_end, Y_end) inside the launch that leaves Y_0 (run_vdag_projected)
+aqc::RgradSecond projected_rgrad_plan(aqc_ws* ws, bool walked_back);   // the virtual plan's gradient walk, to ride in the real plan's launch (walked_back: its R rows come from the backward walk)
 bool vdag_route_projected(aqc_ws* ws, int x_buf);   // the objective's V^H by two passes over y instead of its stages (host-known single basis state)
 int run_vdag_projected(aqc_ws* ws, int x_buf);      // Y -> Z on the lhs tiles, the virtual z for the sweep that follows
 int proj_fix_amplitudes(aqc_ws* ws, int x_buf);     // after the gather: the amplitudes outside the lhs tiles, from the virtual z

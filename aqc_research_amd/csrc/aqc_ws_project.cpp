@@ -242,7 +242,9 @@ Stage3Args projected_sweep_stage(aqc_ws* ws, size_t s) {
 
 // Objective by projection: its six tile launches are three pairs of independent launches over disjoint buffers (psi with M_end, V^H's
 // last stage with Y_0 -- Y_0 alone where the sweep walks backwards, projected_backwalk --, the sweep's first stage with the virtual stage), and each pair runs as ONE launch (launch_apply3_pair /
-// launch_sweep3_pair) when the virtual plan has a single stage of the real plans' tile size (unless switched off).
+// launch_sweep3_pair) when the virtual plan has a single stage of the real plans' tile size (unless switched off).  Where the virtual
+// stage walks backwards too (projected_virtual_backwalk) the third pair dissolves: its virtual member has become the Y_0 launch, and
+// the sweep's first stage -- the real walk back -- is launched alone.  psi with M_end stays a pair.
 static bool plan_has_pairs(const aqc_ws* ws) {   // the plans allow them: one virtual stage of the real plans' tile size
     const ProjRoute& pr = ws->proj;
     return pr.ok && pr.vsw.h_stages.size() == 1 && pr.vinv.h_stages.size() == 1 && ws->sweep.k == pr.kv && ws->inv.k == pr.kv;
@@ -269,8 +271,38 @@ bool projected_backwalk(const aqc_ws* ws) {
 // are on: there the stage is not launched and the walk writes the tile.
 bool backwalk_keeps_vdag_stage(const aqc_ws* ws) { return projected_backwalk(ws) && plan_has_pairs(ws) && ws->sw.projected_pairs == 0; }
 
+// ... and the VIRTUAL register is walked once as well.  The launch that takes Y_end down to Y_0 through the mirrored virtual plan starts
+// from the states the forward virtual stage would end in -- (w, z) = (M_end, Y_end), both in HBM by then (vme, vy) -- so it is that
+// stage's backward walk: the same body forms every R of the virtual plan from its sub-stage's inputs on the way down and leaves Y_0 in
+// place; its w ends as the 0/1 pattern M_0, which nobody reads.  No virtual stage is launched behind the real walk then.  Static per
+// workspace: the real member walks back, the virtual plans have ONE stage each (the gradient walk conjugates one sub-stage per plan) of
+// at least two sub-stages, they mirror each other sub-stage by sub-stage, and the virtual tile size has the form.
+bool projected_virtual_backwalk(const aqc_ws* ws) {
+    const DevPlan& v = ws->proj.vsw;
+    const DevPlan& vi = ws->proj.vinv;
+    return projected_backwalk(ws) && v.v3 && vi.v3 && v.h_stages.size() == 1 && vi.h_stages.size() == 1 && vi.k == v.k && v.k == ws->proj.kv && backwalk_tile(ws->proj.kv) &&
+           vi.h_subs3.size() == v.h_subs3.size() && v.h_stages[0].nsubs >= 2 && vi.h_stages[0].nsubs == v.h_stages[0].nsubs &&
+           vi.h_stages[0].sub_begin + vi.h_stages[0].nsubs == (int)vi.h_subs3.size();
+}
+// Single launches (AQC_PROJECTED_PAIRS=0 on a plan that has pairs), as for the real member: the plain Y_0 launch stays and writes Y_0,
+// the walk is a launch of its own kind (K_SWEEP_VIRTUAL) in front of it -- the apply overwrites Y_end in place -- and stores nothing.
+static bool virtual_backwalk_keeps_y0_launch(const aqc_ws* ws) { return projected_virtual_backwalk(ws) && backwalk_keeps_vdag_stage(ws); }
+
+// The virtual stage walked back from (M_end, Y_end): the mirrored virtual plan's stage on (vme, vy), every R to the row of the forward
+// sub-stage it mirrors in the virtual sweep plan's partial-R buffer (aqc_backwalk.h), z = Y_0 in place unless a plain launch writes it.
+static Stage3Args virtual_backwalk_stage(aqc_ws* ws, bool store_y0) {
+    const ProjRoute& pr = ws->proj;
+    Stage3Args a = virtual_stage3_args(ws, pr.vinv, 0);
+    a.in0 = pr.vme; a.in1 = pr.vy; a.out0 = nullptr; a.out1 = pr.vy;
+    a.store_out = store_y0 ? 2 : 0;
+    a.backwalk = 1;
+    stage3_sweep_fields(a, pr.vinv, a.ntiles, 0);   // (the first sub-stage's operand offsets: the persistent 2^12 form reads them)
+    a.rpart = pr.vsw.d_rpart;
+    return a;
+}
+
 // the gradient entries of the virtual plan's gate groups: its walk rides in the launch of the real plan's (which stops after its first stage)
-RgradSecond projected_rgrad_plan(aqc_ws* ws) {
+RgradSecond projected_rgrad_plan(aqc_ws* ws, bool walked_back) {
     ProjRoute& pr = ws->proj;
     DevPlan& v = pr.vsw;
     RgradSecond r;
@@ -278,6 +310,8 @@ RgradSecond projected_rgrad_plan(aqc_ws* ws) {
     r.subs = v.d_subs3; r.grps = v.d_grps; r.rpart = v.d_rpart; r.lane_parts = pr.d_lane_parts; r.umat = v.d_umat;
     r.nparts = 2 * pr.ntiles_v;
     r.nsubs_total = r.count = (int)v.h_subs3.size();
+    // walked back: the R of the mirrored stage's first sub-stage -- the forward stage's last -- arrives in the "inputs" form (aqc_backwalk.h)
+    r.conj_sub = walked_back ? backwalk_conj_sub(r.nsubs_total, pr.vinv.h_stages[0].sub_begin) : -1;
     return r;
 }
 
@@ -291,7 +325,8 @@ RgradSecond projected_rgrad_plan(aqc_ws* ws) {
 // then V^H's last stage on the lhs tile alone (Z there), the sweep's first stage as ever, the virtual stages from (M_0, Y_0), and
 // <g|V^H y> = sum_c Y_0[(c, g on T n F), c] for the gather indices outside the tile.
 // Where projected_backwalk holds, V^H's last stage and the sweep's first stage are ONE launch: the sweep walks back from (psi, C), writes
-// the Z tile on its way and enqueues the gather itself.
+// the Z tile on its way and enqueues the gather itself.  Where projected_virtual_backwalk holds as well, the launch Y_end -> Y_0 here is
+// the virtual stage's walk back from (M_end, Y_end): it leaves the virtual plan's R, and the sweep launches no virtual stage.
 bool vdag_route_projected(aqc_ws* ws, int x_buf) {
     ProjRoute& pr = ws->proj;
     if (!pr.ok || !ws->sw.projected_vdag || ws->capturing || (long long)ws->lane_elems * ws->batch < ws->sw.projected_vdag_min_elems) return false;
@@ -389,7 +424,15 @@ int run_vdag_projected(aqc_ws* ws, int x_buf) {   // for a route eval_route has 
         ProfScope ps(ws, AQC_K_PROJECT);
         HIP_OK(launch_project(q, ws->stream));
     }
-    if ((!pairs || back) && enqueue_couple(ws, iv.k, nullptr, &y0)) return 1;          // Y_0
+    // Y_0.  projected_virtual_backwalk: the launch that leaves it is the virtual stage's walk back from (M_end, Y_end) -- still ONE launch
+    // of the kind of the plain one, the same U^H products on Y_end, and the virtual plan's R on the way.  Single launches keep the
+    // plain launch behind a walk that stores nothing (the apply overwrites Y_end in place, so the walk goes first).
+    const bool vback = projected_virtual_backwalk(ws), keep_y0 = virtual_backwalk_keeps_y0_launch(ws);
+    if (vback) {
+        ProfScope ps(ws, keep_y0 ? AQC_K_SWEEP_VIRTUAL : AQC_K_APPLY_VIRTUAL);
+        HIP_OK(launch_sweep3(pr.kv, ws->stream, virtual_backwalk_stage(ws, !keep_y0), ws->sw));
+    }
+    if ((!pairs || back) && (!vback || keep_y0) && enqueue_couple(ws, iv.k, nullptr, &y0)) return 1;
     if ((!back || backwalk_keeps_vdag_stage(ws)) && enqueue_couple(ws, iv.k, &last, pairs && !back ? &y0 : nullptr)) return 1;   // V^H's last stage (pairs: with Y_0)
     vdag_projected_state_after(ws, x_buf);
     return 0;

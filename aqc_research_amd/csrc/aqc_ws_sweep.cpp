@@ -22,7 +22,7 @@ using namespace aqc;
 namespace aqc {
 
 // ---- bookkeeping: what the buffers hold ------------------------------------------------------------------------------
-// Every field of the record (ckpt_valid, z_full, z_key, z_from_y, w_clean, proj_y0_ready, the lhs supports, the list keys, the
+// Every field of the record (ckpt_valid, z_full, z_key, z_from_y, w_clean, proj_y0_ready, proj_vr_ready, the lhs supports, the list keys, the
 // theta state) is assigned in this section alone; the rest of the library calls these transitions.
 
 void thetas_changed(aqc_ws* ws, double* d_thetas) {
@@ -31,7 +31,7 @@ void thetas_changed(aqc_ws* ws, double* d_thetas) {
     ws->fwd.u_level = ws->inv.u_level = ws->sweep.u_level = kUNone;
     ws->ckpt_valid = false;   // ZW (and Z) belong to the previous thetas
     ws->z_from_y = false;
-    ws->proj_y0_ready = false;
+    ws->proj_y0_ready = ws->proj_vr_ready = false;
 }
 
 // family 3: ensure_umat has built the unitaries of `p` up to `level` (the V^H and sweep plans share one launch); a level never drops here
@@ -50,7 +50,7 @@ static void touch_buf(aqc_ws* ws, int buf) {
     ws->combo_valid[buf] = false;
     if (buf == AQC_BUF_Z || buf == AQC_BUF_ZW) ws->ckpt_valid = false;
     if (buf == AQC_BUF_Y || buf == AQC_BUF_Z) ws->z_from_y = false;
-    ws->proj_y0_ready = false;
+    ws->proj_y0_ready = ws->proj_vr_ready = false;
     if (buf == AQC_BUF_Z) ws->z_full = true;
     if (buf == AQC_BUF_W) ws->w_clean = false;
 }
@@ -305,6 +305,7 @@ void vdag_projected_state_after(aqc_ws* ws, int x_buf) {
     ws->ckpt_valid = false;     // ZW holds the lhs tiles of the checkpoint only
     ws->z_from_y = true;
     ws->proj_y0_ready = true;   // the virtual z holds Y_0 for the sweep of the same call
+    ws->proj_vr_ready = projected_virtual_backwalk(ws);   // ... and the launch that left it has formed the virtual plan's R on its way
 }
 // support_in_gather_set: the lhs state is picked among the registered gather indices (surrogate objective: |state_0> and the
 // leading flip state) -- the gather set alone names the tiles, and the list only changes when that set does
@@ -422,7 +423,7 @@ static int sweep_sparse_prepare(aqc_ws* ws) {
 }
 static void sweep_state_after(aqc_ws* ws, bool sparse) {   // host-side state a sweep leaves (also after a graph replay)
     umat_state_after(ws, ws->sweep, sweep_route_projected(ws, sparse) ? route_level(ws) : kUAll);
-    ws->proj_y0_ready = false;                 // (consumed by the projected stages)
+    ws->proj_y0_ready = ws->proj_vr_ready = false;   // (consumed by the projected stages / the gradient walk)
     if (!sparse) {
         ws->w_clean = false;
         ws->ckpt_valid = false;                // the dense route works in place on (W, ZW)
@@ -544,7 +545,10 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
         if (ensure_umat(ws, ws->inv, kURoute)) return 1;
         r_only_sub = backwalk_conj_sub(nsubs, ws->inv.h_stages.back().sub_begin);
     }
-    bool pair_virtual = projected && ws->proj_y0_ready && projected_pairs(ws);   // the first stage and the virtual stage as one launch
+    // ... and that launch of run_vdag_projected has walked the virtual stage back from (M_end, Y_end) as well (projected_virtual_backwalk):
+    // the virtual plan's R rows are there, no virtual stage is launched here, and the real walk goes alone
+    const bool virtual_walked = backwalk && ws->proj_vr_ready;
+    bool pair_virtual = !virtual_walked && projected && ws->proj_y0_ready && projected_pairs(ws);   // the first stage and the virtual stage as one launch
 #ifdef AQC_TUNING
     if (ws->sw.stamps) pair_virtual = false;
 #endif
@@ -608,11 +612,11 @@ static int sweep_mfma(aqc_ws* ws, const EvalRoute& route, int block_from, int bl
     // the backward walk has written Z on the lhs tiles and Y_0 is still on the virtual register (several virtual stages work in place
     // on it): the call's gather, which reads both, goes here
     if (backwalk && route.gather && !route.gather_rides && proj_fix_amplitudes(ws, x_buf)) return 1;
-    if (projected && !pair_virtual && run_projected_stages(ws)) return 1;
+    if (projected && !pair_virtual && !virtual_walked && run_projected_stages(ws)) return 1;
     sweep_state_after(ws, sparse);
     ProfScope ps(ws, AQC_K_FINALIZE);
     RgradSecond vwalk;   // projected route: the virtual plan's walk in the same launch (two launches: 54 + 54 us at the headline, one: ~70)
-    if (projected) vwalk = projected_rgrad_plan(ws);
+    if (projected) vwalk = projected_rgrad_plan(ws, virtual_walked);
     HIP_OK(launch_rgrad(p.d_subs3, p.d_grps, prog.entangler, ws->d_thetas, prog.num_thetas(), p.d_rpart, p.ntiles, nsubs, ws->d_partial,
                         ws->nslots, block_from, block_to, front_layer ? 1 : 0, ws->batch, ws->stream,
                         ws->grads_direct ? ws->d_slot_theta : nullptr, ws->d_grads, ws->mirror_grads,
@@ -684,6 +688,7 @@ int aqc_ws_apply(aqc_ws* ws, int inverse, int src_buf, int dst_buf) {
 }
 
 int aqc_ws_sweep_r_only_sub(aqc_ws* ws) { return ws ? sweep_r_only_sub(ws) : -1; }
+int aqc_ws_virtual_backwalk(aqc_ws* ws) { return ws && projected_virtual_backwalk(ws) ? 1 : 0; }
 
 int aqc_ws_grad(aqc_ws* ws, int block_from, int block_to, int front_layer) {
     return aqc_ws_grad_from(ws, AQC_BUF_X, block_from, block_to, front_layer);

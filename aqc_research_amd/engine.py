@@ -495,6 +495,10 @@ class Workspace:
         """Index (over all stages) of the sweep's sub-stage that is taken from its inputs alone (R-only), or -1."""
         return int(self._L.aqc_ws_sweep_r_only_sub(self.handle))
 
+    def virtual_backwalk(self) -> int:
+        """1 when an objective by projection walks its virtual stage back from (M_end, Y_end) in the launch that leaves Y_0, else 0."""
+        return int(self._L.aqc_ws_virtual_backwalk(self.handle))
+
     def sparse_counts(self) -> Tuple[int, int, int]:
         """Items of the last sparse evaluation: (sweep first stage, tiles cleared in W, V^H last stage); -1 = never built."""
         c = (c_int64 * 3)()

@@ -601,6 +601,9 @@ int aqc_ws_plan_skips(aqc_ws* ws, int which, int stage, int* out, int max_subs);
 /* index (over all stages) of the sweep's sub-stage that is taken from its inputs alone -- the last one of the last stage,
  * R = U (Z W^H) U^H: a third of a sub-stage's matrix work -- or -1 when the sweep runs it like the others */
 int aqc_ws_sweep_r_only_sub(aqc_ws* ws);
+/* 1 when an objective by projection walks its virtual stage BACK from (M_end, Y_end) inside the launch that leaves Y_0 -- one walk over
+ * the virtual tiles instead of two, every R of the virtual plan from its sub-stage's inputs --, 0 when that stage is swept forwards */
+int aqc_ws_virtual_backwalk(aqc_ws* ws);
 /* item lists of the last sparse evaluation (synchronises): counts[0] first-stage items of the sweep, [1] tiles it cleared in W,
  * [2] last-stage items of V^H; -1 where that list has never been built */
 int aqc_ws_sparse_counts(aqc_ws* ws, int64_t* counts);
