@@ -1,15 +1,20 @@
 // The skeleton of a call that reads single-lane MPS states (aqc_mps_obs_api.cpp, aqc_mps_sample_api.cpp, aqc_mps_pauli_api.cpp,
 // aqc_mps_ent_api.cpp, aqc_mps_compress_api.cpp, aqc_mps_layers_api.cpp): check the handles, view the distinct states, pack what the kernels read
 // of them into one table, launch on the first state's stream, synchronise once, assemble.  Each of those files keeps its own plan,
-// launches and results; what they share about their input states is here and in the HIP-free aqc_mps_states_rule.h.  Private to
-// csrc/ (everything has internal linkage).
+// launches and results; what they share about their input states is here and in the HIP-free aqc_mps_states_rule.h.  The second
+// half holds the host scaffolding of a truncating sweep (aqc_mps_compress_api.cpp, aqc_mps_layers_api.cpp, aqc_mps_fromvec_api.cpp;
+// DESIGN.md 6w, "Sweep calls"): the argument checks, the chunk budget, the stores of a chunk of the batched SVD (those also in aqc_mps_ent_api.cpp),
+// flat stores sized by static bounds, and the adoption of the new states from them; the device side of the cut is aqc_mps_cut.h.
+// Private to csrc/ (everything has internal linkage).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "aqc_devbuf.h"
+#include "aqc_mps_compress_rule.h"
 #include "aqc_mps_host.h"
 #include "aqc_mps_states_rule.h"
 
@@ -147,6 +152,99 @@ struct NormEnvs { DevBuf<double2> l, r, tmp; };
         *m = nullptr;
     }
     return rc;
+}
+
+// ======== sweep calls: compression, gate layers, conversion of dense vectors (and, for its SVDs alone, the Schmidt spectra).  A sweep
+// forms a matrix per lane, runs launch_svd_batch over a chunk of lanes and cuts (aqc_mps_cut.h on the device); the new states are
+// adopted from flat stores after the call's one synchronisation.
+
+// ---- check: what every truncating call refuses, in one order; out[] is nulled first: whatever follows, the caller finds null or a
+// state it owns.  what: "state" or "vector"; method_ok: the call's own verdict on its method number
+[[maybe_unused]] int check_truncating_call(const void* in, aqc_mps** out, int count, double trunc_thr, int max_bond, const char* what, bool method_ok,
+                                           int method) {
+    if (!in || !out) return failf("null argument");
+    if (count < 1) return failf("at least one %s is needed", what);
+    for (int i = 0; i < count; ++i) out[i] = nullptr;
+    if (!method_ok) return failf("unknown method %d", method);
+    if (!(trunc_thr >= 0.0) || !std::isfinite(trunc_thr)) return failf("trunc_thr must be a non-negative number");
+    if (max_bond < 0) return failf("max_bond must be non-negative");
+    return 0;
+}
+
+// ---- budget: the bytes a call sizes its chunks by, behind the *_budget entry points (tests lower it to run many chunks on few lanes):
+// bytes > 0 sets it, else the default comes back; returns the value before
+[[maybe_unused]] int64_t swap_budget(std::atomic<size_t>& budget, int64_t bytes, size_t dflt) {
+    return (int64_t)budget.exchange(bytes > 0 ? (size_t)bytes : dflt);
+}
+
+// ---- the stores of one chunk of the batched SVD of m x n matrices (m >= n): a, u [chunk][m][n], s [chunk][n], vh [chunk][n][n], the
+// work stores of aqc_svd_batch.hip, and per matrix rows | cols | sweeps | status in one block.  results = false: s, sweeps and status
+// are the caller's, for the whole call (aqc_mps_ent_api.cpp), and go to the second launch()
+struct SvdChunk {
+    int chunk = 0, m = 0, n = 0;
+    DevBuf<double2> a, u, vh, work, vmat;
+    DevBuf<double> s;
+    DevBuf<int> ints;
+    int alloc(int chunk_, int m_, int n_, bool results = true) {
+        chunk = chunk_; m = m_; n = n_;
+        const size_t c = (size_t)chunk, mat = (size_t)m * n;
+        return a.alloc(c * mat) || u.alloc(c * mat) || vh.alloc(c * n * n) || work.alloc(svd_batch_work_elems(chunk, m, n)) ||
+               vmat.alloc(svd_batch_v_elems(chunk, m, n)) || ints.alloc((results ? 4 : 2) * c) || (results && s.alloc(c * n));
+    }
+    int* rows() const { return ints; }
+    int* cols() const { return ints + chunk; }
+    int* sweeps() const { return ints + 2 * (size_t)chunk; }
+    int* status() const { return ints + 3 * (size_t)chunk; }
+    hipError_t launch(int count, double* d_s, int* d_sweeps, int* d_status, hipStream_t st) const {
+        return launch_svd_batch(count, m, n, rows(), cols(), a, u, d_s, vh, d_sweeps, d_status, work, vmat, st);
+    }
+    hipError_t launch(int count, hipStream_t st) const { return launch(count, s, sweeps(), status(), st); }
+};
+
+// ---- adopt: a new engine state from site tensors and bond vectors that the sweep left in flat device stores, site q at
+// site_base + site_off[q], bond vector q at lam_base + lam_off[q]
+[[maybe_unused]] int adopt_flat(int device, int n, const int* dims, const double2* site_base, const size_t* site_off, const double* lam_base,
+                                const size_t* lam_off, double discarded, aqc_mps** out) {
+    std::vector<const void*> sites(n);
+    std::vector<const double*> lams(std::max(n - 1, 1), nullptr);
+    for (int q = 0; q < n; ++q) {
+        sites[q] = site_base + site_off[q];
+        if (q < n - 1) lams[q] = lam_base + lam_off[q];
+    }
+    return mps_adopt(device, n, dims, sites.data(), lams.data(), discarded, out);
+}
+
+// ---- flat stores sized by static bounds of the bonds, every lane at the same offsets (gate layers, dense vectors; compression sizes
+// its stores per state): site_off (n + 1 entries) | lam_off (n entries) on the device in one upload
+struct BoundedStores {
+    std::vector<size_t> site_off, lam_off;
+    size_t site_total = 0, lam_total = 1;
+    DevBuf<double2> sites;
+    DevBuf<double> lam;
+    DevBuf<size_t> off;
+    int alloc(int n, const int* bounds, size_t lanes) {
+        site_off = mps_site_offsets(n, bounds);
+        lam_off = mps_compress_lam_offsets(n, bounds);
+        site_total = site_off[n];
+        lam_total = std::max<size_t>(lam_off[n - 1], 1);
+        std::vector<size_t> both(site_off);
+        both.insert(both.end(), lam_off.begin(), lam_off.end());
+        return off.upload(both) || sites.alloc(lanes * site_total) || lam.alloc(lanes * lam_total);
+    }
+    const size_t* d_site_off() const { return off; }
+    const size_t* d_lam_off() const { return off + site_off.size(); }
+    double2* site(size_t lane, int q) const { return sites + lane * site_total + site_off[q]; }
+    int adopt(int device, int n, size_t lane, const int* dims, double discarded, aqc_mps** out) const {
+        return adopt_flat(device, n, dims, sites + lane * site_total, site_off.data(), lam + lane * lam_total, lam_off.data(), discarded, out);
+    }
+};
+
+// ---- a failed call gives back every state it has made
+[[maybe_unused]] void drop_outputs(aqc_mps** out, int count) {
+    for (int i = 0; i < count; ++i) {
+        if (out[i]) (void)aqc_mps_destroy(out[i]);
+        out[i] = nullptr;
+    }
 }
 
 // ---- the end of the launches: the one synchronisation of the call, before any buffer goes, also after a failure (rc != 0)

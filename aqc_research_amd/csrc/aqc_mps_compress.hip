@@ -6,50 +6,24 @@
 //                              B_s = M_s D_{q+1}^T with the factor streamed transposed, written as rows s r_q .. of the state's matrix of the
 //                              SVD batch, rows[i] = 2 r_q, cols[i] = chi_{q+1}: r_q is read from the ranks the split before has written;
 //   launch_svd_batch           (aqc_svd_batch.hip) over the states of the chunk;
-//   mps_compress_split_kernel  thread 0 takes the decision of the cut (mps_compress_decide, the host's text); the new site, packed at the
-//                              ranks just decided, the bond vector, rank, dropped weight and sweeps; the new carry
+//   mps_compress_split_kernel  the cut by the steps of aqc_mps_cut.h (thread 0 takes mps_compress_decide, the host's text; the bond vector;
+//                              the new site, packed at the ranks just decided); rank, dropped weight and sweeps; the new carry
 //                              W_{q+1} = rescale (U_0^H M_0 + U_1^H M_1) on the matrix cores, M back in the planes, U streamed.
 // The form kernel of q = n - 1 writes the last site instead of B.  One workgroup per state in every launch; a state whose SVD gave a
 // status, or whose spectrum is zero or not finite, gets its status written by its own workgroup and is skipped from then on (rows = 0:
 // the SVD kernel leaves at once).  No atomics, every sum in a fixed order, no loop bound depends on data other than bond dimensions
-// and ranks, nothing is read from or written to another state's stores.
+// and ranks, nothing is read from or written to another state's stores.  planes_zero, plane_load, acc_to_mem and the grant of the
+// planes' dynamic LDS: aqc_mps_planes.h.
 #include <hip/hip_runtime.h>
 
 #include "aqc_launch.h"
 #include "aqc_mps_compress_rule.h"
+#include "aqc_mps_cut.h"
 #include "aqc_mps_planes.h"
 
 namespace aqc {
 
 static_assert((int)kMpsEntFusedCap == (int)kMpsObsFusedCap, "the planes of aqc_mps_planes.h are sized by the observables' cap");
-
-namespace {
-
-// the planes zeroed, then a packed rows x cols matrix (rows, cols <= kCap) into the pair (pr, pi); the caller synchronises after
-__device__ __forceinline__ void planes_zero(double* smem) {
-    for (int e = threadIdx.x; e < 4 * kPlane; e += 256) smem[e] = 0.0;
-}
-__device__ __forceinline__ void plane_load(const cplx* __restrict__ src, int rows, int cols, double* pr, double* pi) {
-    for (int e = threadIdx.x; e < rows * cols; e += 256) {
-        const cplx x = src[e];
-        const int i = e / cols, c = e - i * cols;
-        pr[i * kLd + c] = x.x;
-        pi[i * kLd + c] = x.y;
-    }
-}
-// the wave's part of acc, rows below m and columns below nn, times f into dst with leading dimension ld
-__device__ __forceinline__ void acc_to_mem(const Acc& acc, cplx* __restrict__ dst, int ld, int m, int nn, double f) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = 16 * wave + 4 * r + lk, j = 16 * t + li;
-            if (i < m && j < nn) dst[(size_t)i * ld + j] = make_double2(f * acc.re[t][r], f * acc.im[t][r]);
-        }
-}
-
-}  // namespace
 
 // grid (states of the chunk); 256 threads; dynamic LDS kFusedLds
 __global__ __launch_bounds__(256) void mps_compress_form_kernel(MpsCompressArgs a) {
@@ -95,8 +69,8 @@ __global__ __launch_bounds__(256) void mps_compress_form_kernel(MpsCompressArgs 
         }
         return;
     }
-    acc_to_mem(p0, m, chi, r, chi, 1.0);
-    acc_to_mem(p1, m + (size_t)r * chi, chi, r, chi, 1.0);
+    acc_to_mem(p0, m, chi, r, chi);
+    acc_to_mem(p1, m + (size_t)r * chi, chi, r, chi);
     __syncthreads();   // every wave is done reading the carry
     acc_store(p0, fr, fi, r, chi);
     acc_store(p1, er, ei, r, chi);
@@ -105,8 +79,8 @@ __global__ __launch_bounds__(256) void mps_compress_form_kernel(MpsCompressArgs 
     prod_lds_mem<true>(fr, fi, D, r, chi, chi, p0);   // B_s[i][j] = sum_k M_s[i][k] D[j][k]
     prod_lds_mem<true>(er, ei, D, r, chi, chi, p1);
     cplx* B = a.a + (size_t)item * 2 * a.k * a.k;     // 2 r <= 2 k rows, chi <= k columns
-    acc_to_mem(p0, B, a.k, r, chi, 1.0);
-    acc_to_mem(p1, B + (size_t)r * a.k, a.k, r, chi, 1.0);
+    acc_to_mem(p0, B, a.k, r, chi);
+    acc_to_mem(p1, B + (size_t)r * a.k, a.k, r, chi);
     if (tid == 0) { a.rows[item] = 2 * r; a.cols[item] = chi; }
 }
 
@@ -126,23 +100,13 @@ __global__ __launch_bounds__(256) void mps_compress_split_kernel(MpsCompressArgs
     const int chi = st.in.dims[q + 1], r = q > 0 ? st.ranks[q - 1] : 1;
     const int count = 2 * r < chi ? 2 * r : chi;   // <= kCap
     const double* s = a.s + (size_t)item * a.k;
-    if (tid == 0) {
-        MpsCompressDecision d = {0, 0, 0.0, 0.0, 0.0, 1.0};
-        if (svd_status == 0) d = mps_compress_decide(count, s, a.trunc_thr, a.max_bond);
-        dec = d;
-    }
-    __syncthreads();   // (every thread has read the status before thread 0 writes it)
-    const MpsCompressDecision d = dec;
+    const MpsCompressDecision d = cut_decide(svd_status, count, s, a.trunc_thr, a.max_bond, &dec);
     if (!d.ok) {
-        if (tid == 0) st.status[0] = svd_status == 1 ? kMpsCompressSweepLimit : kMpsCompressNonFinite;
+        if (tid == 0) st.status[0] = cut_failure(svd_status);
         return;
     }
     const int rk = d.rank;   // 1 .. count
-    if (tid < rk) {
-        const double v = d.rescale * s[tid];
-        lam[tid] = v;
-        st.out_lam[st.lam_off[q] + tid] = v;
-    }
+    cut_bond(d, s, lam, st.out_lam + st.lam_off[q]);
     if (tid == 0) { st.ranks[q] = rk; st.dropped[q] = d.total - d.kept; st.sweeps[q] = a.svd_sweeps[item]; }
     planes_zero(cmp_smem);
     __syncthreads();
@@ -150,16 +114,7 @@ __global__ __launch_bounds__(256) void mps_compress_split_kernel(MpsCompressArgs
     const cplx* m = a.m + (size_t)item * 2 * kCap * kCap;
     plane_load(m, r, chi, fr, fi);
     plane_load(m + (size_t)r * chi, r, chi, er, ei);
-    {   // T'_q[s][l][j] = U[(s, l), j] lambda'_q[j] / lambda'_{q-1}[l], packed [2][r][rk]
-        cplx* out = st.out_sites + st.site_off[q];
-        const double* lam_left = q > 0 ? st.out_lam + st.lam_off[q - 1] : nullptr;
-        for (int e = tid; e < 2 * r * rk; e += 256) {
-            const int row = e / rk, j = e - row * rk, l = row < r ? row : row - r;
-            const double f = mps_compress_site_factor(lam[j], lam_left ? lam_left[l] : 1.0);
-            const cplx x = u[(size_t)row * a.k + j];
-            out[e] = make_double2(f * x.x, f * x.y);
-        }
-    }
+    cut_left_site(u, a.k, r, rk, lam, q > 0 ? st.out_lam + st.lam_off[q - 1] : nullptr, st.out_sites + st.site_off[q]);
     __syncthreads();
     // W_{q+1} = rescale (U_0^H M_0 + U_1^H M_1): U_s is [r][k] in memory, every one of its k columns is taken (zero beyond count)
     Acc w0, w1;
@@ -171,23 +126,11 @@ __global__ __launch_bounds__(256) void mps_compress_split_kernel(MpsCompressArgs
 }
 
 namespace {
-hipError_t compress_attributes() {
-    static bool attr_set[64] = {};   // per device: hipFuncSetAttribute applies to the current one
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;   // unknown device: set, remember nothing
-    if (dev < 0 || !attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mps_compress_form_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(mps_compress_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    return hipSuccess;
-}
+constexpr auto grant_planes = grant_dynamic_lds<kFusedLds, mps_compress_form_kernel, mps_compress_split_kernel>;
 }  // namespace
 
 hipError_t launch_mps_compress_form(const MpsCompressArgs& a, int count, hipStream_t s) {
-    hipError_t e = compress_attributes();
+    const hipError_t e = grant_planes();
     if (e != hipSuccess) return e;
     if (count <= 0) return hipSuccess;
     mps_compress_form_kernel<<<count, 256, kFusedLds, s>>>(a);
@@ -195,7 +138,7 @@ hipError_t launch_mps_compress_form(const MpsCompressArgs& a, int count, hipStre
 }
 
 hipError_t launch_mps_compress_split(const MpsCompressArgs& a, int count, hipStream_t s) {
-    hipError_t e = compress_attributes();
+    const hipError_t e = grant_planes();
     if (e != hipSuccess) return e;
     if (count <= 0) return hipSuccess;
     mps_compress_split_kernel<<<count, 256, kFusedLds, s>>>(a);

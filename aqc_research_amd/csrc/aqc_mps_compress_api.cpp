@@ -38,9 +38,10 @@ struct Call {
     MpsTable table;                        // per fused state: site pointers | factor offsets | site offsets | bond offsets | dims
     DevBuf<MpsEntState> d_in;
     DevBuf<MpsCompressState> d_states;
-    DevBuf<double2> d_factors, d_sites, d_carry, d_m, d_a, d_u, d_vh, d_work, d_vmat;
-    DevBuf<double> d_lam, d_dropped, d_s;
-    DevBuf<int> d_results, d_ints;         // per fused state: ranks | sweeps | status; per state of a chunk: rows | cols | sweeps | status
+    DevBuf<double2> d_factors, d_sites, d_carry, d_m;
+    DevBuf<double> d_lam, d_dropped;
+    DevBuf<int> d_results;                 // per fused state: ranks | sweeps | status
+    SvdChunk svd;                          // of 2 k x k matrices, one per state of a chunk
     std::vector<int> h_results;
     std::vector<double> h_dropped;
 };
@@ -63,12 +64,9 @@ int run_fused(Call& c, const std::vector<int>& fused, hipStream_t st) {
         for (size_t q = 1; q < n; ++q) lam_total += (size_t)v.dims[q];
     }
     const int K = c.k, chunk = mps_compress_chunk(K, fused.size(), g_svd_budget.load());
-    const size_t mat = (size_t)2 * K * K;
     if (c.table.upload() || c.d_factors.alloc(std::max<size_t>(fac_total, 1)) || c.d_sites.alloc(site_total) ||
         c.d_lam.alloc(std::max<size_t>(lam_total, 1)) || c.d_results.alloc(res * fused.size()) || c.d_dropped.alloc(cuts * fused.size()) ||
-        c.d_carry.alloc((size_t)chunk * kPlaneElems) || c.d_m.alloc((size_t)chunk * 2 * kPlaneElems) || c.d_ints.alloc((size_t)4 * chunk) ||
-        c.d_s.alloc((size_t)chunk * K) || c.d_a.alloc(chunk * mat) || c.d_u.alloc(chunk * mat) || c.d_vh.alloc((size_t)chunk * K * K) ||
-        c.d_work.alloc(svd_batch_work_elems(chunk, 2 * K, K)) || c.d_vmat.alloc(svd_batch_v_elems(chunk, 2 * K, K))) return 1;
+        c.d_carry.alloc((size_t)chunk * kPlaneElems) || c.d_m.alloc((size_t)chunk * 2 * kPlaneElems) || c.svd.alloc(chunk, 2 * K, K)) return 1;
     std::vector<MpsEntState> hin(fused.size());
     std::vector<MpsCompressState> hs(fused.size());
     for (size_t i = 0; i < fused.size(); ++i) {
@@ -94,17 +92,13 @@ int run_fused(Call& c, const std::vector<int>& fused, hipStream_t st) {
         MpsEntChainArgs a{c.n, c.d_in + s0, 1};
         HIP_OK(launch_mps_ent_chain_right(a, (int)std::min<size_t>(kMaxGridY, fused.size() - s0), st));
     }
-    int* d_rows = c.d_ints;
-    int* d_cols = d_rows + chunk;
-    int* d_sweeps = d_cols + chunk;
-    int* d_status = d_sweeps + chunk;
     for (size_t first = 0; first < fused.size(); first += chunk) {   // the chunks share the step's stores: one stream orders them
         const int count = (int)std::min<size_t>(chunk, fused.size() - first);
-        MpsCompressArgs a{c.n, 0, K, (int)first, c.d_states, c.d_carry, c.d_m, c.d_a, d_rows, d_cols, c.d_u, c.d_s, d_sweeps, d_status, c.trunc_thr, c.max_bond};
+        MpsCompressArgs a{c.n, 0, K, (int)first, c.d_states, c.d_carry, c.d_m, c.svd.a, c.svd.rows(), c.svd.cols(), c.svd.u, c.svd.s, c.svd.sweeps(), c.svd.status(), c.trunc_thr, c.max_bond};
         for (int q = 0; q + 1 < c.n; ++q) {
             a.q = q;
             HIP_OK(launch_mps_compress_form(a, count, st));
-            HIP_OK(launch_svd_batch(count, 2 * K, K, d_rows, d_cols, c.d_a, c.d_u, c.d_s, c.d_vh, d_sweeps, d_status, c.d_work, c.d_vmat, st));
+            HIP_OK(c.svd.launch(count, st));
             HIP_OK(launch_mps_compress_split(a, count, st));
         }
         a.q = c.n - 1;
@@ -123,13 +117,7 @@ int adopt_fused(const Call& c, const MpsView& v, const StateWork& w, int device,
     std::vector<int> dims(n + 1, 1);
     double discarded = aqc_mps_discarded_weight(v.h);
     for (int q = 1; q < n; ++q) { dims[q] = w.ranks[q - 1]; discarded += w.dropped[q - 1]; }
-    std::vector<const void*> sites(n);
-    std::vector<const double*> lams(std::max(n - 1, 1), nullptr);
-    for (int q = 0; q < n; ++q) {
-        sites[q] = c.d_sites + w.site_at + w.site_off[q];
-        if (q < n - 1) lams[q] = c.d_lam + w.lam_at + w.lam_off[q];
-    }
-    return mps_adopt(device, n, dims.data(), sites.data(), lams.data(), discarded, out);
+    return adopt_flat(device, n, dims.data(), c.d_sites + w.site_at, w.site_off.data(), c.d_lam + w.lam_at, w.lam_off.data(), discarded, out);
 }
 
 // canonical route: on a clone, the identity sweeps of the engine, then its truncating sweep left to right.  The engine reports an SVD at
@@ -155,11 +143,9 @@ int run_canonical(const Call& c, const MpsView& v, StateWork& w) {
     return 0;
 }
 
+// a failed call: the outputs and the canonical route's clones that no lane has taken
 void drop_outputs(Call& c, aqc_mps** out, int nstates) {
-    for (int i = 0; i < nstates; ++i) {
-        if (out[i]) (void)aqc_mps_destroy(out[i]);
-        out[i] = nullptr;
-    }
+    drop_outputs(out, nstates);
     for (StateWork& w : c.states) {
         if (w.made) (void)aqc_mps_destroy(w.made);
         w.made = nullptr;
@@ -178,18 +164,12 @@ int aqc_mps_compress_route(int n, const int32_t* dims) {
 }
 
 int64_t aqc_mps_compress_svd_budget(int64_t bytes) {
-    const size_t before = g_svd_budget.exchange(bytes > 0 ? (size_t)bytes : kMpsCallBudget);
-    return (int64_t)before;
+    return swap_budget(g_svd_budget, bytes, kMpsCallBudget);
 }
 
 int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int max_bond, int method, aqc_mps** out, int32_t* ranks,
                      double* dropped, int32_t* sweeps, int32_t* status) {
-    if (!states || !out) return failf("null argument");
-    if (nstates < 1) return failf("at least one state is needed");
-    for (int i = 0; i < nstates; ++i) out[i] = nullptr;   // whatever follows, the caller finds null or a state it owns
-    if (!mps_ent_method_ok(method)) return failf("unknown method %d", method);
-    if (!(trunc_thr >= 0.0) || !std::isfinite(trunc_thr)) return failf("trunc_thr must be a non-negative number");
-    if (max_bond < 0) return failf("max_bond must be non-negative");
+    if (check_truncating_call(states, out, nstates, trunc_thr, max_bond, "state", mps_ent_method_ok(method), method)) return 1;
     int n = 0, device = 0;
     if (check_states(states, nullptr, nstates, 1, &n, &device)) return 1;
     Call c;

@@ -72,6 +72,12 @@ AQC_CMP_HD inline MpsCompressDecision mps_compress_decide(int count, const doubl
 }
 // the factor of U[(s, l), j] in T'_q[s][l][j]
 AQC_CMP_HD inline double mps_compress_site_factor(double lam_new_j, double lam_left_l) { return lam_new_j / lam_left_l; }
+// element e of T'_q packed [2][r][rk]: row (s, l) = s r + l of U, kept column j, left index l
+struct MpsCompressSiteIndex { int row, j, l; };
+AQC_CMP_HD inline MpsCompressSiteIndex mps_compress_site_index(int e, int r, int rk) {
+    const int row = e / rk, j = e - row * rk, l = row < r ? row : row - r;
+    return {row, j, l};
+}
 
 #undef AQC_CMP_HD
 
@@ -94,9 +100,10 @@ inline MpsCompressStep mps_compress_step(int rows, int cols, const std::complex<
     out.lam.resize(r);
     for (int j = 0; j < r; ++j) out.lam[j] = out.d.rescale * s[j];
     out.site.resize((size_t)rows * r);
-    for (int i = 0; i < rows; ++i)
-        for (int j = 0; j < r; ++j)
-            out.site[(size_t)i * r + j] = u[(size_t)i * ldu + j] * mps_compress_site_factor(out.lam[j], lam_left ? lam_left[i % rq] : 1.0);
+    for (int e = 0; e < rows * r; ++e) {
+        const MpsCompressSiteIndex at = mps_compress_site_index(e, rq, r);
+        out.site[e] = u[(size_t)at.row * ldu + at.j] * mps_compress_site_factor(out.lam[at.j], lam_left ? lam_left[at.l] : 1.0);
+    }
     out.carry.assign((size_t)r * cols, cd(0.0, 0.0));
     for (int j = 0; j < r; ++j)
         for (int c = 0; c < cols; ++c) {

@@ -123,24 +123,8 @@ __global__ __launch_bounds__(256) void mps_ent_cut_kernel(MpsEntCutArgs a) {
     if (tid == 0) { a.rows[item] = chi; a.cols[item] = chi; }
 }
 
-namespace {
-hipError_t ent_attributes() {
-    static bool attr_set[64] = {};   // per device: hipFuncSetAttribute applies to the current one
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev] || dev == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mps_ent_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(mps_ent_cut_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEntCutLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    return hipSuccess;
-}
-}  // namespace
-
 hipError_t launch_mps_ent_chain(const MpsEntChainArgs& a, int nstates, hipStream_t s) {
-    hipError_t e = ent_attributes();
+    const hipError_t e = grant_dynamic_lds<kFusedLds, mps_ent_chain_kernel>();
     if (e != hipSuccess) return e;
     if (nstates <= 0 || a.n < 2) return hipSuccess;
     mps_ent_chain_kernel<<<dim3(2, nstates), 256, kFusedLds, s>>>(a);
@@ -148,7 +132,7 @@ hipError_t launch_mps_ent_chain(const MpsEntChainArgs& a, int nstates, hipStream
 }
 
 hipError_t launch_mps_ent_chain_right(const MpsEntChainArgs& a, int nstates, hipStream_t s) {
-    hipError_t e = ent_attributes();
+    const hipError_t e = grant_dynamic_lds<kFusedLds, mps_ent_chain_kernel>();
     if (e != hipSuccess) return e;
     if (nstates <= 0 || a.n < 2) return hipSuccess;
     MpsEntChainArgs r = a;
@@ -158,7 +142,7 @@ hipError_t launch_mps_ent_chain_right(const MpsEntChainArgs& a, int nstates, hip
 }
 
 hipError_t launch_mps_ent_cut(const MpsEntCutArgs& a, int count, hipStream_t s) {
-    hipError_t e = ent_attributes();
+    const hipError_t e = grant_dynamic_lds<kEntCutLds, mps_ent_cut_kernel>();
     if (e != hipSuccess) return e;
     if (count <= 0) return hipSuccess;
     mps_ent_cut_kernel<<<count, 256, kEntCutLds, s>>>(a);

@@ -35,9 +35,10 @@ struct Call {
     int k = 1;
     MpsTable table;                        // per fused state: site pointers | factor offsets | dims
     DevBuf<MpsEntState> d_states;
-    DevBuf<double2> d_factors, d_a, d_u, d_vh, d_work, d_vmat;
-    DevBuf<double> d_s;
-    DevBuf<int> d_items, d_ints;           // state | cut of every matrix; sweeps | status of every matrix, rows | cols of a chunk
+    DevBuf<double2> d_factors;
+    DevBuf<double> d_s;                    // the spectra of every matrix of the call
+    DevBuf<int> d_items, d_ints;           // state | cut of every matrix; sweeps | status of every matrix
+    SvdChunk svd;                          // of k x k matrices, one per (state, cut) of a chunk; s, sweeps and status are the call's
 };
 
 int run_fused(Call& c, const std::vector<int>& fused, double* factors_out, const std::vector<size_t>& lane_factor_at, hipStream_t st) {
@@ -70,20 +71,14 @@ int run_fused(Call& c, const std::vector<int>& fused, double* factors_out, const
         const int K = c.k, chunk = mps_ent_chunk(K, total, kMpsCallBudget);
         std::vector<int> items(c.item_state);
         items.insert(items.end(), c.item_cut.begin(), c.item_cut.end());
-        const size_t mat = (size_t)K * K;
-        if (c.d_items.upload(items) || c.d_ints.alloc(2 * total + 2 * (size_t)chunk) || c.d_s.alloc(total * K) || c.d_a.alloc(chunk * mat) ||
-            c.d_u.alloc(chunk * mat) || c.d_vh.alloc(chunk * mat) || c.d_work.alloc(svd_batch_work_elems(chunk, K, K)) ||
-            c.d_vmat.alloc(svd_batch_v_elems(chunk, K, K))) return 1;
+        if (c.d_items.upload(items) || c.d_ints.alloc(2 * total) || c.d_s.alloc(total * K) || c.svd.alloc(chunk, K, K, false)) return 1;
         int* d_sweeps = c.d_ints;
         int* d_status = d_sweeps + total;
-        int* d_rows = d_status + total;
-        int* d_cols = d_rows + chunk;
         for (size_t first = 0; first < total; first += chunk) {   // the chunks share the SVD's stores: one stream orders them
             const int count = (int)std::min<size_t>(chunk, total - first);
-            MpsEntCutArgs a{c.n, K, (int)first, c.d_items, c.d_items + total, c.d_states, c.d_a, d_rows, d_cols};
+            MpsEntCutArgs a{c.n, K, (int)first, c.d_items, c.d_items + total, c.d_states, c.svd.a, c.svd.rows(), c.svd.cols()};
             HIP_OK(launch_mps_ent_cut(a, count, st));
-            HIP_OK(launch_svd_batch(count, K, K, d_rows, d_cols, c.d_a, c.d_u, c.d_s + first * K, c.d_vh, d_sweeps + first, d_status + first, c.d_work,
-                                    c.d_vmat, st));
+            HIP_OK(c.svd.launch(count, c.d_s + first * K, d_sweeps + first, d_status + first, st));
         }
         c.h_s.resize(total * K);
         c.h_sweeps.resize(total);

@@ -8,8 +8,9 @@
 //                               step with the factors of the level before as blocks of c rows, four to a workgroup, until one factor
 //                               per lane is left; that level writes R^T as matrix `lane` of the batched SVD, rows = c, cols = min(c, N_r).
 //   launch_svd_batch            (aqc_svd_batch.hip) over the lanes of the chunk;
-//   mps_fromvec_split_kernel    thread 0 takes the decision of the cut (mps_compress_decide, the host's text); the new site, the bond vector,
-//                               r_{q+1}, the weight of the cut, sweeps and status; W = rescale conj(U[:, :r]) for the projection.
+//   mps_fromvec_split_kernel    the cut by the steps of aqc_mps_cut.h (thread 0 takes mps_compress_decide, the host's text; the bond vector;
+//                               the new site and, in the same loop, W = rescale conj(U[:, :r]) for the projection); r_{q+1}, the weight of
+//                               the cut, sweeps and status.  A matrix wider than the planes or a rank beyond the cap is this kernel's own refusal.
 //   mps_fromvec_project_kernel  grid (row groups, lanes).  Y = A_q W on the fp64 matrix cores: W (c x r) in LDS planes, A_q streamed in
 //                               chunks of 64 rows, a wave owning 16 of them with its whole strip of A_q loaded before the products, Y
 //                               written with row stride r.  The memory-bound pass of the call.
@@ -19,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "aqc_launch.h"
+#include "aqc_mps_cut.h"
 #include "aqc_mps_fromvec_rule.h"
 #include "aqc_mps_householder.h"
 #include "aqc_mps_planes.h"
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(256) void mps_fromvec_qr_kernel(MpsFromVecArgs a) {
     const cplx* src = a.level == 0 ? a.src + (size_t)lane * a.lane_elems : a.fac_in + (size_t)lane * a.max_parts * kFacElems;
     const size_t src_rows = a.level == 0 ? a.nr : a.in_blocks * (size_t)c;
     const size_t b0 = (size_t)p * a.blocks_per_part, b1 = b0 + a.blocks_per_part < a.in_blocks ? b0 + a.blocks_per_part : a.in_blocks;
-    for (int e = tid; e < 4 * kPlane; e += 256) fv_smem[e] = 0.0;
+    planes_zero(fv_smem);
     __syncthreads();
     for (size_t b = b0; b < b1; ++b) {
         const size_t row0 = b * height;
@@ -60,12 +62,7 @@ __global__ __launch_bounds__(256) void mps_fromvec_qr_kernel(MpsFromVecArgs a) {
         const cplx* blk = src + row0 * c;
         double* pr = b == b0 ? fr : er;   // the first block of the part by itself: R in its leading min(h, c) rows, exact zeros below
         double* pi = b == b0 ? fi : ei;
-        for (int e = tid; e < h * c; e += 256) {
-            const cplx x = blk[e];
-            const int i = e / c, col = e - i * c;
-            pr[i * kLd + col] = x.x;
-            pi[i * kLd + col] = x.y;
-        }
+        plane_load(blk, h, c, pr, pi);
         __syncthreads();
         householder_lds(fv_smem, kCap, c, v, wp, np);   // leaves R in the leading rows of the F planes and zeros in the E planes
     }
@@ -97,25 +94,15 @@ __global__ __launch_bounds__(256) void mps_fromvec_split_kernel(MpsFromVecArgs a
     const int r = bonds[q], c = 2 * r;
     const int count = (size_t)c < a.nr ? c : (int)a.nr;   // <= kCap
     const double* s = a.s + (size_t)lane * a.kc;
-    if (tid == 0) {
-        MpsCompressDecision d = {0, 0, 0.0, 0.0, 0.0, 1.0};
-        if (svd_status == 0 && c <= kCap) d = mps_compress_decide(count, s, a.trunc_thr, a.max_bond);
-        if (d.ok && d.rank > kMpsFromVecCap) d.ok = 0;   // (never: a rank stays within the bound of its bond)
-        dec = d;
-    }
-    __syncthreads();   // (every thread has read the status before thread 0 writes it)
-    const MpsCompressDecision d = dec;
+    MpsCompressDecision d = cut_decide(c <= kCap ? svd_status : -1, count, s, a.trunc_thr, a.max_bond, &dec);   // (c <= kCap always)
+    if (d.ok && d.rank > kMpsFromVecCap) d.ok = 0;   // (never: a rank stays within the bound of its bond)
     if (!d.ok) {
-        if (tid == 0) { a.status[g] = svd_status == 1 ? kMpsCompressSweepLimit : kMpsCompressNonFinite; a.failed_at[g] = q; }
+        if (tid == 0) { a.status[g] = cut_failure(svd_status); a.failed_at[g] = q; }
         return;
     }
     const int rk = d.rank;   // 1 .. min(count, kMpsFromVecCap)
     double* out_lam = a.lam + (size_t)g * a.lam_off[cuts];
-    if (tid < rk) {
-        const double x = d.rescale * s[tid];
-        lam[tid] = x;
-        out_lam[a.lam_off[q] + tid] = x;
-    }
+    cut_bond(d, s, lam, out_lam + a.lam_off[q]);
     if (tid == 0) {
         bonds[q + 1] = rk;
         a.dropped[(size_t)g * cuts + q] = d.total - d.kept;
@@ -125,14 +112,7 @@ __global__ __launch_bounds__(256) void mps_fromvec_split_kernel(MpsFromVecArgs a
     const cplx* u = a.u + (size_t)lane * a.kc * a.kc;   // [c][kc], the leading `count` columns
     cplx* site = a.sites + (size_t)g * a.site_off[a.n] + a.site_off[q];   // T'_q[s][l][j], packed [2][r][rk]
     cplx* w = a.w + (size_t)lane * kCap * kMpsFromVecCap;                 // W[(s, l)][j], packed [c][rk]
-    const double* lam_left = q > 0 ? out_lam + a.lam_off[q - 1] : nullptr;
-    for (int e = tid; e < c * rk; e += 256) {
-        const int row = e / rk, j = e - row * rk, l = row < r ? row : row - r;
-        const double f = mps_compress_site_factor(lam[j], lam_left ? lam_left[l] : 1.0);
-        const cplx x = u[(size_t)row * a.kc + j];
-        site[e] = make_double2(f * x.x, f * x.y);
-        w[e] = make_double2(d.rescale * x.x, -(d.rescale * x.y));
-    }
+    cut_left_site<true>(u, a.kc, r, rk, lam, q > 0 ? out_lam + a.lam_off[q - 1] : nullptr, site, d.rescale, w);
 }
 
 // grid (ceil(N_r / (64 kMpsFromVecProjectChunks)), lanes of the chunk); 256 threads
@@ -212,22 +192,8 @@ __global__ __launch_bounds__(64) void mps_fromvec_last_kernel(MpsFromVecArgs a) 
     if (tid == 0) bonds[n] = 1;
 }
 
-namespace {
-hipError_t fromvec_attributes() {
-    static bool attr_set[64] = {};   // per device: hipFuncSetAttribute applies to the current one
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;   // unknown device: set, remember nothing
-    if (dev < 0 || !attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mps_fromvec_qr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    return hipSuccess;
-}
-}  // namespace
-
 hipError_t launch_mps_fromvec_qr(const MpsFromVecArgs& a, int parts, int count, hipStream_t s) {
-    const hipError_t e = fromvec_attributes();
+    const hipError_t e = grant_dynamic_lds<kFusedLds, mps_fromvec_qr_kernel>();
     if (e != hipSuccess) return e;
     if (count <= 0 || parts <= 0) return hipSuccess;
     mps_fromvec_qr_kernel<<<dim3(parts, count), 256, kFusedLds, s>>>(a);

@@ -20,31 +20,25 @@ struct Call {
     double trunc_thr = 0.0;
     int max_bond = 0;
     std::vector<int> bounds;                 // n + 1
-    std::vector<size_t> site_off, lam_off;   // n + 1, n entries, sized by the bounds
-    DevBuf<double2> d_ping, d_pong, d_fac0, d_fac1, d_a, d_u, d_vh, d_work, d_vmat, d_w, d_sites;
-    DevBuf<double> d_s, d_lam, d_dropped;
+    BoundedStores stores;                    // the new sites and bond vectors of every lane, sized by the bounds
+    DevBuf<double2> d_ping, d_pong, d_fac0, d_fac1, d_w;
+    DevBuf<double> d_dropped;
     DevBuf<int> d_lane_ints;                 // bonds [lanes][n + 1] | status [lanes] | failed_at [lanes] | sweeps [lanes][cuts]
-    DevBuf<int> d_ints;                      // per lane of a chunk: rows | cols | sweeps | status
-    DevBuf<size_t> d_off;                    // site_off | lam_off
+    SvdChunk svd;                            // of kc x kc matrices, one per lane of a chunk
     std::vector<int> h_lane_ints;
     std::vector<double> h_dropped;
 };
 
 int run_fused(Call& c, const double2* vecs, hipStream_t st) {
     const size_t n = (size_t)c.n, cuts = (size_t)c.cuts, lanes = (size_t)c.lanes, chunk = (size_t)c.chunk, elems = (size_t)1 << c.n;
-    const size_t ints = (n + 1) + 2 + cuts, kc = (size_t)c.kc, fac = (size_t)c.max_parts * 64 * 64;
-    std::vector<size_t> off(c.site_off);
-    off.insert(off.end(), c.lam_off.begin(), c.lam_off.end());
+    const size_t ints = (n + 1) + 2 + cuts, fac = (size_t)c.max_parts * 64 * 64;
     c.h_lane_ints.assign(lanes * ints, 0);
     int* h_bonds = c.h_lane_ints.data();
     int* h_failed = h_bonds + lanes * (n + 1) + lanes;
     for (size_t i = 0; i < lanes; ++i) { h_bonds[i * (n + 1)] = 1; h_failed[i] = -1; }
     if (c.d_ping.alloc(chunk * elems) || c.d_pong.alloc(chunk * elems) || c.d_fac0.alloc(chunk * fac) || c.d_fac1.alloc(chunk * fac) ||
-        c.d_a.alloc(chunk * kc * kc) || c.d_u.alloc(chunk * kc * kc) || c.d_vh.alloc(chunk * kc * kc) || c.d_s.alloc(chunk * kc) ||
-        c.d_work.alloc(svd_batch_work_elems(c.chunk, c.kc, c.kc)) || c.d_vmat.alloc(svd_batch_v_elems(c.chunk, c.kc, c.kc)) ||
-        c.d_w.alloc(chunk * 64 * kMpsFromVecCap) || c.d_ints.alloc(4 * chunk) || c.d_sites.alloc(lanes * c.site_off[n]) ||
-        c.d_lam.alloc(lanes * std::max<size_t>(c.lam_off[cuts], 1)) || c.d_dropped.alloc(lanes * cuts) || c.d_off.upload(off) ||
-        c.d_lane_ints.upload(c.h_lane_ints)) return 1;
+        c.svd.alloc(c.chunk, c.kc, c.kc) || c.d_w.alloc(chunk * 64 * kMpsFromVecCap) || c.stores.alloc(c.n, c.bounds.data(), lanes) ||
+        c.d_dropped.alloc(lanes * cuts) || c.d_lane_ints.upload(c.h_lane_ints)) return 1;
     HIP_OK(hipMemsetAsync(c.d_dropped, 0, sizeof(double) * lanes * cuts, st));
     MpsFromVecArgs a{};
     a.n = c.n;
@@ -55,20 +49,18 @@ int run_fused(Call& c, const double2* vecs, hipStream_t st) {
     a.failed_at = a.status + lanes;
     a.sweeps = a.failed_at + lanes;
     a.dropped = c.d_dropped;
-    a.sites = c.d_sites;
-    a.lam = c.d_lam;
-    a.site_off = c.d_off;
-    a.lam_off = a.site_off + (n + 1);
+    a.sites = c.stores.sites;
+    a.lam = c.stores.lam;
+    a.site_off = c.stores.d_site_off();
+    a.lam_off = c.stores.d_lam_off();
     a.max_parts = c.max_parts;
-    a.a = c.d_a;
-    a.rows = c.d_ints;
-    a.cols = a.rows + chunk;
-    int* d_sweeps = a.cols + chunk;
-    int* d_status = d_sweeps + chunk;
-    a.u = c.d_u;
-    a.s = c.d_s;
-    a.svd_sweeps = d_sweeps;
-    a.svd_status = d_status;
+    a.a = c.svd.a;
+    a.rows = c.svd.rows();
+    a.cols = c.svd.cols();
+    a.u = c.svd.u;
+    a.s = c.svd.s;
+    a.svd_sweeps = c.svd.sweeps();
+    a.svd_status = c.svd.status();
     a.w = c.d_w;
     a.trunc_thr = c.trunc_thr;
     a.max_bond = c.max_bond;
@@ -97,7 +89,7 @@ int run_fused(Call& c, const double2* vecs, hipStream_t st) {
                 a.blocks_per_part = kMpsFromVecFanIn;
                 parts = mps_fromvec_fold(parts);
             }
-            HIP_OK(launch_svd_batch(count, c.kc, c.kc, a.rows, a.cols, c.d_a, c.d_u, c.d_s, c.d_vh, d_sweeps, d_status, c.d_work, c.d_vmat, st));
+            HIP_OK(c.svd.launch(count, st));
             HIP_OK(launch_mps_fromvec_split(a, count, st));
             HIP_OK(launch_mps_fromvec_project(a, count, st));
         }
@@ -112,13 +104,6 @@ int run_fused(Call& c, const double2* vecs, hipStream_t st) {
     return 0;
 }
 
-void drop_outputs(aqc_mps** out, int lanes) {
-    for (int i = 0; i < lanes; ++i) {
-        if (out[i]) (void)aqc_mps_destroy(out[i]);
-        out[i] = nullptr;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -129,18 +114,12 @@ int aqc_mps_from_vec_route(int n, int max_bond) {
 }
 
 int64_t aqc_mps_from_vec_budget(int64_t bytes) {
-    const size_t before = g_budget.exchange(bytes > 0 ? (size_t)bytes : kMpsFromVecBudget);
-    return (int64_t)before;
+    return swap_budget(g_budget, bytes, kMpsFromVecBudget);
 }
 
 int aqc_mps_from_vec(int device, int n, int lanes, const double* vecs, double trunc_thr, int max_bond, int method, aqc_mps** out, int32_t* bonds,
                      double* dropped, int32_t* sweeps, int32_t* status, int32_t* failed_at, int32_t* parts) {
-    if (!vecs || !out) return failf("null argument");
-    if (lanes < 1) return failf("at least one vector is needed");
-    for (int i = 0; i < lanes; ++i) out[i] = nullptr;   // whatever follows, the caller finds null or a state it owns
-    if (!mps_fromvec_method_ok(method)) return failf("unknown method %d", method);
-    if (!(trunc_thr >= 0.0) || !std::isfinite(trunc_thr)) return failf("trunc_thr must be a non-negative number");
-    if (max_bond < 0) return failf("max_bond must be non-negative");
+    if (check_truncating_call(vecs, out, lanes, trunc_thr, max_bond, "vector", mps_fromvec_method_ok(method), method)) return 1;
     if (n < kMpsFromVecMinQubits) return failf("a vector needs at least %d qubits", (int)kMpsFromVecMinQubits);
     const int route = method == kMpsFromVecByRule ? mps_fromvec_route(n, max_bond) : method;
     if (route == kMpsFromVecHost) return failf("the host route of the conversion (%d qubits, max_bond %d) is the caller's: vector_to_canonical_mps", n, max_bond);
@@ -163,8 +142,6 @@ int aqc_mps_from_vec(int device, int n, int lanes, const double* vecs, double tr
     if (device < 0 || device >= ndev) return failf("device out of range");
     HIP_OK(hipSetDevice(device));
     c.bounds = mps_fromvec_bounds(n, max_bond);
-    c.site_off = mps_site_offsets(n, c.bounds.data());
-    c.lam_off = mps_compress_lam_offsets(n, c.bounds.data());
     c.kc = 2 * mps_max_bond(n, c.bounds.data());
     for (int q = 0; q + 1 < n; ++q) {
         const int p = mps_fromvec_parts((size_t)1 << (n - 1 - q));
@@ -185,16 +162,8 @@ int aqc_mps_from_vec(int device, int n, int lanes, const double* vecs, double tr
         const int* b = h_bonds + i * np1;
         if (h_status[i] == kMpsCompressOk) {
             double discarded = 0.0;
-            std::vector<const void*> sites(n);
-            std::vector<const double*> lams(std::max(n - 1, 1), nullptr);
-            for (int q = 0; q < n; ++q) {
-                sites[q] = c.d_sites + i * c.site_off[n] + c.site_off[q];
-                if (q < n - 1) {
-                    lams[q] = c.d_lam + i * c.lam_off[cuts] + c.lam_off[q];
-                    discarded += c.h_dropped[i * cuts + q];
-                }
-            }
-            if (mps_adopt(device, n, b, sites.data(), lams.data(), discarded, &out[i])) { drop_outputs(out, lanes); return 1; }
+            for (size_t q = 0; q < cuts; ++q) discarded += c.h_dropped[i * cuts + q];
+            if (c.stores.adopt(device, n, i, b, discarded, &out[i])) { drop_outputs(out, lanes); return 1; }
         }
         for (size_t q = 0; q < np1; ++q)
             if (bonds) bonds[i * np1 + q] = b[q];

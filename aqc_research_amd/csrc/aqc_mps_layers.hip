@@ -7,9 +7,11 @@
 //                            v_mfma_f64_16x16x4_f64; up to 16: a plain loop per element), then in place
 //                            theta[(a', l), (b', r)] = lambda_{q-1}[l] sum_ab G[2a' + b'][2a + b] P_ab[l][r]; rows = 2 chi_q, cols = 2 chi_{q+2}
 //   launch_svd_batch         (aqc_svd_batch.hip) over the chunk; a wide theta goes through its transpose there
-//   mps_layer_split_kernel   thread 0 takes mps_compress_decide (the host's text); rank into dims[q + 1], total - kept onto the bond's
+//   mps_layer_split_kernel   the cut by the steps of aqc_mps_cut.h (thread 0 takes mps_compress_decide, the host's text; the decision in
+//                            static LDS, the new bond vector in dynamic LDS); rank into dims[q + 1], total - kept onto the bond's
 //                            dropped weight, sweeps; T'_q = U Sigma rescale / lambda_{q-1}, T'_{q+1} = V^H, lambda'_q = Sigma rescale
-//                            packed at the new dims over the old sites (theta has consumed them).
+//                            packed at the new dims over the old sites (theta has consumed them).  A rank beyond bounds[q + 1] is this
+//                            kernel's own refusal.
 // mps_layer_load_kernel copies the inputs into the stores first; the inputs are never written.  One workgroup per (gate, unit).  The
 // gates of a layer touch disjoint sites and bonds: a workgroup writes T_q, T_{q+1}, lambda_q, dims[q + 1] and the words of bond q alone,
 // and reads lambda_{q-1}, dims[q], dims[q + 2], which no gate of the same layer writes.  A unit whose spectrum is zero or not finite, whose
@@ -18,17 +20,19 @@
 #include <hip/hip_runtime.h>
 
 #include "aqc_launch.h"
+#include "aqc_mps_cut.h"
 #include "aqc_mps_layers_rule.h"
 #include "aqc_mps_planes.h"
 
 namespace aqc {
 
 static_assert((int)kMpsLayersCap == (int)kMpsObsFusedCap, "the planes of aqc_mps_planes.h are sized by the observables' cap");
+static_assert((int)kMpsLayersSweepLimit == (int)kMpsCompressSweepLimit && (int)kMpsLayersNonFinite == (int)kMpsCompressNonFinite, "cut_failure");
 
 namespace {
 
 constexpr int kLayerSmallBond = 16;                                // middle bonds up to here take the plain loop
-constexpr size_t kSplitLds = sizeof(double) * (2 * kCap + 8);      // the new bond vector and the decision
+constexpr size_t kSplitLds = sizeof(double) * 2 * kCap;            // the new bond vector
 
 __device__ __forceinline__ const cplx* const* unit_sites(const MpsLayersArgs& a, int unit) {
     return reinterpret_cast<const cplx* const*>(a.table + (size_t)unit * a.per + a.at_sites);
@@ -38,18 +42,6 @@ __device__ __forceinline__ const double* const* unit_lams(const MpsLayersArgs& a
 }
 __device__ __forceinline__ const int* unit_dims(const MpsLayersArgs& a, int unit) {
     return reinterpret_cast<const int*>(a.table + (size_t)unit * a.per + a.at_dims);
-}
-
-// the wave's part of acc, rows below m and columns below nn, into dst with leading dimension ld
-__device__ __forceinline__ void acc_to_theta(const Acc& acc, cplx* __restrict__ dst, int ld, int m, int nn) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = 16 * wave + 4 * r + lk, j = 16 * t + li;
-            if (i < m && j < nn) dst[(size_t)i * ld + j] = make_double2(acc.re[t][r], acc.im[t][r]);
-        }
 }
 
 }  // namespace
@@ -95,7 +87,7 @@ __global__ __launch_bounds__(256) void mps_layer_form_kernel(MpsLayersArgs a) {
         double* ei = er + kPlane;
         double* fr = ei + kPlane;
         double* fi = fr + kPlane;
-        for (int e = tid; e < 4 * kPlane; e += 256) lay_smem[e] = 0.0;
+        planes_zero(lay_smem);
         __syncthreads();
         for (int e = tid; e < 2 * cl * cm; e += 256) {
             const cplx x = tq[e];
@@ -109,7 +101,7 @@ __global__ __launch_bounds__(256) void mps_layer_form_kernel(MpsLayersArgs a) {
         for (int ab = 0; ab < 4; ++ab) {
             const int s = ab >> 1, b = ab & 1;
             prod_lds_mem<false>(s ? fr : er, s ? fi : ei, tn + (size_t)b * cm * cr, cl, cm, cr, p);
-            acc_to_theta(p, theta + (size_t)s * cl * ld + (size_t)b * cr, ld, cl, cr);
+            acc_to_mem(p, theta + (size_t)s * cl * ld + (size_t)b * cr, ld, cl, cr);
         }
     } else {
         for (int e = tid; e < cl * cr; e += 256) {
@@ -157,8 +149,8 @@ __global__ __launch_bounds__(256) void mps_layer_form_kernel(MpsLayersArgs a) {
 // grid (matrices of the chunk); 256 threads; dynamic LDS kSplitLds
 __global__ __launch_bounds__(256) void mps_layer_split_kernel(MpsLayersArgs a) {
     extern __shared__ __attribute__((aligned(16))) double lay_smem[];
+    __shared__ MpsCompressDecision dec;
     double* lam = lay_smem;                        // [2 kCap]
-    double* dec = lay_smem + 2 * kCap;             // ok, rank, rescale, total - kept
     const int item = blockIdx.x, tid = threadIdx.x;
     const int idx = a.first + item, unit = idx / a.gates, g = idx - unit * a.gates, q = a.gate_q[g];
     if (a.rows[item] == 0) return;   // the form kernel of this chunk has skipped the unit
@@ -167,32 +159,22 @@ __global__ __launch_bounds__(256) void mps_layer_split_kernel(MpsLayersArgs a) {
     const int count = 2 * (cl < cr ? cl : cr);     // <= m
     const int svd_status = a.svd_status[item];
     const double* s = a.s + (size_t)item * ld;
-    if (tid == 0) {
-        MpsCompressDecision d = {0, 0, 0.0, 0.0, 0.0, 1.0};
-        if (svd_status == 0) d = mps_compress_decide(count, s, a.trunc_thr, a.max_bond);
-        dec[0] = d.ok; dec[1] = d.rank; dec[2] = d.rescale; dec[3] = d.total - d.kept;
-    }
-    __syncthreads();
-    const int ok = (int)dec[0], rk = (int)dec[1];
-    const double rescale = dec[2];
+    const MpsCompressDecision d = cut_decide(svd_status, count, s, a.trunc_thr, a.max_bond, &dec);
+    const int rk = d.rank;
     const size_t bond = (size_t)unit * (a.n - 1) + q;
-    if (!ok || rk > a.bounds[q + 1]) {
+    if (!d.ok || rk > a.bounds[q + 1]) {
         if (tid == 0) {
-            a.fail_code[bond] = !ok ? (svd_status == 1 ? kMpsLayersSweepLimit : kMpsLayersNonFinite) : kMpsLayersOverflow;
+            a.fail_code[bond] = !d.ok ? cut_failure(svd_status) : kMpsLayersOverflow;
             a.fail_layer[bond] = a.layer;
             a.failed[unit] = a.layer + 1;   // (every failing gate of the layer writes the same value)
         }
         return;
     }
-    if (tid < rk) {
-        const double v = rescale * s[tid];
-        lam[tid] = v;
-        a.lam[(size_t)unit * a.lam_total + a.lam_off[q] + tid] = v;
-    }
+    cut_bond(d, s, lam, a.lam + (size_t)unit * a.lam_total + a.lam_off[q]);
     __syncthreads();   // (every thread has read dims before thread 0 writes the rank)
     if (tid == 0) {
         a.dims[(size_t)unit * (a.n + 1) + q + 1] = rk;
-        a.dropped[bond] += dec[3];
+        a.dropped[bond] += d.total - d.kept;
         a.sweeps[(size_t)unit * a.ngates + a.gate_id[g]] = a.svd_sweeps[item];
     }
     const cplx* u = a.u + (size_t)item * ld * ld;
@@ -200,31 +182,12 @@ __global__ __launch_bounds__(256) void mps_layer_split_kernel(MpsLayersArgs a) {
     const double* lam_left = q > 0 ? a.lam + (size_t)unit * a.lam_total + a.lam_off[q - 1] : nullptr;
     cplx* out_q = a.sites + (size_t)unit * a.site_total + a.site_off[q];        // [2][cl][rk], rk <= bounds[q + 1]
     cplx* out_n = a.sites + (size_t)unit * a.site_total + a.site_off[q + 1];    // [2][rk][cr]
-    for (int e = tid; e < 2 * cl * rk; e += 256) {
-        const int row = e / rk, j = e - row * rk, l = row < cl ? row : row - cl;
-        const double f = mps_compress_site_factor(lam[j], lam_left ? lam_left[l] : 1.0);
-        const cplx x = u[(size_t)row * ld + j];
-        out_q[e] = make_double2(f * x.x, f * x.y);
-    }
+    cut_left_site(u, ld, cl, rk, lam, lam_left, out_q);
     for (int e = tid; e < 2 * rk * cr; e += 256) {
         const int b = e / (rk * cr), rest = e - b * rk * cr, j = rest / cr, r = rest - j * cr;
         out_n[e] = vh[(size_t)j * ld + (size_t)b * cr + r];
     }
 }
-
-namespace {
-hipError_t layers_attributes() {
-    static bool attr_set[64] = {};   // per device: hipFuncSetAttribute applies to the current one
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;   // unknown device: set, remember nothing
-    if (dev < 0 || !attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mps_layer_form_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    return hipSuccess;
-}
-}  // namespace
 
 hipError_t launch_mps_layer_load(const MpsLayersArgs& a, int units, hipStream_t s) {
     if (units <= 0 || a.n <= 0) return hipSuccess;
@@ -233,7 +196,7 @@ hipError_t launch_mps_layer_load(const MpsLayersArgs& a, int units, hipStream_t 
 }
 
 hipError_t launch_mps_layer_form(const MpsLayersArgs& a, int count, hipStream_t s) {
-    const hipError_t e = layers_attributes();
+    const hipError_t e = grant_dynamic_lds<kFusedLds, mps_layer_form_kernel>();
     if (e != hipSuccess) return e;
     if (count <= 0) return hipSuccess;
     const size_t lds = a.m / 2 > kLayerSmallBond ? kFusedLds : 0;   // no middle bond passes K = m / 2

@@ -54,12 +54,12 @@ struct Call {
     std::vector<int> lane_state, lane_unit;
     std::vector<Unit> units;
     std::vector<int> bounds;
-    std::vector<size_t> site_off, lam_off;
     MpsTable table;
-    DevBuf<double2> d_sites, d_mats, d_a, d_u, d_vh, d_work, d_vmat;
-    DevBuf<double> d_lam, d_dropped, d_s;
-    DevBuf<int> d_plan, d_unit_set, d_bounds, d_dims, d_sweeps, d_fail, d_ints;   // d_fail: failed | fail_code | fail_layer
-    DevBuf<size_t> d_off;                                                            // site_off | lam_off
+    BoundedStores stores;                  // the working copy of every unit, sized by the bounds
+    DevBuf<double2> d_mats;
+    DevBuf<double> d_dropped;
+    DevBuf<int> d_plan, d_unit_set, d_bounds, d_dims, d_sweeps, d_fail;   // d_fail: failed | fail_code | fail_layer
+    SvdChunk svd;                          // of 2 K x 2 K matrices, one per (gate, unit) of a chunk
     std::vector<int> h_dims, h_sweeps, h_fail;
     std::vector<double> h_dropped;
 };
@@ -73,9 +73,6 @@ bool finite_matrix(const double* m, int count) {
 int run_fused(Call& c, const Program& p, hipStream_t st) {
     const size_t n = (size_t)c.n, units = c.units.size(), ngates = p.ngates(), bonds = std::max<size_t>(n - 1, 1);
     const int K = *std::max_element(c.bounds.begin(), c.bounds.end()), M = 2 * K;
-    c.site_off = mps_site_offsets(c.n, c.bounds.data());
-    c.lam_off = mps_compress_lam_offsets(c.n, c.bounds.data());
-    const size_t site_total = c.site_off[n], lam_total = std::max<size_t>(c.lam_off[n - 1] + (n > 1 ? 0 : 1), 1);
     c.table = MpsTable({mps_table_words(n), mps_table_words(n), mps_table_ints(n + 1)}, units);
     std::vector<std::vector<const double*>> view_lams(c.views.size());
     for (size_t k = 0; k < c.views.size(); ++k) {
@@ -103,16 +100,12 @@ int run_fused(Call& c, const Program& p, hipStream_t st) {
     }
     const size_t widest = p.plan.widest();
     const int chunk = widest ? mps_layers_chunk(K, widest * units, g_svd_budget.load()) : 0;
-    const size_t mat = (size_t)M * M;
     std::vector<double2> mats(p.gates.size());
     memcpy(mats.data(), p.gates.data(), sizeof(double2) * mats.size());
-    std::vector<size_t> off(c.site_off);
-    off.insert(off.end(), c.lam_off.begin(), c.lam_off.end());
     if (c.table.upload() || c.d_plan.upload(plan_words) || c.d_unit_set.upload(unit_set) || c.d_bounds.upload(c.bounds) || c.d_mats.upload(mats) ||
-        c.d_off.upload(off) || c.d_sites.alloc(units * site_total) || c.d_lam.alloc(units * lam_total) || c.d_dims.alloc(units * (n + 1)) ||
+        c.stores.alloc(c.n, c.bounds.data(), units) || c.d_dims.alloc(units * (n + 1)) ||
         c.d_dropped.alloc(units * bonds) || c.d_sweeps.alloc(units * std::max<size_t>(ngates, 1)) || c.d_fail.alloc(units * (1 + 2 * bonds))) return 1;
-    if (chunk && (c.d_a.alloc(chunk * mat) || c.d_u.alloc(chunk * mat) || c.d_vh.alloc(chunk * mat) || c.d_s.alloc((size_t)chunk * M) || c.d_ints.alloc((size_t)4 * chunk) ||
-                  c.d_work.alloc(svd_batch_work_elems(chunk, M, M)) || c.d_vmat.alloc(svd_batch_v_elems(chunk, M, M)))) return 1;
+    if (chunk && c.svd.alloc(chunk, M, M)) return 1;
     HIP_OK(hipMemsetAsync(c.d_dropped, 0, sizeof(double) * units * bonds, st));
     HIP_OK(hipMemsetAsync(c.d_sweeps, 0, sizeof(int) * units * std::max<size_t>(ngates, 1), st));
     HIP_OK(hipMemsetAsync(c.d_fail, 0, sizeof(int) * units * (1 + 2 * bonds), st));
@@ -121,15 +114,12 @@ int run_fused(Call& c, const Program& p, hipStream_t st) {
     a.mats = c.d_mats; a.unit_set = c.d_unit_set;
     a.table = c.table.dev; a.per = c.table.layout.per;
     a.at_sites = c.table.layout.at[kSites]; a.at_lams = c.table.layout.at[kLams]; a.at_dims = c.table.layout.at[kDims];
-    a.site_off = c.d_off; a.lam_off = c.d_off + (n + 1); a.bounds = c.d_bounds;
-    a.site_total = site_total; a.lam_total = lam_total;
-    a.sites = c.d_sites; a.lam = c.d_lam; a.dims = c.d_dims; a.dropped = c.d_dropped; a.sweeps = c.d_sweeps;
+    a.site_off = c.stores.d_site_off(); a.lam_off = c.stores.d_lam_off(); a.bounds = c.d_bounds;
+    a.site_total = c.stores.site_total; a.lam_total = c.stores.lam_total;
+    a.sites = c.stores.sites; a.lam = c.stores.lam; a.dims = c.d_dims; a.dropped = c.d_dropped; a.sweeps = c.d_sweeps;
     a.failed = c.d_fail; a.fail_code = c.d_fail + units; a.fail_layer = c.d_fail + units * (1 + bonds);
-    a.a = c.d_a; a.u = c.d_u; a.s = c.d_s; a.vh = c.d_vh;
-    a.rows = c.d_ints; a.cols = a.rows + chunk;
-    int* d_sweeps = a.cols + chunk;
-    int* d_status = d_sweeps + chunk;
-    a.svd_sweeps = d_sweeps; a.svd_status = d_status;
+    a.a = c.svd.a; a.u = c.svd.u; a.s = c.svd.s; a.vh = c.svd.vh;
+    a.rows = c.svd.rows(); a.cols = c.svd.cols(); a.svd_sweeps = c.svd.sweeps(); a.svd_status = c.svd.status();
     a.trunc_thr = c.trunc_thr; a.max_bond = c.max_bond;
     HIP_OK(launch_mps_layer_load(a, (int)units, st));
     for (size_t l = 0; l < p.plan.layers.size(); ++l) {   // the chunks share the layer's stores: one stream orders them
@@ -142,7 +132,7 @@ int run_fused(Call& c, const Program& p, hipStream_t st) {
             const int count = (int)std::min<size_t>(chunk, total - first);
             a.first = (int)first;
             HIP_OK(launch_mps_layer_form(a, count, st));
-            HIP_OK(launch_svd_batch(count, M, M, a.rows, a.cols, c.d_a, c.d_u, c.d_s, c.d_vh, d_sweeps, d_status, c.d_work, c.d_vmat, st));
+            HIP_OK(c.svd.launch(count, st));
             HIP_OK(launch_mps_layer_split(a, count, st));
         }
     }
@@ -150,7 +140,7 @@ int run_fused(Call& c, const Program& p, hipStream_t st) {
         for (int q = 0; q < c.n; ++q)
             if (p.plan.has_single[q]) {
                 const MpsView& v = c.views[c.units[u].view];
-                double2* site = c.d_sites + u * site_total + c.site_off[q];
+                double2* site = c.stores.site(u, q);
                 HIP_OK(launch_gate1q(site, site, 1, (size_t)v.dims[q] * v.dims[q + 1], 0, p.single(c.units[u].set, q), st));
             }
     c.h_dims.resize(units * (n + 1));
@@ -188,15 +178,7 @@ int read_fused(Call& c, const Program& p) {
 
 int adopt_fused(const Call& c, size_t u, int device, aqc_mps** out) {
     const Unit& w = c.units[u];
-    const int n = c.n;
-    const size_t site_total = c.site_off[n], lam_total = std::max<size_t>(c.lam_off[n - 1] + (n > 1 ? 0 : 1), 1);
-    std::vector<const void*> sites(n);
-    std::vector<const double*> lams(std::max(n - 1, 1), nullptr);
-    for (int q = 0; q < n; ++q) {
-        sites[q] = c.d_sites + u * site_total + c.site_off[q];
-        if (q < n - 1) lams[q] = c.d_lam + u * lam_total + c.lam_off[q];
-    }
-    return mps_adopt(device, n, w.dims.data(), sites.data(), lams.data(), aqc_mps_discarded_weight(c.views[w.view].h) + w.dropped, out);
+    return c.stores.adopt(device, c.n, u, w.dims.data(), aqc_mps_discarded_weight(c.views[w.view].h) + w.dropped, out);
 }
 
 // gatewise route: gate_adjacent in layer order on a clone, with the folded matrices; the engine reports an SVD at its sweep limit as an
@@ -233,11 +215,9 @@ int run_gatewise(const Call& c, const Program& p, Unit& w) {
     return 0;
 }
 
+// a failed call: the outputs and the gatewise route's clones that no lane has taken
 void drop_outputs(Call& c, aqc_mps** out, int nstates) {
-    for (int i = 0; i < nstates; ++i) {
-        if (out[i]) (void)aqc_mps_destroy(out[i]);
-        out[i] = nullptr;
-    }
+    drop_outputs(out, nstates);
     for (Unit& w : c.units) {
         if (w.made) (void)aqc_mps_destroy(w.made);
         w.made = nullptr;
@@ -245,13 +225,7 @@ void drop_outputs(Call& c, aqc_mps** out, int nstates) {
 }
 
 int check_call(aqc_mps* const* states, int nstates, aqc_mps** out, double trunc_thr, int max_bond, int method) {
-    if (!states || !out) return failf("null argument");
-    if (nstates < 1) return failf("at least one state is needed");
-    for (int i = 0; i < nstates; ++i) out[i] = nullptr;   // whatever follows, the caller finds null or a state it owns
-    if (!mps_layers_method_ok(method)) return failf("unknown method %d", method);
-    if (!(trunc_thr >= 0.0) || !std::isfinite(trunc_thr)) return failf("trunc_thr must be a non-negative number");
-    if (max_bond < 0) return failf("max_bond must be non-negative");
-    return 0;
+    return check_truncating_call(states, out, nstates, trunc_thr, max_bond, "state", mps_layers_method_ok(method), method);
 }
 
 // the route of the call: the method, or the rule's choice; the fused route refuses what the rule does not allow
@@ -354,8 +328,7 @@ int aqc_mps_apply_route(int n, const int32_t* dims, int max_bond) {
 }
 
 int64_t aqc_mps_apply_svd_budget(int64_t bytes) {
-    const size_t before = g_svd_budget.exchange(bytes > 0 ? (size_t)bytes : kMpsCallBudget);
-    return (int64_t)before;
+    return swap_budget(g_svd_budget, bytes, kMpsCallBudget);
 }
 
 int aqc_mps_apply_plan(int n, int nops, const int32_t* qubits, const int32_t* kinds, int32_t* counts, int32_t* gate_sites, int32_t* gate_layers) {

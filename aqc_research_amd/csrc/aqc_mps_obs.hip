@@ -202,30 +202,18 @@ __global__ __launch_bounds__(256) void mps_obs_sums_kernel(const cplx* __restric
 }
 
 namespace {
-hipError_t fused_attributes() {
-    static bool attr_set[64] = {};   // per device: hipFuncSetAttribute applies to the current one
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev] || dev == 0) {
-        for (const void* f : {reinterpret_cast<const void*>(mps_obs_fused_kernel), reinterpret_cast<const void*>(mps_obs_env_kernel)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds);
-            if (e != hipSuccess) return e;
-        }
-        attr_set[dev] = true;
-    }
-    return hipSuccess;
-}
+constexpr auto grant_planes = grant_dynamic_lds<kFusedLds, mps_obs_fused_kernel, mps_obs_env_kernel>;
 }  // namespace
 
 hipError_t launch_mps_obs_env(const MpsObsFusedArgs& a, hipStream_t s) {
-    hipError_t e = fused_attributes();
+    const hipError_t e = grant_planes();
     if (e != hipSuccess) return e;
     mps_obs_env_kernel<<<2, 256, kFusedLds, s>>>(a);
     return hipGetLastError();
 }
 
 hipError_t launch_mps_obs_fused(const MpsObsFusedArgs& a, int nchains, hipStream_t s) {
-    hipError_t e = fused_attributes();
+    const hipError_t e = grant_planes();
     if (e != hipSuccess) return e;
     if (nchains <= 0) return hipSuccess;
     mps_obs_fused_kernel<<<dim3(kMpsObsComps, nchains), 256, kFusedLds, s>>>(a);

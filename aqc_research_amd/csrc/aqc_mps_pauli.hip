@@ -240,14 +240,8 @@ __global__ __launch_bounds__(256) void mps_pauli_close_kernel(const cplx* const*
 }
 
 hipError_t launch_mps_pauli_fused(const MpsPauliFusedArgs& a, int npairs, hipStream_t s) {
-    static bool attr_set[64] = {};   // per device: hipFuncSetAttribute applies to the current one
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev] || dev == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mps_pauli_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
+    const hipError_t e = grant_dynamic_lds<kFusedLds, mps_pauli_fused_kernel>();
+    if (e != hipSuccess) return e;
     if (npairs <= 0 || a.nstrings <= 0) return hipSuccess;
     mps_pauli_fused_kernel<<<dim3(a.nstrings, npairs), 256, kFusedLds, s>>>(a);
     return hipGetLastError();

@@ -1,11 +1,16 @@
 // Products of complex matrices held as split re / im planes in LDS, on v_mfma_f64_16x16x4_f64: what the fused walks of
-// aqc_mps_obs.hip (pair density matrices), aqc_mps_sample.hip (measurement) and aqc_mps_pauli.hip (Pauli strings) are made of.  Device
-// code, internal linkage.
+// aqc_mps_obs.hip (pair density matrices), aqc_mps_sample.hip (measurement) and aqc_mps_pauli.hip (Pauli strings) and the sweeps of
+// aqc_mps_ent.hip, aqc_mps_compress.hip, aqc_mps_layers.hip and aqc_mps_fromvec.hip are made of: the products, the moves between
+// memory, planes and accumulators (planes_zero, plane_load, acc_store, acc_to_mem), the workgroup's sums, and -- host side, at the
+// end -- grant_dynamic_lds, the one way these seven files ask for the planes' dynamic LDS.  The truncating cut that follows an SVD of
+// such a sweep is in aqc_mps_cut.h.  Device code but for the grant, internal linkage.
 // A plane is [kCap][kLd] doubles; a workgroup is 4 waves, wave w owns rows [16w, 16w + 16) of a product and all four 16-column tiles.
 // Operand layout of the instruction: top of aqc_mps.hip.  Operand tiles are zero-filled beyond the given dimensions, so accumulators
 // there are exact zeros and whole tiles are stored; reads never leave the tiles written for the current dimensions.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <atomic>
 
 #include "aqc_mps_obs_rule.h"
 
@@ -88,6 +93,30 @@ __device__ __forceinline__ void acc_store(const Acc& acc, double* pr, double* pi
     }
 }
 
+// the four planes zeroed, then a packed rows x cols matrix (rows, cols <= kCap) into the pair (pr, pi); the caller synchronises after each
+__device__ __forceinline__ void planes_zero(double* smem) {
+    for (int e = threadIdx.x; e < 4 * kPlane; e += 256) smem[e] = 0.0;
+}
+__device__ __forceinline__ void plane_load(const cplx* __restrict__ src, int rows, int cols, double* pr, double* pi) {
+    for (int e = threadIdx.x; e < rows * cols; e += 256) {
+        const cplx x = src[e];
+        const int i = e / cols, c = e - i * cols;
+        pr[i * kLd + c] = x.x;
+        pi[i * kLd + c] = x.y;
+    }
+}
+// the wave's part of acc, rows below m and columns below nn, times f (1: exact) into dst with leading dimension ld
+__device__ __forceinline__ void acc_to_mem(const Acc& acc, cplx* __restrict__ dst, int ld, int m, int nn, double f = 1.0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = 16 * wave + 4 * r + lk, j = 16 * t + li;
+            if (i < m && j < nn) dst[(size_t)i * ld + j] = make_double2(f * acc.re[t][r], f * acc.im[t][r]);
+        }
+}
+
 // sum over the workgroup (4 waves) in a fixed order; every thread gets the result.  red: 8 doubles of LDS
 __device__ __forceinline__ cplx block_sum(double re, double im, double* red) {
 #pragma unroll
@@ -117,6 +146,23 @@ __device__ __forceinline__ void acc_dot(const Acc& w, const cplx* __restrict__ R
             }
         }
     }
+}
+
+// Host side: dynamic LDS beyond the default for `Kernels` on the current device (hipFuncSetAttribute applies to that one alone), before
+// their launches.  Every set of kernels and size is an instantiation with a memo of its own: a known device is set once, an unknown
+// one every time and nothing is remembered.  Two host threads may make the first call at the same time: both set the same value
+template <size_t kBytes, auto... Kernels>
+hipError_t grant_dynamic_lds() {
+    static std::atomic<bool> granted[64];
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev >= 0 && granted[dev].load(std::memory_order_acquire)) return hipSuccess;
+    for (const void* f : {reinterpret_cast<const void*>(Kernels)...}) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBytes);
+        if (e != hipSuccess) return e;
+    }
+    if (dev >= 0) granted[dev].store(true, std::memory_order_release);
+    return hipSuccess;
 }
 
 }  // namespace

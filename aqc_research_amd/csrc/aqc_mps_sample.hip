@@ -209,16 +209,8 @@ __global__ void mps_sample_ones_kernel(cplx* v, long long rows) {
 }
 
 hipError_t launch_mps_sample_fused(const MpsSampleArgs& a, int nstates, bool amplitudes, hipStream_t s) {
-    static bool attr_set[64] = {};   // per device: hipFuncSetAttribute applies to the current one
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev] || dev == 0) {
-        for (const void* f : {reinterpret_cast<const void*>(mps_sample_fused_kernel<false>), reinterpret_cast<const void*>(mps_sample_fused_kernel<true>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds);
-            if (e != hipSuccess) return e;
-        }
-        attr_set[dev] = true;
-    }
+    const hipError_t e = grant_dynamic_lds<kFusedLds, mps_sample_fused_kernel<false>, mps_sample_fused_kernel<true>>();
+    if (e != hipSuccess) return e;
     if (nstates <= 0 || a.shots <= 0) return hipSuccess;
     const dim3 grid((unsigned)((a.shots + kMpsSampleBlockShots - 1) / kMpsSampleBlockShots), (unsigned)nstates);
     if (amplitudes) mps_sample_fused_kernel<true><<<grid, 256, kFusedLds, s>>>(a);

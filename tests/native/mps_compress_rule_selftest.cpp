@@ -137,6 +137,17 @@ int main() {
         CHECK(d.rank == 2 && d.tail == 0.1 * 0.1 && std::fabs((d.total - d.kept) - (0.01 + 1e-6 + 1e-30)) <= 1e-15);
         CHECK(mps_compress_site_factor(3.0, 1.5) == 2.0);
     }
+    {   // the index of a packed site element, shared by host and device, against the % form: every element for r = 1 .. 5, rk = 1 .. 2 r
+        int checked = 0;
+        for (int r = 1; r <= 5; ++r)
+            for (int rk = 1; rk <= 2 * r; ++rk)
+                for (int e = 0; e < 2 * r * rk; ++e, ++checked) {
+                    const MpsCompressSiteIndex at = mps_compress_site_index(e, r, rk);
+                    CHECK(at.row == e / rk && at.j == e % rk && at.l == (e / rk) % r && at.row * rk + at.j == e && at.row < 2 * r);
+                }
+        std::printf("site index: %d elements\n", checked);
+        CHECK(checked == 2 * (1 * 3 + 2 * 10 + 3 * 21 + 4 * 36 + 5 * 55));
+    }
     // one step: a tall stacked matrix (three values, one dropped by the threshold; all kept) and a wide one (two values; capped to one)
     step_case(6, 3, {2.0, 0.5, 0.01}, 1e-3, 0, 2);
     step_case(6, 3, {2.0, 0.5, 0.01}, 0.0, 0, 3);
