@@ -101,6 +101,11 @@ SIGNATURES = {
     "aqc_mps_from_vec_budget": (c_int64, [c_int64]),
     "aqc_mps_from_vec": (c_int, [c_int, c_int, c_int, _D, c_double, c_int, c_int, POINTER(_P), POINTER(c_int32), _D, POINTER(c_int32), POINTER(c_int32),
                                  POINTER(c_int32), POINTER(c_int32)]),
+    "aqc_mps_to_vec_route": (c_int, [c_int, POINTER(c_int32)]),
+    "aqc_mps_to_vec_budget": (c_int64, [c_int64]),
+    "aqc_mps_to_vec_outer_ms": (c_double, []),
+    "aqc_mps_to_vec": (c_int, [POINTER(_P), c_int, c_int, _D, POINTER(c_int32)]),
+    "aqc_mps_amp_blocks": (c_int, [POINTER(_P), c_int, c_int, c_int64, POINTER(c_uint8), c_int, _D]),
     "aqc_mps_apply_route": (c_int, [c_int, POINTER(c_int32), c_int]),
     "aqc_mps_apply_svd_budget": (c_int64, [c_int64]),
     "aqc_mps_apply_plan": (c_int, [c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),

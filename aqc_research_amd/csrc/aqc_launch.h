@@ -530,6 +530,25 @@ hipError_t launch_mps_fromvec_split(const MpsFromVecArgs& a, int count, hipStrea
 hipError_t launch_mps_fromvec_project(const MpsFromVecArgs& a, int count, hipStream_t s);              // grid (row groups, lanes of the chunk)
 hipError_t launch_mps_fromvec_last(const MpsFromVecArgs& a, int count, hipStream_t s);                 // grid (lanes of the chunk); q = n - 1
 
+// aqc_mps_tovec.hip (MPS states into dense vectors and blocks of amplitudes, fused route; rules: aqc_mps_tovec_rule.h).  A lane is one
+// distinct state; lane z of a launch is state first + z of the call's table, whose record holds sites [n] | bufs [5]: low store 0, 1,
+// high store 0, 1, output | dims [n + 1] and the route.  A state of another route is skipped by every workgroup.
+struct MpsToVecArgs {
+    const unsigned long long* table;   // a record of `per` words per state
+    int per, at_sites, at_bufs, at_dims;
+    int first;                     // the chunk's first state
+    int n, k;                      // qubits; the low sites 0 .. k - 1
+    int low_len, high_len;         // sites of each half that the grow steps walk (blocks: high_len = 0, the rows are walked instead)
+    int step;                      // grow step: the factors of 2^step rows become those of 2^(step+1)
+    int low_store, high_store;     // outer product: which store of each half holds L and H
+    long long high_rows;           // rows of H: 2^(n-k), or the listed rows of a block call
+    const unsigned char* high_bits;   // blocks: [high_rows][n - k], entry i the bit of site k + i
+};
+hipError_t launch_mps_tovec_head(const MpsToVecArgs& a, int count, hipStream_t s);    // grid (halves, lanes): the first steps of each half
+hipError_t launch_mps_tovec_step(const MpsToVecArgs& a, int count, hipStream_t s);    // grid (tiles of 64 rows, halves, lanes)
+hipError_t launch_mps_tovec_rows(const MpsToVecArgs& a, int count, hipStream_t s);    // grid (tiles of 64 listed rows, lanes)
+hipError_t launch_mps_tovec_outer(const MpsToVecArgs& a, int count, hipStream_t s);   // grid (column groups, row tiles, lanes)
+
 // aqc_mps_layers.hip (gate layers on MPS states, fused route; rules: aqc_mps_layers_rule.h).  A unit is one evolved state: its working
 // copy lives in the call's flat stores, every unit at the same offsets (sized by the call's bounds), the bond dimensions on the device.
 // Matrix i of a layer is (unit i / gates, gate i % gates); a chunk takes the matrices [first, first + count).

@@ -1,5 +1,5 @@
 // The skeleton of a call that reads single-lane MPS states (aqc_mps_obs_api.cpp, aqc_mps_sample_api.cpp, aqc_mps_pauli_api.cpp,
-// aqc_mps_ent_api.cpp, aqc_mps_compress_api.cpp, aqc_mps_layers_api.cpp): check the handles, view the distinct states, pack what the kernels read
+// aqc_mps_ent_api.cpp, aqc_mps_compress_api.cpp, aqc_mps_layers_api.cpp, aqc_mps_tovec_api.cpp): check the handles, view the distinct states, pack what the kernels read
 // of them into one table, launch on the first state's stream, synchronise once, assemble.  Each of those files keeps its own plan,
 // launches and results; what they share about their input states is here and in the HIP-free aqc_mps_states_rule.h.  The second
 // half holds the host scaffolding of a truncating sweep (aqc_mps_compress_api.cpp, aqc_mps_layers_api.cpp, aqc_mps_fromvec_api.cpp;

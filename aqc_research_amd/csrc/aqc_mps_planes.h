@@ -1,8 +1,8 @@
 // Products of complex matrices held as split re / im planes in LDS, on v_mfma_f64_16x16x4_f64: what the fused walks of
 // aqc_mps_obs.hip (pair density matrices), aqc_mps_sample.hip (measurement) and aqc_mps_pauli.hip (Pauli strings) and the sweeps of
-// aqc_mps_ent.hip, aqc_mps_compress.hip, aqc_mps_layers.hip and aqc_mps_fromvec.hip are made of: the products, the moves between
-// memory, planes and accumulators (planes_zero, plane_load, acc_store, acc_to_mem), the workgroup's sums, and -- host side, at the
-// end -- grant_dynamic_lds, the one way these seven files ask for the planes' dynamic LDS.  The truncating cut that follows an SVD of
+// aqc_mps_ent.hip, aqc_mps_compress.hip, aqc_mps_layers.hip, aqc_mps_fromvec.hip and aqc_mps_tovec.hip are made of: the products, the
+// moves between memory, planes and accumulators (planes_zero, plane_load, acc_store, acc_to_mem), the workgroup's sums, and -- host side,
+// at the end -- grant_dynamic_lds, the one way these eight files ask for the planes' dynamic LDS.  The truncating cut that follows an SVD of
 // such a sweep is in aqc_mps_cut.h.  Device code but for the grant, internal linkage.
 // A plane is [kCap][kLd] doubles; a workgroup is 4 waves, wave w owns rows [16w, 16w + 16) of a product and all four 16-column tiles.
 // Operand layout of the instruction: top of aqc_mps.hip.  Operand tiles are zero-filled beyond the given dimensions, so accumulators

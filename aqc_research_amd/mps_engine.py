@@ -222,6 +222,18 @@ class DeviceMPS:
 
         return amplitudes(self, bits, method=method)
 
+    @property
+    def device(self) -> int:
+        return int(self._L.aqc_mps_device(self.handle))
+
+    def to_vector(self, **kw):
+        """The dense vector of 2^n amplitudes (n <= 30): ``to_vectors`` of this state."""
+        return to_vectors(self, **kw)
+
+    def amplitude_blocks(self, low_qubits: int, high_bits, **kw) -> np.ndarray:
+        """The 2^low_qubits amplitudes of every listed row of high bits: ``amplitude_blocks`` of this state."""
+        return amplitude_blocks(self, low_qubits, high_bits, **kw)
+
     def pauli_strings(self, strings, *, bra=None, method=None) -> np.ndarray:
         """<self|P_s|self> (with ``bra``: <bra|P_s|self>) of the given Pauli strings: ``mps_observables.pauli_strings`` of this state."""
         from .mps_observables import pauli_strings
@@ -850,6 +862,108 @@ def from_vectors(vecs, trunc_thr: float = 0.0, max_bond: int = 0, *, device: Opt
         info = {k: v[0] for k, v in info.items()}
     info["route"], info["parts"] = route, parts
     return (made[0] if single else made), info
+
+
+# ---- MPS states into dense vectors and blocks of amplitudes (aqc_mps_to_vec, aqc_mps_amp_blocks; rules: csrc/aqc_mps_tovec_rule.h, kernels:
+# csrc/aqc_mps_tovec.hip)
+
+TO_VECTOR_FUSED_CAP = 64                                      # the planes of the fused route
+TO_VECTOR_MAX_QUBITS = 30
+AMPLITUDE_BLOCK_MAX_LOW = 24
+_TO_VECTOR_METHODS = {None: 0, "fused": 1, "gemm": 2}         # AQC_MPS_TO_VEC_*
+_TO_VECTOR_ROUTES = {1: "fused", 2: "gemm"}
+
+
+def to_vector_route(bond_dims) -> str:
+    """The route ``to_vectors`` picks for a state with these n + 1 bond dimensions: ``"fused"`` when every bond is at most
+    ``TO_VECTOR_FUSED_CAP``, else ``"gemm"``.  Host only."""
+    d = np.ascontiguousarray(bond_dims, dtype=np.int32)
+    if d.ndim != 1 or d.size < 2:
+        raise ValueError("expects the n + 1 bond dimensions of a state")
+    r = _lib.lib().aqc_mps_to_vec_route(d.size - 1, iptr(d))
+    if r not in _TO_VECTOR_ROUTES:
+        raise ValueError("expects the n + 1 bond dimensions of a state")
+    return _TO_VECTOR_ROUTES[r]
+
+
+def _to_vector_states(states, method, methods):
+    """What both calls refuse about their states and method before anything else; returns (single, states, n, bond dimensions)."""
+    if method not in methods:
+        raise ValueError(f"method must be one of {sorted(m for m in methods if m)} or None, not {method!r}")
+    single = isinstance(states, DeviceMPS)
+    items = [states] if single else states
+    if not isinstance(items, (list, tuple)) or not items or any(not isinstance(s, DeviceMPS) for s in items):
+        raise ValueError("states is a DeviceMPS or a non-empty list of them")
+    if any(not s.handle for s in items):
+        raise ValueError("a closed DeviceMPS")
+    n, dev = items[0].num_qubits, items[0].device
+    if any(s.num_qubits != n or s.device != dev for s in items):
+        raise ValueError("the states differ in size or device")
+    return single, list(items), n, [np.asarray(s.bond_dims) for s in items]
+
+
+def to_vectors(states, *, method: Optional[str] = None, out: Optional[np.ndarray] = None, details: bool = False):
+    """The dense vectors of one or many states in one call, the inverse of ``from_vectors``: ``states`` is a DeviceMPS or a list of them
+    (one qubit count, 1 <= n <= 30, one device; any gauge, any norm; they are not modified).  Returns complex128 ``[2^n]`` for a single
+    state, else ``[states][2^n]``, index bit q being site q.  ``out``: a C-contiguous complex128 array of exactly that shape, filled and
+    returned.  A state listed twice is contracted once and delivered twice; a lane's result does not depend on the other states.
+
+    ``method``: ``None`` lets the rule choose per state (``to_vector_route``).  ``"fused"`` (bonds up to ``TO_VECTOR_FUSED_CAP``) grows the
+    two halves of every state site by site on the matrix cores, all states in every launch, and writes the amplitudes in one pass;
+    ``"gemm"`` (any bond) runs the chain of batched products of the workspace's ``mps_to_vec`` on the states' own tensors.  The states go
+    in chunks under a budget of device memory (``aqc_mps_to_vec_budget``), one synchronisation and one download per chunk.
+
+    ``details``: also returns ``{"route", "split", "chunks", "launches"}``, ``route`` per state."""
+    single, items, n, dims = _to_vector_states(states, method, _TO_VECTOR_METHODS)
+    if n > TO_VECTOR_MAX_QUBITS:
+        raise ValueError(f"a dense vector takes at most {TO_VECTOR_MAX_QUBITS} qubits, the states have {n}: amplitude_blocks reads blocks of it")
+    if method == "fused":
+        for i, d in enumerate(dims):
+            if int(d.max()) > TO_VECTOR_FUSED_CAP:
+                raise ValueError(f"the fused route takes bond dimensions up to {TO_VECTOR_FUSED_CAP}; state {i} has {int(d.max())}")
+    shape = (1 << n,) if single else (len(items), 1 << n)
+    if out is not None:
+        if not isinstance(out, np.ndarray) or out.dtype != np.complex128 or out.shape != shape or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError(f"out must be a writeable C-contiguous complex128 array of shape {shape}")
+    else:
+        out = np.empty(shape, dtype=np.complex128)
+    count = len(items)
+    info = np.zeros(count + 3, dtype=np.int32)
+    handles = (c_void_p * count)(*[m.handle for m in items])
+    check(_lib.lib().aqc_mps_to_vec(handles, count, _TO_VECTOR_METHODS[method], dptr(out), iptr(info)))
+    if not details:
+        return out
+    routes = [_TO_VECTOR_ROUTES[int(r)] for r in info[:count]]
+    return out, {"route": routes[0] if single else routes, "split": int(info[count]), "chunks": int(info[count + 1]), "launches": int(info[count + 2])}
+
+
+def amplitude_blocks(states, low_qubits: int, high_bits, *, method: Optional[str] = None) -> np.ndarray:
+    """Blocks of amplitudes that share their high bits, at any n >= 2: ``high_bits`` is ``[rows][n - low_qubits]`` of 0 / 1, row r holding
+    the bits of the sites low_qubits .. n - 1 (the shape convention of ``mps_sampling.amplitudes``), shared by the states.  Returns
+    complex128 ``[rows][2^low_qubits]`` for a single state, else ``[states][rows][2^low_qubits]``: entry l of row r is psi at index
+    l + 2^low_qubits (sum_i high_bits[r][i] 2^i).  1 <= low_qubits <= min(n - 1, 24).  A block costs one walk of the high sites
+    plus one product, where ``amplitudes`` walks the chain once per number.  Fused route only (``method`` None or ``"fused"``): a bond
+    above ``TO_VECTOR_FUSED_CAP`` is refused."""
+    single, items, n, dims = _to_vector_states(states, method, {None: 0, "fused": 1})
+    k = int(low_qubits)
+    if n < 2 or k < 1 or k > min(n - 1, AMPLITUDE_BLOCK_MAX_LOW):
+        raise ValueError(f"low_qubits must be in 1 .. min(n - 1, {AMPLITUDE_BLOCK_MAX_LOW}) at n >= 2; got {low_qubits} at n = {n}")
+    arr = np.asarray(high_bits)
+    if arr.ndim != 2 or arr.shape[0] < 1 or not (np.issubdtype(arr.dtype, np.integer) or arr.dtype == np.bool_):
+        raise ValueError("high_bits is a non-empty [rows][n - low_qubits] array of bits")
+    if arr.shape[1] != n - k:
+        raise ValueError(f"a row of high_bits has {arr.shape[1]} bits, the states have {n - k} sites above the low ones")
+    if arr.min() < 0 or arr.max() > 1:
+        raise ValueError("a bit is 0 or 1")
+    for i, d in enumerate(dims):
+        if int(d.max()) > TO_VECTOR_FUSED_CAP:
+            raise ValueError(f"blocks of amplitudes take bond dimensions up to {TO_VECTOR_FUSED_CAP}; state {i} has a bond of {int(d.max())}")
+    arr = np.ascontiguousarray(arr, dtype=np.uint8)
+    count, rows = len(items), arr.shape[0]
+    out = np.empty((count, rows, 1 << k), dtype=np.complex128)
+    handles = (c_void_p * count)(*[m.handle for m in items])
+    check(_lib.lib().aqc_mps_amp_blocks(handles, count, k, rows, arr.ctypes.data_as(POINTER(ctypes.c_uint8)), 1 if method == "fused" else 0, dptr(out)))
+    return out[0] if single else out
 
 
 def fast_dot_gradient_mps(circ, thetas, lvec: DeviceMPS, vh_phi: DeviceMPS, *, trunc_thr: float = 0.0, max_bond: int = 0,

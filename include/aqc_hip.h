@@ -415,6 +415,35 @@ int64_t aqc_mps_from_vec_budget(int64_t bytes);
 int aqc_mps_from_vec(int device, int n, int lanes, const double* vecs /* [lanes][2^n] c128 */, double trunc_thr, int max_bond, int method,
                      aqc_mps** out /* [lanes] */, int32_t* bonds /* [lanes][n+1] */, double* dropped /* [lanes][n-1] */,
                      int32_t* sweeps /* [lanes][n-1] */, int32_t* status /* [lanes] */, int32_t* failed_at /* [lanes] */, int32_t* parts /* [n-1] */);
+/* MPS states into dense vectors, and into blocks of amplitudes, one or many states per call (rules: csrc/aqc_mps_tovec_rule.h, kernels:
+ * csrc/aqc_mps_tovec.hip): the inverse of aqc_mps_from_vec.  psi(b) = T_0[b_0] ... T_{n-1}[b_{n-1}] at index sum_q b_q 2^q, the site
+ * tensors as the engine keeps them (any gauge, any norm).  With k low sites, L[l] = the row vector of the sites 0 .. k - 1 and H[r] the
+ * column vector of the sites k .. n - 1, out[r 2^k + l] = sum_j H[r][j] L[l][j].  The states share n and the device and are left as
+ * they are; a state listed several times is contracted once and delivered to each of its lanes; a lane's result does not depend on
+ * which other states are in the call.  A state that holds NaN gives NaN in its own lanes, and the call returns 0.
+ * to_vec_route: host only, needs no device.  AQC_MPS_TO_VEC_FUSED when every one of the n + 1 bond dimensions is at most 64: the two
+ *   halves grow site by site on the matrix cores, all states of a chunk in every launch, and one pass writes the 2^n amplitudes
+ *   straight into the output lane.  Else AQC_MPS_TO_VEC_GEMM: the chain of batched products of aqc_ws_mps_to_vec_batch on the states'
+ *   own tensors, states of equal bonds together (-1: invalid argument).
+ * to_vec_budget: device bytes the output lanes and halves of a chunk may take (default 8 GiB): the distinct states of a call go in
+ *   chunks that fit, one synchronisation and one download per chunk; one state that does not fit is an error that names the size.  Sets
+ *   it (bytes <= 0: the default) and returns the earlier value; results do not depend on it.
+ * to_vec: 1 <= n <= 30, k = n / 2.  method AQC_MPS_TO_VEC_BY_RULE (per state), _FUSED (an error for a state with a bond above 64) or
+ *   _GEMM.  info (may be null): [nstates] the route of every state | k | chunks | launches.
+ * amp_blocks: any n >= 2, k = low_qubits in 1 .. min(n - 1, 24).  high_bits [rows][n - k]: the bits (0 / 1) of the sites k .. n - 1 of
+ *   every row, shared by the states; out [nstates][rows][2^k]: the amplitudes that share those high bits.  Fused route only: a bond
+ *   above 64 is an error that names it. */
+#define AQC_MPS_TO_VEC_BY_RULE 0
+#define AQC_MPS_TO_VEC_FUSED 1
+#define AQC_MPS_TO_VEC_GEMM 2
+int aqc_mps_to_vec_route(int n, const int32_t* dims /* [n+1] */);
+int64_t aqc_mps_to_vec_budget(int64_t bytes);
+/* device milliseconds (HIP events) of the outer-product launches of the calling thread's last to_vec / amp_blocks, summed over its
+ * chunks; -1 when that call had no state on the fused route.  For tools/mps_tovec_probe.py. */
+double aqc_mps_to_vec_outer_ms(void);
+int aqc_mps_to_vec(aqc_mps* const* states, int nstates, int method, double* out /* host [nstates][2^n] c128 */, int32_t* info /* [nstates+3] */);
+int aqc_mps_amp_blocks(aqc_mps* const* states, int nstates, int low_qubits, int64_t rows, const uint8_t* high_bits /* [rows][n-low_qubits] */,
+                       int method, double* out /* host [nstates][rows][2^low_qubits] c128 */);
 /* Whole programs of gates on MPS states, layer by layer, one or many states per call (rules: csrc/aqc_mps_layers_rule.h, kernels:
  * csrc/aqc_mps_layers.hip).  A program is nops ops in order: kinds[i] = 1, a 2 x 2 matrix on qubit qubits[i][0], or kinds[i] = 2, a 4 x 4
  * matrix (index 2 bit_a + bit_b) on the pair (qubits[i][0], qubits[i][1]), adjacent or not (routed as aqc_mps_gate2 routes it).  mats:
