@@ -549,6 +549,26 @@ hipError_t launch_mps_tovec_step(const MpsToVecArgs& a, int count, hipStream_t s
 hipError_t launch_mps_tovec_rows(const MpsToVecArgs& a, int count, hipStream_t s);    // grid (tiles of 64 listed rows, lanes)
 hipError_t launch_mps_tovec_outer(const MpsToVecArgs& a, int count, hipStream_t s);   // grid (column groups, row tiles, lanes)
 
+// aqc_mps_combine.hip (linear combinations of MPS states: the direct sum of an output's terms; rules: aqc_mps_combine_rule.h).  The terms
+// are read through the table of the call's distinct states, whose record holds sites [n] | dims [n + 1]; every output writes its own
+// stretch of one flat store.
+struct MpsCombineOutput {          // one output of a call
+    const int* term_state;         // [nterms] the record of each term's state in the table
+    const double2* coeffs;         // [nterms]
+    const int* block_off;          // [nterms + 1][n + 1] mps_combine_block_offsets
+    const size_t* site_off;        // [n + 1] element offset of assembled site q in `sites`; entry n: the elements of the output
+    double2* sites;                // <- S_0 .. S_{n-1}, every element written once
+    int nterms;
+};
+struct MpsCombineArgs {
+    const unsigned long long* table;   // a record of `per` words per distinct state
+    int per, at_sites, at_dims;
+    int nstates;                   // records of the table
+    int n, first;                  // qubits; the launch's first output
+    const MpsCombineOutput* outputs;
+};
+hipError_t launch_mps_combine_assemble(const MpsCombineArgs& a, int count, size_t largest_site, hipStream_t s);   // grid (tiles, sites, outputs)
+
 // aqc_mps_layers.hip (gate layers on MPS states, fused route; rules: aqc_mps_layers_rule.h).  A unit is one evolved state: its working
 // copy lives in the call's flat stores, every unit at the same offsets (sized by the call's bounds), the bond dimensions on the device.
 // Matrix i of a layer is (unit i / gates, gate i % gates); a chunk takes the matrices [first, first + count).

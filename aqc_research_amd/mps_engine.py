@@ -270,6 +270,14 @@ class DeviceMPS:
         self.version += 1
         return self
 
+    def plus(self, other, coeff=1.0, trunc_thr: float = 0.0, max_bond: int = 0, **kw):
+        """A new state: self + coeff other, compressed (``linear_combinations`` of the two, which it leaves as they are)."""
+        return linear_combinations([self, other], [1.0, coeff], trunc_thr, max_bond, **kw)
+
+    def scaled(self, coeff) -> "DeviceMPS":
+        """A new state: coeff self, in the engine's gauge (``linear_combinations`` of this state alone)."""
+        return linear_combinations([self], [coeff])
+
     def applied(self, gates, trunc_thr: float = 0.0, max_bond: int = 0, *, method=None, details: bool = False):
         """A new state: the program ``gates`` applied to this one (``apply_gates`` of this state, which it leaves as it is)."""
         return apply_gates(self, gates, trunc_thr, max_bond, method=method, details=details)
@@ -360,6 +368,113 @@ def compress(states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optio
             if m is not None:
                 m.close()
         raise RuntimeError(f"state {lane}, cut {cut}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
+    if not details:
+        return made[0] if single else made
+    info = {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes}
+    if single:
+        info = {k: v[0] for k, v in info.items()}
+    return (made[0] if single else made), info
+
+
+# ---- linear combinations: sums of states, compressed (aqc_mps_combine; rules: csrc/aqc_mps_combine_rule.h, kernel:
+# csrc/aqc_mps_combine.hip, the sweep of compression)
+
+def combine_route(bond_dims_of_terms) -> str:
+    """The route ``linear_combinations`` picks for an output whose terms have these bond dimensions (K rows of n + 1): ``"fused"`` when
+    every summed bond is at most ``COMPRESS_FUSED_CAP``, else ``"canonical"``."""
+    d = np.ascontiguousarray(bond_dims_of_terms, dtype=np.int32)
+    if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 2:
+        raise ValueError("expects the n + 1 bond dimensions of every term, (K, n + 1)")
+    r = _lib.lib().aqc_mps_combine_route(d.shape[1] - 1, d.shape[0], iptr(d))
+    if r not in _COMPRESS_ROUTES:
+        raise ValueError("expects the n + 1 bond dimensions of every term, (K, n + 1)")
+    return _COMPRESS_ROUTES[r]
+
+
+def _term_dims(s):
+    """The bond dimensions of a term without touching a device (a tuple is only packed); None for what is not a state."""
+    if isinstance(s, DeviceMPS):
+        if not s.handle:
+            raise ValueError("a closed DeviceMPS")
+        return s.bond_dims
+    if isinstance(s, tuple) and len(s) == 2:
+        return _pack(s)[1]
+    raise ValueError("a state is a DeviceMPS or a QiskitMPS tuple")
+
+
+def linear_combinations(states, coeffs, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
+    """New states sum_k coeffs[k] states[k], compressed: the direct sum of the terms (bonds sum_k chi^k_q, assembled on the device) goes
+    through ``compress`` at ``trunc_thr`` / ``max_bond`` -- the engine's gauge, every bond cut left to right by the engine's rank rule,
+    the same statuses.  ``states``: a list of K DeviceMPS or QiskitMPS tuples of one qubit count, any gauge; the same object may be
+    listed twice; they are not modified.  ``coeffs``: complex ``(K,)`` gives one new state, ``(J, K)`` a list of J.  An exactly zero
+    coefficient leaves its term out of that output (outputs may have different numbers of terms); a row of zeros is a ``ValueError``.
+
+    The result's ``discarded_weight`` is what the cuts of this call dropped; the weights the terms carry are not taken over.  Errors are
+    of the size of rounding relative to ``scale = sum_k |c_k| |psi_k|``, not to the norm of the result: an exact cancellation is not
+    detected (psi - psi gives rounding of that size, not a failure).
+
+    ``method``: ``None`` lets the rule choose per output (``combine_route``): ``"fused"`` (summed bonds up to ``COMPRESS_FUSED_CAP``)
+    sweeps all outputs of the call together with one synchronisation; ``"canonical"`` (any bond) adopts the sum as an engine state and
+    runs the engine's sweeps on it.  An output's result does not depend on which other outputs are in the call.
+
+    An output whose coefficients or tensors are not finite, or whose SVD reaches its sweep limit, fails alone: without ``details`` that
+    raises ``RuntimeError`` naming the output and the cut; with ``details`` its entry is ``None`` and the second return value
+    ``{"ranks", "dropped", "sweeps", "status", "route"}`` tells why."""
+    from .mps_observables import _Lanes
+
+    if method not in _COMPRESS_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'canonical', not {method!r}")
+    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
+    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
+        raise ValueError("trunc_thr and max_bond must be non-negative")
+    if not isinstance(states, list) or not states:
+        raise ValueError("states is a list of DeviceMPS or QiskitMPS tuples")
+    shapes = [_term_dims(s) for s in states]
+    if len({d.size for d in shapes}) > 1:
+        raise ValueError("the states differ in the number of qubits")
+    n = shapes[0].size - 1
+    c = np.asarray(coeffs, dtype=np.complex128)
+    single = c.ndim == 1
+    if c.ndim not in (1, 2) or c.shape[-1] != len(states) or c.size == 0:
+        raise ValueError(f"coeffs must have shape ({len(states)},) or (J, {len(states)})")
+    c = np.atleast_2d(c)
+    term_off, term_state, routes = [0], [], []
+    for j, row in enumerate(c):
+        used = [k for k in range(len(states)) if row[k] != 0]   # (NaN != 0: a NaN coefficient is data, and fails its output)
+        if not used:
+            raise ValueError(f"output {j}: every coefficient is zero")
+        term_state += used
+        term_off.append(len(term_state))
+        route = combine_route(np.stack([shapes[k] for k in used]))
+        if method == "fused" and route != "fused":
+            raise ValueError(f"the fused route takes summed bond dimensions up to {COMPRESS_FUSED_CAP} (output {j})")
+        routes.append(method or route)
+    term_off, term_state = np.array(term_off, dtype=np.int32), np.array(term_state, dtype=np.int32)
+    cf = np.ascontiguousarray(np.concatenate([row[term_state[term_off[j]:term_off[j + 1]]] for j, row in enumerate(c)]))
+    # the same object listed twice is uploaded once and is one state of the call
+    first, distinct = {}, []
+    for s in states:
+        if id(s) not in first:
+            first[id(s)] = len(distinct)
+            distinct.append(s)
+    index = np.array([first[id(s)] for s in states], dtype=np.int32)
+    term_state = np.ascontiguousarray(index[term_state])
+    count = c.shape[0]
+    with _Lanes(distinct) as lanes:
+        out = (c_void_p * count)()
+        ranks, sweeps = np.zeros((count, max(n - 1, 0)), dtype=np.int32), np.zeros((count, max(n - 1, 0)), dtype=np.int32)
+        dropped, status = np.zeros((count, max(n - 1, 0)), dtype=np.float64), np.zeros(count, dtype=np.int32)
+        check(_lib.lib().aqc_mps_combine(lanes.handles(), len(lanes.lanes), count, iptr(term_off), iptr(term_state), dptr(cf), trunc_thr, max_bond,
+                                         _COMPRESS_METHODS[method], out, iptr(ranks), dptr(dropped), iptr(sweeps), iptr(status)))
+        made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
+    bad = np.flatnonzero(status)
+    if bad.size and not details:
+        lane = int(bad[0])
+        cut = int(np.flatnonzero(ranks[lane] == 0)[0]) + 1 if n > 1 else 0
+        for m in made:
+            if m is not None:
+                m.close()
+        raise RuntimeError(f"output {lane}, cut {cut}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
     if not details:
         return made[0] if single else made
     info = {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes}

@@ -388,6 +388,32 @@ int64_t aqc_mps_compress_svd_budget(int64_t bytes);
 int aqc_mps_compress(aqc_mps* const* states, int nstates, double trunc_thr, int max_bond, int method, aqc_mps** out /* [nstates] */,
                      int32_t* ranks /* [nstates][n-1] */, double* dropped /* [nstates][n-1] */, int32_t* sweeps /* [nstates][n-1] */,
                      int32_t* status /* [nstates] */);
+/* Linear combinations of MPS states: output j = sum over its terms of c_t psi_{term_state[t]}, t = term_off[j] .. term_off[j+1] - 1,
+ * compressed; one or many outputs per call (rules: csrc/aqc_mps_combine_rule.h, kernel: csrc/aqc_mps_combine.hip, the sweep of
+ * aqc_mps_compress).  The states may be in any gauge, share n >= 1 and the device, and are left bit for bit as they are; a state may
+ * appear in several terms and several outputs.  The direct sum S of an output's terms (summed bonds Sigma_q = sum_k chi^k_q, the
+ * coefficients on site 0, block-diagonal middle sites) is assembled on the device, and out[j] is compress(S, trunc_thr, max_bond) as
+ * aqc_mps_compress states it: a NEW state (the caller destroys it) in the engine's gauge, every bond cut left to right by the engine's
+ * rank rule, the same statuses.  Its discarded weight is what the cuts of THIS call dropped: the weights the terms carry are not taken
+ * over.  Errors are of the size of rounding relative to scale = sum_k |c_k| |psi_k|, not to the norm of the result: an exact
+ * cancellation is not detected (what is left of psi - psi is rounding of that size, normalised by the cuts' spectra as any state).
+ * n = 1: the 2-vector sum_k c_k T^k_0.  An output's result does not depend on which other outputs are in the call.
+ * combine_route: host only, needs no device.  dims: the bonds of one output's terms.  AQC_MPS_ENT_FUSED when every summed bond is at most
+ *   AQC_MPS_ENT_FUSED_CAP (all outputs advance through one sweep together, one synchronisation per call), else AQC_MPS_ENT_CANONICAL
+ *   (the assembled sum becomes an engine state with unit bond vectors and takes the canonical route of aqc_mps_compress)
+ *   (-1: invalid argument).
+ * combine_svd_budget: as aqc_mps_compress_svd_budget, for this call.
+ * combine: method as for aqc_mps_compress, per output.  coeffs: (re, im) per term; they need not be finite: an output with a NaN
+ *   coefficient or tensor fails alone with status 2 and a null out[j], as does a zero sum of one qubit; status 1 as for compression.
+ *   ranks, dropped, sweeps, status as there, per output; they may be null.  out is nulled before anything else can fail.  Argument
+ *   errors (null pointers, states that differ in size or device, a term table that does not start at 0, has an output without terms
+ *   or names a state outside the call, a negative or non-finite trunc_thr, a negative max_bond, the fused route beyond its cap) are
+ *   reported before any device work. */
+int aqc_mps_combine_route(int n, int nterms, const int32_t* dims /* [nterms][n+1] */);
+int64_t aqc_mps_combine_svd_budget(int64_t bytes);
+int aqc_mps_combine(aqc_mps* const* states, int nstates, int nout, const int32_t* term_off /* [nout+1] */, const int32_t* term_state /* [terms] */,
+                    const double* coeffs /* [terms][2] */, double trunc_thr, int max_bond, int method, aqc_mps** out /* [nout] */,
+                    int32_t* ranks /* [nout][n-1] */, double* dropped /* [nout][n-1] */, int32_t* sweeps /* [nout][n-1] */, int32_t* status /* [nout] */);
 /* Dense vectors into MPS states: one or many vectors of 2^n c128 amplitudes (index bit q is site q, any norm, left as they are) per call
  * (rules: csrc/aqc_mps_fromvec_rule.h, kernels: csrc/aqc_mps_fromvec.hip).  out[i] is a NEW state (the caller destroys it) in the engine's
  * gauge, as aqc_mps_compress returns it: every bond cut left to right by the engine's rank rule at trunc_thr / max_bond
