@@ -569,6 +569,32 @@ struct MpsCombineArgs {
 };
 hipError_t launch_mps_combine_assemble(const MpsCombineArgs& a, int count, size_t largest_site, hipStream_t s);   // grid (tiles, sites, outputs)
 
+// aqc_mps_opsum.hip (operator sums on MPS states: the direct sum of an output's terms c_t O_t psi_t; rules: aqc_mps_opsum_rule.h).  The
+// states are read through the table of the call's distinct states as above, the operators through one packed buffer of 8-byte words:
+// site offsets [nops][n + 1] (elements of the data) | dims [nops][n + 1] (ints) | the data (complex elements, 16-byte aligned).
+struct MpsOpsumOutput {            // one output of a call
+    const int* term_state;         // [nterms] the record of each term's state in the table
+    const int* term_op;            // [nterms] the term's operator in the packed buffer, -1: none
+    const double2* coeffs;         // [nterms]
+    const int* block_off;          // [nterms + 1][n + 1] mps_combine_block_offsets of the product bonds
+    const int* chi;                // [nterms][n + 1] the bonds of each term's state
+    const size_t* site_off;        // [n + 1] element offset of assembled site q in `sites`; entry n: the elements of the output
+    double2* sites;                // <- S_0 .. S_{n-1}, every element written once
+    int nterms;
+};
+struct MpsOpsumArgs {
+    const unsigned long long* table;   // a record of `per` words per distinct state
+    int per, at_sites, at_dims;
+    int nstates;                   // records of the table
+    int n, first;                  // qubits; the launch's first output
+    const unsigned long long* ops;     // the packed operators
+    int nops;
+    size_t at_op_dims, at_op_data;     // word offsets of the dims and of the data
+    size_t op_elems;               // complex elements of the data
+    const MpsOpsumOutput* outputs;
+};
+hipError_t launch_mps_opsum_assemble(const MpsOpsumArgs& a, int count, size_t largest_site, hipStream_t s);   // grid (tiles, sites, outputs)
+
 // aqc_mps_layers.hip (gate layers on MPS states, fused route; rules: aqc_mps_layers_rule.h).  A unit is one evolved state: its working
 // copy lives in the call's flat stores, every unit at the same offsets (sized by the call's bounds), the bond dimensions on the device.
 // Matrix i of a layer is (unit i / gates, gate i % gates); a chunk takes the matrices [first, first + count).

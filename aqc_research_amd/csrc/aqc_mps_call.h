@@ -1,11 +1,12 @@
 // The skeleton of a call that reads single-lane MPS states (aqc_mps_obs_api.cpp, aqc_mps_sample_api.cpp, aqc_mps_pauli_api.cpp,
-// aqc_mps_ent_api.cpp, aqc_mps_compress_api.cpp, aqc_mps_combine_api.cpp, aqc_mps_layers_api.cpp, aqc_mps_tovec_api.cpp): check the handles, view the distinct states, pack what the kernels read
+// aqc_mps_ent_api.cpp, aqc_mps_compress_api.cpp, aqc_mps_combine_api.cpp, aqc_mps_opsum_api.cpp, aqc_mps_layers_api.cpp, aqc_mps_tovec_api.cpp): check the handles, view the distinct states, pack what the kernels read
 // of them into one table, launch on the first state's stream, synchronise once, assemble.  Each of those files keeps its own plan,
 // launches and results; what they share about their input states is here and in the HIP-free aqc_mps_states_rule.h.  The second
 // half holds the host scaffolding of a truncating sweep (aqc_mps_compress_api.cpp, aqc_mps_layers_api.cpp, aqc_mps_fromvec_api.cpp;
 // DESIGN.md 6w, "Sweep calls"): the argument checks, the chunk budget, the stores of a chunk of the batched SVD (those also in aqc_mps_ent_api.cpp),
 // flat stores sized by static bounds, and the adoption of the new states from them; the device side of the cut is aqc_mps_cut.h; the
-// sweep over whole states that compression and linear combinations share is aqc_mps_sweep.h.
+// sweep over whole states that compression, linear combinations and operator sums share is aqc_mps_sweep.h (the two that sweep a direct
+// sum share aqc_mps_sum_call.h on top of it).
 // Private to csrc/ (everything has internal linkage).
 #pragma once
 #include <algorithm>

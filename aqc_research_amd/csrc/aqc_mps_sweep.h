@@ -1,5 +1,5 @@
-// The truncating sweep over whole states that compression (aqc_mps_compress_api.cpp) and linear combinations
-// (aqc_mps_combine_api.cpp) share, on both routes (rules: aqc_mps_compress_rule.h; kernels: aqc_mps_compress.hip, the right factors by
+// The truncating sweep over whole states that compression (aqc_mps_compress_api.cpp), linear combinations
+// (aqc_mps_combine_api.cpp) and operator sums (aqc_mps_opsum_api.cpp; both through aqc_mps_sum_call.h) share, on both routes (rules: aqc_mps_compress_rule.h; kernels: aqc_mps_compress.hip, the right factors by
 // aqc_mps_ent.hip, the SVDs of a step by aqc_svd_batch.hip).  A state to sweep is site pointers and bond dimensions: it need not be an
 // engine state (the assembled sites of a direct sum are not).
 //   fused      FusedSweep::run enqueues, for all its states together: the right chain, then per chunk of states and per bond form /

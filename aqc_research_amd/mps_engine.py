@@ -278,6 +278,10 @@ class DeviceMPS:
         """A new state: coeff self, in the engine's gauge (``linear_combinations`` of this state alone)."""
         return linear_combinations([self], [coeff])
 
+    def applied_operator(self, op, trunc_thr: float = 0.0, max_bond: int = 0, **kw):
+        """A new state: the ``MPO`` ``op`` applied to this one, compressed (``apply_operator`` of this state, which it leaves as it is)."""
+        return apply_operator(op, self, trunc_thr, max_bond, **kw)
+
     def applied(self, gates, trunc_thr: float = 0.0, max_bond: int = 0, *, method=None, details: bool = False):
         """A new state: the program ``gates`` applied to this one (``apply_gates`` of this state, which it leaves as it is)."""
         return apply_gates(self, gates, trunc_thr, max_bond, method=method, details=details)
@@ -481,6 +485,282 @@ def linear_combinations(states, coeffs, trunc_thr: float = 0.0, max_bond: int = 
     if single:
         info = {k: v[0] for k, v in info.items()}
     return (made[0] if single else made), info
+
+
+# ---- operator sums: sum_t c_t O_t psi_t, compressed (aqc_mps_opsum; rules: csrc/aqc_mps_opsum_rule.h, kernel: csrc/aqc_mps_opsum.hip,
+# the sweep of compression)
+
+_PAULIS = (np.eye(2, dtype=np.complex128), _X, _Y, _Z)
+MPO_DENSE_MAX_QUBITS = 12
+
+
+class MPO:
+    """A matrix-product operator on the host: sites W_q of shape ``(D_q, D_{q+1}, 2, 2)``, complex128, indexed ``[a][b][s_out][s_in]``,
+    D_0 = D_n = 1.  O(b_out, b_in) = W_0[:, :, b_out0, b_in0] ... W_{n-1}[...] as a product of D x D matrices; qubit q is index bit q of
+    the dense vector (the project's order).  No gauge or Hermiticity is assumed.  Immutable: the sites are copies that cannot be written."""
+
+    __slots__ = ("_sites", "_dims")
+
+    def __init__(self, sites):
+        if not isinstance(sites, (list, tuple)) or len(sites) < 1:
+            raise ValueError("an MPO is a non-empty list of site tensors (D_q, D_{q+1}, 2, 2)")
+        made, dims = [], [1]
+        for q, w in enumerate(sites):
+            w = np.array(w, dtype=np.complex128, order="C")
+            if w.ndim != 4 or w.shape[2:] != (2, 2) or w.shape[0] < 1 or w.shape[1] < 1:
+                raise ValueError(f"MPO site {q}: expects shape (D_q, D_q+1, 2, 2), not {w.shape}")
+            if w.shape[0] != dims[-1]:
+                raise ValueError(f"MPO site {q}: its left bond {w.shape[0]} differs from the bond {dims[-1]} before it")
+            dims.append(w.shape[1])
+            w.setflags(write=False)
+            made.append(w)
+        if dims[-1] != 1:
+            raise ValueError(f"the last bond of an MPO is 1, not {dims[-1]}")
+        object.__setattr__(self, "_sites", tuple(made))
+        object.__setattr__(self, "_dims", np.array(dims, dtype=np.int32))
+        self._dims.setflags(write=False)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("an MPO is immutable")
+
+    @property
+    def sites(self):
+        return self._sites
+
+    @property
+    def num_qubits(self) -> int:
+        return len(self._sites)
+
+    @property
+    def bond_dims(self) -> np.ndarray:
+        """D_0 .. D_n."""
+        return self._dims
+
+    def to_dense(self) -> np.ndarray:
+        """The 2^n x 2^n matrix (n <= ``MPO_DENSE_MAX_QUBITS``), row b_out, column b_in, contracted from site 0 on."""
+        n = self.num_qubits
+        if n > MPO_DENSE_MAX_QUBITS:
+            raise ValueError(f"to_dense takes operators on up to {MPO_DENSE_MAX_QUBITS} qubits, not {n}")
+        acc = np.ones((1, 1, 1), dtype=np.complex128)   # [rows][columns][bond]
+        for w in self._sites:
+            r, c = acc.shape[:2]
+            acc = np.einsum("rca,abst->srtcb", acc, w).reshape(2 * r, 2 * c, w.shape[1])   # bit q is the major one so far
+        return np.ascontiguousarray(acc[:, :, 0])
+
+    @classmethod
+    def product_operator(cls, matrices) -> "MPO":
+        """M_0 on qubit 0 (x) M_1 on qubit 1 ...: bond dimension 1 (projectors, local rotations)."""
+        if not isinstance(matrices, (list, tuple)) or len(matrices) < 1:
+            raise ValueError("expects a non-empty list of 2 x 2 matrices")
+        mats = [np.asarray(m, dtype=np.complex128) for m in matrices]
+        if any(m.shape != (2, 2) for m in mats):
+            raise ValueError("expects 2 x 2 matrices")
+        return cls([m.reshape(1, 1, 2, 2) for m in mats])
+
+    @classmethod
+    def identity(cls, num_qubits: int) -> "MPO":
+        if int(num_qubits) < 1:
+            raise ValueError("an operator acts on at least one qubit")
+        return cls.product_operator([_PAULIS[0]] * int(num_qubits))
+
+    @staticmethod
+    def _letters(strings, num_qubits):
+        from .mps_observables import _strings
+
+        if num_qubits is None:
+            first = strings[0] if isinstance(strings, (list, tuple)) and len(strings) else None
+            if isinstance(strings, np.ndarray) and strings.ndim == 2:
+                num_qubits = strings.shape[1]
+            elif isinstance(first, str):
+                num_qubits = len(first)
+            else:
+                raise ValueError("num_qubits is needed for strings given as (letters, qubits)")
+        if int(num_qubits) < 1:
+            raise ValueError("an operator acts on at least one qubit")
+        return _strings(strings, int(num_qubits))
+
+    @classmethod
+    def from_pauli_string(cls, string, coeff=1.0, *, num_qubits: Optional[int] = None) -> "MPO":
+        """coeff P for one Pauli string as ``mps_observables.pauli_strings`` takes it (letter q acts on qubit q): bond dimension 1,
+        the coefficient on site 0."""
+        return cls.from_pauli_sum([(coeff, string)], num_qubits=num_qubits)
+
+    @classmethod
+    def from_pauli_sum(cls, terms, *, num_qubits: Optional[int] = None) -> "MPO":
+        """sum_k w_k P_k for ``terms = [(weight, string), ...]`` as ``mps_observables.energy`` takes them, complex weights allowed: the
+        direct sum of the strings, bond dimension = the number of terms, exact (nothing is compressed); the weights sit on site 0."""
+        if not isinstance(terms, (list, tuple)) or len(terms) < 1 or any(not (isinstance(t, tuple) and len(t) == 2) for t in terms):
+            raise ValueError("terms is a non-empty list of (weight, string)")
+        w = np.array([complex(t[0]) for t in terms], dtype=np.complex128)
+        strings = [t[1] for t in terms]
+        letters = cls._letters(np.stack(strings) if isinstance(strings[0], np.ndarray) else strings, num_qubits)
+        k, n = letters.shape
+        if n == 1:
+            return cls([sum(w[t] * _PAULIS[letters[t, 0]] for t in range(k)).reshape(1, 1, 2, 2)])
+        sites = []
+        for q in range(n):
+            site = np.zeros((1 if q == 0 else k, 1 if q == n - 1 else k, 2, 2), dtype=np.complex128)
+            for t in range(k):
+                site[0 if q == 0 else t, 0 if q == n - 1 else t] = (w[t] if q == 0 else 1.0) * _PAULIS[letters[t, q]]
+            sites.append(site)
+        return cls(sites)
+
+    @classmethod
+    def xxz(cls, num_qubits: int, delta: float) -> "MPO":
+        """H = -1/4 sum_i (X_i X_{i+1} + Y_i Y_{i+1} + delta Z_i Z_{i+1}) on the open chain of ``xxz.py``: the automaton of bond
+        dimension 5 (0: nothing placed yet, 1 .. 3: X, Y, Z placed on the site before, 4: a bond term is complete)."""
+        n, delta = int(num_qubits), float(delta)
+        if n < 1:
+            raise ValueError("an operator acts on at least one qubit")
+        if n == 1:
+            return cls([np.zeros((1, 1, 2, 2), dtype=np.complex128)])
+        full = np.zeros((5, 5, 2, 2), dtype=np.complex128)
+        full[0, 0] = full[4, 4] = _PAULIS[0]
+        for a, (p, weight) in enumerate(((_X, -0.25), (_Y, -0.25), (_Z, -0.25 * delta)), start=1):
+            full[0, a] = p
+            full[a, 4] = weight * p
+        return cls([full[:1]] + [full] * (n - 2) + [full[:, 4:]])
+
+
+def _op_dims(op):
+    if not isinstance(op, MPO):
+        raise ValueError("an operator is an MPO or None")
+    return op.bond_dims
+
+
+def opsum_route(bond_dims_of_states, bond_dims_of_ops) -> str:
+    """The route ``operator_sums`` picks for an output whose terms have states and operators of these bond dimensions (K rows of n + 1
+    each; ``None`` in place of an operator's row: no operator): ``"fused"`` when every summed product bond sum_t D^t_q chi^t_q is at most
+    ``COMPRESS_FUSED_CAP``, else ``"canonical"``.  An XXZ Hamiltonian (D = 5) alone stays fused for state bonds up to 12, a Pauli string
+    (D = 1) up to 64."""
+    bad = "expects the n + 1 bond dimensions of every term's state and operator, (K, n + 1) each"
+    try:
+        d = np.ascontiguousarray(bond_dims_of_states, dtype=np.int32)
+        if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 2 or len(bond_dims_of_ops) != d.shape[0]:
+            raise ValueError(bad)
+        w = np.ascontiguousarray([np.ones(d.shape[1], dtype=np.int32) if r is None else np.asarray(r, dtype=np.int32) for r in bond_dims_of_ops], dtype=np.int32)
+    except (TypeError, ValueError):
+        raise ValueError(bad) from None
+    if w.shape != d.shape:
+        raise ValueError(bad)
+    r = _lib.lib().aqc_mps_opsum_route(d.shape[1] - 1, d.shape[0], iptr(d), iptr(w))
+    if r not in _COMPRESS_ROUTES:
+        raise ValueError(bad)
+    return _COMPRESS_ROUTES[r]
+
+
+def operator_sums(outputs, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
+    """New states sum_t c_t O_t psi_t, compressed, one per output: ``outputs`` is a list of outputs, each a list of terms
+    ``(coeff, op_or_None, state)`` with ``op`` an ``MPO`` (``None``: the identity, the state itself) and ``state`` a DeviceMPS or a
+    QiskitMPS tuple of the operator's qubit count, any gauge.  H psi, (H - E) psi and a Lanczos residual H v - alpha v - beta w are one
+    output each, and all outputs of a call share one truncating sweep.  Nothing given is modified; operators and states that are the same
+    object are uploaded once.  An exactly zero coefficient leaves its term out; an output left without terms is a ``ValueError``.
+
+    The product O psi has bonds D_q chi_q (``MPO.bond_dims`` times the state's), the direct sum of an output's terms the sum of those;
+    it is assembled on the device and goes through ``compress`` at ``trunc_thr`` / ``max_bond`` -- the engine's gauge, every bond cut
+    left to right by the engine's rank rule, the same statuses.  The result's ``discarded_weight`` is what the cuts of this call dropped.
+    Errors are of the size of rounding relative to ``scale = sum_t |c_t| |O_t|_2 |psi_t|``, not to the norm of the result.
+
+    ``method``: ``None`` lets the rule choose per output (``opsum_route``): ``"fused"`` (summed product bonds up to
+    ``COMPRESS_FUSED_CAP``: an XXZ Hamiltonian on state bonds up to 12, Pauli strings up to 64) sweeps all outputs of the call together
+    with one synchronisation; ``"canonical"`` (any bond) adopts the sum as an engine state and runs the engine's sweeps on it.  An
+    output's result does not depend on which other outputs are in the call.
+
+    An output that is exactly zero (a projector that annihilates the state), whose coefficients, operator entries or tensors are not
+    finite, or whose SVD reaches its sweep limit fails alone: without ``details`` that raises ``RuntimeError`` naming the output and the
+    cut; with ``details`` its entry is ``None`` and the second return value ``{"ranks", "dropped", "sweeps", "status", "route"}`` tells
+    why."""
+    from .mps_observables import _Lanes
+
+    if method not in _COMPRESS_METHODS:
+        raise ValueError(f"method must be None, 'fused' or 'canonical', not {method!r}")
+    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
+    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
+        raise ValueError("trunc_thr and max_bond must be non-negative")
+    if not isinstance(outputs, list) or not outputs:
+        raise ValueError("outputs is a non-empty list of outputs, each a list of (coeff, op_or_None, state)")
+    states, ops, state_at, op_at = [], [], {}, {}
+    term_off, term_state, term_op, cf, routes, n = [0], [], [], [], [], None
+    for j, terms in enumerate(outputs):
+        if not isinstance(terms, list) or any(not (isinstance(t, tuple) and len(t) == 3) for t in terms):
+            raise ValueError(f"output {j}: expects a list of (coeff, op_or_None, state)")
+        chi, dop = [], []
+        for coeff, op, state in terms:
+            coeff = complex(coeff)
+            sd = _term_dims(state)
+            od = None if op is None else _op_dims(op)
+            n = sd.size - 1 if n is None else n
+            if sd.size - 1 != n:
+                raise ValueError("the states differ in the number of qubits")
+            if od is not None and od.size - 1 != n:
+                raise ValueError(f"output {j}: an operator on {od.size - 1} qubits meets a state of {n}")
+            if coeff == 0:   # (NaN != 0: a NaN coefficient is data, and fails its output)
+                continue
+            if id(state) not in state_at:
+                state_at[id(state)] = len(states)
+                states.append(state)
+            if op is not None and id(op) not in op_at:
+                op_at[id(op)] = len(ops)
+                ops.append(op)
+            term_state.append(state_at[id(state)])
+            term_op.append(-1 if op is None else op_at[id(op)])
+            cf.append(coeff)
+            chi.append(sd)
+            dop.append(od)
+        if len(term_state) == term_off[-1]:
+            raise ValueError(f"output {j}: no term is left (an output needs a term with a coefficient that is not zero)")
+        term_off.append(len(term_state))
+        route = opsum_route(np.stack(chi), dop)
+        if method == "fused" and route != "fused":
+            raise ValueError(f"the fused route takes summed product bond dimensions up to {COMPRESS_FUSED_CAP} (output {j})")
+        routes.append(method or route)
+    term_off, term_state, term_op = (np.array(a, dtype=np.int32) for a in (term_off, term_state, term_op))
+    cf = np.ascontiguousarray(cf, dtype=np.complex128)
+    op_dims = np.ascontiguousarray([op.bond_dims for op in ops], dtype=np.int32).reshape(len(ops), n + 1)
+    sizes = np.array([[w.size for w in op.sites] for op in ops], dtype=np.int64).reshape(len(ops), n)
+    op_off = np.zeros((len(ops), n + 1), dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(sizes.sum(axis=1))]) if len(ops) else np.zeros(1, dtype=np.int64)
+    for k in range(len(ops)):
+        op_off[k] = starts[k] + np.concatenate([[0], np.cumsum(sizes[k])])
+    op_data = np.ascontiguousarray(np.concatenate([w.ravel() for op in ops for w in op.sites])) if ops else np.zeros(1, dtype=np.complex128)
+    count = len(outputs)
+    with _Lanes(states) as lanes:
+        out = (c_void_p * count)()
+        ranks, sweeps = np.zeros((count, max(n - 1, 0)), dtype=np.int32), np.zeros((count, max(n - 1, 0)), dtype=np.int32)
+        dropped, status = np.zeros((count, max(n - 1, 0)), dtype=np.float64), np.zeros(count, dtype=np.int32)
+        check(_lib.lib().aqc_mps_opsum(lanes.handles(), len(lanes.lanes), len(ops), iptr(op_dims) if ops else None,
+                                       op_off.ctypes.data_as(POINTER(ctypes.c_int64)) if ops else None, dptr(op_data) if ops else None, count,
+                                       iptr(term_off), iptr(term_state), iptr(term_op), dptr(cf), trunc_thr, max_bond, _COMPRESS_METHODS[method], out,
+                                       iptr(ranks), dptr(dropped), iptr(sweeps), iptr(status)))
+        made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
+    bad = np.flatnonzero(status)
+    if bad.size and not details:
+        lane = int(bad[0])
+        cut = int(np.flatnonzero(ranks[lane] == 0)[0]) + 1 if n > 1 else 0
+        for m in made:
+            if m is not None:
+                m.close()
+        raise RuntimeError(f"output {lane}, cut {cut}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
+    if not details:
+        return made
+    return made, {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes}
+
+
+def apply_operator(op, states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
+    """New states O psi, compressed: ``operator_sums`` with one term per output.  ``states``: a DeviceMPS or a QiskitMPS tuple gives a
+    state, a list gives a list."""
+    single = isinstance(states, (DeviceMPS, tuple))
+    items = [states] if single else states
+    if not isinstance(items, list) or not items:
+        raise ValueError("states is a DeviceMPS, a QiskitMPS tuple or a non-empty list of those")
+    if not isinstance(op, MPO):
+        raise ValueError("an operator is an MPO")
+    result = operator_sums([[(1.0, op, s)] for s in items], trunc_thr, max_bond, method=method, details=details)
+    if not single:
+        return result
+    if not details:
+        return result[0]
+    return result[0][0], {k: v[0] for k, v in result[1].items()}
 
 
 def svd(a: np.ndarray, device: Optional[int] = None):

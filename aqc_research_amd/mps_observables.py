@@ -359,6 +359,29 @@ def energy(states, terms, *, method: Optional[str] = None) -> np.ndarray:
     return pauli_strings(states, strings, method=method).real @ w
 
 
+def variance(states, op, *, method: Optional[str] = None) -> np.ndarray:
+    """<O psi|O psi> / <psi|psi> - |<psi|O psi> / <psi|psi>|^2 for an ``mps_engine.MPO``: ``()`` for one state, ``(lanes,)`` for a list.
+    O psi of every state comes from ONE ``mps_engine.apply_operator`` call (exact: nothing is truncated), the three overlaps of every
+    state from ``overlaps``.  For a Hermitian operator this is the variance of O in psi; it is zero on an eigenstate up to rounding of
+    the size of |O|_2^2.  A state that O annihilates has no O psi: ``RuntimeError``, as ``apply_operator`` raises it."""
+    from .mps_engine import MPO, apply_operator
+
+    if not isinstance(op, MPO):
+        raise ValueError("an operator is an MPO")
+    single, count, n = _shape_of(states)
+    if op.num_qubits != n:
+        raise ValueError(f"an operator on {op.num_qubits} qubits meets a state of {n}")
+    with _Lanes(states) as kets:
+        images = apply_operator(op, kets.lanes, method=method)
+        try:   # <psi|psi>, <psi|O psi>, <O psi|O psi> of every state: the identity string between 3 x lanes pairs, one call
+            g = _pauli_call(kets.lanes + kets.lanes + images, kets.lanes + images + images, np.zeros((1, n), dtype=np.uint8), None)[:, 0].reshape(3, count)
+        finally:
+            for m in images:
+                m.close()
+    out = g[2].real / g[0].real - np.abs(g[1] / g[0].real) ** 2
+    return out[0] if single else out
+
+
 # ---- entanglement: the Schmidt spectra of every cut (aqc_mps_ent_schmidt; rules: csrc/aqc_mps_ent_rule.h, kernels: csrc/aqc_mps_ent.hip)
 
 _ENT_METHODS = {None: 0, "fused": 1, "canonical": 2}   # AQC_MPS_ENT_*

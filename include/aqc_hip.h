@@ -414,6 +414,40 @@ int64_t aqc_mps_combine_svd_budget(int64_t bytes);
 int aqc_mps_combine(aqc_mps* const* states, int nstates, int nout, const int32_t* term_off /* [nout+1] */, const int32_t* term_state /* [terms] */,
                     const double* coeffs /* [terms][2] */, double trunc_thr, int max_bond, int method, aqc_mps** out /* [nout] */,
                     int32_t* ranks /* [nout][n-1] */, double* dropped /* [nout][n-1] */, int32_t* sweeps /* [nout][n-1] */, int32_t* status /* [nout] */);
+/* Operator sums on MPS states: output j = sum over its terms of c_t O_t psi_t, t = term_off[j] .. term_off[j+1] - 1, compressed; O_t is
+ * operator term_op[t] of the call, or absent (term_op[t] = -1: the identity), psi_t is state term_state[t]; one or many outputs per call
+ * (rules: csrc/aqc_mps_opsum_rule.h, kernel: csrc/aqc_mps_opsum.hip, the sweep of aqc_mps_compress).  A strict generalisation of
+ * aqc_mps_combine: H psi, (H - E) psi and a Lanczos residual H v - alpha v - beta w are one call with one truncating sweep each.
+ * An operator (MPO) on n qubits has sites W_q [D_q][D_{q+1}][2][2], complex, indexed [a][b][s_out][s_in], D_0 = D_n = 1:
+ * O(b_out, b_in) = W_0[., ., b_out0, b_in0] ... W_{n-1}[...] as a product of D x D matrices, qubit q index bit q of the dense vector; no
+ * gauge or Hermiticity is assumed.  The operators of a call come packed: op_dims[o] are D_0 .. D_n of operator o, its site q lies at
+ * complex element op_site_off[o][q] of op_data and is 4 D_q D_{q+1} elements long, op_site_off[o][n] is the operator's end.  The
+ * product O psi has sites P_q[s][(a, i), (b, j)] = sum_{s'} W_q[a][b][s][s'] T_q[s'][i][j] with bonds D_q chi_q (the operator index is the
+ * major one); the direct sum of an output's terms (the coefficients on site 0) is assembled on the device, and out[j] is
+ * compress(S, trunc_thr, max_bond) as aqc_mps_compress states it: a NEW state (the caller destroys it), its discarded weight what the cuts
+ * of THIS call dropped.  The states are left bit for bit as they are.  Errors are of the size of rounding relative to
+ * scale = sum_t |c_t| |O_t|_2 |psi_t|, not to the norm of the result.  n = 1: the 2-vector sum_t c_t W^t_0[0][0] T^t_0.  An output's
+ * result does not depend on which other outputs are in the call.
+ * opsum_route: host only.  state_dims, op_dims: the bonds of one output's terms and of their operators (a row of ones for a term without
+ *   operator).  AQC_MPS_ENT_FUSED when every summed product bond sum_t D^t_q chi^t_q is at most AQC_MPS_ENT_FUSED_CAP, else
+ *   AQC_MPS_ENT_CANONICAL, as for aqc_mps_combine (-1: invalid argument).  An XXZ Hamiltonian (D = 5) alone stays fused for state bonds
+ *   up to 12, Pauli strings (D = 1) up to 64.
+ * opsum_svd_budget: as aqc_mps_compress_svd_budget, for this call.
+ * opsum: method as for aqc_mps_compress, per output.  coeffs: (re, im) per term.  Coefficients and operator entries need not be
+ *   finite: an output with a NaN in them or in a tensor fails alone with status 2 and a null out[j], as does an output that is exactly
+ *   zero (a projector that annihilates the state); status 1 as for compression.  nops may be 0 (then the op_* arrays may be null).
+ *   ranks, dropped, sweeps, status as for aqc_mps_combine; they may be null.  out is nulled before anything else can fail.  Argument errors
+ *   (null pointers, states that differ in size or device, a term table that does not start at 0, has an output without terms or names
+ *   a state or an operator outside the call, operator dims that are not those of an operator on n qubits or offsets that are not their
+ *   packed layout, a negative or non-finite trunc_thr, a negative max_bond, the fused route beyond its cap, a summed product bond
+ *   beyond 2^20) are reported before any device work. */
+int aqc_mps_opsum_route(int n, int nterms, const int32_t* state_dims /* [nterms][n+1] */, const int32_t* op_dims /* [nterms][n+1] */);
+int64_t aqc_mps_opsum_svd_budget(int64_t bytes);
+int aqc_mps_opsum(aqc_mps* const* states, int nstates, int nops, const int32_t* op_dims /* [nops][n+1] */, const int64_t* op_site_off /* [nops][n+1] */,
+                  const double* op_data /* complex elements (re, im) */, int nout, const int32_t* term_off /* [nout+1] */,
+                  const int32_t* term_state /* [terms] */, const int32_t* term_op /* [terms], -1: none */, const double* coeffs /* [terms][2] */,
+                  double trunc_thr, int max_bond, int method, aqc_mps** out /* [nout] */, int32_t* ranks /* [nout][n-1] */,
+                  double* dropped /* [nout][n-1] */, int32_t* sweeps /* [nout][n-1] */, int32_t* status /* [nout] */);
 /* Dense vectors into MPS states: one or many vectors of 2^n c128 amplitudes (index bit q is site q, any norm, left as they are) per call
  * (rules: csrc/aqc_mps_fromvec_rule.h, kernels: csrc/aqc_mps_fromvec.hip).  out[i] is a NEW state (the caller destroys it) in the engine's
  * gauge, as aqc_mps_compress returns it: every bond cut left to right by the engine's rank rule at trunc_thr / max_bond
