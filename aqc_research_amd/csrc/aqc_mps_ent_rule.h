@@ -8,7 +8,7 @@
 //   cut q   (qubits 0 .. q-1 | q .. n-1, q = 1 .. n-1): the Schmidt values are the singular values of S_q = C_q D_q^T (chi_q x chi_q),
 //           descending.  Nothing is normalised: sum_k s_k^2 = <psi|psi> at every cut.
 //   R       by unpivoted Householder reflections, R only: column j takes its reflection from rows j .. of the stacked matrix, a column
-//           that is exactly zero there is skipped, the last row needs none; no Q is kept.  Any R with R^H R = M^H M gives the same
+//           that is zero there (or below 1e-150: mps_ent_reflects) is skipped, the last row needs none; no Q is kept.  Any R with R^H R = M^H M gives the same
 //           singular values, so rank-deficient bonds need no special case.  (Eigenvalues of L_q R_q would square the condition number
 //           and lose every value below about 1e-8 s_max.)
 //   route   fused (one workgroup walks the whole chain of factors inside one launch, the stacked matrix in LDS; the cuts' SVDs in one
@@ -58,6 +58,10 @@ AQC_ENT_HD inline int mps_ent_reflections(int rows, int cols) { return rows - 1 
 // rows of the R factor that can be non-zero
 AQC_ENT_HD inline int mps_ent_r_rows(int rows, int cols) { return rows < cols ? rows : cols; }
 
+// Whether a column with this sum of squares takes a reflection: not when it is zero, nor when it is so small (|x| < 1e-150: columns of
+// deeply rank-deficient states) that tau below, 1 / (|x| (|x| + |x0|)), would overflow; a NaN reflects (and spreads).
+AQC_ENT_HD inline bool mps_ent_reflects(double norm2) { return !(norm2 < 1e-300); }
+
 // One reflection from the column x (its first entry x0, sum of squares norm2 > 0): H = 1 - tau v v^H with v = x + phase |x| e_0,
 // H x = alpha e_0.  Stated on real numbers so that the device code takes the same operations.
 struct MpsEntReflection { double v0r, v0i, alphar, alphai, tau; };
@@ -82,7 +86,7 @@ inline void mps_ent_householder_r(int rows, int cols, std::complex<double>* m) {
     for (int j = 0; j < nref; ++j) {
         double norm2 = 0.0;
         for (int r = j; r < rows; ++r) norm2 += std::norm(m[(size_t)r * cols + j]);
-        if (norm2 == 0.0) continue;
+        if (!mps_ent_reflects(norm2)) continue;
         const cd x0 = m[(size_t)j * cols + j];
         const MpsEntReflection h = mps_ent_reflection(x0.real(), x0.imag(), norm2);
         v[0] = cd(h.v0r, h.v0i);

@@ -32,7 +32,7 @@ __device__ __forceinline__ void householder_lds(double* smem, int chi_in, int ch
     __syncthreads();
     for (int j = 0; j < nref; ++j) {
         const double norm2 = (np[0] + np[1]) + (np[2] + np[3]);
-        const bool reflect = !(norm2 == 0.0);   // the same for every thread; a NaN reflects
+        const bool reflect = mps_ent_reflects(norm2);   // the same for every thread; a NaN reflects
         const int jj = stacked_at(j, j, chi_in);
         const MpsEntReflection h = mps_ent_reflection(smem[jj], smem[jj + kPlane], norm2);
         if (tid < rows - j) {   // rows - j <= kEntRows <= the workgroup

@@ -962,7 +962,9 @@ def _apply(circ, thetas, mps: DeviceMPS, inverse: bool, trunc_thr: float, max_bo
             return out
         if method == "lockstep":
             raise LanesRefused("aqc_hip: the state or a bond on the way exceeds the lockstep lanes (bonds <= 32)")
-    return _apply_circuit(circ, thetas, mps.clone(), inverse, trunc_thr, max_bond)
+    out = _apply_circuit(circ, thetas, mps.clone(), inverse, trunc_thr, max_bond)
+    out.version = 0   # a new state, as the lanes' route hands it out
+    return out
 
 
 def v_mul_mps(circ, thetas, mps: DeviceMPS, trunc_thr: float = 0.0, max_bond: int = 0, method: Optional[str] = None) -> DeviceMPS:

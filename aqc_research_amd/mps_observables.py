@@ -356,7 +356,7 @@ def energy(states, terms, *, method: Optional[str] = None) -> np.ndarray:
     strings = [t[1] for t in terms]
     if isinstance(strings[0], np.ndarray):
         strings = np.stack(strings)
-    return pauli_strings(states, strings, method=method).real @ w
+    return (pauli_strings(states, strings, method=method).real * w).sum(axis=-1)   # row by row: a state's sum does not depend on the other lanes
 
 
 def variance(states, op, *, method: Optional[str] = None) -> np.ndarray:

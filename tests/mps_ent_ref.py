@@ -15,14 +15,15 @@ from tests import mps_obs_ref
 
 
 def householder_r(m: np.ndarray) -> np.ndarray:
-    """The cols x cols R factor of ``m`` (rows x cols): column j takes its reflection from rows j .., a column that is exactly zero
-    there is skipped, the last row needs none; rows beyond min(rows, cols) are zero."""
+    """The cols x cols R factor of ``m`` (rows x cols): column j takes its reflection from rows j .., a column that is zero
+    there (or below 1e-150, where its reflection cannot be formed: ``mps_ent_reflects`` of the rule) is skipped, the last row needs
+    none; rows beyond min(rows, cols) are zero."""
     a = np.array(m, dtype=np.complex128)
     rows, cols = a.shape
     for j in range(min(rows - 1, cols)):
         x = a[j:, j].copy()
         norm2 = float(np.sum(x.real ** 2 + x.imag ** 2))
-        if norm2 == 0.0:
+        if norm2 < 1e-300:   # zero, or so small (|x| < 1e-150: deeply rank-deficient sums) that the reflection's 1 / |x|^2 overflows
             continue
         nrm, ax = np.sqrt(norm2), abs(x[0])
         phase = x[0] / ax if ax > 0.0 else 1.0
