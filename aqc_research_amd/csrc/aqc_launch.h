@@ -141,6 +141,7 @@ struct ProjArgs {
     int* vcount;
     int* vlane_parts;
     int batch;
+    int item0;               // kernels with the items in grid.y: the first item of this launch (launch_project, the sums of the fused pass)
 };
 hipError_t launch_project_init(const ProjArgs& a, hipStream_t s);
 hipError_t launch_project_fused(const ProjArgs& a, const void* mend, void* ctile, void* yout, hipStream_t s, int qb);   // qb: 2 or 4 blocks of u per wave; both products of the objective by projection, one fetch of y

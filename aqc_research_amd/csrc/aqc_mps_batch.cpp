@@ -519,7 +519,8 @@ int aqc_mpsb_create(int device, int num_qubits, int lanes, aqc_mpsb** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return failf("no HIP device available: the aqc_hip path has no CPU fallback");
     if (device < 0 || device >= ndev) return failf("device out of range");
-    if (num_qubits < 2 || num_qubits > 4096 || lanes < 1 || lanes > 32767) return failf("number of qubits / lanes out of range");
+    if (num_qubits < 2 || num_qubits > 4096) return failf("number of qubits out of range");
+    if (lanes < 1 || lanes > 32767) return failf("lanes must be in [1, 32767] (a gate launch has two workgroups per lane in the y dimension of its grid)");
     HIP_OK(hipSetDevice(device));
     aqc_mpsb* b = new aqc_mpsb();
     b->device = device; b->n = num_qubits; b->L = lanes; b->active = lanes;
@@ -661,8 +662,9 @@ int aqc_mpsb_vh(aqc_mpsb* b, const aqc_circuit* circ, const double* thetas, doub
 
 /* K lhs states shared by all lanes (the states S|0>, S X_i|0> of a general state preparation, objective_base.py:345-435), bonds <= 32 */
 int aqc_mpsb_set_bank(aqc_mpsb* b, aqc_mps* const* states, int count) {
-    if (!b || !states) return failf("null argument");
-    if (count < 1 || count > 32767) return failf("bank: count out of range");
+    if (!b) return failf("null argument");
+    if (count < 1 || count > 32767) return failf("bank: count must be in [1, 32767]");
+    if (!states) return failf("null argument");
     HIP_OK(hipSetDevice(b->device));
     b->have_bank = false;
     if (b->bank.L != count) {

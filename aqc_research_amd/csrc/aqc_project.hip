@@ -12,6 +12,7 @@
 // A (2^cb x 2^nk) by (2^nk x 2^nkeep) complex product per item on the fp64 matrix cores; Y is read once, which is what a launch costs.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 
 #include "aqc_launch.h"
@@ -41,7 +42,7 @@ __device__ __forceinline__ size_t pj_tile_bits(const ProjArgs& a, int tile) {   
 // 16 values of k a lane loads the 4 elements k = 16 kb + 4 (lane / 16) + jj of its row(s) of Y and of its row of S.
 template <int RB, int NB>
 __global__ __launch_bounds__(256) void project_kernel(const ProjArgs a) {
-    const int item = blockIdx.y;
+    const int item = a.item0 + (int)blockIdx.y;
     if (item >= *a.nitems) return;
     const TileItem it = a.items[item];
     const size_t ebits = pj_tile_bits(a, it.tile);
@@ -128,7 +129,7 @@ constexpr int kPjRow = 17;   // elements per LDS row
 // shared tile that is double-buffered over the blocks of k: one workgroup barrier per block.)
 __global__ __launch_bounds__(256) void project_staged_kernel(const ProjArgs a) {
     extern __shared__ __attribute__((aligned(16))) char pj_smem[];
-    const int item = blockIdx.y;
+    const int item = a.item0 + (int)blockIdx.y;
     if (item >= *a.nitems) return;   // (uniform over the workgroup: before any barrier)
     const TileItem it = a.items[item];
     const size_t ebits = pj_tile_bits(a, it.tile);
@@ -196,26 +197,39 @@ __global__ __launch_bounds__(256) void project_staged_kernel(const ProjArgs a) {
     }
 }
 
-hipError_t launch_project(const ProjArgs& a, hipStream_t s) {
-    if (a.staged) {   // (the host has checked: the low four bits of k are address bits 0..3 of both operands)
-        if (a.keep_bits < 4 || a.k_bits < 4 || a.cb < 0 || a.cb > 12 || a.batch < 1 || !a.y || !a.s || !a.out) return hipErrorInvalidValue;
-        const int blocks = 1 << (a.keep_bits - 4);
-        project_staged_kernel<<<dim3((unsigned)((blocks + 3) / 4), (unsigned)(2 * a.batch)), 256, 6 * 16 * kPjRow * sizeof(cplx), s>>>(a);
-        return hipGetLastError();
+// The kernels above (and the two sums of the fused pass) take their item from grid.y, and there are two items per lane: from 32768
+// lanes on they pass the 65535 that a grid's y dimension is good for, so these go out as one launch per kPjGridY items (a.item0)
+constexpr int kPjGridY = 65535;
+template <typename Launch>
+static hipError_t pj_for_items(const ProjArgs& a, Launch launch) {
+    ProjArgs q = a;
+    for (q.item0 = 0; q.item0 < 2 * a.batch; q.item0 += kPjGridY) {
+        launch(q, (unsigned)std::min(kPjGridY, 2 * a.batch - q.item0));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
     }
+    return hipSuccess;
+}
+
+hipError_t launch_project(const ProjArgs& a, hipStream_t s) {
     if (a.keep_bits < 4 || a.k_bits < 4 || a.cb < 0 || a.cb > 12 || a.batch < 1 || !a.y || !a.s || !a.out) return hipErrorInvalidValue;
     const int blocks = 1 << (a.keep_bits - 4);
+    if (a.staged)   // (the host has checked: the low four bits of k are address bits 0..3 of both operands)
+        return pj_for_items(a, [&](const ProjArgs& q, unsigned ny) {
+            project_staged_kernel<<<dim3((unsigned)((blocks + 3) / 4), ny), 256, 6 * 16 * kPjRow * sizeof(cplx), s>>>(q);
+        });
     const bool wide = blocks >= 16;   // four blocks of `keep` per wave: S is fetched once for four columns of Y
-    const dim3 grid((unsigned)((blocks / (wide ? 4 : 1) + 3) / 4), (unsigned)(2 * a.batch));
-    if (wide) {
-        if (a.cb <= 4) project_kernel<4, 1><<<grid, 256, 0, s>>>(a);
-        else project_kernel<4, 2><<<grid, 256, 0, s>>>(a);
-    } else {
-        if (a.cb <= 4) project_kernel<1, 1><<<grid, 256, 0, s>>>(a);
-        else if (a.cb == 5) project_kernel<1, 2><<<grid, 256, 0, s>>>(a);
-        else project_kernel<1, 4><<<grid, 256, 0, s>>>(a);
-    }
-    return hipGetLastError();
+    return pj_for_items(a, [&](const ProjArgs& q, unsigned ny) {
+        const dim3 grid((unsigned)((blocks / (wide ? 4 : 1) + 3) / 4), ny);
+        if (wide) {
+            if (a.cb <= 4) project_kernel<4, 1><<<grid, 256, 0, s>>>(q);
+            else project_kernel<4, 2><<<grid, 256, 0, s>>>(q);
+        } else {
+            if (a.cb <= 4) project_kernel<1, 1><<<grid, 256, 0, s>>>(q);
+            else if (a.cb == 5) project_kernel<1, 2><<<grid, 256, 0, s>>>(q);
+            else project_kernel<1, 4><<<grid, 256, 0, s>>>(q);
+        }
+    });
 }
 
 // The lhs state of the virtual register, M_0[i_T, c] = [i_T on the shared bits = c][i_T on the other touched bits = the tile's], and
@@ -448,7 +462,7 @@ __global__ __launch_bounds__(64 * (16 / QB), 1) void project_fused_kernel(const 
 // more than 256 values of u: the workgroups of an item leave partial projections in consecutive copies of the virtual register
 // (part_stride apart); this adds copies 1 .. nparts - 1 into copy 0, in that order
 __global__ __launch_bounds__(256) void project_sum_kernel(const ProjArgs a, double2* __restrict__ yout, int nparts) {
-    const int item = blockIdx.y;
+    const int item = a.item0 + (int)blockIdx.y;
     if (item >= *a.nitems) return;
     const TileItem it = a.items[item];
     const size_t vbase = ((size_t)it.lane * 2 + it.slot) << a.nvp;
@@ -460,7 +474,7 @@ __global__ __launch_bounds__(256) void project_sum_kernel(const ProjArgs a, doub
 }
 // ... and the shares of the tile product over i_T (blockIdx.z of the fused pass): added in share order into the tile of ZW
 __global__ __launch_bounds__(256) void project_csum_kernel(const ProjArgs a, double2* __restrict__ ctile, int nshares, int nitems_max) {
-    const int item = blockIdx.y;
+    const int item = a.item0 + (int)blockIdx.y;
     if (item >= *a.nitems) return;
     const TileItem it = a.items[item];
     const size_t ebits = pj_tile_bits(a, it.tile);
@@ -507,17 +521,16 @@ hipError_t launch_project_fused(const ProjArgs& a, const void* mend, void* ctile
         if (masked) project_fused_kernel<4, true><<<grid, 256, lds4, s>>>(a, m, c, y);
         else project_fused_kernel<4, false><<<grid, 256, lds4, s>>>(a, m, c, y);
     }
-    if (nparts > 1) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        project_sum_kernel<<<dim3((unsigned)(((1u << (a.t + a.cb)) + 255) / 256), (unsigned)(2 * a.batch)), 256, 0, s>>>(a, y, nparts);
-    }
-    if (nshares > 1) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        project_csum_kernel<<<dim3((unsigned)(((16u << a.us_bits) + 255) / 256), (unsigned)(2 * a.batch)), 256, 0, s>>>(a, c, nshares, 2 * a.batch);
-    }
-    return hipGetLastError();
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && nparts > 1)
+        e = pj_for_items(a, [&](const ProjArgs& q, unsigned ny) {
+            project_sum_kernel<<<dim3((unsigned)(((1u << (a.t + a.cb)) + 255) / 256), ny), 256, 0, s>>>(q, y, nparts);
+        });
+    if (e == hipSuccess && nshares > 1)
+        e = pj_for_items(a, [&](const ProjArgs& q, unsigned ny) {
+            project_csum_kernel<<<dim3((unsigned)(((16u << a.us_bits) + 255) / 256), ny), 256, 0, s>>>(q, c, nshares, 2 * a.batch);
+        });
+    return e;
 }
 
 // Amplitudes <g|V^H y> of gather indices g that lie OUTSIDE the lane's first-stage tile but share its index on the first stage's local

@@ -1575,9 +1575,7 @@ class LockstepLanes:
     def set_bank(self, states) -> "LockstepLanes":
         """A bank of K lhs states shared by all lanes (``aqc_mpsb_set_bank``; bonds <= 32): the states S|0>, S X_i|0> of a general
         state preparation, whose amplitudes ``apply_vh_bank`` returns.  Unchanged states since the last call are not copied again."""
-        lst = list(states)
-        if not lst:
-            raise ValueError("the bank needs at least one state")
+        lst = list(states)   # (the count is the library's to refuse: 1 .. 32767)
         return self._load("_bank", lst, lambda: check(_lib.lib().aqc_mpsb_set_bank(self.handle, (c_void_p * len(lst))(*[m.handle for m in lst]), len(lst))))
 
     def apply_vh_bank(self, circ, thetas, *, trunc_thr: float = 0.0, max_bond: int = 0, half: bool = False, details: bool = False):
