@@ -298,6 +298,143 @@ class DeviceMPS:
             pass
 
 
+# ---- what the wrappers of the many-state calls share (the Python side of DESIGN.md §6w): the states of a call, its method and
+# truncation, the rule's route, and the new states of a truncating call
+
+_BOND_DIMS_OF_A_STATE = "expects the n + 1 bond dimensions of a state"
+
+
+def _is_tuple_state(s) -> bool:
+    return isinstance(s, tuple) and len(s) == 2   # a QiskitMPS (gammas, lambdas); several states come as a list
+
+
+def _call_states(states, device_only: bool = False):
+    """``(single, items, n, bond dimensions)`` of the states of a call -- a DeviceMPS, a QiskitMPS tuple or a list of those -- read on
+    the host, so that a refused call uploads nothing (a tuple is only packed).  ``device_only``: DeviceMPS only, on one device."""
+    if device_only:
+        single = isinstance(states, DeviceMPS)
+        items = [states] if single else states
+        if not isinstance(items, (list, tuple)) or not items or any(not isinstance(s, DeviceMPS) for s in items):
+            raise ValueError("states is a DeviceMPS or a non-empty list of them")
+    else:
+        single = isinstance(states, DeviceMPS) or _is_tuple_state(states)
+        if not single and not isinstance(states, list):
+            raise ValueError("states is a DeviceMPS, a QiskitMPS tuple or a list of those")
+        items = [states] if single else states
+        if not items:
+            raise ValueError("expects at least one state")
+    dims = []
+    for s in items:
+        if isinstance(s, DeviceMPS):
+            if not s.handle:
+                raise ValueError("a closed DeviceMPS")
+            dims.append(np.asarray(s.bond_dims))
+        elif _is_tuple_state(s):
+            dims.append(_pack(s)[1])
+        else:
+            raise ValueError("a state is a DeviceMPS or a QiskitMPS tuple")
+    if len({d.size for d in dims}) > 1 or (device_only and len({s.device for s in items}) > 1):
+        raise ValueError("the states differ in size or device" if device_only else "the states differ in the number of qubits")
+    return single, list(items), dims[0].size - 1, dims
+
+
+def _handles(lanes):
+    """Open DeviceMPS states as the handle array that the native calls take."""
+    return (c_void_p * len(lanes))(*[m.handle for m in lanes])
+
+
+class _Lanes:
+    """The states of a call as DeviceMPS handles.  Making one reads the states on the host (``_call_states``: ``single``, ``items``,
+    ``n``, ``dims``) and refuses what is no call; entering it uploads the tuples; what was uploaded for the call is closed on exit."""
+
+    def __init__(self, states):
+        self.single, self.items, self.n, self.dims = _call_states(states)
+        self.own = []
+        self.lanes = []
+
+    def __enter__(self):
+        try:
+            for s in self.items:
+                if not isinstance(s, DeviceMPS):
+                    s = DeviceMPS.from_qiskit(s, assume_canonical=True)   # exact arithmetic: the gauge is taken as it is
+                    self.own.append(s)
+                self.lanes.append(s)
+        except Exception:
+            self.__exit__(None, None, None)
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.own:
+            m.close()
+        self.own = []
+        return False
+
+    def handles(self):
+        return _handles(self.lanes)
+
+
+def _method_code(method, table) -> int:
+    """The native code of a call's ``method`` out of the call's table of them."""
+    if method not in table:
+        names = [repr(k) for k in table]
+        raise ValueError(f"method must be {', '.join(names[:-1])} or {names[-1]}, not {method!r}")
+    return table[method]
+
+
+def _within_fused_cap(method, dims, cap: int) -> None:
+    """Refuses ``method="fused"`` for a state beyond the cap, before the native call."""
+    if method == "fused":
+        for d in dims:
+            if int(d.max()) > cap:
+                raise ValueError(f"the fused route takes bond dimensions up to {cap}, not {int(d.max())}")
+
+
+def _truncation(trunc_thr, max_bond) -> Tuple[float, int]:
+    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
+    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
+        raise ValueError("trunc_thr and max_bond must be non-negative")
+    return trunc_thr, max_bond
+
+
+def _route_of(entry: str, names: dict, refusal: str, args) -> str:
+    """The answer of the native rule ``entry`` to ``args`` by name (``args`` None: the caller's shape test failed); what the test or the
+    rule itself refuses is a ``ValueError``."""
+    r = getattr(_lib.lib(), entry)(*args) if args is not None else -1
+    if r not in names:
+        raise ValueError(refusal)
+    return names[r]
+
+
+def _adopt(out):
+    """The handle array that a truncating call filled as ``DeviceMPS | None`` per lane."""
+    return [DeviceMPS(c_void_p(h)) if h else None for h in out]
+
+
+def _failed_cut(ranks) -> int:
+    """The cut at which a lane of a sweep failed: the first one without a rank (0 for a single site)."""
+    return int(np.flatnonzero(ranks == 0)[0]) + 1 if ranks.size else 0
+
+
+def _finish(made, status, words, place, single, details, per_lane, per_call=()):
+    """What a truncating call returns.  A lane with a status failed: without ``details`` every state the call made is closed and the
+    first such lane raises ``RuntimeError`` (``place(lane)``: where, ``words``: why); with ``details`` its entry of ``made`` is None.
+    ``per_lane`` info is unwrapped with the states for a single one, ``per_call`` info is not."""
+    bad = np.flatnonzero(status)
+    if bad.size and not details:
+        lane = int(bad[0])
+        for m in made:
+            if m is not None:
+                m.close()
+        raise RuntimeError(f"{place(lane)}: {words.get(int(status[lane]), 'failed')}")
+    result = made[0] if single else made
+    if not details:
+        return result
+    info = {k: v[0] for k, v in per_lane.items()} if single else dict(per_lane)
+    info.update(per_call)
+    return result, info
+
+
 # ---- compression: canonical form and truncation of every bond (aqc_mps_compress; rules: csrc/aqc_mps_compress_rule.h, kernels:
 # csrc/aqc_mps_compress.hip)
 
@@ -311,12 +448,7 @@ def compress_route(bond_dims) -> str:
     """The route ``compress`` picks for a state with these n + 1 bond dimensions: ``"fused"`` when every bond is at most
     ``COMPRESS_FUSED_CAP``, else ``"canonical"``."""
     d = np.ascontiguousarray(bond_dims, dtype=np.int32)
-    if d.ndim != 1 or d.size < 2:
-        raise ValueError("expects the n + 1 bond dimensions of a state")
-    r = _lib.lib().aqc_mps_compress_route(d.size - 1, iptr(d))
-    if r not in _COMPRESS_ROUTES:
-        raise ValueError("expects the n + 1 bond dimensions of a state")
-    return _COMPRESS_ROUTES[r]
+    return _route_of("aqc_mps_compress_route", _COMPRESS_ROUTES, _BOND_DIMS_OF_A_STATE, (d.size - 1, iptr(d)) if d.ndim == 1 and d.size >= 2 else None)
 
 
 def compress(states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
@@ -335,49 +467,21 @@ def compress(states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optio
     A state that is zero or not finite, or whose SVD reaches its sweep limit, fails alone: without ``details`` that raises
     ``RuntimeError`` naming the lane and the cut; with ``details`` its entry is ``None`` and the second return value
     ``{"ranks", "dropped", "sweeps", "status", "route"}`` tells why (ranks are 0 from the failed cut on)."""
-    from .mps_observables import _Lanes
-
-    if method not in _COMPRESS_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'canonical', not {method!r}")
-    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
-    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
-        raise ValueError("trunc_thr and max_bond must be non-negative")
-    items = [states] if isinstance(states, (DeviceMPS, tuple)) else states
-    if isinstance(items, list):   # refused before anything is uploaded: tuples that differ in size, the fused route beyond its cap
-        shapes = []
-        for s in items:
-            if isinstance(s, DeviceMPS) and s.handle:
-                shapes.append(s.bond_dims)
-            elif isinstance(s, tuple) and len(s) == 2:
-                shapes.append(_pack(s)[1])
-        if len({d.size for d in shapes}) > 1:
-            raise ValueError("the states differ in the number of qubits")
-        if method == "fused" and any(int(d.max()) > COMPRESS_FUSED_CAP for d in shapes):
-            raise ValueError(f"the fused route takes bond dimensions up to {COMPRESS_FUSED_CAP}")
-    with _Lanes(states) as lanes:
-        count, n = len(lanes.lanes), lanes.lanes[0].num_qubits
-        routes = [method or compress_route(m.bond_dims) for m in lanes.lanes]
-        out = (c_void_p * count)()
-        ranks, sweeps = np.zeros((count, n - 1), dtype=np.int32), np.zeros((count, n - 1), dtype=np.int32)
-        dropped, status = np.zeros((count, n - 1), dtype=np.float64), np.zeros(count, dtype=np.int32)
-        check(_lib.lib().aqc_mps_compress(lanes.handles(), count, trunc_thr, max_bond, _COMPRESS_METHODS[method], out, iptr(ranks), dptr(dropped),
-                                          iptr(sweeps), iptr(status)))
-        made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
-        single = lanes.single
-    bad = np.flatnonzero(status)
-    if bad.size and not details:
-        lane = int(bad[0])
-        cut = int(np.flatnonzero(ranks[lane] == 0)[0]) + 1 if n > 1 else 0
-        for m in made:
-            if m is not None:
-                m.close()
-        raise RuntimeError(f"state {lane}, cut {cut}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
-    if not details:
-        return made[0] if single else made
-    info = {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes}
-    if single:
-        info = {k: v[0] for k, v in info.items()}
-    return (made[0] if single else made), info
+    code = _method_code(method, _COMPRESS_METHODS)
+    trunc_thr, max_bond = _truncation(trunc_thr, max_bond)
+    lanes = _Lanes(states)
+    if method == "fused" and any(int(d.max()) > COMPRESS_FUSED_CAP for d in lanes.dims):
+        raise ValueError(f"the fused route takes bond dimensions up to {COMPRESS_FUSED_CAP}")
+    count, n = len(lanes.items), lanes.n
+    routes = [method or compress_route(d) for d in lanes.dims]
+    out = (c_void_p * count)()
+    ranks, sweeps = np.zeros((count, n - 1), dtype=np.int32), np.zeros((count, n - 1), dtype=np.int32)
+    dropped, status = np.zeros((count, n - 1), dtype=np.float64), np.zeros(count, dtype=np.int32)
+    with lanes:
+        check(_lib.lib().aqc_mps_compress(lanes.handles(), count, trunc_thr, max_bond, code, out, iptr(ranks), dptr(dropped), iptr(sweeps), iptr(status)))
+        made = _adopt(out)
+    return _finish(made, status, _COMPRESS_STATUS, lambda lane: f"state {lane}, cut {_failed_cut(ranks[lane])}", lanes.single, details,
+                   {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes})
 
 
 # ---- linear combinations: sums of states, compressed (aqc_mps_combine; rules: csrc/aqc_mps_combine_rule.h, kernel:
@@ -387,23 +491,9 @@ def combine_route(bond_dims_of_terms) -> str:
     """The route ``linear_combinations`` picks for an output whose terms have these bond dimensions (K rows of n + 1): ``"fused"`` when
     every summed bond is at most ``COMPRESS_FUSED_CAP``, else ``"canonical"``."""
     d = np.ascontiguousarray(bond_dims_of_terms, dtype=np.int32)
-    if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 2:
-        raise ValueError("expects the n + 1 bond dimensions of every term, (K, n + 1)")
-    r = _lib.lib().aqc_mps_combine_route(d.shape[1] - 1, d.shape[0], iptr(d))
-    if r not in _COMPRESS_ROUTES:
-        raise ValueError("expects the n + 1 bond dimensions of every term, (K, n + 1)")
-    return _COMPRESS_ROUTES[r]
-
-
-def _term_dims(s):
-    """The bond dimensions of a term without touching a device (a tuple is only packed); None for what is not a state."""
-    if isinstance(s, DeviceMPS):
-        if not s.handle:
-            raise ValueError("a closed DeviceMPS")
-        return s.bond_dims
-    if isinstance(s, tuple) and len(s) == 2:
-        return _pack(s)[1]
-    raise ValueError("a state is a DeviceMPS or a QiskitMPS tuple")
+    fits = d.ndim == 2 and d.shape[0] >= 1 and d.shape[1] >= 2
+    return _route_of("aqc_mps_combine_route", _COMPRESS_ROUTES, "expects the n + 1 bond dimensions of every term, (K, n + 1)",
+                     (d.shape[1] - 1, d.shape[0], iptr(d)) if fits else None)
 
 
 def linear_combinations(states, coeffs, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
@@ -424,19 +514,19 @@ def linear_combinations(states, coeffs, trunc_thr: float = 0.0, max_bond: int = 
     An output whose coefficients or tensors are not finite, or whose SVD reaches its sweep limit, fails alone: without ``details`` that
     raises ``RuntimeError`` naming the output and the cut; with ``details`` its entry is ``None`` and the second return value
     ``{"ranks", "dropped", "sweeps", "status", "route"}`` tells why."""
-    from .mps_observables import _Lanes
-
-    if method not in _COMPRESS_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'canonical', not {method!r}")
-    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
-    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
-        raise ValueError("trunc_thr and max_bond must be non-negative")
+    code = _method_code(method, _COMPRESS_METHODS)
+    trunc_thr, max_bond = _truncation(trunc_thr, max_bond)
     if not isinstance(states, list) or not states:
         raise ValueError("states is a list of DeviceMPS or QiskitMPS tuples")
-    shapes = [_term_dims(s) for s in states]
-    if len({d.size for d in shapes}) > 1:
-        raise ValueError("the states differ in the number of qubits")
-    n = shapes[0].size - 1
+    # the same object listed twice is uploaded once and is one state of the call
+    first, distinct = {}, []
+    for s in states:
+        if id(s) not in first:
+            first[id(s)] = len(distinct)
+            distinct.append(s)
+    index = np.array([first[id(s)] for s in states], dtype=np.int32)
+    lanes = _Lanes(distinct)
+    shapes, n = [lanes.dims[k] for k in index], lanes.n
     c = np.asarray(coeffs, dtype=np.complex128)
     single = c.ndim == 1
     if c.ndim not in (1, 2) or c.shape[-1] != len(states) or c.size == 0:
@@ -455,36 +545,17 @@ def linear_combinations(states, coeffs, trunc_thr: float = 0.0, max_bond: int = 
         routes.append(method or route)
     term_off, term_state = np.array(term_off, dtype=np.int32), np.array(term_state, dtype=np.int32)
     cf = np.ascontiguousarray(np.concatenate([row[term_state[term_off[j]:term_off[j + 1]]] for j, row in enumerate(c)]))
-    # the same object listed twice is uploaded once and is one state of the call
-    first, distinct = {}, []
-    for s in states:
-        if id(s) not in first:
-            first[id(s)] = len(distinct)
-            distinct.append(s)
-    index = np.array([first[id(s)] for s in states], dtype=np.int32)
     term_state = np.ascontiguousarray(index[term_state])
     count = c.shape[0]
-    with _Lanes(distinct) as lanes:
-        out = (c_void_p * count)()
-        ranks, sweeps = np.zeros((count, max(n - 1, 0)), dtype=np.int32), np.zeros((count, max(n - 1, 0)), dtype=np.int32)
-        dropped, status = np.zeros((count, max(n - 1, 0)), dtype=np.float64), np.zeros(count, dtype=np.int32)
+    out = (c_void_p * count)()
+    ranks, sweeps = np.zeros((count, max(n - 1, 0)), dtype=np.int32), np.zeros((count, max(n - 1, 0)), dtype=np.int32)
+    dropped, status = np.zeros((count, max(n - 1, 0)), dtype=np.float64), np.zeros(count, dtype=np.int32)
+    with lanes:
         check(_lib.lib().aqc_mps_combine(lanes.handles(), len(lanes.lanes), count, iptr(term_off), iptr(term_state), dptr(cf), trunc_thr, max_bond,
-                                         _COMPRESS_METHODS[method], out, iptr(ranks), dptr(dropped), iptr(sweeps), iptr(status)))
-        made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
-    bad = np.flatnonzero(status)
-    if bad.size and not details:
-        lane = int(bad[0])
-        cut = int(np.flatnonzero(ranks[lane] == 0)[0]) + 1 if n > 1 else 0
-        for m in made:
-            if m is not None:
-                m.close()
-        raise RuntimeError(f"output {lane}, cut {cut}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
-    if not details:
-        return made[0] if single else made
-    info = {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes}
-    if single:
-        info = {k: v[0] for k, v in info.items()}
-    return (made[0] if single else made), info
+                                         code, out, iptr(ranks), dptr(dropped), iptr(sweeps), iptr(status)))
+        made = _adopt(out)
+    return _finish(made, status, _COMPRESS_STATUS, lambda lane: f"output {lane}, cut {_failed_cut(ranks[lane])}", single, details,
+                   {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes})
 
 
 # ---- operator sums: sum_t c_t O_t psi_t, compressed (aqc_mps_opsum; rules: csrc/aqc_mps_opsum_rule.h, kernel: csrc/aqc_mps_opsum.hip,
@@ -641,12 +712,7 @@ def opsum_route(bond_dims_of_states, bond_dims_of_ops) -> str:
         w = np.ascontiguousarray([np.ones(d.shape[1], dtype=np.int32) if r is None else np.asarray(r, dtype=np.int32) for r in bond_dims_of_ops], dtype=np.int32)
     except (TypeError, ValueError):
         raise ValueError(bad) from None
-    if w.shape != d.shape:
-        raise ValueError(bad)
-    r = _lib.lib().aqc_mps_opsum_route(d.shape[1] - 1, d.shape[0], iptr(d), iptr(w))
-    if r not in _COMPRESS_ROUTES:
-        raise ValueError(bad)
-    return _COMPRESS_ROUTES[r]
+    return _route_of("aqc_mps_opsum_route", _COMPRESS_ROUTES, bad, (d.shape[1] - 1, d.shape[0], iptr(d), iptr(w)) if w.shape == d.shape else None)
 
 
 def operator_sums(outputs, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
@@ -670,13 +736,8 @@ def operator_sums(outputs, trunc_thr: float = 0.0, max_bond: int = 0, *, method:
     finite, or whose SVD reaches its sweep limit fails alone: without ``details`` that raises ``RuntimeError`` naming the output and the
     cut; with ``details`` its entry is ``None`` and the second return value ``{"ranks", "dropped", "sweeps", "status", "route"}`` tells
     why."""
-    from .mps_observables import _Lanes
-
-    if method not in _COMPRESS_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'canonical', not {method!r}")
-    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
-    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
-        raise ValueError("trunc_thr and max_bond must be non-negative")
+    code = _method_code(method, _COMPRESS_METHODS)
+    trunc_thr, max_bond = _truncation(trunc_thr, max_bond)
     if not isinstance(outputs, list) or not outputs:
         raise ValueError("outputs is a non-empty list of outputs, each a list of (coeff, op_or_None, state)")
     states, ops, state_at, op_at = [], [], {}, {}
@@ -687,7 +748,7 @@ def operator_sums(outputs, trunc_thr: float = 0.0, max_bond: int = 0, *, method:
         chi, dop = [], []
         for coeff, op, state in terms:
             coeff = complex(coeff)
-            sd = _term_dims(state)
+            sd = _call_states([state])[3][0]   # (a term takes one state: a list in its place is refused as no state)
             od = None if op is None else _op_dims(op)
             n = sd.size - 1 if n is None else n
             if sd.size - 1 != n:
@@ -724,26 +785,17 @@ def operator_sums(outputs, trunc_thr: float = 0.0, max_bond: int = 0, *, method:
         op_off[k] = starts[k] + np.concatenate([[0], np.cumsum(sizes[k])])
     op_data = np.ascontiguousarray(np.concatenate([w.ravel() for op in ops for w in op.sites])) if ops else np.zeros(1, dtype=np.complex128)
     count = len(outputs)
+    out = (c_void_p * count)()
+    ranks, sweeps = np.zeros((count, max(n - 1, 0)), dtype=np.int32), np.zeros((count, max(n - 1, 0)), dtype=np.int32)
+    dropped, status = np.zeros((count, max(n - 1, 0)), dtype=np.float64), np.zeros(count, dtype=np.int32)
     with _Lanes(states) as lanes:
-        out = (c_void_p * count)()
-        ranks, sweeps = np.zeros((count, max(n - 1, 0)), dtype=np.int32), np.zeros((count, max(n - 1, 0)), dtype=np.int32)
-        dropped, status = np.zeros((count, max(n - 1, 0)), dtype=np.float64), np.zeros(count, dtype=np.int32)
         check(_lib.lib().aqc_mps_opsum(lanes.handles(), len(lanes.lanes), len(ops), iptr(op_dims) if ops else None,
                                        op_off.ctypes.data_as(POINTER(ctypes.c_int64)) if ops else None, dptr(op_data) if ops else None, count,
-                                       iptr(term_off), iptr(term_state), iptr(term_op), dptr(cf), trunc_thr, max_bond, _COMPRESS_METHODS[method], out,
+                                       iptr(term_off), iptr(term_state), iptr(term_op), dptr(cf), trunc_thr, max_bond, code, out,
                                        iptr(ranks), dptr(dropped), iptr(sweeps), iptr(status)))
-        made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
-    bad = np.flatnonzero(status)
-    if bad.size and not details:
-        lane = int(bad[0])
-        cut = int(np.flatnonzero(ranks[lane] == 0)[0]) + 1 if n > 1 else 0
-        for m in made:
-            if m is not None:
-                m.close()
-        raise RuntimeError(f"output {lane}, cut {cut}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
-    if not details:
-        return made
-    return made, {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes}
+        made = _adopt(out)
+    return _finish(made, status, _COMPRESS_STATUS, lambda lane: f"output {lane}, cut {_failed_cut(ranks[lane])}", False, details,
+                   {"ranks": ranks, "dropped": dropped, "sweeps": sweeps, "status": status, "route": routes})
 
 
 def apply_operator(op, states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
@@ -993,64 +1045,37 @@ def apply_route(bond_dims, max_bond: int = 0) -> str:
     """The route ``apply_gates`` picks for a state with these n + 1 bond dimensions at this ``max_bond``: ``"fused"`` when no bond can
     pass ``APPLY_FUSED_CAP`` (``max_bond`` in 1 .. 64, or at most 13 qubits, and no input bond above the cap), else ``"gatewise"``."""
     d = np.ascontiguousarray(bond_dims, dtype=np.int32)
-    if d.ndim != 1 or d.size < 2 or int(max_bond) < 0:
-        raise ValueError("expects the n + 1 bond dimensions of a state and a non-negative max_bond")
-    r = _lib.lib().aqc_mps_apply_route(d.size - 1, iptr(d), int(max_bond))
-    if r not in _APPLY_ROUTES:
-        raise ValueError("expects the n + 1 bond dimensions of a state and a non-negative max_bond")
-    return _APPLY_ROUTES[r]
+    fits = d.ndim == 1 and d.size >= 2 and int(max_bond) >= 0
+    return _route_of("aqc_mps_apply_route", _APPLY_ROUTES, f"{_BOND_DIMS_OF_A_STATE} and a non-negative max_bond",
+                     (d.size - 1, iptr(d), int(max_bond)) if fits else None)
 
 
 def _apply_arguments(states, trunc_thr, max_bond, method):
-    """What is refused before anything is uploaded; returns (trunc_thr, max_bond, the bond dimensions that are known already)."""
-    if method not in _APPLY_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'gatewise', not {method!r}")
-    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
-    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
-        raise ValueError("trunc_thr and max_bond must be non-negative")
-    items = [states] if isinstance(states, (DeviceMPS, tuple)) else states
-    shapes = []
-    if isinstance(items, list):
-        for s in items:
-            if isinstance(s, DeviceMPS) and s.handle:
-                shapes.append(s.bond_dims)
-            elif isinstance(s, tuple) and len(s) == 2:
-                shapes.append(_pack(s)[1])
-        if len({d.size for d in shapes}) > 1:
-            raise ValueError("the states differ in the number of qubits")
-        if method == "fused" and any(apply_route(d, max_bond) != "fused" for d in shapes):
-            raise ValueError(f"the fused route takes bond dimensions up to {APPLY_FUSED_CAP}: max_bond in 1 .. {APPLY_FUSED_CAP} or at most 13 qubits, "
-                             f"and no input bond above {APPLY_FUSED_CAP}")
-    return trunc_thr, max_bond
+    """What is refused before anything is uploaded; returns (trunc_thr, max_bond, the states of the call, not uploaded yet)."""
+    _method_code(method, _APPLY_METHODS)
+    trunc_thr, max_bond = _truncation(trunc_thr, max_bond)
+    lanes = _Lanes(states)
+    if method == "fused" and any(apply_route(d, max_bond) != "fused" for d in lanes.dims):
+        raise ValueError(f"the fused route takes bond dimensions up to {APPLY_FUSED_CAP}: max_bond in 1 .. {APPLY_FUSED_CAP} or at most 13 qubits, "
+                         f"and no input bond above {APPLY_FUSED_CAP}")
+    return trunc_thr, max_bond, lanes
 
 
-def _apply_results(lanes, call, plan, n, method, max_bond, details):
+def _apply_results(lanes, call, plan, method, max_bond, details):
     """The outputs of one native call of the two entry points, as ``apply_gates`` returns them."""
     count = len(lanes.lanes)
     layers, ngates = int(plan[0]), int(plan[1])
     route = method
     if route is None:
-        route = "fused" if all(apply_route(m.bond_dims, max_bond) == "fused" for m in lanes.lanes) else "gatewise"
+        route = "fused" if all(apply_route(d, max_bond) == "fused" for d in lanes.dims) else "gatewise"
     out = (c_void_p * count)()
-    ranks, sweeps = np.zeros((count, n + 1), dtype=np.int32), np.zeros((count, max(ngates, 1)), dtype=np.int32)
+    ranks, sweeps = np.zeros((count, lanes.n + 1), dtype=np.int32), np.zeros((count, max(ngates, 1)), dtype=np.int32)
     dropped, status = np.zeros(count, dtype=np.float64), np.zeros((count, 3), dtype=np.int32)
     check(call(lanes.handles(), count, out, iptr(ranks), dptr(dropped), iptr(sweeps), iptr(status)))
-    made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
-    single = lanes.single
-    bad = np.flatnonzero(status[:, 0])
-    if bad.size and not details:
-        lane = int(bad[0])
-        for m in made:
-            if m is not None:
-                m.close()
-        raise RuntimeError(f"lane {lane}, layer {int(status[lane, 1])}, site {int(status[lane, 2])}: {_APPLY_STATUS.get(int(status[lane, 0]), 'failed')}")
-    if not details:
-        return made[0] if single else made
-    info = {"bonds": ranks, "dropped": dropped, "sweeps": sweeps[:, :ngates], "status": status[:, 0].copy(), "failed_at": status[:, 1:].copy()}
-    if single:
-        info = {k: v[0] for k, v in info.items()}
-    info["layers"], info["route"] = layers, route
-    return (made[0] if single else made), info
+    return _finish(_adopt(out), status[:, 0], _APPLY_STATUS, lambda lane: f"lane {lane}, layer {int(status[lane, 1])}, site {int(status[lane, 2])}",
+                   lanes.single, details,
+                   {"bonds": ranks, "dropped": dropped, "sweeps": sweeps[:, :ngates], "status": status[:, 0].copy(), "failed_at": status[:, 1:].copy()},
+                   {"layers": layers, "route": route})
 
 
 def apply_gates(states, gates, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None, details: bool = False):
@@ -1073,12 +1098,10 @@ def apply_gates(states, gates, trunc_thr: float = 0.0, max_bond: int = 0, *, met
     A lane whose state is zero or not finite, or whose SVD reaches its sweep limit, fails alone: without ``details`` that raises
     ``RuntimeError`` naming lane, layer and site; with ``details`` its entry is ``None`` and the second return value
     ``{"layers", "bonds", "dropped", "sweeps", "status", "failed_at", "route"}`` tells why."""
-    from .mps_observables import _Lanes
-
-    trunc_thr, max_bond = _apply_arguments(states, trunc_thr, max_bond, method)
+    trunc_thr, max_bond, lanes = _apply_arguments(states, trunc_thr, max_bond, method)
     if not isinstance(gates, (list, tuple)):
         raise ValueError("gates is a list of (matrix, qubit) and (matrix, (a, b))")
-    count = 1 if isinstance(states, (DeviceMPS, tuple)) else (len(states) if isinstance(states, list) else 0)
+    count, n = len(lanes.items), lanes.n
     qubits, kinds, mats, per_state = np.zeros((len(gates), 2), dtype=np.int32), np.zeros(len(gates), dtype=np.int32), [], False
     for i, item in enumerate(gates):
         if not (isinstance(item, (list, tuple)) and len(item) == 2):
@@ -1103,10 +1126,9 @@ def apply_gates(states, gates, trunc_thr: float = 0.0, max_bond: int = 0, *, met
     else:
         flat = np.concatenate([m.ravel() for m in mats]) if mats else np.zeros(1, dtype=np.complex128)
     flat = np.ascontiguousarray(flat, dtype=np.complex128)
-    with _Lanes(states) as lanes:
-        n = lanes.lanes[0].num_qubits
-        if len(gates) and int(qubits.max()) >= n:
-            raise ValueError("a qubit is out of range")
+    if len(gates) and int(qubits.max()) >= n:
+        raise ValueError("a qubit is out of range")
+    with lanes:
         plan = np.zeros(2, dtype=np.int32)
         check(_lib.lib().aqc_mps_apply_plan(n, len(gates), iptr(qubits), iptr(kinds), iptr(plan), None, None))
 
@@ -1114,24 +1136,21 @@ def apply_gates(states, gates, trunc_thr: float = 0.0, max_bond: int = 0, *, met
             return _lib.lib().aqc_mps_apply_gates(handles, nstates, len(gates), iptr(qubits), iptr(kinds), dptr(flat), int(per_state), trunc_thr, max_bond,
                                                   _APPLY_METHODS[method], out, ranks, dropped, sweeps, status)
 
-        return _apply_results(lanes, call, plan, n, method, max_bond, details)
+        return _apply_results(lanes, call, plan, method, max_bond, details)
 
 
 def _circuit_many(circ, thetas, states, inverse: bool, trunc_thr, max_bond, method, details):
-    from .mps_observables import _Lanes
-
-    trunc_thr, max_bond = _apply_arguments(states, trunc_thr, max_bond, method)
+    trunc_thr, max_bond, lanes = _apply_arguments(states, trunc_thr, max_bond, method)
     th = np.ascontiguousarray(thetas, dtype=np.float64)
-    count = 1 if isinstance(states, (DeviceMPS, tuple)) else (len(states) if isinstance(states, list) else 0)
+    count = len(lanes.items)
     if th.shape not in ((circ.num_thetas,), (count, circ.num_thetas)):
         raise ValueError(f"expected {circ.num_thetas} thetas, or [{count}, {circ.num_thetas}], got an array of shape {th.shape}")
     if not np.all(np.isfinite(th)):
         raise ValueError("thetas must be finite")
+    if lanes.n != circ.num_qubits:
+        raise ValueError("circuit and states differ in the number of qubits")
     desc, keep = _describe(circ)
-    with _Lanes(states) as lanes:
-        n = lanes.lanes[0].num_qubits
-        if n != circ.num_qubits:
-            raise ValueError("circuit and states differ in the number of qubits")
+    with lanes:
         plan = np.zeros(2, dtype=np.int32)
         check(_lib.lib().aqc_mps_apply_circuit_plan(byref(desc), int(inverse), iptr(plan)))
 
@@ -1139,7 +1158,7 @@ def _circuit_many(circ, thetas, states, inverse: bool, trunc_thr, max_bond, meth
             return _lib.lib().aqc_mps_apply_circuit_many(byref(desc), dptr(th), circ.num_thetas, int(th.ndim == 2), handles, nstates, int(inverse), trunc_thr,
                                                          max_bond, _APPLY_METHODS[method], out, ranks, dropped, sweeps, status)
 
-        result = _apply_results(lanes, call, plan, n, method, max_bond, details)
+        result = _apply_results(lanes, call, plan, method, max_bond, details)
     del keep
     return result
 
@@ -1166,19 +1185,14 @@ _FROM_VECTOR_ROUTES = {1: "fused", 2: "host"}
 def from_vector_route(num_qubits: int, max_bond: int = 0) -> str:
     """The route ``from_vectors`` picks: ``"fused"`` for 2 .. 30 qubits when no bond can pass ``FROM_VECTOR_FUSED_CAP`` (``max_bond`` in
     1 .. 32, or at most 11 qubits), else ``"host"``."""
-    r = _lib.lib().aqc_mps_from_vec_route(int(num_qubits), int(max_bond))
-    if r not in _FROM_VECTOR_ROUTES:
-        raise ValueError("expects a positive number of qubits and a non-negative max_bond")
-    return _FROM_VECTOR_ROUTES[r]
+    return _route_of("aqc_mps_from_vec_route", _FROM_VECTOR_ROUTES, "expects a positive number of qubits and a non-negative max_bond",
+                     (int(num_qubits), int(max_bond)))
 
 
 def _from_vectors_arguments(vecs, trunc_thr, max_bond, method):
     """What is refused before any device call; returns (lanes x 2^n array, single, n, trunc_thr, max_bond, route)."""
-    if method not in _FROM_VECTOR_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'host', not {method!r}")
-    trunc_thr, max_bond = float(trunc_thr), int(max_bond)
-    if not (trunc_thr >= 0.0 and np.isfinite(trunc_thr)) or max_bond < 0:
-        raise ValueError("trunc_thr and max_bond must be non-negative")
+    _method_code(method, _FROM_VECTOR_METHODS)
+    trunc_thr, max_bond = _truncation(trunc_thr, max_bond)
     if isinstance(vecs, (list, tuple)):
         rows = [np.asarray(v) for v in vecs]
         if not rows or any(v.ndim != 1 for v in rows):
@@ -1230,7 +1244,7 @@ def from_vectors(vecs, trunc_thr: float = 0.0, max_bond: int = 0, *, device: Opt
         out = (c_void_p * lanes)()
         check(_lib.lib().aqc_mps_from_vec(dev, n, lanes, dptr(arr), trunc_thr, max_bond, _FROM_VECTOR_METHODS[method], out, iptr(bonds), dptr(dropped),
                                           iptr(sweeps), iptr(status), iptr(failed_at), iptr(parts)))
-        made = [DeviceMPS(c_void_p(h)) if h else None for h in out]
+        made = _adopt(out)
     else:
         from .mps_operations import _canonical_sweep
 
@@ -1245,20 +1259,8 @@ def from_vectors(vecs, trunc_thr: float = 0.0, max_bond: int = 0, *, device: Opt
             made.append(DeviceMPS.from_qiskit((gam, lam), dev, assume_canonical=True))
             bonds[i] = [1] + [v.size for v in lam] + [1]
             dropped[i] = weights
-    bad = np.flatnonzero(status)
-    if bad.size and not details:
-        lane = int(bad[0])
-        for m in made:
-            if m is not None:
-                m.close()
-        raise RuntimeError(f"lane {lane}, site {int(failed_at[lane])}: {_COMPRESS_STATUS.get(int(status[lane]), 'failed')}")
-    if not details:
-        return made[0] if single else made
-    info = {"bonds": bonds, "dropped": dropped, "sweeps": sweeps, "status": status, "failed_at": failed_at}
-    if single:
-        info = {k: v[0] for k, v in info.items()}
-    info["route"], info["parts"] = route, parts
-    return (made[0] if single else made), info
+    return _finish(made, status, _COMPRESS_STATUS, lambda lane: f"lane {lane}, site {int(failed_at[lane])}", single, details,
+                   {"bonds": bonds, "dropped": dropped, "sweeps": sweeps, "status": status, "failed_at": failed_at}, {"route": route, "parts": parts})
 
 
 # ---- MPS states into dense vectors and blocks of amplitudes (aqc_mps_to_vec, aqc_mps_amp_blocks; rules: csrc/aqc_mps_tovec_rule.h, kernels:
@@ -1269,34 +1271,14 @@ TO_VECTOR_MAX_QUBITS = 30
 AMPLITUDE_BLOCK_MAX_LOW = 24
 _TO_VECTOR_METHODS = {None: 0, "fused": 1, "gemm": 2}         # AQC_MPS_TO_VEC_*
 _TO_VECTOR_ROUTES = {1: "fused", 2: "gemm"}
+_AMPLITUDE_BLOCK_METHODS = {None: 0, "fused": 1}
 
 
 def to_vector_route(bond_dims) -> str:
     """The route ``to_vectors`` picks for a state with these n + 1 bond dimensions: ``"fused"`` when every bond is at most
     ``TO_VECTOR_FUSED_CAP``, else ``"gemm"``.  Host only."""
     d = np.ascontiguousarray(bond_dims, dtype=np.int32)
-    if d.ndim != 1 or d.size < 2:
-        raise ValueError("expects the n + 1 bond dimensions of a state")
-    r = _lib.lib().aqc_mps_to_vec_route(d.size - 1, iptr(d))
-    if r not in _TO_VECTOR_ROUTES:
-        raise ValueError("expects the n + 1 bond dimensions of a state")
-    return _TO_VECTOR_ROUTES[r]
-
-
-def _to_vector_states(states, method, methods):
-    """What both calls refuse about their states and method before anything else; returns (single, states, n, bond dimensions)."""
-    if method not in methods:
-        raise ValueError(f"method must be one of {sorted(m for m in methods if m)} or None, not {method!r}")
-    single = isinstance(states, DeviceMPS)
-    items = [states] if single else states
-    if not isinstance(items, (list, tuple)) or not items or any(not isinstance(s, DeviceMPS) for s in items):
-        raise ValueError("states is a DeviceMPS or a non-empty list of them")
-    if any(not s.handle for s in items):
-        raise ValueError("a closed DeviceMPS")
-    n, dev = items[0].num_qubits, items[0].device
-    if any(s.num_qubits != n or s.device != dev for s in items):
-        raise ValueError("the states differ in size or device")
-    return single, list(items), n, [np.asarray(s.bond_dims) for s in items]
+    return _route_of("aqc_mps_to_vec_route", _TO_VECTOR_ROUTES, _BOND_DIMS_OF_A_STATE, (d.size - 1, iptr(d)) if d.ndim == 1 and d.size >= 2 else None)
 
 
 def to_vectors(states, *, method: Optional[str] = None, out: Optional[np.ndarray] = None, details: bool = False):
@@ -1311,7 +1293,8 @@ def to_vectors(states, *, method: Optional[str] = None, out: Optional[np.ndarray
     in chunks under a budget of device memory (``aqc_mps_to_vec_budget``), one synchronisation and one download per chunk.
 
     ``details``: also returns ``{"route", "split", "chunks", "launches"}``, ``route`` per state."""
-    single, items, n, dims = _to_vector_states(states, method, _TO_VECTOR_METHODS)
+    code = _method_code(method, _TO_VECTOR_METHODS)
+    single, items, n, dims = _call_states(states, device_only=True)
     if n > TO_VECTOR_MAX_QUBITS:
         raise ValueError(f"a dense vector takes at most {TO_VECTOR_MAX_QUBITS} qubits, the states have {n}: amplitude_blocks reads blocks of it")
     if method == "fused":
@@ -1326,8 +1309,7 @@ def to_vectors(states, *, method: Optional[str] = None, out: Optional[np.ndarray
         out = np.empty(shape, dtype=np.complex128)
     count = len(items)
     info = np.zeros(count + 3, dtype=np.int32)
-    handles = (c_void_p * count)(*[m.handle for m in items])
-    check(_lib.lib().aqc_mps_to_vec(handles, count, _TO_VECTOR_METHODS[method], dptr(out), iptr(info)))
+    check(_lib.lib().aqc_mps_to_vec(_handles(items), count, code, dptr(out), iptr(info)))
     if not details:
         return out
     routes = [_TO_VECTOR_ROUTES[int(r)] for r in info[:count]]
@@ -1341,7 +1323,8 @@ def amplitude_blocks(states, low_qubits: int, high_bits, *, method: Optional[str
     l + 2^low_qubits (sum_i high_bits[r][i] 2^i).  1 <= low_qubits <= min(n - 1, 24).  A block costs one walk of the high sites
     plus one product, where ``amplitudes`` walks the chain once per number.  Fused route only (``method`` None or ``"fused"``): a bond
     above ``TO_VECTOR_FUSED_CAP`` is refused."""
-    single, items, n, dims = _to_vector_states(states, method, {None: 0, "fused": 1})
+    code = _method_code(method, _AMPLITUDE_BLOCK_METHODS)
+    single, items, n, dims = _call_states(states, device_only=True)
     k = int(low_qubits)
     if n < 2 or k < 1 or k > min(n - 1, AMPLITUDE_BLOCK_MAX_LOW):
         raise ValueError(f"low_qubits must be in 1 .. min(n - 1, {AMPLITUDE_BLOCK_MAX_LOW}) at n >= 2; got {low_qubits} at n = {n}")
@@ -1358,8 +1341,7 @@ def amplitude_blocks(states, low_qubits: int, high_bits, *, method: Optional[str
     arr = np.ascontiguousarray(arr, dtype=np.uint8)
     count, rows = len(items), arr.shape[0]
     out = np.empty((count, rows, 1 << k), dtype=np.complex128)
-    handles = (c_void_p * count)(*[m.handle for m in items])
-    check(_lib.lib().aqc_mps_amp_blocks(handles, count, k, rows, arr.ctypes.data_as(POINTER(ctypes.c_uint8)), 1 if method == "fused" else 0, dptr(out)))
+    check(_lib.lib().aqc_mps_amp_blocks(_handles(items), count, k, rows, arr.ctypes.data_as(POINTER(ctypes.c_uint8)), code, dptr(out)))
     return out[0] if single else out
 
 

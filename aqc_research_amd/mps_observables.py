@@ -28,20 +28,21 @@ Entanglement across the cuts of the chain (aqc_mps_ent_schmidt; kernels: csrc/aq
 (``entropies_of``: NumPy), ``bond_dims_needed`` the bond dimensions the engine's rank rule would keep at a given ``trunc_thr`` /
 ``max_bond``.
 """
-from ctypes import POINTER, c_uint8, c_void_p
+from ctypes import POINTER, c_uint8
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, dptr, iptr
-from .mps_engine import DeviceMPS
+from .mps_engine import MPO, _BOND_DIMS_OF_A_STATE, _handles, _Lanes, _method_code, _route_of, _truncation, _within_fused_cap, apply_operator
 from .observables import (_bond_energies_of, _bond_pairs, _correlation_letters, _correlation_of, _correlation_pairs, _magnetisation_of,
                           _magnetisation_pairs, _single_axis, pauli_expectation, pauli_matrix)  # noqa: F401  (the last two: for callers)
 from .xxz import _finite
 
 FUSED_CAP = 64   # AQC_MPS_OBS_FUSED_CAP of include/aqc_hip.h
 _METHODS = {None: 0, "fused": 1, "gemm": 2}   # AQC_MPS_OBS_*
+_ROUTES = {1: "fused", 2: "gemm"}
 
 
 def _pairs(pairs, n: int) -> np.ndarray:
@@ -77,88 +78,34 @@ def plan(num_qubits: int, pairs: Sequence[Sequence[int]]) -> dict:
 def route(bond_dims) -> str:
     """The route the rule picks for a state with these n + 1 bond dimensions: ``"fused"`` or ``"gemm"``."""
     d = np.ascontiguousarray(bond_dims, dtype=np.int32)
-    r = _lib.lib().aqc_mps_obs_route(d.size - 1, iptr(d))
-    if r not in (1, 2):
-        raise ValueError("expects the n + 1 bond dimensions of a state")
-    return "fused" if r == 1 else "gemm"
+    return _route_of("aqc_mps_obs_route", _ROUTES, _BOND_DIMS_OF_A_STATE, (d.size - 1, iptr(d)))
 
 
-def _is_tuple_state(s) -> bool:
-    return isinstance(s, tuple) and len(s) == 2   # a QiskitMPS (gammas, lambdas); several states come as a list
+def _two_qubits(n: int) -> None:
+    if n < 2:
+        raise ValueError("pair density matrices need at least 2 qubits")
 
 
-class _Lanes:
-    """The states of a call as DeviceMPS handles; what was uploaded for the call is closed on exit."""
-
-    def __init__(self, states):
-        self.single = isinstance(states, DeviceMPS) or _is_tuple_state(states)
-        if not self.single and not isinstance(states, list):
-            raise ValueError("states is a DeviceMPS, a QiskitMPS tuple or a list of those")
-        self.items = [states] if self.single else list(states)
-        if not self.items:
-            raise ValueError("expects at least one state")
-        self.own = []
-        self.lanes = []
-
-    def __enter__(self):
-        try:
-            for s in self.items:
-                if isinstance(s, DeviceMPS):
-                    if not s.handle:
-                        raise ValueError("a closed DeviceMPS")
-                    self.lanes.append(s)
-                elif _is_tuple_state(s):
-                    m = DeviceMPS.from_qiskit(s, assume_canonical=True)   # exact arithmetic: the gauge is taken as it is
-                    self.own.append(m)
-                    self.lanes.append(m)
-                else:
-                    raise ValueError("a state is a DeviceMPS or a QiskitMPS tuple")
-        except Exception:
-            self.__exit__(None, None, None)
-            raise
-        n = self.lanes[0].num_qubits
-        if any(m.num_qubits != n for m in self.lanes):
-            self.__exit__(None, None, None)
-            raise ValueError("the states differ in the number of qubits")
-        return self
-
-    def __exit__(self, *exc):
-        for m in self.own:
-            m.close()
-        self.own = []
-        return False
-
-    def handles(self):
-        """The lanes as the handle array that the native calls take."""
-        return (c_void_p * len(self.lanes))(*[m.handle for m in self.lanes])
-
-    def check_fused_cap(self, method, cap: int = FUSED_CAP) -> None:
-        """Refuses ``method="fused"`` for a lane beyond the cap, before the native call."""
-        if method == "fused":
-            for m in self.lanes:
-                if int(m.bond_dims.max()) > cap:
-                    raise ValueError(f"the fused route takes bond dimensions up to {cap}, not {int(m.bond_dims.max())}")
-
-
-def _rdms(lanes: _Lanes, arr: np.ndarray, method: Optional[str]) -> np.ndarray:
-    if method not in _METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
-    lanes.check_fused_cap(method)
-    out = np.empty((len(lanes.lanes), arr.shape[0], 4, 4), dtype=np.complex128)
-    check(_lib.lib().aqc_mps_obs_pairs(lanes.handles(), len(lanes.lanes), arr.shape[0], iptr(arr), _METHODS[method], dptr(out)))
-    return out[0] if lanes.single else out
+def _rdms(states, pairs_of, method: Optional[str]):
+    """``(rho, lanes)``: the matrices of the pairs ``pairs_of(n)`` of every state of the call; everything is refused before an upload."""
+    code = _method_code(method, _METHODS)
+    lanes = _Lanes(states)
+    arr = _pairs(pairs_of(lanes.n), lanes.n)
+    _within_fused_cap(method, lanes.dims, FUSED_CAP)
+    out = np.empty((len(lanes.items), arr.shape[0], 4, 4), dtype=np.complex128)
+    with lanes:
+        check(_lib.lib().aqc_mps_obs_pairs(lanes.handles(), len(lanes.lanes), arr.shape[0], iptr(arr), code, dptr(out)))
+    return (out[0] if lanes.single else out), lanes
 
 
 def pair_density_matrices(states, pairs=None, *, method: Optional[str] = None) -> np.ndarray:
     """The two-qubit reduced density matrices of ``pairs`` (``None``: all i < j in lexicographic order): ``(P, 4, 4)`` for one state,
     ``(lanes, P, 4, 4)`` for a list."""
-    with _Lanes(states) as lanes:
-        n = lanes.lanes[0].num_qubits
-        if n < 2:
-            raise ValueError("pair density matrices need at least 2 qubits")
-        if pairs is None:
-            pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
-        return _rdms(lanes, _pairs(pairs, n), method)
+    def wanted(n):
+        _two_qubits(n)
+        return _correlation_pairs(n) if pairs is None else pairs
+
+    return _rdms(states, wanted, method)[0]
 
 
 def reduced_density_matrix(states, qubits: Sequence[int], *, method: Optional[str] = None) -> np.ndarray:
@@ -167,52 +114,44 @@ def reduced_density_matrix(states, qubits: Sequence[int], *, method: Optional[st
     qs = np.asarray(qubits)
     if qs.ndim != 1 or qs.size not in (1, 2) or not np.issubdtype(qs.dtype, np.integer):
         raise ValueError("expects a flat list of 1 or 2 qubit numbers")
-    with _Lanes(states) as lanes:
-        n = lanes.lanes[0].num_qubits
-        if n < 2:
-            raise ValueError("pair density matrices need at least 2 qubits")
+    q = int(qs[0])
+
+    def pair(n):
+        _two_qubits(n)
         if qs.size == 2:
-            out = _rdms(lanes, _pairs(qs[None, :], n), method)
-            return out[0] if lanes.single else out[:, 0]
-        q = int(qs[0])
+            return qs[None, :]
         if not 0 <= q < n:
             raise ValueError(f"qubit out of range: {n} qubits")
-        other = q + 1 if q + 1 < n else q - 1
-        rho = _rdms(lanes, _pairs([(q, other)], n), method)
-        rho = rho[0] if lanes.single else rho[:, 0]
-        r = rho.reshape(rho.shape[:-2] + (2, 2, 2, 2))   # [other][q][other'][q']
-        return r[..., 0, :, 0, :] + r[..., 1, :, 1, :]
+        return [(q, q + 1 if q + 1 < n else q - 1)]
 
-
-
-
-def _rho_of(states, pairs_of, method: Optional[str]):
-    """``(rho, n)``: the matrices of the pairs ``pairs_of(n)`` that a derived observable of ``observables.py`` asks for."""
-    with _Lanes(states) as lanes:
-        n = lanes.lanes[0].num_qubits
-        return _rdms(lanes, _pairs(pairs_of(n), n), method), n
+    rho, lanes = _rdms(states, pair, method)
+    rho = rho[0] if lanes.single else rho[:, 0]
+    if qs.size == 2:
+        return rho
+    r = rho.reshape(rho.shape[:-2] + (2, 2, 2, 2))   # [other][q][other'][q']
+    return r[..., 0, :, 0, :] + r[..., 1, :, 1, :]
 
 
 def magnetisation(states, axis: str = "z", *, method: Optional[str] = None) -> np.ndarray:
     """<sigma_i> along ``axis`` for every qubit: ``(n,)`` or ``(lanes, n)``.  Read from the ceil(n / 2) pairs (0, 1), (2, 3), ...
     (the last qubit of an odd chain with its left neighbour).  Not divided by <psi|psi>."""
     a = _single_axis(axis)
-    rho, n = _rho_of(states, _magnetisation_pairs, method)
-    return _magnetisation_of(rho, n, a)
+    rho, lanes = _rdms(states, _magnetisation_pairs, method)
+    return _magnetisation_of(rho, lanes.n, a)
 
 
 def correlation_matrix(states, letters: str = "zz", connected: bool = False, *, method: Optional[str] = None) -> np.ndarray:
     """C[i][j] = <a_i b_j> for ``letters = "ab"`` out of x, y, z, over all pairs: ``(n, n)`` or ``(lanes, n, n)``.  The diagonal is 1
     for equal letters and 0 otherwise, as in ``observables.correlation_matrix``.  ``connected``: minus <a_i><b_j>."""
     a, b = _correlation_letters(letters)
-    rho, n = _rho_of(states, _correlation_pairs, method)
-    return _correlation_of(rho, n, a, b, connected)
+    rho, lanes = _rdms(states, _correlation_pairs, method)
+    return _correlation_of(rho, lanes.n, a, b, connected)
 
 
 def bond_energies(states, delta: float, *, method: Optional[str] = None) -> np.ndarray:
     """-1/4 tr rho_{i,i+1} (XX + YY + delta ZZ) for the n - 1 bonds of the open XXZ chain: ``(n - 1,)`` or ``(lanes, n - 1)``."""
     delta = _finite(delta, "delta")
-    rho, _ = _rho_of(states, _bond_pairs, method)
+    rho, _ = _rdms(states, _bond_pairs, method)
     return _bond_energies_of(rho, delta)
 
 
@@ -227,35 +166,9 @@ def pauli_route(bra_dims, ket_dims) -> str:
     bond of both is at most ``FUSED_CAP``, else ``"gemm"``."""
     k = np.ascontiguousarray(ket_dims, dtype=np.int32)
     b = None if bra_dims is None else np.ascontiguousarray(bra_dims, dtype=np.int32)
-    if k.ndim != 1 or k.size < 2 or (b is not None and b.shape != k.shape):
-        raise ValueError("expects the n + 1 bond dimensions of the bra and of the ket")
-    r = _lib.lib().aqc_mps_pauli_route(k.size - 1, None if b is None else iptr(b), iptr(k))
-    if r not in (1, 2):
-        raise ValueError("expects the n + 1 bond dimensions of the bra and of the ket")
-    return "fused" if r == 1 else "gemm"
-
-
-def _shape_of(states):
-    """``(single, count, n)`` of what ``_Lanes`` would take, read on the host: no upload is made for a call that is then refused."""
-    single = isinstance(states, DeviceMPS) or _is_tuple_state(states)
-    if not single and not isinstance(states, list):
-        raise ValueError("states is a DeviceMPS, a QiskitMPS tuple or a list of those")
-    items = [states] if single else states
-    if not items:
-        raise ValueError("expects at least one state")
-    ns = set()
-    for s in items:
-        if isinstance(s, DeviceMPS):
-            if not s.handle:
-                raise ValueError("a closed DeviceMPS")
-            ns.add(s.num_qubits)
-        elif _is_tuple_state(s):
-            ns.add(len(s[0]))
-        else:
-            raise ValueError("a state is a DeviceMPS or a QiskitMPS tuple")
-    if len(ns) != 1:
-        raise ValueError("the states differ in the number of qubits")
-    return single, len(items), ns.pop()
+    fits = k.ndim == 1 and k.size >= 2 and (b is None or b.shape == k.shape)
+    return _route_of("aqc_mps_pauli_route", _ROUTES, "expects the n + 1 bond dimensions of the bra and of the ket",
+                     (k.size - 1, None if b is None else iptr(b), iptr(k)) if fits else None)
 
 
 def _strings(strings, n: int) -> np.ndarray:
@@ -290,18 +203,11 @@ def _strings(strings, n: int) -> np.ndarray:
     return arr
 
 
-def _pauli_call(bras, kets, arr: np.ndarray, method: Optional[str]) -> np.ndarray:
+def _pauli_call(bras, kets, arr: np.ndarray, code: int) -> np.ndarray:
     """``(len(kets), S)``: <bras[p]| P_s |kets[p]> (``bras`` None: expectation mode) for lists of open DeviceMPS."""
-    if method not in _PAULI_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
-    if method == "fused":
-        for m in {id(m): m for m in kets + (bras or [])}.values():   # (a state may be listed many times: overlaps)
-            if int(m.bond_dims.max()) > FUSED_CAP:
-                raise ValueError(f"the fused route takes bond dimensions up to {FUSED_CAP}, not {int(m.bond_dims.max())}")
-    kh = (c_void_p * len(kets))(*[m.handle for m in kets])
-    bh = None if bras is None else (c_void_p * len(bras))(*[m.handle for m in bras])
     out = np.empty((len(kets), arr.shape[0]), dtype=np.complex128)
-    check(_lib.lib().aqc_mps_pauli(bh, kh, len(kets), arr.shape[0], arr.ctypes.data_as(POINTER(c_uint8)), _PAULI_METHODS[method], dptr(out)))
+    check(_lib.lib().aqc_mps_pauli(None if bras is None else _handles(bras), _handles(kets), len(kets), arr.shape[0],
+                                   arr.ctypes.data_as(POINTER(c_uint8)), code, dptr(out)))
     return out
 
 
@@ -316,35 +222,36 @@ def pauli_strings(states, strings, *, bras=None, method: Optional[str] = None) -
     Without bras a string is walked over its support only, between the environments of the state, so a local term costs its support and
     not the chain.  ``method``: ``None`` lets the rule choose per pair (``pauli_route``).  A value does not depend on which other
     strings or states are in the call."""
-    if method not in _PAULI_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
-    single, count, n = _shape_of(states)
-    arr = _strings(strings, n)
-    if bras is not None and _shape_of(bras) != (single, count, n):
+    code = _method_code(method, _PAULI_METHODS)
+    kets = _Lanes(states)
+    arr = _strings(strings, kets.n)
+    b = None if bras is None else _Lanes(bras)
+    if b is not None and (b.single, len(b.items), b.n) != (kets.single, len(kets.items), kets.n):
         raise ValueError("bras is one state for one state, or a list as long as states, of the same number of qubits")
-    with _Lanes(states) as kets:
-        if bras is None:
-            out = _pauli_call(None, kets.lanes, arr, method)
+    _within_fused_cap(method, kets.dims + ([] if b is None else b.dims), FUSED_CAP)
+    with kets:
+        if b is None:
+            out = _pauli_call(None, kets.lanes, arr, code)
         else:
-            with _Lanes(bras) as b:
-                out = _pauli_call(b.lanes, kets.lanes, arr, method)
-    return out[0] if single else out
+            with b:
+                out = _pauli_call(b.lanes, kets.lanes, arr, code)
+    return out[0] if kets.single else out
 
 
 def overlaps(bras, kets, *, method: Optional[str] = None) -> np.ndarray:
     """The ``(len(bras), len(kets))`` matrix <phi_a|psi_b> in one call (the identity string between all pairs)."""
-    if method not in _PAULI_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
+    code = _method_code(method, _PAULI_METHODS)
     if not isinstance(bras, list) or not isinstance(kets, list):
         raise ValueError("bras and kets are lists of states")
-    (_, nb, n), (_, nk, n2) = _shape_of(bras), _shape_of(kets)
-    if n != n2:
+    b, k = _Lanes(bras), _Lanes(kets)
+    if b.n != k.n:
         raise ValueError("the states differ in the number of qubits")
-    with _Lanes(bras) as b, _Lanes(kets) as k:
+    _within_fused_cap(method, k.dims + b.dims, FUSED_CAP)
+    with b, k:
         pb = [m for m in b.lanes for _ in k.lanes]
         pk = [m for _ in b.lanes for m in k.lanes]
-        out = _pauli_call(pb, pk, np.zeros((1, n), dtype=np.uint8), method)
-    return out[:, 0].reshape(nb, nk)
+        out = _pauli_call(pb, pk, np.zeros((1, k.n), dtype=np.uint8), code)
+    return out[:, 0].reshape(len(b.lanes), len(k.lanes))
 
 
 def energy(states, terms, *, method: Optional[str] = None) -> np.ndarray:
@@ -364,22 +271,22 @@ def variance(states, op, *, method: Optional[str] = None) -> np.ndarray:
     O psi of every state comes from ONE ``mps_engine.apply_operator`` call (exact: nothing is truncated), the three overlaps of every
     state from ``overlaps``.  For a Hermitian operator this is the variance of O in psi; it is zero on an eigenstate up to rounding of
     the size of |O|_2^2.  A state that O annihilates has no O psi: ``RuntimeError``, as ``apply_operator`` raises it."""
-    from .mps_engine import MPO, apply_operator
-
     if not isinstance(op, MPO):
         raise ValueError("an operator is an MPO")
-    single, count, n = _shape_of(states)
+    kets = _Lanes(states)
+    count, n = len(kets.items), kets.n
     if op.num_qubits != n:
         raise ValueError(f"an operator on {op.num_qubits} qubits meets a state of {n}")
-    with _Lanes(states) as kets:
+    with kets:
         images = apply_operator(op, kets.lanes, method=method)
         try:   # <psi|psi>, <psi|O psi>, <O psi|O psi> of every state: the identity string between 3 x lanes pairs, one call
-            g = _pauli_call(kets.lanes + kets.lanes + images, kets.lanes + images + images, np.zeros((1, n), dtype=np.uint8), None)[:, 0].reshape(3, count)
+            g = _pauli_call(kets.lanes + kets.lanes + images, kets.lanes + images + images, np.zeros((1, n), dtype=np.uint8),
+                            _PAULI_METHODS[None])[:, 0].reshape(3, count)
         finally:
             for m in images:
                 m.close()
     out = g[2].real / g[0].real - np.abs(g[1] / g[0].real) ** 2
-    return out[0] if single else out
+    return out[0] if kets.single else out
 
 
 # ---- entanglement: the Schmidt spectra of every cut (aqc_mps_ent_schmidt; rules: csrc/aqc_mps_ent_rule.h, kernels: csrc/aqc_mps_ent.hip)
@@ -393,38 +300,23 @@ def entanglement_route(bond_dims) -> str:
     """The route the rule picks for a state with these n + 1 bond dimensions: ``"fused"`` when every bond is at most ``FUSED_CAP``,
     else ``"canonical"``."""
     d = np.ascontiguousarray(bond_dims, dtype=np.int32)
-    if d.ndim != 1 or d.size < 2:
-        raise ValueError("expects the n + 1 bond dimensions of a state")
-    r = _lib.lib().aqc_mps_ent_route(d.size - 1, iptr(d))
-    if r not in _ENT_ROUTES:
-        raise ValueError("expects the n + 1 bond dimensions of a state")
-    return _ENT_ROUTES[r]
+    return _route_of("aqc_mps_ent_route", _ENT_ROUTES, _BOND_DIMS_OF_A_STATE, (d.size - 1, iptr(d)) if d.ndim == 1 and d.size >= 2 else None)
 
 
-def _ent_method(method):
-    if method not in _ENT_METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'canonical', not {method!r}")
-    return _ENT_METHODS[method]
-
-
-def _schmidt_call(lanes, method: Optional[str], factors: bool = False):
-    """``(values (L, max(n - 1, 1), K), sweeps, status, routes, factors or None)`` for a list of open DeviceMPS."""
-    dims = [m.bond_dims for m in lanes]
-    n = lanes[0].num_qubits
+def _schmidt_call(lanes: _Lanes, method: Optional[str], factors: bool = False):
+    """``(values (L, max(n - 1, 1), K), sweeps, status, routes, factors or None)`` of the states of a call, which it uploads for itself;
+    ``factors`` go with ``method="fused"``."""
+    code = _method_code(method, _ENT_METHODS)
+    dims, n, count = lanes.dims, lanes.n, len(lanes.items)
     routes = [method or entanglement_route(d) for d in dims]
-    for d, r in zip(dims, routes):
-        if r == "fused" and int(d.max()) > FUSED_CAP:
-            raise ValueError(f"the fused route takes bond dimensions up to {FUSED_CAP}, not {int(d.max())}")
-        if factors and r != "fused":
-            raise ValueError("the factors are those of the fused route")
+    _within_fused_cap(method, dims, FUSED_CAP)
     kmax = max([1] + [int(d[1:n].max()) for d in dims if n > 1])
     rows = max(n - 1, 1)
-    handles = (c_void_p * len(lanes))(*[m.handle for m in lanes])
-    s = np.zeros((len(lanes), rows, kmax), dtype=np.float64)
-    sweeps, status = np.zeros((len(lanes), rows), dtype=np.int32), np.zeros((len(lanes), rows), dtype=np.int32)
+    s = np.zeros((count, rows, kmax), dtype=np.float64)
+    sweeps, status = np.zeros((count, rows), dtype=np.int32), np.zeros((count, rows), dtype=np.int32)
     fac = np.zeros(max(1, sum(2 * int((d[1:n].astype(np.int64) ** 2).sum()) for d in dims)), dtype=np.complex128) if factors else None
-    check(_lib.lib().aqc_mps_ent_schmidt(handles, len(lanes), _ENT_METHODS[method], kmax, dptr(s), iptr(sweeps), iptr(status),
-                                         None if fac is None else dptr(fac)))
+    with lanes:
+        check(_lib.lib().aqc_mps_ent_schmidt(lanes.handles(), count, code, kmax, dptr(s), iptr(sweeps), iptr(status), None if fac is None else dptr(fac)))
     hit = np.argwhere(status == _ENT_SWEEP_LIMIT)
     if hit.size:
         raise RuntimeError(f"state {int(hit[0, 0])}, cut {int(hit[0, 1]) + 1}: the SVD of the cut reached its sweep limit")
@@ -442,38 +334,33 @@ def schmidt_values(states, *, method: Optional[str] = None, details: bool = Fals
     clone and reads the bond vectors, where values below 1e-14 of the largest come back as 0.  A state that is not finite gives NaN
     rows and raises nothing; a cut whose SVD reaches its sweep limit raises ``RuntimeError``.  A state's values do not depend on which
     other states are in the call.  ``details``: ``(values, {"sweeps", "status", "route"})``."""
-    _ent_method(method)
-    _shape_of(states)
-    with _Lanes(states) as lanes:
-        n = lanes.lanes[0].num_qubits
-        s, sweeps, status, routes, _ = _schmidt_call(lanes.lanes, method)
-        cut = slice(0, n - 1)
-        s, sweeps, status = s[:, cut], sweeps[:, cut], status[:, cut]
-        if lanes.single:
-            s, sweeps, status, routes = s[0], sweeps[0], status[0], routes[0]
-        return (s, {"sweeps": sweeps, "status": status, "route": routes}) if details else s
+    lanes = _Lanes(states)
+    s, sweeps, status, routes, _ = _schmidt_call(lanes, method)
+    cut = slice(0, lanes.n - 1)
+    s, sweeps, status = s[:, cut], sweeps[:, cut], status[:, cut]
+    if lanes.single:
+        s, sweeps, status, routes = s[0], sweeps[0], status[0], routes[0]
+    return (s, {"sweeps": sweeps, "status": status, "route": routes}) if details else s
 
 
 def schmidt_factors(state):
     """``(values, C, D)`` of one state on the fused route: lists of the left factors C_q and the right factors D_q of the bonds
     q = 1 .. n - 1 (chi_q x chi_q, upper triangular): C_q^H C_q is the left environment of bond q, D_q^H D_q the conjugate of the right
     one, and the values of cut q are the singular values of C_q D_q^T."""
-    single, _, _ = _shape_of(state)
-    if not single:
+    lanes = _Lanes(state)
+    if not lanes.single:
         raise ValueError("expects one state")
-    with _Lanes(state) as lanes:
-        m = lanes.lanes[0]
-        n, d = m.num_qubits, m.bond_dims
-        s, _, _, _, fac = _schmidt_call(lanes.lanes, "fused", factors=True)
-        block = int((d[1:n].astype(np.int64) ** 2).sum())
-        out = []
-        for base in (0, block):
-            at, mats = base, []
-            for q in range(1, n):
-                mats.append(fac[at:at + int(d[q]) ** 2].reshape(int(d[q]), int(d[q])).copy())
-                at += int(d[q]) ** 2
-            out.append(mats)
-        return s[0, :n - 1], out[0], out[1]
+    n, d = lanes.n, lanes.dims[0]
+    s, _, _, _, fac = _schmidt_call(lanes, "fused", factors=True)
+    block = int((d[1:n].astype(np.int64) ** 2).sum())
+    out = []
+    for base in (0, block):
+        at, mats = base, []
+        for q in range(1, n):
+            mats.append(fac[at:at + int(d[q]) ** 2].reshape(int(d[q]), int(d[q])).copy())
+            at += int(d[q]) ** 2
+        out.append(mats)
+    return s[0, :n - 1], out[0], out[1]
 
 
 def entropies_of(values, alpha: float = 1.0) -> np.ndarray:
@@ -514,16 +401,11 @@ def rank_rule(values, trunc_thr: float = 0.0, max_bond: int = 0):
 def bond_dims_needed(states, trunc_thr: float = 0.0, max_bond: int = 0, *, method: Optional[str] = None):
     """``(ranks, dropped)`` per cut: the bond dimension the engine's rank rule keeps of each cut's spectrum at ``trunc_thr`` /
     ``max_bond`` and the weight it drops: int ``(n - 1,)`` and float64 ``(n - 1,)``, with a leading lanes axis for a list."""
-    trunc_thr = _finite(trunc_thr, "trunc_thr")
-    if trunc_thr < 0.0 or int(max_bond) < 0:
-        raise ValueError("trunc_thr and max_bond must be non-negative")
-    _ent_method(method)
-    single, _, _ = _shape_of(states)
-    with _Lanes(states) as lanes:
-        dims = [m.bond_dims for m in lanes.lanes]
-        s = schmidt_values(lanes.lanes, method=method)
+    trunc_thr, max_bond = _truncation(_finite(trunc_thr, "trunc_thr"), max_bond)
+    lanes = _Lanes(states)
+    s = _schmidt_call(lanes, method)[0][:, :lanes.n - 1]
     ranks, dropped = np.zeros(s.shape[:2], dtype=np.int64), np.zeros(s.shape[:2], dtype=np.float64)
     for lane in range(s.shape[0]):
         for cut in range(s.shape[1]):
-            ranks[lane, cut], dropped[lane, cut] = rank_rule(s[lane, cut, :int(dims[lane][cut + 1])], trunc_thr, max_bond)
-    return (ranks[0], dropped[0]) if single else (ranks, dropped)
+            ranks[lane, cut], dropped[lane, cut] = rank_rule(s[lane, cut, :int(lanes.dims[lane][cut + 1])], trunc_thr, max_bond)
+    return (ranks[0], dropped[0]) if lanes.single else (ranks, dropped)

@@ -24,12 +24,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, dptr, iptr
-from .mps_observables import _Lanes
+from .mps_engine import _BOND_DIMS_OF_A_STATE, _Lanes, _method_code, _route_of, _within_fused_cap
 
 FUSED_CAP = 64       # AQC_MPS_SAMPLE_FUSED_CAP of include/aqc_hip.h
 SAMPLE_STREAM = 16   # AQC_SAMPLE_STREAM
 MAX_SHOTS = 1 << 24
 _METHODS = {None: 0, "fused": 1, "gemm": 2}   # AQC_MPS_SAMPLE_*
+_ROUTES = {1: "fused", 2: "gemm"}
 
 
 def _u8ptr(arr: np.ndarray):
@@ -39,21 +40,13 @@ def _u8ptr(arr: np.ndarray):
 def route(bond_dims) -> str:
     """The route the rule picks for a state with these n + 1 bond dimensions: ``"fused"`` or ``"gemm"``."""
     d = np.ascontiguousarray(bond_dims, dtype=np.int32)
-    r = _lib.lib().aqc_mps_sample_route(d.size - 1, iptr(d)) if d.ndim == 1 else -1
-    if r not in (1, 2):
-        raise ValueError("expects the n + 1 bond dimensions of a state")
-    return "fused" if r == 1 else "gemm"
+    return _route_of("aqc_mps_sample_route", _ROUTES, _BOND_DIMS_OF_A_STATE, (d.size - 1, iptr(d)) if d.ndim == 1 else None)
 
 
 def _count(value, name: str, low: int, high: int) -> int:
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not low <= int(value) <= high:
         raise ValueError(f"{name} must be an integer in [{low}, {high}]")
     return int(value)
-
-
-def _check_method(method) -> None:
-    if method not in _METHODS:
-        raise ValueError(f"method must be None, 'fused' or 'gemm', not {method!r}")
 
 
 def sample(states, shots: int, *, seed: int, first_shot: int = 0, method: Optional[str] = None, details: bool = False):
@@ -63,16 +56,16 @@ def sample(states, shots: int, *, seed: int, first_shot: int = 0, method: Option
     shots = _count(shots, "shots", 1, MAX_SHOTS)
     seed = _count(seed, "seed", 0, 2 ** 64 - 1)
     first_shot = _count(first_shot, "first_shot", 0, 2 ** 64 - 1 - MAX_SHOTS)
-    _check_method(method)
-    with _Lanes(states) as lanes:
-        lanes.check_fused_cap(method, FUSED_CAP)
-        count, n = len(lanes.lanes), lanes.lanes[0].num_qubits
-        bits = np.empty((count, shots, n), dtype=np.uint8)
-        amps = np.empty((count, shots), dtype=np.complex128) if details else None
-        norm2 = np.empty(count, dtype=np.float64) if details else None
-        check(_lib.lib().aqc_mps_sample(lanes.handles(), count, shots, first_shot, seed, _METHODS[method], _u8ptr(bits), dptr(amps) if details else None,
+    code = _method_code(method, _METHODS)
+    lanes = _Lanes(states)
+    _within_fused_cap(method, lanes.dims, FUSED_CAP)
+    count, single = len(lanes.items), lanes.single
+    bits = np.empty((count, shots, lanes.n), dtype=np.uint8)
+    amps = np.empty((count, shots), dtype=np.complex128) if details else None
+    norm2 = np.empty(count, dtype=np.float64) if details else None
+    with lanes:
+        check(_lib.lib().aqc_mps_sample(lanes.handles(), count, shots, first_shot, seed, code, _u8ptr(bits), dptr(amps) if details else None,
                                         dptr(norm2) if details else None))
-        single = lanes.single
     if not details:
         return bits[0] if single else bits
     prob = (amps.real ** 2 + amps.imag ** 2) / norm2[:, None]
@@ -91,15 +84,15 @@ def amplitudes(states, bits, *, method: Optional[str] = None) -> np.ndarray:
     if arr.size and (arr.min() < 0 or arr.max() > 1):
         raise ValueError("a bit is 0 or 1")
     arr = np.ascontiguousarray(arr, dtype=np.uint8)
-    _check_method(method)
-    with _Lanes(states) as lanes:
-        lanes.check_fused_cap(method, FUSED_CAP)
-        count, n = len(lanes.lanes), lanes.lanes[0].num_qubits
-        if arr.shape[1] != n:
-            raise ValueError(f"the bit strings have {arr.shape[1]} bits, the states {n} qubits")
-        out = np.empty((count, arr.shape[0]), dtype=np.complex128)
-        check(_lib.lib().aqc_mps_amplitudes(lanes.handles(), count, arr.shape[0], _u8ptr(arr), _METHODS[method], dptr(out)))
-        return out[0] if lanes.single else out
+    code = _method_code(method, _METHODS)
+    lanes = _Lanes(states)
+    _within_fused_cap(method, lanes.dims, FUSED_CAP)
+    if arr.shape[1] != lanes.n:
+        raise ValueError(f"the bit strings have {arr.shape[1]} bits, the states {lanes.n} qubits")
+    out = np.empty((len(lanes.items), arr.shape[0]), dtype=np.complex128)
+    with lanes:
+        check(_lib.lib().aqc_mps_amplitudes(lanes.handles(), len(lanes.lanes), arr.shape[0], _u8ptr(arr), code, dptr(out)))
+    return out[0] if lanes.single else out
 
 
 def counts(bits):
