@@ -105,6 +105,11 @@ SIGNATURES = {
     "aqc_mps_opsum_svd_budget": (c_int64, [c_int64]),
     "aqc_mps_opsum": (c_int, [POINTER(_P), c_int, c_int, POINTER(c_int32), POINTER(c_int64), _D, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), _D,
                               c_double, c_int, c_int, POINTER(_P), POINTER(c_int32), _D, POINTER(c_int32), POINTER(c_int32)]),
+    "aqc_mps_melem_route": (c_int, [c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "aqc_mps_melem_entries": (c_int, [c_int, c_int, _D, POINTER(c_int32), POINTER(c_int32)]),
+    "aqc_mps_melem_budget": (c_int64, [c_int64]),
+    "aqc_mps_melem": (c_int, [POINTER(_P), c_int, c_int, POINTER(c_int32), POINTER(c_int64), _D, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                              c_int, _D]),
     "aqc_mps_from_vec_route": (c_int, [c_int, c_int]),
     "aqc_mps_from_vec_budget": (c_int64, [c_int64]),
     "aqc_mps_from_vec": (c_int, [c_int, c_int, c_int, _D, c_double, c_int, c_int, POINTER(_P), POINTER(c_int32), _D, POINTER(c_int32), POINTER(c_int32),

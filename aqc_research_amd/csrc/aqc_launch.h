@@ -438,6 +438,39 @@ hipError_t launch_mps_pauli_dress(const double2* const* sites, const int* dims, 
 // out[idx[k]] = sum_uv M_k[u][v] R_k[v][u] over chi x chi, one workgroup per job k (m_tab, r_tab: `count` device pointers each)
 hipError_t launch_mps_pauli_close(const void* const* m_tab, const void* const* r_tab, const int* idx, int count, int chi, void* out, hipStream_t s);
 
+// aqc_mps_melem.hip (matrix elements of operators between MPS states; rules: aqc_mps_melem_rule.h)
+struct MpsMelemEntry;
+struct MpsMelemOp {                // one operator of a call (the identity is one of them), its sites as the lists of the rule header
+    const int* dims;               // [n + 1]
+    const int* ent_off;            // [n + 1] the entries of site q: ent[ent_off[q] .. ent_off[q + 1]), in the order a, s', b, s
+    const MpsMelemEntry* ent;
+    const int* slot_off;           // site q: 2 D_{q+1} + 1 offsets into ent_by_slot from slot_off[2 mask_off[q] + q] on (slot 2 b + s)
+    const MpsMelemEntry* ent_by_slot;   // the same entries, those of a slot together, in the order of the list
+    const int* mask_off;           // [n + 1] the masks of site q: mask[mask_off[q] + b], bit s: G_{b,s} exists
+    const int* mask;
+};
+struct MpsMelemJob {
+    const double2* const* bra_sites;   // [n] site tensors [2][dims[q]][dims[q+1]]
+    const int* bra_dims;               // [n + 1]
+    const double2* const* ket_sites;
+    const int* ket_dims;
+    const MpsMelemOp* op;
+    int out;                           // index of the job's value in the call's output
+};
+struct MpsMelemFusedArgs {
+    int n;
+    const MpsMelemJob* jobs;       // [grid]
+    double2* scratch;              // [grid][job_elems]: E | E' | G, the E sets e_elems each
+    size_t e_elems, job_elems;
+    double2* out;
+};
+hipError_t launch_mps_melem_fused(const MpsMelemFusedArgs& a, int njobs, hipStream_t s);   // grid (jobs)
+// gemm route, one site of a group of jobs that share bonds and operator: G_{b,s} = its entries' w F_{a,s'} in the order of the list
+// (F, G: slots 2 a + s' / 2 b + s of x * v elements at f, g + job * stride); E'[b] = 0 (u * v elements at e_next + job * stride) for
+// every b without a G
+hipError_t launch_mps_melem_combine(const MpsMelemOp* op, int q, const double2* f, double2* g, double2* e_next, size_t stride, int x, int u, int v,
+                                    int slots, int njobs, hipStream_t s);
+
 // aqc_mps_ent.hip (Schmidt spectra of MPS states, fused route; rules: aqc_mps_ent_rule.h)
 struct MpsEntState {               // one distinct state of a call
     const double2* const* sites;   // [n] site tensors [2][dims[q]][dims[q+1]]

@@ -1,8 +1,8 @@
 // Products of complex matrices held as split re / im planes in LDS, on v_mfma_f64_16x16x4_f64: what the fused walks of
-// aqc_mps_obs.hip (pair density matrices), aqc_mps_sample.hip (measurement) and aqc_mps_pauli.hip (Pauli strings) and the sweeps of
+// aqc_mps_obs.hip (pair density matrices), aqc_mps_sample.hip (measurement), aqc_mps_pauli.hip (Pauli strings) and aqc_mps_melem.hip (operator matrix elements) and the sweeps of
 // aqc_mps_ent.hip, aqc_mps_compress.hip, aqc_mps_layers.hip, aqc_mps_fromvec.hip and aqc_mps_tovec.hip are made of: the products, the
-// moves between memory, planes and accumulators (planes_zero, plane_load, acc_store, acc_to_mem), the workgroup's sums, and -- host side,
-// at the end -- grant_dynamic_lds, the one way these eight files ask for the planes' dynamic LDS.  The truncating cut that follows an SVD of
+// moves between memory, planes and accumulators (planes_zero, plane_load, plane_fill, acc_store, acc_to_mem, acc_axpy), the workgroup's sums, and -- host side,
+// at the end -- grant_dynamic_lds, the one way these nine files ask for the planes' dynamic LDS.  The truncating cut that follows an SVD of
 // such a sweep is in aqc_mps_cut.h.  Device code but for the grant, internal linkage.
 // A plane is [kCap][kLd] doubles; a workgroup is 4 waves, wave w owns rows [16w, 16w + 16) of a product and all four 16-column tiles.
 // Operand layout of the instruction: top of aqc_mps.hip.  Operand tiles are zero-filled beyond the given dimensions, so accumulators
@@ -105,6 +105,17 @@ __device__ __forceinline__ void plane_load(const cplx* __restrict__ src, int row
         pi[i * kLd + c] = x.y;
     }
 }
+// the same with the tiles made whole: a packed rows x cols matrix into the planes (pr, pi), zeros up to rows_to x cols_to (<= kCap
+// each), which are the whole tiles that the next product reads; the caller synchronises
+__device__ __forceinline__ void plane_fill(const cplx* src, int rows, int cols, int rows_to, int cols_to, double* pr, double* pi) {
+    for (int e = threadIdx.x; e < rows_to * cols_to; e += 256) {
+        const int i = e / cols_to, c = e - i * cols_to;
+        cplx x = make_double2(0.0, 0.0);
+        if (i < rows && c < cols) x = src[(size_t)i * cols + c];
+        pr[i * kLd + c] = x.x;
+        pi[i * kLd + c] = x.y;
+    }
+}
 // the wave's part of acc, rows below m and columns below nn, times f (1: exact) into dst with leading dimension ld
 __device__ __forceinline__ void acc_to_mem(const Acc& acc, cplx* __restrict__ dst, int ld, int m, int nn, double f = 1.0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
@@ -114,6 +125,28 @@ __device__ __forceinline__ void acc_to_mem(const Acc& acc, cplx* __restrict__ ds
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * wave + 4 * r + lk, j = 16 * t + li;
             if (i < m && j < nn) dst[(size_t)i * ld + j] = make_double2(f * acc.re[t][r], f * acc.im[t][r]);
+        }
+}
+
+// dst (m x nn, packed) = w acc (first) or += w acc, element (i, j) written by the thread that writes it in acc_to_mem: the same thread in
+// every product of one shape, so a read-modify-write of memory that only this mapping touches needs no atomics and no barrier
+__device__ __forceinline__ void acc_axpy(const Acc& acc, double wr, double wi, cplx* dst, int m, int nn, bool first) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = 16 * wave + 4 * r + lk, j = 16 * t + li;
+            if (i < m && j < nn) {
+                cplx* at = dst + (size_t)i * nn + j;
+                const double re = wr * acc.re[t][r] - wi * acc.im[t][r], im = wr * acc.im[t][r] + wi * acc.re[t][r];
+                if (first) {
+                    *at = make_double2(re, im);
+                } else {
+                    const cplx old = *at;
+                    *at = make_double2(old.x + re, old.y + im);
+                }
+            }
         }
 }
 

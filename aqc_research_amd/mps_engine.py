@@ -246,6 +246,17 @@ class DeviceMPS:
 
         return overlaps([self], kets, method=method)[0]
 
+    def operator_elements(self, op, bras=None, *, method=None):
+        """<self|O|self> for an ``MPO`` (``None``: the identity), or with ``bras`` (a list) the ``(len(bras),)`` values <bra|O|self>:
+        ``mps_observables.operator_elements`` with this state as the ket."""
+        from .mps_observables import operator_elements
+
+        if bras is None:
+            return operator_elements([(self, op, self)], method=method)[0]
+        if not isinstance(bras, list):
+            raise ValueError("bras is a list of states")
+        return operator_elements([(b, op, self) for b in bras], method=method)
+
     def schmidt_values(self, *, method=None, details: bool = False):
         """The singular values of every cut, ``(n - 1, K)``: ``mps_observables.schmidt_values`` of this state (which it leaves as it is)."""
         from .mps_observables import schmidt_values
@@ -618,6 +629,20 @@ class MPO:
             acc = np.einsum("rca,abst->srtcb", acc, w).reshape(2 * r, 2 * c, w.shape[1])   # bit q is the major one so far
         return np.ascontiguousarray(acc[:, :, 0])
 
+    def adjoint(self) -> "MPO":
+        """O^H: every site with s_out and s_in swapped and conjugated; the bonds stay.  Exact."""
+        return MPO([w.transpose(0, 1, 3, 2).conj() for w in self._sites])
+
+    def times(self, other: "MPO") -> "MPO":
+        """self . other (``other`` acts first) as an MPO with bonds D_self D_other, self's index the major one:
+        W[(a2, a1)][(b2, b1)][s][s'] = sum_t W_self[a2][b2][s][t] W_other[a1][b1][t][s'].  Nothing is compressed."""
+        if not isinstance(other, MPO):
+            raise ValueError("an operator is an MPO")
+        if other.num_qubits != self.num_qubits:
+            raise ValueError(f"an operator on {self.num_qubits} qubits meets one on {other.num_qubits}")
+        return MPO([np.einsum("abst,cdtu->acbdsu", w2, w1).reshape(w2.shape[0] * w1.shape[0], w2.shape[1] * w1.shape[1], 2, 2)
+                    for w2, w1 in zip(self._sites, other._sites)])
+
     @classmethod
     def product_operator(cls, matrices) -> "MPO":
         """M_0 on qubit 0 (x) M_1 on qubit 1 ...: bond dimension 1 (projectors, local rotations)."""
@@ -699,6 +724,19 @@ def _op_dims(op):
     return op.bond_dims
 
 
+def _packed_ops(ops, n: int):
+    """``(op_dims (K, n + 1) int32, op_off (K, n + 1) int64, op_data complex128)``: the operators of a call in the packed layout of
+    aqc_mps_opsum (site q of operator k at element ``op_off[k][q]``)."""
+    op_dims = np.ascontiguousarray([op.bond_dims for op in ops], dtype=np.int32).reshape(len(ops), n + 1)
+    sizes = np.array([[w.size for w in op.sites] for op in ops], dtype=np.int64).reshape(len(ops), n)
+    op_off = np.zeros((len(ops), n + 1), dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(sizes.sum(axis=1))]) if len(ops) else np.zeros(1, dtype=np.int64)
+    for k in range(len(ops)):
+        op_off[k] = starts[k] + np.concatenate([[0], np.cumsum(sizes[k])])
+    op_data = np.ascontiguousarray(np.concatenate([w.ravel() for op in ops for w in op.sites])) if ops else np.zeros(1, dtype=np.complex128)
+    return op_dims, op_off, op_data
+
+
 def opsum_route(bond_dims_of_states, bond_dims_of_ops) -> str:
     """The route ``operator_sums`` picks for an output whose terms have states and operators of these bond dimensions (K rows of n + 1
     each; ``None`` in place of an operator's row: no operator): ``"fused"`` when every summed product bond sum_t D^t_q chi^t_q is at most
@@ -777,13 +815,7 @@ def operator_sums(outputs, trunc_thr: float = 0.0, max_bond: int = 0, *, method:
         routes.append(method or route)
     term_off, term_state, term_op = (np.array(a, dtype=np.int32) for a in (term_off, term_state, term_op))
     cf = np.ascontiguousarray(cf, dtype=np.complex128)
-    op_dims = np.ascontiguousarray([op.bond_dims for op in ops], dtype=np.int32).reshape(len(ops), n + 1)
-    sizes = np.array([[w.size for w in op.sites] for op in ops], dtype=np.int64).reshape(len(ops), n)
-    op_off = np.zeros((len(ops), n + 1), dtype=np.int64)
-    starts = np.concatenate([[0], np.cumsum(sizes.sum(axis=1))]) if len(ops) else np.zeros(1, dtype=np.int64)
-    for k in range(len(ops)):
-        op_off[k] = starts[k] + np.concatenate([[0], np.cumsum(sizes[k])])
-    op_data = np.ascontiguousarray(np.concatenate([w.ravel() for op in ops for w in op.sites])) if ops else np.zeros(1, dtype=np.complex128)
+    op_dims, op_off, op_data = _packed_ops(ops, n)
     count = len(outputs)
     out = (c_void_p * count)()
     ranks, sweeps = np.zeros((count, max(n - 1, 0)), dtype=np.int32), np.zeros((count, max(n - 1, 0)), dtype=np.int32)

@@ -23,19 +23,25 @@ Operators on more than two sites, and anything between two different states, are
 csrc/aqc_mps_pauli.hip, rules: csrc/aqc_mps_pauli_rule.h): ``pauli_strings`` gives <phi|P|psi> for many strings and pairs of states in
 one call, ``overlaps`` the matrix <phi_a|psi_b>, ``energy`` a weighted sum of expectation values.
 
+General operators (``mps_engine.MPO``) between states are a walk that carries the operator's bond (aqc_mps_melem; kernels:
+csrc/aqc_mps_melem.hip, rules: csrc/aqc_mps_melem_rule.h): ``operator_elements`` gives <phi|O|psi> for many (bra, operator, ket) jobs in
+one call without forming O psi, ``operator_matrix`` an operator in a basis of states, ``expectations`` and ``variance_by_walk`` what
+their names say.
+
 Entanglement across the cuts of the chain (aqc_mps_ent_schmidt; kernels: csrc/aqc_mps_ent.hip, rules: csrc/aqc_mps_ent_rule.h):
 ``schmidt_values`` gives the singular values of every cut of one or many states per call, ``entanglement_entropies`` their entropies
 (``entropies_of``: NumPy), ``bond_dims_needed`` the bond dimensions the engine's rank rule would keep at a given ``trunc_thr`` /
 ``max_bond``.
 """
-from ctypes import POINTER, c_uint8
+from ctypes import POINTER, c_int64, c_uint8
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, dptr, iptr
-from .mps_engine import MPO, _BOND_DIMS_OF_A_STATE, _handles, _Lanes, _method_code, _route_of, _truncation, _within_fused_cap, apply_operator
+from .mps_engine import (MPO, _BOND_DIMS_OF_A_STATE, _call_states, _handles, _Lanes, _method_code, _packed_ops, _route_of, _truncation,
+                         _within_fused_cap, apply_operator)
 from .observables import (_bond_energies_of, _bond_pairs, _correlation_letters, _correlation_of, _correlation_pairs, _magnetisation_of,
                           _magnetisation_pairs, _single_axis, pauli_expectation, pauli_matrix)  # noqa: F401  (the last two: for callers)
 from .xxz import _finite
@@ -287,6 +293,111 @@ def variance(states, op, *, method: Optional[str] = None) -> np.ndarray:
                 m.close()
     out = g[2].real / g[0].real - np.abs(g[1] / g[0].real) ** 2
     return out[0] if kets.single else out
+
+
+# ---- matrix elements of operators: <phi|O|psi> for many (bra, operator, ket) jobs per call, by a walk that carries the operator's bond
+# (aqc_mps_melem; rules: csrc/aqc_mps_melem_rule.h, kernels: csrc/aqc_mps_melem.hip)
+
+MELEM_OP_CAP = 32                                   # AQC_MPS_MELEM_OP_CAP
+_MELEM_METHODS = {None: 0, "fused": 1, "gemm": 2}   # AQC_MPS_MELEM_*
+
+
+def melem_route(bra_dims, ket_dims, op_dims) -> str:
+    """The route the rule picks for a job with these n + 1 bond dimensions each (``bra_dims`` None: the ket's, ``op_dims`` None: the
+    identity): ``"fused"`` when every bond of bra and ket is at most ``FUSED_CAP`` and every operator bond at most ``MELEM_OP_CAP``, else
+    ``"gemm"``."""
+    k = np.ascontiguousarray(ket_dims, dtype=np.int32)
+    b = None if bra_dims is None else np.ascontiguousarray(bra_dims, dtype=np.int32)
+    o = None if op_dims is None else np.ascontiguousarray(op_dims, dtype=np.int32)
+    fits = k.ndim == 1 and k.size >= 2 and (b is None or b.shape == k.shape) and (o is None or o.shape == k.shape)
+    return _route_of("aqc_mps_melem_route", _ROUTES, "expects the n + 1 bond dimensions of the bra, of the ket and of the operator",
+                     (k.size - 1, None if b is None else iptr(b), iptr(k), None if o is None else iptr(o)) if fits else None)
+
+
+def operator_elements(jobs, *, method: Optional[str] = None) -> np.ndarray:
+    """<phi|O|psi> for every job of ``jobs = [(bra, op_or_None, ket), ...]``: ``(J,)`` complex128, nothing normalised.  ``op`` is an
+    ``mps_engine.MPO`` (``None``: the identity, the overlap), bra and ket a DeviceMPS or a QiskitMPS tuple of the operator's qubit
+    count, any gauge.  States and operators that are the same object are uploaded once.  O psi is never formed: there is no SVD, no
+    truncation and no intermediate state, and the cost of a job is 2 (D_q + D_{q+1}) matrix products per site for an operator whose
+    sites are as sparse as those of ``MPO.xxz``.  Errors are of the size of rounding relative to ``|phi| |O|_2 |psi|``.
+
+    ``method``: ``None`` lets the rule choose per job (``melem_route``).  A job's value does not depend on which other jobs are in the
+    call; non-finite entries are data and spoil their own jobs only."""
+    code = _method_code(method, _MELEM_METHODS)
+    if not isinstance(jobs, list) or not jobs or any(not (isinstance(j, tuple) and len(j) == 3) for j in jobs):
+        raise ValueError("jobs is a non-empty list of (bra, op_or_None, ket)")
+    states, ops, state_at, op_at, n = [], [], {}, {}, None
+    job_bra, job_op, job_ket = [], [], []
+    for j, (bra, op, ket) in enumerate(jobs):
+        if op is not None and not isinstance(op, MPO):
+            raise ValueError(f"job {j}: an operator is an MPO or None")
+        dims = []
+        for state in (bra, ket):
+            d = _call_states([state])[3][0]   # (a job takes one state each side: a list in its place is refused as no state)
+            n = d.size - 1 if n is None else n
+            if d.size - 1 != n:
+                raise ValueError("the states differ in the number of qubits")
+            dims.append(d)
+        if op is not None and op.num_qubits != n:
+            raise ValueError(f"job {j}: an operator on {op.num_qubits} qubits meets a state of {n}")
+        if method == "fused" and melem_route(dims[0], dims[1], None if op is None else op.bond_dims) != "fused":
+            raise ValueError(f"the fused route takes bond dimensions up to {FUSED_CAP} and operator bond dimensions up to {MELEM_OP_CAP} (job {j})")
+        for state, column in ((bra, job_bra), (ket, job_ket)):
+            if id(state) not in state_at:
+                state_at[id(state)] = len(states)
+                states.append(state)
+            column.append(state_at[id(state)])
+        if op is not None and id(op) not in op_at:
+            op_at[id(op)] = len(ops)
+            ops.append(op)
+        job_op.append(-1 if op is None else op_at[id(op)])
+    job_bra, job_op, job_ket = (np.array(a, dtype=np.int32) for a in (job_bra, job_op, job_ket))
+    op_dims, op_off, op_data = _packed_ops(ops, n)
+    out = np.empty(len(jobs), dtype=np.complex128)
+    with _Lanes(states) as lanes:
+        check(_lib.lib().aqc_mps_melem(lanes.handles(), len(lanes.lanes), len(ops), iptr(op_dims) if ops else None,
+                                       op_off.ctypes.data_as(POINTER(c_int64)) if ops else None, dptr(op_data) if ops else None, len(jobs),
+                                       iptr(job_bra), iptr(job_op), iptr(job_ket), code, dptr(out)))
+    return out
+
+
+def _state_list(states, what: str):
+    if not isinstance(states, list) or not states:
+        raise ValueError(f"{what} is a non-empty list of states")
+    return states
+
+
+def operator_matrix(op, kets, bras=None, *, method: Optional[str] = None) -> np.ndarray:
+    """The ``(len(bras), len(kets))`` matrix <phi_a|O|psi_b> in one call (``bras`` None: the kets): a Hamiltonian in a basis of MPS
+    states, or with ``op`` None their Gram matrix."""
+    kets = _state_list(kets, "kets")
+    bras = kets if bras is None else _state_list(bras, "bras")
+    return operator_elements([(b, op, k) for b in bras for k in kets], method=method).reshape(len(bras), len(kets))
+
+
+def expectations(states, ops, *, method: Optional[str] = None) -> np.ndarray:
+    """<psi|O_k|psi> for every state and every operator of the list ``ops`` in one call: ``(nops,)`` complex128 for one state,
+    ``(lanes, nops)`` for a list; not divided by <psi|psi>."""
+    if not isinstance(ops, (list, tuple)) or not ops:
+        raise ValueError("ops is a non-empty list of operators")
+    single, items, _, _ = _call_states(states)
+    out = operator_elements([(s, o, s) for s in items for o in ops], method=method).reshape(len(items), len(ops))
+    return out[0] if single else out
+
+
+def variance_by_walk(states, op, *, method: Optional[str] = None) -> np.ndarray:
+    """<psi|O^H O|psi> / <psi|psi> - |<psi|O|psi> / <psi|psi>|^2 as ``variance`` gives it, from ONE ``operator_elements`` call with three
+    jobs per state (the identity, O, and ``op.adjoint().times(op)`` with bonds D^2): O psi is never formed, so nothing is compressed and
+    a state that O annihilates simply has variance 0.  ``()`` for one state, ``(lanes,)`` for a list."""
+    if not isinstance(op, MPO):
+        raise ValueError("an operator is an MPO")
+    single, items, n, _ = _call_states(states)
+    if op.num_qubits != n:
+        raise ValueError(f"an operator on {op.num_qubits} qubits meets a state of {n}")
+    square = op.adjoint().times(op)
+    g = operator_elements([(s, o, s) for s in items for o in (None, op, square)], method=method).reshape(len(items), 3)
+    out = g[:, 2].real / g[:, 0].real - np.abs(g[:, 1] / g[:, 0].real) ** 2
+    return out[0] if single else out
 
 
 # ---- entanglement: the Schmidt spectra of every cut (aqc_mps_ent_schmidt; rules: csrc/aqc_mps_ent_rule.h, kernels: csrc/aqc_mps_ent.hip)

@@ -448,6 +448,38 @@ int aqc_mps_opsum(aqc_mps* const* states, int nstates, int nops, const int32_t* 
                   const int32_t* term_state /* [terms] */, const int32_t* term_op /* [terms], -1: none */, const double* coeffs /* [terms][2] */,
                   double trunc_thr, int max_bond, int method, aqc_mps** out /* [nout] */, int32_t* ranks /* [nout][n-1] */,
                   double* dropped /* [nout][n-1] */, int32_t* sweeps /* [nout][n-1] */, int32_t* status /* [nout] */);
+/* Matrix elements of operators between MPS states: out[j] = <phi|O|psi> for job j = (state job_bra[j], operator job_op[j] or -1: the
+ * identity, state job_ket[j]) of the call's tables, many jobs per call, without forming O psi: no SVD, no truncation, no new state
+ * (rules: csrc/aqc_mps_melem_rule.h, kernels: csrc/aqc_mps_melem.hip).  Operators are packed as aqc_mps_opsum takes them.  The walk
+ * E_0 = [1], E_{q+1}[b] = sum_a sum_{s,s'} W_q[a][b][s][s'] B_q[s]^H E_q[a] T_q[s'] carries the operator's bond: D_q matrices of
+ * beta_q x chi_q; out[j] = E_n[0][0][0], not normalised.  Entries of W_q that are exactly zero are skipped, and with them the products
+ * that only they would read: a site of an XXZ Hamiltonian costs 20 matrix products, not 100.  States and operators are left bit for bit
+ * as they are; a state or an operator listed in many jobs is read once.  Errors are of the size of rounding relative to
+ * scale = |phi| |O|_2 |psi|.  A job's value does not depend on which other jobs are in the call, and non-finite inputs are data: their
+ * jobs return what the arithmetic gives.
+ * melem_route: host only.  AQC_MPS_MELEM_FUSED (one workgroup walks a whole chain inside one launch) when every bond of bra and ket is at
+ *   most AQC_MPS_MELEM_FUSED_CAP and every operator bond at most AQC_MPS_MELEM_OP_CAP, else AQC_MPS_MELEM_GEMM (-1: invalid argument).
+ * melem_entries: host only.  The entries of one operator site that the walk does not skip, in the order of the rule (a, s', b, s), with
+ *   the mark of the first entry of every G_{b,s}, and per b the mask of the G_{b,s} that exist; returns their number (-1: invalid argument).
+ * melem_budget: the bytes of scratch that the jobs of one group may take together; bytes > 0 sets it, else the default comes back; returns
+ *   the value before.  Results do not depend on it.
+ * melem: method AQC_MPS_MELEM_BY_RULE (per job), _FUSED (an error that names the job when a bond exceeds a cap) or _GEMM.  nops may be 0
+ *   (then the op_* arrays may be null).  Argument errors (null pointers, states that differ in size or device, a job that names a state
+ *   or an operator outside the call, operator dims that are not those of an operator on n qubits or offsets that are not their packed
+ *   layout, an unknown method, the fused route beyond a cap) are reported before any device work. */
+#define AQC_MPS_MELEM_BY_RULE 0
+#define AQC_MPS_MELEM_FUSED 1
+#define AQC_MPS_MELEM_GEMM 2
+#define AQC_MPS_MELEM_FUSED_CAP 64
+#define AQC_MPS_MELEM_OP_CAP 32
+int aqc_mps_melem_route(int n, const int32_t* bra_dims /* [n+1], null: the ket's */, const int32_t* ket_dims /* [n+1] */,
+                        const int32_t* op_dims /* [n+1], null: the identity */);
+int aqc_mps_melem_entries(int dl, int dr, const double* w /* [dl][dr][2][2] c128, null: the identity site */,
+                          int32_t* out /* [4 dl dr][5]: a, s', b, s, first */, int32_t* mask /* [dr] */);
+int64_t aqc_mps_melem_budget(int64_t bytes);
+int aqc_mps_melem(aqc_mps* const* states, int nstates, int nops, const int32_t* op_dims /* [nops][n+1] */, const int64_t* op_site_off /* [nops][n+1] */,
+                  const double* op_data /* complex elements (re, im) */, int njobs, const int32_t* job_bra /* [njobs] */,
+                  const int32_t* job_op /* [njobs], -1: the identity */, const int32_t* job_ket /* [njobs] */, int method, double* out /* [njobs] c128 */);
 /* Dense vectors into MPS states: one or many vectors of 2^n c128 amplitudes (index bit q is site q, any norm, left as they are) per call
  * (rules: csrc/aqc_mps_fromvec_rule.h, kernels: csrc/aqc_mps_fromvec.hip).  out[i] is a NEW state (the caller destroys it) in the engine's
  * gauge, as aqc_mps_compress returns it: every bond cut left to right by the engine's rank rule at trunc_thr / max_bond
